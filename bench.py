@@ -12,12 +12,16 @@ includes the trainer's per-step coordinate shift, SparseTensor construction (coo
 maps), forward, cross-entropy over 200 classes, backward, RCCL gradient all-reduce (N>1) and the SGD update.
 Scenes shard over ranks with no data-path collective ("weak" scaling: per-GPU work fixed).
 
-Rank 0 prints ONE JSON line; besides the driver's contract it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times exactly --steps steps and prints the driver's
+contract (value, ms_per_step, step_ms, ...).  With --full the line also carries
   roofline     -- the dominant kernel family (k_conv_gather: sparse-conv forward/dgrad implicit GEMM),
                   algorithmic bytes of every launch of one step (SURVEY 8d byte model) / their HIP-event
                   durations, vs the 8 TB/s HBM peak; plus the whole-step B_alg fraction
   cpu_baseline -- the oracle's BLAS gather-GEMM-scatter restatement of the same model on the host cores,
                   on a bounded sample (it is a restatement of MinkowskiEngine's CPU algorithm, not ME itself)
+  secondary    -- one number per secondary measurement (single scene, call by call, balanced CE, fp32, clip,
+                  insseg, the per-rank path of N > 1), each timed in steps of its own after the headline's
+--dump-outputs DIR writes what the last timed step computed (step_outputs) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -208,14 +212,15 @@ def phase_summary(steps, origin=None):
     return out
 
 
-def train_step(model, ddp, opt, coords, feats, labels, dtype, step_idx, shift=True, ctx=None):
+def train_step(model, ddp, opt, coords, feats, labels, dtype, step_idx, shift=True, ctx=None, keep=None):
     """One training step.  The input side (the trainer's per-step coordinate shift, the feature cast and the
     SparseTensor construction = coordinate insert) runs on a separate "data" stream, like a DataLoader's copy
     stream: the engine builds all coordinate / kernel maps on the manager's own stream, so the maps of step t+1 are
     constructed while step t's backward is still running on the compute stream.
     ctx: None = cross-entropy fine-tune (configs[1]); {"kind": "clip", crit, anchors} = CLIP-contrastive pretrain
     (configs[2], pl_RepresentationTrainer.py:168-264); {"kind": "insseg", inst, centers} = instance-segmentation step
-    (configs[4], downstream/insseg/lib/pl_Trainer.py:245-321: CE + offset-L1 + direction losses)."""
+    (configs[4], downstream/insseg/lib/pl_Trainer.py:245-321: CE + offset-L1 + direction losses).
+    keep: None, or a dict that receives the network output the loss was computed from ("output", a SparseTensor)."""
     main = torch.cuda.current_stream()
     dev = coords.device
     ds = _DATA_STREAM.setdefault(dev.index, torch.cuda.Stream(device=dev))
@@ -236,11 +241,12 @@ def train_step(model, ddp, opt, coords, feats, labels, dtype, step_idx, shift=Tr
     _mark("start")
     kind = ctx["kind"] if ctx else "ce"
     if kind == "clip":
-        out = model(sinput)
+        out = net = model(sinput)
         loss, _, _ = ctx["crit"](out.F, labels, ctx["anchors"])
     elif kind == "insseg":
         from languagegroundedsemseg_amd.losses import instance_offset_losses
         off, logits, _ = model(sinput)
+        net = logits
         nl, dl = instance_offset_losses(off.F, c[:, 1:], ctx["centers"], ctx["inst"], 0.02)
         loss = fused_cross_entropy(logits.F, labels, ignore_index=-1) + nl + dl
     elif kind == "ce_balanced":
@@ -249,12 +255,16 @@ def train_step(model, ddp, opt, coords, feats, labels, dtype, step_idx, shift=Tr
         # lib/losses/utils.py:13-77); split statistics stay on the device (what the trainer's head / common / tail meters consume)
         from languagegroundedsemseg_amd.losses import sample_categories_for_balancing
         logits, _ = model(sinput)
+        net = logits
         rows = fused_cross_entropy(logits.F, labels, ignore_index=-1, reduction="none")
         loss, ctx["split_stats"], _ = sample_categories_for_balancing(rows, labels, ctx["foc"], ctx["head_ratio"], ctx["common_ratio"],
                                                                        ignore_label=-1, split="stats")
     else:
         logits, _ = model(sinput)
+        net = logits
         loss = fused_cross_entropy(logits.F, labels, ignore_index=-1)
+    if keep is not None:
+        keep["output"] = net
     _mark("forward")
     loss.backward()
     _mark("backward")       # compute stream done with backward; the weight-gradient stream may still be busy
@@ -495,13 +505,56 @@ def step_stats(ms):
     return {"median": med, "p90": v[min(n - 1, int(0.9 * n))], "min": v[0], "max": v[-1]}
 
 
-def measure(model, ddp, opt, coords, feats, labels, dtype, steps, warmup, ctx, clog, world, want_roofline, base=0, settle=15):
-    """`warmup` untimed plain steps, then -- still untimed -- up to `settle` more in rounds of five until two consecutive rounds
-    agree (`_settled`) (a fresh box pays for allocator growth, code-object loading and clock ramps in its first steps: round 5's
-    driver run had six 35 - 56 ms steps inside the timed region); then exactly `steps` timed steps bracketed by barrier +
-    synchronize on both sides.  The fully instrumented DISCOVERY step and the SAMPLING steps of the roofline run AFTER the timed
-    region: nothing before or inside it is bracketed, enqueued call by call or allocated differently from production.
-    -> dict(dt, loss, disc, step_ms, phases, warmup_ms, warmup_extra)"""
+DUMP_ROWS = 16384            # rows of the network output in the dump (at most 32 MB of them)
+DUMP_ELEMS = 1 << 20         # entries of the parameters / gradients / running statistics in the dump
+DUMP_LIMIT = 64 << 20        # bytes of all dumped arrays together
+
+
+def step_outputs(model, loss, keep, seed=0):
+    """What a caller of the timed step holds after its last step, as host arrays in float32 / float64: the loss, rows of the
+    network output (logits; the representation for clip) with their coordinates, and the model state the step left -- the
+    parameters after the SGD update, their gradients, the normalisation layers' running statistics.  The large ones are a fixed
+    sample: seeded rows / entries in ascending order, the same for every run of the same arguments."""
+    rng = np.random.default_rng(seed)
+
+    def sample(n, k):
+        return torch.from_numpy(np.sort(rng.choice(n, size=k, replace=False)) if k < n else np.arange(n))
+
+    net = keep["output"]
+    F = net.F.detach()
+    C = net.C
+    rows = sample(F.shape[0], min(DUMP_ROWS, (32 << 20) // (4 * F.shape[1])))
+    out = {"loss": np.array([float(loss.detach().float().item())], np.float64),
+           "output": F[rows.to(F.device)].float().cpu().numpy(),
+           "output_coords": C[rows.to(C.device)].cpu().numpy().astype(np.float64)}
+    params = [p for _, p in model.named_parameters()]
+    state = {"params": [p.detach() for p in params],
+             "grads": [p.grad.detach() if p.grad is not None else torch.zeros_like(p) for p in params],
+             "buffers": [b.detach() for _, b in model.named_buffers() if b.is_floating_point()]}
+    for name, ts in state.items():
+        flat = torch.cat([t.reshape(-1).float() for t in ts])
+        out[name] = flat[sample(flat.numel(), DUMP_ELEMS).to(flat.device)].cpu().numpy()
+    assert sum(a.nbytes for a in out.values()) <= DUMP_LIMIT
+    return out
+
+
+def write_outputs(outputs, path):
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log("outputs of the last timed step -> %s (%s)" % (path, ", ".join("%s %s" % (k, tuple(a.shape)) for k, a in outputs.items())))
+
+
+def measure(model, ddp, opt, coords, feats, labels, dtype, steps, warmup, ctx, clog, world, want_roofline, base=0, settle=15,
+            want_outputs=False):
+    """`warmup` untimed plain steps, then -- still untimed -- `settle` more in rounds of five (a fresh box pays for allocator
+    growth, code-object loading and clock ramps in its first steps: round 5's driver run had six 35 - 56 ms steps inside the
+    timed region).  All rounds run whatever their times, so the model has taken the same steps before the timed region in every
+    run of the same arguments; whether the last two rounds agreed (`_settled`) is reported as `warmup_settled`.  Then exactly
+    `steps` timed steps bracketed by barrier + synchronize on both sides.  The fully instrumented DISCOVERY step and the SAMPLING
+    steps of the roofline run AFTER the timed region: nothing before or inside it is bracketed, enqueued call by call or allocated
+    differently from production.  want_outputs: the last timed step's outputs (`step_outputs`), taken before anything else runs.
+    -> dict(dt, loss, disc, step_ms, phases, warmup_ms, warmup_extra, warmup_settled, outputs)"""
     disc = None
     if clog is not None:
         clog.rows, clog.mode, clog.only_key = [], None, None
@@ -517,21 +570,16 @@ def measure(model, ddp, opt, coords, feats, labels, dtype, steps, warmup, ctx, c
 
     rounds = [plain(warmup, base)] if warmup > 0 else []
     extra = 0
-    while settle > 0 and extra < settle and warmup > 0:
-        ok = _settled(rounds)
-        if world > 1:      # every rank runs the same number of steps (the steps contain collectives)
-            flag = torch.tensor([0.0 if ok else 1.0], device=coords.device)
-            dist.all_reduce(flag, op=dist.ReduceOp.MAX)
-            ok = flag.item() == 0.0
-        if ok:
-            break
+    while warmup > 0 and extra < settle:
         rounds.append(plain(SETTLE_ROUND, base + warmup + extra))
         extra += SETTLE_ROUND
+    settled = _settled(rounds)
     warm_ms = [m for r in rounds for m in r]
     if ddp.timing is not None:
         ddp.timing_summary(1)                   # drop the warm-up's collective events
     del _PHASES[:]
-    log("warmup done (%d + %d steps): %s ms" % (warmup, extra, " ".join("%.1f" % m for m in warm_ms)))
+    log("warmup done (%d + %d steps, %s): %s ms" % (warmup, extra, "settled" if settled else "NOT settled",
+                                                    " ".join("%.1f" % m for m in warm_ms)))
     first = base + warmup + extra
     if world > 1:
         dist.barrier()
@@ -539,8 +587,9 @@ def measure(model, ddp, opt, coords, feats, labels, dtype, steps, warmup, ctx, c
     t0 = time.perf_counter()
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     marks[0].record()
+    keep = {} if want_outputs else None
     for i in range(steps):
-        loss = train_step(model, ddp, opt, coords, feats, labels, dtype, first + i, ctx=ctx)
+        loss = train_step(model, ddp, opt, coords, feats, labels, dtype, first + i, ctx=ctx, keep=keep if i == steps - 1 else None)
         marks[i + 1].record()
     torch.cuda.synchronize()
     if world > 1:
@@ -548,7 +597,8 @@ def measure(model, ddp, opt, coords, feats, labels, dtype, steps, warmup, ctx, c
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     out = {"dt": dt, "loss": loss, "disc": None, "phases": phase_summary(steps, origin=(marks[0], t0)),
-           "step_ms": [marks[i].elapsed_time(marks[i + 1]) for i in range(steps)], "warmup_ms": warm_ms, "warmup_extra": extra}
+           "step_ms": [marks[i].elapsed_time(marks[i + 1]) for i in range(steps)], "warmup_ms": warm_ms, "warmup_extra": extra,
+           "warmup_settled": settled, "outputs": step_outputs(model, loss, keep) if keep is not None else None}
     if ddp.timing is not None:
         out["ddp"] = ddp.timing_summary(steps)
     if want_roofline:
@@ -863,8 +913,13 @@ def main():
     ap.add_argument("--workload", default="ce", choices=["ce", "clip"],
                     help="ce = BASELINE configs[1] (the headline metric); clip = configs[2], CLIP-contrastive pretrain step "
                          "(scripts/text_representation_train.sh: Res16UNet34D, 512-d text anchors)")
-    ap.add_argument("--settle", type=int, default=15, help="at most this many extra untimed warm-up steps (rounds of five) until two "
-                                                            "rounds agree; 0 = exactly --warmup steps (profiling runs that count steps)")
+    ap.add_argument("--settle", type=int, default=15, help="this many extra untimed warm-up steps after --warmup (rounds of five, all "
+                                                            "of them run; `warmup_settled` says whether the last two agreed); 0 = "
+                                                            "exactly --warmup steps (profiling runs that count steps)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need, in steps of their own after the "
+                                                        "timed ones: roofline, CPU baseline, single-scene line and the secondary "
+                                                        "workloads (the --no-* options below drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (step_outputs) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-single-scene", action="store_true", help="skip the secondary 1-scene-per-step measurement")
@@ -959,8 +1014,9 @@ def main():
     import gc
     gc.collect()
     gc.disable()   # no cyclic-GC pauses inside the timed region (tensors are freed by refcount as usual)
+    want_roofline = args.full and not args.no_roofline
     clog = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and want_roofline:
         clog = ConvLog()
         clog.patch()
     if args.roctx:
@@ -972,8 +1028,10 @@ def main():
         rl.mode = "roctx"
     if world > 1 or args.dp_world1:
         ddp.enable_timing()
-    res = measure(model, ddp, opt, coords, feats, labels, dtype, args.steps, args.warmup, ctx, clog, world, not args.no_roofline,
-                  settle=args.settle)
+    res = measure(model, ddp, opt, coords, feats, labels, dtype, args.steps, args.warmup, ctx, clog, world, want_roofline,
+                  settle=args.settle, want_outputs=rank == 0 and args.dump_outputs is not None)
+    if res["outputs"] is not None:
+        write_outputs(res["outputs"], args.dump_outputs)
     dt, loss = res["dt"], res["loss"]
     tmax = torch.tensor([dt], dtype=torch.float64, device=device)
     nv = torch.tensor([float(n_vox)], dtype=torch.float64, device=device)
@@ -1010,7 +1068,7 @@ def main():
         "final_loss": final_loss,
         "phases": res["phases"],
         "step_ms": dict(step_stats(res["step_ms"]), all=res["step_ms"]),
-        "warmup_ms": res["warmup_ms"], "warmup_extra": res["warmup_extra"],
+        "warmup_ms": res["warmup_ms"], "warmup_extra": res["warmup_extra"], "warmup_settled": res["warmup_settled"],
     }
     # one record per rank (also at N = 1, so that the schema of the line does not depend on N): where a step spends its time
     # (compute-stream phases, the part of the bucket all-reduces that backward did not hide, the compute-stream stalls inside
@@ -1036,9 +1094,10 @@ def main():
                                           pmc_traffic(res["disc"]["top"][0][0], args), res.get("sample_steps", 0))
         if args.workload == "clip":
             out["roofline"]["mfma"] = clip_mfma_report(out_dim=model.PLANES[7], n=n_vox, dtype=dtype, device=device)
-    log("roofline pass done")
-    secondary = rank == 0 and world == 1 and not args.no_secondary and args.workload == "ce" and args.dtype == "bf16" and not args.dp_world1
-    if rank == 0 and world == 1 and not args.no_single_scene and args.scenes != 1:
+        log("roofline pass done")
+    secondary = (args.full and rank == 0 and world == 1 and not args.no_secondary and args.workload == "ce" and args.dtype == "bf16"
+                 and not args.dp_world1)
+    if args.full and rank == 0 and world == 1 and not args.no_single_scene and args.scenes != 1:
         out["single_scene"] = single_scene_line(model, ddp, opt, dtype, device, args, ctx)
         log("single-scene line done")
     if secondary:
@@ -1088,7 +1147,7 @@ def main():
         log("insseg block done")
         out["dp_path_world1"] = dp_path_block(coords, feats, labels, device, args, dtype)
         log("dp-path block done")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(model_name=args.model, voxels=args.voxels, loss="clip" if args.workload == "clip" else "ce")
         log("cpu baseline done")
         if secondary:

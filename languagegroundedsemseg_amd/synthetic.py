@@ -17,6 +17,21 @@ def _plane(rng, origin, u, v, density):
     return origin[None] + ab[:, :1] * u[None] + ab[:, 1:] * v[None]
 
 
+def _unique_rows(vox):
+    """np.unique(vox, axis=0) for int32 [N,3] voxels -- the same rows in the same (lexicographic) order -- through one int64 key
+    per row: a 1-D sort instead of a sort of structured rows, several times faster at scene size"""
+    lo = vox.min(0).astype(np.int64)
+    span = vox.max(0).astype(np.int64) - lo + 1
+    v = vox.astype(np.int64) - lo
+    key = np.unique((v[:, 0] * span[1] + v[:, 1]) * span[2] + v[:, 2])
+    out = np.empty((key.shape[0], 3), np.int64)
+    out[:, 2] = key % span[2]
+    key //= span[2]
+    out[:, 1] = key % span[1]
+    out[:, 0] = key // span[1]
+    return (out + lo).astype(np.int32)
+
+
 def make_scene(seed, voxel=0.02, n_target=150000, tol=0.05, num_labels=200, ignore_frac=0.10, ignore_label=-1):
     """-> (coords[N,3] int32 unique voxels, feats[N,3] float32 in [0,255], labels[N] int64)"""
     rng = np.random.default_rng(seed)
@@ -48,7 +63,7 @@ def make_scene(seed, voxel=0.02, n_target=150000, tol=0.05, num_labels=200, igno
         R = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1.0]])
         p = (p - p.mean(0)) @ R.T                      # rigid augmentation about the origin -> negative coords
         vox = np.floor(p / voxel).astype(np.int32)
-        vox = np.unique(vox, axis=0)
+        vox = _unique_rows(vox)
         n = vox.shape[0]
         if abs(n - n_target) <= tol * n_target:
             break

@@ -19,6 +19,9 @@
                           logits + features of the REFERENCE's forward code (res16unet.py:196-270,
                           resnet_block.py:41-57) run on the CPU oracle backend with name-keyed
                           deterministic weights; pins the build's models.py dataflow.
+4. deferred_units_res16unet34c.npz
+                          the reference's unchanged res16unet.py + resnet_block.py through the deferred ME
+                          surface: state-dict keys, the fused units recorded, logits (`deferred_units`).
 """
 import json
 import os
@@ -120,7 +123,7 @@ def distance_fixture():
 
 
 def ce_and_latent_fixture():
-    """2e. contrastive_ce_latent.npz
+    """2e. contrastive_ce_cos.npz + contrastive_ce_l2.npz + contrastive_latent.npz + contrastive_latent_anchors.npz
     (a) the reference's ContrastiveLanguageCELoss.forward (lib/losses/ContrastiveLanguageLoss.py:196-237) on CPU, 'cos' and 'l2';
     (b) the reference's ContrastiveLanguageLoss.forward with (category, attribute) labels and instance_augmentation='latent'
         (:62-70,:149-181) run on CPU: its two `torch.cuda.FloatTensor(...)` allocations are pointed at the CPU allocator for the
@@ -207,7 +210,12 @@ def ce_and_latent_fixture():
                 "lat_pos_loss": pos_loss.numpy(), "lat_neg_loss": neg_loss.numpy(),
                 "lat_proj_w": torch.stack([sd["attr_linears.%d.weight" % i] for i in range(8)]).numpy(),
                 "lat_proj_b": torch.stack([sd["attr_linears.%d.bias" % i] for i in range(8)]).numpy()})
-    np.savez_compressed(os.path.join(HERE, "contrastive_ce_latent.npz"), **out)
+    # one fixture in four files: no committed file above 1 MiB (the tests merge them)
+    for fname, keys in (("contrastive_ce_cos.npz", [k for k in out if k.startswith("ce_cos_")]),
+                        ("contrastive_ce_l2.npz", [k for k in out if k.startswith("ce_l2_")]),
+                        ("contrastive_latent_anchors.npz", ["lat_T"]),
+                        ("contrastive_latent.npz", [k for k in out if k.startswith("lat_") and k != "lat_T"])):
+        np.savez_compressed(os.path.join(HERE, fname), **{k: out[k] for k in keys})
     print("CE + latent fixture: ce losses", {k: float(v[0]) for k, v in out.items() if k.endswith("_loss") and k.startswith("ce_")},
           "latent: %d of %d targets augmented, %d rows changed, loss %.5f" % (int(plan_on.sum()), len(uts),
                                                                               int((F != F0).any(1).sum()), float(loss)))
@@ -338,7 +346,41 @@ def insseg_fixture(seed=11, n=1400):
         json.dump(man, f)
 
 
+def deferred_units_fixture(seed=3, n=1500):
+    """the reference's unchanged models/res16unet.py + modules/resnet_block.py run through the deferred ME surface on the torch
+    oracle backend: state-dict keys, the fused units the forward is recorded as, and the logits (tests/test_deferred_cpu.py)"""
+    from models import load_model
+    from languagegroundedsemseg_amd.me import deferred
+    prev = ME.set_backend(OracleBackend("torch"))
+    was = deferred.ENABLED, deferred.INCREMENTAL
+    deferred.ENABLED, deferred.INCREMENTAL = True, False
+    try:
+        coords = small_scene(seed, n=n)
+        feats = np.random.default_rng(seed).uniform(-0.5, 0.5, (coords.shape[0], 3)).astype(np.float32)
+        m = deterministic_init(load_model("Res16UNet34C")(3, 20, Cfg()), 42).train()
+        x = ME.SparseTensor(torch.from_numpy(feats), torch.from_numpy(coords))
+        logits, _ = m(x)
+        q = x.coordinate_manager._pending
+        units = [(op.kind, type(op.mod).__name__, op.relu, op.residual is not None) for op in q]
+        out = logits.F.detach().numpy()
+        deferred.ENABLED = False
+        m2 = deterministic_init(load_model("Res16UNet34C")(3, 20, Cfg()), 42).train()
+        l2, _ = m2(ME.SparseTensor(torch.from_numpy(feats), torch.from_numpy(coords)))
+        assert np.array_equal(l2.F.detach().numpy(), out)
+        np.savez_compressed(os.path.join(HERE, "deferred_units_res16unet34c.npz"), coords=coords, feats=feats, logits=out,
+                            state_keys=np.array(list(m.state_dict().keys())),
+                            unit_kind=np.array([u[0] for u in units], np.int32), unit_mod=np.array([u[1] for u in units]),
+                            unit_relu=np.array([u[2] for u in units]), unit_residual=np.array([u[3] for u in units]))
+        print("deferred units fixture:", coords.shape, len(units), "units")
+    finally:
+        deferred.ENABLED, deferred.INCREMENTAL = was
+        ME.set_backend(prev)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "deferred_units":
+        deferred_units_fixture()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "insseg":
         insseg_fixture()
         sys.exit(0)
@@ -360,3 +402,4 @@ if __name__ == "__main__":
     balancing_fixture()
     forward_fixture("Res16UNet14A", 3, 1500)
     forward_fixture("Res16UNet34C", 5, 1200)
+    deferred_units_fixture()

@@ -136,7 +136,7 @@ def test_bench_prints_one_line_for_two_gpus(allreduce):
     under 4 KB with both ranks' step times, the exposed all-reduce wait and the communicator bring-up time"""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--scenes", "2",
-                        "--no-cpu-baseline", "--no-secondary", "--no-single-scene", "--allreduce", allreduce],
+                        "--full", "--no-cpu-baseline", "--no-secondary", "--no-single-scene", "--allreduce", allreduce],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]

@@ -10,7 +10,9 @@ pytestmark = [pytest.mark.gpu, pytest.mark.parity("reference-generated golden fi
 DEV = "cuda:0"
 G = os.path.join(os.path.dirname(__file__), "golden")
 FX = np.load(os.path.join(G, "contrastive_loss.npz"))
-CL = np.load(os.path.join(G, "contrastive_ce_latent.npz"))
+CL = {}      # one fixture in four files (none above 1 MiB)
+for _part in ("contrastive_ce_cos", "contrastive_ce_l2", "contrastive_latent", "contrastive_latent_anchors"):
+    CL.update(np.load(os.path.join(G, _part + ".npz")))
 
 
 @pytest.mark.parametrize("dtype,tol_loss,tol_grad", [(torch.float32, 5e-6, 2e-6), (torch.bfloat16, 2e-2, None)])

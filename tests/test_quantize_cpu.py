@@ -59,3 +59,14 @@ def test_host_sparse_quantize_matches_oracle():
     # float32 division (host path) vs float64 product (oracle): identical away from cell boundaries, which _points avoids
     assert np.array_equal(idx.numpy(), ui) and np.array_equal(inverse.numpy(), inv)
     assert np.array_equal(c.numpy(), coords[ui][:, 1:]) and np.array_equal(l.numpy(), lab)
+
+
+def test_synthetic_scene_deduplication_equals_numpy_unique_rows():
+    """make_scene de-duplicates its voxels through one int64 key per row: the same rows in the same order as np.unique(axis=0)"""
+    from languagegroundedsemseg_amd.synthetic import _unique_rows
+    rng = np.random.default_rng(5)
+    for n in (1, 7, 5000):
+        v = rng.integers(-300, 300, (n, 3)).astype(np.int32)
+        v = np.concatenate([v, v[: n // 2]], 0)
+        got = _unique_rows(v)
+        assert got.dtype == np.int32 and np.array_equal(got, np.unique(v, axis=0))
