@@ -1008,6 +1008,20 @@ int bn_partial_rows_t(const View &v, int K, int o_real) {
   return split ? 0 : (int)gx;
 }
 
+// bytes of the workspace region that holds the packed weight image of a launch on this view: the image is ncp x nbp blocks
+// of the tile configuration gather_cfg picks (slabs of sc chunks, column tiles of wb blocks), which the (nc + 3) x (nb_total + 3)
+// blocks sized here before do not always cover (ids 12 / 13 pack 8-chunk slabs: 32 -> 64 is 8 x 4 = 32 blocks against 4 x 5 = 20).
+// Never smaller than that older size, so the offsets of everything behind the image only move where it did not fit.
+// lgs_conv_workspace_bytes sizes for both views of the map with the same function.
+template <typename TK>
+int64_t packed_region_bytes(const View &v, int K, int g_real, int o_real) {
+  const int nc = pad32(g_real) / 32, nb_total = pad32(o_real) / 32;
+  const GatherCfg cfg = gather_cfg<TK>(v, nb_total);
+  const int64_t ncp = (nc + cfg.sc - 1) / cfg.sc * cfg.sc, nbp = (nb_total + cfg.wb - 1) / cfg.wb * cfg.wb;
+  const int64_t legacy = (int64_t)(nc + 3) * (nb_total + 3);
+  return align256((int64_t)K * (ncp * nbp > legacy ? ncp * nbp : legacy) * Tr<TK>::WLD * 64 * 16);
+}
+
 // T = storage type of the tensors, TK = the kernel instance that multiplies them (TK = f32s_t: fp32 tensors, split-bf16 products)
 template <typename T, typename TK = T>
 int conv_gather_op(const View &v, const void *in_v, int g_real, const float *weight, int K, int cin_w, int cout_w,
@@ -1029,7 +1043,7 @@ int conv_gather_op(const View &v, const void *in_v, int g_real, const float *wei
   uint4 *wp = reinterpret_cast<uint4 *>(ws);
   const GatherCfg cfg = gather_cfg<TK>(v, nb_total);
   const int ncp = (nc + cfg.sc - 1) / cfg.sc * cfg.sc, nbp = (nb_total + cfg.wb - 1) / cfg.wb * cfg.wb;
-  int64_t wbytes = align256((int64_t)K * (nc + 3) * (nb_total + 3) * LD * 64 * 16);
+  const int64_t wbytes = packed_region_bytes<TK>(v, K, g_real, o_real);
   if (o_real % 4 != 0) {
     // rows are written in 4-channel groups: route odd widths (e.g. the 3-channel input gradient of a
     // test) through a 4-aligned scratch image placed after the packed weights and the padded input
@@ -1075,6 +1089,8 @@ int conv_gather_op(const View &v, const void *in_v, int g_real, const float *wei
   // packed_ext: a caller-owned image of exactly this layout (lgs_conv_pack_desc); pack_mode 2 = it is up to date
   if (packed_ext && o_real % 4 == 0 && g_real % EPL == 0) wp = reinterpret_cast<uint4 *>(packed_ext);
   else pack_mode = 0;
+  LGS_REQUIRE(wp != reinterpret_cast<uint4 *>(ws) || total * 16 <= wbytes,
+              "sparse conv: the packed weight image is larger than its workspace region (internal error)");
   if (pack_mode != 2)
     LGS_KLAUNCH((k_pack_weights<TK>), (unsigned)((total + 255) / 256), 256, 0, s, weight, K, cin_w, cout_w, transposed_w,
                        v.mirror, g_real, w_o_real, ncp, nbp, wp);
@@ -1141,6 +1157,8 @@ int clip_similarity_t(const void *feat, int64_t n, int c, const float *anchors, 
   const GatherCfg cfg = gather_cfg<T>(v, nb_total);
   const int ncp = (nc + cfg.sc - 1) / cfg.sc * cfg.sc, nbp = (nb_total + cfg.wb - 1) / cfg.wb * cfg.wb;
   int64_t total = (int64_t)ncp * nbp * LD * 64;
+  LGS_REQUIRE(total * 16 <= align256((int64_t)(nc + 3) * (nb_total + 3) * LD * 64 * 16),
+              "lgs_clip_similarity: the packed anchor image is larger than its workspace region (SMALL_CFG 12 / 13 on a narrow feature)");
   // T^[a][c] read as w[o = a][g = c]  ("transposed" form of the packer with cin_w = na, cout_w = c)
   LGS_KLAUNCH((k_pack_weights<T>), (unsigned)((total + 255) / 256), 256, 0, s, tn, 1, na, c, 1, 0, c, na, ncp, nbp, wp);
   LGS_KLAUNCH((k_row_invnorm<T>), (unsigned)((n * 64 + 255) / 256), 256, 0, s, f, n, c, inv);
@@ -1167,6 +1185,8 @@ int clip_loss_forward_t(const void *feat, int64_t n, int c, const float *anchors
   uint4 *wp = reinterpret_cast<uint4 *>(ws);
   LGS_KLAUNCH(k_normalize_anchors, na, 64, 0, s, anchors, na, c, anchors_n);
   int64_t total = (int64_t)ncp * nbp * LD * 64;
+  LGS_REQUIRE(total * 16 <= align256((int64_t)(nc + 3) * (nb_total + 3) * LD * 64 * 16),
+              "lgs_clip_similarity: the packed anchor image is larger than its workspace region (SMALL_CFG 12 / 13 on a narrow feature)");
   // T^[a][c] read as w[o = a][g = c]  ("transposed" form of the packer with cin_w = na, cout_w = c)
   LGS_KLAUNCH((k_pack_weights<T>), (unsigned)((total + 255) / 256), 256, 0, s, anchors_n, 1, na, c, 1, 0, c, na, ncp, nbp, wp);
   View v;
@@ -1227,6 +1247,12 @@ int64_t lgs_conv_workspace_bytes(const lgs_kmap *km, int cin, int cout, int dtyp
   int g = op == 0 ? cin : cout, o = op == 0 ? cout : cin;
   // packed weights: fp32 images of the split path hold three bf16 pieces per element (6 instead of 4 bytes)
   int64_t bytes = align256((int64_t)km->K * (pad32(g) + 96) * (pad32(o) + 96) * (dtype == LGS_F32 ? 6 : e));
+  // ... or the image of the tile configuration the launch will pick (either view: op 0 / 1 run on fwd or bwd by `transposed`)
+  for (const View *v : {&km->fwd, &km->bwd}) {
+    const int64_t pr = dtype == LGS_BF16 ? packed_region_bytes<bf16_t>(*v, km->K, g, o)
+                       : fp32_split_on() ? packed_region_bytes<f32s_t>(*v, km->K, g, o) : packed_region_bytes<float>(*v, km->K, g, o);
+    if (pr > bytes) bytes = pr;
+  }
   int64_t nmax = km->fwd.n_in > km->bwd.n_in ? km->fwd.n_in : km->bwd.n_in;
   if (g % epl(dtype) != 0) bytes += align256(nmax * pad32(g) * e);
   if (o % 4 != 0) bytes += align256(nmax * (int64_t)((o + 3) / 4 * 4) * e) + align256(4 * (int64_t)((o + 3) / 4 * 4)) + 256;   // scratch image + padded bias

@@ -254,11 +254,13 @@ class HipKernelMap:
     def __init__(self, mgr, handle, in_key, out_key, ks):
         self.mgr, self.h, self.in_key, self.out_key, self.ks = mgr, handle, in_key, out_key, ks
         self.K = ks ** 3
-        self._wsb = {}            # lgs_conv_workspace_bytes per (cin, cout, dtype, op): several layers share a map
-        self._pdesc = {}          # lgs_conv_pack_desc per (op, transposed, cin, cout, dtype)
+        # lgs_conv_workspace_bytes per (cin, cout, dtype, op, tuning epoch): several layers share a map, and the answer depends
+        # on knobs (tile configuration, weight-gradient plans), so a knob change must not reuse a size computed before it
+        self._wsb = {}
+        self._pdesc = {}          # lgs_conv_pack_desc per (op, transposed, cin, cout, dtype, tuning epoch)
 
     def _ws_bytes(self, L, cin, cout, dt, op):
-        key = (cin, cout, dt, op)
+        key = (cin, cout, dt, op, engine.TUNING_EPOCH)
         b = self._wsb.get(key)
         if b is None:
             b = self._wsb[key] = L.lgs_conv_workspace_bytes(self.h, cin, cout, dt, op)
@@ -613,7 +615,7 @@ class HipBackend:
         return st
 
     def _block_ws(self, L, kmap3, kmap1, cin, planes, dt, n, device):
-        key = ("cblk_ws", cin, planes, dt)
+        key = ("cblk_ws", cin, planes, dt, engine.TUNING_EPOCH)
         b = kmap3._wsb.get(key)
         if b is None:
             b = kmap3._wsb[key] = L.lgs_block_workspace_bytes(kmap3.h, kmap1.h if kmap1 is not None else None, cin, planes, dt)

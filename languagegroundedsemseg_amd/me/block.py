@@ -7,6 +7,7 @@ reference's own BasicBlock, the build's models.BasicBlock, or loose calls -- onl
 import torch
 import torch.nn as nn
 
+from .. import engine
 from .. import tuning as _tuning
 from .core import get_backend
 from . import modules as _mod
@@ -132,10 +133,9 @@ def _c_block_ok(x, kmap3, kmap1, cin, planes, be):
         return False
     if _BLOCK_C_VETO is not None and _BLOCK_C_VETO(x.shape[0], cin, planes):
         return False
-    key = ("cblk", cin, planes, x.dtype)
+    key = ("cblk", cin, planes, x.dtype, engine.TUNING_EPOCH)     # the launch shape behind the answer depends on knobs
     ok = kmap3._wsb.get(key)
     if ok is None:
-        from .. import engine
         dt = engine.LGS_BF16 if x.dtype == torch.bfloat16 else engine.LGS_F32
         ok = kmap3._wsb[key] = bool(engine.lib().lgs_conv_dgrad_can_accumulate(kmap3.h, 0, cin, planes, dt))
     return ok
