@@ -41,12 +41,13 @@
 extern "C" {
 #endif
 
-#define LGS_ABI_VERSION 13
+#define LGS_ABI_VERSION 14
 
 enum lgs_dtype { LGS_F32 = 0, LGS_BF16 = 1 };
 
 typedef struct lgs_manager lgs_manager; /* coordinate manager: owns coordinate maps + kernel maps */
 typedef struct lgs_kmap lgs_kmap;       /* one cached kernel map (owned by its manager) */
+typedef struct lgs_segmap lgs_segmap;   /* one cached segment map: pooling / broadcast (owned by its manager) */
 
 /* ---- library ---------------------------------------------------------------------------- */
 int lgs_abi_version(void);
@@ -90,7 +91,8 @@ int lgs_manager_stride2(lgs_manager *mgr, int in_key, void *stream, int *out_key
 /* Device-side consistency flags of this manager's maps, read back with ONE synchronisation of the manager's map stream
  * (test / debug infrastructure: the map builders size coarse maps from counts taken at insert time and never synchronise;
  * a builder that finds its own count disagreeing raises the flag instead of writing past its arrays).  *flags: 0 = consistent,
- * bit 0 = coordinate out of the key range at insert, bit 1 = a coarse map's row count differs from the insert-time count.
+ * bit 0 = coordinate out of the key range at insert, bit 1 = a coarse map's row count differs from the insert-time count,
+ * bit 2 = the origin map's row count differs from the insert-time batch count.
  * Same call sites as lgs_manager_stride2.                                                                             */
 int lgs_manager_check(lgs_manager *mgr, int *flags);
 
@@ -115,6 +117,35 @@ int lgs_manager_kernel_map(lgs_manager *mgr, int in_key, int out_key, int kernel
 /* Export the map as (k, in_row, out_row) triples for set-equality parity tests.
  * Pass NULL buffers to query *m only (synchronises). Buffers are device int32[*m]. */
 int lgs_kmap_export(lgs_kmap *km, int32_t *k, int32_t *in_row, int32_t *out_row, void *stream, int64_t *m);
+
+/* ---- pooling, global pooling and broadcast (ABI 14; csrc/lgs_pool.hip) ----------------------
+ * replaces MinkowskiSumPooling / AvgPooling / MaxPooling / PoolingTranspose / AvgUnpooling (kernel_size == stride == 2^k),
+ * MinkowskiGlobal{Sum,Avg,Max}Pooling and MinkowskiBroadcast{,Addition,Multiplication,Concatenation}:
+ *   /root/reference/models/modules/common.py:239-300, models/resnet.py:48, models/resunet.py:367,388,409,
+ *   downstream/insseg/lib/layers.py
+ * lgs_manager_origin: the origin map of the manager -- one row (b, 0, 0, 0) per batch index of the insert, ascending, tensor
+ *   stride 0.  Its row count was taken at insert time: no synchronisation.  Cached.
+ * lgs_manager_segment_map: the fine -> coarse relation between `fine_key` and `coarse_key`, where the coarse map is the origin
+ *   map or a stride-2^k descendant of the fine map (lgs_manager_stride2 applied k times, 1 <= k <= 12).  Each coarse row owns
+ *   one contiguous run of the fine map's Morton-sorted positions.  Built on the manager's stream, cached per key pair; the
+ *   compute calls below order themselves after it.
+ * lgs_seg_reduce: out[q] = reduction over the fine rows of coarse row q of x (row stride x_ld elements; out [n_coarse, c]
+ *   contiguous).  op 0 sum, 1 average (sum / rows present), 2 max (argmax[q][c] = the fine row that won, the smallest row on
+ *   ties; int32 [n_coarse, c]), 3 sum of x * x2 (x2 with the same row stride).  fp32 accumulation in a fixed order, one
+ *   rounding to `dtype`, no atomics.  `workspace`: lgs_seg_workspace_bytes(sm, c) bytes (0 for maps of stride 2, 4 and 8).
+ * lgs_seg_broadcast: for every fine row r of coarse row q: out[r] (row stride out_ld) = op 0 g[q], 1 g[q] / rows of q,
+ *   2 x[r] + g[q], 3 x[r] * g[q], 4 x[r] (g unused; the other half of a concatenation).  g is [n_coarse, c] contiguous.
+ * lgs_seg_max_backward: dx[r][c] = (argmax[q][c] == r) ? dy[q][c] : 0 for every fine row r (dx, dy contiguous).
+ * lgs_segmap_size: rows of the fine and the coarse map. */
+int lgs_manager_origin(lgs_manager *mgr, void *stream, int *out_key, int64_t *n_out);
+int lgs_manager_segment_map(lgs_manager *mgr, int fine_key, int coarse_key, void *stream, lgs_segmap **out);
+int lgs_segmap_size(const lgs_segmap *sm, int64_t *n_fine, int64_t *n_coarse);
+int64_t lgs_seg_workspace_bytes(const lgs_segmap *sm, int c);
+int lgs_seg_reduce(lgs_segmap *sm, int op, const void *x, const void *x2, int64_t x_ld, int c, void *out, int32_t *argmax,
+                   int dtype, void *workspace, void *stream);
+int lgs_seg_broadcast(lgs_segmap *sm, int op, const void *g, int c, const void *x, int64_t x_ld, void *out, int64_t out_ld,
+                      int dtype, void *stream);
+int lgs_seg_max_backward(lgs_segmap *sm, const void *dy, const int32_t *argmax, int c, void *dx, int dtype, void *stream);
 
 /* ---- sparse convolution --------------------------------------------------------------------
  * replaces MinkowskiConvolution / MinkowskiConvolutionTranspose forward + autograd backward

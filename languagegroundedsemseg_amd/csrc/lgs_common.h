@@ -9,6 +9,7 @@
 #include "../../include/lgs_engine.h"
 
 struct lgs_kmap;
+struct lgs_segmap;
 
 namespace lgs {
 
@@ -71,6 +72,22 @@ struct View {
   int mirror = 0;     // weight index = K-1-s (the 3^3 map read in the dgrad direction)
 };
 
+// A segment map between a fine map and a coarser one (a stride-2^k descendant or the origin map):
+// the fine rows of coarse row q are the fine SORTED positions [seg_start[q], seg_start[q+1]) -- one contiguous run, because
+// coarsening masks low key bits and keeps the Morton sort, and the batch index is the top key field.
+// Segments longer than kSegChunk rows are reduced in two passes over chunk items of at most kSegChunk rows each.
+constexpr int kSegChunk = 512;
+struct SegMap {
+  const int32_t *fine_row = nullptr;    // [n_fine] sorted position -> fine row; NULL = identity (coarse levels)
+  const int32_t *seg_start = nullptr;   // [n_coarse + 1]
+  const int32_t *coarse_of = nullptr;   // [n_fine] coarse row of each fine sorted position
+  const int32_t *item_start = nullptr;  // [n_coarse + 1] first chunk item of each segment (two-pass maps only)
+  const int32_t *item_seg = nullptr;    // [n_items] segment of each chunk item, -1 = unused slot (two-pass maps only)
+  int64_t n_fine = 0, n_coarse = 0, n_items = 0;
+  int64_t max_len = 0;                  // bound on the rows of one segment (8^k for stride 2^k); 0 = none (origin map)
+  bool single_pass() const { return max_len > 0 && max_len <= kSegChunk; }
+};
+
 inline int pad32(int c) { return (c + 31) / 32 * 32; }
 inline int esize(int dtype) { return dtype == LGS_BF16 ? 2 : 4; }
 inline int epl(int dtype) { return dtype == LGS_BF16 ? 8 : 4; }
@@ -107,6 +124,7 @@ int conv_wgrad_wide(const View &v, const void *in, int cin, int in_ld, const voi
                     hipStream_t s, bool *done);
 // order `stream` after the construction of km's manager's maps (they are built on the manager's own stream)
 int kmap_wait(lgs_kmap *km, hipStream_t stream);
+int segmap_wait(lgs_segmap *sm, hipStream_t stream);
 
 }  // namespace lgs
 
@@ -115,4 +133,10 @@ struct lgs_kmap {
   int in_key = -1, out_key = -1, ks = 0, K = 1;
   lgs::View fwd;  // gathers from the in map, writes the out map
   lgs::View bwd;  // gathers from the out map, writes the in map (dgrad / transposed conv)
+};
+
+struct lgs_segmap {
+  lgs_manager *mgr = nullptr;
+  int fine_key = -1, coarse_key = -1;
+  lgs::SegMap sm;
 };

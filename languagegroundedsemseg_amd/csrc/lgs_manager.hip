@@ -162,15 +162,18 @@ __global__ void k_hash_insert(const uint64_t *skeys, const int32_t *order, int64
 // matter: equal keys stay equal under any mask).
 constexpr int kPreLevels = 8;
 constexpr int kCountPerThread = 16;
+constexpr int kBatchShift = 54;   // key bits above it: the batch index
+// counts[kPreLevels] (one slot more): the distinct batch indices, i.e. the rows of the origin map (lgs_manager_origin) --
+// the same at every level of one insert
 __global__ __launch_bounds__(256) void k_count_levels(const uint64_t *__restrict__ skeys, int64_t n, int32_t *__restrict__ counts) {
   // a workgroup walks 256 x kCountPerThread consecutive keys and adds ONE number per level to the global counters (one
   // atomic per wave and level on eight shared addresses cost 0.67 ms at 1.2 M keys: the atomics serialise at the L2)
-  __shared__ int32_t l_cnt[kPreLevels];
-  if (threadIdx.x < kPreLevels) l_cnt[threadIdx.x] = 0;
+  __shared__ int32_t l_cnt[kPreLevels + 1];
+  if (threadIdx.x <= kPreLevels) l_cnt[threadIdx.x] = 0;
   __syncthreads();
-  int32_t c[kPreLevels];
+  int32_t c[kPreLevels + 1];
 #pragma unroll
-  for (int L = 0; L < kPreLevels; ++L) c[L] = 0;
+  for (int L = 0; L <= kPreLevels; ++L) c[L] = 0;
   const int64_t base = (int64_t)blockIdx.x * 256 * kCountPerThread;
 #pragma unroll 4
   for (int i = 0; i < kCountPerThread; ++i) {
@@ -179,16 +182,17 @@ __global__ __launch_bounds__(256) void k_count_levels(const uint64_t *__restrict
     const uint64_t k = skeys[p], q = p > 0 ? skeys[p - 1] : ~0ull, d = k ^ q;
 #pragma unroll
     for (int L = 1; L <= kPreLevels; ++L) c[L - 1] += (p == 0 || (d >> (3 * L)) != 0) ? 1 : 0;
+    c[kPreLevels] += (p == 0 || (d >> kBatchShift) != 0) ? 1 : 0;
   }
 #pragma unroll
-  for (int L = 0; L < kPreLevels; ++L) {
+  for (int L = 0; L <= kPreLevels; ++L) {
     int32_t v = c[L];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(&l_cnt[L], v);
   }
   __syncthreads();
-  if (threadIdx.x < kPreLevels && l_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], l_cnt[threadIdx.x]);
+  if (threadIdx.x <= kPreLevels && l_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], l_cnt[threadIdx.x]);
 }
 
 // 3x3x3 stride-1 map: one thread per sorted position, 27 probes; nbr is offset-major [27][n_pad].
@@ -394,6 +398,61 @@ __global__ void k_view_export(View v, int32_t *cursor, int32_t *ek, int32_t *ein
   }
 }
 
+// ---- origin map + segment maps (pooling / broadcast)
+// origin map: one row (b, 0, 0, 0) per batch index, ascending; nb = the count taken at insert time (d_err bit 2 if it differs)
+__global__ void k_origin_coords(const uint64_t *skeys, const int32_t *head, const int32_t *cincl, int64_t n, int64_t nb,
+                                int32_t *coords, int *d_err) {
+  int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const int32_t q = cincl[p] - 1;
+  if (p == n - 1 && (int64_t)q + 1 != nb && d_err) atomicOr(d_err, 4);
+  if (q >= nb || !head[p]) return;
+  reinterpret_cast<int4 *>(coords)[q] = make_int4((int)(skeys[p] >> kBatchShift), 0, 0, 0);
+}
+// segments of the origin map over a fine map: one run of sorted positions per batch index
+__global__ void k_origin_segments(const int32_t *head, const int32_t *cincl, int64_t n, int64_t nb, int32_t *seg_start,
+                                  int32_t *coarse_of) {
+  int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const int32_t q = cincl[p] - 1;
+  coarse_of[p] = q < nb ? q : (int32_t)(nb - 1);
+  if (q >= nb) return;
+  if (head[p]) seg_start[q] = (int32_t)p;
+  if (p == n - 1) seg_start[q + 1] = (int32_t)n;
+}
+// a stride-2^k segment map composes the k stride-2 steps in between (each keeps the sort, so runs stay runs)
+constexpr int kMaxChain = 12;
+struct Chain {
+  const int32_t *fine_cidx[kMaxChain];  // level j's fine_cidx (indexed by level j-1 sorted positions), j = 1..k
+  const int32_t *cstart[kMaxChain];     // level j's cstart [n_j + 1]
+  int k;
+};
+__global__ void k_compose_coarse_of(Chain ch, int64_t n, int32_t *coarse_of) {
+  int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  int32_t v = (int32_t)p;
+  for (int j = 0; j < ch.k; ++j) v = ch.fine_cidx[j][v];
+  coarse_of[p] = v;
+}
+__global__ void k_compose_seg_start(Chain ch, int64_t nc, int32_t *seg_start) {
+  int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q > nc) return;
+  int32_t v = (int32_t)q;
+  for (int j = ch.k - 1; j >= 0; --j) v = ch.cstart[j][v];
+  seg_start[q] = v;
+}
+// chunk items of a two-pass map: segment q owns items [item_start[q], item_start[q+1]), ceil(len / kSegChunk) of them
+__global__ void k_item_counts(const int32_t *seg_start, int64_t nc, int32_t *cnt) {
+  int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nc) return;
+  cnt[q] = (seg_start[q + 1] - seg_start[q] + kSegChunk - 1) / kSegChunk;
+}
+__global__ void k_item_fill(const int32_t *item_start, int64_t nc, int64_t n_items, int32_t *item_seg) {
+  int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nc) return;
+  for (int32_t j = item_start[q]; j < item_start[q + 1] && j < n_items; ++j) item_seg[j] = (int32_t)q;
+}
+
 struct CoordMap {
   int ts = 1, log2ts = 0;
   int64_t n = 0, n_pad = 0;
@@ -404,6 +463,7 @@ struct CoordMap {
   int32_t *hvals = nullptr;
   int64_t hcap = 0;
   int fine_key = -1, coarse_key = -1;
+  bool origin = false;           // one row (b, 0, 0, 0) per batch index (lgs_manager_origin); tensor stride 0
   int32_t *cstart = nullptr;     // [n+1] first fine sorted position of each row (maps made by stride2)
   int32_t *fine_cidx = nullptr;  // [n_fine] coarse row of each fine sorted position
 };
@@ -433,6 +493,9 @@ struct lgs_manager {
   std::vector<Blk> blks;           // live arena blocks in allocation order (a stack: freed blocks on top are popped)
   size_t pool_live = 0, pool_peak = 0;
   int64_t precount[8] = {-1, -1, -1, -1, -1, -1, -1, -1};   // rows of the maps at tensor stride 2^(i+1), counted by the insert (-1: unknown)
+  int64_t precount_batches = -1;   // distinct batch indices of the insert = rows of the origin map
+  int origin_key = -1;             // lgs_manager_origin's map (-1: not made yet)
+  std::vector<lgs_segmap *> segmaps;
 };
 
 namespace {
@@ -632,6 +695,12 @@ int kmap_wait(lgs_kmap *km, hipStream_t stream) {
   add_user(m, stream);
   return 0;
 }
+int segmap_wait(lgs_segmap *sm, hipStream_t stream) {
+  lgs_manager *m = sm->mgr;
+  LGS_HIP(hipStreamWaitEvent(stream, m->ev_ready, 0));
+  add_user(m, stream);
+  return 0;
+}
 }  // namespace lgs
 
 extern "C" {
@@ -677,6 +746,7 @@ int lgs_manager_destroy(lgs_manager *m) {
   for (void *p : m->allocs) (void)hipFreeAsync(p, fs);   // pool fallbacks only (none in the steady state)
   arena_release(m);                                      // the block goes back to the device's FIFO, stamped per user stream
   for (lgs_kmap *k : m->kmaps) delete k;
+  for (lgs_segmap *k : m->segmaps) delete k;
   (void)hipEventDestroy(m->ev_ready);
   (void)hipEventDestroy(m->ev_in);
   delete m;
@@ -723,15 +793,16 @@ int lgs_manager_insert(lgs_manager *m, const int32_t *coords, int64_t n, int64_t
     if (scan_incl(m, is_first, urow + 1, n, s)) return 1;
   }
   int32_t *lvl_counts;
-  if (dalloc(m, &lvl_counts, kPreLevels, s)) return 1;
-  LGS_HIP(hipMemsetAsync(lvl_counts, 0, sizeof(int32_t) * kPreLevels, s));
+  if (dalloc(m, &lvl_counts, kPreLevels + 1, s)) return 1;
+  LGS_HIP(hipMemsetAsync(lvl_counts, 0, sizeof(int32_t) * (kPreLevels + 1), s));
   LGS_KLAUNCH(k_count_levels, (unsigned)((n + 256 * kCountPerThread - 1) / (256 * kCountPerThread)), 256, 0, s, skeys, n, lvl_counts);
-  int32_t h_nu = 0; int h_err = 0; int32_t h_lvl[kPreLevels];
+  int32_t h_nu = 0; int h_err = 0; int32_t h_lvl[kPreLevels + 1];
   LGS_HIP(hipMemcpyAsync(&h_nu, urow + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   LGS_HIP(hipMemcpyAsync(&h_err, m->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
-  LGS_HIP(hipMemcpyAsync(h_lvl, lvl_counts, sizeof(int32_t) * kPreLevels, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipMemcpyAsync(h_lvl, lvl_counts, sizeof(int32_t) * (kPreLevels + 1), hipMemcpyDeviceToHost, s));
   LGS_HIP(hipStreamSynchronize(s));
   for (int i = 0; i < kPreLevels; ++i) m->precount[i] = h_lvl[i];
+  m->precount_batches = h_lvl[kPreLevels];
   LGS_REQUIRE(h_err == 0,
               "lgs_manager_insert: coordinate out of range (batch must be in [0,1024), |x|,|y|,|z| < 131008)");
   int64_t nu = h_nu;
@@ -752,6 +823,7 @@ int lgs_manager_insert(lgs_manager *m, const int32_t *coords, int64_t n, int64_t
 int lgs_manager_stride2(lgs_manager *m, int in_key, void *stream, int *out_key, int64_t *n_out) {
   LGS_REQUIRE(m && out_key && n_out, "lgs_manager_stride2: null argument");
   LGS_REQUIRE(in_key >= 0 && in_key < (int)m->maps.size(), "lgs_manager_stride2: bad key");
+  LGS_REQUIRE(!m->maps[in_key].origin, "lgs_manager_stride2: the origin map has no coarser map");
   hipStream_t s = m->ms;
   (void)stream;
   DeviceGuard guard(m->device);
@@ -840,6 +912,7 @@ int lgs_manager_kernel_map(lgs_manager *m, int in_key, int out_key, int ks, void
   LGS_REQUIRE(m && out, "lgs_manager_kernel_map: null argument");
   int nm = (int)m->maps.size();
   LGS_REQUIRE(in_key >= 0 && in_key < nm && out_key >= 0 && out_key < nm, "lgs_manager_kernel_map: bad key");
+  LGS_REQUIRE(!m->maps[in_key].origin && !m->maps[out_key].origin, "lgs_manager_kernel_map: no kernel maps on the origin map");
   for (lgs_kmap *k : m->kmaps)
     if (k->in_key == in_key && k->out_key == out_key && k->ks == ks) { *out = k; return 0; }
   hipStream_t s = m->ms;
@@ -938,6 +1011,116 @@ int lgs_manager_kernel_map(lgs_manager *m, int in_key, int out_key, int ks, void
   }
   m->kmaps.push_back(km);
   *out = km;
+  return publish(m, nullptr, false);
+}
+
+int lgs_manager_origin(lgs_manager *m, void *stream, int *out_key, int64_t *n_out) {
+  LGS_REQUIRE(m && out_key && n_out, "lgs_manager_origin: null argument");
+  LGS_REQUIRE(!m->maps.empty(), "lgs_manager_origin: the manager holds no map yet");
+  (void)stream;
+  if (m->origin_key >= 0) {
+    *out_key = m->origin_key; *n_out = m->maps[m->origin_key].n;
+    return 0;
+  }
+  hipStream_t s = m->ms;
+  DeviceGuard guard(m->device);
+  const CoordMap f = m->maps[0];
+  CoordMap o;
+  o.ts = 0; o.log2ts = 0; o.origin = true;
+  const int64_t n = f.n;
+  const int64_t nb = n > 0 ? m->precount_batches : 0;   // counted by lgs_manager_insert: no host synchronisation here
+  LGS_REQUIRE(nb >= 0, "lgs_manager_origin: batch count unknown");
+  o.n = nb; o.n_pad = pad_rows(nb);
+  if (n > 0) {
+    int32_t *head, *cincl;
+    if (dalloc(m, &o.coords, nb * 4, s) || dalloc(m, &head, n, s) || dalloc(m, &cincl, n, s)) return 1;
+    LGS_KLAUNCH(k_heads, nblk(n), 256, 0, s, f.skeys, n, ~((1ull << kBatchShift) - 1), head);
+    if (scan_incl(m, head, cincl, n, s)) return 1;
+    LGS_KLAUNCH(k_origin_coords, nblk(n), 256, 0, s, f.skeys, head, cincl, n, nb, o.coords, m->d_err);
+    LGS_HIP(hipGetLastError());
+    if (dfree_now(m, head, s) || dfree_now(m, cincl, s)) return 1;
+  }
+  m->maps.push_back(o);
+  m->origin_key = (int)m->maps.size() - 1;
+  *out_key = m->origin_key; *n_out = nb;
+  return publish(m, nullptr, false);
+}
+
+int lgs_manager_segment_map(lgs_manager *m, int fine_key, int coarse_key, void *stream, lgs_segmap **out) {
+  LGS_REQUIRE(m && out, "lgs_manager_segment_map: null argument");
+  const int nm = (int)m->maps.size();
+  LGS_REQUIRE(fine_key >= 0 && fine_key < nm && coarse_key >= 0 && coarse_key < nm, "lgs_manager_segment_map: bad key");
+  LGS_REQUIRE(!m->maps[fine_key].origin, "lgs_manager_segment_map: the fine map is the origin map");
+  for (lgs_segmap *k : m->segmaps)
+    if (k->fine_key == fine_key && k->coarse_key == coarse_key) { *out = k; return 0; }
+  (void)stream;
+  const CoordMap &cf = m->maps[fine_key];
+  const CoordMap &cc = m->maps[coarse_key];
+  Chain ch;
+  ch.k = 0;
+  if (!cc.origin) {   // walk coarse -> fine through the maps stride2 made
+    int levels[kMaxChain];
+    int c = coarse_key;
+    while (c != fine_key) {
+      LGS_REQUIRE(c >= 0 && !m->maps[c].origin && ch.k < kMaxChain,
+                  "lgs_manager_segment_map: the coarse map is neither the origin map nor a stride-2^k descendant of the fine map");
+      levels[ch.k++] = c;
+      c = m->maps[c].fine_key;
+    }
+    LGS_REQUIRE(ch.k >= 1, "lgs_manager_segment_map: fine and coarse map are the same map");
+    for (int j = 0; j < ch.k; ++j) {           // levels[] runs coarse -> fine; the chain fine -> coarse
+      const CoordMap &lv = m->maps[levels[ch.k - 1 - j]];
+      ch.fine_cidx[j] = lv.fine_cidx;
+      ch.cstart[j] = lv.cstart;
+    }
+  }
+  hipStream_t s = m->ms;
+  DeviceGuard guard(m->device);
+  SegMap sm;
+  sm.n_fine = cf.n; sm.n_coarse = cc.n;
+  sm.fine_row = cf.order;
+  sm.max_len = cc.origin ? 0 : (int64_t)1 << (3 * ch.k);
+  const int64_t n = cf.n, nc = cc.n;
+  if (n > 0) {
+    if (cc.origin) {
+      int32_t *head, *cincl, *seg_start, *coarse_of;
+      if (dalloc(m, &seg_start, nc + 1, s) || dalloc(m, &coarse_of, n, s) || dalloc(m, &head, n, s) || dalloc(m, &cincl, n, s))
+        return 1;
+      LGS_KLAUNCH(k_heads, nblk(n), 256, 0, s, cf.skeys, n, ~((1ull << kBatchShift) - 1), head);
+      if (scan_incl(m, head, cincl, n, s)) return 1;
+      LGS_KLAUNCH(k_origin_segments, nblk(n), 256, 0, s, head, cincl, n, nc, seg_start, coarse_of);
+      LGS_HIP(hipGetLastError());
+      if (dfree_now(m, head, s) || dfree_now(m, cincl, s)) return 1;
+      sm.seg_start = seg_start; sm.coarse_of = coarse_of;
+    } else if (ch.k == 1) {                    // one stride-2 step: its own arrays are the segment map
+      sm.seg_start = ch.cstart[0]; sm.coarse_of = ch.fine_cidx[0];
+    } else {
+      int32_t *seg_start, *coarse_of;
+      if (dalloc(m, &seg_start, nc + 1, s) || dalloc(m, &coarse_of, n, s)) return 1;
+      LGS_KLAUNCH(k_compose_coarse_of, nblk(n), 256, 0, s, ch, n, coarse_of);
+      LGS_KLAUNCH(k_compose_seg_start, nblk(nc + 1), 256, 0, s, ch, nc, seg_start);
+      LGS_HIP(hipGetLastError());
+      sm.seg_start = seg_start; sm.coarse_of = coarse_of;
+    }
+    if (!sm.single_pass()) {
+      // at most n / kSegChunk + nc items: the tables are sized by that bound (no host synchronisation), unused slots -1
+      const int64_t n_items = n / kSegChunk + nc + 1;
+      int32_t *cnt, *item_start, *item_seg;
+      if (dalloc(m, &item_start, nc + 1, s) || dalloc(m, &item_seg, n_items, s) || dalloc(m, &cnt, nc, s)) return 1;
+      LGS_KLAUNCH(k_item_counts, nblk(nc), 256, 0, s, sm.seg_start, nc, cnt);
+      LGS_HIP(hipMemsetAsync(item_start, 0, sizeof(int32_t), s));
+      if (scan_incl(m, cnt, item_start + 1, nc, s)) return 1;
+      LGS_KLAUNCH(k_fill_i32, nblk(n_items), 256, 0, s, item_seg, n_items, -1);
+      LGS_KLAUNCH(k_item_fill, nblk(nc), 256, 0, s, item_start, nc, n_items, item_seg);
+      LGS_HIP(hipGetLastError());
+      if (dfree_now(m, cnt, s)) return 1;
+      sm.item_start = item_start; sm.item_seg = item_seg; sm.n_items = n_items;
+    }
+  }
+  lgs_segmap *h = new lgs_segmap();
+  h->mgr = m; h->fine_key = fine_key; h->coarse_key = coarse_key; h->sm = sm;
+  m->segmaps.push_back(h);
+  *out = h;
   return publish(m, nullptr, false);
 }
 

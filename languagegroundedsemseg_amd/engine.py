@@ -10,7 +10,7 @@ import os
 from . import build as _build
 
 LGS_F32, LGS_BF16 = 0, 1
-ABI_VERSION = 13     # LGS_ABI_VERSION of include/lgs_engine.h
+ABI_VERSION = 14     # LGS_ABI_VERSION of include/lgs_engine.h
 
 
 class PackDesc(ctypes.Structure):
@@ -83,6 +83,8 @@ EXPORTS = [
     "lgs_manager_create", "lgs_manager_destroy", "lgs_manager_insert", "lgs_manager_stride2", "lgs_manager_check",
     "lgs_manager_parent_of", "lgs_manager_map_size", "lgs_manager_get_coords", "lgs_manager_kernel_map",
     "lgs_kmap_export",
+    "lgs_manager_origin", "lgs_manager_segment_map", "lgs_segmap_size", "lgs_seg_workspace_bytes", "lgs_seg_reduce",
+    "lgs_seg_broadcast", "lgs_seg_max_backward",
     "lgs_conv_workspace_bytes", "lgs_conv_bn_partial_rows", "lgs_conv_forward", "lgs_conv_dgrad", "lgs_conv_wgrad",
     "lgs_conv_wgrad_supports_stride", "lgs_conv_dgrad_can_accumulate", "lgs_conv_dgrad_accumulate",
     "lgs_conv_pack_desc", "lgs_pack_weights_batch",
@@ -137,6 +139,12 @@ def lib():
         "lgs_manager_get_coords": [vp, ci, vp, vp],
         "lgs_manager_kernel_map": [vp, ci, ci, ci, vp, pvp],
         "lgs_kmap_export": [vp, vp, vp, vp, vp, pi64],
+        "lgs_manager_origin": [vp, vp, pi, pi64],
+        "lgs_manager_segment_map": [vp, ci, ci, vp, pvp],
+        "lgs_segmap_size": [vp, pi64, pi64],
+        "lgs_seg_reduce": [vp, ci, vp, vp, i64, ci, vp, vp, ci, vp, vp],
+        "lgs_seg_broadcast": [vp, ci, vp, ci, vp, i64, vp, i64, ci, vp],
+        "lgs_seg_max_backward": [vp, vp, vp, ci, vp, ci, vp],
         "lgs_conv_forward": [vp, ci, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, ci, ci, vp],
         "lgs_conv_pack_desc": [vp, ci, ci, ci, ci, ci, ctypes.POINTER(PackDesc)],
         "lgs_pack_weights_batch": [vp, ci, i64, vp],
@@ -184,6 +192,8 @@ def lib():
     L.lgs_debug_dispatch_counts.argtypes = [ctypes.c_char_p, i64, ci]
     L.lgs_block_workspace_bytes.restype = i64
     L.lgs_block_workspace_bytes.argtypes = [vp, vp, ci, ci, ci]
+    L.lgs_seg_workspace_bytes.restype = i64
+    L.lgs_seg_workspace_bytes.argtypes = [vp, ci]
     L.lgs_cluster_workspace_bytes.restype = i64
     L.lgs_cluster_workspace_bytes.argtypes = [i64]
     L.lgs_conv_workspace_bytes.restype = i64

@@ -382,6 +382,14 @@ class HipKernelMap:
         return gw
 
 
+class HipSegmentMap:
+    """fine -> coarse segment map of one manager (include/lgs_engine.h, lgs_manager_segment_map)"""
+
+    def __init__(self, mgr, handle, fine_key, coarse_key):
+        self.mgr, self.h, self.fine_key, self.coarse_key = mgr, handle, fine_key, coarse_key
+        self.n_fine, self.n_coarse = mgr.map_size(fine_key), mgr.map_size(coarse_key)
+
+
 class HipManager:
     """One per input batch (ME semantics); owns the coordinate maps and kernel maps on the device."""
 
@@ -463,6 +471,26 @@ class HipManager:
             self._coords[key] = c
         return self._coords[key]
 
+    def origin(self):
+        """key of the origin map: one row (b, 0, 0, 0) per batch index, ascending (lgs_manager_origin; no synchronisation)"""
+        ok, n = ctypes.c_int(0), ctypes.c_int64(0)
+        with _dev(self.device):
+            engine.check(engine.lib().lgs_manager_origin(self.h, _stream(), ctypes.byref(ok), ctypes.byref(n)))
+        self._sizes[ok.value] = (n.value, 0)
+        return ok.value
+
+    def segment_map(self, fine_key, coarse_key):
+        """segment map fine -> coarse (a stride-2^k descendant or the origin map) for pooling / broadcast (cached)"""
+        k = ("seg", fine_key, coarse_key)
+        sm = self._kmaps.get(k)
+        if sm is None:
+            h = _vp(None)
+            with _dev(self.device):
+                engine.check(engine.lib().lgs_manager_segment_map(self.h, fine_key, coarse_key, _stream(), ctypes.byref(h)))
+            sm = HipSegmentMap(self, h, fine_key, coarse_key)
+            self._kmaps[k] = sm
+        return sm
+
     def kernel_map(self, in_key, out_key, ks):
         k = (in_key, out_key, ks)
         km = self._kmaps.get(k)
@@ -536,6 +564,66 @@ class HipBackend:
         if key not in self._side:
             self._side[key] = torch.cuda.Stream(device=device)
         return self._side[key]
+
+    # ---- pooling / global pooling / broadcast: segmented reductions and broadcasts (lgs_seg_*)
+    POOL_OPS = {"sum": 0, "avg": 1, "max": 2, "prod": 3}
+    BCAST_OPS = {"copy": 0, "scale": 1, "add": 2, "mul": 3, "copy_x": 4}
+
+    def pool_reduce(self, sm, op, x, x2=None):
+        """-> (out [n_coarse, C], argmax int32 [n_coarse, C] for max else None).  x: [n_fine, C] (a column slice of a wider
+        row-major tensor is read in place); op "prod" reduces x * x2 (x2 the same layout as x)."""
+        _require_dev(x, "features")
+        L = engine.lib()
+        c = x.shape[1]
+        assert x.dim() == 2 and x.shape[0] == sm.n_fine, (tuple(x.shape), sm.n_fine)
+        if x.stride(1) != 1 or x.stride(0) < c or (x2 is not None and x2.stride() != x.stride()):
+            x = x.contiguous()
+            x2 = x2.contiguous() if x2 is not None else None
+        if x2 is not None:
+            assert x2.shape == x.shape and x2.dtype == x.dtype
+        dt = _dtype_code(x)
+        with _dev(x.device):
+            out = torch.empty((sm.n_coarse, c), dtype=x.dtype, device=x.device)
+            amax = torch.empty((sm.n_coarse, c), dtype=torch.int32, device=x.device) if op == "max" else None
+            wsb = L.lgs_seg_workspace_bytes(sm.h, c)
+            ws = _ws(wsb, x.device) if wsb > 0 else None
+            engine.check(L.lgs_seg_reduce(sm.h, self.POOL_OPS[op], _ptr(x), _ptr(x2), max(x.stride(0), c), c, _ptr(out), _ptr(amax),
+                                          dt, _ptr(ws), _stream()))
+        return out, amax
+
+    def pool_broadcast(self, sm, op, g, x=None, out=None, col=0):
+        """fine rows r of coarse row q: out[r] = g[q] ("copy"), g[q] / rows of q ("scale"), x[r] + g[q] ("add"), x[r] * g[q]
+        ("mul"), x[r] ("copy_x").  out: a [n_fine, >= col + C] tensor to write columns [col, col + C) of (default: a new one)."""
+        src = x if op == "copy_x" else g
+        _require_dev(src, "features")
+        L = engine.lib()
+        c = src.shape[1]
+        if g is not None:
+            g = g.contiguous()
+            assert g.shape[0] == sm.n_coarse, (tuple(g.shape), sm.n_coarse)
+        if x is not None:
+            if x.stride(1) != 1 or x.stride(0) < c:
+                x = x.contiguous()
+            assert x.shape[0] == sm.n_fine and x.shape[1] == c, (tuple(x.shape), sm.n_fine, c)
+        dt = _dtype_code(src)
+        with _dev(src.device):
+            if out is None:
+                out = torch.empty((sm.n_fine, c), dtype=src.dtype, device=src.device)
+            assert out.is_contiguous() and out.shape[0] == sm.n_fine and out.shape[1] >= col + c and out.dtype == src.dtype
+            dst = out.data_ptr() + col * out.element_size()
+            engine.check(L.lgs_seg_broadcast(sm.h, self.BCAST_OPS[op], _ptr(g), c, _ptr(x), x.stride(0) if x is not None else c,
+                                             dst, out.shape[1], dt, _stream()))
+        return out
+
+    def pool_max_backward(self, sm, dy, amax):
+        """dx [n_fine, C]: dy of each coarse row goes to the fine row that won its max, per channel"""
+        _require_dev(dy, "gradient")
+        dy = dy.contiguous()
+        c = dy.shape[1]
+        with _dev(dy.device):
+            dx = torch.empty((sm.n_fine, c), dtype=dy.dtype, device=dy.device)
+            engine.check(engine.lib().lgs_seg_max_backward(sm.h, _ptr(dy), _ptr(amax), c, _ptr(dx), _dtype_code(dy), _stream()))
+        return dx
 
     # ---- fused BN(+residual)(+ReLU): lgs_bn_forward / lgs_bn_backward
     def bn_forward(self, x, gamma, beta, eps, momentum, running_mean, running_var, residual, relu, num_batches_tracked=None,

@@ -106,6 +106,36 @@ class CoordinateManager:
             raise RuntimeError("transposed convolution needs a cached finer coordinate map; none exists for %r" % key)
         return self._key(fk)
 
+    def origin_key(self):
+        """key of the origin map (one row (b, 0, 0, 0) per batch index, ascending): where global pooling lands"""
+        if not hasattr(self._m, "origin"):
+            raise NotImplementedError("global pooling needs the HIP engine (backend %r has no origin map)" % self.backend.name)
+        return self._key(self._m.origin())
+
+    def coarser_key(self, key, stride):
+        """the map `stride` (= 2^k) times coarser than `key`: stride 2 applied k times (the maps convolutions use)"""
+        k = key
+        s = int(stride)
+        assert s >= 2 and s & (s - 1) == 0, "stride must be a power of two"
+        while s > 1:
+            k = self._key(self._m.stride2(k.id))
+            s //= 2
+        return k
+
+    def finer_key_by(self, key, stride):
+        """the cached map `stride` (= 2^k) times finer than `key`: parent_of walked k times"""
+        k = key
+        s = int(stride)
+        while s > 1:
+            k = self.finer_key(k)
+            s //= 2
+        return k
+
+    def segment_map_handle(self, fine_key, coarse_key):
+        if not hasattr(self._m, "segment_map"):
+            raise NotImplementedError("pooling and broadcast need the HIP engine (backend %r has no segment maps)" % self.backend.name)
+        return self._m.segment_map(fine_key.id, coarse_key.id)
+
     def size(self, key):
         return self._m.map_size(key.id)
 

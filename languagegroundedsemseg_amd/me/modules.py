@@ -6,6 +6,7 @@ reference relies on:
 so released checkpoints' state-dict keys/shapes load (lib/utils.py:17-45).
 """
 import math
+from enum import Enum
 
 import torch
 import torch.nn as nn
@@ -626,64 +627,301 @@ class MinkowskiLinear(nn.Module):
         return input._like(self.linear(input.F))
 
 
-class _OutOfScope(nn.Module):
-    """Placeholder for ME modules that only out-of-scope model families construct:
-    constructible (so `import models` and unrelated ctors work) but raises if executed."""
+# ------------------------------------------------------------------------------------------ pooling / broadcast
+class PoolingMode(Enum):
+    """MinkowskiEngine's pooling modes.  The three GLOBAL_*_POOLING variants of one reduction (DEFAULT / KERNEL /
+    PYTORCH_INDEX: implementation choices in ME) all run the same engine kernels here."""
+    LOCAL_SUM_POOLING = 0
+    LOCAL_AVG_POOLING = 1
+    LOCAL_MAX_POOLING = 2
+    GLOBAL_SUM_POOLING_DEFAULT = 3
+    GLOBAL_AVG_POOLING_DEFAULT = 4
+    GLOBAL_MAX_POOLING_DEFAULT = 5
+    GLOBAL_SUM_POOLING_KERNEL = 6
+    GLOBAL_AVG_POOLING_KERNEL = 7
+    GLOBAL_MAX_POOLING_KERNEL = 8
+    GLOBAL_SUM_POOLING_PYTORCH_INDEX = 9
+    GLOBAL_AVG_POOLING_PYTORCH_INDEX = 10
+    GLOBAL_MAX_POOLING_PYTORCH_INDEX = 11
 
-    def __init__(self, *args, **kwargs):
+
+def _pool_op(mode):
+    """PoolingMode -> "sum" / "avg" / "max" """
+    return mode.name.split("_")[1].lower()
+
+
+def _need_engine(what):
+    backend = get_backend()
+    if not hasattr(backend, "pool_reduce"):
+        raise RuntimeError("%s needs the HIP engine: backend %r has no pooling kernels (there is no fallback)"
+                           % (what, getattr(backend, "name", backend)))
+    return backend
+
+
+_MAX_POOL_LOG2 = 8      # coarsest target the coordinate manager counts at insert time: stride 2^8 relative to the input
+
+
+def _pow2_window(name, kernel_size, stride, dilation, kernel_generator, dimension):
+    """-> the stride s = kernel_size = 2^k of a supported local pooling window; NotImplementedError for anything else"""
+    if kernel_generator is None:
+        assert dimension is not None and dimension > 0, "dimension must be a positive integer"
+        kernel_generator = KernelGenerator(kernel_size=kernel_size, stride=stride, dilation=dilation, dimension=dimension)
+    kg = kernel_generator
+    ks, st, dil = kg.kernel_size, kg.kernel_stride, kg.kernel_dilation
+    k0 = ks[0]
+    ok = (kg.dimension == 3 and kg.region_type == RegionType.HYPER_CUBE and all(d == 1 for d in dil)
+          and all(k == k0 for k in ks) and all(t == k0 for t in st) and k0 >= 2 and k0 & (k0 - 1) == 0
+          and k0 <= (1 << _MAX_POOL_LOG2))
+    if not ok:
+        raise NotImplementedError(
+            "%s(kernel_size=%s, stride=%s, dilation=%s, dimension=%d) is not supported: the engine pools non-overlapping "
+            "windows only -- kernel_size == stride == 2^k (2, 4, ..., %d), dilation 1, HYPER_CUBE, D = 3"
+            % (name, ks, st, dil, kg.dimension, 1 << _MAX_POOL_LOG2))
+    return kg, k0
+
+
+class _SegReduceFunction(torch.autograd.Function):
+    """out[q] = sum / mean / max over the fine rows of coarse row q (lgs_seg_reduce); backward: the segmented broadcast of dy
+    (sum: copy, avg: divided by the rows of q) or, for max, dy to the arg-max row of each (q, channel)."""
+
+    @staticmethod
+    def forward(ctx, x, sm, op, backend):
+        y, amax = backend.pool_reduce(sm, op, x)
+        ctx.sm, ctx.op, ctx.backend, ctx.amax = sm, op, backend, amax
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if ctx.op == "max":
+            dx = ctx.backend.pool_max_backward(ctx.sm, dy, ctx.amax)
+        else:
+            dx = ctx.backend.pool_broadcast(ctx.sm, "copy" if ctx.op == "sum" else "scale", dy)
+        return dx, None, None, None
+
+
+class _SegCopyFunction(torch.autograd.Function):
+    """fine row r <- coarse row q of r (lgs_seg_broadcast "copy"): the unpooling of a kernel_size == stride window, where
+    each output row has exactly one contributor; backward: the segmented sum"""
+
+    @staticmethod
+    def forward(ctx, g, sm, backend):
+        ctx.sm, ctx.backend = sm, backend
+        return backend.pool_broadcast(sm, "copy", g)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ctx.backend.pool_reduce(ctx.sm, "sum", dy)[0], None, None
+
+
+class _BroadcastFunction(torch.autograd.Function):
+    """out[r] = x[r] + g[b(r)] ("add"), x[r] * g[b(r)] ("mul"), [x[r], g[b(r)]] ("cat"), g[b(r)] ("copy"); g is a global-pooled
+    tensor (one row per batch index).  d g = per-batch segmented sum of dy (of dy * x for "mul", of dy's g columns for "cat")."""
+
+    @staticmethod
+    def forward(ctx, x, g, sm, op, backend):
+        ctx.sm, ctx.op, ctx.backend = sm, op, backend
+        if op == "mul":
+            ctx.save_for_backward(x, g)
+        if op in ("add", "mul"):
+            return backend.pool_broadcast(sm, op, g, x)
+        if op == "copy":
+            return backend.pool_broadcast(sm, "copy", g)
+        ctx.cx = x.shape[1]
+        out = torch.empty((sm.n_fine, x.shape[1] + g.shape[1]), dtype=x.dtype, device=x.device)
+        backend.pool_broadcast(sm, "copy_x", None, x, out=out, col=0)
+        backend.pool_broadcast(sm, "copy", g, out=out, col=x.shape[1])
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        sm, op, be = ctx.sm, ctx.op, ctx.backend
+        dx = dg = None
+        if op == "add":
+            dx = dy if ctx.needs_input_grad[0] else None
+            dg = be.pool_reduce(sm, "sum", dy)[0] if ctx.needs_input_grad[1] else None
+        elif op == "mul":
+            x, g = ctx.saved_tensors
+            dy = dy.contiguous()
+            dx = be.pool_broadcast(sm, "mul", g, dy) if ctx.needs_input_grad[0] else None
+            dg = be.pool_reduce(sm, "prod", dy, x.contiguous())[0] if ctx.needs_input_grad[1] else None
+        elif op == "copy":
+            dg = be.pool_reduce(sm, "sum", dy)[0] if ctx.needs_input_grad[1] else None
+        else:
+            dx = dy[:, :ctx.cx] if ctx.needs_input_grad[0] else None
+            dg = be.pool_reduce(sm, "sum", dy[:, ctx.cx:])[0] if ctx.needs_input_grad[1] else None
+        return dx, dg, None, None, None
+
+
+class MinkowskiPoolingBase(MinkowskiModuleBase):
+    """Local pooling over non-overlapping 2^k windows: the output lives on the map stride 2 makes k times, the map a
+    (kernel 2, stride 2) convolution would produce, so the two outputs share their coordinate_map_key."""
+    MODE = None
+
+    def __init__(self, kernel_size=-1, stride=1, dilation=1, kernel_generator=None, dimension=None):
+        super().__init__()
+        self.kernel_generator, s = _pow2_window(self.__class__.__name__, kernel_size, stride, dilation, kernel_generator, dimension)
+        self.kernel_size = self.kernel_generator.kernel_size
+        self.stride = self.kernel_generator.kernel_stride
+        self.dilation = self.kernel_generator.kernel_dilation
+        self.dimension = self.kernel_generator.dimension
+        self.pooling_mode = self.MODE
+        self._s = s
+
+    def forward(self, input, coordinates=None):
+        assert isinstance(input, SparseTensor)
+        assert coordinates is None, "explicit output coordinates are not supported"
+        backend = _need_engine(self.__class__.__name__)
+        mgr = input.coordinate_manager
+        out_key = mgr.coarser_key(input.coordinate_map_key, self._s)
+        sm = mgr.segment_map_handle(input.coordinate_map_key, out_key)
+        y = _SegReduceFunction.apply(input.F, sm, _pool_op(self.MODE), backend)
+        return SparseTensor(y, coordinate_map_key=out_key, coordinate_manager=mgr)
+
+    def __repr__(self):
+        return "%s(kernel_size=%s, stride=%s, dilation=%s)" % (self.__class__.__name__, self.kernel_size, self.stride, self.dilation)
+
+
+class MinkowskiSumPooling(MinkowskiPoolingBase):
+    MODE = PoolingMode.LOCAL_SUM_POOLING
+
+
+class MinkowskiAvgPooling(MinkowskiPoolingBase):
+    """average over the input rows PRESENT in the window (ME's rule), not over the kernel volume"""
+    MODE = PoolingMode.LOCAL_AVG_POOLING
+
+
+class MinkowskiMaxPooling(MinkowskiPoolingBase):
+    """per-channel maximum; its gradient goes to one input row per (output row, channel): on ties the smallest row index"""
+    MODE = PoolingMode.LOCAL_MAX_POOLING
+
+
+class MinkowskiPoolingTranspose(MinkowskiModuleBase):
+    """Unpooling of a kernel_size == stride == 2^k window onto the cached map 2^k times finer (the one the matching pooling or
+    strided convolution came from).  Each output row has exactly one contributing input row, so ME's "sum of contributors /
+    their count" is a copy; the backward pass is the segmented sum."""
+
+    def __init__(self, kernel_size=-1, stride=1, dilation=1, kernel_generator=None, expand_coordinates=False, dimension=None):
+        super().__init__()
+        if expand_coordinates:
+            raise NotImplementedError("%s(expand_coordinates=True) is not supported" % self.__class__.__name__)
+        self.kernel_generator, s = _pow2_window(self.__class__.__name__, kernel_size, stride, dilation, kernel_generator, dimension)
+        self.kernel_size = self.kernel_generator.kernel_size
+        self.stride = self.kernel_generator.kernel_stride
+        self.dilation = self.kernel_generator.kernel_dilation
+        self.dimension = self.kernel_generator.dimension
+        self._s = s
+
+    def forward(self, input, coordinates=None):
+        assert isinstance(input, SparseTensor)
+        assert coordinates is None, "explicit output coordinates are not supported"
+        backend = _need_engine(self.__class__.__name__)
+        mgr = input.coordinate_manager
+        out_key = mgr.finer_key_by(input.coordinate_map_key, self._s)
+        sm = mgr.segment_map_handle(out_key, input.coordinate_map_key)
+        y = _SegCopyFunction.apply(input.F, sm, backend)
+        return SparseTensor(y, coordinate_map_key=out_key, coordinate_manager=mgr)
+
+    def __repr__(self):
+        return "%s(kernel_size=%s, stride=%s, dilation=%s)" % (self.__class__.__name__, self.kernel_size, self.stride, self.dilation)
+
+
+class MinkowskiAvgUnpooling(MinkowskiPoolingTranspose):
+    """with kernel_size == stride every output row has one contributor: the same copy as MinkowskiPoolingTranspose"""
+
+
+class MinkowskiGlobalPooling(MinkowskiModuleBase):
+    """One output row per batch index present in the input, in ascending batch order, on the manager's origin map
+    (`.C` = [b, 0, 0, 0]).  Default: average, as in ME."""
+    KIND = None
+
+    def __init__(self, mode=PoolingMode.GLOBAL_AVG_POOLING_DEFAULT):
+        super().__init__()
+        if not isinstance(mode, PoolingMode) or not mode.name.startswith("GLOBAL_"):
+            raise ValueError("%s: mode must be a global PoolingMode, got %r" % (self.__class__.__name__, mode))
+        if self.KIND is not None and _pool_op(mode) != self.KIND:
+            raise ValueError("%s: mode %s is not a global %s pooling mode" % (self.__class__.__name__, mode.name, self.KIND))
+        self.pooling_mode = mode
+
+    def forward(self, input, coordinates=None):
+        assert isinstance(input, SparseTensor)
+        assert coordinates is None, "explicit output coordinates are not supported"
+        backend = _need_engine(self.__class__.__name__)
+        mgr = input.coordinate_manager
+        out_key = mgr.origin_key()
+        sm = mgr.segment_map_handle(input.coordinate_map_key, out_key)
+        y = _SegReduceFunction.apply(input.F, sm, _pool_op(self.pooling_mode), backend)
+        return SparseTensor(y, coordinate_map_key=out_key, coordinate_manager=mgr)
+
+    def __repr__(self):
+        return "%s(mode=%s)" % (self.__class__.__name__, self.pooling_mode.name)
+
+
+class MinkowskiGlobalSumPooling(MinkowskiGlobalPooling):
+    KIND = "sum"
+
+    def __init__(self, mode=PoolingMode.GLOBAL_SUM_POOLING_DEFAULT):
+        super().__init__(mode)
+
+
+class MinkowskiGlobalAvgPooling(MinkowskiGlobalPooling):
+    KIND = "avg"
+
+    def __init__(self, mode=PoolingMode.GLOBAL_AVG_POOLING_DEFAULT):
+        super().__init__(mode)
+
+
+class MinkowskiGlobalMaxPooling(MinkowskiGlobalPooling):
+    KIND = "max"
+
+    def __init__(self, mode=PoolingMode.GLOBAL_MAX_POOLING_DEFAULT):
+        super().__init__(mode)
+
+
+class MinkowskiBroadcastBase(MinkowskiModuleBase):
+    """`module(x, g)` (ME 0.5): x a SparseTensor, g a global-pooled SparseTensor of the same manager; the output lives on x's
+    map and row i combines x[i] with g[batch(i)]."""
+    OP = None
+
+    def __init__(self):
         super().__init__()
 
-    def forward(self, *a, **k):
-        raise NotImplementedError("%s is outside the Res16UNet hot path (SURVEY.md section 8)" % self.__class__.__name__)
+    def forward(self, input, input_glob):
+        assert isinstance(input, SparseTensor) and isinstance(input_glob, SparseTensor)
+        backend = _need_engine(self.__class__.__name__)
+        mgr = input.coordinate_manager
+        if input_glob.coordinate_manager is not mgr or input_glob.coordinate_map_key != mgr.origin_key():
+            raise ValueError("%s: the second input must be a global-pooled tensor of the first input's coordinate manager"
+                             % self.__class__.__name__)
+        sm = mgr.segment_map_handle(input.coordinate_map_key, input_glob.coordinate_map_key)
+        g = input_glob.F
+        if self.OP == "copy":
+            y = _BroadcastFunction.apply(None, g, sm, "copy", backend)
+        else:
+            x = input.F
+            if x.dtype != g.dtype:
+                raise ValueError("%s: both inputs must share one dtype (%s vs %s)" % (self.__class__.__name__, x.dtype, g.dtype))
+            if self.OP != "cat" and x.shape[1] != g.shape[1]:
+                raise ValueError("%s: channel counts differ (%d vs %d)" % (self.__class__.__name__, x.shape[1], g.shape[1]))
+            y = _BroadcastFunction.apply(x, g, sm, self.OP, backend)
+        return SparseTensor(y, coordinate_map_key=input.coordinate_map_key, coordinate_manager=mgr)
+
+    def __repr__(self):
+        return self.__class__.__name__ + "()"
 
 
-class MinkowskiSumPooling(_OutOfScope):
-    pass
+class MinkowskiBroadcast(MinkowskiBroadcastBase):
+    """g[batch(i)] on x's map (x contributes its coordinates only)"""
+    OP = "copy"
 
 
-class MinkowskiAvgPooling(_OutOfScope):
-    pass
+class MinkowskiBroadcastAddition(MinkowskiBroadcastBase):
+    OP = "add"
 
 
-class MinkowskiMaxPooling(_OutOfScope):
-    pass
+class MinkowskiBroadcastMultiplication(MinkowskiBroadcastBase):
+    OP = "mul"
 
 
-class MinkowskiAvgUnpooling(_OutOfScope):
-    pass
-
-
-class MinkowskiPoolingTranspose(_OutOfScope):
-    pass
-
-
-class MinkowskiGlobalPooling(_OutOfScope):
-    pass
-
-
-class MinkowskiGlobalSumPooling(_OutOfScope):
-    pass
-
-
-class MinkowskiGlobalAvgPooling(_OutOfScope):
-    pass
-
-
-class MinkowskiGlobalMaxPooling(_OutOfScope):
-    pass
-
-
-class MinkowskiBroadcast(_OutOfScope):
-    pass
-
-
-class MinkowskiBroadcastAddition(_OutOfScope):
-    pass
-
-
-class MinkowskiBroadcastMultiplication(_OutOfScope):
-    pass
-
-
-class MinkowskiBroadcastConcatenation(_OutOfScope):
-    pass
+class MinkowskiBroadcastConcatenation(MinkowskiBroadcastBase):
+    """[x[i], g[batch(i)]] (x's channels first)"""
+    OP = "cat"

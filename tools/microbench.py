@@ -1,5 +1,5 @@
 """Per-op timings on the GPU (HIP events on torch's current stream) for the hot layer shapes.
-usage: python tools/microbench.py [scenes]"""
+usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool]"""
 import os
 import sys
 import time
@@ -296,8 +296,50 @@ def wide():
     td = timeit(lambda: km2.conv_dgrad(g, w, True), 3, 1)
     print("L1->L0 transposed 2^3 256->512 rows %7d  fwd %.3f ms (%.0f TF)  dgrad %.3f ms (%.0f TF)" % (n0, tf, 2.0 * n0 * 256 * 512 / tf / 1e9, td, 2.0 * n0 * 256 * 512 / td / 1e9))
 
+def pool():
+    """pooling / global pooling / broadcast on the 8-scene level-0 map (C = 96, bf16): us per op and the fraction of 8 TB/s on
+    algorithmic bytes (features read + written once, int32 index arrays read once, arg-max rows written / read once)"""
+    be = ME.get_backend()
+    coords, _, _ = make_batch(list(range(8)), voxel=0.02, n_target=150000)
+    c = torch.from_numpy(coords).to(DEV)
+    C, e = 96, 2
+    x = ME.SparseTensor(torch.randn(c.shape[0], C, device=DEV).bfloat16(), c)
+    m, k0 = x.coordinate_manager, x.coordinate_map_key
+    n0 = m.size(k0)
+    k1, k3, ko = m.coarser_key(k0, 2), m.coarser_key(k0, 8), m.origin_key()
+    n1, n3, nb = m.size(k1), m.size(k3), m.size(ko)
+    s1, s3, so = m.segment_map_handle(k0, k1), m.segment_map_handle(k0, k3), m.segment_map_handle(k0, ko)
+    f0 = x.F
+    y1 = torch.randn(n1, C, device=DEV).bfloat16()
+    y3 = torch.randn(n3, C, device=DEV).bfloat16()
+    g = torch.randn(nb, C, device=DEV).bfloat16()
+    _, amax = be.pool_reduce(s1, "max", f0)
+    torch.cuda.synchronize()
+    peak = 8e12
+    print("level 0: %d rows, level 1: %d, level 3: %d, %d batch items; C = %d bf16" % (n0, n1, n3, nb, C))
+    rows = [
+        ("sum pool (2,2) fwd", lambda: be.pool_reduce(s1, "sum", f0), (n0 + n1) * C * e + n0 * 4 + n1 * 4),
+        ("avg pool (2,2) fwd", lambda: be.pool_reduce(s1, "avg", f0), (n0 + n1) * C * e + n0 * 4 + n1 * 4),
+        ("max pool (2,2) fwd", lambda: be.pool_reduce(s1, "max", f0), (n0 + n1) * C * e + n1 * C * 4 + n0 * 4 + n1 * 4),
+        ("sum pool (2,2) bwd", lambda: be.pool_broadcast(s1, "copy", y1), (n0 + n1) * C * e + n0 * 8),
+        ("avg pool (2,2) bwd", lambda: be.pool_broadcast(s1, "scale", y1), (n0 + n1) * C * e + n0 * 8 + n1 * 4),
+        ("max pool (2,2) bwd", lambda: be.pool_max_backward(s1, y1, amax), (n0 + n1) * C * e + n1 * C * 4 + n0 * 8),
+        ("PoolingTranspose (8,8) fwd", lambda: be.pool_broadcast(s3, "copy", y3), (n0 + n3) * C * e + n0 * 8),
+        ("PoolingTranspose (8,8) bwd", lambda: be.pool_reduce(s3, "sum", f0), (n0 + n3) * C * e + n0 * 4 + n3 * 4),
+        ("global avg pool fwd", lambda: be.pool_reduce(so, "avg", f0), (n0 + nb) * C * e + n0 * 4),
+        ("global avg pool bwd", lambda: be.pool_broadcast(so, "scale", g), (n0 + nb) * C * e + n0 * 8),
+        ("broadcast mul fwd", lambda: be.pool_broadcast(so, "mul", g, f0), (2 * n0 + nb) * C * e + n0 * 8),
+        ("broadcast mul bwd (d g)", lambda: be.pool_reduce(so, "prod", f0, f0), (2 * n0 + nb) * C * e + n0 * 4),
+    ]
+    for name, fn, nbytes in rows:
+        t = timeit(fn, 20, 3)
+        print("%-28s %8.1f us  %6.1f MB  %.2f TB/s  %.2f of 8 TB/s" % (name, t * 1e3, nbytes / 1e6, nbytes / t / 1e9, nbytes / t / 1e9 * 1e12 / peak))
+
 
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "pool":
+        pool()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "wide":
         wide()
         sys.exit(0)
