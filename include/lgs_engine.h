@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LGS_ABI_VERSION 14
+#define LGS_ABI_VERSION 15
 
 enum lgs_dtype { LGS_F32 = 0, LGS_BF16 = 1 };
 
@@ -211,6 +211,37 @@ int lgs_conv_wgrad(lgs_kmap *km, int transposed, const void *in, int cin, const 
  * it declines e.g. for >= 4 GiB at the wider stride, odd channel counts, or when forced off), else 0: the caller then
  * passes a contiguous copy.  The Python host asks before every strided weight gradient instead of letting the call fail. */
 int lgs_conv_wgrad_supports_stride(const lgs_kmap *km, int transposed, int cin, int cout, int dtype, int in_row_stride);
+
+/* lgs_debug_conv_plan: the launch plan of a forward (op 0) / dgrad (op 1) convolution on a SYNTHETIC kernel map given by plain
+ * integers, plus what the four public queries answer for that map.  No HIP call and no table is read, so it runs without a GPU
+ * (tests/test_conv_plan_cpu.py holds the plan to a recorded table and checks that the workspace regions are sound).        */
+typedef struct lgs_conv_plan_view {
+  int64_t n_pad, n_in, n_out;
+  int KS, K;                                /* slots per position, weight matrices */
+  int has_nbr, has_tile_k, has_out_row;     /* which tables the view carries (a view with nbr and KS > 1 also has mask64) */
+} lgs_conv_plan_view;
+typedef struct lgs_conv_plan_query {
+  lgs_conv_plan_view fwd, bwd;
+  int ks;                                   /* kernel size of the map: 1 / 2 / 3 */
+  int op, transposed, cin, cout, dtype;
+  int epilogue;                             /* 0 none, 1 BatchNorm statistics, 2 accumulate */
+} lgs_conv_plan_query;
+typedef struct lgs_conv_plan_region { int64_t offset, bytes; } lgs_conv_plan_region;
+typedef struct lgs_conv_plan_info {
+  int path;                                 /* 0 empty map, 1 k_pointwise, 2 k_pointwise_f32, 3 k_conv_wide, 4 k_conv_gather */
+  int tile_id, sc, wb, tm;                  /* tile configuration of the packed image (whichever path runs) */
+  int nc, nb_total, ncp, nbp, gc, wld;
+  int64_t total;                            /* uint4 of the packed image */
+  int pad_input, scratch_out, packed_ext_ok, split, bn_rows, can_accumulate;
+  int64_t grid_x; int grid_y, grid_z;       /* k_conv_gather launches only, else 0 */
+  lgs_conv_plan_region packed, padded_in, scratch, bias, partials;
+  int64_t bytes_total;
+  /* the public queries on the same map */
+  int64_t workspace_bytes;
+  int q_bn_partial_rows, q_can_accumulate;
+  lgs_pack_desc pack_desc;
+} lgs_conv_plan_info;
+int lgs_debug_conv_plan(const lgs_conv_plan_query *q, lgs_conv_plan_info *out);
 
 /* ---- fused batch-norm / ReLU / residual ------------------------------------------------------
  * replaces ME.MinkowskiBatchNorm (.bn = nn.BatchNorm1d over all rows) + MinkowskiReLU + `out += residual`

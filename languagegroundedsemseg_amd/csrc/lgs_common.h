@@ -108,7 +108,6 @@ __device__ inline float ld_elem(const bf16_t *p) { return bf16_to_f32(*p); }
 #endif
 
 int64_t wgrad_workspace_bytes(const lgs_kmap *km, int cin, int cout, int dtype);
-// lgs_conv_wide.hip: 2-D blocked forward / dgrad for >= 256 output channels (bf16); same packed weight image as k_conv_gather's wide tile
 // 1x1 stride-1 convolutions of the big maps as a streaming GEMM (lgs_pointwise.hip)
 bool pointwise_supported(const View &v, int K, int g_real, int o_real, int64_t in_ld);
 int launch_pointwise(const View &v, const void *in, int64_t in_ld, int g_real, const float *w, int cin_w, int cout_w, int transposed,
@@ -116,6 +115,7 @@ int launch_pointwise(const View &v, const void *in, int64_t in_ld, int g_real, c
 bool pointwise_f32_supported(const View &v, int K, int g_real, int o_real, int64_t in_ld);
 int launch_pointwise_f32(const View &v, const void *in, int64_t in_ld, int g_real, const float *w, int cin_w, int cout_w, int transposed,
                          int o_real, const float *bias, void *out, hipStream_t s);
+// lgs_conv_wide.hip: 2-D blocked forward / dgrad for >= 256 output channels (bf16); same packed weight image as k_conv_gather's wide tile
 int launch_conv_wide(const View &v, const void *in, int cin_real, int in_ld, const void *wp, int nb_total, int ncp, int nbp, int K,
                      void *out, int cout_real, const float *bias, int gc64, hipStream_t s);
 // lgs_wgrad_wide.hip: per-offset dense GEMM over compacted pair lists for >= 256 x 256 channel 3^3 weight gradients (bf16)

@@ -65,9 +65,6 @@ template <typename T> __device__ inline void mma16(f32x16 &acc, const u32x4 &w, 
 template <> __device__ inline void mma16<bf16_t>(f32x16 &acc, const u32x4 &w, const u32x4 &f) {
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, f), acc, 0, 0, 0);
 }
-__device__ inline void mma_bf16(f32x16 &acc, const u32x4 &w, const u32x4 &f) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, f), acc, 0, 0, 0);
-}
 // one fp32 value -> its three bf16 pieces as the upper halves of three dwords (hi + mid + lo == x exactly)
 __device__ inline void split3(uint32_t x, uint32_t &hi, uint32_t &mid, uint32_t &lo) {
   hi = x & 0xffff0000u;
@@ -88,7 +85,6 @@ __device__ inline void split8(const u32x4 &a, const u32x4 &b, u32x4 &hi, u32x4 &
   lo = u32x4{LGS_PK(l, 0), LGS_PK(l, 1), LGS_PK(l, 2), LGS_PK(l, 3)};
 #undef LGS_PK
 }
-template <> __device__ inline void mma16<f32s_t>(f32x16 &acc, const u32x4 &w, const u32x4 &f) { (void)acc; (void)w; (void)f; }   // (unused: see compute)
 template <> __device__ inline void mma16<float>(f32x16 &acc, const u32x4 &w, const u32x4 &f) {
   acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(w.x), __uint_as_float(f.x), acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(w.y), __uint_as_float(f.y), acc, 0, 0, 0);
@@ -179,7 +175,6 @@ __global__ void k_pack_weights_batch(const lgs_pack_desc *__restrict__ descs) {
   else dst[idx] = pack_one<float>(e.weight, e.K, e.cin_w, e.cout_w, e.transposed, e.mirror, e.g_real, e.o_real, e.ncp, e.nbp, idx);
 }
 
-// (descriptor dtype code of a split-fp32 image: internal to the packed-image descriptors, never a tensor dtype)
 // pad rows [n, c] -> [n, cpad] (zero fill) for channel counts that are not a multiple of the load width
 template <typename T>
 __global__ void k_pad_rows(const T *__restrict__ src, int64_t n, int c, int cpad, T *__restrict__ dst) {
@@ -235,7 +230,10 @@ template <typename T> __device__ inline float stored_value(float x);
 template <> __device__ inline float stored_value<f32s_t>(float x) { return x; }
 template <> __device__ inline float stored_value<float>(float x) { return x; }
 template <> __device__ inline float stored_value<bf16_t>(float x) { return bf16_to_f32(f32_to_bf16(x)); }
-template <typename T> __device__ inline float sq16(const u32x4 &f, float s);
+template <typename T> __device__ inline float sq16(const u32x4 &f, float s) {   // four fp32 (float and f32s_t rows)
+  const float a = __uint_as_float(f.x), b = __uint_as_float(f.y), c = __uint_as_float(f.z), d = __uint_as_float(f.w);
+  return fmaf(d, d, fmaf(c, c, fmaf(b, b, fmaf(a, a, s))));
+}
 template <> __device__ inline float sq16<bf16_t>(const u32x4 &f, float s) {
   // two bf16 per dword: the high one IS an fp32 with the low half masked off, the low one is a 16-bit shift away
   const uint32_t w[4] = {f.x, f.y, f.z, f.w};
@@ -245,14 +243,6 @@ template <> __device__ inline float sq16<bf16_t>(const u32x4 &f, float s) {
     s = fmaf(hi, hi, fmaf(lo, lo, s));
   }
   return s;
-}
-template <> __device__ inline float sq16<f32s_t>(const u32x4 &f, float s) {
-  const float a = __uint_as_float(f.x), b = __uint_as_float(f.y), c = __uint_as_float(f.z), d = __uint_as_float(f.w);
-  return fmaf(d, d, fmaf(c, c, fmaf(b, b, fmaf(a, a, s))));
-}
-template <> __device__ inline float sq16<float>(const u32x4 &f, float s) {
-  const float a = __uint_as_float(f.x), b = __uint_as_float(f.y), c = __uint_as_float(f.z), d = __uint_as_float(f.w);
-  return fmaf(d, d, fmaf(c, c, fmaf(b, b, fmaf(a, a, s))));
 }
 
 // ------------------------------------------------------------------------------------ forward / dgrad
@@ -460,36 +450,36 @@ __global__ __launch_bounds__(WM *WN * 64) void k_conv_gather(View v, const T *__
             u32x4 fh, fm, fl;
             split8(F[rb][2 * tt], F[rb][2 * tt + 1], fh, fm, fl);
 #pragma unroll
-            for (int nb = 0; nb < NCB; ++nb) mma_bf16(acc[rb][nb], wf3[2][nb], fh);
+            for (int nb = 0; nb < NCB; ++nb) mma16<bf16_t>(acc[rb][nb], wf3[2][nb], fh);
 #pragma unroll
-            for (int nb = 0; nb < NCB; ++nb) mma_bf16(acc[rb][nb], wf3[0][nb], fl);
+            for (int nb = 0; nb < NCB; ++nb) mma16<bf16_t>(acc[rb][nb], wf3[0][nb], fl);
 #pragma unroll
-            for (int nb = 0; nb < NCB; ++nb) mma_bf16(acc[rb][nb], wf3[1][nb], fm);
+            for (int nb = 0; nb < NCB; ++nb) mma16<bf16_t>(acc[rb][nb], wf3[1][nb], fm);
 #pragma unroll
-            for (int nb = 0; nb < NCB; ++nb) mma_bf16(acc[rb][nb], wf3[1][nb], fh);
+            for (int nb = 0; nb < NCB; ++nb) mma16<bf16_t>(acc[rb][nb], wf3[1][nb], fh);
 #pragma unroll
-            for (int nb = 0; nb < NCB; ++nb) mma_bf16(acc[rb][nb], wf3[0][nb], fm);
+            for (int nb = 0; nb < NCB; ++nb) mma16<bf16_t>(acc[rb][nb], wf3[0][nb], fm);
 #pragma unroll
-            for (int nb = 0; nb < NCB; ++nb) mma_bf16(acc[rb][nb], wf3[0][nb], fh);
+            for (int nb = 0; nb < NCB; ++nb) mma16<bf16_t>(acc[rb][nb], wf3[0][nb], fh);
           }
         }
       }
-      return;
-    }
-    // all weight fragments of the chunk are requested up front: the LDS latency of step t+1 hides under the
-    // MFMAs of step t (the compiler otherwise waits lgkmcnt(0) in front of every MFMA triple)
-    u32x4 wf[LD][NCB];
+    } else {
+      // all weight fragments of the chunk are requested up front: the LDS latency of step t+1 hides under the
+      // MFMAs of step t (the compiler otherwise waits lgkmcnt(0) in front of every MFMA triple)
+      u32x4 wf[LD][NCB];
 #pragma unroll
-    for (int t = 0; t < LD; ++t)
+      for (int t = 0; t < LD; ++t)
 #pragma unroll
-      for (int nb = 0; nb < NCB; ++nb) wf[t][nb] = wl[(nb * LD + t) * 64];
+        for (int nb = 0; nb < NCB; ++nb) wf[t][nb] = wl[(nb * LD + t) * 64];
 #pragma unroll
-    for (int t = 0; t < LD; ++t) {
+      for (int t = 0; t < LD; ++t) {
 #pragma unroll
-      for (int rb = 0; rb < RB; ++rb) {
-        if (act & (1u << rb)) {
+        for (int rb = 0; rb < RB; ++rb) {
+          if (act & (1u << rb)) {
 #pragma unroll
-          for (int nb = 0; nb < NCB; ++nb) mma16<T>(acc[rb][nb], wf[t][nb], F[rb][t]);
+            for (int nb = 0; nb < NCB; ++nb) mma16<T>(acc[rb][nb], wf[t][nb], F[rb][t]);
+          }
         }
       }
     }
@@ -838,51 +828,62 @@ stats:
   }
 }
 
-// rows that no position of the view writes must still be defined: the forward output of a strided
-// map always covers every row, but a grouped view's padding never does -- nothing to do there.
-
 // ------------------------------------------------------------------------------------ host side
+
+// THE tile table of k_conv_gather: id -> chunks per weight slab, column blocks and positions per workgroup of the
+// <RB, NCB, WM, WN, SC, D> instance launch_gather runs for it (every LGS_LAUNCH row static_asserts against its entry).
+// SC = chunks per weight slab (sized to ~6-8 staging registers per thread), D = depth of the gather ring.
+struct GatherCfg { int id, sc, wb, tm; };   // tm = positions per workgroup tile
+constexpr GatherCfg tile_of(int id, bool f32) {
+  switch (id) {
+    case 0: return {0, f32 ? 2 : 4, 1, 256};
+    case 1: return {1, f32 ? 2 : 4, 2, 256};
+    case 2: return {2, f32 ? 2 : 4, 3, 256};
+    case 3: return {3, f32 ? 1 : 2, 4, 256};     // 256 positions x 128 channels (64 x 128 per wave)
+    case 4: return {4, f32 ? 2 : 4, 1, 64};
+    case 5: return {5, f32 ? 2 : 4, 2, 64};
+    case 6: return {6, f32 ? 1 : 2, 7, 128};
+    case 7: return {7, 2, 4, 128};               // ids 7 .. 13, 16, 17: bf16 only.  128 positions x 128 channels (32 x 128 per wave)
+    case 8: return {8, 4, 2, 128};
+    case 9: return {9, 4, 4, 64};
+    case 10: return {10, 4, 2, 64};
+    case 11: return {11, 4, 4, 64};
+    case 12: return {12, 8, 2, 128};             // as 8 with 8-chunk (256-channel) weight slabs: half the slab barriers
+    case 13: return {13, 8, 4, 128};             // 128 positions x 128 channels, 8-chunk slabs
+    default: return {id, 2, 8, 256};             // 16: eight waves of 32 positions x 256 channels; 17: k_conv_wide on the same image
+  }
+}
 
 // Tile choice: 256 positions x up to 128 channels when the map fills the chip, otherwise 128-position x 64-channel
 // tiles, one 32 x 64 block per wave (coarse levels: few rows, many channels).
-// SC = chunks per weight slab (sized to ~6-8 staging registers per thread), D = depth of the gather ring.
-struct GatherCfg { int id, sc, wb, tm; };   // tm = positions per workgroup tile
 template <typename T>
-GatherCfg gather_cfg(const View &v, int nb_total) {
+int gather_id(const View &v, int nb_total) {
   constexpr bool kF32 = (sizeof(T) == 4);
-  const bool big = v.n_pad >= 256 * 256;
-  if (big) {
+  if (v.n_pad >= 256 * 256) {
     // 5..7 blocks (e.g. the 200 classes / 200 CLIP anchors = 7 blocks): one 128-position tile spans ALL output
     // channels, so the [N, C] feature matrix is streamed exactly once (dense GEMM with a small N)
-    if (nb_total >= 5 && nb_total <= 7 && v.nbr == nullptr && tune(T_HEAD_TILE) == 0) return {6, kF32 ? 1 : 2, 7, 128};
-    if (nb_total == 1) return {0, kF32 ? 2 : 4, 1, 256};
-    if (nb_total == 2) return {1, kF32 ? 2 : 4, 2, 256};
-    if (nb_total == 3 || (nb_total % 3 == 0 && nb_total % 4 != 0)) return {2, kF32 ? 2 : 4, 3, 256};
+    if (nb_total >= 5 && nb_total <= 7 && v.nbr == nullptr && tune(T_HEAD_TILE) == 0) return 6;
+    if (nb_total == 1) return 0;
+    if (nb_total == 2) return 1;
+    if (nb_total == 3 || (nb_total % 3 == 0 && nb_total % 4 != 0)) return 2;
     // wide outputs (>= 256 channels, e.g. the 512-d CLIP representation model): id 17 = the 2-D blocked LDS-DMA kernel of
     // lgs_conv_wide.hip (round 3; L0 512 -> 512: 9.4 ms); id 16 = eight waves of 32 positions x 256 channels on this kernel
     // (round 2: 12.0 ms; still what 1x1 layers below 512 output channels and CONV_WIDE=0 take)
     if (!kF32 && tune(T_CONV_WIDE) != 0 && (nb_total % 8 == 0 || nb_total >= 16) && !(v.KS == 1 && v.nbr == nullptr && nb_total < 16))
-      return {17, 2, 8, 256};
-    if (!kF32 && nb_total % 8 == 0) return {16, 2, 8, 256};
-    if (!kF32) return {7, 2, 4, 128};   // bf16: 128-position tiles, 4 column blocks per wave at 3 waves/SIMD
-    return {3, kF32 ? 1 : 2, 4, 256};
+      return 17;
+    if (!kF32 && nb_total % 8 == 0) return 16;
+    return kF32 ? 3 : 7;                // bf16: 128-position tiles, 4 column blocks per wave at 3 waves/SIMD
   }
-  if (nb_total == 1) return {4, kF32 ? 2 : 4, 1, 64};
+  if (nb_total == 1) return 4;
+  if (kF32) return 5;
   const int small_override = (int)tune(T_SMALL_CFG);  // tuning knob
-  if (!kF32 && small_override == 5) return {5, 4, 2, 64};
-  if (!kF32 && small_override == 9) return {9, 4, 4, 64};
-  if (!kF32 && small_override == 10) return {10, 4, 2, 64};
-  if (!kF32 && small_override == 11) return {11, 4, 4, 64};
-  if (!kF32 && small_override == 3 && nb_total % 4 == 0) return {3, 2, 4, 256};     // 256 positions x 128 channels (64 x 128 per wave)
-  if (!kF32 && small_override == 7 && nb_total % 4 == 0) return {7, 2, 4, 128};     // 128 positions x 128 channels (32 x 128 per wave)
-  if (!kF32 && small_override == 12) return {12, 8, 2, 128};
-  if (!kF32 && small_override == 13) return {13, 8, 4, 128};
+  if (small_override == 5 || (small_override >= 9 && small_override <= 13)) return small_override;
+  if ((small_override == 3 || small_override == 7) && nb_total % 4 == 0) return small_override;
   // 3^3 maps of 16 k+ positions with 256 output channels (level 3 of the 8-scene batch): 128 positions x 128 channels per workgroup
   // gathers every row half as often as the 64-channel tile (stand-alone 256 -> 256 at 19.6 k rows: 0.127 vs 0.147 ms; the other
   // coarse shapes -- level 3 128 -> 128, level 4 256 -> 256 at 5 k rows -- are faster on the small tile, r04_experiments.txt)
-  if (!kF32 && nb_total == 8 && v.KS > 1 && v.n_pad >= 16384) return {7, 2, 4, 128};
-  if (!kF32) return {8, 4, 2, 128};   // measured best on the other L3/L4 shapes (tools/microbench.py coarse): 128 positions x 64 channels
-  return {5, 2, 2, 64};
+  if (nb_total == 8 && v.KS > 1 && v.n_pad >= 16384) return 7;
+  return 8;   // measured best on the other L3/L4 shapes (tools/microbench.py coarse): 128 positions x 64 channels
 }
 
 // out = p0 + p1 + p2 (+ bias), fixed order; 4 elements per thread
@@ -913,78 +914,129 @@ __global__ void k_sum_partials(const float *__restrict__ part, int64_t n4, int64
 }
 
 constexpr int64_t kSplitMaxBytes = 16ll << 20;   // fp32 partial images of the slot split (larger ones cost more than the split gains)
-inline int64_t split_partial_bytes(int K, int64_t n_out, int o_real) {
-  if (K != 27 || n_out <= 0) return 0;
-  const int64_t b = 3 * n_out * (int64_t)o_real * 4;
-  return b <= kSplitMaxBytes ? align256(b) : 0;
+
+// ------------------------------------------------------------------------------------ the launch plan
+// Everything a forward / dgrad launch decides on the host, computed ONCE by conv_plan() from the view, the channel counts, the
+// kernel instance, the requested epilogue and the tuning table: which kernel runs, its tile and grid, the layout of the packed
+// weight image, whether the launch takes the slot split, and where every piece of the workspace lies.  The op, the launcher and
+// every public query (workspace size, statistic rows, pack descriptor, accumulate) read this struct and nothing else, so they
+// cannot disagree.  It is the plan part of lgs_conv_plan_info, which lgs_debug_conv_plan hands out as it stands.
+using ConvPlan = lgs_conv_plan_info;
+enum ConvPath { kPathEmpty = 0, kPathPointwise = 1, kPathPointwiseF32 = 2, kPathWide = 3, kPathGather = 4 };
+// requested epilogue: BatchNorm statistics and accumulation exist on k_conv_gather only (they keep a 1x1 layer off the pointwise
+// kernels); kEpiF32Out = fp32 output with a row scale (the CLIP similarity), which also never splits
+enum ConvEpi { kEpiNone = 0, kEpiBnStats = 1, kEpiAccum = 2, kEpiF32Out = 3 };
+
+// layout of a packed weight image: K matrices of nc x nb_total 32 x 32 blocks, rounded up to whole slabs and column tiles
+inline void plan_image(ConvPlan &p, const GatherCfg &cfg, int K, int g_real, int o_real, int wld) {
+  p.tile_id = cfg.id; p.sc = cfg.sc; p.wb = cfg.wb; p.tm = cfg.tm;
+  p.nc = pad32(g_real) / 32; p.nb_total = pad32(o_real) / 32;
+  p.ncp = (p.nc + cfg.sc - 1) / cfg.sc * cfg.sc;
+  p.nbp = (p.nb_total + cfg.wb - 1) / cfg.wb * cfg.wb;
+  p.wld = wld;
+  p.total = (int64_t)K * p.ncp * p.nbp * wld * 64;
 }
 
-// epilogue options of one launch: a slot-split launch writes fp32 partial images (statistics / accumulation happen in
-// k_sum_partials or not at all)
-inline BnEpi bn_epi(const BnEpi *bn, bool did_split) {
-  BnEpi e = (bn && !did_split) ? *bn : BnEpi();
-  return e;
+// T = storage type of the tensors, TK = the kernel instance that multiplies them (TK = f32s_t: fp32 tensors, split-bf16 products).
+// Pure: no HIP call, no table of the view is read.
+template <typename T, typename TK = T>
+ConvPlan conv_plan(const View &v, int K, int g_real, int o_real, ConvEpi epi, int64_t in_ld = 0) {
+  constexpr int EPL = Tr<T>::EPL;
+  ConvPlan p = {};
+  plan_image(p, tile_of(gather_id<TK>(v, pad32(o_real) / 32), sizeof(TK) == 4), K, g_real, o_real, Tr<TK>::WLD);
+  // channel groups of the reduction (see the kernel): rows wider than 8 chunks (256 channels) are walked in 4-chunk groups
+  p.gc = p.nc > 8 ? 4 : p.nc;
+  p.bytes_total = 256;             // never an empty buffer: the entry points insist on a workspace pointer
+  if (v.n_pad == 0) return p;      // the maps of an empty batch: no row to write, nothing is packed
+  p.pad_input = g_real % EPL != 0;      // e.g. the 3-channel colour input of conv0p1s1: rows padded to one 16-byte piece
+  p.scratch_out = o_real % 4 != 0;      // rows are written in 4-channel groups: odd widths go through a 4-aligned scratch image
+  p.packed_ext_ok = !p.pad_input && !p.scratch_out;     // a caller-owned packed image (and a strided input) can be used
+  // 1x1 layers of the big maps: streaming GEMMs with persistent workgroups (lgs_pointwise.hip), no packed image, no workspace;
+  // fp32 on the exact-fp32 MFMA, whichever instance multiplies the 3^3 layers
+  const int64_t ld = in_ld > 0 ? in_ld : g_real;
+  if (epi == kEpiNone && std::is_same<TK, bf16_t>::value && pointwise_supported(v, K, g_real, o_real, ld)) { p.path = kPathPointwise; return p; }
+  if (epi == kEpiNone && std::is_same<T, float>::value && o_real % 4 == 0 && pointwise_f32_supported(v, K, g_real, o_real, ld)) { p.path = kPathPointwiseF32; return p; }
+  p.path = p.tile_id == 17 ? kPathWide : kPathGather;
+  const int o4 = (o_real + 3) / 4 * 4;
+  if (p.path == kPathGather) {
+    p.grid_x = v.n_pad / p.tm; p.grid_y = (p.nb_total + p.wb - 1) / p.wb;
+    // Slot split: bf16 storage only.  The fp32 path is the parity mode and keeps ONE accumulator per output (a different summation
+    // order moves results by ~1e-7, which BatchNorm over a handful of coarse rows with near-zero variance amplifies into
+    // ReLU gate flips against the oracle -- measured on the 14A fixture).  The chip holds >= 512 of these workgroups.
+    p.split = tune(T_CONV_SPLIT) != 0 && sizeof(TK) == 2 && epi != kEpiF32Out && !p.scratch_out && v.KS > 1 && K == 27 &&
+              v.n_out > 0 && 3 * v.n_out * (int64_t)o_real * 4 <= kSplitMaxBytes && p.grid_x * p.grid_y < 600;
+    p.grid_z = p.split ? 3 : 1;
+    // rows of BatchNorm statistics the launch writes (= its position tiles): a split launch sums partial images afterwards and
+    // the scratch route unpads them, neither has the statistics; the same two and the wide kernel cannot accumulate
+    p.bn_rows = (p.split || p.scratch_out) ? 0 : (int)p.grid_x;
+    p.can_accumulate = !p.scratch_out;
+  }
+  // workspace: the regions in the order they are taken, each 256-byte aligned
+  int64_t used = 0;
+  auto take = [&](int64_t bytes) { const lgs_conv_plan_region r = {used, align256(bytes)}; used += r.bytes; return r; };
+  p.packed = take(p.total * 16);
+  if (p.pad_input) p.padded_in = take(v.n_in * (int64_t)((g_real + EPL - 1) / EPL * EPL) * (int64_t)sizeof(T));
+  if (p.scratch_out) {    // + the bias padded to the scratch width (e.g. the 3-channel offset head of the instance-segmentation model)
+    p.scratch = take(v.n_out * (int64_t)o4 * (int64_t)sizeof(T));
+    p.bias = take(4 * (int64_t)o4);
+  }
+  if (p.split) p.partials = take(3 * v.n_out * (int64_t)o_real * 4);
+  if (used > p.bytes_total) p.bytes_total = used;
+  return p;
 }
 
 template <typename T>
-int launch_gather(const View &v, const GatherCfg &cfg, const T *in, int cin_real, int nc, const uint4 *wp,
-                  int nb_total, int ncp, int nbp, int K, T *out, int cout_real, const float *bias, hipStream_t s,
-                  float *out_f32 = nullptr, const float *row_scale = nullptr, float *zpartial = nullptr,
-                  const BnEpi *bn = nullptr, int *bn_rows = nullptr, int in_ld = 0) {
+int launch_gather(const View &v, const ConvPlan &pl, const T *in, int cin_real, const uint4 *wp, int K, T *out, int cout_real,
+                  const float *bias, hipStream_t s, float *out_f32 = nullptr, const float *row_scale = nullptr,
+                  float *zpartial = nullptr, const BnEpi *bn = nullptr, int in_ld = 0) {
   if (v.n_pad == 0) return 0;
-  constexpr int LDc = Tr<T>::WLD;
+  const int nc = pl.nc, nb_total = pl.nb_total, ncp = pl.ncp, nbp = pl.nbp, gc = pl.gc;
   const uint64_t in_bytes64 = (uint64_t)v.n_in * (uint64_t)(in_ld > 0 ? in_ld : cin_real) * sizeof(T);
-  const uint64_t w_bytes64 = (uint64_t)K * ncp * nbp * LDc * 64 * 16;
+  const uint64_t w_bytes64 = (uint64_t)pl.total * 16;
   LGS_REQUIRE(in_bytes64 < 0xfffff000ull && w_bytes64 < 0xfffff000ull,
               "sparse conv: a feature or weight tensor of 4 GiB or more is beyond the 32-bit buffer-descriptor path");
   const unsigned in_bytes = (unsigned)in_bytes64, w_bytes = (unsigned)w_bytes64;
-  // bf16 storage only: the fp32 path is the parity mode and keeps ONE accumulator per output (a different summation
-  // order moves results by ~1e-7, which BatchNorm over a handful of coarse rows with near-zero variance amplifies into
-  // ReLU gate flips against the oracle -- measured on the 14A fixture)
-  const bool no_split = tune(T_CONV_SPLIT) == 0;   // debugging knob
-  const bool can_split = !no_split && sizeof(T) == 2 && zpartial && !out_f32 && v.KS > 1 && K == 27 && split_partial_bytes(K, v.n_out, cout_real) > 0;
-  const int64_t zstride = v.n_out * (int64_t)cout_real;
-  bool did_split = false;
-  constexpr bool kF32 = (sizeof(T) == 4);
-  // channel groups of the reduction (see the kernel): rows wider than 8 chunks (256 channels) are walked in 4-chunk groups
-  const int gc = nc > 8 ? 4 : nc;
-#define LGS_LAUNCH(RB, NCB, WM, WN, SC, D)                                                                        \
-  do {                                                                                                            \
-    dim3 grid((unsigned)(v.n_pad / (WM * RB * 32)), (unsigned)((nb_total + WN * NCB - 1) / (WN * NCB)));         \
-    did_split = can_split && (int64_t)grid.x * grid.y < 600;   /* the chip holds >= 512 of these workgroups */    \
-    if (did_split) grid.z = 3;                                                                                    \
-    LGS_KLAUNCH((k_conv_gather<T, RB, NCB, WM, WN, SC, D>), grid, dim3(WM *WN * 64), 0, s, v, in, cin_real, nc,    \
-                       reinterpret_cast<const u32x4 *>(wp), nb_total, ncp, nbp, out, cout_real, did_split ? nullptr : bias, \
-                       did_split ? zpartial : out_f32, row_scale, in_bytes, w_bytes, zstride, ClipEpi(),           \
-                       bn_epi(bn, did_split), gc, in_ld > 0 ? in_ld : cin_real);                                  \
-    if (bn_rows) *bn_rows = did_split ? 0 : (int)grid.x;                                                          \
-  } while (0)
-  if (cfg.id == 17) {
+  if (pl.path == kPathWide) {
     LGS_REQUIRE(sizeof(T) == 2 && !out_f32 && !row_scale && !(bn && bn->partial), "wide conv: bf16 feature output only (internal error)");
     LGS_REQUIRE(!(bn && bn->accum), "wide conv: no accumulating epilogue (lgs_conv_dgrad_can_accumulate says so)");
-    if (bn_rows) *bn_rows = 0;
     return launch_conv_wide(v, in, cin_real, in_ld > 0 ? in_ld : cin_real, wp, nb_total, ncp, nbp, K, out, cout_real, bias,
                             gc >= nc ? 0 : (gc + 1) / 2, s);
   }
-  switch (cfg.id) {
-    case 0: LGS_LAUNCH(2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
-    case 1: LGS_LAUNCH(2, 2, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
-    case 2: LGS_LAUNCH(2, 3, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
-    case 3: LGS_LAUNCH(2, 4, 4, 1, (kF32 ? 1 : 2), (kF32 ? 2 : 3)); break;
-    case 4: LGS_LAUNCH(1, 1, 2, 1, (kF32 ? 2 : 4), (kF32 ? 4 : 8)); break;
-    case 6: LGS_LAUNCH(1, 7, 4, 1, (kF32 ? 1 : 2), (kF32 ? 3 : 4)); break;
-    case 7: if constexpr (!kF32) LGS_LAUNCH(1, 4, 4, 1, 2, 4); break;      // ids 7 .. 13, 16: bf16 only (gather_cfg)
-    case 16: if constexpr (!kF32) LGS_LAUNCH(1, 8, 8, 1, 2, 4); break;
-    case 8: if constexpr (!kF32) LGS_LAUNCH(1, 2, 4, 1, 4, 6); break;
-    case 9: if constexpr (!kF32) LGS_LAUNCH(1, 2, 2, 2, 4, 6); break;
-    case 10: if constexpr (!kF32) LGS_LAUNCH(1, 2, 2, 1, 4, 6); break;
-    case 11: if constexpr (!kF32) LGS_LAUNCH(1, 4, 2, 1, 4, 6); break;
-    case 12: if constexpr (!kF32) LGS_LAUNCH(1, 2, 4, 1, 8, 6); break;     // as 8 with 8-chunk (256-channel) weight slabs: half the slab barriers
-    case 13: if constexpr (!kF32) LGS_LAUNCH(1, 4, 4, 1, 8, 4); break;     // 128 positions x 128 channels, 8-chunk slabs
-    default: LGS_LAUNCH(1, 1, 2, 2, (kF32 ? 2 : 4), (kF32 ? 4 : 8)); break;
+  // a slot-split launch writes fp32 partial images: bias and accumulation happen in k_sum_partials, statistics not at all
+  const bool split = pl.split;
+  LGS_REQUIRE(!split || zpartial, "sparse conv: a split launch without its partial images (internal error)");
+  const int64_t zstride = v.n_out * (int64_t)cout_real;
+  const BnEpi be = (bn && !split) ? *bn : BnEpi();
+  const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)pl.grid_z);
+  constexpr bool kF32 = (sizeof(T) == 4);
+#define LGS_LAUNCH(ID, RB, NCB, WM, WN, SC, D)                                                                            \
+  do {                                                                                                                    \
+    constexpr GatherCfg t = tile_of(ID, kF32);                                                                            \
+    static_assert(t.sc == SC && t.wb == WN * NCB && t.tm == WM * RB * 32, "tile_of() and the launched instance disagree"); \
+    LGS_KLAUNCH((k_conv_gather<T, RB, NCB, WM, WN, SC, D>), grid, dim3(WM *WN * 64), 0, s, v, in, cin_real, nc,            \
+                       reinterpret_cast<const u32x4 *>(wp), nb_total, ncp, nbp, out, cout_real, split ? nullptr : bias,   \
+                       split ? zpartial : out_f32, row_scale, in_bytes, w_bytes, zstride, ClipEpi(), be, gc,              \
+                       in_ld > 0 ? in_ld : cin_real);                                                                     \
+  } while (0)
+  switch (pl.tile_id) {
+    case 0: LGS_LAUNCH(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
+    case 1: LGS_LAUNCH(1, 2, 2, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
+    case 2: LGS_LAUNCH(2, 2, 3, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
+    case 3: LGS_LAUNCH(3, 2, 4, 4, 1, (kF32 ? 1 : 2), (kF32 ? 2 : 3)); break;
+    case 4: LGS_LAUNCH(4, 1, 1, 2, 1, (kF32 ? 2 : 4), (kF32 ? 4 : 8)); break;
+    case 6: LGS_LAUNCH(6, 1, 7, 4, 1, (kF32 ? 1 : 2), (kF32 ? 3 : 4)); break;
+    case 7: if constexpr (!kF32) LGS_LAUNCH(7, 1, 4, 4, 1, 2, 4); break;      // ids 7 .. 13, 16: bf16 only (gather_id)
+    case 16: if constexpr (!kF32) LGS_LAUNCH(16, 1, 8, 8, 1, 2, 4); break;
+    case 8: if constexpr (!kF32) LGS_LAUNCH(8, 1, 2, 4, 1, 4, 6); break;
+    case 9: if constexpr (!kF32) LGS_LAUNCH(9, 1, 2, 2, 2, 4, 6); break;
+    case 10: if constexpr (!kF32) LGS_LAUNCH(10, 1, 2, 2, 1, 4, 6); break;
+    case 11: if constexpr (!kF32) LGS_LAUNCH(11, 1, 4, 2, 1, 4, 6); break;
+    case 12: if constexpr (!kF32) LGS_LAUNCH(12, 1, 2, 4, 1, 8, 6); break;
+    case 13: if constexpr (!kF32) LGS_LAUNCH(13, 1, 4, 4, 1, 8, 4); break;
+    default: LGS_LAUNCH(5, 1, 1, 2, 2, (kF32 ? 2 : 4), (kF32 ? 4 : 8)); break;
   }
 #undef LGS_LAUNCH
-  if (did_split) {
+  if (split) {
     const int64_t n4 = zstride / 4;
     if (n4 > 0) LGS_KLAUNCH((k_sum_partials<T>), (unsigned)((n4 + 255) / 256), 256, 0, s, zpartial, n4, zstride, bias, cout_real, out,
                                    (bn && bn->accum) ? 1 : 0);
@@ -993,118 +1045,59 @@ int launch_gather(const View &v, const GatherCfg &cfg, const T *in, int cin_real
   return 0;
 }
 
-// rows of BatchNorm statistics the forward launch of this shape writes (= its position tiles), 0 if the launch cannot
-// produce them (slot-split launches sum partial images afterwards; odd output widths go through a scratch image)
-template <typename T>
-int bn_partial_rows_t(const View &v, int K, int o_real) {
-  if (v.n_pad == 0 || o_real % 4 != 0) return 0;
-  const int nb_total = pad32(o_real) / 32;
-  const GatherCfg cfg = gather_cfg<T>(v, nb_total);
-  if (cfg.id == 17) return 0;        // the wide kernel has no statistics epilogue
-  const int64_t gx = v.n_pad / cfg.tm, gy = (nb_total + cfg.wb - 1) / cfg.wb;
-  const bool no_split = tune(T_CONV_SPLIT) == 0;
-  const bool split = sizeof(T) == 2 && !no_split && v.KS > 1 && K == 27 &&
-                     split_partial_bytes(K, v.n_out, o_real) > 0 && gx * gy < 600;
-  return split ? 0 : (int)gx;
-}
-
-// bytes of the workspace region that holds the packed weight image of a launch on this view: the image is ncp x nbp blocks
-// of the tile configuration gather_cfg picks (slabs of sc chunks, column tiles of wb blocks), which the (nc + 3) x (nb_total + 3)
-// blocks sized here before do not always cover (ids 12 / 13 pack 8-chunk slabs: 32 -> 64 is 8 x 4 = 32 blocks against 4 x 5 = 20).
-// Never smaller than that older size, so the offsets of everything behind the image only move where it did not fit.
-// lgs_conv_workspace_bytes sizes for both views of the map with the same function.
-template <typename TK>
-int64_t packed_region_bytes(const View &v, int K, int g_real, int o_real) {
-  const int nc = pad32(g_real) / 32, nb_total = pad32(o_real) / 32;
-  const GatherCfg cfg = gather_cfg<TK>(v, nb_total);
-  const int64_t ncp = (nc + cfg.sc - 1) / cfg.sc * cfg.sc, nbp = (nb_total + cfg.wb - 1) / cfg.wb * cfg.wb;
-  const int64_t legacy = (int64_t)(nc + 3) * (nb_total + 3);
-  return align256((int64_t)K * (ncp * nbp > legacy ? ncp * nbp : legacy) * Tr<TK>::WLD * 64 * 16);
-}
-
-// T = storage type of the tensors, TK = the kernel instance that multiplies them (TK = f32s_t: fp32 tensors, split-bf16 products)
 template <typename T, typename TK = T>
 int conv_gather_op(const View &v, const void *in_v, int g_real, const float *weight, int K, int cin_w, int cout_w,
                    int transposed_w, int o_real, const float *bias, void *out_v, void *workspace, hipStream_t s,
-                   int w_o_real = -1, const BnEpi *bn = nullptr, void *packed_ext = nullptr, int pack_mode = 0, int in_ld = 0) {
-  if (w_o_real < 0) w_o_real = o_real;
-  if (v.n_pad == 0) return 0;      // the maps of an empty batch: no row to write (and a 256-byte workspace: nothing is packed)
-  if constexpr (std::is_same<TK, bf16_t>::value) {
-    // 1x1 layers of the big maps: a streaming GEMM with persistent workgroups (lgs_pointwise.hip), no packed image, no workspace
-    const int64_t ld = in_ld > 0 ? in_ld : g_real;
-    if (!bn && w_o_real == o_real && pointwise_supported(v, K, g_real, o_real, ld))
-      return launch_pointwise(v, in_v, ld, g_real, weight, cin_w, cout_w, transposed_w, o_real, bias, out_v, s);
-  }
-  LGS_REQUIRE(in_ld == 0 || in_ld == g_real || (g_real % Tr<T>::EPL == 0 && o_real % 4 == 0 && in_ld > g_real && (in_ld * (int)sizeof(T)) % 16 == 0),
+                   const BnEpi *bn = nullptr, void *packed_ext = nullptr, int pack_mode = 0, int in_ld = 0) {
+  constexpr int EPL = Tr<T>::EPL;
+  const ConvPlan pl = conv_plan<T, TK>(v, K, g_real, o_real, !bn ? kEpiNone : bn->accum ? kEpiAccum : kEpiBnStats, in_ld);
+  const int64_t ld = in_ld > 0 ? in_ld : g_real;
+  if (pl.path == kPathEmpty) return 0;
+  if (pl.path == kPathPointwise) return launch_pointwise(v, in_v, ld, g_real, weight, cin_w, cout_w, transposed_w, o_real, bias, out_v, s);
+  LGS_REQUIRE(in_ld == 0 || in_ld == g_real || (pl.packed_ext_ok && in_ld > g_real && (in_ld * (int)sizeof(T)) % 16 == 0),
               "sparse conv: a strided input needs 16-byte aligned rows and channel counts on the 16-byte grid");
-  constexpr int EPL = Tr<T>::EPL, LD = Tr<TK>::WLD;
-  const int g_pad = pad32(g_real), nc = g_pad / 32, nb_total = pad32(o_real) / 32;
+  if (pl.path == kPathPointwiseF32) return launch_pointwise_f32(v, in_v, ld, g_real, weight, cin_w, cout_w, transposed_w, o_real, bias, out_v, s);
   char *ws = reinterpret_cast<char *>(workspace);
-  uint4 *wp = reinterpret_cast<uint4 *>(ws);
-  const GatherCfg cfg = gather_cfg<TK>(v, nb_total);
-  const int ncp = (nc + cfg.sc - 1) / cfg.sc * cfg.sc, nbp = (nb_total + cfg.wb - 1) / cfg.wb * cfg.wb;
-  const int64_t wbytes = packed_region_bytes<TK>(v, K, g_real, o_real);
-  if (o_real % 4 != 0) {
-    // rows are written in 4-channel groups: route odd widths (e.g. the 3-channel input gradient of a
-    // test) through a 4-aligned scratch image placed after the packed weights and the padded input
-    const int o4 = (o_real + 3) / 4 * 4;
-    int64_t off = wbytes + ((g_real % EPL != 0) ? align256(v.n_in * (int64_t)g_pad * (int64_t)sizeof(T)) : 0);
-    T *tmp = reinterpret_cast<T *>(ws + off);
-    if (v.n_out > 0) LGS_HIP(hipMemsetAsync(tmp, 0, (size_t)v.n_out * o4 * sizeof(T), s));
-    const float *bias4 = nullptr;
-    if (bias) {   // e.g. the 3-channel offset head of the instance-segmentation model: bias padded to the scratch width
-      float *bp = reinterpret_cast<float *>(ws + off + align256(v.n_out * (int64_t)o4 * (int64_t)sizeof(T)));
-      LGS_HIP(hipMemsetAsync(bp, 0, sizeof(float) * o4, s));
+  T *out = reinterpret_cast<T *>(out_v);
+  int o_launch = o_real;
+  if (pl.scratch_out) {     // (statistics, accumulation and a caller's packed image do not exist on this route)
+    out = reinterpret_cast<T *>(ws + pl.scratch.offset);
+    o_launch = (o_real + 3) / 4 * 4;
+    bn = nullptr;
+    if (v.n_out > 0) LGS_HIP(hipMemsetAsync(out, 0, (size_t)v.n_out * o_launch * sizeof(T), s));
+    if (bias) {
+      float *bp = reinterpret_cast<float *>(ws + pl.bias.offset);
+      LGS_HIP(hipMemsetAsync(bp, 0, sizeof(float) * o_launch, s));
       LGS_HIP(hipMemcpyAsync(bp, bias, sizeof(float) * o_real, hipMemcpyDeviceToDevice, s));
-      bias4 = bp;
+      bias = bp;
     }
-    int rc = conv_gather_op<T, TK>(v, in_v, g_real, weight, K, cin_w, cout_w, transposed_w, o4, bias4, tmp, workspace, s, o_real);
-    if (rc) return rc;
-    int64_t tot = v.n_out * (int64_t)o_real;
-    if (tot > 0)
-      LGS_KLAUNCH((k_unpad_rows<T>), (unsigned)((tot + 255) / 256), 256, 0, s, tmp, v.n_out, o_real, o4,
-                         reinterpret_cast<T *>(out_v));
-    LGS_HIP(hipGetLastError());
-    return 0;
-  }
-  if constexpr (std::is_same<T, float>::value) {
-    // fp32 1x1 layers of the big maps: streaming GEMM on the exact-fp32 MFMA (k_pointwise_f32), whichever instance multiplies the 3^3 layers
-    const int64_t ld = in_ld > 0 ? in_ld : g_real;
-    if (!bn && w_o_real == o_real && pointwise_f32_supported(v, K, g_real, o_real, ld))
-      return launch_pointwise_f32(v, in_v, ld, g_real, weight, cin_w, cout_w, transposed_w, o_real, bias, out_v, s);
   }
   const T *in = reinterpret_cast<const T *>(in_v);
   int g_stride = g_real;
-  if (g_real % EPL != 0) {  // e.g. the 3-channel colour input of conv0p1s1
+  if (pl.pad_input) {
     // rows are padded to ONE 16-byte piece multiple (3 -> 8 bf16 / 4 fp32 channels), not to the 32-channel chunk: the
     // pieces beyond the row are masked by the gather's channel-tail test, so neighbours cost 16 instead of 64 bytes
-    T *padded = reinterpret_cast<T *>(ws + wbytes);
-    const int g_al = (g_real + EPL - 1) / EPL * EPL;
-    int64_t tot = v.n_in * g_al;
-    if (tot > 0) LGS_KLAUNCH((k_pad_rows<T>), (unsigned)((tot + 255) / 256), 256, 0, s, in, v.n_in, g_real, g_al, padded);
+    T *padded = reinterpret_cast<T *>(ws + pl.padded_in.offset);
+    g_stride = (g_real + EPL - 1) / EPL * EPL;
+    const int64_t tot = v.n_in * g_stride;
+    if (tot > 0) LGS_KLAUNCH((k_pad_rows<T>), (unsigned)((tot + 255) / 256), 256, 0, s, in, v.n_in, g_real, g_stride, padded);
     in = padded;
-    g_stride = g_al;
   }
-  int64_t total = (int64_t)K * ncp * nbp * LD * 64;
   // packed_ext: a caller-owned image of exactly this layout (lgs_conv_pack_desc); pack_mode 2 = it is up to date
-  if (packed_ext && o_real % 4 == 0 && g_real % EPL == 0) wp = reinterpret_cast<uint4 *>(packed_ext);
-  else pack_mode = 0;
-  LGS_REQUIRE(wp != reinterpret_cast<uint4 *>(ws) || total * 16 <= wbytes,
-              "sparse conv: the packed weight image is larger than its workspace region (internal error)");
-  if (pack_mode != 2)
-    LGS_KLAUNCH((k_pack_weights<TK>), (unsigned)((total + 255) / 256), 256, 0, s, weight, K, cin_w, cout_w, transposed_w,
-                       v.mirror, g_real, w_o_real, ncp, nbp, wp);
+  const bool ext = packed_ext && pl.packed_ext_ok;
+  uint4 *wp = ext ? reinterpret_cast<uint4 *>(packed_ext) : reinterpret_cast<uint4 *>(ws + pl.packed.offset);
+  if (!ext || pack_mode != 2)
+    LGS_KLAUNCH((k_pack_weights<TK>), (unsigned)((pl.total + 255) / 256), 256, 0, s, weight, K, cin_w, cout_w, transposed_w,
+                       v.mirror, g_real, o_real, pl.ncp, pl.nbp, wp);
   LGS_HIP(hipGetLastError());
-  // fp32 partial images of the slot split live behind the packed weights and the padded input
-  float *zpartial = nullptr;
-  if (w_o_real == o_real && split_partial_bytes(K, v.n_out, o_real) > 0)
-    zpartial = reinterpret_cast<float *>(ws + wbytes + ((g_real % EPL != 0) ? align256(v.n_in * (int64_t)g_pad * (int64_t)sizeof(T)) : 0));
-  int rows = 0;
-  int rc = launch_gather<TK>(v, cfg, reinterpret_cast<const TK *>(in), g_stride, nc, wp, nb_total, ncp, nbp, K, reinterpret_cast<TK *>(out_v), o_real, bias, s,
-                            nullptr, nullptr, zpartial, bn, &rows, (in_ld > g_real && g_stride == g_real) ? in_ld : 0);
-  if (rc) return rc;
-  LGS_REQUIRE(!(bn && bn->partial) || rows == bn_partial_rows_t<TK>(v, K, o_real),
-              "conv forward: BatchNorm statistics rows differ from lgs_conv_bn_partial_rows (internal error)");
+  int rc = launch_gather<TK>(v, pl, reinterpret_cast<const TK *>(in), g_stride, wp, K, reinterpret_cast<TK *>(out), o_launch, bias, s, nullptr,
+                            nullptr, pl.split ? reinterpret_cast<float *>(ws + pl.partials.offset) : nullptr, bn,
+                            (in_ld > g_real && !pl.pad_input) ? in_ld : 0);
+  if (rc || !pl.scratch_out) return rc;
+  const int64_t tot = v.n_out * (int64_t)o_real;
+  if (tot > 0)
+    LGS_KLAUNCH((k_unpad_rows<T>), (unsigned)((tot + 255) / 256), 256, 0, s, out, v.n_out, o_real, o_launch, reinterpret_cast<T *>(out_v));
+  LGS_HIP(hipGetLastError());
   return 0;
 }
 
@@ -1136,34 +1129,37 @@ __global__ void k_normalize_anchors(const float *__restrict__ a, int na, int c, 
   for (int ch = lane; ch < c; ch += 64) out[(int64_t)row * c + ch] = a[(int64_t)row * c + ch] * inv;
 }
 
+// room for the packed anchor image of the CLIP launches: what lgs_clip_workspace_bytes / lgs_clip_loss_workspace_bytes promise the
+// caller (who does not know the tile yet) and what the launches check their image against
+inline int64_t clip_image_room(int c, int n_anchor, int dtype) {
+  return align256((int64_t)(pad32(c) + 96) * (pad32(n_anchor) + 96) * esize(dtype));
+}
+inline int64_t clip_loss_image_room(int c, int dtype) {   // <= (nc + 7) chunks x 7 blocks
+  return align256((int64_t)(pad32(c) + 256) * 256 * esize(dtype));
+}
+
 template <typename T>
 int clip_similarity_t(const void *feat, int64_t n, int c, const float *anchors, int na, float *sim, float *inv_norm_f,
                       void *workspace, hipStream_t s) {
-  constexpr int EPL = Tr<T>::EPL, LD = Tr<T>::LD;
-  LGS_REQUIRE(c % EPL == 0, "lgs_clip_similarity: feature dim must be a multiple of the 16-byte load width");
+  constexpr int dtype = sizeof(T) == 2 ? LGS_BF16 : LGS_F32;
+  LGS_REQUIRE(c % Tr<T>::EPL == 0, "lgs_clip_similarity: feature dim must be a multiple of the 16-byte load width");
   LGS_REQUIRE(na % 4 == 0, "lgs_clip_similarity: anchor count must be a multiple of 4");
   if (n == 0) return 0;
-  const int nc = pad32(c) / 32, nb_total = pad32(na) / 32;
   char *ws = reinterpret_cast<char *>(workspace);
   float *tn = reinterpret_cast<float *>(ws);
-  int64_t off = align256((int64_t)na * c * 4);
-  uint4 *wp = reinterpret_cast<uint4 *>(ws + off);
-  off += align256((int64_t)(nc + 3) * (nb_total + 3) * LD * 64 * 16);
-  float *inv = inv_norm_f ? inv_norm_f : reinterpret_cast<float *>(ws + off);
+  uint4 *wp = reinterpret_cast<uint4 *>(ws + align256((int64_t)na * c * 4));
   const T *f = reinterpret_cast<const T *>(feat);
   LGS_KLAUNCH(k_normalize_anchors, na, 64, 0, s, anchors, na, c, tn);
   View v;
   v.n_pad = pad_rows(n); v.n_out = n; v.n_in = n; v.KS = 1; v.K = 1;
-  const GatherCfg cfg = gather_cfg<T>(v, nb_total);
-  const int ncp = (nc + cfg.sc - 1) / cfg.sc * cfg.sc, nbp = (nb_total + cfg.wb - 1) / cfg.wb * cfg.wb;
-  int64_t total = (int64_t)ncp * nbp * LD * 64;
-  LGS_REQUIRE(total * 16 <= align256((int64_t)(nc + 3) * (nb_total + 3) * LD * 64 * 16),
+  const ConvPlan pl = conv_plan<T>(v, 1, c, na, kEpiF32Out);
+  LGS_REQUIRE(pl.total * 16 <= clip_image_room(c, na, dtype),
               "lgs_clip_similarity: the packed anchor image is larger than its workspace region (SMALL_CFG 12 / 13 on a narrow feature)");
   // T^[a][c] read as w[o = a][g = c]  ("transposed" form of the packer with cin_w = na, cout_w = c)
-  LGS_KLAUNCH((k_pack_weights<T>), (unsigned)((total + 255) / 256), 256, 0, s, tn, 1, na, c, 1, 0, c, na, ncp, nbp, wp);
-  LGS_KLAUNCH((k_row_invnorm<T>), (unsigned)((n * 64 + 255) / 256), 256, 0, s, f, n, c, inv);
+  LGS_KLAUNCH((k_pack_weights<T>), (unsigned)((pl.total + 255) / 256), 256, 0, s, tn, 1, na, c, 1, 0, c, na, pl.ncp, pl.nbp, wp);
+  LGS_KLAUNCH((k_row_invnorm<T>), (unsigned)((n * 64 + 255) / 256), 256, 0, s, f, n, c, inv_norm_f);
   LGS_HIP(hipGetLastError());
-  return launch_gather<T>(v, cfg, f, c, nc, wp, nb_total, ncp, nbp, 1, (T *)nullptr, na, nullptr, s, sim, inv);
+  return launch_gather<T>(v, pl, f, c, wp, 1, (T *)nullptr, na, nullptr, s, sim, inv_norm_f);
 }
 
 // Fused CLIP loss forward: one launch of the EPI = 1 instance.  The wave owns whole rows (all anchor columns), so
@@ -1171,27 +1167,25 @@ int clip_similarity_t(const void *feat, int64_t n, int c, const float *anchors, 
 template <typename T>
 int clip_loss_forward_t(const void *feat, int64_t n, int c, const float *anchors, int na, const ClipEpi &ce_in, float *anchors_n,
                         float *sim, void *workspace, hipStream_t s) {
-  constexpr int EPL = Tr<T>::EPL, LD = Tr<T>::LD;
   constexpr bool kF32 = (sizeof(T) == 4);
-  LGS_REQUIRE(c % EPL == 0, "lgs_clip_loss_forward: feature dim must be a multiple of the 16-byte load width");
+  LGS_REQUIRE(c % Tr<T>::EPL == 0, "lgs_clip_loss_forward: feature dim must be a multiple of the 16-byte load width");
   LGS_REQUIRE(na % 4 == 0 && na >= 4 && na <= 224, "lgs_clip_loss_forward: anchor count must be a multiple of 4 in [4, 224]");
   LGS_REQUIRE(ce_in.k_neg >= 1 && ce_in.k_neg <= 7, "lgs_clip_loss_forward: 1..7 negatives per row");
   if (n == 0) return 0;
-  const int nc = pad32(c) / 32, nb_total = pad32(na) / 32;
+  const int nb_total = pad32(na) / 32;
   const int ncb = nb_total <= 1 ? 1 : nb_total <= 2 ? 2 : nb_total <= 4 ? 4 : 7;
-  const int sc = ncb == 1 ? (kF32 ? 4 : 8) : ncb == 2 ? (kF32 ? 2 : 4) : ncb == 4 ? (kF32 ? 1 : 2) : (kF32 ? 1 : 2);
-  const int ncp = (nc + sc - 1) / sc * sc, nbp = ncb;
-  char *ws = reinterpret_cast<char *>(workspace);
-  uint4 *wp = reinterpret_cast<uint4 *>(ws);
+  ConvPlan pl = {};  // the image of the EPI = 1 instances: one column tile of ncb blocks
+  plan_image(pl, GatherCfg{-1, ncb == 1 ? (kF32 ? 4 : 8) : ncb == 2 ? (kF32 ? 2 : 4) : (kF32 ? 1 : 2), ncb, 128}, 1, c, na, Tr<T>::WLD);
+  const int nc = pl.nc, ncp = pl.ncp, nbp = pl.nbp;
+  uint4 *wp = reinterpret_cast<uint4 *>(workspace);
   LGS_KLAUNCH(k_normalize_anchors, na, 64, 0, s, anchors, na, c, anchors_n);
-  int64_t total = (int64_t)ncp * nbp * LD * 64;
-  LGS_REQUIRE(total * 16 <= align256((int64_t)(nc + 3) * (nb_total + 3) * LD * 64 * 16),
-              "lgs_clip_similarity: the packed anchor image is larger than its workspace region (SMALL_CFG 12 / 13 on a narrow feature)");
+  LGS_REQUIRE(pl.total * 16 <= clip_loss_image_room(c, kF32 ? LGS_F32 : LGS_BF16),
+              "lgs_clip_loss_forward: the packed anchor image is larger than its workspace region (internal error)");
   // T^[a][c] read as w[o = a][g = c]  ("transposed" form of the packer with cin_w = na, cout_w = c)
-  LGS_KLAUNCH((k_pack_weights<T>), (unsigned)((total + 255) / 256), 256, 0, s, anchors_n, 1, na, c, 1, 0, c, na, ncp, nbp, wp);
+  LGS_KLAUNCH((k_pack_weights<T>), (unsigned)((pl.total + 255) / 256), 256, 0, s, anchors_n, 1, na, c, 1, 0, c, na, ncp, nbp, wp);
   View v;
   v.n_pad = pad_rows(n); v.n_out = n; v.n_in = n; v.KS = 1; v.K = 1;
-  const uint64_t in_bytes64 = (uint64_t)n * (uint64_t)c * sizeof(T), w_bytes64 = (uint64_t)total * 16;
+  const uint64_t in_bytes64 = (uint64_t)n * (uint64_t)c * sizeof(T), w_bytes64 = (uint64_t)pl.total * 16;
   LGS_REQUIRE(in_bytes64 < 0xfffff000ull, "lgs_clip_loss_forward: feature tensor of 4 GiB or more");
   ClipEpi ce = ce_in;
   ce.n_anchor = na;
@@ -1212,24 +1206,36 @@ int clip_loss_forward_t(const void *feat, int64_t n, int c, const float *anchors
   return 0;
 }
 
-template <typename T>
-int pack_desc_t(const View &v, int K, int cin_w, int cout_w, int transposed_w, int mirror, int g_real, int o_real, int dtype,
-                lgs_pack_desc *d) {
-  constexpr int EPL = Tr<T>::EPL, LD = Tr<T>::LD;
-  memset(d, 0, sizeof(*d));
-  if (o_real % 4 != 0 || g_real % EPL != 0 || v.n_pad == 0) return 0;      // scratch / padded-input paths pack internally
-  const int nc = pad32(g_real) / 32, nb_total = pad32(o_real) / 32;
-  const GatherCfg cfg = gather_cfg<T>(v, nb_total);
-  d->ncp = (nc + cfg.sc - 1) / cfg.sc * cfg.sc;
-  d->nbp = (nb_total + cfg.wb - 1) / cfg.wb * cfg.wb;
-  d->K = K; d->cin_w = cin_w; d->cout_w = cout_w; d->transposed = transposed_w; d->mirror = mirror;
-  d->g_real = g_real; d->o_real = o_real; d->dtype = Tr<T>::SPLIT ? kDtF32Split : dtype;
-  d->total = (int64_t)K * d->ncp * d->nbp * Tr<T>::WLD * 64;
-  d->bytes = d->total * 16;
-  return 0;
+// ---- one kernel instance per tensor dtype: f(Inst<storage type, multiplying instance>)
+template <typename T, typename TK = T> struct Inst { using S = T; using M = TK; };
+template <typename F>
+auto with_instance(int dtype, F &&f) {
+  if (dtype == LGS_BF16) return f(Inst<bf16_t>());
+  if (tune(T_FP32_SPLIT) != 0) return f(Inst<float, f32s_t>());
+  return f(Inst<float>());
+}
+inline bool known_dtype(int dtype) { return dtype == LGS_F32 || dtype == LGS_BF16; }
+
+// the view op 0 (forward) / 1 (dgrad) walks, and its plan
+inline const View &op_view(const lgs_kmap *km, int op, int transposed) { return (op == 1) == (transposed != 0) ? km->fwd : km->bwd; }
+inline ConvPlan plan_of(const View &v, int K, int g_real, int o_real, int dtype, ConvEpi epi) {
+  return with_instance(dtype, [&](auto i) { return conv_plan<typename decltype(i)::S, typename decltype(i)::M>(v, K, g_real, o_real, epi); });
 }
 
-inline bool fp32_split_on() { return tune(T_FP32_SPLIT) != 0; }
+// one forward / dgrad call: op 1 gathers grad_out [*, cout] and reads the weights transposed (3^3: mirrored)
+inline int conv_call(lgs_kmap *km, int op, int transposed, const void *in, int cin, const float *weight, int cout, const float *bias,
+                     void *out, int dtype, void *workspace, const BnEpi *bn, void *packed, int pack_mode, int in_ld, void *stream) {
+  LGS_REQUIRE(!(transposed && km->ks == 3), "transposed 3x3x3 convolution is not part of the model family");
+  LGS_REQUIRE(known_dtype(dtype), "sparse conv: unknown dtype");
+  View v = op_view(km, op, transposed);
+  v.mirror = (op == 1 && km->ks == 3) ? 1 : 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (kmap_wait(km, s)) return 1;
+  return with_instance(dtype, [&](auto i) {
+    return conv_gather_op<typename decltype(i)::S, typename decltype(i)::M>(v, in, op == 0 ? cin : cout, weight, km->K, cin, cout, op,
+                                                                           op == 0 ? cout : cin, bias, out, workspace, s, bn, packed, pack_mode, in_ld);
+  });
+}
 
 }  // namespace lgs
 
@@ -1239,45 +1245,40 @@ extern "C" {
 
 int64_t lgs_conv_workspace_bytes(const lgs_kmap *km, int cin, int cout, int dtype, int op) {
   if (!km) return -1;
-  const int e = esize(dtype);
   // the maps of an empty batch: no launch plan to size (the planners divide by range and lane counts); the entry points return
   // before they touch the workspace
   if (km->fwd.n_pad == 0 && km->bwd.n_pad == 0) return 256;
   if (op == 2) return lgs::wgrad_workspace_bytes(km, cin, cout, dtype);
-  int g = op == 0 ? cin : cout, o = op == 0 ? cout : cin;
-  // packed weights: fp32 images of the split path hold three bf16 pieces per element (6 instead of 4 bytes)
-  int64_t bytes = align256((int64_t)km->K * (pad32(g) + 96) * (pad32(o) + 96) * (dtype == LGS_F32 ? 6 : e));
-  // ... or the image of the tile configuration the launch will pick (either view: op 0 / 1 run on fwd or bwd by `transposed`)
-  for (const View *v : {&km->fwd, &km->bwd}) {
-    const int64_t pr = dtype == LGS_BF16 ? packed_region_bytes<bf16_t>(*v, km->K, g, o)
-                       : fp32_split_on() ? packed_region_bytes<f32s_t>(*v, km->K, g, o) : packed_region_bytes<float>(*v, km->K, g, o);
-    if (pr > bytes) bytes = pr;
-  }
-  int64_t nmax = km->fwd.n_in > km->bwd.n_in ? km->fwd.n_in : km->bwd.n_in;
-  if (g % epl(dtype) != 0) bytes += align256(nmax * pad32(g) * e);
-  if (o % 4 != 0) bytes += align256(nmax * (int64_t)((o + 3) / 4 * 4) * e) + align256(4 * (int64_t)((o + 3) / 4 * 4)) + 256;   // scratch image + padded bias
-  int64_t omax = km->fwd.n_out > km->bwd.n_out ? km->fwd.n_out : km->bwd.n_out;
-  bytes += lgs::split_partial_bytes(km->K, omax, o) + lgs::split_partial_bytes(km->K, omax, (o + 3) / 4 * 4);
-  return bytes + 256;
+  // either view (op 0 / 1 run on fwd or bwd by `transposed`), with and without the epilogue that keeps a 1x1 layer off the
+  // pointwise kernels
+  int64_t bytes = 0;
+  for (const View *v : {&km->fwd, &km->bwd})
+    for (ConvEpi e : {kEpiNone, op == 0 ? kEpiBnStats : kEpiAccum}) {
+      const int64_t b = plan_of(*v, km->K, op == 0 ? cin : cout, op == 0 ? cout : cin, dtype, e).bytes_total;
+      if (b > bytes) bytes = b;
+    }
+  return bytes;
 }
 
+// rows of BatchNorm statistics the forward launch of this shape writes, 0 if it cannot produce them
 int lgs_conv_bn_partial_rows(const lgs_kmap *km, int transposed, int cout, int dtype) {
-  if (!km) return 0;
-  const View &v = transposed ? km->bwd : km->fwd;
-  if (dtype == LGS_F32) return bn_partial_rows_t<float>(v, km->K, cout);
-  if (dtype == LGS_BF16) return bn_partial_rows_t<bf16_t>(v, km->K, cout);
-  return 0;
+  if (!km || !known_dtype(dtype)) return 0;
+  return plan_of(op_view(km, 0, transposed), km->K, cout, cout, dtype, kEpiBnStats).bn_rows;   // (the input width does not matter)
 }
 
 int lgs_conv_pack_desc(const lgs_kmap *km, int op, int transposed, int cin, int cout, int dtype, lgs_pack_desc *out) {
   LGS_REQUIRE(km && out && (op == 0 || op == 1), "lgs_conv_pack_desc: bad argument");
-  const View &v = op == 0 ? (transposed ? km->bwd : km->fwd) : (transposed ? km->fwd : km->bwd);
-  const int mirror = (op == 1 && km->ks == 3) ? 1 : 0;
+  LGS_REQUIRE(known_dtype(dtype), "lgs_conv_pack_desc: unknown dtype");
   const int g = op == 0 ? cin : cout, o = op == 0 ? cout : cin;
-  if (dtype == LGS_F32 && fp32_split_on()) return pack_desc_t<f32s_t>(v, km->K, cin, cout, op, mirror, g, o, dtype, out);
-  if (dtype == LGS_F32) return pack_desc_t<float>(v, km->K, cin, cout, op, mirror, g, o, dtype, out);
-  if (dtype == LGS_BF16) return pack_desc_t<bf16_t>(v, km->K, cin, cout, op, mirror, g, o, dtype, out);
-  LGS_REQUIRE(false, "lgs_conv_pack_desc: unknown dtype");
+  const ConvPlan pl = plan_of(op_view(km, op, transposed), km->K, g, o, dtype, op == 0 ? kEpiBnStats : kEpiAccum);
+  memset(out, 0, sizeof(*out));
+  if (!pl.packed_ext_ok) return 0;      // empty maps, scratch / padded-input routes pack internally
+  out->K = km->K; out->cin_w = cin; out->cout_w = cout; out->transposed = op; out->mirror = (op == 1 && km->ks == 3) ? 1 : 0;
+  out->g_real = g; out->o_real = o; out->ncp = pl.ncp; out->nbp = pl.nbp;
+  out->dtype = (dtype == LGS_F32 && tune(T_FP32_SPLIT) != 0) ? kDtF32Split : dtype;
+  out->total = pl.total;
+  out->bytes = pl.total * 16;
+  return 0;
 }
 
 int lgs_pack_weights_batch(const lgs_pack_desc *descs_device, int n, int64_t max_total, void *stream) {
@@ -1292,44 +1293,25 @@ int lgs_conv_forward(lgs_kmap *km, int transposed, const void *in, int cin, cons
                      const float *bias, void *out, int dtype, void *workspace, float *bn_partial, const float *bn_pivot,
                      void *packed, int pack_mode, int in_row_stride, void *stream) {
   LGS_REQUIRE(km && weight && workspace, "lgs_conv_forward: null argument");
-  LGS_REQUIRE(!(transposed && km->ks == 3), "transposed 3x3x3 convolution is not part of the model family");
-  const View &v = transposed ? km->bwd : km->fwd;
-  View vv = v; vv.mirror = 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (kmap_wait(km, s)) return 1;
   BnEpi bn;
   bn.partial = bn_partial; bn.pivot = bn_pivot;
   LGS_REQUIRE(!bn_partial || lgs_conv_bn_partial_rows(km, transposed, cout, dtype) > 0,
               "lgs_conv_forward: this launch shape produces no BatchNorm statistics (see lgs_conv_bn_partial_rows)");
-  if (dtype == LGS_F32 && fp32_split_on()) return conv_gather_op<float, f32s_t>(vv, in, cin, weight, km->K, cin, cout, 0, cout, bias, out, workspace, s, -1, bn_partial ? &bn : nullptr, packed, pack_mode, in_row_stride);
-  if (dtype == LGS_F32) return conv_gather_op<float>(vv, in, cin, weight, km->K, cin, cout, 0, cout, bias, out, workspace, s, -1, bn_partial ? &bn : nullptr, packed, pack_mode, in_row_stride);
-  if (dtype == LGS_BF16) return conv_gather_op<bf16_t>(vv, in, cin, weight, km->K, cin, cout, 0, cout, bias, out, workspace, s, -1, bn_partial ? &bn : nullptr, packed, pack_mode, in_row_stride);
-  LGS_REQUIRE(false, "lgs_conv_forward: unknown dtype");
+  return conv_call(km, 0, transposed, in, cin, weight, cout, bias, out, dtype, workspace, bn_partial ? &bn : nullptr, packed, pack_mode,
+                   in_row_stride, stream);
 }
 
 int lgs_conv_dgrad(lgs_kmap *km, int transposed, const void *grad_out, int cout, const float *weight, int cin,
                    void *grad_in, int dtype, void *workspace, void *packed, int pack_mode, void *stream) {
   LGS_REQUIRE(km && weight && workspace, "lgs_conv_dgrad: null argument");
-  LGS_REQUIRE(!(transposed && km->ks == 3), "transposed 3x3x3 convolution is not part of the model family");
-  const View &v = transposed ? km->fwd : km->bwd;  // the opposite direction of the forward
-  View vv = v; vv.mirror = (km->ks == 3) ? 1 : 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (kmap_wait(km, s)) return 1;
-  if (dtype == LGS_F32 && fp32_split_on()) return conv_gather_op<float, f32s_t>(vv, grad_out, cout, weight, km->K, cin, cout, 1, cin, nullptr, grad_in, workspace, s, -1, nullptr, packed, pack_mode);
-  if (dtype == LGS_F32) return conv_gather_op<float>(vv, grad_out, cout, weight, km->K, cin, cout, 1, cin, nullptr, grad_in, workspace, s, -1, nullptr, packed, pack_mode);
-  if (dtype == LGS_BF16) return conv_gather_op<bf16_t>(vv, grad_out, cout, weight, km->K, cin, cout, 1, cin, nullptr, grad_in, workspace, s, -1, nullptr, packed, pack_mode);
-  LGS_REQUIRE(false, "lgs_conv_dgrad: unknown dtype");
+  return conv_call(km, 1, transposed, grad_out, cin, weight, cout, nullptr, grad_in, dtype, workspace, nullptr, packed, pack_mode, 0, stream);
 }
 
 // 1 if lgs_conv_dgrad_accumulate adds inside the kernel epilogue for this launch shape (everything but the 2-D blocked wide
 // kernel and input widths off the 4-channel grid)
 int lgs_conv_dgrad_can_accumulate(const lgs_kmap *km, int transposed, int cin, int cout, int dtype) {
-  if (!km || (transposed && km->ks == 3) || cin % 4 != 0 || (dtype != LGS_F32 && dtype != LGS_BF16)) return 0;
-  const View &v = transposed ? km->fwd : km->bwd;
-  if (v.n_pad == 0) return 0;
-  const int nb_total = pad32(cin) / 32;
-  const int id = dtype == LGS_F32 ? gather_cfg<float>(v, nb_total).id : gather_cfg<bf16_t>(v, nb_total).id;
-  return id == 17 ? 0 : 1;
+  if (!km || (transposed && km->ks == 3) || !known_dtype(dtype)) return 0;
+  return plan_of(op_view(km, 1, transposed), km->K, cout, cin, dtype, kEpiAccum).can_accumulate;
 }
 
 // grad_in += dgrad(grad_out): the sum autograd would form when the convolution's input also feeds a residual branch, taken
@@ -1338,28 +1320,39 @@ int lgs_conv_dgrad_accumulate(lgs_kmap *km, int transposed, const void *grad_out
                               void *grad_in, int dtype, void *workspace, void *packed, int pack_mode, void *stream) {
   LGS_REQUIRE(km && weight && workspace && grad_in, "lgs_conv_dgrad_accumulate: null argument");
   LGS_REQUIRE(lgs_conv_dgrad_can_accumulate(km, transposed, cin, cout, dtype), "lgs_conv_dgrad_accumulate: this launch shape has no accumulating epilogue (ask lgs_conv_dgrad_can_accumulate first)");
-  const View &v = transposed ? km->fwd : km->bwd;
-  View vv = v; vv.mirror = (km->ks == 3) ? 1 : 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (kmap_wait(km, s)) return 1;
   BnEpi acc; acc.accum = 1;
-  if (dtype == LGS_F32 && fp32_split_on()) return conv_gather_op<float, f32s_t>(vv, grad_out, cout, weight, km->K, cin, cout, 1, cin, nullptr, grad_in, workspace, s, -1, &acc, packed, pack_mode);
-  if (dtype == LGS_F32) return conv_gather_op<float>(vv, grad_out, cout, weight, km->K, cin, cout, 1, cin, nullptr, grad_in, workspace, s, -1, &acc, packed, pack_mode);
-  return conv_gather_op<bf16_t>(vv, grad_out, cout, weight, km->K, cin, cout, 1, cin, nullptr, grad_in, workspace, s, -1, &acc, packed, pack_mode);
+  return conv_call(km, 1, transposed, grad_out, cin, weight, cout, nullptr, grad_in, dtype, workspace, &acc, packed, pack_mode, 0, stream);
 }
 
-}  // extern "C"
-
-extern "C" {
+// the plan of op 0 / 1 on a synthetic map + what the public queries say for it: no HIP call, `present` tables are never read
+int lgs_debug_conv_plan(const lgs_conv_plan_query *q, lgs_conv_plan_info *out) {
+  LGS_REQUIRE(q && out && (q->op == 0 || q->op == 1) && known_dtype(q->dtype) && q->epilogue >= 0 && q->epilogue <= 2, "lgs_debug_conv_plan: bad argument");
+  static const int32_t present = 0;
+  auto view = [&](const lgs_conv_plan_view &s) {
+    View v;
+    v.n_pad = s.n_pad; v.n_in = s.n_in; v.n_out = s.n_out; v.KS = s.KS; v.K = s.K;
+    if (s.has_nbr) v.nbr = &present;
+    if (s.has_nbr && s.KS > 1) v.mask64 = reinterpret_cast<const uint32_t *>(&present);
+    if (s.has_tile_k) v.tile_k = &present;
+    if (s.has_out_row) v.out_row = &present;
+    return v;
+  };
+  lgs_kmap km;
+  km.ks = q->ks; km.K = q->fwd.K; km.fwd = view(q->fwd); km.bwd = view(q->bwd);
+  *out = plan_of(op_view(&km, q->op, q->transposed), km.K, q->op == 0 ? q->cin : q->cout, q->op == 0 ? q->cout : q->cin, q->dtype, (ConvEpi)q->epilogue);
+  out->workspace_bytes = lgs_conv_workspace_bytes(&km, q->cin, q->cout, q->dtype, q->op);
+  out->q_bn_partial_rows = q->op == 0 ? lgs_conv_bn_partial_rows(&km, q->transposed, q->cout, q->dtype) : 0;
+  out->q_can_accumulate = q->op == 1 ? lgs_conv_dgrad_can_accumulate(&km, q->transposed, q->cin, q->cout, q->dtype) : 0;
+  return lgs_conv_pack_desc(&km, q->op, q->transposed, q->cin, q->cout, q->dtype, &out->pack_desc);
+}
 
 int64_t lgs_clip_workspace_bytes(int c, int n_anchor, int dtype) {
-  int64_t b = align256((int64_t)n_anchor * c * 4) + align256((int64_t)(pad32(c) + 96) * (pad32(n_anchor) + 96) * esize(dtype));
-  return b + 256;
+  return align256((int64_t)n_anchor * c * 4) + clip_image_room(c, n_anchor, dtype) + 256;
 }
 
 int64_t lgs_clip_loss_workspace_bytes(int c, int n_anchor, int dtype) {
   (void)n_anchor;
-  return align256((int64_t)(pad32(c) + 256) * 256 * esize(dtype)) + 256;   // packed anchors: <= (nc + 7) chunks x 7 blocks
+  return clip_loss_image_room(c, dtype) + 256;
 }
 
 int lgs_clip_loss_forward(const void *feat, int64_t n, int c, const float *anchors, int n_anchor, const int64_t *labels,

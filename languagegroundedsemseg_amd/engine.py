@@ -10,7 +10,7 @@ import os
 from . import build as _build
 
 LGS_F32, LGS_BF16 = 0, 1
-ABI_VERSION = 14     # LGS_ABI_VERSION of include/lgs_engine.h
+ABI_VERSION = 15     # LGS_ABI_VERSION of include/lgs_engine.h
 
 
 class PackDesc(ctypes.Structure):
@@ -19,6 +19,33 @@ class PackDesc(ctypes.Structure):
                 ("K", ctypes.c_int), ("cin_w", ctypes.c_int), ("cout_w", ctypes.c_int), ("transposed", ctypes.c_int),
                 ("mirror", ctypes.c_int), ("g_real", ctypes.c_int), ("o_real", ctypes.c_int), ("ncp", ctypes.c_int),
                 ("nbp", ctypes.c_int), ("dtype", ctypes.c_int)]
+
+class ConvPlanView(ctypes.Structure):
+    """lgs_conv_plan_view: one view of a synthetic kernel map, by plain integers"""
+    _fields_ = [("n_pad", ctypes.c_int64), ("n_in", ctypes.c_int64), ("n_out", ctypes.c_int64), ("KS", ctypes.c_int), ("K", ctypes.c_int),
+                ("has_nbr", ctypes.c_int), ("has_tile_k", ctypes.c_int), ("has_out_row", ctypes.c_int)]
+
+
+class ConvPlanQuery(ctypes.Structure):
+    """lgs_conv_plan_query"""
+    _fields_ = [("fwd", ConvPlanView), ("bwd", ConvPlanView), ("ks", ctypes.c_int), ("op", ctypes.c_int), ("transposed", ctypes.c_int),
+                ("cin", ctypes.c_int), ("cout", ctypes.c_int), ("dtype", ctypes.c_int), ("epilogue", ctypes.c_int)]
+
+
+class ConvPlanRegion(ctypes.Structure):
+    _fields_ = [("offset", ctypes.c_int64), ("bytes", ctypes.c_int64)]
+
+
+class ConvPlanInfo(ctypes.Structure):
+    """lgs_conv_plan_info: what lgs_debug_conv_plan answers (no GPU needed)"""
+    _fields_ = [(n, ctypes.c_int) for n in ("path", "tile_id", "sc", "wb", "tm", "nc", "nb_total", "ncp", "nbp", "gc", "wld")] + \
+               [("total", ctypes.c_int64)] + \
+               [(n, ctypes.c_int) for n in ("pad_input", "scratch_out", "packed_ext_ok", "split", "bn_rows", "can_accumulate")] + \
+               [("grid_x", ctypes.c_int64), ("grid_y", ctypes.c_int), ("grid_z", ctypes.c_int)] + \
+               [(n, ConvPlanRegion) for n in ("packed", "padded_in", "scratch", "bias", "partials")] + \
+               [("bytes_total", ctypes.c_int64), ("workspace_bytes", ctypes.c_int64),
+                ("q_bn_partial_rows", ctypes.c_int), ("q_can_accumulate", ctypes.c_int), ("pack_desc", PackDesc)]
+
 
 class BnParams(ctypes.Structure):
     """lgs_bn_params"""
@@ -79,7 +106,7 @@ _lib = None
 # every symbol include/lgs_engine.h declares; tests check the built library exports all of them
 EXPORTS = [
     "lgs_abi_version", "lgs_last_error",
-    "lgs_tuning_set", "lgs_tuning_get", "lgs_tuning_describe", "lgs_debug_dispatch_counts",
+    "lgs_tuning_set", "lgs_tuning_get", "lgs_tuning_describe", "lgs_debug_dispatch_counts", "lgs_debug_conv_plan",
     "lgs_manager_create", "lgs_manager_destroy", "lgs_manager_insert", "lgs_manager_stride2", "lgs_manager_check",
     "lgs_manager_parent_of", "lgs_manager_map_size", "lgs_manager_get_coords", "lgs_manager_kernel_map",
     "lgs_kmap_export",
@@ -148,6 +175,7 @@ def lib():
         "lgs_conv_forward": [vp, ci, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, ci, ci, vp],
         "lgs_conv_pack_desc": [vp, ci, ci, ci, ci, ci, ctypes.POINTER(PackDesc)],
         "lgs_pack_weights_batch": [vp, ci, i64, vp],
+        "lgs_debug_conv_plan": [ctypes.POINTER(ConvPlanQuery), ctypes.POINTER(ConvPlanInfo)],
         "lgs_conv_bn_partial_rows": [vp, ci, ci, ci],
         "lgs_conv_dgrad": [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, vp],
         "lgs_sgd_step": [vp, vp, vp, vp, i64, cf, cf, cf, cf, ci, vp],
