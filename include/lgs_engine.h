@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LGS_ABI_VERSION 15
+#define LGS_ABI_VERSION 16
 
 enum lgs_dtype { LGS_F32 = 0, LGS_BF16 = 1 };
 
@@ -207,9 +207,9 @@ int lgs_conv_dgrad_accumulate(lgs_kmap *km, int transposed, const void *grad_out
 /* grad_weight[K,cin,cout] (float32, overwritten) */
 int lgs_conv_wgrad(lgs_kmap *km, int transposed, const void *in, int cin, const void *grad_out, int cout,
                    float *grad_weight, int dtype, void *workspace, int in_row_stride /* elements; 0 = cin */, void *stream);
-/* 1 if lgs_conv_wgrad can read `in` through `in_row_stride` for this shape (only the position-stationary bf16 kernel does;
- * it declines e.g. for >= 4 GiB at the wider stride, odd channel counts, or when forced off), else 0: the caller then
- * passes a contiguous copy.  The Python host asks before every strided weight gradient instead of letting the call fail. */
+/* 1 if the kernel that serves this call reads `in` through a row stride in place (k_wgrad_ps without padded rows and
+ * k_wgrad_wide do; neither serves e.g. >= 4 GiB at the wider stride or odd channel counts), else 0: the caller then passes a
+ * contiguous copy.  The Python host asks before every strided weight gradient instead of letting the call fail. */
 int lgs_conv_wgrad_supports_stride(const lgs_kmap *km, int transposed, int cin, int cout, int dtype, int in_row_stride);
 
 /* lgs_debug_conv_plan: the launch plan of a forward (op 0) / dgrad (op 1) convolution on a SYNTHETIC kernel map given by plain
@@ -242,6 +242,38 @@ typedef struct lgs_conv_plan_info {
   lgs_pack_desc pack_desc;
 } lgs_conv_plan_info;
 int lgs_debug_conv_plan(const lgs_conv_plan_query *q, lgs_conv_plan_info *out);
+
+/* lgs_debug_wgrad_plan (ABI 16): the same for lgs_conv_wgrad -- which kernel serves the call, its launch parameters and workspace
+ * regions, and what lgs_conv_workspace_bytes(op 2) / lgs_conv_wgrad_supports_stride answer on that map
+ * (tests/test_wgrad_plan_cpu.py).  One partial slab is [K][pad_a][pad_b] floats, whichever kernel writes it. */
+typedef struct lgs_wgrad_plan_query {
+  lgs_conv_plan_view fwd, bwd;
+  int ks, transposed, cin, cout, dtype, in_row_stride;
+} lgs_wgrad_plan_query;
+typedef struct lgs_wgrad_plan_info {
+  int path;                /* 0 empty map, 1 k_wgrad_wide, 2 k_wgrad_ps, 3 k_wgrad_bf16 (pair list), 4 fp32 (k_wgrad_f32*) */
+  int bwd_view;            /* the view the kernel walks: 0 the map's fwd, 1 its bwd */
+  int in_place;            /* 1: the kernel reads `in` through in_row_stride as it lies */
+  int pad_in, pad_gout;    /* channels the input / gradient rows are zero-padded to in the workspace, 0 = read as they are */
+  int all_cus;             /* k_wgrad_ps: all 32 CUs of every XCD instead of PS_CUS (the padded colour input) */
+  int f32_kernel;          /* fp32 path, operands on the 16-byte grid: 0 k_wgrad_f32, 1 k_wgrad_f32_lds, 2 k_wgrad_f32s_lds */
+  int t0, t1;              /* template parameters: KIND, NCS (k_wgrad_ps) / NCI, NCO (k_wgrad_bf16) / NCB, 0 (fp32) */
+  int pad_a, pad_b;        /* channel extents of a partial slab */
+  int slots;               /* partial slabs per kernel offset set: ps lanes / pair-list and fp32 slots / wide position ranges */
+  int64_t span;            /* positions per slot, range (pair list, fp32) or workgroup range (wide) */
+  int n_ranges, kpw;       /* k_wgrad_bf16: position ranges dealt to the slots, kernel offsets per workgroup */
+  int tasks_a, tasks_b;    /* channel tiles per slab side: ci / co tasks, gathered / stationary slices, 256-channel tiles */
+  int cpl, n_chunks, xcd_map;   /* k_wgrad_ps: chunks per lane, 128-position chunks, slices of a lane pinned to one XCD */
+  int ntile;               /* k_wgrad_wide: 256-position compaction tiles */
+  int64_t grid_x; int grid_y, grid_z, lds_bytes;   /* the main launch (dynamic LDS) */
+  int64_t reduce_blocks;   /* 256-thread workgroups of the reduce launch */
+  lgs_conv_plan_region partials, padded_in, padded_gout, ww_count, ww_offset, ww_total, ww_pair_in, ww_pair_out;
+  int64_t bytes_total;
+  /* the public queries on the same map */
+  int64_t workspace_bytes;
+  int supports_stride;
+} lgs_wgrad_plan_info;
+int lgs_debug_wgrad_plan(const lgs_wgrad_plan_query *q, lgs_wgrad_plan_info *out);
 
 /* ---- fused batch-norm / ReLU / residual ------------------------------------------------------
  * replaces ME.MinkowskiBatchNorm (.bn = nn.BatchNorm1d over all rows) + MinkowskiReLU + `out += residual`

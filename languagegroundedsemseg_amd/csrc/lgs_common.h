@@ -105,9 +105,21 @@ __device__ inline uint16_t f32_to_bf16(float f) {  // round to nearest even
 }
 __device__ inline float ld_elem(const float *p) { return *p; }
 __device__ inline float ld_elem(const bf16_t *p) { return bf16_to_f32(*p); }
+// LDS-DMA kernels: the LDS destination of a buffer_load ... lds, and s_waitcnt vmcnt(n) with expcnt / lgkmcnt left alone (gfx9 encoding)
+#define LGS_AS3(p) ((__attribute__((address_space(3))) void *)(p))
+#define LGS_VMCNT(n) __builtin_amdgcn_s_waitcnt((((n) & 15) | (7 << 4) | (15 << 8) | (((n) >> 4) << 14)))
 #endif
 
+// lgs_wgrad.hip: everything a weight-gradient call decides on the host (kernel, tile, grid, workspace regions), see wgrad_plan()
+using WgradPlan = lgs_wgrad_plan_info;
+enum WgradPath { kWgEmpty = 0, kWgWide = 1, kWgPs = 2, kWgPairs = 3, kWgF32 = 4 };
 int64_t wgrad_workspace_bytes(const lgs_kmap *km, int cin, int cout, int dtype);
+// the next region of a workspace that is laid out front to back
+inline lgs_conv_plan_region take_region(int64_t &used, int64_t bytes) {
+  const lgs_conv_plan_region r = {used, align256(bytes)};
+  used += r.bytes;
+  return r;
+}
 // 1x1 stride-1 convolutions of the big maps as a streaming GEMM (lgs_pointwise.hip)
 bool pointwise_supported(const View &v, int K, int g_real, int o_real, int64_t in_ld);
 int launch_pointwise(const View &v, const void *in, int64_t in_ld, int g_real, const float *w, int cin_w, int cout_w, int transposed,
@@ -119,9 +131,10 @@ int launch_pointwise_f32(const View &v, const void *in, int64_t in_ld, int g_rea
 int launch_conv_wide(const View &v, const void *in, int cin_real, int in_ld, const void *wp, int nb_total, int ncp, int nbp, int K,
                      void *out, int cout_real, const float *bias, int gc64, hipStream_t s);
 // lgs_wgrad_wide.hip: per-offset dense GEMM over compacted pair lists for >= 256 x 256 channel 3^3 weight gradients (bf16)
-int64_t wgrad_wide_workspace_bytes(const View &v, int cin, int cout);
-int conv_wgrad_wide(const View &v, const void *in, int cin, int in_ld, const void *gout, int cout, float *gw, void *workspace,
-                    hipStream_t s, bool *done);
+// (wgrad_wide_plan fills p and answers true where that kernel serves the call; in_ld = row stride of `in` in elements)
+bool wgrad_wide_plan(const View &v, int cin, int cout, int in_ld, WgradPlan &p);
+int launch_wgrad_wide(const View &v, const WgradPlan &p, const void *in, int cin, int in_ld, const void *gout, int cout, float *gw,
+                      void *workspace, hipStream_t s);
 // order `stream` after the construction of km's manager's maps (they are built on the manager's own stream)
 int kmap_wait(lgs_kmap *km, hipStream_t stream);
 int segmap_wait(lgs_segmap *sm, hipStream_t stream);

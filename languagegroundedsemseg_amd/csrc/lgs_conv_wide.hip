@@ -39,8 +39,6 @@ namespace lgs {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2w __attribute__((ext_vector_type(2)));
-#define LGS_AS3(p) ((__attribute__((address_space(3))) void *)(p))
-#define LGS_VMCNT(n) __builtin_amdgcn_s_waitcnt((((n) & 15) | (7 << 4) | (15 << 8) | (((n) >> 4) << 14)))
 // The 8 accumulator tiles live in FIXED accumulation registers a[0:127] (the unified register file is split 128 + 128 at
 // two waves per SIMD): tile (row block j, column block n) = a[32 j + 16 n : 32 j + 16 n + 15].  They are NOT C++ values:
 // the asm statements of the main loop and of the epilogue name them literally and list all of a0..a127 as clobbered, so

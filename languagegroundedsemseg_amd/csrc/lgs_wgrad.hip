@@ -797,9 +797,6 @@ struct PsArgs {
 };
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-#define LGS_AS3(p) ((__attribute__((address_space(3))) void *)(p))
-// s_waitcnt immediates (gfx9 encoding): vmcnt = N with expcnt / lgkmcnt left alone
-#define LGS_VMCNT(n) __builtin_amdgcn_s_waitcnt((((n) & 15) | (7 << 4) | (15 << 8) | (((n) >> 4) << 14)))
 
 __host__ __device__ constexpr int ps_wave_lds(int nw) { return 3 * nw * 1024 + 2 * (nw * 512 + 64); }
 
@@ -1140,7 +1137,13 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce_ps(const float *__restrict
 }
 
 // ------------------------------------------------------------------------------------ host side
-struct WgradPlan {
+// Everything a weight-gradient call decides on the host is computed ONCE by wgrad_plan() from the map, the channel counts, the
+// dtype, the row stride and the tuning knobs: which kernel serves the call, its tile / slice parameters, grid and LDS bytes, and
+// where every workspace region lies.  lgs_conv_wgrad, the workspace and stride queries and the CLIP anchor gradient read it, so
+// they cannot disagree.  WgradPlan is lgs_wgrad_plan_info, which lgs_debug_wgrad_plan hands out as it stands.
+
+// ---- slots and tiles of the pair-list kernels (k_wgrad_bf16; k_wgrad_f32*)
+struct PairPlan {
   int S;          // partial slots
   int64_t span;   // positions per slot
   int cin_pad, cout_pad;
@@ -1150,9 +1153,11 @@ struct WgradPlan {
   int kpw;        // bf16 path: kernel offsets per workgroup (one per wave)
   int n_ranges;   // bf16 path: position ranges of `span` voxels, dealt round-robin to the S lanes
 };
+// LDS of one k_wgrad_bf16 wave: the compacted pair list and the two row tiles
+constexpr int pair_wave_bytes(int nci, int nco) { return 2 * kQ * 4 + 16 * tile_stride(32 * nci) + 16 * tile_stride(32 * nco); }
 
-inline WgradPlan wgrad_plan(const View &v, int cin, int cout, int dtype) {
-  WgradPlan p{};
+inline PairPlan pair_plan(const View &v, int cin, int cout, int dtype) {
+  PairPlan p{};
   p.cin_pad = pad32(cin);
   p.cout_pad = pad32(cout);
   const int nbi = p.cin_pad / 32, nbo = p.cout_pad / 32;
@@ -1176,8 +1181,7 @@ inline WgradPlan wgrad_plan(const View &v, int cin, int cout, int dtype) {
     // kernel): S is what fits the chip's workgroup slots (LDS bound, <= 4 per CU), a multiple of 8 (XCD pinning), and
     // every lane costs one partial slab of K x Cin x Cout floats
     const int64_t KG = (v.K + p.kpw - 1) / p.kpw, tasks = (int64_t)p.n_ci_tasks * p.n_co_tasks;
-    const int wave_bytes = 2 * kQ * 4 + 16 * tile_stride(32 * p.nci) + 16 * tile_stride(32 * p.nco);
-    int wg_per_cu = (160 * 1024) / (4 * wave_bytes);
+    int wg_per_cu = (160 * 1024) / (4 * pair_wave_bytes(p.nci, p.nco));
     if (wg_per_cu > 4) wg_per_cu = 4;
     if (wg_per_cu < 1) wg_per_cu = 1;
     const int64_t slots = 256 * (int64_t)wg_per_cu;
@@ -1215,7 +1219,7 @@ inline WgradPlan wgrad_plan(const View &v, int cin, int cout, int dtype) {
     int64_t chunks = (v.n_pad + kWgChunk - 1) / kWgChunk;
     int64_t S = chunks / 4;
     if (S < 1) S = 1;
-    if (S > 128) S = 128;     // (64 until round 5: 27 x 64 workgroups of very unequal work -- the centre offset has ~7 x a corner's pairs -- left a long tail)
+    if (S > 128) S = 128;
     while (S > 1 && S * per > (1ll << 30)) S /= 2;
     int64_t cps = (chunks + S - 1) / S;
     p.span = cps * kWgChunk;
@@ -1225,20 +1229,23 @@ inline WgradPlan wgrad_plan(const View &v, int cin, int cout, int dtype) {
   return p;
 }
 
-// ---- plan of the position-stationary kernel
+// ---- slices and lanes of the position-stationary kernel
 struct PsPlan {
   bool ok = false;
-  int noff = 0, ncs = 0;
+  int ncs = 0;
   int cg_pad = 0, cs_pad = 0, n_cg = 0, n_cs = 0, n_lanes = 0, cpl = 0, n_chunks = 0, xcd_map = 1;
   int64_t partial_bytes = 0;
 };
-inline PsPlan ps_plan(const View &v, int cg, int cs, int cus_override = 0) {
+// dynamic LDS of one k_wgrad_ps<KIND, NCS> workgroup: the double-buffered stationary tile and the eight waves' gather rings
+constexpr int ps_lds_bytes(int kind, int ncs) {
+  return 2 * kPsChunk * tile_stride(32 * ncs) + (kind == 27 ? 5 * ps_wave_lds(3) + 3 * ps_wave_lds(4) : 8 * ps_wave_lds(1));
+}
+inline PsPlan ps_plan(const View &v, int cg, int cs, bool all_cus) {
   PsPlan p;
   if (!(v.K == 27 || v.K == 8) || v.KS != v.K || v.nbr == nullptr || v.n_pad < kPsChunk || v.n_pad % kPsChunk != 0) return p;
   if (cg % 8 != 0 || cs % 8 != 0) return p;
   p.cg_pad = pad32(cg); p.cs_pad = pad32(cs);
   const int nbs = p.cs_pad / 32;
-  p.noff = v.K == 27 ? 4 : 1;
   // K = 27: <= 3 blocks (4 offsets x 3 blocks = 192 accumulators).  Every stationary slice re-gathers all neighbour rows, and
   // gather instructions are what a wide-channel launch is made of (PMC at 512 x 512: 83 M vector-memory instructions
   // for 68 M MFMAs): from 8 blocks on, 3-block slices are used even when the last one is partly padding (16 blocks:
@@ -1255,15 +1262,14 @@ inline PsPlan ps_plan(const View &v, int cg, int cs, int cus_override = 0) {
   // One (K = 27: LDS / register bound) or two workgroups per CU.  Workgroup b runs on XCD b % 8 and the slices of a lane
   // are placed on one XCD (they share its rows in that L2), so the lanes of an XCD must fit ITS 32 CUs: with 3 slices
   // 85 lanes would put 33 workgroups on five of the XCDs and the 33rd runs alone in a second round (measured 2x).
-  const int lds_wg = 2 * kPsChunk * tile_stride(32 * p.ncs) + (v.K == 27 ? 5 * ps_wave_lds(3) + 3 * ps_wave_lds(4) : 8 * ps_wave_lds(1));
-  const int wg_per_cu = v.K == 27 ? 1 : (2 * lds_wg <= 160 * 1024 ? 2 : 1);
+  const int wg_per_cu = v.K == 27 ? 1 : (2 * ps_lds_bytes(v.K, p.ncs) <= 160 * 1024 ? 2 : 1);
   // CUs per XCD the kernel fills: 20 of 32 (tuning knob PS_CUS).  A workgroup owns its CU (all registers, all LDS) for the
   // whole launch, and the kernel runs next to the dgrad / BatchNorm chain of the compute stream: with every CU taken, each
   // compute-stream kernel waits for weight-gradient workgroups to retire before it gets anywhere.  Leaving 12 CUs per XCD makes
   // the weight gradients ~1.3 x longer on their own stream (which has the slack) and the 8-scene step 0.7 ms shorter
   // (32: 29.97, 28: 29.6, 24: 29.4, 20: 29.27, 16: 29.36 ms; `finalize`, the side stream's tail, stays 0.40 ms down to 20)
-  const int cus_env = cus_override > 0 ? cus_override : (int)tune(T_PS_CUS);
-  const int per_xcd = (cus_env >= 4 && cus_env <= 32 ? cus_env : 32) * wg_per_cu, n_sl = p.n_cg * p.n_cs;
+  const int cus = all_cus ? 32 : (int)tune(T_PS_CUS);
+  const int per_xcd = (cus >= 4 && cus <= 32 ? cus : 32) * wg_per_cu, n_sl = p.n_cg * p.n_cs;
   p.xcd_map = n_sl <= per_xcd ? 1 : 0;
   int lanes = p.xcd_map ? 8 * (per_xcd / n_sl) : (8 * per_xcd) / n_sl;
   if (lanes < 1) lanes = 1;
@@ -1278,50 +1284,120 @@ inline PsPlan ps_plan(const View &v, int cg, int cs, int cus_override = 0) {
   p.ok = p.partial_bytes <= (2ll << 30);
   return p;
 }
-inline bool ps_enabled() {
-  return tune(T_WGRAD_PS) != 0;   // debugging knob: 0 forces the pair-list kernel
+
+// k_wgrad_ps on the forward view v (3^3, or the coarse-stationary 2^3 view), or false where it declines (WGRAD_PS = 0 forces
+// the pair-list kernel: debugging).  transposed = 0: gathered operand = in (rows of v's input side), stationary = gout;
+// transposed = 1 (the transposed conv that reuses the strided conv's map): gathered = gout (fine rows), stationary = in
+// (coarse rows).  pad_in > 0 (forward direction): `in` is first zero-padded to pad_in channels behind the partial slabs -- the
+// 3-channel colour input of the network's first convolution, whose weight gradient is the LAST launch of the backward pass
+// (`finalize` waits for exactly it; the pair-list kernel took 0.31 ms at 1.2 M voxels); nothing runs beside it, so it takes all
+// 32 CUs of every XCD instead of PS_CUS.
+inline bool ps_path(WgradPlan &p, const View &v, int transposed, int cin, int cout, int in_ld, int pad_in) {
+  if (tune(T_WGRAD_PS) == 0) return false;
+  const int c = pad_in ? pad_in : cin, ld = pad_in ? pad_in : in_ld;
+  const int cg = transposed ? cout : c, cs = transposed ? c : cout;
+  const PsPlan ps = ps_plan(v, cg, cs, pad_in != 0);
+  if (!ps.ok) return false;
+  // both operands and the neighbour table go through 32-bit buffer descriptors, the rows in 16-byte pieces
+  const int g_ld = transposed ? cg : ld, s_ld = transposed ? ld : cs;
+  if ((g_ld * 2) % 16 != 0 || (s_ld * 2) % 16 != 0) return false;
+  const uint64_t g_b = (uint64_t)v.n_in * g_ld * 2, s_b = (uint64_t)v.n_out * s_ld * 2, n_b = (uint64_t)v.KS * v.n_pad * 4;
+  if (!(g_b < 0xfffff000ull && s_b < 0xfffff000ull && n_b < 0xfffff000ull)) return false;
+  p.path = kWgPs; p.in_place = pad_in == 0; p.pad_in = pad_in; p.all_cus = pad_in != 0;
+  p.t0 = v.K; p.t1 = ps.ncs; p.pad_a = ps.cg_pad; p.pad_b = ps.cs_pad; p.tasks_a = ps.n_cg; p.tasks_b = ps.n_cs;
+  p.slots = ps.n_lanes; p.cpl = ps.cpl; p.n_chunks = ps.n_chunks; p.xcd_map = ps.xcd_map;
+  p.grid_x = (int64_t)(ps.xcd_map ? (ps.n_lanes + 7) / 8 * 8 : ps.n_lanes) * ps.n_cg * ps.n_cs; p.grid_y = p.grid_z = 1;
+  p.lds_bytes = ps_lds_bytes(v.K, ps.ncs);
+  p.reduce_blocks = ((int64_t)v.K * (transposed ? cout : cin) * ((cs + 3) / 4) + 255) / 256;
+  int64_t used = 0;
+  p.partials = take_region(used, ps.partial_bytes);
+  if (pad_in) p.padded_in = take_region(used, v.n_in * (int64_t)pad_in * 2);
+  p.bytes_total = used;
+  return true;
 }
 
-// bytes of the zero-padded input copy the fp32 path makes for input widths off the 4-channel grid (the 3-channel colour input)
-inline int64_t f32_pad_bytes(const View &v, int cin, int cout) {
-  return (cin % 4 != 0 && cout % 4 == 0 && tune(T_WGRAD_F32_LDS) != 0) ? align256(v.n_in * (int64_t)((cin + 3) / 4 * 4) * 4) : 0;
+// The one plan.  No HIP call, no table is read.  The kernels are tried in the order of preference; each declines for reasons of
+// its own (knobs, channel grids, the 4 GiB descriptor limits, partial-slab caps) and the pair-list / fp32 kernels take what is
+// left -- they read contiguous rows only (in_place = 0), which lgs_conv_wgrad holds against the call's row stride.
+WgradPlan wgrad_plan(const lgs_kmap &km, int transposed, int cin, int cout, int dtype, int in_row_stride) {
+  WgradPlan p = {};
+  const View &v = transposed ? km.bwd : km.fwd;  // same view as the forward
+  if (v.n_pad == 0) return p;
+  if (dtype == LGS_BF16 && km.fwd.n_pad > 0 && (km.ks == 3 || km.ks == 2)) {
+    const int ld = in_row_stride > 0 ? in_row_stride : cin;
+    const bool k3 = km.ks == 3 && !transposed;
+    if (k3 && wgrad_wide_plan(km.fwd, cin, cout, ld, p)) return p;
+    if (k3 && cin % 8 != 0 && cout % 8 == 0 && ld == cin && ps_path(p, km.fwd, 0, cin, cout, ld, (cin + 7) / 8 * 8)) return p;
+    if (ps_path(p, km.fwd, transposed, cin, cout, ld, 0)) return p;
+  }
+  const PairPlan pp = pair_plan(v, cin, cout, dtype);
+  p.bwd_view = transposed ? 1 : 0;
+  p.pad_a = pp.cin_pad; p.pad_b = pp.cout_pad; p.slots = pp.S; p.span = pp.span;
+  p.reduce_blocks = ((int64_t)v.K * cin * ((cout + 3) / 4) + 255) / 256;
+  int64_t used = 0;
+  p.partials = take_region(used, (int64_t)pp.S * v.K * pp.cin_pad * pp.cout_pad * 4);
+  if (dtype == LGS_F32) {
+    p.path = kWgF32; p.t0 = pp.ncb;
+    // input widths off the 4-channel grid (the 3 colour channels of the network's first convolution, the last launch of the backward
+    // pass): rows zero-padded to 16 bytes go through the staged kernels instead of k_wgrad_f32's one 4-byte load per lane and
+    // operand (1.39 ms at 1.2 M voxels).  Gradient rows off the grid (odd head widths) keep k_wgrad_f32.
+    const int64_t mode = tune(T_WGRAD_F32_LDS);
+    if (mode != 0 && cin % 4 != 0 && cout % 4 == 0) p.pad_in = (cin + 3) / 4 * 4;
+    const int c = p.pad_in ? p.pad_in : cin;
+    // 2: bf16-split products everywhere; 3: only where they are also faster stand-alone (>= 96 input channels, <= 128 outputs)
+    if (mode != 0 && c % 4 == 0 && cout % 4 == 0) p.f32_kernel = (mode == 2 || (mode >= 3 && c >= 96 && cout <= 128)) ? 2 : 1;
+    if (p.pad_in) p.padded_in = take_region(used, v.n_in * (int64_t)p.pad_in * 4);
+    p.grid_x = pp.S; p.grid_y = v.K; p.grid_z = (pp.cout_pad / (32 * pp.ncb)) * ((pp.cin_pad / 32 + 3) / 4);
+  } else {
+    p.path = kWgPairs; p.t0 = pp.nci; p.t1 = pp.nco; p.n_ranges = pp.n_ranges; p.kpw = pp.kpw; p.tasks_a = pp.n_ci_tasks; p.tasks_b = pp.n_co_tasks;
+    // rows off the 8-channel grid are zero-padded behind the partials: the 3-channel colour input, and the gradient of the
+    // 3-channel offset head of the instance-segmentation model (96 -> 3; the reduce kernel drops the padding)
+    if (cin % 8 != 0) { p.pad_in = (cin + 7) / 8 * 8; p.padded_in = take_region(used, v.n_in * (int64_t)p.pad_in * 2); }
+    if (cout % 8 != 0) { p.pad_gout = (cout + 7) / 8 * 8; p.padded_gout = take_region(used, v.n_out * (int64_t)p.pad_gout * 2); }
+    p.grid_x = (int64_t)((pp.S + 7) / 8 * 8) * ((v.K + pp.kpw - 1) / pp.kpw) * pp.n_ci_tasks * pp.n_co_tasks; p.grid_y = p.grid_z = 1;
+    p.lds_bytes = 4 * pair_wave_bytes(pp.nci, pp.nco);
+  }
+  p.bytes_total = used;
+  return p;
 }
 
+// one buffer per map and shape serves every call the caller can make with it: either `transposed` where legal, contiguous
+// or strided input
 int64_t wgrad_workspace_bytes(const lgs_kmap *km, int cin, int cout, int dtype) {
-  WgradPlan a = wgrad_plan(km->fwd, cin, cout, dtype), b = wgrad_plan(km->bwd, cin, cout, dtype);
-  int64_t per = (int64_t)km->K * pad32(cin) * (a.cout_pad > b.cout_pad ? a.cout_pad : b.cout_pad) * 4;
-  int64_t bytes = align256((int64_t)(a.S > b.S ? a.S : b.S) * per) + 256;
-  if (dtype == LGS_BF16) {   // position-stationary kernel: forward direction (gathered = in) and transposed (gathered = gout)
-    PsPlan f = ps_plan(km->fwd, cin, cout), t = ps_plan(km->fwd, cout, cin);
-    const int64_t pb = (f.ok ? f.partial_bytes : 0) > (t.ok ? t.partial_bytes : 0) ? (f.ok ? f.partial_bytes : 0) : (t.ok ? t.partial_bytes : 0);
-    if (align256(pb) + 256 > bytes) bytes = align256(pb) + 256;
-    const int64_t wb = wgrad_wide_workspace_bytes(km->fwd, cin, cout);
-    if (wb > bytes) bytes = wb;
-  }
-  if (dtype == LGS_F32) {   // zero-padded input copy behind the partial slabs (conv_wgrad_f32path)
-    const int64_t pf = f32_pad_bytes(km->fwd, cin, cout), pb = f32_pad_bytes(km->bwd, cin, cout);
-    bytes += (pf > pb ? pf : pb) + 256;
-  }
-  if (dtype == LGS_BF16 && cin % 8 != 0) {
-    int64_t nmax = km->fwd.n_in > km->bwd.n_in ? km->fwd.n_in : km->bwd.n_in;
-    const int c8 = (cin + 7) / 8 * 8;
-    const int64_t padded = align256(nmax * (int64_t)c8 * 2);
-    bytes += padded;
-    // ... or the position-stationary kernel on the padded rows (lgs_conv_wgrad): partial slabs | padded input
-    const PsPlan f8 = ps_plan(km->fwd, c8, cout, 32);
-    if (f8.ok && align256(f8.partial_bytes) + 256 + padded + 256 > bytes) bytes = align256(f8.partial_bytes) + 256 + padded + 256;
-  }
-  if (dtype == LGS_BF16 && cout % 8 != 0) {
-    int64_t nmax = km->fwd.n_out > km->bwd.n_out ? km->fwd.n_out : km->bwd.n_out;
-    bytes += align256(nmax * (int64_t)((cout + 7) / 8 * 8) * 2);
-  }
+  int64_t bytes = 0;
+  for (int transposed = 0; transposed <= (km->ks == 3 ? 0 : 1); ++transposed)
+    for (int in_row_stride : {0, cin + 8}) {
+      const int64_t b = wgrad_plan(*km, transposed, cin, cout, dtype, in_row_stride).bytes_total;
+      if (b > bytes) bytes = b;
+    }
   return bytes;
 }
 
+// ---- dispatch: the run-time tile of a plan -> the kernel instance.  f is called with std::integral_constant<int, n>.
+template <int MAX, typename F>
+int with_blocks(int n, F &&f) {
+  if constexpr (MAX >= 1) return n == MAX ? f(std::integral_constant<int, MAX>()) : with_blocks<MAX - 1>(n, f);
+  LGS_REQUIRE(false, "weight gradient: no kernel instance for this tile");
+}
+
+template <typename T>
+__global__ void k_pad_rows(const T *__restrict__ src, int64_t n, int c, int cpad, T *__restrict__ dst) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * cpad) return;
+  int64_t r = i / cpad;
+  int ch = (int)(i % cpad);
+  dst[i] = ch < c ? src[r * c + ch] : (T)0;
+}
+// rows [n][c] -> region r of the workspace as [n][cpad], zero-padded
+template <typename T>
+const T *pad_rows_into(void *workspace, const lgs_conv_plan_region &r, const void *src, int64_t n, int c, int cpad, hipStream_t s) {
+  T *dst = reinterpret_cast<T *>(reinterpret_cast<char *>(workspace) + r.offset);
+  if (n * cpad > 0) LGS_KLAUNCH(k_pad_rows<T>, (unsigned)((n * cpad + 255) / 256), 256, 0, s, reinterpret_cast<const T *>(src), n, c, cpad, dst);
+  return dst;
+}
+
 template <int NCI, int NCO>
-int launch_wgrad_bf16(const View &v, const WgradPlan &p, const bf16_t *in, int cin, const bf16_t *go, int cout,
-                      float *partial, hipStream_t s) {
-  constexpr int CA = 32 * NCI, CG = 32 * NCO;
+int launch_wgrad_bf16(const View &v, const WgradPlan &p, const bf16_t *in, int cin, const bf16_t *go, int cout, float *partial, hipStream_t s) {
   const uint64_t in_b = (uint64_t)v.n_in * cin * 2, go_b = (uint64_t)v.n_out * cout * 2;
   LGS_REQUIRE(in_b < 0xfffff000ull && go_b < 0xfffff000ull,
               "bf16 wgrad: a feature tensor of 4 GiB or more is beyond the 32-bit buffer-descriptor path");
@@ -1330,203 +1406,101 @@ int launch_wgrad_bf16(const View &v, const WgradPlan &p, const bf16_t *in, int c
   constexpr int ACC = 16 * NCI * NCO, RING1 = 4 * (NCI + NCO);
   constexpr int OCC = (ACC + 2 * RING1 <= 192) ? 2 : 1;
   constexpr int D = OCC == 1 ? 3 : ((ACC + 4 * RING1 <= 192) ? 4 : (ACC + 3 * RING1 <= 192) ? 3 : 2);
-  constexpr int WAVE_BYTES = 2 * kQ * 4 + 16 * tile_stride(CA) + 16 * tile_stride(CG);
-  static_assert(4 * WAVE_BYTES >= NCI * NCO * 16 * 64 * 4, "staging LDS must hold one accumulator tile");
-  const int n_tasks = p.n_ci_tasks * p.n_co_tasks;
-  const int n_ranges = p.n_ranges, n_lanes = p.S;
-  const int KG = (v.K + p.kpw - 1) / p.kpw;
-  const unsigned nblocks = (unsigned)(((n_lanes + 7) / 8) * 8 * KG * n_tasks);
-  LGS_KLAUNCH((k_wgrad_bf16<NCI, NCO, D, OCC>), dim3(nblocks), 256, 4 * WAVE_BYTES, s, v, in, cin, go, cout, p.cin_pad,
-                     p.cout_pad, p.span, p.kpw, p.n_ci_tasks, n_tasks, n_ranges, n_lanes, partial, (unsigned)in_b, (unsigned)go_b);
+  static_assert(4 * pair_wave_bytes(NCI, NCO) >= NCI * NCO * 16 * 64 * 4, "staging LDS must hold one accumulator tile");
+  // every (slot, k, ci, co) element of `partial` is written exactly once by the wave that owns it
+  LGS_KLAUNCH((k_wgrad_bf16<NCI, NCO, D, OCC>), dim3((unsigned)p.grid_x), 256, p.lds_bytes, s, v, in, cin, go, cout, p.pad_a, p.pad_b, p.span,
+              p.kpw, p.tasks_a, p.tasks_a * p.tasks_b, p.n_ranges, p.slots, partial, (unsigned)in_b, (unsigned)go_b);
+  return 0;
+}
+
+int conv_wgrad_pairs(const View &v, const WgradPlan &p, const void *in_v, int cin, const void *gout_v, int cout, float *gw, void *workspace,
+                     hipStream_t s) {
+  float *partial = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + p.partials.offset);
+  const bf16_t *in = reinterpret_cast<const bf16_t *>(in_v), *go = reinterpret_cast<const bf16_t *>(gout_v);
+  if (p.pad_in) in = pad_rows_into<bf16_t>(workspace, p.padded_in, in, v.n_in, cin, p.pad_in, s);
+  if (p.pad_gout) go = pad_rows_into<bf16_t>(workspace, p.padded_gout, go, v.n_out, cout, p.pad_gout, s);
+  const int rc = with_blocks<4>(p.t0, [&](auto nci) {
+    return with_blocks<4>(p.t1, [&](auto nco) {
+      if constexpr (nci() == 4 && nco() == 4) { LGS_REQUIRE(false, "bf16 wgrad: no kernel instance for this tile"); }
+      else return launch_wgrad_bf16<nci(), nco()>(v, p, in, p.pad_in ? p.pad_in : cin, go, p.pad_gout ? p.pad_gout : cout, partial, s);
+    });
+  });
+  if (rc) return rc;
+  LGS_KLAUNCH(k_wgrad_reduce, (unsigned)p.reduce_blocks, 256, 0, s, partial, p.slots, v.K, p.pad_a, p.pad_b, cin, cout, gw);
+  LGS_HIP(hipGetLastError());
+  return 0;
+}
+
+template <int NCB>
+int launch_wgrad_f32(const View &v, const WgradPlan &p, const float *in, int cin, const float *go, int cout, float *partial, hipStream_t s) {
+  const dim3 grid((unsigned)p.grid_x, (unsigned)p.grid_y, (unsigned)p.grid_z);
+  // the one thing the plan cannot see: the staged kernels load 16 bytes at a time, so both operands must lie on the 16-byte grid
+  // (either alternative uses the same workspace regions)
+  const bool aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(go)) & 15u) == 0;
+  if (aligned && p.f32_kernel == 2) LGS_KLAUNCH((k_wgrad_f32s_lds<NCB>), grid, 256, 0, s, v, in, cin, go, cout, p.pad_a, p.pad_b, p.span, partial);
+  else if (aligned && p.f32_kernel == 1) LGS_KLAUNCH((k_wgrad_f32_lds<NCB>), grid, 256, 0, s, v, in, cin, go, cout, p.pad_a, p.pad_b, p.span, partial);
+  else LGS_KLAUNCH((k_wgrad_f32<float, NCB>), grid, 256, 0, s, v, in, cin, go, cout, p.pad_a, p.pad_b, p.span, partial);
+  return 0;
+}
+
+int conv_wgrad_f32(const View &v, const WgradPlan &p, const void *in_v, int cin, const void *gout_v, int cout, float *gw, void *workspace,
+                   hipStream_t s) {
+  float *partial = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + p.partials.offset);
+  const float *in = reinterpret_cast<const float *>(in_v), *go = reinterpret_cast<const float *>(gout_v);
+  if (p.pad_in) in = pad_rows_into<float>(workspace, p.padded_in, in, v.n_in, cin, p.pad_in, s);
+  const int rc = with_blocks<4>(p.t0, [&](auto ncb) { return launch_wgrad_f32<ncb()>(v, p, in, p.pad_in ? p.pad_in : cin, go, cout, partial, s); });
+  if (rc) return rc;
+  LGS_KLAUNCH(k_wgrad_reduce, (unsigned)p.reduce_blocks, 256, 0, s, partial, p.slots, v.K, p.pad_a, p.pad_b, cin, cout, gw);   // drops the padding
+  LGS_HIP(hipGetLastError());
   return 0;
 }
 
 template <int KIND, int NCS>
-int launch_wgrad_ps(const PsArgs &a, const PsPlan &p, hipStream_t s) {
-  constexpr int SGB = tile_stride(32 * NCS);
-  constexpr int LDS = 2 * kPsChunk * SGB + (KIND == 27 ? 5 * ps_wave_lds(3) + 3 * ps_wave_lds(4) : 8 * ps_wave_lds(1));
-  static_assert(LDS <= 160 * 1024, "k_wgrad_ps: LDS budget of one CU");
+int launch_wgrad_ps(const PsArgs &a, const WgradPlan &p, hipStream_t s) {
+  static_assert(ps_lds_bytes(KIND, NCS) <= 160 * 1024, "k_wgrad_ps: LDS budget of one CU");
   static bool attr_set = false;
   if (!attr_set) {
-    LGS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgrad_ps<KIND, NCS>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+    LGS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgrad_ps<KIND, NCS>), hipFuncAttributeMaxDynamicSharedMemorySize, ps_lds_bytes(KIND, NCS)));
     attr_set = true;
   }
-  const unsigned nblocks = (unsigned)((p.xcd_map ? ((p.n_lanes + 7) / 8) * 8 : p.n_lanes) * p.n_cg * p.n_cs);
-  LGS_KLAUNCH((k_wgrad_ps<KIND, NCS>), dim3(nblocks), 512, LDS, s, a);
+  LGS_KLAUNCH((k_wgrad_ps<KIND, NCS>), dim3((unsigned)p.grid_x), 512, ps_lds_bytes(KIND, NCS), s, a);
   return 0;
 }
 
-// gw[K][cin][cout] through the position-stationary kernel.  v = the map's forward view (3^3, or the coarse-stationary
-// 2^3 view); transposed = 0: gathered operand = in (rows of v's input side), stationary = gout;  transposed = 1 (the
-// transposed conv that reuses the strided conv's map): gathered = gout (fine rows), stationary = in (coarse rows).
-int conv_wgrad_ps(const View &v, int transposed, const bf16_t *in, int cin, const bf16_t *go, int cout, float *gw, void *workspace,
-                  hipStream_t s, bool *done, int in_ld, int cin_out = -1, int cus_override = 0) {
-  // cin_out (> 0, forward direction only): `in` was zero-padded to cin channels by the caller; gw has cin_out input channels
-  *done = false;
-  if (!ps_enabled()) return 0;
-  const int cg = transposed ? cout : cin, cs = transposed ? cin : cout;
-  const PsPlan p = ps_plan(v, cg, cs, cus_override);
-  if (!p.ok) return 0;
-  const int64_t g_rows = v.n_in, s_rows = v.n_out;
-  const int g_ld = transposed ? cg : (in_ld > 0 ? in_ld : cg), s_ld = transposed ? (in_ld > 0 ? in_ld : cs) : cs;
-  if ((g_ld * 2) % 16 != 0 || (s_ld * 2) % 16 != 0) return 0;
-  const uint64_t g_b = (uint64_t)g_rows * g_ld * 2, s_b = (uint64_t)s_rows * s_ld * 2, n_b = (uint64_t)v.KS * v.n_pad * 4, o_b = (uint64_t)v.n_pad * 4;
-  if (!(g_b < 0xfffff000ull && s_b < 0xfffff000ull && n_b < 0xfffff000ull)) return 0;   // beyond the 32-bit descriptor path
+// gw[K][cin][cout] through the position-stationary kernel (operands as ps_path lays them out)
+int conv_wgrad_ps(const View &v, const WgradPlan &p, int transposed, const void *in_v, int cin, const void *gout_v, int cout, int in_ld, float *gw,
+                  void *workspace, hipStream_t s) {
+  const bf16_t *in = reinterpret_cast<const bf16_t *>(in_v), *go = reinterpret_cast<const bf16_t *>(gout_v);
+  if (p.pad_in) { in = pad_rows_into<bf16_t>(workspace, p.padded_in, in, v.n_in, cin, p.pad_in, s); in_ld = p.pad_in; }
+  const int c = p.pad_in ? p.pad_in : cin;
   PsArgs a;
   a.v = v; a.v.mirror = 0;
   a.G = transposed ? go : in; a.S = transposed ? in : go;
-  a.g_ld = g_ld; a.s_ld = s_ld;
-  a.cg_real = cg; a.cs_real = cs; a.cg_pad = p.cg_pad; a.cs_pad = p.cs_pad; a.n_cg = p.n_cg; a.n_cs = p.n_cs;
-  a.n_lanes = p.n_lanes; a.chunks_per_lane = p.cpl; a.n_chunks = p.n_chunks; a.xcd_map = p.xcd_map;
-  a.partial = reinterpret_cast<float *>(workspace);
-  a.g_bytes = (unsigned)g_b; a.s_bytes = (unsigned)s_b; a.nbr_bytes = (unsigned)n_b; a.orow_bytes = (unsigned)o_b;
-  int rc = 0;
-  if (p.noff == 4) {
-    if (p.ncs == 1) rc = launch_wgrad_ps<27, 1>(a, p, s);
-    else if (p.ncs == 2) rc = launch_wgrad_ps<27, 2>(a, p, s);
-    else rc = launch_wgrad_ps<27, 3>(a, p, s);
-  } else {
-    if (p.ncs == 1) rc = launch_wgrad_ps<8, 1>(a, p, s);
-    else if (p.ncs == 2) rc = launch_wgrad_ps<8, 2>(a, p, s);
-    else if (p.ncs == 3) rc = launch_wgrad_ps<8, 3>(a, p, s);
-    else rc = launch_wgrad_ps<8, 4>(a, p, s);
-  }
+  a.cg_real = transposed ? cout : c; a.cs_real = transposed ? c : cout;
+  a.g_ld = transposed ? cout : in_ld; a.s_ld = transposed ? in_ld : cout;
+  a.cg_pad = p.pad_a; a.cs_pad = p.pad_b; a.n_cg = p.tasks_a; a.n_cs = p.tasks_b;
+  a.n_lanes = p.slots; a.chunks_per_lane = p.cpl; a.n_chunks = p.n_chunks; a.xcd_map = p.xcd_map;
+  a.partial = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + p.partials.offset);
+  a.g_bytes = (unsigned)((uint64_t)v.n_in * a.g_ld * 2); a.s_bytes = (unsigned)((uint64_t)v.n_out * a.s_ld * 2);
+  a.nbr_bytes = (unsigned)((uint64_t)v.KS * v.n_pad * 4); a.orow_bytes = (unsigned)((uint64_t)v.n_pad * 4);
+  const int rc = with_blocks<4>(p.t1, [&](auto ncs) {
+    if constexpr (ncs() == 4) { LGS_REQUIRE(p.t0 == 8, "k_wgrad_ps: no kernel instance for this slice"); return launch_wgrad_ps<8, 4>(a, p, s); }
+    else return p.t0 == 27 ? launch_wgrad_ps<27, ncs()>(a, p, s) : launch_wgrad_ps<8, ncs()>(a, p, s);
+  });
   if (rc) return rc;
-  const int cg_o = (!transposed && cin_out > 0) ? cin_out : cg;
-  const int64_t total = (int64_t)v.K * cg_o * ((cs + 3) / 4);
-  LGS_KLAUNCH(k_wgrad_reduce_ps, (unsigned)((total + 255) / 256), 256, 0, s, a.partial, p.n_lanes, v.K, p.cg_pad, p.cs_pad, cg_o, cs,
-                     transposed, gw);
-  LGS_HIP(hipGetLastError());
-  *done = true;
-  return 0;
-}
-
-__global__ void k_pad_rows_bf16(const bf16_t *__restrict__ src, int64_t n, int c, int cpad, bf16_t *__restrict__ dst) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n * cpad) return;
-  int64_t r = i / cpad;
-  int ch = (int)(i % cpad);
-  dst[i] = ch < c ? src[r * c + ch] : (bf16_t)0;
-}
-
-int conv_wgrad_bf16(const View &v, const void *in_v, int cin, const void *gout_v, int cout, float *gw, void *workspace,
-                    hipStream_t s) {
-  WgradPlan p = wgrad_plan(v, cin, cout, LGS_BF16);
-  char *wsb = reinterpret_cast<char *>(workspace);
-  float *partial = reinterpret_cast<float *>(wsb);
-  const bf16_t *in = reinterpret_cast<const bf16_t *>(in_v), *go = reinterpret_cast<const bf16_t *>(gout_v);
-  const int cin_real = cin, cout_real = cout;
-  int64_t pad_off = align256((int64_t)p.S * v.K * p.cin_pad * p.cout_pad * 4);
-  if (cin % 8 != 0) {  // e.g. the 3-channel colour input of conv0p1s1: zero-pad rows to 8 channels behind the partials
-    const int c8 = (cin + 7) / 8 * 8;
-    bf16_t *padded = reinterpret_cast<bf16_t *>(wsb + pad_off);
-    int64_t tot = v.n_in * (int64_t)c8;
-    if (tot > 0) LGS_KLAUNCH(k_pad_rows_bf16, (unsigned)((tot + 255) / 256), 256, 0, s, in, v.n_in, cin, c8, padded);
-    in = padded;
-    cin = c8;
-    pad_off += align256(tot * 2);
-  }
-  if (cout % 8 != 0) {  // e.g. the 3-channel offset head of the instance-segmentation model (96 -> 3): pad the gradient rows the
-    // same way (the fp32-style fallback took 6.6 ms for this launch at 1.2 M voxels; the reduce kernel drops the padding)
-    const int c8 = (cout + 7) / 8 * 8;
-    bf16_t *padded = reinterpret_cast<bf16_t *>(wsb + pad_off);
-    int64_t tot = v.n_out * (int64_t)c8;
-    if (tot > 0) LGS_KLAUNCH(k_pad_rows_bf16, (unsigned)((tot + 255) / 256), 256, 0, s, go, v.n_out, cout, c8, padded);
-    go = padded;
-    cout = c8;
-  }
-  // every (slot, k, ci, co) element of `partial` is written exactly once by the wave that owns it
-#define LGS_WG(A, B) if (p.nci == A && p.nco == B) { launch_wgrad_bf16<A, B>(v, p, in, cin, go, cout, partial, s); } else
-  LGS_WG(1, 1) LGS_WG(1, 2) LGS_WG(1, 3) LGS_WG(1, 4)
-  LGS_WG(2, 1) LGS_WG(2, 2) LGS_WG(2, 3) LGS_WG(2, 4)
-  LGS_WG(3, 1) LGS_WG(3, 2) LGS_WG(3, 3) LGS_WG(3, 4)
-  LGS_WG(4, 1) LGS_WG(4, 2) LGS_WG(4, 3)
-  { LGS_REQUIRE(false, "bf16 wgrad: no kernel instance for this tile"); }
-#undef LGS_WG
-  int64_t total = (int64_t)v.K * cin_real * ((cout_real + 3) / 4);
-  LGS_KLAUNCH(k_wgrad_reduce, (unsigned)((total + 255) / 256), 256, 0, s, partial, p.S, v.K, p.cin_pad, p.cout_pad, cin_real,
-                     cout_real, gw);
+  // the reduce kernel drops the padded input channels: gw has cin of them
+  LGS_KLAUNCH(k_wgrad_reduce_ps, (unsigned)p.reduce_blocks, 256, 0, s, a.partial, p.slots, v.K, p.pad_a, p.pad_b, transposed ? cout : cin,
+              transposed ? c : cout, transposed, gw);
   LGS_HIP(hipGetLastError());
   return 0;
 }
 
-__global__ void k_pad_rows_f32(const float *__restrict__ src, int64_t n, int c, int cpad, float *__restrict__ dst) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n * cpad) return;
-  int64_t r = i / cpad;
-  int ch = (int)(i % cpad);
-  dst[i] = ch < c ? src[r * c + ch] : 0.f;
-}
-
-template <typename T>
-int conv_wgrad_f32path(const View &v, const void *in_v, int cin, const void *gout_v, int cout, float *gw, void *workspace,
-                       hipStream_t s) {
-  WgradPlan p = wgrad_plan(v, cin, cout, LGS_F32);
-  float *partial = reinterpret_cast<float *>(workspace);
-  const T *in = reinterpret_cast<const T *>(in_v);
-  const T *go = reinterpret_cast<const T *>(gout_v);
-  const int cin_gw = cin;                 // rows of gw[k] (the reduction drops the padding)
-  if constexpr (sizeof(T) == 4) {
-    // the network's first convolution (3 colour channels; round 6): its weight gradient is the LAST launch of the backward pass,
-    // `finalize` waits for exactly it.  Rows padded to 4 channels (16 bytes) go through the staged kernels instead of
-    // k_wgrad_f32's one 4-byte load per lane and operand (1.39 ms at 1.2 M voxels)
-    if (f32_pad_bytes(v, cin, cout) > 0) {
-      const int c4 = (cin + 3) / 4 * 4;
-      float *padded = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) +
-                                                align256((int64_t)p.S * v.K * p.cin_pad * p.cout_pad * 4) + 256);
-      const int64_t tot = v.n_in * (int64_t)c4;
-      if (tot > 0) LGS_KLAUNCH(k_pad_rows_f32, (unsigned)((tot + 255) / 256), 256, 0, s, reinterpret_cast<const float *>(in), v.n_in, cin, c4, padded);
-      in = reinterpret_cast<const T *>(padded);
-      cin = c4;
-    }
-  }
-  int n_cot = p.cout_pad / (32 * p.ncb);
-  int n_cig = (p.cin_pad / 32 + 3) / 4;
-  dim3 grid((unsigned)p.S, (unsigned)v.K, (unsigned)(n_cot * n_cig));
-  bool staged = false;
-  if constexpr (sizeof(T) == 4) {
-    const float *fi = reinterpret_cast<const float *>(in), *fg = reinterpret_cast<const float *>(go);
-    // rows off the 16-byte grid (the 3-channel input layer: 1.99 vs 1.70 ms staged element by element, odd head widths) keep k_wgrad_f32
-    if (tune(T_WGRAD_F32_LDS) != 0 && cin % 4 == 0 && cout % 4 == 0 && (reinterpret_cast<uintptr_t>(fi) & 15u) == 0 &&
-        (reinterpret_cast<uintptr_t>(fg) & 15u) == 0) {
-      staged = true;
-#define LGS_WF(KERNEL)                                                                                                          \
-      switch (p.ncb) {                                                                                                         \
-        case 4: LGS_KLAUNCH((KERNEL<4>), grid, 256, 0, s, v, fi, cin, fg, cout, p.cin_pad, p.cout_pad, p.span, partial); break;  \
-        case 3: LGS_KLAUNCH((KERNEL<3>), grid, 256, 0, s, v, fi, cin, fg, cout, p.cin_pad, p.cout_pad, p.span, partial); break;  \
-        case 2: LGS_KLAUNCH((KERNEL<2>), grid, 256, 0, s, v, fi, cin, fg, cout, p.cin_pad, p.cout_pad, p.span, partial); break;  \
-        default: LGS_KLAUNCH((KERNEL<1>), grid, 256, 0, s, v, fi, cin, fg, cout, p.cin_pad, p.cout_pad, p.span, partial); break; \
-      }
-      // 2: bf16-split products everywhere; 3: only where they are also faster stand-alone (>= 96 input channels, <= 128 outputs)
-      const int64_t mode = tune(T_WGRAD_F32_LDS);
-      const bool split = mode == 2 || (mode >= 3 && cin >= 96 && cout <= 128);
-      if (split) { LGS_WF(k_wgrad_f32s_lds) } else { LGS_WF(k_wgrad_f32_lds) }
-#undef LGS_WF
-    }
-  }
-  if (!staged) switch (p.ncb) {
-    case 4: LGS_KLAUNCH((k_wgrad_f32<T, 4>), grid, 256, 0, s, v, in, cin, go, cout, p.cin_pad, p.cout_pad, p.span, partial); break;
-    case 3: LGS_KLAUNCH((k_wgrad_f32<T, 3>), grid, 256, 0, s, v, in, cin, go, cout, p.cin_pad, p.cout_pad, p.span, partial); break;
-    case 2: LGS_KLAUNCH((k_wgrad_f32<T, 2>), grid, 256, 0, s, v, in, cin, go, cout, p.cin_pad, p.cout_pad, p.span, partial); break;
-    default: LGS_KLAUNCH((k_wgrad_f32<T, 1>), grid, 256, 0, s, v, in, cin, go, cout, p.cin_pad, p.cout_pad, p.span, partial); break;
-  }
-  int64_t total = (int64_t)v.K * cin_gw * ((cout + 3) / 4);
-  LGS_KLAUNCH(k_wgrad_reduce, (unsigned)((total + 255) / 256), 256, 0, s, partial, p.S, v.K, p.cin_pad, p.cout_pad, cin_gw,
-                     cout, gw);
-  LGS_HIP(hipGetLastError());
-  return 0;
-}
-
-}  // namespace lgs
-
-using namespace lgs;
-
-namespace lgs {
 // ---- gradient of the CLIP text-anchor loss w.r.t. the (normalised) anchors: d/dT^ = G^T F^, with G[n, a] the 4-sparse upstream
 // gradient dL/dS[n, a] (-g_dpos at the voxel's class, -g_dneg / K at each of its K negatives; zero rows for ignored voxels).
 // That is the weight gradient of the 1x1 "convolution" S = F^ T^^T, so it runs on the weight-gradient kernels: the coefficient
 // rows (already scaled by 1/|f_n|, so that the RAW features are the other operand) are materialised once in the feature dtype
-// and the identity-map launch of k_wgrad_bf16 / k_wgrad_f32 contracts them with the features (fixed summation order).
+// behind the plan's regions and the identity-map launch of k_wgrad_bf16 / k_wgrad_f32 contracts them with the features (fixed
+// summation order).
 template <typename T>
 __global__ void k_clip_coef_rows(const int64_t *__restrict__ labels, const int64_t *__restrict__ neg, int k_neg, int64_t ignore,
                                  const float *__restrict__ inv_norm, const float *__restrict__ g_dpos, const float *__restrict__ g_dneg,
@@ -1553,20 +1527,28 @@ __global__ void k_clip_coef_rows(const int64_t *__restrict__ labels, const int64
     if constexpr (sizeof(T) == 4) row[idx[q]] = val[q]; else row[idx[q]] = f32_to_bf16(val[q]);
   }
 }
-inline View clip_identity_view(int64_t n) {
-  View v;
+// the identity map over n rows, its plan (c features x a8 anchors) and the coefficient rows behind the plan's regions
+struct ClipAnchorPlan { lgs_kmap km; WgradPlan p; lgs_conv_plan_region coef; int64_t bytes_total; };
+inline ClipAnchorPlan clip_anchor_plan(int64_t n, int c, int a8, int dtype) {
+  ClipAnchorPlan cp;
+  View &v = cp.km.fwd;
   v.n_pad = pad_rows(n); v.n_out = n; v.n_in = n; v.KS = 1; v.K = 1;
-  return v;
+  cp.km.bwd = v; cp.km.ks = 1; cp.km.K = 1;
+  cp.p = wgrad_plan(cp.km, 0, c, a8, dtype, 0);
+  cp.bytes_total = cp.p.bytes_total;
+  cp.coef = take_region(cp.bytes_total, n * (int64_t)a8 * esize(dtype));
+  return cp;
 }
+
 }  // namespace lgs
+
+using namespace lgs;
 
 extern "C" {
 
 int64_t lgs_clip_anchor_grad_workspace_bytes(int64_t n, int c, int n_anchor, int dtype) {
-  const int a8 = (n_anchor + 7) / 8 * 8;
-  const View v = clip_identity_view(n);
-  const WgradPlan p = wgrad_plan(v, c, a8, dtype);
-  return align256((int64_t)p.S * p.cin_pad * p.cout_pad * 4) + align256(n * (int64_t)a8 * esize(dtype)) + 512;
+  if (n <= 0) return 256;      // nothing is planned or launched for an empty batch
+  return clip_anchor_plan(n, c, (n_anchor + 7) / 8 * 8, dtype).bytes_total;
 }
 
 int lgs_clip_loss_backward_anchors(const void *feat, int64_t n, int c, int n_anchor, const int64_t *labels, const int64_t *neg,
@@ -1582,10 +1564,9 @@ int lgs_clip_loss_backward_anchors(const void *feat, int64_t n, int c, int n_anc
     LGS_HIP(hipMemsetAsync(grad_anchors_t, 0, sizeof(float) * (size_t)c * a8, s));
     return 0;
   }
-  const View v = clip_identity_view(n);
-  const WgradPlan p = wgrad_plan(v, c, a8, dtype);
-  char *ws = reinterpret_cast<char *>(workspace);
-  void *G = ws + align256((int64_t)p.S * p.cin_pad * p.cout_pad * 4);
+  const ClipAnchorPlan cp = clip_anchor_plan(n, c, a8, dtype);
+  const View &v = cp.km.fwd;
+  void *G = reinterpret_cast<char *>(workspace) + cp.coef.offset;
   LGS_HIP(hipMemsetAsync(G, 0, (size_t)n * a8 * esize(dtype), s));
   const unsigned blocks = (unsigned)((n + 255) / 256);
   if (dtype == LGS_F32)
@@ -1596,74 +1577,60 @@ int lgs_clip_loss_backward_anchors(const void *feat, int64_t n, int c, int n_anc
                        n_anchor, a8, reinterpret_cast<bf16_t *>(G));
   LGS_HIP(hipGetLastError());
   // grad_anchors_t[c][a8] = F^T G   (transposed: the caller reads column a as d/dT^_a)
-  if (dtype == LGS_F32) return conv_wgrad_f32path<float>(v, feat, c, G, a8, grad_anchors_t, workspace, s);
-  return conv_wgrad_bf16(v, feat, c, G, a8, grad_anchors_t, workspace, s);
+  if (dtype == LGS_F32) return conv_wgrad_f32(v, cp.p, feat, c, G, a8, grad_anchors_t, workspace, s);
+  return conv_wgrad_pairs(v, cp.p, feat, c, G, a8, grad_anchors_t, workspace, s);
 }
 
-}  // extern "C"
-
-extern "C" {
-
 int lgs_conv_wgrad_supports_stride(const lgs_kmap *km, int transposed, int cin, int cout, int dtype, int in_row_stride) {
-  // mirrors the conditions under which conv_wgrad_ps accepts the call (it is the only weight-gradient kernel that reads a
-  // column slice of a wider row-major tensor in place)
-  if (!km || dtype != LGS_BF16 || !(km->ks == 3 || km->ks == 2) || km->fwd.n_pad == 0 || !ps_enabled()) return 0;
-  if (transposed && km->ks == 3) return 0;
-  if (in_row_stride <= 0 || in_row_stride == cin) return 1;
-  const int cg = transposed ? cout : cin, cs = transposed ? cin : cout;
-  const PsPlan p = ps_plan(km->fwd, cg, cs);
-  if (!p.ok || (in_row_stride * 2) % 16 != 0) return 0;
-  const View &v = km->fwd;
-  const uint64_t rows = transposed ? (uint64_t)v.n_out : (uint64_t)v.n_in;
-  return rows * (uint64_t)in_row_stride * 2 < 0xfffff000ull ? 1 : 0;
+  if (!km || (transposed && km->ks == 3) || !(dtype == LGS_F32 || dtype == LGS_BF16)) return 0;
+  return wgrad_plan(*km, transposed, cin, cout, dtype, in_row_stride).in_place;
 }
 
 int lgs_conv_wgrad(lgs_kmap *km, int transposed, const void *in, int cin, const void *grad_out, int cout,
                    float *grad_weight, int dtype, void *workspace, int in_row_stride, void *stream) {
   LGS_REQUIRE(km && grad_weight && workspace, "lgs_conv_wgrad: null argument");
   LGS_REQUIRE(!(transposed && km->ks == 3), "transposed 3x3x3 convolution is not part of the model family");
-  const View &v = transposed ? km->bwd : km->fwd;  // same view as the forward
-  View vv = v; vv.mirror = 0;
+  LGS_REQUIRE(dtype == LGS_F32 || dtype == LGS_BF16, "lgs_conv_wgrad: unknown dtype");
   hipStream_t s = (hipStream_t)stream;
   if (kmap_wait(km, s)) return 1;
-  if (vv.n_pad == 0) {
+  const WgradPlan p = wgrad_plan(*km, transposed, cin, cout, dtype, in_row_stride);
+  if (p.path == kWgEmpty) {
     LGS_HIP(hipMemsetAsync(grad_weight, 0, sizeof(float) * (size_t)km->K * cin * cout, s));
     return 0;
   }
-  LGS_REQUIRE(dtype == LGS_BF16 || in_row_stride == 0 || in_row_stride == cin, "lgs_conv_wgrad: strided input needs bf16");
-  if (dtype == LGS_F32) return conv_wgrad_f32path<float>(vv, in, cin, grad_out, cout, grad_weight, workspace, s);
-  if (dtype == LGS_BF16) {
-    if (km->fwd.n_pad > 0 && km->ks == 3 && !transposed) {
-      bool done = false;
-      int rc = conv_wgrad_wide(km->fwd, in, cin, in_row_stride, grad_out, cout, grad_weight, workspace, s, &done);
-      if (rc || done) return rc;
-    }
-    if (km->fwd.n_pad > 0 && (km->ks == 3 || km->ks == 2)) {
-      bool done = false;
-      int rc = 0;
-      if (!transposed && km->ks == 3 && cin % 8 != 0 && cout % 8 == 0 && (in_row_stride == 0 || in_row_stride == cin) && ps_enabled()) {
-        // the 3-channel colour input of the network's first convolution: rows zero-padded to 8 channels behind the partial slabs,
-        // then the position-stationary kernel (this launch is the LAST of the backward pass: `finalize` waits for exactly it;
-        // the pair-list kernel took 0.31 ms at 1.2 M voxels)
-        const int c8 = (cin + 7) / 8 * 8;
-        // nothing runs beside the last launch of the backward pass: all 32 CUs of every XCD instead of PS_CUS
-        const PsPlan pp = ps_plan(km->fwd, c8, cout, 32);
-        if (pp.ok) {
-          bf16_t *padded = reinterpret_cast<bf16_t *>(reinterpret_cast<char *>(workspace) + align256(pp.partial_bytes) + 256);
-          const int64_t tot = km->fwd.n_in * (int64_t)c8;
-          if (tot > 0) LGS_KLAUNCH(k_pad_rows_bf16, (unsigned)((tot + 255) / 256), 256, 0, s, reinterpret_cast<const bf16_t *>(in), km->fwd.n_in, cin, c8, padded);
-          rc = conv_wgrad_ps(km->fwd, 0, padded, c8, reinterpret_cast<const bf16_t *>(grad_out), cout, grad_weight, workspace, s, &done, 0, cin, 32);
-          if (rc || done) return rc;
-        }
-      }
-      rc = conv_wgrad_ps(km->fwd, transposed, reinterpret_cast<const bf16_t *>(in), cin, reinterpret_cast<const bf16_t *>(grad_out),
-                         cout, grad_weight, workspace, s, &done, in_row_stride);
-      if (rc || done) return rc;
-    }
-    LGS_REQUIRE(in_row_stride == 0 || in_row_stride == cin, "lgs_conv_wgrad: a strided input is only supported by the position-stationary bf16 kernel");
-    return conv_wgrad_bf16(vv, in, cin, grad_out, cout, grad_weight, workspace, s);
+  const bool strided = in_row_stride != 0 && in_row_stride != cin;
+  LGS_REQUIRE(dtype == LGS_BF16 || !strided, "lgs_conv_wgrad: strided input needs bf16");
+  LGS_REQUIRE(!strided || p.in_place, "lgs_conv_wgrad: a strided input is only supported by the position-stationary bf16 kernel");
+  View v = p.bwd_view ? km->bwd : km->fwd;
+  v.mirror = 0;
+  const int in_ld = in_row_stride > 0 ? in_row_stride : cin;
+  switch (p.path) {
+    case kWgWide: return launch_wgrad_wide(v, p, in, cin, in_ld, grad_out, cout, grad_weight, workspace, s);
+    case kWgPs: return conv_wgrad_ps(v, p, transposed, in, cin, grad_out, cout, in_ld, grad_weight, workspace, s);
+    case kWgPairs: return conv_wgrad_pairs(v, p, in, cin, grad_out, cout, grad_weight, workspace, s);
+    default: return conv_wgrad_f32(v, p, in, cin, grad_out, cout, grad_weight, workspace, s);
   }
-  LGS_REQUIRE(false, "lgs_conv_wgrad: unknown dtype");
+}
+
+// the plan of lgs_conv_wgrad on a synthetic map + what the public queries say for it: no HIP call, `present` tables are never read
+int lgs_debug_wgrad_plan(const lgs_wgrad_plan_query *q, lgs_wgrad_plan_info *out) {
+  LGS_REQUIRE(q && out && (q->dtype == LGS_F32 || q->dtype == LGS_BF16) && !(q->transposed && q->ks == 3), "lgs_debug_wgrad_plan: bad argument");
+  static const int32_t present = 0;
+  auto view = [&](const lgs_conv_plan_view &s) {
+    View v;
+    v.n_pad = s.n_pad; v.n_in = s.n_in; v.n_out = s.n_out; v.KS = s.KS; v.K = s.K;
+    if (s.has_nbr) v.nbr = &present;
+    if (s.has_nbr && s.KS > 1) v.mask64 = reinterpret_cast<const uint32_t *>(&present);
+    if (s.has_tile_k) v.tile_k = &present;
+    if (s.has_out_row) v.out_row = &present;
+    return v;
+  };
+  lgs_kmap km;
+  km.ks = q->ks; km.K = q->fwd.K; km.fwd = view(q->fwd); km.bwd = view(q->bwd);
+  *out = wgrad_plan(km, q->transposed, q->cin, q->cout, q->dtype, q->in_row_stride);
+  out->workspace_bytes = lgs_conv_workspace_bytes(&km, q->cin, q->cout, q->dtype, 2);
+  out->supports_stride = lgs_conv_wgrad_supports_stride(&km, q->transposed, q->cin, q->cout, q->dtype, q->in_row_stride);
+  return 0;
 }
 
 }  // extern "C"

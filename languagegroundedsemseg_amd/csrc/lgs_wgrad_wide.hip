@@ -36,8 +36,6 @@
 namespace lgs {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#define LGS_AS3(p) ((__attribute__((address_space(3))) void *)(p))
-#define LGS_VMCNT(n) __builtin_amdgcn_s_waitcnt((((n) & 15) | (7 << 4) | (15 << 8) | (((n) >> 4) << 14)))
 
 constexpr int kWwTile = 256;             // positions per compaction tile
 constexpr int kWwStage = 64;             // pairs per stage
@@ -378,55 +376,46 @@ __global__ __launch_bounds__(256) void k_wgrad_wide_reduce(const float *__restri
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-struct WwPlan {
-  bool ok = false;
-  int ntile = 0, nchunk = 0, chunk = 0, ti = 0, tj = 0;
-  int64_t cnt_b = 0, pair_b = 0, partial_b = 0, total_b = 0;
-};
-inline WwPlan ww_plan(const View &v, int cin, int cout) {
-  WwPlan p;
-  const bool on = tune(T_WGRAD_WIDE) != 0;   // A/B knob
+bool wgrad_wide_plan(const View &v, int cin, int cout, int in_ld, WgradPlan &p) {
   // maps below ~200 k positions keep the position-stationary kernel (level 2, 81 k rows, 256 -> 256: 0.82 vs 0.31 ms); the
   // parity tests lower WW_MIN_ROWS to send in-network layers of a 70 k-voxel scene through this kernel
-  if (!on || v.K != 27 || v.KS != 27 || v.nbr == nullptr || v.n_pad < tune(T_WW_MIN_ROWS) || v.n_pad % kWwTile != 0) return p;
+  if (tune(T_WGRAD_WIDE) == 0 || v.K != 27 || v.KS != 27 || v.nbr == nullptr || v.n_pad < tune(T_WW_MIN_ROWS) || v.n_pad % kWwTile != 0) return false;
+  if (cin < 256 || cout < 256 || cin % 8 != 0 || cout % 8 != 0) return false;
   // positions per workgroup range (a whole number of 256-position tiles): small enough that the rows of the ranges in flight
   // fit the Infinity Cache, large enough that the fp32 partial tiles (256 KB per workgroup) stay a small part of the traffic
-  const int range_env = (int)tune(T_WW_RANGE);   // tuning knob
-  p.chunk = range_env >= 256 ? range_env / 256 * 256 : 16384;
-  if (cin < 256 || cout < 256 || cin % 8 != 0 || cout % 8 != 0) return p;
-  while ((int64_t)27 * ((v.n_pad + p.chunk - 1) / p.chunk) * (((cin + 255) / 256) * 256) * (int64_t)(((cout + 255) / 256) * 256) * 4 > (3ll << 30))
-    p.chunk *= 2;
-  p.ntile = (int)(v.n_pad / kWwTile);
-  p.nchunk = (int)((v.n_pad + p.chunk - 1) / p.chunk);
-  p.ti = (cin + 255) / 256; p.tj = (cout + 255) / 256;
-  p.cnt_b = align256((int64_t)27 * p.ntile * 4);
-  p.pair_b = align256((int64_t)27 * v.n_pad * 4);
-  p.partial_b = (int64_t)27 * p.nchunk * (p.ti * 256) * (int64_t)(p.tj * 256) * 4;
-  p.total_b = 2 * p.cnt_b + 256 + 2 * p.pair_b + align256(p.partial_b);
-  p.ok = p.partial_b <= (3ll << 30);
-  return p;
+  const int range_env = (int)tune(T_WW_RANGE);
+  int64_t chunk = range_env >= 256 ? range_env / 256 * 256 : 16384;
+  const int ti = (cin + 255) / 256, tj = (cout + 255) / 256;
+  const int64_t tile_b = (int64_t)27 * (ti * 256) * (int64_t)(tj * 256) * 4;   // the partial tiles of one range
+  while ((v.n_pad + chunk - 1) / chunk * tile_b > (3ll << 30)) chunk *= 2;
+  // both operands go through 32-bit buffer descriptors, in 16-byte pieces
+  const uint64_t in_b = (uint64_t)v.n_in * in_ld * 2, go_b = (uint64_t)v.n_out * cout * 2;
+  if (!(in_b < 0xfffff000ull && go_b < 0xfffff000ull) || (in_ld * 2) % 16 != 0) return false;
+  p.path = kWgWide; p.in_place = 1;
+  p.pad_a = ti * 256; p.pad_b = tj * 256; p.tasks_a = ti; p.tasks_b = tj;
+  p.ntile = (int)(v.n_pad / kWwTile); p.span = chunk; p.slots = (int)((v.n_pad + chunk - 1) / chunk);
+  p.grid_x = (int64_t)27 * p.slots * ti * tj; p.grid_y = p.grid_z = 1; p.lds_bytes = kWwLds;
+  p.reduce_blocks = ((int64_t)27 * cin * (cout / 4) + 255) / 256;
+  int64_t used = 0;
+  p.ww_count = take_region(used, (int64_t)27 * p.ntile * 4);
+  p.ww_offset = take_region(used, (int64_t)27 * p.ntile * 4);
+  p.ww_total = take_region(used, 27 * 4);
+  p.ww_pair_in = take_region(used, (int64_t)27 * v.n_pad * 4);
+  p.ww_pair_out = take_region(used, (int64_t)27 * v.n_pad * 4);
+  p.partials = take_region(used, p.slots * tile_b);
+  p.bytes_total = used;
+  return true;
 }
 
-int64_t wgrad_wide_workspace_bytes(const View &v, int cin, int cout) {
-  const WwPlan p = ww_plan(v, cin, cout);
-  return p.ok ? p.total_b + 256 : 0;
-}
-
-int conv_wgrad_wide(const View &v, const void *in, int cin, int in_ld, const void *gout, int cout, float *gw, void *workspace,
-                    hipStream_t s, bool *done) {
-  *done = false;
-  const WwPlan p = ww_plan(v, cin, cout);
-  if (!p.ok) return 0;
-  const int ld = in_ld > 0 ? in_ld : cin;
-  const uint64_t in_b = (uint64_t)v.n_in * ld * 2, go_b = (uint64_t)v.n_out * cout * 2;
-  if (!(in_b < 0xfffff000ull && go_b < 0xfffff000ull) || (ld * 2) % 16 != 0) return 0;
+int launch_wgrad_wide(const View &v, const WgradPlan &p, const void *in, int cin, int in_ld, const void *gout, int cout, float *gw,
+                      void *workspace, hipStream_t s) {
   char *ws = reinterpret_cast<char *>(workspace);
-  int32_t *cnt = reinterpret_cast<int32_t *>(ws);
-  int32_t *off = reinterpret_cast<int32_t *>(ws + p.cnt_b);
-  int32_t *total = reinterpret_cast<int32_t *>(ws + 2 * p.cnt_b);
-  int32_t *pin = reinterpret_cast<int32_t *>(ws + 2 * p.cnt_b + 256);
-  int32_t *pout = reinterpret_cast<int32_t *>(ws + 2 * p.cnt_b + 256 + p.pair_b);
-  float *partial = reinterpret_cast<float *>(ws + 2 * p.cnt_b + 256 + 2 * p.pair_b);
+  int32_t *cnt = reinterpret_cast<int32_t *>(ws + p.ww_count.offset);
+  int32_t *off = reinterpret_cast<int32_t *>(ws + p.ww_offset.offset);
+  int32_t *total = reinterpret_cast<int32_t *>(ws + p.ww_total.offset);
+  int32_t *pin = reinterpret_cast<int32_t *>(ws + p.ww_pair_in.offset);
+  int32_t *pout = reinterpret_cast<int32_t *>(ws + p.ww_pair_out.offset);
+  float *partial = reinterpret_cast<float *>(ws + p.partials.offset);
   View vv = v; vv.mirror = 0;
   LGS_KLAUNCH(k_ww_count, dim3(p.ntile), dim3(256), 0, s, vv, p.ntile, cnt);
   LGS_KLAUNCH(k_ww_scan, dim3(27), dim3(256), 0, s, cnt, p.ntile, off, total);
@@ -439,14 +428,11 @@ int conv_wgrad_wide(const View &v, const void *in, int cin, int in_ld, const voi
   WwArgs a;
   a.in = reinterpret_cast<const bf16_t *>(in); a.gout = reinterpret_cast<const bf16_t *>(gout);
   a.pin = pin; a.pout = pout; a.total = total; a.off = off; a.ntile = p.ntile; a.partial = partial; a.stride = v.n_pad;
-  a.cin = cin; a.cout = cout; a.in_ld = ld; a.nchunk = p.nchunk; a.chunk = p.chunk; a.ci_pad = p.ti * 256; a.co_pad = p.tj * 256; a.ti = p.ti; a.tj = p.tj;
-  a.in_bytes = (unsigned)in_b; a.go_bytes = (unsigned)go_b;
-  LGS_KLAUNCH(k_wgrad_wide, dim3((unsigned)(27 * p.nchunk * p.ti * p.tj)), dim3(512), kWwLds, s, a);
-  const int64_t tot = (int64_t)27 * cin * (cout / 4);
-  LGS_KLAUNCH(k_wgrad_wide_reduce, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, partial, total, p.nchunk, p.chunk, a.ci_pad, a.co_pad,
-                     cin, cout, gw);
+  a.cin = cin; a.cout = cout; a.in_ld = in_ld; a.nchunk = p.slots; a.chunk = (int)p.span; a.ci_pad = p.pad_a; a.co_pad = p.pad_b; a.ti = p.tasks_a; a.tj = p.tasks_b;
+  a.in_bytes = (unsigned)((uint64_t)v.n_in * in_ld * 2); a.go_bytes = (unsigned)((uint64_t)v.n_out * cout * 2);
+  LGS_KLAUNCH(k_wgrad_wide, dim3((unsigned)p.grid_x), dim3(512), p.lds_bytes, s, a);
+  LGS_KLAUNCH(k_wgrad_wide_reduce, dim3((unsigned)p.reduce_blocks), dim3(256), 0, s, partial, total, p.slots, (int)p.span, p.pad_a, p.pad_b, cin, cout, gw);
   LGS_HIP(hipGetLastError());
-  *done = true;
   return 0;
 }
 

@@ -10,7 +10,7 @@ import os
 from . import build as _build
 
 LGS_F32, LGS_BF16 = 0, 1
-ABI_VERSION = 15     # LGS_ABI_VERSION of include/lgs_engine.h
+ABI_VERSION = 16     # LGS_ABI_VERSION of include/lgs_engine.h
 
 
 class PackDesc(ctypes.Structure):
@@ -45,6 +45,25 @@ class ConvPlanInfo(ctypes.Structure):
                [(n, ConvPlanRegion) for n in ("packed", "padded_in", "scratch", "bias", "partials")] + \
                [("bytes_total", ctypes.c_int64), ("workspace_bytes", ctypes.c_int64),
                 ("q_bn_partial_rows", ctypes.c_int), ("q_can_accumulate", ctypes.c_int), ("pack_desc", PackDesc)]
+
+
+class WgradPlanQuery(ctypes.Structure):
+    """lgs_wgrad_plan_query"""
+    _fields_ = [("fwd", ConvPlanView), ("bwd", ConvPlanView)] + \
+               [(n, ctypes.c_int) for n in ("ks", "transposed", "cin", "cout", "dtype", "in_row_stride")]
+
+
+class WgradPlanInfo(ctypes.Structure):
+    """lgs_wgrad_plan_info: what lgs_debug_wgrad_plan answers (no GPU needed)"""
+    _fields_ = [(n, ctypes.c_int) for n in ("path", "bwd_view", "in_place", "pad_in", "pad_gout", "all_cus", "f32_kernel", "t0", "t1",
+                                            "pad_a", "pad_b", "slots")] + \
+               [("span", ctypes.c_int64)] + \
+               [(n, ctypes.c_int) for n in ("n_ranges", "kpw", "tasks_a", "tasks_b", "cpl", "n_chunks", "xcd_map", "ntile")] + \
+               [("grid_x", ctypes.c_int64), ("grid_y", ctypes.c_int), ("grid_z", ctypes.c_int), ("lds_bytes", ctypes.c_int),
+                ("reduce_blocks", ctypes.c_int64)] + \
+               [(n, ConvPlanRegion) for n in ("partials", "padded_in", "padded_gout", "ww_count", "ww_offset", "ww_total", "ww_pair_in",
+                                              "ww_pair_out")] + \
+               [("bytes_total", ctypes.c_int64), ("workspace_bytes", ctypes.c_int64), ("supports_stride", ctypes.c_int)]
 
 
 class BnParams(ctypes.Structure):
@@ -106,7 +125,7 @@ _lib = None
 # every symbol include/lgs_engine.h declares; tests check the built library exports all of them
 EXPORTS = [
     "lgs_abi_version", "lgs_last_error",
-    "lgs_tuning_set", "lgs_tuning_get", "lgs_tuning_describe", "lgs_debug_dispatch_counts", "lgs_debug_conv_plan",
+    "lgs_tuning_set", "lgs_tuning_get", "lgs_tuning_describe", "lgs_debug_dispatch_counts", "lgs_debug_conv_plan", "lgs_debug_wgrad_plan",
     "lgs_manager_create", "lgs_manager_destroy", "lgs_manager_insert", "lgs_manager_stride2", "lgs_manager_check",
     "lgs_manager_parent_of", "lgs_manager_map_size", "lgs_manager_get_coords", "lgs_manager_kernel_map",
     "lgs_kmap_export",
@@ -176,6 +195,7 @@ def lib():
         "lgs_conv_pack_desc": [vp, ci, ci, ci, ci, ci, ctypes.POINTER(PackDesc)],
         "lgs_pack_weights_batch": [vp, ci, i64, vp],
         "lgs_debug_conv_plan": [ctypes.POINTER(ConvPlanQuery), ctypes.POINTER(ConvPlanInfo)],
+        "lgs_debug_wgrad_plan": [ctypes.POINTER(WgradPlanQuery), ctypes.POINTER(WgradPlanInfo)],
         "lgs_conv_bn_partial_rows": [vp, ci, ci, ci],
         "lgs_conv_dgrad": [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, vp],
         "lgs_sgd_step": [vp, vp, vp, vp, i64, cf, cf, cf, cf, ci, vp],
