@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LGS_ABI_VERSION 16
+#define LGS_ABI_VERSION 17
 
 enum lgs_dtype { LGS_F32 = 0, LGS_BF16 = 1 };
 
@@ -282,7 +282,10 @@ int lgs_debug_wgrad_plan(const lgs_wgrad_plan_query *q, lgs_wgrad_plan_info *out
  * on return mean[C], invstd[C].  running_mean/var (float32 [C]) updated with `momentum`
  * (unbiased variance), may be NULL; num_batches_tracked (device int64 scalar, nn.BatchNorm1d's buffer) is
  * incremented by the same kernel, may be NULL.  residual may be NULL.  y may alias x.
- * workspace: lgs_bn_workspace_bytes(n, c) bytes of caller-owned device scratch (no allocation inside).
+ * workspace: lgs_bn_workspace_bytes(n, c) bytes of caller-owned device scratch (no allocation inside).  The size is the bound
+ * over every path a BatchNorm entry point can take for (n, c) -- it depends on neither dtype, direction nor the tuning table, so
+ * a caller may keep it per (n, c) and use one buffer for lgs_bn_forward / backward / stats / backward_reduce, whatever the
+ * knobs are when the call is made.
  * conv_partials / conv_partial_rows / pivot: statistics already produced by the preceding lgs_conv_forward (see there);
  * NULL / 0 = compute them from x. */
 int64_t lgs_bn_workspace_bytes(int64_t n, int c);
@@ -331,6 +334,32 @@ int lgs_bn_backward_apply(const void *x, const void *y, const void *dy, int64_t 
                           const float *beta, const float *stats, const float *sums, float inv_n_total,
                           const float *inv_n_device, int relu, void *dx, void *dresidual, int dtype, int64_t dy_row_stride,
                           int64_t y_row_stride, void *stream);
+
+/* lgs_debug_norm_plan (ABI 17): what a BatchNorm call decides on the host, for a call given by plain integers: the path, every
+ * grid and rows-per-workgroup, and the workspace regions, plus what lgs_bn_workspace_bytes answers.  resident_cap stands for the
+ * one thing the engine asks the device (workgroups of the direction's grid-barrier kernel it holds at once).  No HIP call: it
+ * runs without a GPU (tests/test_norm_plan_cpu.py). */
+typedef struct lgs_norm_plan_query {
+  int direction;           /* 0 lgs_bn_forward, 1 lgs_bn_backward, 2 lgs_bn_stats, 3 lgs_bn_backward_reduce */
+  int c, dtype;
+  int conv_partial_rows;   /* rows of the conv epilogue's partial sums (directions 0 and 2), 0 = statistics from x */
+  int resident_cap;
+  int64_t n;
+} lgs_norm_plan_query;
+typedef struct lgs_norm_plan_info {
+  int path;                /* 1 fold (two launches), 2 fused (one grid-barrier launch), 3 three launches */
+  int from_partials;       /* 1: the statistics come from the conv epilogue's rows, x is not reduced */
+  int reduce_grid;         /* workgroups that reduce x: k_colreduce, or the whole fused launch; 0 = none (path 3 from partials) */
+  int64_t rows_per_block;  /* rows of x per workgroup of it */
+  int partial_rpb;         /* conv partial rows folded into one row (k_partial_reduce / step 1 of k_bn_fwd_fused), 0 = none */
+  int fold_rows;           /* partial rows [2c] the fold reads = rows written to the workspace */
+  int fold_grid;           /* path 3: workgroups of k_fold_fwd / k_fold_stats / k_fold_bwd */
+  int apply_grid;          /* workgroups of the apply launch of paths 1 and 3; 0 = none (empty tensor, directions 2 and 3) */
+  lgs_conv_plan_region partials, sums, spill;   /* partial rows; [2c] sums of lgs_bn_backward; dgamma / dbeta of lgs_bn_backward_reduce */
+  int64_t bytes_total;
+  int64_t workspace_bytes; /* lgs_bn_workspace_bytes(n, c) */
+} lgs_norm_plan_info;
+int lgs_debug_norm_plan(const lgs_norm_plan_query *q, lgs_norm_plan_info *out);
 
 /* ---- SyncBatchNorm as one call per direction, on the engine's own RCCL communicator (csrc/lgs_comm.hip) --------
  * replaces the per-layer statistics exchange of ME.MinkowskiSyncBatchNorm (convert_sync_batchnorm, /root/reference/main.py:121-123;

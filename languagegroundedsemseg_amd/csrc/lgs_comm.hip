@@ -174,6 +174,16 @@ inline int mbox_next(lgs_comm *c) {
   if (c->seq == 0) c->seq = 1;
   return 0;
 }
+// SyncBN workspace (byte offsets): BatchNorm scratch at 0 | local record [2C+1], then the records of all ranks [world][2C+1] |
+// gradient sums [2C]
+struct SyncBnLayout {
+  int64_t records, sums, total;
+  SyncBnLayout(int64_t n, int c, int world) {
+    records = align256(lgs_bn_workspace_bytes(n, c));
+    sums = records + align256((int64_t)(world + 1) * (2 * c + 1) * 4);
+    total = sums + align256(2 * c * 4) + 256;
+  }
+};
 }  // namespace
 
 extern "C" {
@@ -292,10 +302,7 @@ int lgs_comm_destroy(lgs_comm *c) {
 
 int lgs_comm_world(const lgs_comm *c) { return c ? c->world : 0; }
 
-int64_t lgs_bn_sync_workspace_bytes(int64_t n, int c, int world) {
-  // BatchNorm scratch | local record [2C+1] | records of all ranks [world][2C+1] | gradient sums [2C]
-  return align256(lgs_bn_workspace_bytes(n, c)) + align256((int64_t)(world + 1) * (2 * c + 1) * 4) + align256(2 * c * 4) + 256;
-}
+int64_t lgs_bn_sync_workspace_bytes(int64_t n, int c, int world) { return SyncBnLayout(n, c, world).total; }
 
 // forward: local (mean, M2, count) -> all-gather of the records -> Chan's combination (+ running statistics) -> normalise
 // (+ residual) (+ ReLU); stats [2C] and inv_n [1] (device: 1 / global rows) are what the backward needs
@@ -304,8 +311,7 @@ int lgs_bn_forward_sync(lgs_comm *comm, const void *x, int64_t n, int c, const f
                         int relu, void *y, float *stats, float *inv_n, int dtype, void *workspace, int64_t y_row_stride, void *stream) {
   LGS_REQUIRE(comm && (comm->comm || (comm->ipc && comm->d_boxes)) && x && y && gamma && beta && stats && inv_n && workspace,
               "lgs_bn_forward_sync: null argument");
-  char *ws = reinterpret_cast<char *>(workspace);
-  float *local = reinterpret_cast<float *>(ws + align256(lgs_bn_workspace_bytes(n, c)));
+  float *local = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + SyncBnLayout(n, c, comm->world).records);
   float *all = local + (2 * c + 1);
   int rc;
   if ((rc = lgs_bn_stats(x, n, c, local, dtype, workspace, nullptr, 0, nullptr, stream))) return rc;
@@ -329,8 +335,7 @@ int lgs_bn_backward_sync(lgs_comm *comm, const void *x, const void *y, const voi
                          float *dbeta, int dtype, void *workspace, int64_t dy_row_stride, int64_t y_row_stride, void *stream) {
   LGS_REQUIRE(comm && (comm->comm || (comm->ipc && comm->d_boxes)) && x && dy && dx && gamma && stats && inv_n && workspace,
               "lgs_bn_backward_sync: null argument");
-  char *ws = reinterpret_cast<char *>(workspace);
-  float *sums = reinterpret_cast<float *>(ws + align256(lgs_bn_workspace_bytes(n, c)) + align256((int64_t)(comm->world + 1) * (2 * c + 1) * 4));
+  float *sums = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + SyncBnLayout(n, c, comm->world).sums);
   int rc;
   if ((rc = lgs_bn_backward_reduce(x, y, dy, n, c, gamma, beta, stats, relu, sums, dgamma, dbeta, dtype, workspace, dy_row_stride, y_row_stride,
                                    stream)))

@@ -11,6 +11,7 @@
 // are reduced per block in LDS, then across blocks through a [blocks, 2C] fp32 scratch that a small fold
 // kernel sums in a fixed order (double accumulation) -> deterministic, no float atomics.
 #include "lgs_common.h"
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 
@@ -184,6 +185,7 @@ __device__ inline void fold_sums(const float *__restrict__ scratch, int nblocks,
 }
 // statistics that arrive as per-tile partial rows from the conv epilogue (BnEpi): fold groups of rows into <= 128 rows
 // of the same [row][2][C] layout, fixed order (deterministic)
+constexpr int kPartialFoldRows = 128;
 __global__ __launch_bounds__(256) void k_partial_reduce(const float *__restrict__ part, int rows, int c2, int rows_per_block,
                                                         float *__restrict__ out) {
   const int r0 = blockIdx.x * rows_per_block, r1 = min(r0 + rows_per_block, rows);
@@ -384,16 +386,9 @@ __global__ __launch_bounds__(kNT) void k_bn_bwd_apply(const T *__restrict__ x, c
   }
 }
 
-inline int reduce_blocks(int64_t n, int64_t *rows_per_block) {
-  // >= 128 rows per block, <= 512 blocks: coarse levels (a few thousand rows) still get tens of blocks -- with 1024
-  // rows per block their reductions were 5-block, 13 us latency chains
-  int64_t nb = (n + 127) / 128;
-  if (nb > 512) nb = 512;
-  if (nb < 1) nb = 1;
-  *rows_per_block = (n + nb - 1) / nb;
-  if (*rows_per_block < 1) *rows_per_block = 1;
-  return (int)((n + *rows_per_block - 1) / *rows_per_block > 0 ? (n + *rows_per_block - 1) / *rows_per_block : 1);
-}
+// k_colreduce as the first of three launches: >= 128 rows per block, <= 512 blocks: coarse levels (a few thousand rows) still get
+// tens of blocks -- with 1024 rows per block their reductions were 5-block, 13 us latency chains
+constexpr int kReduceMaxBlocks = 512;
 
 // ------------------------------------------------------------------------------------------------ one launch per direction
 // A BatchNorm direction is three dependent steps (column sums over all rows -> fold + finish the statistics -> elementwise
@@ -847,11 +842,26 @@ __global__ __launch_bounds__(kNT) void k_bn_bwd_apply_fold(const T *__restrict__
   }
 }
 
-// partial rows / apply workgroups of the two-launch path (knobs BN_FOLD_PARTS / BN_FOLD_GRID)
-inline bool bn_fold_on(int64_t tensor_bytes) { return tune(T_BN_FOLD) != 0 && tensor_bytes <= (tune(T_BN_FOLD_MAX_MB) << 20); }
-inline int fold_parts(int64_t n, int64_t *rows_per_block) {
-  int64_t cap = tune(T_BN_FOLD_PARTS);
-  if (cap < 1 || cap > kFoldParts) cap = kFoldParts;
+// ------------------------------------------------------------------------------------------------ host: one plan per call
+// Everything a BatchNorm call decides on the host is computed ONCE by norm_plan() from (direction, n, c, element size, conv
+// partial rows, resident-workgroup cap, tuning table): the path, every grid and rows-per-block, and where each workspace region
+// lies.  The entry points are plan + one switch; lgs_bn_workspace_bytes is the bound over every plan.  Paths are tried in this
+// order -- the order IS the policy:
+//   fold  (directions that apply, statistics from x, n > 0, BN_FOLD != 0, tensor <= BN_FOLD_MAX_MB): k_colreduce into
+//         <= min(BN_FOLD_PARTS, kFoldParts) partial rows, then k_bn_apply_fold / k_bn_bwd_apply_fold on <= BN_FOLD_GRID workgroups;
+//   fused (directions that apply, BN_FUSED != 0, tensor <= BN_FUSED_MAX_MB -- forward: the smaller of it and BN_FUSED_FWD_MAX_MB --
+//         and the device holds >= 16 workgroups of the kernel at once): ONE launch of <= min(cap, kFusedMaxBlocks, BN_FUSED_BLOCKS);
+//   three: k_colreduce into <= kReduceMaxBlocks rows (or k_partial_reduce: the conv epilogue's rows into <= kPartialFoldRows),
+//         k_fold_*, then the apply on <= kApplyMaxBlocks workgroups (skipped for an empty tensor).
+// lgs_bn_stats and lgs_bn_backward_reduce are the first two launches of `three`.
+using NormPlan = lgs_norm_plan_info;
+enum NormDir { kNormFwd = 0, kNormBwd = 1, kNormStats = 2, kNormBwdReduce = 3 };
+enum NormPath { kNormFold = 1, kNormFused = 2, kNormThree = 3 };
+constexpr int kApplyMaxBlocks = 4096;   // k_bn_apply / k_bn_bwd_apply: grid-stride over the rows
+constexpr int kCoopMinBlocks = 16;      // fewer co-resident workgroups than this: the grid-barrier kernels are not worth it
+
+// n rows over at most `cap` workgroups of at least 128 rows each -> workgroups used (>= 1, also for n == 0)
+inline int row_blocks(int64_t n, int64_t cap, int64_t *rows_per_block) {
   int64_t nb = (n + 127) / 128;
   if (nb > cap) nb = cap;
   if (nb < 1) nb = 1;
@@ -861,14 +871,74 @@ inline int fold_parts(int64_t n, int64_t *rows_per_block) {
   nb = (n + rpb - 1) / rpb;
   return (int)(nb > 0 ? nb : 1);
 }
-inline int fold_grid(int64_t n, int c, int W) {
-  int64_t cap = tune(T_BN_FOLD_GRID);
-  if (cap < 1) cap = 256;
-  const int64_t total = n * (int64_t)(c / W);
-  int64_t g = (total + 2 * kNT - 1) / (2 * kNT);       // two rows per thread and sweep in the forward kernel
-  if (g > cap) g = cap;
-  return (int)(g < 1 ? 1 : g);
+// workgroups of an elementwise launch that gives each thread `per_thread` vectors before it strides; 0 = nothing to launch
+inline int apply_blocks(int64_t n, int c, int W, int per_thread, int64_t cap) {
+  const int64_t total = n * (int64_t)(c / W), g = (total + per_thread * kNT - 1) / (per_thread * kNT);
+  return (int)(g < cap ? g : cap);
 }
+// The scratch of a call is [partial rows][2c] floats, then ONE more row: `sums` (backward) or the dgamma / dbeta spill
+// (lgs_bn_backward_reduce) -- never both in one call.  The size is the bound over every path and knob setting (callers cache it
+// per (n, c) and change knobs afterwards), so it depends on neither: the most rows any splitter makes, that row, and what the
+// size has always carried on top (a second row and 256 bytes) so that it does not move under its callers.
+inline int64_t norm_workspace_bytes(int64_t n, int c) {
+  int64_t rpb, rows = kPartialFoldRows;
+  for (int cap : {kReduceMaxBlocks, kFusedMaxBlocks, kFoldParts}) rows = std::max<int64_t>(rows, row_blocks(n, cap, &rpb));
+  return (int64_t)sizeof(float) * 2 * c * (rows + 2) + 256;
+}
+
+// resident_cap(): workgroups of the direction's grid-barrier kernel the device holds at once (fused_resident); asked only
+// where the knobs and the size allow that path.  partial_rows: the conv epilogue's rows, 0 = statistics from x.  No HIP call.
+template <typename Cap>
+NormPlan norm_plan(int dir, int64_t n, int c, int dtype, int partial_rows, Cap &&resident_cap) {
+  NormPlan p = {};
+  const int W = epl(dtype);
+  const int64_t tensor_bytes = n * (int64_t)c * (int64_t)esize(dtype);
+  const bool applies = dir == kNormFwd || dir == kNormBwd;
+  p.from_partials = (dir == kNormFwd || dir == kNormStats) && partial_rows > 0;
+  if (p.from_partials) {     // wherever it happens (k_partial_reduce, step 1 of k_bn_fwd_fused): into <= kPartialFoldRows rows
+    const int nb = partial_rows < kPartialFoldRows ? partial_rows : kPartialFoldRows;
+    p.partial_rpb = (partial_rows + nb - 1) / nb;
+    p.fold_rows = (partial_rows + p.partial_rpb - 1) / p.partial_rpb;
+  }
+  int64_t cap = 0;
+  if (applies && !p.from_partials && n > 0 && tune(T_BN_FOLD) != 0 && tensor_bytes <= (tune(T_BN_FOLD_MAX_MB) << 20)) {
+    p.path = kNormFold;
+    cap = tune(T_BN_FOLD_PARTS);
+    if (cap < 1 || cap > kFoldParts) cap = kFoldParts;
+    const int64_t grid_cap = tune(T_BN_FOLD_GRID) < 1 ? 256 : tune(T_BN_FOLD_GRID);
+    p.apply_grid = apply_blocks(n, c, W, 2, grid_cap);       // two rows per thread and sweep in the forward kernel
+    if (p.apply_grid < 1) p.apply_grid = 1;
+  } else {
+    // above ~24 MB a direction is bandwidth-bound and the three-launch path's 4096-workgroup apply streams faster than 512
+    // resident workgroups can (1.2 M rows x 96 ch bf16 forward: 0.135 ms vs 0.181 ms fused); below, launches dominate
+    int64_t max_mb = tune(T_BN_FUSED_MAX_MB);
+    if (dir == kNormFwd && tune(T_BN_FUSED_FWD_MAX_MB) < max_mb) max_mb = tune(T_BN_FUSED_FWD_MAX_MB);
+    if (applies && tune(T_BN_FUSED) != 0 && tensor_bytes <= (max_mb << 20)) {
+      cap = resident_cap();
+      if (cap > kFusedMaxBlocks) cap = kFusedMaxBlocks;
+      if (cap < kCoopMinBlocks) cap = 0;
+      if (tune(T_BN_FUSED_BLOCKS) > 0 && tune(T_BN_FUSED_BLOCKS) < cap) cap = tune(T_BN_FUSED_BLOCKS);
+    }
+    if (cap > 0) {
+      p.path = kNormFused;
+    } else {
+      p.path = kNormThree;
+      cap = kReduceMaxBlocks;
+      p.fold_grid = (c + kFoldCh - 1) / kFoldCh;
+      if (applies) p.apply_grid = apply_blocks(n, c, W, 1, kApplyMaxBlocks);
+    }
+  }
+  if (!(p.path == kNormThree && p.from_partials)) p.reduce_grid = row_blocks(n, cap, &p.rows_per_block);
+  if (!p.from_partials) p.fold_rows = p.reduce_grid;
+  const int64_t row_bytes = (int64_t)sizeof(float) * 2 * c;
+  p.partials = {0, row_bytes * p.fold_rows};
+  if (dir == kNormBwd && p.path != kNormFold) p.sums = {p.partials.bytes, row_bytes};
+  if (dir == kNormBwdReduce) p.spill = {p.partials.bytes, row_bytes};
+  p.bytes_total = p.partials.bytes + p.sums.bytes + p.spill.bytes;
+  p.workspace_bytes = norm_workspace_bytes(n, c);
+  return p;
+}
+inline float *region(void *workspace, const lgs_conv_plan_region &r) { return reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + r.offset); }
 
 // barrier counters of the fused kernels: a ring of slots per device, zeroed once; a kernel leaves its slot at zero
 constexpr int kCtrSlots = 256;
@@ -901,21 +971,13 @@ inline unsigned *fused_counter(hipStream_t s) {
   }
   return ring[dev] + (next[dev].fetch_add(1) % kCtrSlots);
 }
-inline bool bn_fused_on(int64_t tensor_bytes, bool forward = false) {
-  const bool on = tune(T_BN_FUSED) != 0;   // A/B knob: 0 = three launches
-  // above ~24 MB a direction is bandwidth-bound and the three-launch path's 4096-workgroup apply streams faster than 512
-  // resident workgroups can (1.2 M rows x 96 ch bf16 forward: 0.135 ms vs 0.181 ms fused); below, launches dominate
-  int64_t max_mb = tune(T_BN_FUSED_MAX_MB);
-  if (forward && tune(T_BN_FUSED_FWD_MAX_MB) < max_mb) max_mb = tune(T_BN_FUSED_FWD_MAX_MB);
-  return on && tensor_bytes <= (max_mb << 20);
-}
 // Workgroups a grid-barrier kernel may be launched with: every one of them must be RESIDENT at the same time, or the resident
 // ones spin on the barrier for workgroups the dispatcher can never place (a hard GPU hang).  The bound is the kernel's own
 // occupancy on THIS device x its CU count (a CPX partition of the chip has 32-38 CUs, not 256), halved for headroom against
-// another stream's kernels holding CUs, cached per (device, kernel).  Below 16 the fused path is not worth it: 0 = use the
-// three-launch path.  What this cannot see: HSA_CU_MASK-style external masks and other PROCESSES on the same GPU -- those
-// setups must run with the tuning knob BN_FUSED=0 (bench.py --same-device does).
-inline int fused_cap(const void *kernel) {
+// another stream's kernels holding CUs, cached per (device, kernel); norm_plan caps it at kFusedMaxBlocks and takes the
+// three-launch path below kCoopMinBlocks.  What this cannot see: HSA_CU_MASK-style external masks and other PROCESSES on the
+// same GPU -- those setups must run with the tuning knob BN_FUSED=0 (bench.py --same-device does).
+inline int fused_resident(const void *kernel) {
   static std::mutex mu;
   static std::vector<std::pair<std::pair<int, const void *>, int>> cache;
   int dev = 0;
@@ -929,201 +991,134 @@ inline int fused_cap(const void *kernel) {
     cap = per_cu * cus / 2;
   else
     (void)hipGetLastError();
-  if (cap > kFusedMaxBlocks) cap = kFusedMaxBlocks;
-  if (cap < 16) cap = 0;
   cache.push_back({{dev, kernel}, cap});
   return cap;
 }
-inline int fused_blocks(int64_t n, int64_t *rows_per_block, int cap) {
-  const int cap_env = (int)tune(T_BN_FUSED_BLOCKS);   // tuning knob: 0 = the device bound
-  if (cap_env > 0 && cap_env < cap) cap = cap_env;
-  int64_t nb = (n + 127) / 128;
-  if (nb > cap) nb = cap;
-  if (nb < 1) nb = 1;
-  int64_t rpb = (n + nb - 1) / nb;
-  if (rpb < 1) rpb = 1;
-  *rows_per_block = rpb;
-  nb = (n + rpb - 1) / rpb;
-  return (int)(nb > 0 ? nb : 1);
-}
 
-// statistics source: either the column reduction over x, or the conv epilogue's per-tile partial rows
-template <typename T>
-int stats_partials(const T *x, int64_t n, int c, const float *partials, int partial_rows, float *scratch, hipStream_t s, int *nb_out) {
-  if (partials && partial_rows > 0) {
-    int nb = partial_rows < 128 ? partial_rows : 128;
-    const int rpb = (partial_rows + nb - 1) / nb;
-    nb = (partial_rows + rpb - 1) / rpb;
-    LGS_KLAUNCH(k_partial_reduce, nb, 256, 0, s, partials, partial_rows, 2 * c, rpb, scratch);
-    *nb_out = nb;
-    return 0;
-  }
-  int64_t rpb;
-  const int nb = reduce_blocks(n, &rpb);
-  LGS_KLAUNCH((k_colreduce<T, 0>), nb, kNT, 0, s, x, (const T *)nullptr, (const T *)nullptr, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, n, c, 0,
-                     rpb, scratch, (int64_t)c, (int64_t)c);
-  *nb_out = nb;
-  return 0;
+template <typename T> constexpr int dtype_of() { return sizeof(T) == 2 ? LGS_BF16 : LGS_F32; }
+// the element type of a call: its void pointers as T
+template <typename T> struct Elem {
+  static const T *in(const void *p) { return reinterpret_cast<const T *>(p); }
+  static T *out(void *p) { return reinterpret_cast<T *>(p); }
+};
+// dtype -> f(Elem<T>()), behind the family's one dtype and channel-count check
+template <typename F>
+int with_elem(int dtype, int c, const char *who, F &&f) {
+  LGS_REQUIRE(dtype == LGS_F32 || dtype == LGS_BF16, std::string(who) + ": unknown dtype");
+  LGS_REQUIRE(c % epl(dtype) == 0 && c / epl(dtype) <= kNT && c <= 2048, std::string(who) + ": channel count unsupported");
+  return dtype == LGS_F32 ? f(Elem<float>()) : f(Elem<bf16_t>());
 }
-
-template <typename T>
-int bn_forward_t(const void *xv, int64_t n, int c, const float *gamma, const float *beta, float eps, float momentum,
-                 float *rm, float *rv, long long *nbt, const void *res, int relu, void *yv, float *stats, void *workspace,
-                 hipStream_t s, const float *partials, int partial_rows, const float *pivot, int64_t y_ld) {
-  constexpr int W = Vec<T>::W;
-  LGS_REQUIRE(c % W == 0 && c / W <= kNT && c <= 2048, "lgs_bn_forward: channel count unsupported");
-  int nb = 0;
-  float *scratch = reinterpret_cast<float *>(workspace);  // caller-owned: no allocator call (and no implicit sync) here
-  const T *x = reinterpret_cast<const T *>(xv);
-  const int pm = (partials && partial_rows > 0) ? 1 : 0;
-  if (!pm && n > 0 && bn_fold_on(n * (int64_t)c * (int64_t)sizeof(T))) {
-    int64_t rpb;
-    const int parts = fold_parts(n, &rpb);
-    LGS_KLAUNCH((k_colreduce<T, 0>), parts, kNT, 0, s, x, (const T *)nullptr, (const T *)nullptr, (const float *)nullptr, (const float *)nullptr,
-                (const float *)nullptr, n, c, 0, rpb, scratch, (int64_t)c, (int64_t)c);
-    LGS_KLAUNCH((k_bn_apply_fold<T>), fold_grid(n, c, W), kNT, 0, s, x, reinterpret_cast<const T *>(res), n, c, gamma, beta, eps, momentum,
-                rm, rv, nbt, stats, scratch, parts, relu, reinterpret_cast<T *>(yv), y_ld);
-    LGS_HIP(hipGetLastError());
-    return 0;
-  }
-  const int fcap = bn_fused_on(n * (int64_t)c * (int64_t)sizeof(T), true) ? fused_cap(reinterpret_cast<const void *>(&k_bn_fwd_fused<T>)) : 0;
-  if (fcap > 0) {
-    unsigned *ctr = fused_counter(s);
-    LGS_REQUIRE(ctr != nullptr, "lgs_bn_forward: could not allocate the grid-barrier counters");
-    int64_t rpb;
-    const int grid = fused_blocks(n, &rpb, fcap);
-    int prpb = 0, nfold = grid;
-    if (pm) {
-      int pnb = partial_rows < 128 ? partial_rows : 128;
-      prpb = (partial_rows + pnb - 1) / pnb;
-      nfold = (partial_rows + prpb - 1) / prpb;
-    }
-    LGS_KLAUNCH((k_bn_fwd_fused<T>), grid, kNT, 0, s, x, reinterpret_cast<const T *>(res), n, c, gamma, beta, eps, momentum, rm, rv, nbt,
-                       stats, relu, reinterpret_cast<T *>(yv), y_ld, scratch, pm ? partials : (const float *)nullptr, partial_rows, prpb, nfold,
-                       pivot, rpb, ctr);
-    LGS_HIP(hipGetLastError());
-    return 0;
-  }
-  stats_partials<T>(x, n, c, partials, partial_rows, scratch, s, &nb);
-  LGS_KLAUNCH((k_fold_fwd<T>), (c + kFoldCh - 1) / kFoldCh, 256, 0, s, scratch, x, nb, c, n, eps, momentum, rm, rv, nbt, stats, pm, pivot);
-  int64_t total = n * (int64_t)(c / W);
-  if (total > 0) {
-    int grid = (int)((total + kNT - 1) / kNT < 4096 ? (total + kNT - 1) / kNT : 4096);
-    LGS_KLAUNCH((k_bn_apply<T>), grid, kNT, 0, s, x, reinterpret_cast<const T *>(res), n, c, gamma, beta, stats, relu,
-                       reinterpret_cast<T *>(yv), y_ld);
-  }
-  LGS_HIP(hipGetLastError());
-  return 0;
-}
-
-template <typename T>
-int bn_backward_t(const void *xv, const void *yv, const void *dyv, int64_t n, int c, const float *gamma, const float *beta,
-                  const float *stats, int relu, void *dxv, void *dresv, float *dgamma, float *dbeta, void *workspace,
-                  hipStream_t s, int64_t dy_ld, int64_t y_ld) {
-  constexpr int W = Vec<T>::W;
-  LGS_REQUIRE(c % W == 0 && c / W <= kNT && c <= 2048, "lgs_bn_backward: channel count unsupported");
-  int64_t rpb;
-  int nb = reduce_blocks(n, &rpb);
-  float *scratch = reinterpret_cast<float *>(workspace);
-  float *sums = scratch + (size_t)2 * c * nb;
-  const T *x = reinterpret_cast<const T *>(xv), *y = reinterpret_cast<const T *>(yv), *dy = reinterpret_cast<const T *>(dyv);
-  if (n > 0 && bn_fold_on(n * (int64_t)c * (int64_t)sizeof(T))) {
-    int64_t prpb;
-    const int parts = fold_parts(n, &prpb);
-    LGS_KLAUNCH((k_colreduce<T, 1>), parts, kNT, 0, s, x, y, dy, stats, gamma, beta, n, c, relu, prpb, scratch, dy_ld, y_ld);
-    LGS_KLAUNCH((k_bn_bwd_apply_fold<T>), fold_grid(n, c, W), kNT, 0, s, x, y, dy, n, c, gamma, beta, stats, scratch, parts, 1.f / (float)n, relu,
-                reinterpret_cast<T *>(dxv), reinterpret_cast<T *>(dresv), dgamma, dbeta, dy_ld, y_ld);
-    LGS_HIP(hipGetLastError());
-    return 0;
-  }
-  const int fcap = bn_fused_on(n * (int64_t)c * (int64_t)sizeof(T)) ? fused_cap(reinterpret_cast<const void *>(&k_bn_bwd_fused<T>)) : 0;
-  if (fcap > 0) {
-    unsigned *ctr = fused_counter(s);
-    LGS_REQUIRE(ctr != nullptr, "lgs_bn_backward: could not allocate the grid-barrier counters");
-    int64_t frpb;
-    const int grid = fused_blocks(n, &frpb, fcap);
-    LGS_KLAUNCH((k_bn_bwd_fused<T>), grid, kNT, 0, s, x, y, dy, n, c, gamma, beta, stats, relu, reinterpret_cast<T *>(dxv),
-                       reinterpret_cast<T *>(dresv), dgamma, dbeta, scratch, scratch + (size_t)2 * c * grid, dy_ld, y_ld, frpb,
-                       n > 0 ? 1.f / (float)n : 0.f, ctr);
-    LGS_HIP(hipGetLastError());
-    return 0;
-  }
-  LGS_KLAUNCH((k_colreduce<T, 1>), nb, kNT, 0, s, x, y, dy, stats, gamma, beta, n, c, relu, rpb, scratch, dy_ld, y_ld);
-  LGS_KLAUNCH(k_fold_bwd, (c + kFoldCh - 1) / kFoldCh, 256, 0, s, scratch, nb, c, dgamma, dbeta, sums);
-  int64_t total = n * (int64_t)(c / W);
-  if (total > 0) {
-    int grid = (int)((total + kNT - 1) / kNT < 4096 ? (total + kNT - 1) / kNT : 4096);
-    LGS_KLAUNCH((k_bn_bwd_apply<T>), grid, kNT, 0, s, x, y, dy, n, c, gamma, beta, stats, sums, n > 0 ? 1.f / (float)n : 0.f, relu, reinterpret_cast<T *>(dxv),
-                       reinterpret_cast<T *>(dresv), dy_ld, (const float *)nullptr, y_ld);
-  }
-  LGS_HIP(hipGetLastError());
-  return 0;
-}
-
-template <typename T>
-int bn_stats_t(const void *xv, int64_t n, int c, float *mean_m2, void *workspace, hipStream_t s, const float *partials,
-               int partial_rows, const float *pivot) {
-  constexpr int W = Vec<T>::W;
-  LGS_REQUIRE(c % W == 0 && c / W <= kNT && c <= 2048, "lgs_bn_stats: channel count unsupported");
-  int nb = 0;
-  float *scratch = reinterpret_cast<float *>(workspace);
-  const T *x = reinterpret_cast<const T *>(xv);
-  const int pm = (partials && partial_rows > 0) ? 1 : 0;
-  stats_partials<T>(x, n, c, partials, partial_rows, scratch, s, &nb);
-  LGS_KLAUNCH((k_fold_stats<T>), (c + kFoldCh - 1) / kFoldCh, 256, 0, s, scratch, x, nb, c, n, mean_m2, pm, pivot);
-  LGS_HIP(hipGetLastError());
-  return 0;
-}
-template <typename T>
-int bn_apply_t(const void *xv, int64_t n, int c, const float *gamma, const float *beta, const float *stats, const void *res,
-               int relu, void *yv, hipStream_t s, int64_t y_ld) {
-  constexpr int W = Vec<T>::W;
-  LGS_REQUIRE(c % W == 0 && c / W <= kNT, "lgs_bn_apply: channel count unsupported");
-  int64_t total = n * (int64_t)(c / W);
-  if (total > 0) {
-    int grid = (int)((total + kNT - 1) / kNT < 4096 ? (total + kNT - 1) / kNT : 4096);
-    LGS_KLAUNCH((k_bn_apply<T>), grid, kNT, 0, s, reinterpret_cast<const T *>(xv), reinterpret_cast<const T *>(res), n, c,
-                       gamma, beta, stats, relu, reinterpret_cast<T *>(yv), y_ld);
-  }
-  LGS_HIP(hipGetLastError());
-  return 0;
-}
-template <typename T>
-int bn_bwd_reduce_t(const void *xv, const void *yv, const void *dyv, int64_t n, int c, const float *gamma, const float *beta,
-                    const float *stats, int relu, float *sums, float *dgamma, float *dbeta, void *workspace, hipStream_t s,
-                    int64_t dy_ld, int64_t y_ld) {
-  constexpr int W = Vec<T>::W;
-  LGS_REQUIRE(c % W == 0 && c / W <= kNT && c <= 2048, "lgs_bn_backward_reduce: channel count unsupported");
-  int64_t rpb;
-  int nb = reduce_blocks(n, &rpb);
-  float *scratch = reinterpret_cast<float *>(workspace);
-  float *tmp = scratch + (size_t)2 * c * nb;  // dgamma/dbeta land here when the caller does not want them
-  LGS_KLAUNCH((k_colreduce<T, 1>), nb, kNT, 0, s, reinterpret_cast<const T *>(xv), reinterpret_cast<const T *>(yv),
-                     reinterpret_cast<const T *>(dyv), stats, gamma, beta, n, c, relu, rpb, scratch, dy_ld, y_ld);
-  LGS_KLAUNCH(k_fold_bwd, (c + kFoldCh - 1) / kFoldCh, 256, 0, s, scratch, nb, c, dgamma ? dgamma : tmp + c, dbeta ? dbeta : tmp, sums);
-  LGS_HIP(hipGetLastError());
-  return 0;
-}
-template <typename T>
-int bn_bwd_apply_t(const void *xv, const void *yv, const void *dyv, int64_t n, int c, const float *gamma, const float *beta,
-                   const float *stats, const float *sums, float inv_n_total, const float *inv_n_dev, int relu, void *dxv, void *dresv,
-                   hipStream_t s, int64_t dy_ld, int64_t y_ld) {
-  constexpr int W = Vec<T>::W;
-  LGS_REQUIRE(c % W == 0 && c / W <= kNT, "lgs_bn_backward_apply: channel count unsupported");
-  int64_t total = n * (int64_t)(c / W);
-  if (total > 0) {
-    int grid = (int)((total + kNT - 1) / kNT < 4096 ? (total + kNT - 1) / kNT : 4096);
-    LGS_KLAUNCH((k_bn_bwd_apply<T>), grid, kNT, 0, s, reinterpret_cast<const T *>(xv), reinterpret_cast<const T *>(yv),
-                       reinterpret_cast<const T *>(dyv), n, c, gamma, beta, stats, sums, inv_n_total, relu, reinterpret_cast<T *>(dxv),
-                       reinterpret_cast<T *>(dresv), dy_ld, inv_n_dev, y_ld);
-  }
-  LGS_HIP(hipGetLastError());
-  return 0;
-}
-
 // row stride of a [n, c] operand that may be a column slice of a wider row-major buffer: 0 = c; rows must start 16-byte aligned
 inline bool stride_ok(const void *p, int64_t ld, int c, int dtype) {
-  return ld >= c && ld % (dtype == LGS_BF16 ? 8 : 4) == 0 && (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
+  return ld >= c && ld % epl(dtype) == 0 && (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
+}
+#define LGS_BN_STRIDE(who, p, row_stride, ld)                \
+  const int64_t ld = (row_stride) > 0 ? (row_stride) : c;    \
+  LGS_REQUIRE(!(p) || stride_ok(p, ld, c, dtype), who ": " #p " rows must start 16-byte aligned (row stride a multiple of 16 bytes)")
+
+// the partial rows of a three-launch statistics pass: the column reduction over x, or the conv epilogue's rows folded
+template <typename T>
+void stats_rows(const NormPlan &p, const T *x, int64_t n, int c, const float *partials, int partial_rows, float *rows, hipStream_t s) {
+  const T *no = nullptr;
+  const float *nof = nullptr;
+  if (p.from_partials) LGS_KLAUNCH(k_partial_reduce, p.fold_rows, 256, 0, s, partials, partial_rows, 2 * c, p.partial_rpb, rows);
+  else LGS_KLAUNCH((k_colreduce<T, 0>), p.reduce_grid, kNT, 0, s, x, no, no, nof, nof, nof, n, c, 0, p.rows_per_block, rows, (int64_t)c, (int64_t)c);
+}
+
+template <typename T>
+int bn_forward_t(const T *x, int64_t n, int c, const float *gamma, const float *beta, float eps, float momentum, float *rm, float *rv,
+                 long long *nbt, const T *res, int relu, T *y, float *stats, void *workspace, hipStream_t s, const float *partials,
+                 int partial_rows, const float *pivot, int64_t y_ld) {
+  if (!partials) partial_rows = 0;
+  const NormPlan p = norm_plan(kNormFwd, n, c, dtype_of<T>(), partial_rows, [] { return fused_resident(reinterpret_cast<const void *>(&k_bn_fwd_fused<T>)); });
+  float *rows = region(workspace, p.partials);  // caller-owned: no allocator call (and no implicit sync) here
+  const T *no = nullptr;
+  const float *nof = nullptr;
+  switch (p.path) {
+    case kNormFold:
+      LGS_KLAUNCH((k_colreduce<T, 0>), p.reduce_grid, kNT, 0, s, x, no, no, nof, nof, nof, n, c, 0, p.rows_per_block, rows, (int64_t)c, (int64_t)c);
+      LGS_KLAUNCH((k_bn_apply_fold<T>), p.apply_grid, kNT, 0, s, x, res, n, c, gamma, beta, eps, momentum, rm, rv, nbt, stats, rows, p.fold_rows, relu, y, y_ld);
+      break;
+    case kNormFused: {
+      unsigned *ctr = fused_counter(s);
+      LGS_REQUIRE(ctr != nullptr, "lgs_bn_forward: could not allocate the grid-barrier counters");
+      LGS_KLAUNCH((k_bn_fwd_fused<T>), p.reduce_grid, kNT, 0, s, x, res, n, c, gamma, beta, eps, momentum, rm, rv, nbt, stats, relu, y, y_ld, rows,
+                  p.from_partials ? partials : nof, partial_rows, p.partial_rpb, p.fold_rows, pivot, p.rows_per_block, ctr);
+      break;
+    }
+    default:
+      stats_rows<T>(p, x, n, c, partials, partial_rows, rows, s);
+      LGS_KLAUNCH((k_fold_fwd<T>), p.fold_grid, 256, 0, s, rows, x, p.fold_rows, c, n, eps, momentum, rm, rv, nbt, stats, p.from_partials, pivot);
+      if (p.apply_grid) LGS_KLAUNCH((k_bn_apply<T>), p.apply_grid, kNT, 0, s, x, res, n, c, gamma, beta, stats, relu, y, y_ld);
+  }
+  LGS_HIP(hipGetLastError());
+  return 0;
+}
+
+template <typename T>
+int bn_backward_t(const T *x, const T *y, const T *dy, int64_t n, int c, const float *gamma, const float *beta, const float *stats, int relu,
+                  T *dx, T *dres, float *dgamma, float *dbeta, void *workspace, hipStream_t s, int64_t dy_ld, int64_t y_ld) {
+  const NormPlan p = norm_plan(kNormBwd, n, c, dtype_of<T>(), 0, [] { return fused_resident(reinterpret_cast<const void *>(&k_bn_bwd_fused<T>)); });
+  float *rows = region(workspace, p.partials), *sums = region(workspace, p.sums);
+  const float inv_n = n > 0 ? 1.f / (float)n : 0.f;
+  switch (p.path) {
+    case kNormFold:
+      LGS_KLAUNCH((k_colreduce<T, 1>), p.reduce_grid, kNT, 0, s, x, y, dy, stats, gamma, beta, n, c, relu, p.rows_per_block, rows, dy_ld, y_ld);
+      LGS_KLAUNCH((k_bn_bwd_apply_fold<T>), p.apply_grid, kNT, 0, s, x, y, dy, n, c, gamma, beta, stats, rows, p.fold_rows, inv_n, relu, dx, dres, dgamma,
+                  dbeta, dy_ld, y_ld);
+      break;
+    case kNormFused: {
+      unsigned *ctr = fused_counter(s);
+      LGS_REQUIRE(ctr != nullptr, "lgs_bn_backward: could not allocate the grid-barrier counters");
+      LGS_KLAUNCH((k_bn_bwd_fused<T>), p.reduce_grid, kNT, 0, s, x, y, dy, n, c, gamma, beta, stats, relu, dx, dres, dgamma, dbeta, rows, sums, dy_ld, y_ld,
+                  p.rows_per_block, inv_n, ctr);
+      break;
+    }
+    default:
+      LGS_KLAUNCH((k_colreduce<T, 1>), p.reduce_grid, kNT, 0, s, x, y, dy, stats, gamma, beta, n, c, relu, p.rows_per_block, rows, dy_ld, y_ld);
+      LGS_KLAUNCH(k_fold_bwd, p.fold_grid, 256, 0, s, rows, p.fold_rows, c, dgamma, dbeta, sums);
+      if (p.apply_grid) LGS_KLAUNCH((k_bn_bwd_apply<T>), p.apply_grid, kNT, 0, s, x, y, dy, n, c, gamma, beta, stats, sums, inv_n, relu, dx, dres, dy_ld,
+                                    (const float *)nullptr, y_ld);
+  }
+  LGS_HIP(hipGetLastError());
+  return 0;
+}
+
+template <typename T>
+int bn_stats_t(const T *x, int64_t n, int c, float *mean_m2, void *workspace, hipStream_t s, const float *partials, int partial_rows, const float *pivot) {
+  if (!partials) partial_rows = 0;
+  const NormPlan p = norm_plan(kNormStats, n, c, dtype_of<T>(), partial_rows, [] { return 0; });
+  float *rows = region(workspace, p.partials);
+  stats_rows<T>(p, x, n, c, partials, partial_rows, rows, s);
+  LGS_KLAUNCH((k_fold_stats<T>), p.fold_grid, 256, 0, s, rows, x, p.fold_rows, c, n, mean_m2, p.from_partials, pivot);
+  LGS_HIP(hipGetLastError());
+  return 0;
+}
+template <typename T>
+int bn_apply_t(const T *x, int64_t n, int c, const float *gamma, const float *beta, const float *stats, const T *res, int relu, T *y, hipStream_t s,
+               int64_t y_ld) {
+  const int grid = apply_blocks(n, c, Vec<T>::W, 1, kApplyMaxBlocks);
+  if (grid) LGS_KLAUNCH((k_bn_apply<T>), grid, kNT, 0, s, x, res, n, c, gamma, beta, stats, relu, y, y_ld);
+  LGS_HIP(hipGetLastError());
+  return 0;
+}
+template <typename T>
+int bn_bwd_reduce_t(const T *x, const T *y, const T *dy, int64_t n, int c, const float *gamma, const float *beta, const float *stats, int relu,
+                    float *sums, float *dgamma, float *dbeta, void *workspace, hipStream_t s, int64_t dy_ld, int64_t y_ld) {
+  const NormPlan p = norm_plan(kNormBwdReduce, n, c, dtype_of<T>(), 0, [] { return 0; });
+  float *rows = region(workspace, p.partials), *spill = region(workspace, p.spill);  // dgamma / dbeta land there when the caller does not want them
+  LGS_KLAUNCH((k_colreduce<T, 1>), p.reduce_grid, kNT, 0, s, x, y, dy, stats, gamma, beta, n, c, relu, p.rows_per_block, rows, dy_ld, y_ld);
+  LGS_KLAUNCH(k_fold_bwd, p.fold_grid, 256, 0, s, rows, p.fold_rows, c, dgamma ? dgamma : spill + c, dbeta ? dbeta : spill, sums);
+  LGS_HIP(hipGetLastError());
+  return 0;
+}
+template <typename T>
+int bn_bwd_apply_t(const T *x, const T *y, const T *dy, int64_t n, int c, const float *gamma, const float *beta, const float *stats, const float *sums,
+                   float inv_n_total, const float *inv_n_dev, int relu, T *dx, T *dres, hipStream_t s, int64_t dy_ld, int64_t y_ld) {
+  const int grid = apply_blocks(n, c, Vec<T>::W, 1, kApplyMaxBlocks);
+  if (grid) LGS_KLAUNCH((k_bn_bwd_apply<T>), grid, kNT, 0, s, x, y, dy, n, c, gamma, beta, stats, sums, inv_n_total, relu, dx, dres, dy_ld, inv_n_dev, y_ld);
+  LGS_HIP(hipGetLastError());
+  return 0;
 }
 
 }  // namespace lgs
@@ -1135,18 +1130,17 @@ extern "C" {
 int lgs_bn_stats(const void *x, int64_t n, int c, float *mean_m2, int dtype, void *workspace, const float *conv_partials,
                  int conv_partial_rows, const float *pivot, void *stream) {
   LGS_REQUIRE(x && mean_m2 && workspace, "lgs_bn_stats: null argument");
-  if (dtype == LGS_F32) return bn_stats_t<float>(x, n, c, mean_m2, workspace, (hipStream_t)stream, conv_partials, conv_partial_rows, pivot);
-  if (dtype == LGS_BF16) return bn_stats_t<bf16_t>(x, n, c, mean_m2, workspace, (hipStream_t)stream, conv_partials, conv_partial_rows, pivot);
-  LGS_REQUIRE(false, "lgs_bn_stats: unknown dtype");
+  return with_elem(dtype, c, "lgs_bn_stats", [&](auto e) {
+    return bn_stats_t(e.in(x), n, c, mean_m2, workspace, (hipStream_t)stream, conv_partials, conv_partial_rows, pivot);
+  });
 }
 int lgs_bn_apply(const void *x, int64_t n, int c, const float *gamma, const float *beta, const float *stats,
                  const void *residual, int relu, void *y, int dtype, int64_t y_row_stride, void *stream) {
   LGS_REQUIRE(x && y && gamma && beta && stats, "lgs_bn_apply: null argument");
-  const int64_t y_ld = y_row_stride > 0 ? y_row_stride : c;
-  LGS_REQUIRE(stride_ok(y, y_ld, c, dtype), "lgs_bn_apply: y rows must start 16-byte aligned (row stride a multiple of 16 bytes)");
-  if (dtype == LGS_F32) return bn_apply_t<float>(x, n, c, gamma, beta, stats, residual, relu, y, (hipStream_t)stream, y_ld);
-  if (dtype == LGS_BF16) return bn_apply_t<bf16_t>(x, n, c, gamma, beta, stats, residual, relu, y, (hipStream_t)stream, y_ld);
-  LGS_REQUIRE(false, "lgs_bn_apply: unknown dtype");
+  LGS_BN_STRIDE("lgs_bn_apply", y, y_row_stride, y_ld);
+  return with_elem(dtype, c, "lgs_bn_apply", [&](auto e) {
+    return bn_apply_t(e.in(x), n, c, gamma, beta, stats, e.in(residual), relu, e.out(y), (hipStream_t)stream, y_ld);
+  });
 }
 int lgs_bn_sync_combine(const float *all_stats, int world, int c, float eps, float momentum, float *running_mean,
                         float *running_var, int64_t *num_batches_tracked, float *stats, float *inv_n_total, void *stream) {
@@ -1160,68 +1154,65 @@ int lgs_bn_backward_reduce(const void *x, const void *y, const void *dy, int64_t
                            const float *beta, const float *stats, int relu, float *sums, float *dgamma, float *dbeta, int dtype,
                            void *workspace, int64_t dy_row_stride, int64_t y_row_stride, void *stream) {
   LGS_REQUIRE(x && dy && stats && sums && workspace, "lgs_bn_backward_reduce: null argument");
-  const int64_t dy_ld = dy_row_stride > 0 ? dy_row_stride : c, y_ld = y_row_stride > 0 ? y_row_stride : c;
-  LGS_REQUIRE(stride_ok(dy, dy_ld, c, dtype) && (!y || stride_ok(y, y_ld, c, dtype)),
-              "lgs_bn_backward_reduce: dy / y rows must start 16-byte aligned (row stride a multiple of 16 bytes)");
+  LGS_BN_STRIDE("lgs_bn_backward_reduce", dy, dy_row_stride, dy_ld);
+  LGS_BN_STRIDE("lgs_bn_backward_reduce", y, y_row_stride, y_ld);
   LGS_REQUIRE(relu != 1 || y, "lgs_bn_backward_reduce: relu mode 1 needs the forward output");
   LGS_REQUIRE(relu != 2 || (gamma && beta), "lgs_bn_backward_reduce: relu mode 2 needs gamma and beta");
-  if (dtype == LGS_F32) return bn_bwd_reduce_t<float>(x, y, dy, n, c, gamma, beta, stats, relu, sums, dgamma, dbeta, workspace, (hipStream_t)stream, dy_ld, y_ld);
-  if (dtype == LGS_BF16) return bn_bwd_reduce_t<bf16_t>(x, y, dy, n, c, gamma, beta, stats, relu, sums, dgamma, dbeta, workspace, (hipStream_t)stream, dy_ld, y_ld);
-  LGS_REQUIRE(false, "lgs_bn_backward_reduce: unknown dtype");
+  return with_elem(dtype, c, "lgs_bn_backward_reduce", [&](auto e) {
+    return bn_bwd_reduce_t(e.in(x), e.in(y), e.in(dy), n, c, gamma, beta, stats, relu, sums, dgamma, dbeta, workspace, (hipStream_t)stream, dy_ld, y_ld);
+  });
 }
 int lgs_bn_backward_apply(const void *x, const void *y, const void *dy, int64_t n, int c, const float *gamma,
                           const float *beta, const float *stats, const float *sums, float inv_n_total,
                           const float *inv_n_device, int relu, void *dx, void *dresidual, int dtype, int64_t dy_row_stride,
                           int64_t y_row_stride, void *stream) {
   LGS_REQUIRE(x && dy && dx && gamma && stats && sums, "lgs_bn_backward_apply: null argument");
-  const int64_t dy_ld = dy_row_stride > 0 ? dy_row_stride : c, y_ld = y_row_stride > 0 ? y_row_stride : c;
-  LGS_REQUIRE(stride_ok(dy, dy_ld, c, dtype) && (!y || stride_ok(y, y_ld, c, dtype)),
-              "lgs_bn_backward_apply: dy / y rows must start 16-byte aligned (row stride a multiple of 16 bytes)");
+  LGS_BN_STRIDE("lgs_bn_backward_apply", dy, dy_row_stride, dy_ld);
+  LGS_BN_STRIDE("lgs_bn_backward_apply", y, y_row_stride, y_ld);
   LGS_REQUIRE(relu != 1 || y, "lgs_bn_backward_apply: relu mode 1 needs the forward output");
   LGS_REQUIRE(relu != 2 || beta, "lgs_bn_backward_apply: relu mode 2 needs beta");
-  if (dtype == LGS_F32) return bn_bwd_apply_t<float>(x, y, dy, n, c, gamma, beta, stats, sums, inv_n_total, inv_n_device, relu, dx, dresidual, (hipStream_t)stream, dy_ld, y_ld);
-  if (dtype == LGS_BF16) return bn_bwd_apply_t<bf16_t>(x, y, dy, n, c, gamma, beta, stats, sums, inv_n_total, inv_n_device, relu, dx, dresidual, (hipStream_t)stream, dy_ld, y_ld);
-  LGS_REQUIRE(false, "lgs_bn_backward_apply: unknown dtype");
+  return with_elem(dtype, c, "lgs_bn_backward_apply", [&](auto e) {
+    return bn_bwd_apply_t(e.in(x), e.in(y), e.in(dy), n, c, gamma, beta, stats, sums, inv_n_total, inv_n_device, relu, e.out(dx), e.out(dresidual),
+                          (hipStream_t)stream, dy_ld, y_ld);
+  });
 }
 
-int64_t lgs_bn_workspace_bytes(int64_t n, int c) {
-  int64_t rpb;
-  int nb = reduce_blocks(n, &rpb);
-  if (nb < 128) nb = 128;   // k_partial_reduce folds conv-epilogue partial rows into <= 128 rows
-  return (int64_t)sizeof(float) * 2 * c * (nb + 2) + 256;
-}
+int64_t lgs_bn_workspace_bytes(int64_t n, int c) { return norm_workspace_bytes(n, c); }
 
 int lgs_bn_forward(const void *x, int64_t n, int c, const float *gamma, const float *beta, float eps, float momentum,
                    float *running_mean, float *running_var, int64_t *num_batches_tracked, const void *residual, int relu,
                    void *y, float *stats, int dtype, void *workspace, const float *conv_partials, int conv_partial_rows,
                    const float *pivot, int64_t y_row_stride, void *stream) {
   LGS_REQUIRE(x && y && gamma && beta && stats && workspace, "lgs_bn_forward: null argument");
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t y_ld = y_row_stride > 0 ? y_row_stride : c;
-  LGS_REQUIRE(y_ld >= c && y_ld % (dtype == LGS_BF16 ? 8 : 4) == 0 && (reinterpret_cast<uintptr_t>(y) & 15u) == 0,
-              "lgs_bn_forward: y rows must start 16-byte aligned (row stride a multiple of 16 bytes)");
-  if (dtype == LGS_F32) return bn_forward_t<float>(x, n, c, gamma, beta, eps, momentum, running_mean, running_var, reinterpret_cast<long long *>(num_batches_tracked), residual, relu, y, stats, workspace, s, conv_partials, conv_partial_rows, pivot, y_ld);
-  if (dtype == LGS_BF16) return bn_forward_t<bf16_t>(x, n, c, gamma, beta, eps, momentum, running_mean, running_var, reinterpret_cast<long long *>(num_batches_tracked), residual, relu, y, stats, workspace, s, conv_partials, conv_partial_rows, pivot, y_ld);
-  LGS_REQUIRE(false, "lgs_bn_forward: unknown dtype");
+  LGS_BN_STRIDE("lgs_bn_forward", y, y_row_stride, y_ld);
+  return with_elem(dtype, c, "lgs_bn_forward", [&](auto e) {
+    return bn_forward_t(e.in(x), n, c, gamma, beta, eps, momentum, running_mean, running_var, reinterpret_cast<long long *>(num_batches_tracked),
+                        e.in(residual), relu, e.out(y), stats, workspace, (hipStream_t)stream, conv_partials, conv_partial_rows, pivot, y_ld);
+  });
 }
 
 int lgs_bn_backward(const void *x, const void *y, const void *dy, int64_t dy_row_stride, int64_t n, int c, const float *gamma,
                     const float *beta, const float *stats, int relu, void *dx, void *dresidual, float *dgamma, float *dbeta,
                     int dtype, void *workspace, int64_t y_row_stride, void *stream) {
   LGS_REQUIRE(x && dy && dx && gamma && stats && dgamma && dbeta && workspace, "lgs_bn_backward: null argument");
-  const int64_t dy_ld = dy_row_stride > 0 ? dy_row_stride : c;
-  LGS_REQUIRE(dy_ld >= c && dy_ld % (dtype == LGS_BF16 ? 8 : 4) == 0 &&
-                  (reinterpret_cast<uintptr_t>(dy) & 15u) == 0,
-              "lgs_bn_backward: dy rows must start 16-byte aligned (row stride a multiple of 16 bytes)");
+  LGS_BN_STRIDE("lgs_bn_backward", dy, dy_row_stride, dy_ld);
+  LGS_BN_STRIDE("lgs_bn_backward", y, y_row_stride, y_ld);
   LGS_REQUIRE(relu != 1 || y, "lgs_bn_backward: relu mode 1 needs the forward output");
   LGS_REQUIRE(relu != 2 || beta, "lgs_bn_backward: relu mode 2 needs beta");
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t y_ld = y_row_stride > 0 ? y_row_stride : c;
-  LGS_REQUIRE(!y || (y_ld >= c && y_ld % (dtype == LGS_BF16 ? 8 : 4) == 0 && (reinterpret_cast<uintptr_t>(y) & 15u) == 0),
-              "lgs_bn_backward: y rows must start 16-byte aligned (row stride a multiple of 16 bytes)");
-  if (dtype == LGS_F32) return bn_backward_t<float>(x, y, dy, n, c, gamma, beta, stats, relu, dx, dresidual, dgamma, dbeta, workspace, s, dy_ld, y_ld);
-  if (dtype == LGS_BF16) return bn_backward_t<bf16_t>(x, y, dy, n, c, gamma, beta, stats, relu, dx, dresidual, dgamma, dbeta, workspace, s, dy_ld, y_ld);
-  LGS_REQUIRE(false, "lgs_bn_backward: unknown dtype");
+  return with_elem(dtype, c, "lgs_bn_backward", [&](auto e) {
+    return bn_backward_t(e.in(x), e.in(y), e.in(dy), n, c, gamma, beta, stats, relu, e.out(dx), e.out(dresidual), dgamma, dbeta, workspace,
+                         (hipStream_t)stream, dy_ld, y_ld);
+  });
+}
+
+// the plan of a call given by plain integers, resident-workgroup cap included: no HIP call (tests/test_norm_plan_cpu.py)
+int lgs_debug_norm_plan(const lgs_norm_plan_query *q, lgs_norm_plan_info *out) {
+  LGS_REQUIRE(q && out && q->direction >= kNormFwd && q->direction <= kNormBwdReduce && q->n >= 0 && q->conv_partial_rows >= 0,
+              "lgs_debug_norm_plan: bad argument");
+  return with_elem(q->dtype, q->c, "lgs_debug_norm_plan", [&](auto) {
+    *out = norm_plan(q->direction, q->n, q->c, q->dtype, q->conv_partial_rows, [&] { return q->resident_cap; });
+    return 0;
+  });
 }
 
 }  // extern "C"

@@ -10,7 +10,7 @@ import os
 from . import build as _build
 
 LGS_F32, LGS_BF16 = 0, 1
-ABI_VERSION = 16     # LGS_ABI_VERSION of include/lgs_engine.h
+ABI_VERSION = 17     # LGS_ABI_VERSION of include/lgs_engine.h
 
 
 class PackDesc(ctypes.Structure):
@@ -64,6 +64,19 @@ class WgradPlanInfo(ctypes.Structure):
                [(n, ConvPlanRegion) for n in ("partials", "padded_in", "padded_gout", "ww_count", "ww_offset", "ww_total", "ww_pair_in",
                                               "ww_pair_out")] + \
                [("bytes_total", ctypes.c_int64), ("workspace_bytes", ctypes.c_int64), ("supports_stride", ctypes.c_int)]
+
+
+class NormPlanQuery(ctypes.Structure):
+    """lgs_norm_plan_query"""
+    _fields_ = [(n, ctypes.c_int) for n in ("direction", "c", "dtype", "conv_partial_rows", "resident_cap")] + [("n", ctypes.c_int64)]
+
+
+class NormPlanInfo(ctypes.Structure):
+    """lgs_norm_plan_info: what lgs_debug_norm_plan answers (no GPU needed)"""
+    _fields_ = [("path", ctypes.c_int), ("from_partials", ctypes.c_int), ("reduce_grid", ctypes.c_int), ("rows_per_block", ctypes.c_int64)] + \
+               [(n, ctypes.c_int) for n in ("partial_rpb", "fold_rows", "fold_grid", "apply_grid")] + \
+               [(n, ConvPlanRegion) for n in ("partials", "sums", "spill")] + \
+               [("bytes_total", ctypes.c_int64), ("workspace_bytes", ctypes.c_int64)]
 
 
 class BnParams(ctypes.Structure):
@@ -126,6 +139,7 @@ _lib = None
 EXPORTS = [
     "lgs_abi_version", "lgs_last_error",
     "lgs_tuning_set", "lgs_tuning_get", "lgs_tuning_describe", "lgs_debug_dispatch_counts", "lgs_debug_conv_plan", "lgs_debug_wgrad_plan",
+    "lgs_debug_norm_plan",
     "lgs_manager_create", "lgs_manager_destroy", "lgs_manager_insert", "lgs_manager_stride2", "lgs_manager_check",
     "lgs_manager_parent_of", "lgs_manager_map_size", "lgs_manager_get_coords", "lgs_manager_kernel_map",
     "lgs_kmap_export",
@@ -196,6 +210,7 @@ def lib():
         "lgs_pack_weights_batch": [vp, ci, i64, vp],
         "lgs_debug_conv_plan": [ctypes.POINTER(ConvPlanQuery), ctypes.POINTER(ConvPlanInfo)],
         "lgs_debug_wgrad_plan": [ctypes.POINTER(WgradPlanQuery), ctypes.POINTER(WgradPlanInfo)],
+        "lgs_debug_norm_plan": [ctypes.POINTER(NormPlanQuery), ctypes.POINTER(NormPlanInfo)],
         "lgs_conv_bn_partial_rows": [vp, ci, ci, ci],
         "lgs_conv_dgrad": [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, vp],
         "lgs_sgd_step": [vp, vp, vp, vp, i64, cf, cf, cf, cf, ci, vp],

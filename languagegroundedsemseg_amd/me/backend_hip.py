@@ -639,15 +639,8 @@ class HipBackend:
             raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (list(x.shape),))
         dt = _dtype_code(x)
         part, piv = conv_stats if conv_stats is not None else (None, None)
-        y_ld = 0
         with _dev(x.device):
-            if out_into is not None:
-                buf, off = out_into
-                y = buf[:, off:off + c]
-                y_ld = buf.stride(0)
-                assert buf.dtype == x.dtype and buf.shape[0] == n and (y_ld * x.element_size()) % 16 == 0 and y.data_ptr() % 16 == 0
-            else:
-                y = torch.empty_like(x)
+            y, y_ld = self._y_out(x, out_into)
             stats = torch.empty(2 * c, dtype=torch.float32, device=x.device)
             res = residual.contiguous() if residual is not None else None
             ws = _ws(_bn_ws_bytes(L, n, c), x.device)
@@ -663,19 +656,11 @@ class HipBackend:
         L = engine.lib()
         n, c = x.shape
         dt = _dtype_code(x)
-        # a column slice of a wider row-major tensor (the gradient of one ME.cat input) is read in place
-        esz = dy.element_size()
-        if (dy.dim() == 2 and dy.stride(1) == 1 and dy.stride(0) >= c and (dy.stride(0) * esz) % 16 == 0
-                and dy.data_ptr() % 16 == 0 and dy.dtype == x.dtype):
-            dy_ld = dy.stride(0)
-        else:
-            dy = dy.contiguous()
-            dy_ld = c
-        y_ld = 0
-        if y is not None:
-            y_ld = _row_strided(y, c) or 0
-            if y_ld == 0:
-                y = y.contiguous()
+        # a column slice of a wider row-major tensor (the gradient of one ME.cat input) is read in place; the engine is given
+        # dy's row stride explicitly, also when it is c
+        dy, dy_ld = self._strided_in(dy, c) if dy.dtype == x.dtype else (dy.contiguous(), 0)
+        dy_ld = dy_ld or c
+        y, y_ld = self._strided_in(y, c)
         with _dev(x.device):
             dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
             dres = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_residual else None

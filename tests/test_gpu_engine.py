@@ -197,17 +197,31 @@ def test_single_voxel_and_ragged_batches():
 
 
 # ------------------------------------------------------------------------------------------- norm
+# the launch sites of one BatchNorm forward + backward per path (kernel names of csrc/lgs_norm.hip, template arguments dropped)
+BN_PATHS = {
+    "fold": ({}, {"k_colreduce", "k_bn_apply_fold", "k_bn_bwd_apply_fold"}),
+    "one": (dict(BN_FOLD=0, BN_FUSED=1, BN_FUSED_FWD_MAX_MB=24), {"k_bn_fwd_fused", "k_bn_bwd_fused"}),
+    "three": (dict(BN_FOLD=0, BN_FUSED=0), {"k_colreduce", "k_fold_fwd", "k_bn_apply", "k_fold_bwd", "k_bn_bwd_apply"}),
+}
+BN_PATHS["default"] = BN_PATHS["fold"]      # the production policy for a layer of this size (<= BN_FOLD_MAX_MB)
+
+
 @pytest.mark.parity("plain torch: nn.BatchNorm1d / F.cross_entropy + autograd")
 @pytest.mark.parametrize("dtype,tol", [(torch.float32, 2e-5), (torch.bfloat16, 2e-2)])
 @pytest.mark.parametrize("relu,res", [(False, False), (True, False), (True, True)])
-@pytest.mark.parametrize("launches", ["default", "one", "three"])
+@pytest.mark.parametrize("launches", ["default", "fold", "one", "three"])
 def test_fused_bn_matches_torch(dtype, tol, relu, res, launches):
-    """launches: the default policy (forward = column sums / fold / apply, backward = one grid-barrier launch for layers <= 24 MB),
-    the one-launch kernels in BOTH directions, three launches in both"""
+    """launches: the two-launch fold path (what the default policy picks for this 5000 x 96 layer), the one-launch grid-barrier
+    kernels in BOTH directions, three launches in both.  The dispatch counters must name exactly the kernels of that path."""
+    import re
     from languagegroundedsemseg_amd import engine
-    knobs = {"default": {}, "one": dict(BN_FUSED=1, BN_FUSED_FWD_MAX_MB=24), "three": dict(BN_FUSED=0)}[launches]
+    knobs, want = BN_PATHS[launches]
+    before = engine.dispatch_counts()         # no reset: the session's coverage record of this test reads the same counters
     with engine.tuning(**knobs):
         _bn_matches_torch(dtype, tol, relu, res)
+    sites = [k for k, v in engine.dispatch_counts().items() if v > before.get(k, 0)]
+    hit = {re.match(r"\w+", site).group(0) for site in sites}
+    assert {k for k in hit if k.startswith(("k_bn_", "k_colreduce", "k_fold_", "k_partial_reduce"))} == want, sorted(sites)
 
 
 def _bn_matches_torch(dtype, tol, relu, res):
