@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define LGS_ABI_VERSION 17
+#define LGS_ABI_VERSION 18
 
 enum lgs_dtype { LGS_F32 = 0, LGS_BF16 = 1 };
 
@@ -146,6 +146,21 @@ int lgs_seg_reduce(lgs_segmap *sm, int op, const void *x, const void *x2, int64_
 int lgs_seg_broadcast(lgs_segmap *sm, int op, const void *g, int c, const void *x, int64_t x_ld, void *out, int64_t out_ld,
                       int dtype, void *stream);
 int lgs_seg_max_backward(lgs_segmap *sm, const void *dy, const int32_t *argmax, int c, void *dx, int dtype, void *stream);
+
+/* ---- instance normalisation (ABI 18; csrc/lgs_instnorm.hip) --------------------------------
+ * replaces MinkowskiInstanceNorm forward + autograd backward:
+ *   /root/reference/models/clip_models.py:408-437, models/modules/resnet_block.py:64-70,126-132, models/modules/common.py:17-27
+ *   mean / biased variance per (scene, channel), y = (x - mean) / sqrt(var + eps) * weight + bias; a scene = one batch index.
+ * `sm` is lgs_manager_segment_map(mgr, key of x, lgs_manager_origin's key): any other segment map is refused.  x, y, dy, dx are
+ * [n_fine, c] contiguous in the rows of x's map; weight, bias, dweight, dbias fp32 [c]; stats fp32 [n_seg][2c] = mean, rstd per
+ * scene (written by the forward, read by the backward; y is not kept).  Statistics are summed about the scene's first row in
+ * fp32 runs folded in double in a fixed order: no atomics, the same bits on every run.  n_fine == 0: no launch, success (the
+ * backward zeroes dweight / dbias).  workspace: lgs_in_workspace_bytes(sm, c) bytes, one size for both directions and dtypes. */
+int64_t lgs_in_workspace_bytes(const lgs_segmap *sm, int c);
+int lgs_in_forward(lgs_segmap *sm, const void *x, int c, const float *weight, const float *bias, float eps, void *y,
+                   float *stats /* [n_seg][2c] mean, rstd */, int dtype, void *workspace, void *stream);
+int lgs_in_backward(lgs_segmap *sm, const void *x, const void *dy, int c, const float *weight, const float *stats, void *dx,
+                    float *dweight, float *dbias, int dtype, void *workspace, void *stream);
 
 /* ---- sparse convolution --------------------------------------------------------------------
  * replaces MinkowskiConvolution / MinkowskiConvolutionTranspose forward + autograd backward
@@ -360,6 +375,26 @@ typedef struct lgs_norm_plan_info {
   int64_t workspace_bytes; /* lgs_bn_workspace_bytes(n, c) */
 } lgs_norm_plan_info;
 int lgs_debug_norm_plan(const lgs_norm_plan_query *q, lgs_norm_plan_info *out);
+
+/* lgs_debug_instnorm_plan (ABI 18): what an instance-norm call decides on the host, for a call given by plain integers (the sizes
+ * of the origin segment map: fine rows, scenes, chunk items).  No HIP call: it runs without a GPU (tests/test_instnorm_cpu.py). */
+typedef struct lgs_instnorm_plan_query {
+  int direction;           /* 0 lgs_in_forward, 1 lgs_in_backward */
+  int c, dtype;
+  int64_t n_fine, n_seg, n_items;
+} lgs_instnorm_plan_query;
+typedef struct lgs_instnorm_plan_info {
+  int vec;                 /* 1: 16 bytes per lane (c * element size a multiple of 16), 0: one element per lane */
+  int lanes_log2;          /* log2 of the lanes that share one row */
+  int rows_per_apply_block;
+  int64_t reduce_grid;     /* workgroups of k_in_reduce: one per chunk item */
+  int64_t combine_grid;    /* workgroups of k_in_combine: scenes x channel blocks */
+  int64_t apply_grid;      /* workgroups of k_in_apply; all three are 0 for an empty tensor (no launch) */
+  lgs_conv_plan_region partials, sums;   /* item partial rows [n_items][2c]; the backward's per-scene sums [n_seg][2c] */
+  int64_t bytes_total;
+  int64_t workspace_bytes; /* lgs_in_workspace_bytes(sm, c) */
+} lgs_instnorm_plan_info;
+int lgs_debug_instnorm_plan(const lgs_instnorm_plan_query *q, lgs_instnorm_plan_info *out);
 
 /* ---- SyncBatchNorm as one call per direction, on the engine's own RCCL communicator (csrc/lgs_comm.hip) --------
  * replaces the per-layer statistics exchange of ME.MinkowskiSyncBatchNorm (convert_sync_batchnorm, /root/reference/main.py:121-123;

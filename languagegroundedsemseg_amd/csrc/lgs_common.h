@@ -38,6 +38,7 @@ enum Tune {
   T_WW_MIN_ROWS, T_WW_RANGE, T_WGRAD_WIDE, T_BN_FUSED, T_BN_FUSED_MAX_MB, T_BN_FUSED_FWD_MAX_MB, T_BN_FUSED_BLOCKS, T_PS_CUS, T_PS_WIDE3, T_WGRAD_PS,
   T_MASK_WINDOW, T_CONV_SPLIT, T_SMALL_CFG, T_WIDE_GC64, T_ARENA_DBG, T_CONV_WIDE, T_MASK_ORDER,
   T_BN_FOLD, T_BN_FOLD_MAX_MB, T_BN_FOLD_PARTS, T_BN_FOLD_GRID, T_FP32_SPLIT, T_BLOCK_WGRAD_LATE, T_WGRAD_F32_LDS, T_WIDE_SCHED, T_HEAD_TILE, T_POINTWISE,
+  T_INSTANCE_NORM,
   T_COUNT
 };
 int64_t tune(Tune t);                                                   // current value (environment LGS_<NAME> at start, lgs_tuning_set later)
@@ -83,6 +84,7 @@ struct SegMap {
   const int32_t *coarse_of = nullptr;   // [n_fine] coarse row of each fine sorted position
   const int32_t *item_start = nullptr;  // [n_coarse + 1] first chunk item of each segment (two-pass maps only)
   const int32_t *item_seg = nullptr;    // [n_items] segment of each chunk item, -1 = unused slot (two-pass maps only)
+  const int32_t *row_seg = nullptr;     // [n_fine] coarse row of each fine ROW (origin segment maps only: the instance norm's apply)
   int64_t n_fine = 0, n_coarse = 0, n_items = 0;
   int64_t max_len = 0;                  // bound on the rows of one segment (8^k for stride 2^k); 0 = none (origin map)
   bool single_pass() const { return max_len > 0 && max_len <= kSegChunk; }

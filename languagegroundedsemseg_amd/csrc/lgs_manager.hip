@@ -420,6 +420,13 @@ __global__ void k_origin_segments(const int32_t *head, const int32_t *cincl, int
   if (head[p]) seg_start[q] = (int32_t)p;
   if (p == n - 1) seg_start[q + 1] = (int32_t)n;
 }
+// the origin segment map per fine ROW (the inverse of `order` composed with coarse_of): what a row-stationary pass needs
+__global__ void k_row_seg(const int32_t *fine_row, const int32_t *coarse_of, int64_t n, int32_t *row_seg) {
+  int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const int32_t r = fine_row[p];
+  if (r >= 0 && r < n) row_seg[r] = coarse_of[p];
+}
 // a stride-2^k segment map composes the k stride-2 steps in between (each keeps the sort, so runs stay runs)
 constexpr int kMaxChain = 12;
 struct Chain {
@@ -1091,7 +1098,14 @@ int lgs_manager_segment_map(lgs_manager *m, int fine_key, int coarse_key, void *
       LGS_KLAUNCH(k_origin_segments, nblk(n), 256, 0, s, head, cincl, n, nc, seg_start, coarse_of);
       LGS_HIP(hipGetLastError());
       if (dfree_now(m, head, s) || dfree_now(m, cincl, s)) return 1;
-      sm.seg_start = seg_start; sm.coarse_of = coarse_of;
+      sm.seg_start = seg_start; sm.coarse_of = coarse_of; sm.row_seg = coarse_of;
+      if (cf.order) {   // level 0: rows are in the caller's order
+        int32_t *row_seg;
+        if (dalloc(m, &row_seg, n, s)) return 1;
+        LGS_KLAUNCH(k_row_seg, nblk(n), 256, 0, s, cf.order, coarse_of, n, row_seg);
+        LGS_HIP(hipGetLastError());
+        sm.row_seg = row_seg;
+      }
     } else if (ch.k == 1) {                    // one stride-2 step: its own arrays are the segment map
       sm.seg_start = ch.cstart[0]; sm.coarse_of = ch.fine_cidx[0];
     } else {

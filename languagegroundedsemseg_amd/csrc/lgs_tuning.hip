@@ -70,6 +70,9 @@ const Knob kKnobs[T_COUNT] = {
     {T_POINTWISE, "POINTWISE", 1, "bf16 1x1 stride-1 convolutions (and their dgrads) on maps of >= 65536 positions with <= 224 output channels run on "
                                   "k_pointwise (persistent streaming GEMM, lgs_pointwise.hip) instead of k_conv_gather's identity-map tiles where that wins (5 - 7 output "
                                   "blocks, or > 128 reduction channels into 3 blocks: the 200-class head and its dgrad); 2 = every shape it serves; 0 = off (A/B)"},
+    {T_INSTANCE_NORM, "INSTANCE_NORM", 1, "MinkowskiInstanceNorm on HIP tensors: 1 = the per-scene kernels of lgs_instnorm.hip (two passes per direction, no host "
+                                          "synchronisation, reproducible); 0 = the torch lines the CPU path uses (index_add_ on fp32 copies, one .item() per "
+                                          "call) -- read at call time: for timing the old path in the same process and for switching the kernels off in the field"},
 };
 std::atomic<int64_t> g_val[T_COUNT];
 std::once_flag g_once;

@@ -10,7 +10,7 @@ import os
 from . import build as _build
 
 LGS_F32, LGS_BF16 = 0, 1
-ABI_VERSION = 17     # LGS_ABI_VERSION of include/lgs_engine.h
+ABI_VERSION = 18     # LGS_ABI_VERSION of include/lgs_engine.h
 
 
 class PackDesc(ctypes.Structure):
@@ -79,6 +79,19 @@ class NormPlanInfo(ctypes.Structure):
                [("bytes_total", ctypes.c_int64), ("workspace_bytes", ctypes.c_int64)]
 
 
+class InstNormPlanQuery(ctypes.Structure):
+    """lgs_instnorm_plan_query"""
+    _fields_ = [(n, ctypes.c_int) for n in ("direction", "c", "dtype")] + [(n, ctypes.c_int64) for n in ("n_fine", "n_seg", "n_items")]
+
+
+class InstNormPlanInfo(ctypes.Structure):
+    """lgs_instnorm_plan_info: what lgs_debug_instnorm_plan answers (no GPU needed)"""
+    _fields_ = [(n, ctypes.c_int) for n in ("vec", "lanes_log2", "rows_per_apply_block")] + \
+               [(n, ctypes.c_int64) for n in ("reduce_grid", "combine_grid", "apply_grid")] + \
+               [(n, ConvPlanRegion) for n in ("partials", "sums")] + \
+               [("bytes_total", ctypes.c_int64), ("workspace_bytes", ctypes.c_int64)]
+
+
 class BnParams(ctypes.Structure):
     """lgs_bn_params"""
     _fields_ = [("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p), ("running_mean", ctypes.c_void_p), ("running_var", ctypes.c_void_p),
@@ -139,12 +152,13 @@ _lib = None
 EXPORTS = [
     "lgs_abi_version", "lgs_last_error",
     "lgs_tuning_set", "lgs_tuning_get", "lgs_tuning_describe", "lgs_debug_dispatch_counts", "lgs_debug_conv_plan", "lgs_debug_wgrad_plan",
-    "lgs_debug_norm_plan",
+    "lgs_debug_norm_plan", "lgs_debug_instnorm_plan",
     "lgs_manager_create", "lgs_manager_destroy", "lgs_manager_insert", "lgs_manager_stride2", "lgs_manager_check",
     "lgs_manager_parent_of", "lgs_manager_map_size", "lgs_manager_get_coords", "lgs_manager_kernel_map",
     "lgs_kmap_export",
     "lgs_manager_origin", "lgs_manager_segment_map", "lgs_segmap_size", "lgs_seg_workspace_bytes", "lgs_seg_reduce",
     "lgs_seg_broadcast", "lgs_seg_max_backward",
+    "lgs_in_workspace_bytes", "lgs_in_forward", "lgs_in_backward",
     "lgs_conv_workspace_bytes", "lgs_conv_bn_partial_rows", "lgs_conv_forward", "lgs_conv_dgrad", "lgs_conv_wgrad",
     "lgs_conv_wgrad_supports_stride", "lgs_conv_dgrad_can_accumulate", "lgs_conv_dgrad_accumulate",
     "lgs_conv_pack_desc", "lgs_pack_weights_batch",
@@ -205,12 +219,15 @@ def lib():
         "lgs_seg_reduce": [vp, ci, vp, vp, i64, ci, vp, vp, ci, vp, vp],
         "lgs_seg_broadcast": [vp, ci, vp, ci, vp, i64, vp, i64, ci, vp],
         "lgs_seg_max_backward": [vp, vp, vp, ci, vp, ci, vp],
+        "lgs_in_forward": [vp, vp, ci, vp, vp, cf, vp, vp, ci, vp, vp],
+        "lgs_in_backward": [vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp],
         "lgs_conv_forward": [vp, ci, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, ci, ci, vp],
         "lgs_conv_pack_desc": [vp, ci, ci, ci, ci, ci, ctypes.POINTER(PackDesc)],
         "lgs_pack_weights_batch": [vp, ci, i64, vp],
         "lgs_debug_conv_plan": [ctypes.POINTER(ConvPlanQuery), ctypes.POINTER(ConvPlanInfo)],
         "lgs_debug_wgrad_plan": [ctypes.POINTER(WgradPlanQuery), ctypes.POINTER(WgradPlanInfo)],
         "lgs_debug_norm_plan": [ctypes.POINTER(NormPlanQuery), ctypes.POINTER(NormPlanInfo)],
+        "lgs_debug_instnorm_plan": [ctypes.POINTER(InstNormPlanQuery), ctypes.POINTER(InstNormPlanInfo)],
         "lgs_conv_bn_partial_rows": [vp, ci, ci, ci],
         "lgs_conv_dgrad": [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, vp],
         "lgs_sgd_step": [vp, vp, vp, vp, i64, cf, cf, cf, cf, ci, vp],
@@ -257,6 +274,8 @@ def lib():
     L.lgs_block_workspace_bytes.argtypes = [vp, vp, ci, ci, ci]
     L.lgs_seg_workspace_bytes.restype = i64
     L.lgs_seg_workspace_bytes.argtypes = [vp, ci]
+    L.lgs_in_workspace_bytes.restype = i64
+    L.lgs_in_workspace_bytes.argtypes = [vp, ci]
     L.lgs_cluster_workspace_bytes.restype = i64
     L.lgs_cluster_workspace_bytes.argtypes = [i64]
     L.lgs_conv_workspace_bytes.restype = i64

@@ -625,6 +625,44 @@ class HipBackend:
             engine.check(engine.lib().lgs_seg_max_backward(sm.h, _ptr(dy), _ptr(amax), c, _ptr(dx), _dtype_code(dy), _stream()))
         return dx
 
+    # ---- instance norm: per-scene statistics over the origin segment map (lgs_in_*)
+    @staticmethod
+    def instance_norm_enabled():
+        """tuning knob INSTANCE_NORM, read at call time (0 = the torch lines, also on HIP tensors)"""
+        return engine.tuning_get("INSTANCE_NORM") != 0
+
+    def instance_norm_forward(self, sm, x, weight, bias, eps):
+        """-> (y [n, C] in x's dtype, stats fp32 [n_seg, 2C] = mean, rstd per scene).  sm: the origin segment map of x's map;
+        weight, bias: fp32 [C] (or [1, C]) contiguous."""
+        _require_dev(x, "features")
+        L = engine.lib()
+        n, c = x.shape
+        assert x.is_contiguous() and n == sm.n_fine, (tuple(x.shape), x.stride(), sm.n_fine)
+        assert weight.dtype == torch.float32 and bias.dtype == torch.float32 and weight.numel() == c and bias.numel() == c
+        with _dev(x.device):
+            y = torch.empty_like(x)
+            stats = torch.empty((sm.n_coarse, 2 * c), dtype=torch.float32, device=x.device)
+            ws = _ws(L.lgs_in_workspace_bytes(sm.h, c), x.device)
+            engine.check(L.lgs_in_forward(sm.h, _ptr(x), c, _ptr(weight), _ptr(bias), float(eps), _ptr(y), _ptr(stats), _dtype_code(x),
+                                          _ptr(ws), _stream()))
+        _written_by_engine(y, stats)
+        return y, stats
+
+    def instance_norm_backward(self, sm, x, dy, weight, stats):
+        """-> (dx [n, C] in x's dtype, dweight fp32 [C], dbias fp32 [C]); y is not needed: xhat is recomputed from x and stats"""
+        L = engine.lib()
+        n, c = x.shape
+        assert dy.shape == x.shape and dy.dtype == x.dtype and dy.is_contiguous() and x.is_contiguous()
+        with _dev(x.device):
+            dx = torch.empty_like(x)
+            dweight = torch.empty(c, dtype=torch.float32, device=x.device)
+            dbias = torch.empty(c, dtype=torch.float32, device=x.device)
+            ws = _ws(L.lgs_in_workspace_bytes(sm.h, c), x.device)
+            engine.check(L.lgs_in_backward(sm.h, _ptr(x), _ptr(dy), c, _ptr(weight), _ptr(stats), _ptr(dx), _ptr(dweight), _ptr(dbias),
+                                           _dtype_code(x), _ptr(ws), _stream()))
+        _written_by_engine(dx, dweight, dbias)
+        return dx, dweight, dbias
+
     # ---- fused BN(+residual)(+ReLU): lgs_bn_forward / lgs_bn_backward
     def bn_forward(self, x, gamma, beta, eps, momentum, running_mean, running_var, residual, relu, num_batches_tracked=None,
                    conv_stats=None, out_into=None):

@@ -549,8 +549,31 @@ class MinkowskiSyncBatchNorm(MinkowskiBatchNorm):
         return out
 
 
+class InstanceNormFunction(torch.autograd.Function):
+    """y = (x - mean[scene]) * rstd[scene] * weight + bias on the engine (lgs_in_forward / lgs_in_backward); keeps x and the
+    per-scene (mean, rstd), not y.  `sm`: the origin segment map of x's coordinate map."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, sm, eps, backend):
+        w32, b32 = weight.detach().float().contiguous(), bias.detach().float().contiguous()
+        y, stats = backend.instance_norm_forward(sm, x, w32, b32, eps)
+        ctx.save_for_backward(x, stats, w32)
+        ctx.sm, ctx.backend = sm, backend
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, stats, w32 = ctx.saved_tensors
+        if dy.dtype != x.dtype:
+            dy = dy.to(x.dtype)
+        dx, dw, db = ctx.backend.instance_norm_backward(ctx.sm, x, dy.contiguous(), w32, stats)
+        return dx, dw.view(1, -1), db.view(1, -1), None, None, None
+
+
 class MinkowskiInstanceNorm(nn.Module):
-    """Per-scene normalisation (only the out-of-scope 34Dv2/v3 variants use it, clip_models.py:416,431)."""
+    """Per-scene normalisation: mean / biased variance over the rows of one batch index, per channel (the heads of
+    Res16UNet34Dv2 / Dv3, clip_models.py:416,431; BasicBlockIN[BN]).  HIP tensors run on the engine's per-scene kernels
+    (tuning knob INSTANCE_NORM=0: the torch lines below, which CPU tensors always take)."""
 
     def __init__(self, num_features):
         super().__init__()
@@ -560,7 +583,16 @@ class MinkowskiInstanceNorm(nn.Module):
         self.bias = nn.Parameter(torch.zeros(1, num_features))
 
     def forward(self, input):
-        x, b = input.F, input.C[:, 0].long()
+        x = input.F
+        backend = get_backend()
+        if x.is_cuda and hasattr(backend, "instance_norm_forward") and backend.instance_norm_enabled():
+            mgr = input.coordinate_manager
+            sm = mgr.segment_map_handle(input.coordinate_map_key, mgr.origin_key())
+            w = self.weight if self.weight.dtype == torch.float32 else self.weight.float()
+            b = self.bias if self.bias.dtype == torch.float32 else self.bias.float()
+            y = InstanceNormFunction.apply(x.contiguous(), w, b, sm, self.eps, backend)
+            return input._like(y)
+        b = input.C[:, 0].long()
         nb = int(b.max().item()) + 1 if b.numel() else 0
         cnt = torch.zeros(nb, device=x.device, dtype=torch.float32).index_add_(0, b, torch.ones_like(b, dtype=torch.float32))
         xf = x.float()

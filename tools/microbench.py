@@ -1,5 +1,5 @@
 """Per-op timings on the GPU (HIP events on torch's current stream) for the hot layer shapes.
-usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool]"""
+usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm]"""
 import os
 import sys
 import time
@@ -336,9 +336,68 @@ def pool():
         print("%-28s %8.1f us  %6.1f MB  %.2f TB/s  %.2f of 8 TB/s" % (name, t * 1e3, nbytes / 1e6, nbytes / t / 1e9, nbytes / t / 1e9 * 1e12 / peak))
 
 
+def instnorm():
+    """MinkowskiInstanceNorm on the 8-scene batch: the engine kernels, the torch lines (INSTANCE_NORM=0, same process, same
+    tensors, alternating) and BatchNorm (lgs_bn_forward / lgs_bn_backward, training mode) on the same tensor.  Algorithmic bytes:
+    forward 3 N C e + 4 N (x twice, y once, the scene index per row), backward 5 N C e + 4 N (x and dy twice, dx once)."""
+    from languagegroundedsemseg_amd import engine
+    be = ME.get_backend()
+    coords, _, _ = make_batch(list(range(8)), voxel=0.02, n_target=150000)
+    x0 = ME.SparseTensor(torch.zeros(coords.shape[0], 1, device=DEV), torch.from_numpy(coords).to(DEV))
+    m, k0 = x0.coordinate_manager, x0.coordinate_map_key
+    keys = {0: k0, 2: m.coarser_key(k0, 4)}
+    peak = 8e12
+    for level, C, dtype in [(0, 96, torch.bfloat16), (0, 96, torch.float32), (0, 512, torch.bfloat16), (0, 512, torch.float32),
+                            (2, 128, torch.bfloat16), (2, 128, torch.float32)]:
+        key = keys[level]
+        n, e = m.size(key), (2 if dtype == torch.bfloat16 else 4)
+        f = torch.randn(n, C, device=DEV).to(dtype).requires_grad_(True)
+        dy = torch.randn(n, C, device=DEV).to(dtype)
+        st = ME.SparseTensor(f, coordinate_map_key=key, coordinate_manager=m)
+        mod = ME.MinkowskiInstanceNorm(C).to(DEV)
+        gamma, beta = torch.ones(C, device=DEV), torch.zeros(C, device=DEV)
+        rm, rv, nbt = torch.zeros(C, device=DEV), torch.ones(C, device=DEV), torch.zeros((), dtype=torch.int64, device=DEV)
+        fd = f.detach()
+        bwd_bytes, fwd_bytes = 5 * n * C * e + 4 * n, 3 * n * C * e + 4 * n
+        print("level %d: %d rows, %d scenes, C = %d %s" % (level, n, m.size(m.origin_key()), C, str(dtype).replace("torch.", "")))
+        res = {}
+        for rep in range(2):                       # alternating: engine, torch lines, engine, torch lines
+            for knob in (1, 0):
+                with engine.tuning(INSTANCE_NORM=knob):
+                    out = mod(st).F
+                    tf = timeit(lambda: mod(st).F, 10 if knob else 3, 2)
+                    tb = timeit(lambda: out.backward(dy, retain_graph=True), 10 if knob else 3, 2)
+                    f.grad = None
+                    del out
+                    torch.cuda.synchronize()
+                    base = torch.cuda.memory_allocated()
+                    torch.cuda.reset_peak_memory_stats()
+                    mod(st).F.backward(dy)
+                    torch.cuda.synchronize()
+                    pk = torch.cuda.max_memory_allocated() - base
+                    f.grad = None
+                res[knob] = (min(tf, res[knob][0]) if knob in res else tf, min(tb, res[knob][1]) if knob in res else tb, pk)
+        y, stats = be.bn_forward(fd, gamma, beta, 1e-5, 0.1, rm, rv, None, 0, nbt)
+        tbf = timeit(lambda: be.bn_forward(fd, gamma, beta, 1e-5, 0.1, rm, rv, None, 0, nbt), 10, 2)
+        tbb = timeit(lambda: be.bn_backward(fd, y, dy, gamma, beta, stats, 0, False), 10, 2)
+        del y
+        for name, t, nbytes in [("instance norm fwd (engine)", res[1][0], fwd_bytes), ("instance norm bwd (engine)", res[1][1], bwd_bytes),
+                                ("instance norm fwd (INSTANCE_NORM=0)", res[0][0], fwd_bytes),
+                                ("instance norm bwd (INSTANCE_NORM=0)", res[0][1], bwd_bytes),
+                                ("lgs_bn_forward", tbf, fwd_bytes - 4 * n), ("lgs_bn_backward", tbb, bwd_bytes - 4 * n)]:
+            print("%-36s %9.1f us  %7.1f MB  %.2f TB/s  %.2f of 8 TB/s" % (name, t * 1e3, nbytes / 1e6, nbytes / t / 1e9, nbytes / t / 1e9 * 1e12 / peak))
+        print("%-36s fwd %.2f x, bwd %.2f x faster than the torch lines; %.2f x / %.2f x BatchNorm's time" % (
+            "  engine", res[0][0] / res[1][0], res[0][1] / res[1][1], res[1][0] / tbf, res[1][1] / tbb))
+        print("%-36s engine %.1f MB, INSTANCE_NORM=0 %.1f MB (x is %.1f MB)" % ("  peak memory of one fwd + bwd", res[1][2] / 1e6, res[0][2] / 1e6, n * C * e / 1e6))
+        del f, dy, st, fd
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "pool":
         pool()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "instnorm":
+        instnorm()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "wide":
         wide()
