@@ -109,10 +109,27 @@ int lgs_manager_get_coords(lgs_manager *mgr, int key, int32_t *dst, void *stream
  *   kernel_size 2, out_key == stride2(in_key)   : 2x2x2 stride-2 (a5); the transposed conv (a6)
  *                                                 uses the same object with `transposed` views
  *   kernel_size 1, in_key == out_key            : identity (a7)
+ * Everything else is refused here, as it always was; the strided 3^3 / 1x1 and the dilated 3^3 relations are
+ * lgs_manager_kernel_map_ex's (below).
  * replaces: the implicit kernel-map construction in MinkowskiConvolution[Transpose].forward
  *   /root/reference/models/modules/common.py:179-236                                           */
 int lgs_manager_kernel_map(lgs_manager *mgr, int in_key, int out_key, int kernel_size, void *stream,
                            lgs_kmap **out);
+
+/* The kernel maps of the ResNet encoder family (models/resnet.py: conv(kernel_size=3, stride=2), conv(kernel_size=1, stride=2),
+ * dilation= on every 3x3x3 conv of a block).  A NEW SYMBOL ONLY: LGS_ABI_VERSION stays 18, no existing entry point or struct
+ * changes; a library that lacks the symbol lacks the capability.  Cached per (in_key, out_key, kernel_size, dilation).
+ * With dilation == 1 and one of the three relations above it returns the very object lgs_manager_kernel_map returns.  New:
+ *   kernel_size 3, in_key == out_key, dilation d >= 2 : 3x3x3 stride-1 with offsets (-1,0,1) * d * tensor_stride, K = 27, centred,
+ *                                                       first spatial axis fastest
+ *   kernel_size 3, out_key == stride2(in_key), d == 1 : 3x3x3 stride-2: c_in = c_out + off_k * tensor_stride(in), K = 27; the output
+ *                                                       rows are the stride-2 map's
+ *   kernel_size 1, out_key == stride2(in_key), d == 1 : 1x1 stride-2: the fine row at the coarse row's coordinate, if any, K = 1
+ * Stride 2 combined with dilation > 1 is refused, and so is every other combination.  Offsets that leave the coordinate range
+ * have no pair; dilation * tensor_stride must stay below 2^17.  Every conv entry point below takes the new maps with
+ * `transposed` 0 and 1.                                                                                             */
+int lgs_manager_kernel_map_ex(lgs_manager *mgr, int in_key, int out_key, int kernel_size, int dilation, void *stream,
+                              lgs_kmap **out);
 
 /* Export the map as (k, in_row, out_row) triples for set-equality parity tests.
  * Pass NULL buffers to query *m only (synchronises). Buffers are device int32[*m]. */

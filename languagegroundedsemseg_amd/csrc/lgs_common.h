@@ -146,9 +146,22 @@ int segmap_wait(lgs_segmap *sm, hipStream_t stream);
 struct lgs_kmap {
   lgs_manager *mgr = nullptr;
   int in_key = -1, out_key = -1, ks = 0, K = 1;
+  int dilation = 1;   // offset scale of a 3^3 stride-1 map in units of the tensor stride (part of the cache key)
+  int strided = 0;    // 1: a 3^3 or 1x1 map between a map and its stride-2 map (lgs_manager_kernel_map_ex); both views carry offset k in slot k
   lgs::View fwd;  // gathers from the in map, writes the out map
   lgs::View bwd;  // gathers from the out map, writes the in map (dgrad / transposed conv)
 };
+
+namespace lgs {
+// `transposed` = 1 on a 3^3 map: the maps of lgs_manager_kernel_map_ex take it, the plain stride-1 map refuses it as it always has
+inline bool transposed_ok(const lgs_kmap *km) { return km->ks != 3 || km->strided || km->dilation > 1; }
+// the facts of a map that the synthetic views of the debug plan queries do not carry, derived from their row counts: a 3^3 / 1x1 map
+// whose two sides differ in rows is a strided one; the bwd side of a 3^3 stride-1 map is the shared table read mirrored
+inline void synthetic_kmap_facts(lgs_kmap &km) {
+  km.strided = (km.ks == 3 || km.ks == 1) && km.fwd.n_in != km.fwd.n_out ? 1 : 0;
+  km.bwd.mirror = (km.ks == 3 && !km.strided) ? 1 : 0;
+}
+}  // namespace lgs
 
 struct lgs_segmap {
   lgs_manager *mgr = nullptr;

@@ -101,7 +101,9 @@ template <> __device__ inline void mma16<float>(f32x16 &acc, const u32x4 &w, con
 //   Wsrc[g = c*32 + h*16 + t*EPL + e][o = nb*32 + j]   of weight matrix kd
 // where (g = gathered/reduction channel, o = output channel):
 //   plain      : Wsrc[g][o] = w[ks][g][o],        ks = kd
-//   transposed : Wsrc[g][o] = w[ks][o][g],        ks = mirror ? K-1-kd : kd      (dgrad)
+//   transposed : Wsrc[g][o] = w[ks][o][g]                                        (dgrad)
+// with ks = mirror ? K-1-kd : kd in both: slot kd of a mirrored view (the shared 3^3 stride-1 table read from the other side: its
+// dgrad, and the forward of its transposed conv) carries offset K-1-kd.
 // Out-of-range g / o are zero (channel padding to multiples of 32).
 template <typename T>
 __device__ inline uint4 pack_one(const float *__restrict__ w, int K, int cin_w, int cout_w, int transposed, int mirror, int g_real,
@@ -113,7 +115,7 @@ __device__ inline uint4 pack_one(const float *__restrict__ w, int K, int cin_w, 
   int nb = (int)(r % nb_total); r /= nb_total;
   int c = (int)(r % nc);
   int kd = (int)(r / nc);
-  int ks = (transposed && mirror) ? K - 1 - kd : kd;
+  int ks = mirror ? K - 1 - kd : kd;
   int j = lane & 31, h = lane >> 5;
   int o = nb * 32 + j;
   if constexpr (Tr<T>::SPLIT) {
@@ -1225,10 +1227,9 @@ inline ConvPlan plan_of(const View &v, int K, int g_real, int o_real, int dtype,
 // one forward / dgrad call: op 1 gathers grad_out [*, cout] and reads the weights transposed (3^3: mirrored)
 inline int conv_call(lgs_kmap *km, int op, int transposed, const void *in, int cin, const float *weight, int cout, const float *bias,
                      void *out, int dtype, void *workspace, const BnEpi *bn, void *packed, int pack_mode, int in_ld, void *stream) {
-  LGS_REQUIRE(!(transposed && km->ks == 3), "transposed 3x3x3 convolution is not part of the model family");
+  LGS_REQUIRE(!transposed || transposed_ok(km), "transposed 3x3x3 convolution is not part of the model family");
   LGS_REQUIRE(known_dtype(dtype), "sparse conv: unknown dtype");
-  View v = op_view(km, op, transposed);
-  v.mirror = (op == 1 && km->ks == 3) ? 1 : 0;
+  const View v = op_view(km, op, transposed);   // (with its own mirror flag: set on the bwd side of a shared 3^3 stride-1 table only)
   hipStream_t s = (hipStream_t)stream;
   if (kmap_wait(km, s)) return 1;
   return with_instance(dtype, [&](auto i) {
@@ -1273,7 +1274,7 @@ int lgs_conv_pack_desc(const lgs_kmap *km, int op, int transposed, int cin, int 
   const ConvPlan pl = plan_of(op_view(km, op, transposed), km->K, g, o, dtype, op == 0 ? kEpiBnStats : kEpiAccum);
   memset(out, 0, sizeof(*out));
   if (!pl.packed_ext_ok) return 0;      // empty maps, scratch / padded-input routes pack internally
-  out->K = km->K; out->cin_w = cin; out->cout_w = cout; out->transposed = op; out->mirror = (op == 1 && km->ks == 3) ? 1 : 0;
+  out->K = km->K; out->cin_w = cin; out->cout_w = cout; out->transposed = op; out->mirror = op_view(km, op, transposed).mirror;
   out->g_real = g; out->o_real = o; out->ncp = pl.ncp; out->nbp = pl.nbp;
   out->dtype = (dtype == LGS_F32 && tune(T_FP32_SPLIT) != 0) ? kDtF32Split : dtype;
   out->total = pl.total;
@@ -1310,7 +1311,7 @@ int lgs_conv_dgrad(lgs_kmap *km, int transposed, const void *grad_out, int cout,
 // 1 if lgs_conv_dgrad_accumulate adds inside the kernel epilogue for this launch shape (everything but the 2-D blocked wide
 // kernel and input widths off the 4-channel grid)
 int lgs_conv_dgrad_can_accumulate(const lgs_kmap *km, int transposed, int cin, int cout, int dtype) {
-  if (!km || (transposed && km->ks == 3) || !known_dtype(dtype)) return 0;
+  if (!km || (transposed && !transposed_ok(km)) || !known_dtype(dtype)) return 0;
   return plan_of(op_view(km, 1, transposed), km->K, cout, cin, dtype, kEpiAccum).can_accumulate;
 }
 
@@ -1339,6 +1340,7 @@ int lgs_debug_conv_plan(const lgs_conv_plan_query *q, lgs_conv_plan_info *out) {
   };
   lgs_kmap km;
   km.ks = q->ks; km.K = q->fwd.K; km.fwd = view(q->fwd); km.bwd = view(q->bwd);
+  synthetic_kmap_facts(km);
   *out = plan_of(op_view(&km, q->op, q->transposed), km.K, q->op == 0 ? q->cin : q->cout, q->op == 0 ? q->cout : q->cin, q->dtype, (ConvEpi)q->epilogue);
   out->workspace_bytes = lgs_conv_workspace_bytes(&km, q->cin, q->cout, q->dtype, q->op);
   out->q_bn_partial_rows = q->op == 0 ? lgs_conv_bn_partial_rows(&km, q->transposed, q->cout, q->dtype) : 0;

@@ -18,6 +18,7 @@
 #include "lgs_common.h"
 
 #include <cstring>
+#include <memory>
 #include <rocprim/rocprim.hpp>
 
 namespace lgs {
@@ -300,6 +301,89 @@ __global__ void k_permute_map3(const int32_t *nbr_tmp, const uint32_t *pmask, co
     if (__ballot((pm >> k) & 1u)) m |= 1u << k;
   }
   if ((threadIdx.x & 63) == 0) mask64[q >> 6] = m;
+}
+
+// 3x3x3 stride-2, fine-stationary view (dgrad of the strided conv, forward of its transposed conv): slot k of fine position p holds
+// the coarse row at c_fine - off_k * ts.  That coordinate lies on the coarse grid only where, on every axis, off_k is 0 for an even
+// fine coordinate (in units of ts) and +-1 for an odd one: at most 2^3 of the 27 offsets, fixed by the row's parity class.  Only
+// those are probed, all (<= 8) in flight together as in k_build_map3; the other slots are -1.  Rows of one parity class share the
+// candidate set, so the window mask sort that follows groups them and a 64-row group's mask64 carries at most 8 bits.
+__global__ void k_build_map3_fine(const uint64_t *fkeys, int64_t n, int64_t n_pad, int log2ts, const uint64_t *hkeys,
+                                  const int32_t *hvals, uint64_t capm1, int32_t *nbr, uint32_t *pmask) {
+  int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // blockDim multiple of 64; p < n_pad by grid
+  const bool live = p < n;
+  int b = 0, x = 0, y = 0, z = 0;
+  if (live) unpack_key(fkeys[p], b, x, y, z);
+  const int ts = 1 << log2ts;
+  // the bias 2^17 is a multiple of 2 ts, so the parity of the biased coordinate is the parity of the coordinate
+  const int ox = (x >> log2ts) & 1, oy = (y >> log2ts) & 1, oz = (z >> log2ts) & 1;
+  uint64_t key[8], slot[8], hk[8];
+  int kk[8];
+  bool ok[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int jx = j & 1, jy = (j >> 1) & 1, jz = j >> 2;
+    // an even axis has the single candidate 0 (taken at j-bit 0), an odd one -1 and +1
+    const int dx = ox ? 2 * jx - 1 : 0, dy = oy ? 2 * jy - 1 : 0, dz = oz ? 2 * jz - 1 : 0;
+    const int xx = x - dx * ts, yy = y - dy * ts, zz = z - dz * ts;
+    ok[j] = live && (ox || !jx) && (oy || !jy) && (oz || !jz) && (((unsigned)xx | (unsigned)yy | (unsigned)zz) < (1u << kCoordBits));
+    kk[j] = (dx + 1) + 3 * (dy + 1) + 9 * (dz + 1);
+    key[j] = ok[j] ? pack_key(b, xx, yy, zz) : 0ull;
+    slot[j] = hash64(key[j]) & capm1;
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) hk[j] = ok[j] ? hkeys[slot[j]] : kEmpty;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    if (ok[j]) {
+      uint64_t cur = hk[j], sl = slot[j];
+      while (cur != key[j] && cur != kEmpty) {
+        sl = (sl + 1) & capm1;
+        cur = hkeys[sl];
+      }
+      slot[j] = sl;
+      ok[j] = cur == key[j];
+    }
+  }
+  uint32_t m = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    if (ok[j]) m |= 1u << kk[j];
+  int32_t r[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = ok[j] ? hvals[slot[j]] : -1;
+  for (int k = 0; k < 27; ++k) {
+    int32_t v = -1;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (ok[j] && kk[j] == k) v = r[j];
+    nbr[(int64_t)k * n_pad + p] = v;
+  }
+  pmask[p] = m;
+}
+
+// 1x1 stride-2: the fine row at the coarse row's own coordinate, if there is one.  No hashing: the fine positions of a coarse cell are
+// one run of the Morton order and the cell's own coordinate has the smallest key of the run, so it can only be the run's first position.
+// coarse-stationary view: nbr[q] = that fine row or -1 (padding: -1)
+__global__ void k_build_map1_coarse(const uint64_t *fkeys, const int32_t *forder, const uint64_t *ckeys, const int32_t *cstart,
+                                    int64_t n_c, int64_t nc_pad, int32_t *nbr) {
+  int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nc_pad) return;
+  int32_t r = -1;
+  if (q < n_c) {
+    const int32_t p = cstart[q];
+    if (fkeys[p] == ckeys[q]) r = forder ? forder[p] : p;
+  }
+  nbr[q] = r;
+}
+// fine-stationary view: position p writes fine row out_row[p]; nbr[p] = its coarse row where the fine coordinate lies on the coarse grid
+__global__ void k_build_map1_fine(const uint64_t *fkeys, const int32_t *forder, const int32_t *fine_cidx, int64_t n, int64_t n_pad,
+                                  uint64_t child_bits, int32_t *nbr, int32_t *out_row) {
+  int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_pad) return;
+  const bool live = p < n;
+  nbr[p] = (live && (fkeys[p] & child_bits) == 0) ? fine_cidx[p] : -1;
+  out_row[p] = live ? (forder ? forder[p] : (int32_t)p) : -1;
 }
 
 // 2x2x2 stride-2, coarse-stationary view: nbr8[k][q] = fine row of child k of coarse row q
@@ -693,6 +777,46 @@ int scan_incl(lgs_manager *m, const int32_t *in, int32_t *out, int64_t n, hipStr
   return 0;
 }
 
+// the window mask sort of a 27-slot table built in sorted-position order (nbr_tmp, pmask) and its permutation into the view's arrays:
+// position q of the view is sorted position perm[q] and writes row order[perm[q]] (order == nullptr: the position itself)
+int sort_map3(lgs_manager *m, int64_t n, int64_t n_pad, const int32_t *nbr_tmp, const uint32_t *pmask, const int32_t *order, uint64_t *keys,
+              uint64_t *skeys2, int32_t *vals, int32_t *perm, int32_t *nbr, int32_t *orow, uint32_t *mask, hipStream_t s) {
+  const int window = (int)tune(T_MASK_WINDOW);   // tuning knob (default kMaskWindow)
+  LGS_KLAUNCH(k_mask_sort_keys, (unsigned)(n_pad / 256), 256, 0, s, pmask, n, n_pad, window, (int)tune(T_MASK_ORDER), keys, vals);
+  {
+    size_t tb = 0;
+    const unsigned eb = mask_sort_bits(n_pad, window);
+    LGS_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys, skeys2, vals, perm, (size_t)n_pad, 0, eb, s));
+    void *tmp = nullptr;
+    if (raw_alloc(m, &tmp, tb ? tb : 16, s)) return 1;
+    LGS_HIP(rocprim::radix_sort_pairs(tmp, tb, keys, skeys2, vals, perm, (size_t)n_pad, 0, eb, s));
+    if (dfree_now(m, tmp, s)) return 1;
+  }
+  LGS_KLAUNCH(k_permute_map3, (unsigned)(n_pad / 256), 256, 0, s, nbr_tmp, pmask, perm, order, n, n_pad, nbr, orow, mask);
+  LGS_HIP(hipGetLastError());
+  return 0;
+}
+
+// a 27-slot view over the rows of map `st` (the stationary side): table built by `build` into (nbr_tmp, pmask), then sort_map3
+template <typename Build>
+int make_view27(lgs_manager *m, const CoordMap &st, int64_t n_in, hipStream_t s, View &v, Build &&build) {
+  v = View();
+  v.n_pad = st.n_pad; v.n_out = st.n; v.n_in = n_in; v.KS = 27; v.K = 27;
+  if (st.n == 0) return 0;
+  int32_t *nbr, *orow, *nbr_tmp, *vals, *perm; uint32_t *mask, *pmask; uint64_t *keys, *skeys2;
+  if (dalloc(m, &nbr, 27 * st.n_pad, s) || dalloc(m, &mask, st.n_pad / kGroup, s) || dalloc(m, &orow, st.n_pad, s) ||
+      dalloc(m, &nbr_tmp, 27 * st.n_pad, s) || dalloc(m, &pmask, st.n_pad, s) || dalloc(m, &keys, st.n_pad, s) ||
+      dalloc(m, &skeys2, st.n_pad, s) || dalloc(m, &vals, st.n_pad, s) || dalloc(m, &perm, st.n_pad, s))
+    return 1;
+  if (build(nbr_tmp, pmask)) return 1;
+  if (sort_map3(m, st.n, st.n_pad, nbr_tmp, pmask, st.order, keys, skeys2, vals, perm, nbr, orow, mask, s)) return 1;
+  if (dfree_now(m, nbr_tmp, s) || dfree_now(m, pmask, s) || dfree_now(m, keys, s) || dfree_now(m, skeys2, s) ||
+      dfree_now(m, vals, s) || dfree_now(m, perm, s))
+    return 1;
+  v.nbr = nbr; v.mask64 = mask; v.out_row = orow;
+  return 0;
+}
+
 }  // namespace
 
 namespace lgs {
@@ -921,7 +1045,7 @@ int lgs_manager_kernel_map(lgs_manager *m, int in_key, int out_key, int ks, void
   LGS_REQUIRE(in_key >= 0 && in_key < nm && out_key >= 0 && out_key < nm, "lgs_manager_kernel_map: bad key");
   LGS_REQUIRE(!m->maps[in_key].origin && !m->maps[out_key].origin, "lgs_manager_kernel_map: no kernel maps on the origin map");
   for (lgs_kmap *k : m->kmaps)
-    if (k->in_key == in_key && k->out_key == out_key && k->ks == ks) { *out = k; return 0; }
+    if (k->in_key == in_key && k->out_key == out_key && k->ks == ks && k->dilation == 1 && !k->strided) { *out = k; return 0; }
   hipStream_t s = m->ms;
   (void)stream;
   DeviceGuard guard(m->device);
@@ -936,36 +1060,14 @@ int lgs_manager_kernel_map(lgs_manager *m, int in_key, int out_key, int ks, void
   } else if (ks == 3) {
     LGS_REQUIRE(in_key == out_key, "kernel_size 3 is supported for stride 1 (in_key == out_key) only");
     km->K = 27;
-    int32_t *nbr = nullptr, *orow = nullptr; uint32_t *mask = nullptr;
-    if (ci.n > 0) {
-      if (ensure_hash(m, ci, s)) return 1;
-      int32_t *nbr_tmp, *vals, *perm; uint32_t *pmask; uint64_t *keys, *skeys2;
-      if (dalloc(m, &nbr, 27 * ci.n_pad, s) || dalloc(m, &mask, ci.n_pad / kGroup, s) || dalloc(m, &orow, ci.n_pad, s) ||
-          dalloc(m, &nbr_tmp, 27 * ci.n_pad, s) || dalloc(m, &pmask, ci.n_pad, s) || dalloc(m, &keys, ci.n_pad, s) ||
-          dalloc(m, &skeys2, ci.n_pad, s) || dalloc(m, &vals, ci.n_pad, s) || dalloc(m, &perm, ci.n_pad, s))
-        return 1;
-      LGS_KLAUNCH(k_build_map3, (unsigned)(ci.n_pad / 256), 256, 0, s, ci.skeys, ci.n, ci.n_pad, ci.ts, ci.hkeys,
-                         ci.hvals, (uint64_t)(ci.hcap - 1), nbr_tmp, pmask);
-      const int window = (int)tune(T_MASK_WINDOW);   // tuning knob (default kMaskWindow)
-      LGS_KLAUNCH(k_mask_sort_keys, (unsigned)(ci.n_pad / 256), 256, 0, s, pmask, ci.n, ci.n_pad, window, (int)tune(T_MASK_ORDER), keys, vals);
-      {
-        size_t tb = 0;
-        const unsigned eb = mask_sort_bits(ci.n_pad, window);
-        LGS_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys, skeys2, vals, perm, (size_t)ci.n_pad, 0, eb, s));
-        void *tmp = nullptr;
-        if (raw_alloc(m, &tmp, tb ? tb : 16, s)) return 1;
-        LGS_HIP(rocprim::radix_sort_pairs(tmp, tb, keys, skeys2, vals, perm, (size_t)ci.n_pad, 0, eb, s));
-        if (dfree_now(m, tmp, s)) return 1;
-      }
-      LGS_KLAUNCH(k_permute_map3, (unsigned)(ci.n_pad / 256), 256, 0, s, nbr_tmp, pmask, perm, ci.order, ci.n, ci.n_pad,
-                         nbr, orow, mask);
-      LGS_HIP(hipGetLastError());
-      if (dfree_now(m, nbr_tmp, s) || dfree_now(m, pmask, s) || dfree_now(m, keys, s) || dfree_now(m, skeys2, s) ||
-          dfree_now(m, vals, s) || dfree_now(m, perm, s))
-        return 1;
-    }
-    View v; v.nbr = nbr; v.mask64 = mask; v.out_row = orow; v.n_pad = ci.n_pad; v.n_out = ci.n; v.n_in = ci.n;
-    v.KS = 27; v.K = 27;
+    if (ci.n > 0 && ensure_hash(m, ci, s)) return 1;
+    View v;
+    if (make_view27(m, ci, ci.n, s, v, [&](int32_t *nbr_tmp, uint32_t *pmask) {
+          LGS_KLAUNCH(k_build_map3, (unsigned)(ci.n_pad / 256), 256, 0, s, ci.skeys, ci.n, ci.n_pad, ci.ts, ci.hkeys, ci.hvals,
+                      (uint64_t)(ci.hcap - 1), nbr_tmp, pmask);
+          return 0;
+        }))
+      return 1;
     km->fwd = v;
     km->bwd = v; km->bwd.mirror = 1;
   } else if (ks == 2) {
@@ -1018,6 +1120,84 @@ int lgs_manager_kernel_map(lgs_manager *m, int in_key, int out_key, int ks, void
   }
   m->kmaps.push_back(km);
   *out = km;
+  return publish(m, nullptr, false);
+}
+
+int lgs_manager_kernel_map_ex(lgs_manager *m, int in_key, int out_key, int ks, int dilation, void *stream, lgs_kmap **out) {
+  LGS_REQUIRE(m && out, "lgs_manager_kernel_map_ex: null argument");
+  const int nm = (int)m->maps.size();
+  LGS_REQUIRE(in_key >= 0 && in_key < nm && out_key >= 0 && out_key < nm, "lgs_manager_kernel_map_ex: bad key");
+  LGS_REQUIRE(!m->maps[in_key].origin && !m->maps[out_key].origin, "lgs_manager_kernel_map_ex: no kernel maps on the origin map");
+  LGS_REQUIRE(dilation >= 1, "lgs_manager_kernel_map_ex: dilation must be >= 1");
+  const bool strided = in_key != out_key && m->maps[out_key].fine_key == in_key;
+  LGS_REQUIRE(!(strided && dilation > 1), "lgs_manager_kernel_map_ex: stride 2 combined with dilation > 1 is not supported");
+  LGS_REQUIRE(dilation == 1 || ks == 3, "lgs_manager_kernel_map_ex: dilation > 1 needs kernel_size 3");
+  // the three relations of lgs_manager_kernel_map (and everything it refuses): the same cached objects
+  if (dilation == 1 && !(strided && (ks == 3 || ks == 1))) return lgs_manager_kernel_map(m, in_key, out_key, ks, stream, out);
+  LGS_REQUIRE(strided || in_key == out_key, "lgs_manager_kernel_map_ex: out_key must be in_key or stride2(in_key)");
+  for (lgs_kmap *k : m->kmaps)
+    if (k->in_key == in_key && k->out_key == out_key && k->ks == ks && k->dilation == dilation) { *out = k; return 0; }
+  hipStream_t s = m->ms;
+  DeviceGuard guard(m->device);
+  CoordMap &ci = m->maps[in_key];
+  // the coarse-stationary views take "position == output row": a map made by stride2 has its rows in Morton order (order == nullptr)
+  LGS_REQUIRE(!strided || m->maps[out_key].order == nullptr, "lgs_manager_kernel_map_ex: the stride-2 map's rows are not in sorted order");
+  // every probed coordinate must stay inside the packed range's reach: offsets of d * ts below 2^17
+  LGS_REQUIRE((int64_t)dilation * ci.ts < (1ll << (kCoordBits - 1)), "lgs_manager_kernel_map_ex: dilation * tensor_stride must stay below 2^17");
+  std::unique_ptr<lgs_kmap> km(new lgs_kmap());
+  km->mgr = m; km->in_key = in_key; km->out_key = out_key; km->ks = ks; km->dilation = dilation; km->strided = strided ? 1 : 0;
+  if (!strided) {
+    // dilated 3^3 stride-1: the stride-1 pipeline with the offset scale d * ts; bwd = fwd read mirrored
+    km->K = 27;
+    if (ci.n > 0 && ensure_hash(m, ci, s)) return 1;
+    const int scale = dilation * ci.ts;
+    View v;
+    if (make_view27(m, ci, ci.n, s, v, [&](int32_t *nbr_tmp, uint32_t *pmask) {
+          LGS_KLAUNCH(k_build_map3, (unsigned)(ci.n_pad / 256), 256, 0, s, ci.skeys, ci.n, ci.n_pad, scale, ci.hkeys, ci.hvals,
+                      (uint64_t)(ci.hcap - 1), nbr_tmp, pmask);
+          return 0;
+        }))
+      return 1;
+    km->fwd = v;
+    km->bwd = v; km->bwd.mirror = 1;
+  } else if (ks == 3) {
+    // 3^3 stride-2.  Both views carry offset k in slot k (no mirroring): the fine-stationary one lists, per fine row, the coarse row
+    // of the pair (k, fine, coarse) under the k of the forward direction
+    CoordMap &co = m->maps[out_key];
+    km->K = 27;
+    if (ci.n > 0 && (ensure_hash(m, ci, s) || ensure_hash(m, co, s))) return 1;
+    // coarse-stationary: the 27 probes of k_build_map3, from the coarse rows' keys into the FINE map's hash, offsets scaled by ts_in
+    if (make_view27(m, co, ci.n, s, km->fwd, [&](int32_t *nbr_tmp, uint32_t *pmask) {
+          LGS_KLAUNCH(k_build_map3, (unsigned)(co.n_pad / 256), 256, 0, s, co.skeys, co.n, co.n_pad, ci.ts, ci.hkeys, ci.hvals,
+                      (uint64_t)(ci.hcap - 1), nbr_tmp, pmask);
+          return 0;
+        }))
+      return 1;
+    if (make_view27(m, ci, co.n, s, km->bwd, [&](int32_t *nbr_tmp, uint32_t *pmask) {
+          LGS_KLAUNCH(k_build_map3_fine, (unsigned)(ci.n_pad / 256), 256, 0, s, ci.skeys, ci.n, ci.n_pad, ci.log2ts, co.hkeys, co.hvals,
+                      (uint64_t)(co.hcap - 1), nbr_tmp, pmask);
+          return 0;
+        }))
+      return 1;
+  } else {
+    // 1x1 stride-2: plain nbr (/ out_row) pairs on the KS = 1 path
+    CoordMap &co = m->maps[out_key];
+    km->K = 1;
+    View vf, vb;
+    vf.KS = 1; vf.K = 1; vf.n_pad = co.n_pad; vf.n_out = co.n; vf.n_in = ci.n;
+    vb.KS = 1; vb.K = 1; vb.n_pad = ci.n_pad; vb.n_out = ci.n; vb.n_in = co.n;
+    if (ci.n > 0) {
+      int32_t *nf, *nb, *ob;
+      if (dalloc(m, &nf, co.n_pad, s) || dalloc(m, &nb, ci.n_pad, s) || dalloc(m, &ob, ci.n_pad, s)) return 1;
+      LGS_KLAUNCH(k_build_map1_coarse, nblk(co.n_pad), 256, 0, s, ci.skeys, ci.order, co.skeys, co.cstart, co.n, co.n_pad, nf);
+      LGS_KLAUNCH(k_build_map1_fine, nblk(ci.n_pad), 256, 0, s, ci.skeys, ci.order, co.fine_cidx, ci.n, ci.n_pad, 7ull << (3 * ci.log2ts), nb, ob);
+      LGS_HIP(hipGetLastError());
+      vf.nbr = nf; vb.nbr = nb; vb.out_row = ob;
+    }
+    km->fwd = vf; km->bwd = vb;
+  }
+  m->kmaps.push_back(km.get());
+  *out = km.release();
   return publish(m, nullptr, false);
 }
 

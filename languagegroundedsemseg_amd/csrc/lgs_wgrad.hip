@@ -724,7 +724,9 @@ __global__ __launch_bounds__(256, OCC) void k_wgrad_bf16(View v, const bf16_t *_
 // loads, the padded slab rows are 128-byte aligned), four slabs in flight: the reduce reads S x K x Cin x Cout floats
 // (295 MB at level 0) and used to run as one dependent 4-byte load per slab and thread.
 __global__ __launch_bounds__(256) void k_wgrad_reduce(const float *__restrict__ partial, int S, int K, int cin_pad, int cout_pad,
-                                                      int cin, int cout, float *__restrict__ gw) {
+                                                      int cin, int cout, float *__restrict__ gw, int mirror) {
+  // mirror: the slabs were summed per SLOT of a mirrored view (the shared 3^3 stride-1 table walked from its other side by a
+  // transposed conv), whose slot K-1-k carries offset k
   const int cq = (cout + 3) / 4;                       // channel quads per row
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t total = (int64_t)K * cin * cq;
@@ -733,7 +735,7 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(const float *__restrict__ 
   const int ci = (int)((idx / cq) % cin);
   const int k = (int)(idx / ((int64_t)cq * cin));
   const int64_t slab = (int64_t)K * cin_pad * cout_pad;
-  const float *src = partial + ((int64_t)k * cin_pad + ci) * cout_pad + 4 * q;
+  const float *src = partial + ((int64_t)(mirror ? K - 1 - k : k) * cin_pad + ci) * cout_pad + 4 * q;
   float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0, a3 = a0;
   int x = 0;
   for (; x + 4 <= S; x += 4) {
@@ -1323,7 +1325,10 @@ WgradPlan wgrad_plan(const lgs_kmap &km, int transposed, int cin, int cout, int 
   WgradPlan p = {};
   const View &v = transposed ? km.bwd : km.fwd;  // same view as the forward
   if (v.n_pad == 0) return p;
-  if (dtype == LGS_BF16 && km.fwd.n_pad > 0 && (km.ks == 3 || km.ks == 2)) {
+  // k_wgrad_wide and k_wgrad_ps have been run and measured on the 3^3 stride-1 table and the 2^3 views only: a 3^3 map with two
+  // different row spaces, and any 3^3 map walked by a transposed conv, goes to the pair-list / fp32 kernels, which take any view
+  const bool pairs_only = km.ks == 3 && (km.strided || transposed);
+  if (dtype == LGS_BF16 && km.fwd.n_pad > 0 && (km.ks == 3 || km.ks == 2) && !pairs_only) {
     const int ld = in_row_stride > 0 ? in_row_stride : cin;
     const bool k3 = km.ks == 3 && !transposed;
     if (k3 && wgrad_wide_plan(km.fwd, cin, cout, ld, p)) return p;
@@ -1365,7 +1370,7 @@ WgradPlan wgrad_plan(const lgs_kmap &km, int transposed, int cin, int cout, int 
 // or strided input
 int64_t wgrad_workspace_bytes(const lgs_kmap *km, int cin, int cout, int dtype) {
   int64_t bytes = 0;
-  for (int transposed = 0; transposed <= (km->ks == 3 ? 0 : 1); ++transposed)
+  for (int transposed = 0; transposed <= (transposed_ok(km) ? 1 : 0); ++transposed)
     for (int in_row_stride : {0, cin + 8}) {
       const int64_t b = wgrad_plan(*km, transposed, cin, cout, dtype, in_row_stride).bytes_total;
       if (b > bytes) bytes = b;
@@ -1414,7 +1419,7 @@ int launch_wgrad_bf16(const View &v, const WgradPlan &p, const bf16_t *in, int c
 }
 
 int conv_wgrad_pairs(const View &v, const WgradPlan &p, const void *in_v, int cin, const void *gout_v, int cout, float *gw, void *workspace,
-                     hipStream_t s) {
+                     hipStream_t s, int mirror = 0) {
   float *partial = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + p.partials.offset);
   const bf16_t *in = reinterpret_cast<const bf16_t *>(in_v), *go = reinterpret_cast<const bf16_t *>(gout_v);
   if (p.pad_in) in = pad_rows_into<bf16_t>(workspace, p.padded_in, in, v.n_in, cin, p.pad_in, s);
@@ -1426,7 +1431,7 @@ int conv_wgrad_pairs(const View &v, const WgradPlan &p, const void *in_v, int ci
     });
   });
   if (rc) return rc;
-  LGS_KLAUNCH(k_wgrad_reduce, (unsigned)p.reduce_blocks, 256, 0, s, partial, p.slots, v.K, p.pad_a, p.pad_b, cin, cout, gw);
+  LGS_KLAUNCH(k_wgrad_reduce, (unsigned)p.reduce_blocks, 256, 0, s, partial, p.slots, v.K, p.pad_a, p.pad_b, cin, cout, gw, mirror);
   LGS_HIP(hipGetLastError());
   return 0;
 }
@@ -1444,13 +1449,13 @@ int launch_wgrad_f32(const View &v, const WgradPlan &p, const float *in, int cin
 }
 
 int conv_wgrad_f32(const View &v, const WgradPlan &p, const void *in_v, int cin, const void *gout_v, int cout, float *gw, void *workspace,
-                   hipStream_t s) {
+                   hipStream_t s, int mirror = 0) {
   float *partial = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + p.partials.offset);
   const float *in = reinterpret_cast<const float *>(in_v), *go = reinterpret_cast<const float *>(gout_v);
   if (p.pad_in) in = pad_rows_into<float>(workspace, p.padded_in, in, v.n_in, cin, p.pad_in, s);
   const int rc = with_blocks<4>(p.t0, [&](auto ncb) { return launch_wgrad_f32<ncb()>(v, p, in, p.pad_in ? p.pad_in : cin, go, cout, partial, s); });
   if (rc) return rc;
-  LGS_KLAUNCH(k_wgrad_reduce, (unsigned)p.reduce_blocks, 256, 0, s, partial, p.slots, v.K, p.pad_a, p.pad_b, cin, cout, gw);   // drops the padding
+  LGS_KLAUNCH(k_wgrad_reduce, (unsigned)p.reduce_blocks, 256, 0, s, partial, p.slots, v.K, p.pad_a, p.pad_b, cin, cout, gw, mirror);   // drops the padding
   LGS_HIP(hipGetLastError());
   return 0;
 }
@@ -1582,14 +1587,14 @@ int lgs_clip_loss_backward_anchors(const void *feat, int64_t n, int c, int n_anc
 }
 
 int lgs_conv_wgrad_supports_stride(const lgs_kmap *km, int transposed, int cin, int cout, int dtype, int in_row_stride) {
-  if (!km || (transposed && km->ks == 3) || !(dtype == LGS_F32 || dtype == LGS_BF16)) return 0;
+  if (!km || (transposed && !transposed_ok(km)) || !(dtype == LGS_F32 || dtype == LGS_BF16)) return 0;
   return wgrad_plan(*km, transposed, cin, cout, dtype, in_row_stride).in_place;
 }
 
 int lgs_conv_wgrad(lgs_kmap *km, int transposed, const void *in, int cin, const void *grad_out, int cout,
                    float *grad_weight, int dtype, void *workspace, int in_row_stride, void *stream) {
   LGS_REQUIRE(km && grad_weight && workspace, "lgs_conv_wgrad: null argument");
-  LGS_REQUIRE(!(transposed && km->ks == 3), "transposed 3x3x3 convolution is not part of the model family");
+  LGS_REQUIRE(!transposed || transposed_ok(km), "transposed 3x3x3 convolution is not part of the model family");
   LGS_REQUIRE(dtype == LGS_F32 || dtype == LGS_BF16, "lgs_conv_wgrad: unknown dtype");
   hipStream_t s = (hipStream_t)stream;
   if (kmap_wait(km, s)) return 1;
@@ -1602,19 +1607,20 @@ int lgs_conv_wgrad(lgs_kmap *km, int transposed, const void *in, int cin, const 
   LGS_REQUIRE(dtype == LGS_BF16 || !strided, "lgs_conv_wgrad: strided input needs bf16");
   LGS_REQUIRE(!strided || p.in_place, "lgs_conv_wgrad: a strided input is only supported by the position-stationary bf16 kernel");
   View v = p.bwd_view ? km->bwd : km->fwd;
+  const int mirror = v.mirror;     // the kernels sum per slot; k_wgrad_reduce puts slot K-1-k of a mirrored view at offset k
   v.mirror = 0;
   const int in_ld = in_row_stride > 0 ? in_row_stride : cin;
   switch (p.path) {
     case kWgWide: return launch_wgrad_wide(v, p, in, cin, in_ld, grad_out, cout, grad_weight, workspace, s);
     case kWgPs: return conv_wgrad_ps(v, p, transposed, in, cin, grad_out, cout, in_ld, grad_weight, workspace, s);
-    case kWgPairs: return conv_wgrad_pairs(v, p, in, cin, grad_out, cout, grad_weight, workspace, s);
-    default: return conv_wgrad_f32(v, p, in, cin, grad_out, cout, grad_weight, workspace, s);
+    case kWgPairs: return conv_wgrad_pairs(v, p, in, cin, grad_out, cout, grad_weight, workspace, s, mirror);
+    default: return conv_wgrad_f32(v, p, in, cin, grad_out, cout, grad_weight, workspace, s, mirror);
   }
 }
 
 // the plan of lgs_conv_wgrad on a synthetic map + what the public queries say for it: no HIP call, `present` tables are never read
 int lgs_debug_wgrad_plan(const lgs_wgrad_plan_query *q, lgs_wgrad_plan_info *out) {
-  LGS_REQUIRE(q && out && (q->dtype == LGS_F32 || q->dtype == LGS_BF16) && !(q->transposed && q->ks == 3), "lgs_debug_wgrad_plan: bad argument");
+  LGS_REQUIRE(q && out && (q->dtype == LGS_F32 || q->dtype == LGS_BF16), "lgs_debug_wgrad_plan: bad argument");
   static const int32_t present = 0;
   auto view = [&](const lgs_conv_plan_view &s) {
     View v;
@@ -1627,6 +1633,8 @@ int lgs_debug_wgrad_plan(const lgs_wgrad_plan_query *q, lgs_wgrad_plan_info *out
   };
   lgs_kmap km;
   km.ks = q->ks; km.K = q->fwd.K; km.fwd = view(q->fwd); km.bwd = view(q->bwd);
+  synthetic_kmap_facts(km);
+  LGS_REQUIRE(!q->transposed || transposed_ok(&km), "lgs_debug_wgrad_plan: bad argument");
   *out = wgrad_plan(km, q->transposed, q->cin, q->cout, q->dtype, q->in_row_stride);
   out->workspace_bytes = lgs_conv_workspace_bytes(&km, q->cin, q->cout, q->dtype, 2);
   out->supports_stride = lgs_conv_wgrad_supports_stride(&km, q->transposed, q->cin, q->cout, q->dtype, q->in_row_stride);

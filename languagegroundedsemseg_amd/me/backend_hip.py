@@ -491,13 +491,15 @@ class HipManager:
             self._kmaps[k] = sm
         return sm
 
-    def kernel_map(self, in_key, out_key, ks):
-        k = (in_key, out_key, ks)
+    has_kernel_map_ex = True     # strided 3^3 / 1x1 and dilated 3^3 maps (lgs_manager_kernel_map_ex)
+
+    def kernel_map(self, in_key, out_key, ks, dilation=1):
+        k = (in_key, out_key, ks) if dilation == 1 else (in_key, out_key, ks, dilation)
         km = self._kmaps.get(k)
         if km is None:
             h = _vp(None)     # the engine caches the map itself: a second request returns the same handle at no cost
             with _dev(self.device):
-                engine.check(engine.lib().lgs_manager_kernel_map(self.h, in_key, out_key, ks, _stream(), ctypes.byref(h)))
+                engine.check(engine.lib().lgs_manager_kernel_map_ex(self.h, in_key, out_key, ks, dilation, _stream(), ctypes.byref(h)))
             km = HipKernelMap(self, h, in_key, out_key, ks)
             self._kmaps[k] = km
         return km

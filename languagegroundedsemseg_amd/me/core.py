@@ -142,12 +142,20 @@ class CoordinateManager:
     def get_coordinates(self, key):
         return self._m.coords(key.id)
 
-    def kernel_map_handle(self, in_key, out_key, kernel_size):
+    def kernel_map_handle(self, in_key, out_key, kernel_size, dilation=1):
+        """the backend's kernel map between two maps of this manager.  Dilated 3^3 maps and the 1x1 map onto a stride-2 map
+        exist on the HIP engine only (lgs_manager_kernel_map_ex); a 3^3 map onto a stride-2 map also on backends whose
+        kernel_map is generic in its keys."""
+        if getattr(self._m, "has_kernel_map_ex", False):
+            return self._m.kernel_map(in_key.id, out_key.id, kernel_size, dilation)
+        if dilation != 1 or (kernel_size == 1 and in_key.id != out_key.id):
+            raise NotImplementedError("%s needs the HIP engine: backend %r builds no such kernel map (there is no fallback)" % (
+                "a dilated convolution" if dilation != 1 else "a 1x1 stride-2 convolution", self.backend.name))
         return self._m.kernel_map(in_key.id, out_key.id, kernel_size)
 
-    def kernel_map(self, in_key, out_key, stride=1, kernel_size=3, **kwargs):
+    def kernel_map(self, in_key, out_key, stride=1, kernel_size=3, dilation=1, **kwargs):
         """-> {k: int tensor [2, M_k]} (in_row; out_row), the ME `kernel_map` query."""
-        h = self._m.kernel_map(in_key.id, out_key.id, kernel_size)
+        h = self.kernel_map_handle(in_key, out_key, kernel_size, dilation)
         k, i, o = h.export()
         out = {}
         for kk in torch.unique(k).tolist():

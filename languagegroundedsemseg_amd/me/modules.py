@@ -202,13 +202,13 @@ class MinkowskiConvolutionBase(MinkowskiModuleBase):
         self.dilation = kernel_generator.kernel_dilation
         if kernel_generator.region_type != RegionType.HYPER_CUBE:
             raise NotImplementedError("only HYPER_CUBE regions are part of the D=3 model family")
-        if any(d != 1 for d in self.dilation):
-            raise NotImplementedError("dilation != 1 is not used by the model family")
-        if len(set(self.kernel_size)) != 1 or len(set(self.stride)) != 1:
-            raise NotImplementedError("anisotropic kernels/strides are not used on D=3")
-        ks, st = self.kernel_size[0], self.stride[0]
-        if not ((ks == 3 and st == 1) or (ks == 2 and st == 2) or (ks == 1 and st == 1)):
-            raise NotImplementedError("kernel_size/stride combination (%d,%d) is not part of the model family" % (ks, st))
+        if len(set(self.kernel_size)) != 1 or len(set(self.stride)) != 1 or len(set(self.dilation)) != 1:
+            raise NotImplementedError("anisotropic kernels / strides / dilations are not supported on D=3")
+        ks, st, dil = self.kernel_size[0], self.stride[0], self.dilation[0]
+        if not ((ks, st) in ((3, 1), (2, 2), (1, 1), (3, 2), (1, 2)) and dil >= 1 and (dil == 1 or (ks, st) == (3, 1))):
+            raise NotImplementedError(
+                "(kernel_size, stride, dilation) = (%d, %d, %d) is not supported: the supported set is (3, 1, d >= 1), (3, 2, 1), "
+                "(2, 2, 1), (1, 1, 1) and (1, 2, 1)" % (ks, st, dil))
         self.kernel_volume = kernel_generator.kernel_volume
         if self.kernel_volume == 1 and st == 1:
             self.use_mm = True
@@ -252,14 +252,14 @@ class MinkowskiConvolutionBase(MinkowskiModuleBase):
     def _resolve(self, input):
         """-> (output coordinate map key, kernel map, transposed)"""
         mgr = input.coordinate_manager
-        ks, st = self.kernel_size[0], self.stride[0]
+        ks, st, dil = self.kernel_size[0], self.stride[0], self.dilation[0]
         in_key = input.coordinate_map_key
         if not self.is_transpose:
             out_key = in_key if st == 1 else mgr.stride(in_key, st)
-            return out_key, mgr.kernel_map_handle(in_key, out_key, ks), False
+            return out_key, mgr.kernel_map_handle(in_key, out_key, ks, dil), False
         out_key = in_key if st == 1 else mgr.finer_key(in_key)
         # the transposed conv reuses the forward map of the matching strided conv, in/out swapped
-        return out_key, mgr.kernel_map_handle(out_key, in_key, ks), True
+        return out_key, mgr.kernel_map_handle(out_key, in_key, ks, dil), True
 
     def _forward_now(self, input, bn=None, resolved=None, out=None):
         """run the convolution.  `bn`: in training the conv epilogue may also produce that norm's batch statistics (pivoted on its

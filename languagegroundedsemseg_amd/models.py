@@ -23,8 +23,8 @@ import torch.nn as nn
 from . import me as ME
 
 
-def _conv(cin, cout, ks, stride=1, bias=False, D=3):
-    return ME.MinkowskiConvolution(cin, cout, kernel_size=ks, stride=stride, dilation=1, bias=bias, dimension=D)
+def _conv(cin, cout, ks, stride=1, bias=False, D=3, dilation=1):
+    return ME.MinkowskiConvolution(cin, cout, kernel_size=ks, stride=stride, dilation=dilation, bias=bias, dimension=D)
 
 
 def _conv_tr(cin, cout, ks, stride, D=3):
@@ -36,11 +36,12 @@ class BasicBlock(nn.Module):
     reference's NoReluBlock (resnet_block.py:133-161) used by the representation models."""
     expansion = 1
 
-    def __init__(self, inplanes, planes, downsample=None, bn_momentum=0.1, D=3, final_relu=True):
+    def __init__(self, inplanes, planes, downsample=None, bn_momentum=0.1, D=3, final_relu=True, stride=1, dilation=1):
         super().__init__()
-        self.conv1 = _conv(inplanes, planes, 3, D=D)
+        # resnet_block.py:27-31: the stride belongs to conv1 alone, the dilation to both 3^3 convs
+        self.conv1 = _conv(inplanes, planes, 3, stride=stride, D=D, dilation=dilation)
         self.norm1 = ME.MinkowskiBatchNorm(planes, momentum=bn_momentum)
-        self.conv2 = _conv(planes, planes, 3, D=D)
+        self.conv2 = _conv(planes, planes, 3, D=D, dilation=dilation)
         self.norm2 = ME.MinkowskiBatchNorm(planes, momentum=bn_momentum)
         self.relu = ME.MinkowskiReLU(inplace=True)
         self.downsample = downsample
@@ -302,7 +303,66 @@ class InsSegRes16UNet34C(_InsSegHead, Res16UNet34C):
         self._add_head(D)
 
 
-MODELS = {c.__name__: c for c in [InsSegRes16UNet14A, InsSegRes16UNet34C,
+class ResNetBase(ME.MinkowskiNetwork):
+    """The ResNet encoders (resnet.py:10-139): conv1 - bn1 - relu - 2^3 sum pooling - four layers, each opening with a block whose
+    conv1 is a 3^3 stride-2 conv and whose residual branch is a 1x1 stride-2 conv + norm - 1x1 classifier `final`.
+    config.dilations (default (1, 1, 1, 1)) is the dilation of every 3^3 conv of the layer's blocks.  The momentum quirk of the
+    reference holds here too: bn1 takes config.bn_momentum, block and downsample norms keep 0.1 (resnet.py:84-123)."""
+    LAYERS = ()
+    INIT_DIM = 64
+    PLANES = (64, 128, 256, 512)
+
+    def __init__(self, in_channels, out_channels, config=None, D=3, **kwargs):
+        super().__init__(D)
+        self.in_channels, self.out_channels, self.config = in_channels, out_channels, config
+        bn_m = getattr(config, "bn_momentum", 0.02) if config is not None else 0.02
+        k0 = getattr(config, "conv1_kernel_size", 3) if config is not None else 3
+        dilations = tuple(getattr(config, "dilations", (1, 1, 1, 1))) if config is not None else (1, 1, 1, 1)
+        self.inplanes = self.INIT_DIM
+        self.conv1 = _conv(in_channels, self.inplanes, k0, D=D)
+        self.bn1 = ME.MinkowskiBatchNorm(self.inplanes, momentum=bn_m)
+        self.relu = ME.MinkowskiReLU(inplace=True)
+        self.pool = ME.MinkowskiSumPooling(kernel_size=2, stride=2, dimension=D)
+        for i in range(4):
+            setattr(self, "layer%d" % (i + 1), self._make_layer(self.PLANES[i], self.LAYERS[i], stride=2, dilation=dilations[i]))
+        self.final = _conv(self.PLANES[3] * BasicBlock.expansion, out_channels, 1, bias=True, D=D)
+
+    def _make_layer(self, planes, blocks, stride=1, dilation=1, bn_momentum=0.1):
+        downsample = None
+        if stride != 1 or self.inplanes != planes * BasicBlock.expansion:
+            downsample = nn.Sequential(_conv(self.inplanes, planes * BasicBlock.expansion, 1, stride=stride, D=self.D),
+                                       ME.MinkowskiBatchNorm(planes * BasicBlock.expansion, momentum=bn_momentum))
+        layers = [BasicBlock(self.inplanes, planes, downsample=downsample, D=self.D, stride=stride, dilation=dilation)]
+        self.inplanes = planes * BasicBlock.expansion
+        for _ in range(1, blocks):
+            layers.append(BasicBlock(self.inplanes, planes, D=self.D, dilation=dilation))
+        return nn.Sequential(*layers)
+
+    def forward(self, x):
+        x = self.conv1(x)
+        x = self.bn1(x)
+        x = self.relu(x)
+        x = self.pool(x)
+        x = self.layer1(x)
+        x = self.layer2(x)
+        x = self.layer3(x)
+        x = self.layer4(x)
+        return self.final(x)
+
+
+class ResNet14(ResNetBase):
+    LAYERS = (1, 1, 1, 1)
+
+
+class ResNet18(ResNetBase):
+    LAYERS = (2, 2, 2, 2)
+
+
+class ResNet34(ResNetBase):
+    LAYERS = (3, 4, 6, 3)
+
+
+MODELS = {c.__name__: c for c in [InsSegRes16UNet14A, InsSegRes16UNet34C, ResNet14, ResNet18, ResNet34,
                                   Res16UNet14, Res16UNet18, Res16UNet34, Res16UNet14A, Res16UNet18A, Res16UNet34A,
                                   Res16UNet34B, Res16UNet34C, Res16UNet34CR, Res16UNet34CR_Proj, Res16UNet34D]}
 

@@ -1,5 +1,5 @@
 """Per-op timings on the GPU (HIP events on torch's current stream) for the hot layer shapes.
-usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm]"""
+usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided]"""
 import os
 import sys
 import time
@@ -392,7 +392,58 @@ def instnorm():
         del f, dy, st, fd
 
 
+def strided():
+    """the kernel maps of lgs_manager_kernel_map_ex on the 8-scene batch, levels 0 and 1 (bf16): the three builders, and forward /
+    dgrad / wgrad of 64 -> 128 and 256 -> 512 on the 3^3 stride-2 map and a dilation-2 map, each beside the stride-1 3^3 conv of the
+    same level and channels from the same run.  Rates are REAL pairs per second (pairs = exported triples of the map)."""
+    coords, _, _ = make_batch(list(range(8)), n_target=150000, shift_seed=0)
+    c = torch.from_numpy(coords).to(DEV)
+    n0 = coords.shape[0]
+
+    def fresh(level):
+        x = ME.SparseTensor(torch.zeros(n0, 1, device=DEV), c)
+        m, k = x.coordinate_manager, x.coordinate_map_key
+        for _ in range(level):
+            k = m.stride(k, 2)
+        return x, m, k, m.stride(k, 2)
+
+    for level in (0, 1):
+        # builders: a fresh manager per call (the maps are cached per manager), its cost measured alone and subtracted
+        base = timeit(lambda: fresh(level), 5, 2)
+        for name, ks, to_coarse, d in (("3^3 stride 1", 3, False, 1), ("3^3 dilation 2", 3, False, 2), ("3^3 stride 2 (both views)", 3, True, 1),
+                                       ("1x1 stride 2 (both views)", 1, True, 1)):
+            def build():
+                x, m, k, kc = fresh(level)
+                m.kernel_map_handle(k, kc if to_coarse else k, ks, d)
+            t = timeit(build, 5, 2)
+            print("L%d builder %-26s %.3f ms (insert + strides alone: %.3f ms)" % (level, name, t - base, base))
+        x, m, k, kc = fresh(level)
+        nf, nc = m.size(k), m.size(kc)
+        kms = {"stride 1": (m.kernel_map_handle(k, k, 3), nf, nf), "dilation 2": (m.kernel_map_handle(k, k, 3, 2), nf, nf),
+               "stride 2": (m.kernel_map_handle(k, kc, 3), nf, nc)}
+        for cin, cout in ((64, 128), (256, 512)):
+            w = torch.randn(27, cin, cout, device=DEV) * 0.02
+            ref = None
+            for name, (km, n_in, n_out) in kms.items():
+                M = km.export()[0].shape[0]
+                f = torch.randn(n_in, cin, device=DEV).bfloat16()
+                g = torch.randn(n_out, cout, device=DEV).bfloat16()
+                tf = timeit(lambda: km.conv_forward(f, w, None, False), 5, 2)
+                td = timeit(lambda: km.conv_dgrad(g, w, False), 5, 2)
+                tw = timeit(lambda: km.conv_wgrad(f, g, False), 5, 2)
+                rate = [M / t / 1e6 for t in (tf, td, tw)]                  # G pairs / s
+                if ref is None:
+                    ref = rate
+                print("L%d %-10s %3d->%3d rows %7d -> %7d pairs %8d  fwd %.3f ms  dgrad %.3f ms  wgrad %.3f ms  | G pairs/s %.2f %.2f %.2f  "
+                      "(x stride 1: %.2f %.2f %.2f)" % (level, name, cin, cout, n_in, n_out, M, tf, td, tw, rate[0], rate[1], rate[2],
+                                                        rate[0] / ref[0], rate[1] / ref[1], rate[2] / ref[2]))
+                del f, g
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "strided":
+        strided()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "pool":
         pool()
         sys.exit(0)
