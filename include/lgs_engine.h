@@ -131,6 +131,32 @@ int lgs_manager_kernel_map(lgs_manager *mgr, int in_key, int out_key, int kernel
 int lgs_manager_kernel_map_ex(lgs_manager *mgr, int in_key, int out_key, int kernel_size, int dilation, void *stream,
                               lgs_kmap **out);
 
+/* lgs_debug_kmap_relation: what the two entry points above decide for a request, given by plain facts instead of a live manager, and
+ * what follows from the answer for every consumer of the map.  It is the classifier and the table the entry points, the plans and
+ * the conv entry points themselves read (csrc/lgs_common.h: classify_kmap, traits_of), so it runs without a GPU
+ * (tests/test_kmap_relation_cpu.py holds it to the contract above).  A new symbol only: LGS_ABI_VERSION stays 18.
+ * Returns what the entry point would return for the request: 0, or 2 with the refusal in lgs_last_error(). */
+typedef struct lgs_kmap_relation_query {
+  int entry;                  /* 0 lgs_manager_kernel_map (no dilation argument: the field is ignored), 1 lgs_manager_kernel_map_ex */
+  int ks, dilation;
+  int link;                   /* 0 in_key == out_key, 1 out_key == stride2(in_key), 2 in_key == stride2(out_key), 3 unrelated keys */
+  int tensor_stride;          /* of the in map */
+  int out_sorted;             /* the out map's rows are in Morton order (every map made by lgs_manager_stride2) */
+  int in_origin, out_origin;  /* the map is lgs_manager_origin's */
+} lgs_kmap_relation_query;
+typedef struct lgs_kmap_relation_info {
+  int rc;                     /* the return value, again */
+  int relation;               /* 0 identity 1x1, 1 3^3 stride 1, 2 2^3 stride 2, 3 3^3 dilated stride 1, 4 3^3 stride 2, 5 1x1 stride 2;
+                                 -1 refused (the fields below are then 0) */
+  int K;                      /* weight matrices */
+  int strided;                /* the out map is the in map's stride-2 map */
+  int bwd_mirror;             /* the dgrad side is the forward table read mirrored (weight index K-1-s) */
+  int transposed_ok;          /* the conv entry points take `transposed` = 1 on the map */
+  int pairs_only[2];          /* [transposed]: the weight gradient goes to the pair-list / fp32 kernels only */
+  int served_by_old_entry;    /* lgs_manager_kernel_map builds it too (the same object) */
+} lgs_kmap_relation_info;
+int lgs_debug_kmap_relation(const lgs_kmap_relation_query *q, lgs_kmap_relation_info *out);
+
 /* Export the map as (k, in_row, out_row) triples for set-equality parity tests.
  * Pass NULL buffers to query *m only (synchronises). Buffers are device int32[*m]. */
 int lgs_kmap_export(lgs_kmap *km, int32_t *k, int32_t *in_row, int32_t *out_row, void *stream, int64_t *m);

@@ -143,23 +143,96 @@ int segmap_wait(lgs_segmap *sm, hipStream_t stream);
 
 }  // namespace lgs
 
+namespace lgs {
+// ---- kernel-map relations.  What a request (in_key, out_key, kernel_size, dilation) names is decided ONCE, by classify_kmap; what
+// follows from the answer is read from ONE table, traits_of.  Both map entry points, the plans, the conv entry points and the debug
+// queries go through them (rows as in the contract of include/lgs_engine.h; tests/test_kmap_relation_cpu.py holds them to it).
+enum KmapRelation {
+  kRelIdentity = 0,      // kernel_size 1, in_key == out_key
+  kRelConv3 = 1,         // kernel_size 3, in_key == out_key, dilation 1
+  kRelConv2S2 = 2,       // kernel_size 2, out_key == stride2(in_key); the transposed conv walks the same object
+  kRelConv3Dilated = 3,  // kernel_size 3, in_key == out_key, dilation >= 2
+  kRelConv3S2 = 4,       // kernel_size 3, out_key == stride2(in_key)
+  kRelConv1S2 = 5,       // kernel_size 1, out_key == stride2(in_key)
+};
+struct KmapTraits {
+  int ks, K;
+  bool strided;        // the out map is the in map's stride-2 map: the two views walk different row spaces
+  bool bwd_mirror;     // bwd is the fwd table read from its other side (weight index K-1-s); else both views carry offset k in slot k
+  bool transposed_ok;  // the conv entry points take `transposed` = 1 on it (the plain 3^3 stride-1 map refuses it as it always has)
+  bool old_entry;      // lgs_manager_kernel_map builds it; the others are lgs_manager_kernel_map_ex's alone
+  // k_wgrad_wide and k_wgrad_ps have been run and measured on the 3^3 stride-1 table and the 2^3 views only: a 3^3 map with two
+  // different row spaces, and any 3^3 map walked by a transposed conv, goes to the pair-list / fp32 kernels, which take any view
+  constexpr bool wgrad_pairs_only(bool transposed) const { return ks == 3 && (strided || transposed); }
+};
+constexpr KmapTraits traits_of(KmapRelation r) {
+  switch (r) {           //                 ks   K  strided mirror transp  old
+    case kRelConv3:        return KmapTraits{3, 27, false, true, false, true};
+    case kRelConv2S2:      return KmapTraits{2, 8, true, false, true, true};
+    case kRelConv3Dilated: return KmapTraits{3, 27, false, true, true, false};
+    case kRelConv3S2:      return KmapTraits{3, 27, true, false, true, false};
+    case kRelConv1S2:      return KmapTraits{1, 1, true, false, true, false};
+    default:               return KmapTraits{1, 1, false, false, true, true};   // kRelIdentity
+  }
+}
+constexpr int kCoordBits = 18;   // bits per coordinate in a packed key: every probed coordinate stays within 2^17 of a stored one
+struct KmapRequest {
+  bool ex;               // lgs_manager_kernel_map_ex asked (else lgs_manager_kernel_map, which has no dilation: taken as 1)
+  bool same_key;         // in_key == out_key
+  bool out_is_stride2;   // the out map was made by stride2(in_key)
+  bool out_sorted;       // the out map's rows are in Morton order (order == nullptr)
+  bool origin;           // either map is the origin map
+  int ks, dilation, ts_in;
+};
+// -> nullptr and the relation, or the refusal (no HIP call; the checks in the order a caller of the entry point has always met them)
+inline const char *classify_kmap(const KmapRequest &q, KmapRelation &rel) {
+  if (q.origin) return q.ex ? "lgs_manager_kernel_map_ex: no kernel maps on the origin map" : "lgs_manager_kernel_map: no kernel maps on the origin map";
+  const int d = q.ex ? q.dilation : 1;
+  const bool strided = !q.same_key && q.out_is_stride2;
+  if (d < 1) return "lgs_manager_kernel_map_ex: dilation must be >= 1";
+  if (strided && d > 1) return "lgs_manager_kernel_map_ex: stride 2 combined with dilation > 1 is not supported";
+  if (d > 1 && q.ks != 3) return "lgs_manager_kernel_map_ex: dilation > 1 needs kernel_size 3";
+  if (d > 1) {
+    if (!q.same_key) return "lgs_manager_kernel_map_ex: out_key must be in_key or stride2(in_key)";
+    rel = kRelConv3Dilated;
+  } else if (q.ks == 1 || q.ks == 3) {
+    const char *refusal = q.ks == 1 ? "kernel_size 1 needs in_key == out_key" : "kernel_size 3 is supported for stride 1 (in_key == out_key) only";
+    if (!q.same_key && !strided) return refusal;
+    rel = q.ks == 1 ? (strided ? kRelConv1S2 : kRelIdentity) : (strided ? kRelConv3S2 : kRelConv3);
+    if (!q.ex && !traits_of(rel).old_entry) return refusal;   // the old entry point refuses them as it always has
+  } else if (q.ks == 2) {
+    if (!strided) return "kernel_size 2 needs out_key == stride2(in_key)";
+    rel = kRelConv2S2;
+  } else {
+    return "unsupported kernel_size (the model family uses 1, 2 and 3 only)";
+  }
+  if (!traits_of(rel).old_entry) {
+    // the coarse-stationary views take "position == output row": a map made by stride2 has its rows in Morton order
+    if (strided && !q.out_sorted) return "lgs_manager_kernel_map_ex: the stride-2 map's rows are not in sorted order";
+    if ((int64_t)d * q.ts_in >= (1ll << (kCoordBits - 1))) return "lgs_manager_kernel_map_ex: dilation * tensor_stride must stay below 2^17";
+  }
+  return nullptr;
+}
+}  // namespace lgs
+
 struct lgs_kmap {
   lgs_manager *mgr = nullptr;
-  int in_key = -1, out_key = -1, ks = 0, K = 1;
-  int dilation = 1;   // offset scale of a 3^3 stride-1 map in units of the tensor stride (part of the cache key)
-  int strided = 0;    // 1: a 3^3 or 1x1 map between a map and its stride-2 map (lgs_manager_kernel_map_ex); both views carry offset k in slot k
+  int in_key = -1, out_key = -1, ks = 1, K = 1;
+  lgs::KmapRelation relation = lgs::kRelIdentity;   // with in_key, out_key and dilation: the cache key
+  int dilation = 1;   // offset scale of a 3^3 stride-1 map in units of the tensor stride
   lgs::View fwd;  // gathers from the in map, writes the out map
   lgs::View bwd;  // gathers from the out map, writes the in map (dgrad / transposed conv)
 };
 
 namespace lgs {
-// `transposed` = 1 on a 3^3 map: the maps of lgs_manager_kernel_map_ex take it, the plain stride-1 map refuses it as it always has
-inline bool transposed_ok(const lgs_kmap *km) { return km->ks != 3 || km->strided || km->dilation > 1; }
-// the facts of a map that the synthetic views of the debug plan queries do not carry, derived from their row counts: a 3^3 / 1x1 map
-// whose two sides differ in rows is a strided one; the bwd side of a 3^3 stride-1 map is the shared table read mirrored
-inline void synthetic_kmap_facts(lgs_kmap &km) {
-  km.strided = (km.ks == 3 || km.ks == 1) && km.fwd.n_in != km.fwd.n_out ? 1 : 0;
-  km.bwd.mirror = (km.ks == 3 && !km.strided) ? 1 : 0;
+inline KmapTraits traits_of(const lgs_kmap *km) { return traits_of(km->relation); }
+// the relation of the synthetic map of a debug plan query, which carries the kernel size and two views by their row counts: two sides
+// that differ in rows are a map and its stride-2 map (kernel size 2 names no other link); a dilated map plans as the plain 3^3 one
+inline const char *synthetic_kmap_relation(lgs_kmap &km) {
+  const bool same = km.ks != 2 && km.fwd.n_in == km.fwd.n_out;
+  const char *refusal = classify_kmap(KmapRequest{true, same, !same, true, false, km.ks, 1, 1}, km.relation);
+  if (!refusal) km.bwd.mirror = traits_of(km.relation).bwd_mirror ? 1 : 0;
+  return refusal;
 }
 }  // namespace lgs
 

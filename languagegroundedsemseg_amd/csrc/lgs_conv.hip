@@ -1227,7 +1227,7 @@ inline ConvPlan plan_of(const View &v, int K, int g_real, int o_real, int dtype,
 // one forward / dgrad call: op 1 gathers grad_out [*, cout] and reads the weights transposed (3^3: mirrored)
 inline int conv_call(lgs_kmap *km, int op, int transposed, const void *in, int cin, const float *weight, int cout, const float *bias,
                      void *out, int dtype, void *workspace, const BnEpi *bn, void *packed, int pack_mode, int in_ld, void *stream) {
-  LGS_REQUIRE(!transposed || transposed_ok(km), "transposed 3x3x3 convolution is not part of the model family");
+  LGS_REQUIRE(!transposed || traits_of(km).transposed_ok, "transposed 3x3x3 convolution is not part of the model family");
   LGS_REQUIRE(known_dtype(dtype), "sparse conv: unknown dtype");
   const View v = op_view(km, op, transposed);   // (with its own mirror flag: set on the bwd side of a shared 3^3 stride-1 table only)
   hipStream_t s = (hipStream_t)stream;
@@ -1311,7 +1311,7 @@ int lgs_conv_dgrad(lgs_kmap *km, int transposed, const void *grad_out, int cout,
 // 1 if lgs_conv_dgrad_accumulate adds inside the kernel epilogue for this launch shape (everything but the 2-D blocked wide
 // kernel and input widths off the 4-channel grid)
 int lgs_conv_dgrad_can_accumulate(const lgs_kmap *km, int transposed, int cin, int cout, int dtype) {
-  if (!km || (transposed && !transposed_ok(km)) || !known_dtype(dtype)) return 0;
+  if (!km || (transposed && !traits_of(km).transposed_ok) || !known_dtype(dtype)) return 0;
   return plan_of(op_view(km, 1, transposed), km->K, cout, cin, dtype, kEpiAccum).can_accumulate;
 }
 
@@ -1340,7 +1340,7 @@ int lgs_debug_conv_plan(const lgs_conv_plan_query *q, lgs_conv_plan_info *out) {
   };
   lgs_kmap km;
   km.ks = q->ks; km.K = q->fwd.K; km.fwd = view(q->fwd); km.bwd = view(q->bwd);
-  synthetic_kmap_facts(km);
+  LGS_REQUIRE(synthetic_kmap_relation(km) == nullptr, "lgs_debug_conv_plan: bad argument");
   *out = plan_of(op_view(&km, q->op, q->transposed), km.K, q->op == 0 ? q->cin : q->cout, q->op == 0 ? q->cout : q->cin, q->dtype, (ConvEpi)q->epilogue);
   out->workspace_bytes = lgs_conv_workspace_bytes(&km, q->cin, q->cout, q->dtype, q->op);
   out->q_bn_partial_rows = q->op == 0 ? lgs_conv_bn_partial_rows(&km, q->transposed, q->cout, q->dtype) : 0;

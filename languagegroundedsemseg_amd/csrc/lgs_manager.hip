@@ -26,7 +26,6 @@ namespace lgs {
 static thread_local std::string g_err;
 void set_error(const std::string &msg) { g_err = msg; }
 
-constexpr int kCoordBits = 18;
 constexpr int kBias = 1 << (kCoordBits - 1);  // 131072
 constexpr uint64_t kEmpty = ~0ull;
 
@@ -777,21 +776,30 @@ int scan_incl(lgs_manager *m, const int32_t *in, int32_t *out, int64_t n, hipStr
   return 0;
 }
 
+// radix sort of (key, value) pairs on key bits [begin_bit, end_bit); rocPRIM's temporary is taken from and returned to the arena's top
+template <typename K, typename V>
+int sort_pairs(lgs_manager *m, K *keys, K *keys_out, V *vals, V *vals_out, int64_t n, unsigned begin_bit, unsigned end_bit, hipStream_t s) {
+  size_t tb = 0;
+  LGS_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys, keys_out, vals, vals_out, (size_t)n, begin_bit, end_bit, s));
+  void *tmp = nullptr;
+  if (raw_alloc(m, &tmp, tb ? tb : 16, s)) return 1;
+  LGS_HIP(rocprim::radix_sort_pairs(tmp, tb, keys, keys_out, vals, vals_out, (size_t)n, begin_bit, end_bit, s));
+  return dfree_now(m, tmp, s);
+}
+
+// head[p] = 1 where sorted key p starts a new batch index; cincl = its inclusive scan (the origin map's row of every position, + 1)
+int batch_heads(lgs_manager *m, const uint64_t *skeys, int64_t n, int32_t *head, int32_t *cincl, hipStream_t s) {
+  LGS_KLAUNCH(k_heads, nblk(n), 256, 0, s, skeys, n, ~((1ull << kBatchShift) - 1), head);
+  return scan_incl(m, head, cincl, n, s);
+}
+
 // the window mask sort of a 27-slot table built in sorted-position order (nbr_tmp, pmask) and its permutation into the view's arrays:
 // position q of the view is sorted position perm[q] and writes row order[perm[q]] (order == nullptr: the position itself)
 int sort_map3(lgs_manager *m, int64_t n, int64_t n_pad, const int32_t *nbr_tmp, const uint32_t *pmask, const int32_t *order, uint64_t *keys,
               uint64_t *skeys2, int32_t *vals, int32_t *perm, int32_t *nbr, int32_t *orow, uint32_t *mask, hipStream_t s) {
   const int window = (int)tune(T_MASK_WINDOW);   // tuning knob (default kMaskWindow)
   LGS_KLAUNCH(k_mask_sort_keys, (unsigned)(n_pad / 256), 256, 0, s, pmask, n, n_pad, window, (int)tune(T_MASK_ORDER), keys, vals);
-  {
-    size_t tb = 0;
-    const unsigned eb = mask_sort_bits(n_pad, window);
-    LGS_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys, skeys2, vals, perm, (size_t)n_pad, 0, eb, s));
-    void *tmp = nullptr;
-    if (raw_alloc(m, &tmp, tb ? tb : 16, s)) return 1;
-    LGS_HIP(rocprim::radix_sort_pairs(tmp, tb, keys, skeys2, vals, perm, (size_t)n_pad, 0, eb, s));
-    if (dfree_now(m, tmp, s)) return 1;
-  }
+  if (sort_pairs(m, keys, skeys2, vals, perm, n_pad, 0, mask_sort_bits(n_pad, window), s)) return 1;
   LGS_KLAUNCH(k_permute_map3, (unsigned)(n_pad / 256), 256, 0, s, nbr_tmp, pmask, perm, order, n, n_pad, nbr, orow, mask);
   LGS_HIP(hipGetLastError());
   return 0;
@@ -817,6 +825,134 @@ int make_view27(lgs_manager *m, const CoordMap &st, int64_t n_in, hipStream_t s,
   return 0;
 }
 
+
+// ---- kernel maps: one builder per relation (KmapRelation, lgs_common.h), all on the map stream
+// identity 1x1: no table
+void build_identity(const CoordMap &ci, lgs_kmap *km) {
+  View v; v.n_pad = ci.n_pad; v.n_out = ci.n; v.n_in = ci.n; v.KS = 1; v.K = 1;
+  km->fwd = v; km->bwd = v;
+}
+
+// a 27-slot view over the rows of `st` whose slot k holds the row of `probed` at c + off_k * scale: the 27 probes of k_build_map3
+// from st's sorted keys into probed's hash (st == probed: the stride-1 maps; st = the coarse map: the coarse-stationary strided view)
+int probe_view27(lgs_manager *m, const CoordMap &st, const CoordMap &probed, int scale, hipStream_t s, View &v) {
+  return make_view27(m, st, probed.n, s, v, [&](int32_t *nbr_tmp, uint32_t *pmask) {
+    LGS_KLAUNCH(k_build_map3, (unsigned)(st.n_pad / 256), 256, 0, s, st.skeys, st.n, st.n_pad, scale, probed.hkeys, probed.hvals,
+                (uint64_t)(probed.hcap - 1), nbr_tmp, pmask);
+    return 0;
+  });
+}
+
+// 3^3 stride 1, plain (dilation 1) or dilated: offsets scaled by dilation * ts; bwd = the same table read mirrored
+int build_conv3(lgs_manager *m, CoordMap &ci, int dilation, hipStream_t s, lgs_kmap *km) {
+  if (ci.n > 0 && ensure_hash(m, ci, s)) return 1;
+  View v;
+  if (probe_view27(m, ci, ci, dilation * ci.ts, s, v)) return 1;
+  km->fwd = v;
+  km->bwd = v; km->bwd.mirror = 1;
+  return 0;
+}
+
+// 2^3 stride 2: the children of a coarse row are one run of the fine Morton order
+int build_conv2_s2(lgs_manager *m, const CoordMap &ci, const CoordMap &co, hipStream_t s, lgs_kmap *km) {
+  int shift = 3 * ci.log2ts;
+  View vf, vb;
+  vf.KS = 8; vf.K = 8; vf.n_pad = co.n_pad; vf.n_out = co.n; vf.n_in = ci.n;
+  vb.KS = 1; vb.K = 8; vb.n_out = ci.n; vb.n_in = co.n;
+  if (ci.n > 0) {
+    int32_t *nbr8; uint32_t *mask;
+    if (dalloc(m, &nbr8, 8 * co.n_pad, s) || dalloc(m, &mask, co.n_pad / kGroup, s)) return 1;
+    LGS_KLAUNCH(k_build_map2_coarse, (unsigned)(co.n_pad / 256), 256, 0, s, ci.skeys, ci.order, co.cstart, co.n,
+                       co.n_pad, shift, nbr8, mask);
+    vf.nbr = nbr8; vf.mask64 = mask;
+    // grouped fine view
+    int64_t n = ci.n, gp = pad_rows(n + 8 * kPadRows);
+    uint32_t *kk, *kks; int32_t *pp, *pps, *cnt, *goff, *gsrc, *g_nbr, *g_out, *tile_k;
+    if (dalloc(m, &kk, n, s) || dalloc(m, &kks, n, s) || dalloc(m, &pp, n, s) || dalloc(m, &pps, n, s) ||
+        dalloc(m, &cnt, 8, s) || dalloc(m, &goff, 9, s) || dalloc(m, &gsrc, 9, s) || dalloc(m, &g_nbr, gp, s) ||
+        dalloc(m, &g_out, gp, s) || dalloc(m, &tile_k, gp / kGroup, s))
+      return 1;
+    LGS_HIP(hipMemsetAsync(cnt, 0, 8 * sizeof(int32_t), s));
+    LGS_KLAUNCH(k_child_keys, nblk(n), 256, 0, s, ci.skeys, n, shift, kk, pp, cnt);
+    if (sort_pairs(m, kk, kks, pp, pps, n, 0, 3, s)) return 1;
+    LGS_KLAUNCH(k_group_offsets, 1, 64, 0, s, cnt, goff, gsrc);
+    LGS_KLAUNCH(k_fill_i32, nblk(gp), 256, 0, s, g_nbr, gp, -1);
+    LGS_KLAUNCH(k_fill_i32, nblk(gp), 256, 0, s, g_out, gp, -1);
+    LGS_KLAUNCH(k_fill_i32, nblk(gp / kGroup), 256, 0, s, tile_k, gp / kGroup, -1);
+    LGS_KLAUNCH(k_build_map2_fine, nblk(n), 256, 0, s, kks, pps, n, goff, gsrc, co.fine_cidx, ci.order, g_nbr,
+                       g_out, tile_k);
+    LGS_HIP(hipGetLastError());
+    vb.nbr = g_nbr; vb.out_row = g_out; vb.tile_k = tile_k; vb.n_pad = gp;
+    if (dfree_now(m, kk, s) || dfree_now(m, kks, s) || dfree_now(m, pp, s) || dfree_now(m, pps, s) ||
+        dfree_now(m, cnt, s) || dfree_now(m, goff, s) || dfree_now(m, gsrc, s))
+      return 1;
+  }
+  km->fwd = vf; km->bwd = vb;
+  return 0;
+}
+
+// 3^3 stride 2.  Both views carry offset k in slot k (no mirroring): the fine-stationary one lists, per fine row, the coarse row of
+// the pair (k, fine, coarse) under the k of the forward direction
+int build_conv3_s2(lgs_manager *m, CoordMap &ci, CoordMap &co, hipStream_t s, lgs_kmap *km) {
+  if (ci.n > 0 && (ensure_hash(m, ci, s) || ensure_hash(m, co, s))) return 1;
+  // coarse-stationary: from the coarse rows' keys into the FINE map's hash, offsets scaled by ts_in
+  if (probe_view27(m, co, ci, ci.ts, s, km->fwd)) return 1;
+  return make_view27(m, ci, co.n, s, km->bwd, [&](int32_t *nbr_tmp, uint32_t *pmask) {
+    LGS_KLAUNCH(k_build_map3_fine, (unsigned)(ci.n_pad / 256), 256, 0, s, ci.skeys, ci.n, ci.n_pad, ci.log2ts, co.hkeys, co.hvals,
+                (uint64_t)(co.hcap - 1), nbr_tmp, pmask);
+    return 0;
+  });
+}
+
+// 1x1 stride 2: plain nbr (/ out_row) pairs on the KS = 1 path
+int build_conv1_s2(lgs_manager *m, const CoordMap &ci, const CoordMap &co, hipStream_t s, lgs_kmap *km) {
+  View vf, vb;
+  vf.KS = 1; vf.K = 1; vf.n_pad = co.n_pad; vf.n_out = co.n; vf.n_in = ci.n;
+  vb.KS = 1; vb.K = 1; vb.n_pad = ci.n_pad; vb.n_out = ci.n; vb.n_in = co.n;
+  if (ci.n > 0) {
+    int32_t *nf, *nb, *ob;
+    if (dalloc(m, &nf, co.n_pad, s) || dalloc(m, &nb, ci.n_pad, s) || dalloc(m, &ob, ci.n_pad, s)) return 1;
+    LGS_KLAUNCH(k_build_map1_coarse, nblk(co.n_pad), 256, 0, s, ci.skeys, ci.order, co.skeys, co.cstart, co.n, co.n_pad, nf);
+    LGS_KLAUNCH(k_build_map1_fine, nblk(ci.n_pad), 256, 0, s, ci.skeys, ci.order, co.fine_cidx, ci.n, ci.n_pad, 7ull << (3 * ci.log2ts), nb, ob);
+    LGS_HIP(hipGetLastError());
+    vf.nbr = nf; vb.nbr = nb; vb.out_row = ob;
+  }
+  km->fwd = vf; km->bwd = vb;
+  return 0;
+}
+
+// both map entry points (`who` names the one that was called): argument checks, the classifier, the cache, the relation's builder
+int kernel_map(bool ex, const char *who, lgs_manager *m, int in_key, int out_key, int ks, int dilation, lgs_kmap **out) {
+  LGS_REQUIRE(m && out, std::string(who) + ": null argument");
+  const int nm = (int)m->maps.size();
+  LGS_REQUIRE(in_key >= 0 && in_key < nm && out_key >= 0 && out_key < nm, std::string(who) + ": bad key");
+  CoordMap &ci = m->maps[in_key], &co = m->maps[out_key];
+  KmapRelation rel = kRelIdentity;
+  const char *refusal = classify_kmap(KmapRequest{ex, in_key == out_key, co.fine_key == in_key, co.order == nullptr, ci.origin || co.origin, ks,
+                                                  dilation, ci.ts}, rel);
+  LGS_REQUIRE(refusal == nullptr, refusal);
+  const KmapTraits t = traits_of(rel);
+  if (rel != kRelConv3Dilated) dilation = 1;
+  for (lgs_kmap *k : m->kmaps)
+    if (k->in_key == in_key && k->out_key == out_key && k->relation == rel && k->dilation == dilation) { *out = k; return 0; }
+  hipStream_t s = m->ms;
+  DeviceGuard guard(m->device);
+  std::unique_ptr<lgs_kmap> km(new lgs_kmap());
+  km->mgr = m; km->in_key = in_key; km->out_key = out_key; km->ks = t.ks; km->K = t.K; km->relation = rel; km->dilation = dilation;
+  int rc = 0;
+  switch (rel) {
+    case kRelIdentity: build_identity(ci, km.get()); break;
+    case kRelConv3:
+    case kRelConv3Dilated: rc = build_conv3(m, ci, dilation, s, km.get()); break;
+    case kRelConv2S2: rc = build_conv2_s2(m, ci, co, s, km.get()); break;
+    case kRelConv3S2: rc = build_conv3_s2(m, ci, co, s, km.get()); break;
+    case kRelConv1S2: rc = build_conv1_s2(m, ci, co, s, km.get()); break;
+  }
+  if (rc) return rc;
+  m->kmaps.push_back(km.get());
+  *out = km.release();
+  return publish(m, nullptr, false);
+}
 }  // namespace
 
 namespace lgs {
@@ -908,14 +1044,7 @@ int lgs_manager_insert(lgs_manager *m, const int32_t *coords, int64_t n, int64_t
       dalloc(m, &head, n, s) || dalloc(m, &runid, n, s) || dalloc(m, &is_first, n, s) || dalloc(m, &urow, n + 1, s))
     return 1;
   LGS_KLAUNCH(k_pack_keys, nblk(n), 256, 0, s, coords, n, keys, vals, m->d_err);
-  {
-    size_t tb = 0;
-    LGS_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys, skeys, vals, svals, (size_t)n, 0, 64, s));
-    void *tmp = nullptr;
-    if (raw_alloc(m, &tmp, tb ? tb : 16, s)) return 1;
-    LGS_HIP(rocprim::radix_sort_pairs(tmp, tb, keys, skeys, vals, svals, (size_t)n, 0, 64, s));
-    if (dfree_now(m, tmp, s)) return 1;
-  }
+  if (sort_pairs(m, keys, skeys, vals, svals, n, 0, 64, s)) return 1;
   LGS_KLAUNCH(k_heads, nblk(n), 256, 0, s, skeys, n, ~0ull, head);
   LGS_KLAUNCH(k_mark_first, nblk(n), 256, 0, s, svals, head, n, is_first);
   if (scan_incl(m, head, runid, n, s)) return 1;
@@ -1040,165 +1169,30 @@ int lgs_manager_get_coords(lgs_manager *m, int key, int32_t *dst, void *stream) 
 }
 
 int lgs_manager_kernel_map(lgs_manager *m, int in_key, int out_key, int ks, void *stream, lgs_kmap **out) {
-  LGS_REQUIRE(m && out, "lgs_manager_kernel_map: null argument");
-  int nm = (int)m->maps.size();
-  LGS_REQUIRE(in_key >= 0 && in_key < nm && out_key >= 0 && out_key < nm, "lgs_manager_kernel_map: bad key");
-  LGS_REQUIRE(!m->maps[in_key].origin && !m->maps[out_key].origin, "lgs_manager_kernel_map: no kernel maps on the origin map");
-  for (lgs_kmap *k : m->kmaps)
-    if (k->in_key == in_key && k->out_key == out_key && k->ks == ks && k->dilation == 1 && !k->strided) { *out = k; return 0; }
-  hipStream_t s = m->ms;
   (void)stream;
-  DeviceGuard guard(m->device);
-  lgs_kmap *km = new lgs_kmap();
-  km->mgr = m; km->in_key = in_key; km->out_key = out_key; km->ks = ks;
-  CoordMap &ci = m->maps[in_key];
-  if (ks == 1) {
-    LGS_REQUIRE(in_key == out_key, "kernel_size 1 needs in_key == out_key");
-    km->K = 1;
-    View v; v.n_pad = ci.n_pad; v.n_out = ci.n; v.n_in = ci.n; v.KS = 1; v.K = 1;
-    km->fwd = v; km->bwd = v;
-  } else if (ks == 3) {
-    LGS_REQUIRE(in_key == out_key, "kernel_size 3 is supported for stride 1 (in_key == out_key) only");
-    km->K = 27;
-    if (ci.n > 0 && ensure_hash(m, ci, s)) return 1;
-    View v;
-    if (make_view27(m, ci, ci.n, s, v, [&](int32_t *nbr_tmp, uint32_t *pmask) {
-          LGS_KLAUNCH(k_build_map3, (unsigned)(ci.n_pad / 256), 256, 0, s, ci.skeys, ci.n, ci.n_pad, ci.ts, ci.hkeys, ci.hvals,
-                      (uint64_t)(ci.hcap - 1), nbr_tmp, pmask);
-          return 0;
-        }))
-      return 1;
-    km->fwd = v;
-    km->bwd = v; km->bwd.mirror = 1;
-  } else if (ks == 2) {
-    CoordMap &co = m->maps[out_key];
-    LGS_REQUIRE(co.fine_key == in_key, "kernel_size 2 needs out_key == stride2(in_key)");
-    km->K = 8;
-    int shift = 3 * ci.log2ts;
-    View vf, vb;
-    vf.KS = 8; vf.K = 8; vf.n_pad = co.n_pad; vf.n_out = co.n; vf.n_in = ci.n;
-    vb.KS = 1; vb.K = 8; vb.n_out = ci.n; vb.n_in = co.n;
-    if (ci.n > 0) {
-      int32_t *nbr8; uint32_t *mask;
-      if (dalloc(m, &nbr8, 8 * co.n_pad, s) || dalloc(m, &mask, co.n_pad / kGroup, s)) return 1;
-      LGS_KLAUNCH(k_build_map2_coarse, (unsigned)(co.n_pad / 256), 256, 0, s, ci.skeys, ci.order, co.cstart, co.n,
-                         co.n_pad, shift, nbr8, mask);
-      vf.nbr = nbr8; vf.mask64 = mask;
-      // grouped fine view
-      int64_t n = ci.n, gp = pad_rows(n + 8 * kPadRows);
-      uint32_t *kk, *kks; int32_t *pp, *pps, *cnt, *goff, *gsrc, *g_nbr, *g_out, *tile_k;
-      if (dalloc(m, &kk, n, s) || dalloc(m, &kks, n, s) || dalloc(m, &pp, n, s) || dalloc(m, &pps, n, s) ||
-          dalloc(m, &cnt, 8, s) || dalloc(m, &goff, 9, s) || dalloc(m, &gsrc, 9, s) || dalloc(m, &g_nbr, gp, s) ||
-          dalloc(m, &g_out, gp, s) || dalloc(m, &tile_k, gp / kGroup, s))
-        return 1;
-      LGS_HIP(hipMemsetAsync(cnt, 0, 8 * sizeof(int32_t), s));
-      LGS_KLAUNCH(k_child_keys, nblk(n), 256, 0, s, ci.skeys, n, shift, kk, pp, cnt);
-      {
-        size_t tb = 0;
-        LGS_HIP(rocprim::radix_sort_pairs(nullptr, tb, kk, kks, pp, pps, (size_t)n, 0, 3, s));
-        void *tmp = nullptr;
-        if (raw_alloc(m, &tmp, tb ? tb : 16, s)) return 1;
-        LGS_HIP(rocprim::radix_sort_pairs(tmp, tb, kk, kks, pp, pps, (size_t)n, 0, 3, s));
-        if (dfree_now(m, tmp, s)) return 1;
-      }
-      LGS_KLAUNCH(k_group_offsets, 1, 64, 0, s, cnt, goff, gsrc);
-      LGS_KLAUNCH(k_fill_i32, nblk(gp), 256, 0, s, g_nbr, gp, -1);
-      LGS_KLAUNCH(k_fill_i32, nblk(gp), 256, 0, s, g_out, gp, -1);
-      LGS_KLAUNCH(k_fill_i32, nblk(gp / kGroup), 256, 0, s, tile_k, gp / kGroup, -1);
-      LGS_KLAUNCH(k_build_map2_fine, nblk(n), 256, 0, s, kks, pps, n, goff, gsrc, co.fine_cidx, ci.order, g_nbr,
-                         g_out, tile_k);
-      LGS_HIP(hipGetLastError());
-      vb.nbr = g_nbr; vb.out_row = g_out; vb.tile_k = tile_k; vb.n_pad = gp;
-      if (dfree_now(m, kk, s) || dfree_now(m, kks, s) || dfree_now(m, pp, s) || dfree_now(m, pps, s) ||
-          dfree_now(m, cnt, s) || dfree_now(m, goff, s) || dfree_now(m, gsrc, s))
-        return 1;
-    }
-    km->fwd = vf; km->bwd = vb;
-  } else {
-    delete km;
-    LGS_REQUIRE(false, "unsupported kernel_size (the model family uses 1, 2 and 3 only)");
-  }
-  m->kmaps.push_back(km);
-  *out = km;
-  return publish(m, nullptr, false);
+  return kernel_map(false, "lgs_manager_kernel_map", m, in_key, out_key, ks, 1, out);
 }
 
 int lgs_manager_kernel_map_ex(lgs_manager *m, int in_key, int out_key, int ks, int dilation, void *stream, lgs_kmap **out) {
-  LGS_REQUIRE(m && out, "lgs_manager_kernel_map_ex: null argument");
-  const int nm = (int)m->maps.size();
-  LGS_REQUIRE(in_key >= 0 && in_key < nm && out_key >= 0 && out_key < nm, "lgs_manager_kernel_map_ex: bad key");
-  LGS_REQUIRE(!m->maps[in_key].origin && !m->maps[out_key].origin, "lgs_manager_kernel_map_ex: no kernel maps on the origin map");
-  LGS_REQUIRE(dilation >= 1, "lgs_manager_kernel_map_ex: dilation must be >= 1");
-  const bool strided = in_key != out_key && m->maps[out_key].fine_key == in_key;
-  LGS_REQUIRE(!(strided && dilation > 1), "lgs_manager_kernel_map_ex: stride 2 combined with dilation > 1 is not supported");
-  LGS_REQUIRE(dilation == 1 || ks == 3, "lgs_manager_kernel_map_ex: dilation > 1 needs kernel_size 3");
-  // the three relations of lgs_manager_kernel_map (and everything it refuses): the same cached objects
-  if (dilation == 1 && !(strided && (ks == 3 || ks == 1))) return lgs_manager_kernel_map(m, in_key, out_key, ks, stream, out);
-  LGS_REQUIRE(strided || in_key == out_key, "lgs_manager_kernel_map_ex: out_key must be in_key or stride2(in_key)");
-  for (lgs_kmap *k : m->kmaps)
-    if (k->in_key == in_key && k->out_key == out_key && k->ks == ks && k->dilation == dilation) { *out = k; return 0; }
-  hipStream_t s = m->ms;
-  DeviceGuard guard(m->device);
-  CoordMap &ci = m->maps[in_key];
-  // the coarse-stationary views take "position == output row": a map made by stride2 has its rows in Morton order (order == nullptr)
-  LGS_REQUIRE(!strided || m->maps[out_key].order == nullptr, "lgs_manager_kernel_map_ex: the stride-2 map's rows are not in sorted order");
-  // every probed coordinate must stay inside the packed range's reach: offsets of d * ts below 2^17
-  LGS_REQUIRE((int64_t)dilation * ci.ts < (1ll << (kCoordBits - 1)), "lgs_manager_kernel_map_ex: dilation * tensor_stride must stay below 2^17");
-  std::unique_ptr<lgs_kmap> km(new lgs_kmap());
-  km->mgr = m; km->in_key = in_key; km->out_key = out_key; km->ks = ks; km->dilation = dilation; km->strided = strided ? 1 : 0;
-  if (!strided) {
-    // dilated 3^3 stride-1: the stride-1 pipeline with the offset scale d * ts; bwd = fwd read mirrored
-    km->K = 27;
-    if (ci.n > 0 && ensure_hash(m, ci, s)) return 1;
-    const int scale = dilation * ci.ts;
-    View v;
-    if (make_view27(m, ci, ci.n, s, v, [&](int32_t *nbr_tmp, uint32_t *pmask) {
-          LGS_KLAUNCH(k_build_map3, (unsigned)(ci.n_pad / 256), 256, 0, s, ci.skeys, ci.n, ci.n_pad, scale, ci.hkeys, ci.hvals,
-                      (uint64_t)(ci.hcap - 1), nbr_tmp, pmask);
-          return 0;
-        }))
-      return 1;
-    km->fwd = v;
-    km->bwd = v; km->bwd.mirror = 1;
-  } else if (ks == 3) {
-    // 3^3 stride-2.  Both views carry offset k in slot k (no mirroring): the fine-stationary one lists, per fine row, the coarse row
-    // of the pair (k, fine, coarse) under the k of the forward direction
-    CoordMap &co = m->maps[out_key];
-    km->K = 27;
-    if (ci.n > 0 && (ensure_hash(m, ci, s) || ensure_hash(m, co, s))) return 1;
-    // coarse-stationary: the 27 probes of k_build_map3, from the coarse rows' keys into the FINE map's hash, offsets scaled by ts_in
-    if (make_view27(m, co, ci.n, s, km->fwd, [&](int32_t *nbr_tmp, uint32_t *pmask) {
-          LGS_KLAUNCH(k_build_map3, (unsigned)(co.n_pad / 256), 256, 0, s, co.skeys, co.n, co.n_pad, ci.ts, ci.hkeys, ci.hvals,
-                      (uint64_t)(ci.hcap - 1), nbr_tmp, pmask);
-          return 0;
-        }))
-      return 1;
-    if (make_view27(m, ci, co.n, s, km->bwd, [&](int32_t *nbr_tmp, uint32_t *pmask) {
-          LGS_KLAUNCH(k_build_map3_fine, (unsigned)(ci.n_pad / 256), 256, 0, s, ci.skeys, ci.n, ci.n_pad, ci.log2ts, co.hkeys, co.hvals,
-                      (uint64_t)(co.hcap - 1), nbr_tmp, pmask);
-          return 0;
-        }))
-      return 1;
-  } else {
-    // 1x1 stride-2: plain nbr (/ out_row) pairs on the KS = 1 path
-    CoordMap &co = m->maps[out_key];
-    km->K = 1;
-    View vf, vb;
-    vf.KS = 1; vf.K = 1; vf.n_pad = co.n_pad; vf.n_out = co.n; vf.n_in = ci.n;
-    vb.KS = 1; vb.K = 1; vb.n_pad = ci.n_pad; vb.n_out = ci.n; vb.n_in = co.n;
-    if (ci.n > 0) {
-      int32_t *nf, *nb, *ob;
-      if (dalloc(m, &nf, co.n_pad, s) || dalloc(m, &nb, ci.n_pad, s) || dalloc(m, &ob, ci.n_pad, s)) return 1;
-      LGS_KLAUNCH(k_build_map1_coarse, nblk(co.n_pad), 256, 0, s, ci.skeys, ci.order, co.skeys, co.cstart, co.n, co.n_pad, nf);
-      LGS_KLAUNCH(k_build_map1_fine, nblk(ci.n_pad), 256, 0, s, ci.skeys, ci.order, co.fine_cidx, ci.n, ci.n_pad, 7ull << (3 * ci.log2ts), nb, ob);
-      LGS_HIP(hipGetLastError());
-      vf.nbr = nf; vb.nbr = nb; vb.out_row = ob;
-    }
-    km->fwd = vf; km->bwd = vb;
-  }
-  m->kmaps.push_back(km.get());
-  *out = km.release();
-  return publish(m, nullptr, false);
+  (void)stream;
+  return kernel_map(true, "lgs_manager_kernel_map_ex", m, in_key, out_key, ks, dilation, out);
+}
+
+// what the two entry points above decide for a request given by plain facts, and what follows from it: no manager, no HIP call
+int lgs_debug_kmap_relation(const lgs_kmap_relation_query *q, lgs_kmap_relation_info *out) {
+  LGS_REQUIRE(q && out && (q->entry == 0 || q->entry == 1) && q->link >= 0 && q->link <= 3, "lgs_debug_kmap_relation: bad argument");
+  *out = lgs_kmap_relation_info{};
+  KmapRelation rel = kRelIdentity;
+  const char *refusal = classify_kmap(KmapRequest{q->entry == 1, q->link == 0, q->link == 1, q->out_sorted != 0, q->in_origin || q->out_origin, q->ks,
+                                                  q->dilation, q->tensor_stride}, rel);
+  out->rc = refusal ? 2 : 0;
+  out->relation = -1;
+  LGS_REQUIRE(refusal == nullptr, refusal);
+  const KmapTraits t = traits_of(rel);
+  out->relation = rel; out->K = t.K; out->strided = t.strided; out->bwd_mirror = t.bwd_mirror; out->transposed_ok = t.transposed_ok;
+  out->pairs_only[0] = t.wgrad_pairs_only(false); out->pairs_only[1] = t.wgrad_pairs_only(true);
+  out->served_by_old_entry = t.old_entry;
+  return 0;
 }
 
 int lgs_manager_origin(lgs_manager *m, void *stream, int *out_key, int64_t *n_out) {
@@ -1221,8 +1215,7 @@ int lgs_manager_origin(lgs_manager *m, void *stream, int *out_key, int64_t *n_ou
   if (n > 0) {
     int32_t *head, *cincl;
     if (dalloc(m, &o.coords, nb * 4, s) || dalloc(m, &head, n, s) || dalloc(m, &cincl, n, s)) return 1;
-    LGS_KLAUNCH(k_heads, nblk(n), 256, 0, s, f.skeys, n, ~((1ull << kBatchShift) - 1), head);
-    if (scan_incl(m, head, cincl, n, s)) return 1;
+    if (batch_heads(m, f.skeys, n, head, cincl, s)) return 1;
     LGS_KLAUNCH(k_origin_coords, nblk(n), 256, 0, s, f.skeys, head, cincl, n, nb, o.coords, m->d_err);
     LGS_HIP(hipGetLastError());
     if (dfree_now(m, head, s) || dfree_now(m, cincl, s)) return 1;
@@ -1273,8 +1266,7 @@ int lgs_manager_segment_map(lgs_manager *m, int fine_key, int coarse_key, void *
       int32_t *head, *cincl, *seg_start, *coarse_of;
       if (dalloc(m, &seg_start, nc + 1, s) || dalloc(m, &coarse_of, n, s) || dalloc(m, &head, n, s) || dalloc(m, &cincl, n, s))
         return 1;
-      LGS_KLAUNCH(k_heads, nblk(n), 256, 0, s, cf.skeys, n, ~((1ull << kBatchShift) - 1), head);
-      if (scan_incl(m, head, cincl, n, s)) return 1;
+      if (batch_heads(m, cf.skeys, n, head, cincl, s)) return 1;
       LGS_KLAUNCH(k_origin_segments, nblk(n), 256, 0, s, head, cincl, n, nc, seg_start, coarse_of);
       LGS_HIP(hipGetLastError());
       if (dfree_now(m, head, s) || dfree_now(m, cincl, s)) return 1;

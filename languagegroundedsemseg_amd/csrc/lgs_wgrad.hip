@@ -1325,9 +1325,7 @@ WgradPlan wgrad_plan(const lgs_kmap &km, int transposed, int cin, int cout, int 
   WgradPlan p = {};
   const View &v = transposed ? km.bwd : km.fwd;  // same view as the forward
   if (v.n_pad == 0) return p;
-  // k_wgrad_wide and k_wgrad_ps have been run and measured on the 3^3 stride-1 table and the 2^3 views only: a 3^3 map with two
-  // different row spaces, and any 3^3 map walked by a transposed conv, goes to the pair-list / fp32 kernels, which take any view
-  const bool pairs_only = km.ks == 3 && (km.strided || transposed);
+  const bool pairs_only = traits_of(&km).wgrad_pairs_only(transposed != 0);   // (KmapTraits: which maps the wide / ps kernels were run on)
   if (dtype == LGS_BF16 && km.fwd.n_pad > 0 && (km.ks == 3 || km.ks == 2) && !pairs_only) {
     const int ld = in_row_stride > 0 ? in_row_stride : cin;
     const bool k3 = km.ks == 3 && !transposed;
@@ -1370,7 +1368,7 @@ WgradPlan wgrad_plan(const lgs_kmap &km, int transposed, int cin, int cout, int 
 // or strided input
 int64_t wgrad_workspace_bytes(const lgs_kmap *km, int cin, int cout, int dtype) {
   int64_t bytes = 0;
-  for (int transposed = 0; transposed <= (transposed_ok(km) ? 1 : 0); ++transposed)
+  for (int transposed = 0; transposed <= (traits_of(km).transposed_ok ? 1 : 0); ++transposed)
     for (int in_row_stride : {0, cin + 8}) {
       const int64_t b = wgrad_plan(*km, transposed, cin, cout, dtype, in_row_stride).bytes_total;
       if (b > bytes) bytes = b;
@@ -1587,14 +1585,14 @@ int lgs_clip_loss_backward_anchors(const void *feat, int64_t n, int c, int n_anc
 }
 
 int lgs_conv_wgrad_supports_stride(const lgs_kmap *km, int transposed, int cin, int cout, int dtype, int in_row_stride) {
-  if (!km || (transposed && !transposed_ok(km)) || !(dtype == LGS_F32 || dtype == LGS_BF16)) return 0;
+  if (!km || (transposed && !traits_of(km).transposed_ok) || !(dtype == LGS_F32 || dtype == LGS_BF16)) return 0;
   return wgrad_plan(*km, transposed, cin, cout, dtype, in_row_stride).in_place;
 }
 
 int lgs_conv_wgrad(lgs_kmap *km, int transposed, const void *in, int cin, const void *grad_out, int cout,
                    float *grad_weight, int dtype, void *workspace, int in_row_stride, void *stream) {
   LGS_REQUIRE(km && grad_weight && workspace, "lgs_conv_wgrad: null argument");
-  LGS_REQUIRE(!transposed || transposed_ok(km), "transposed 3x3x3 convolution is not part of the model family");
+  LGS_REQUIRE(!transposed || traits_of(km).transposed_ok, "transposed 3x3x3 convolution is not part of the model family");
   LGS_REQUIRE(dtype == LGS_F32 || dtype == LGS_BF16, "lgs_conv_wgrad: unknown dtype");
   hipStream_t s = (hipStream_t)stream;
   if (kmap_wait(km, s)) return 1;
@@ -1633,8 +1631,7 @@ int lgs_debug_wgrad_plan(const lgs_wgrad_plan_query *q, lgs_wgrad_plan_info *out
   };
   lgs_kmap km;
   km.ks = q->ks; km.K = q->fwd.K; km.fwd = view(q->fwd); km.bwd = view(q->bwd);
-  synthetic_kmap_facts(km);
-  LGS_REQUIRE(!q->transposed || transposed_ok(&km), "lgs_debug_wgrad_plan: bad argument");
+  LGS_REQUIRE(synthetic_kmap_relation(km) == nullptr && (!q->transposed || traits_of(&km).transposed_ok), "lgs_debug_wgrad_plan: bad argument");
   *out = wgrad_plan(km, q->transposed, q->cin, q->cout, q->dtype, q->in_row_stride);
   out->workspace_bytes = lgs_conv_workspace_bytes(&km, q->cin, q->cout, q->dtype, 2);
   out->supports_stride = lgs_conv_wgrad_supports_stride(&km, q->transposed, q->cin, q->cout, q->dtype, q->in_row_stride);

@@ -92,6 +92,17 @@ class InstNormPlanInfo(ctypes.Structure):
                [("bytes_total", ctypes.c_int64), ("workspace_bytes", ctypes.c_int64)]
 
 
+class KmapRelationQuery(ctypes.Structure):
+    """lgs_kmap_relation_query"""
+    _fields_ = [(n, ctypes.c_int) for n in ("entry", "ks", "dilation", "link", "tensor_stride", "out_sorted", "in_origin", "out_origin")]
+
+
+class KmapRelationInfo(ctypes.Structure):
+    """lgs_kmap_relation_info: what lgs_debug_kmap_relation answers (no GPU needed)"""
+    _fields_ = [(n, ctypes.c_int) for n in ("rc", "relation", "K", "strided", "bwd_mirror", "transposed_ok")] + \
+               [("pairs_only", ctypes.c_int * 2), ("served_by_old_entry", ctypes.c_int)]
+
+
 class BnParams(ctypes.Structure):
     """lgs_bn_params"""
     _fields_ = [("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p), ("running_mean", ctypes.c_void_p), ("running_var", ctypes.c_void_p),
@@ -152,7 +163,7 @@ _lib = None
 EXPORTS = [
     "lgs_abi_version", "lgs_last_error",
     "lgs_tuning_set", "lgs_tuning_get", "lgs_tuning_describe", "lgs_debug_dispatch_counts", "lgs_debug_conv_plan", "lgs_debug_wgrad_plan",
-    "lgs_debug_norm_plan", "lgs_debug_instnorm_plan",
+    "lgs_debug_norm_plan", "lgs_debug_instnorm_plan", "lgs_debug_kmap_relation",
     "lgs_manager_create", "lgs_manager_destroy", "lgs_manager_insert", "lgs_manager_stride2", "lgs_manager_check",
     "lgs_manager_parent_of", "lgs_manager_map_size", "lgs_manager_get_coords", "lgs_manager_kernel_map", "lgs_manager_kernel_map_ex",
     "lgs_kmap_export",
@@ -229,6 +240,7 @@ def lib():
         "lgs_debug_wgrad_plan": [ctypes.POINTER(WgradPlanQuery), ctypes.POINTER(WgradPlanInfo)],
         "lgs_debug_norm_plan": [ctypes.POINTER(NormPlanQuery), ctypes.POINTER(NormPlanInfo)],
         "lgs_debug_instnorm_plan": [ctypes.POINTER(InstNormPlanQuery), ctypes.POINTER(InstNormPlanInfo)],
+        "lgs_debug_kmap_relation": [ctypes.POINTER(KmapRelationQuery), ctypes.POINTER(KmapRelationInfo)],
         "lgs_conv_bn_partial_rows": [vp, ci, ci, ci],
         "lgs_conv_dgrad": [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, vp],
         "lgs_sgd_step": [vp, vp, vp, vp, i64, cf, cf, cf, cf, ci, vp],

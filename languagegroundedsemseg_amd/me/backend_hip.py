@@ -12,6 +12,7 @@ import weakref
 import torch
 
 from .. import engine
+from .kernel import ALL_CONV_RELATIONS
 from .. import tuning as _tuning
 
 _vp = ctypes.c_void_p
@@ -491,10 +492,10 @@ class HipManager:
             self._kmaps[k] = sm
         return sm
 
-    has_kernel_map_ex = True     # strided 3^3 / 1x1 and dilated 3^3 maps (lgs_manager_kernel_map_ex)
+    kernel_map_relations = ALL_CONV_RELATIONS     # every relation of the engine's classifier (lgs_manager_kernel_map_ex)
 
     def kernel_map(self, in_key, out_key, ks, dilation=1):
-        k = (in_key, out_key, ks) if dilation == 1 else (in_key, out_key, ks, dilation)
+        k = (in_key, out_key, ks, dilation)
         km = self._kmaps.get(k)
         if km is None:
             h = _vp(None)     # the engine caches the map itself: a second request returns the same handle at no cost

@@ -12,6 +12,7 @@ from enum import Enum
 import torch
 
 from . import deferred as _deferred
+from .kernel import CONV3_DILATED, GENERIC_CONV_RELATIONS, conv_relation
 
 _BACKEND = None
 
@@ -143,15 +144,16 @@ class CoordinateManager:
         return self._m.coords(key.id)
 
     def kernel_map_handle(self, in_key, out_key, kernel_size, dilation=1):
-        """the backend's kernel map between two maps of this manager.  Dilated 3^3 maps and the 1x1 map onto a stride-2 map
-        exist on the HIP engine only (lgs_manager_kernel_map_ex); a 3^3 map onto a stride-2 map also on backends whose
-        kernel_map is generic in its keys."""
-        if getattr(self._m, "has_kernel_map_ex", False):
-            return self._m.kernel_map(in_key.id, out_key.id, kernel_size, dilation)
-        if dilation != 1 or (kernel_size == 1 and in_key.id != out_key.id):
+        """the backend's kernel map between two maps of this manager.  A relation of the supported set (me.kernel.SUPPORTED_CONVS)
+        that the backend's manager does not list in `kernel_map_relations` is refused here, by name; a manager that lists nothing
+        builds what a generic `kernel_map(in_key, out_key, kernel_size)` covers (me.kernel.GENERIC_CONV_RELATIONS)."""
+        rel = conv_relation(kernel_size, 1 if in_key.id == out_key.id else 2, dilation) or (CONV3_DILATED if dilation != 1 else None)
+        if rel is not None and rel.name not in getattr(self._m, "kernel_map_relations", GENERIC_CONV_RELATIONS):
             raise NotImplementedError("%s needs the HIP engine: backend %r builds no such kernel map (there is no fallback)" % (
-                "a dilated convolution" if dilation != 1 else "a 1x1 stride-2 convolution", self.backend.name))
-        return self._m.kernel_map(in_key.id, out_key.id, kernel_size)
+                rel.what, self.backend.name))
+        if dilation == 1:
+            return self._m.kernel_map(in_key.id, out_key.id, kernel_size)
+        return self._m.kernel_map(in_key.id, out_key.id, kernel_size, dilation)
 
     def kernel_map(self, in_key, out_key, stride=1, kernel_size=3, dilation=1, **kwargs):
         """-> {k: int tensor [2, M_k]} (in_row; out_row), the ME `kernel_map` query."""

@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from . import deferred as _deferred
 from .core import SparseTensor, get_backend
-from .kernel import KernelGenerator, RegionType, convert_to_int_list
+from .kernel import KernelGenerator, RegionType, conv_relation, convert_to_int_list, supported_convs_text
 
 
 from .. import tuning as _tuning
@@ -205,10 +205,9 @@ class MinkowskiConvolutionBase(MinkowskiModuleBase):
         if len(set(self.kernel_size)) != 1 or len(set(self.stride)) != 1 or len(set(self.dilation)) != 1:
             raise NotImplementedError("anisotropic kernels / strides / dilations are not supported on D=3")
         ks, st, dil = self.kernel_size[0], self.stride[0], self.dilation[0]
-        if not ((ks, st) in ((3, 1), (2, 2), (1, 1), (3, 2), (1, 2)) and dil >= 1 and (dil == 1 or (ks, st) == (3, 1))):
-            raise NotImplementedError(
-                "(kernel_size, stride, dilation) = (%d, %d, %d) is not supported: the supported set is (3, 1, d >= 1), (3, 2, 1), "
-                "(2, 2, 1), (1, 1, 1) and (1, 2, 1)" % (ks, st, dil))
+        if conv_relation(ks, st, dil) is None:
+            raise NotImplementedError("(kernel_size, stride, dilation) = (%d, %d, %d) is not supported: the supported set is %s" % (
+                ks, st, dil, supported_convs_text()))
         self.kernel_volume = kernel_generator.kernel_volume
         if self.kernel_volume == 1 and st == 1:
             self.use_mm = True

@@ -135,7 +135,10 @@ class OracleManager:
     def coords(self, key):
         return torch.from_numpy(self._coords[key])
 
-    def kernel_map(self, in_key, out_key, ks):
+    kernel_map_relations = ("identity", "conv3", "conv2_s2", "conv3_s2")   # the pair search: dilation 1; its 1x1 map is the identity
+
+    def kernel_map(self, in_key, out_key, ks, dilation=1):
+        assert dilation == 1, "the oracle builds dilation-1 kernel maps only"
         k = (in_key, out_key, ks)
         if k not in self._kmaps:
             self._kmaps[k] = OracleKernelMap(self, in_key, out_key, ks, self.impl)
