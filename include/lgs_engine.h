@@ -439,6 +439,30 @@ typedef struct lgs_instnorm_plan_info {
 } lgs_instnorm_plan_info;
 int lgs_debug_instnorm_plan(const lgs_instnorm_plan_query *q, lgs_instnorm_plan_info *out);
 
+/* lgs_debug_seg_plan: what a pooling / broadcast call decides on the host, for a call given by plain integers (the sizes of the
+ * segment map, whether its segments fit one chunk, and whether the call's operands allow 16-byte accesses).  No HIP call: it
+ * runs without a GPU (tests/test_seg_plan_cpu.py). */
+typedef struct lgs_seg_plan_query {
+  int family;              /* 0 lgs_seg_reduce, 1 lgs_seg_broadcast, 2 lgs_seg_max_backward */
+  int c, dtype;
+  int single_pass;         /* 1: no segment is longer than one chunk (maps of stride 2, 4 and 8); 0: chunk items + combine */
+  int vec_ok;              /* 1: every operand the call dereferences has 16-byte aligned rows (pointer and row stride) */
+  int64_t n_fine, n_coarse, n_items;
+} lgs_seg_plan_query;
+typedef struct lgs_seg_plan_info {
+  int vec;                 /* 1: 16 bytes per lane (vec_ok and c * element size a multiple of 16), 0: one element per lane */
+  int lanes_log2;          /* log2 of the lanes that share one row in k_seg_reduce / k_seg_bcast / k_seg_max_bwd */
+  int combine_lanes_log2;  /* the same for k_seg_combine (one fp32 partial per lane) */
+  int64_t reduce_grid;     /* family 0: workgroups of k_seg_reduce over the coarse rows (single pass) or the chunk items */
+  int64_t combine_grid;    /* family 0, two passes: workgroups of k_seg_combine; 0 = none */
+  int64_t bcast_grid;      /* family 1: workgroups of k_seg_bcast */
+  int64_t max_bwd_grid;    /* family 2: workgroups of k_seg_max_bwd; the grids of the other families are 0 */
+  lgs_conv_plan_region partials, partial_argmax;   /* family 0, two passes: fp32 [n_items][c] and int32 [n_items][c] */
+  int64_t bytes_total;
+  int64_t workspace_bytes; /* lgs_seg_workspace_bytes(sm, c) */
+} lgs_seg_plan_info;
+int lgs_debug_seg_plan(const lgs_seg_plan_query *q, lgs_seg_plan_info *out);
+
 /* ---- SyncBatchNorm as one call per direction, on the engine's own RCCL communicator (csrc/lgs_comm.hip) --------
  * replaces the per-layer statistics exchange of ME.MinkowskiSyncBatchNorm (convert_sync_batchnorm, /root/reference/main.py:121-123;
  * downstream/insseg/lib/ddp_trainer.py:191-194) when it runs rank per GPU: the split kernels above with ncclAllGather /

@@ -19,8 +19,9 @@
 //                  SegMap::row_seg.  A thread owns a fixed channel group (weight / bias loaded once) and reloads the scene's
 //                  statistics only when the scene changes from one of its rows to the next.  The backward apply's first
 //                  workgroups also fold the scene sums into dweight / dbias, scenes in ascending order.
-// No float atomics anywhere: two runs give the same bits.  Everything a call decides on the host comes from instnorm_plan().
-#include "lgs_common.h"
+// No float atomics anywhere: two runs give the same bits.  Everything a call decides on the host comes from instnorm_plan();
+// the row accesses, lanes per row, grids and the lift from (dtype, width) to template arguments are lgs_rows.h's.
+#include "lgs_rows.h"
 
 namespace lgs {
 namespace {
@@ -31,53 +32,6 @@ constexpr int kInCombCh = 16;     // k_in_combine: channels per workgroup ...
 constexpr int kInCombSl = 16;     // ... and item slices per channel (kInCombCh * kInCombSl == kNT)
 constexpr int kInApplyIters = 16;  // k_in_apply: rows per thread; a workgroup covers (kNT >> lg) * kInApplyIters rows
 enum { kInFwd = 0, kInBwd = 1 };
-
-template <typename T, bool VEC> struct Width { static constexpr int V = VEC ? (int)(16 / sizeof(T)) : 1; };
-
-template <int V> __device__ inline void ldv(const float *p, float *v) {
-  if constexpr (V == 4) {
-    const float4 a = *reinterpret_cast<const float4 *>(p);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  } else {
-    v[0] = *p;
-  }
-}
-template <int V> __device__ inline void ldv(const bf16_t *p, float *v) {
-  if constexpr (V == 8) {
-    const uint4 a = *reinterpret_cast<const uint4 *>(p);
-    const uint32_t w[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[2 * i] = __uint_as_float(w[i] << 16);
-      v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  } else {
-    v[0] = bf16_to_f32(*p);
-  }
-}
-template <int V> __device__ inline void stv(float *p, const float *v) {
-  if constexpr (V == 4) *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else *p = v[0];
-}
-template <int V> __device__ inline void stv(bf16_t *p, const float *v) {
-  if constexpr (V == 8) {
-    uint32_t w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = (uint32_t)f32_to_bf16(v[2 * i]) | ((uint32_t)f32_to_bf16(v[2 * i + 1]) << 16);
-    *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-  } else {
-    *p = f32_to_bf16(v[0]);
-  }
-}
-// V consecutive floats of an fp32 row (statistics, weight, bias): V is 1, 4 or 8 and the rows are 16-byte aligned when V > 1
-template <int V> __device__ inline void ldf(const float *p, float *v) {
-  if constexpr (V == 1) {
-    v[0] = *p;
-  } else {
-#pragma unroll
-    for (int i = 0; i < V; i += 4) ldv<4>(p + i, v + i);
-  }
-}
 
 // ---- pass 1 of both directions: one workgroup per chunk item -> part[item][2C]
 // DIR == kInFwd: a = x - pivot, (sum a, sum a^2);  kInBwd: xhat = (x - mean) * rstd, (sum dy, sum dy * xhat)
@@ -318,15 +272,6 @@ __global__ __launch_bounds__(kNT) void k_in_apply(SegMap sm, const T *__restrict
   }
 }
 
-// lanes per row: enough 16-byte (or 1-element) accesses to cover the row once, at most a wave
-inline int lanes_log2(int c, int v) {
-  const int chunks = (c + v - 1) / v;
-  int lg = 0;
-  while ((1 << lg) < chunks && lg < 6) ++lg;
-  return lg;
-}
-inline bool al16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
-
 }  // namespace
 
 // Everything an instance-norm call decides on the host, from plain integers (no HIP call): the access width, the lanes per row,
@@ -346,7 +291,7 @@ InstNormPlan instnorm_plan(int dir, int64_t n_fine, int64_t n_seg, int64_t n_ite
   if (n_fine > 0 && n_seg > 0) {
     p.reduce_grid = n_items;
     p.combine_grid = n_seg * ((c + kInCombCh - 1) / kInCombCh);
-    p.apply_grid = (n_fine + p.rows_per_apply_block - 1) / p.rows_per_apply_block;
+    p.apply_grid = grid_for(n_fine, p.lanes_log2, kInApplyIters);
     if (dir == kInBwd && p.apply_grid < (c + kNT - 1) / kNT) p.apply_grid = (c + kNT - 1) / kNT;   // the dweight / dbias fold
   }
   return p;
@@ -411,11 +356,10 @@ int lgs_in_forward(lgs_segmap *h, const void *x, int c, const float *weight, con
   hipStream_t s = (hipStream_t)stream;
   if (segmap_wait(h, s)) return 1;
   const InstNormPlan p = instnorm_plan(kInFwd, sm.n_fine, sm.n_coarse, sm.n_items, c, dtype, al16(x) && al16(y) && al16(weight) && al16(bias) && al16(stats));
-  if (dtype == LGS_BF16)
-    return p.vec ? forward_t<bf16_t, true>(sm, p, x, c, weight, bias, eps, y, stats, workspace, s)
-                 : forward_t<bf16_t, false>(sm, p, x, c, weight, bias, eps, y, stats, workspace, s);
-  return p.vec ? forward_t<float, true>(sm, p, x, c, weight, bias, eps, y, stats, workspace, s)
-               : forward_t<float, false>(sm, p, x, c, weight, bias, eps, y, stats, workspace, s);
+  return with_row_type(dtype, p.vec, "lgs_in_forward", [&](auto e) {
+    using E = decltype(e);
+    return forward_t<typename E::T, E::vec>(sm, p, x, c, weight, bias, eps, y, stats, workspace, s);
+  });
 }
 
 int lgs_in_backward(lgs_segmap *h, const void *x, const void *dy, int c, const float *weight, const float *stats, void *dx,
@@ -432,11 +376,10 @@ int lgs_in_backward(lgs_segmap *h, const void *x, const void *dy, int c, const f
   LGS_REQUIRE(sm.row_seg && sm.item_seg, "lgs_in_backward: the segment map carries no row table");
   if (segmap_wait(h, s)) return 1;
   const InstNormPlan p = instnorm_plan(kInBwd, sm.n_fine, sm.n_coarse, sm.n_items, c, dtype, al16(x) && al16(dy) && al16(dx) && al16(weight) && al16(stats));
-  if (dtype == LGS_BF16)
-    return p.vec ? backward_t<bf16_t, true>(sm, p, x, dy, c, weight, stats, dx, dweight, dbias, workspace, s)
-                 : backward_t<bf16_t, false>(sm, p, x, dy, c, weight, stats, dx, dweight, dbias, workspace, s);
-  return p.vec ? backward_t<float, true>(sm, p, x, dy, c, weight, stats, dx, dweight, dbias, workspace, s)
-               : backward_t<float, false>(sm, p, x, dy, c, weight, stats, dx, dweight, dbias, workspace, s);
+  return with_row_type(dtype, p.vec, "lgs_in_backward", [&](auto e) {
+    using E = decltype(e);
+    return backward_t<typename E::T, E::vec>(sm, p, x, dy, c, weight, stats, dx, dweight, dbias, workspace, s);
+  });
 }
 
 // the plan of a call given by plain integers: no HIP call (tests/test_instnorm_cpu.py)

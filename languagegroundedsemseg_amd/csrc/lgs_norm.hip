@@ -7,65 +7,16 @@
 //
 // Pure HBM-bound streaming work: features are [N, C] row-major with C in
 // {32..512}; a thread owns a fixed group of 4 (fp32) or 8 (bf16) adjacent channels = one 16-byte
-// access and walks rows, so every wave instruction is a fully coalesced 1 KiB access.  Statistics
+// access (ldv / stv / stv_nt of lgs_rows.h, always at full width: C is a multiple of it) and walks rows,
+// so every wave instruction is a fully coalesced 1 KiB access.  Statistics
 // are reduced per block in LDS, then across blocks through a [blocks, 2C] fp32 scratch that a small fold
 // kernel sums in a fixed order (double accumulation) -> deterministic, no float atomics.
-#include "lgs_common.h"
+#include "lgs_rows.h"
 #include <algorithm>
 #include <atomic>
 #include <mutex>
 
 namespace lgs {
-
-__device__ inline float bf2f(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
-__device__ inline uint16_t f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
-template <typename T> struct Vec;
-template <> struct Vec<float> {
-  static constexpr int W = 4;
-  __device__ static void load(const float *p, float (&v)[4]) {
-    float4 x = *reinterpret_cast<const float4 *>(p);
-    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-  }
-  __device__ static void store(float *p, const float (&v)[4]) {
-    *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  }
-  __device__ static void store_nt(float *p, const float (&v)[4]) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    f4 x = {v[0], v[1], v[2], v[3]};
-    __builtin_nontemporal_store(x, reinterpret_cast<f4 *>(p));
-  }
-};
-template <> struct Vec<bf16_t> {
-  static constexpr int W = 8;
-  __device__ static void load(const bf16_t *p, float (&v)[8]) {
-    uint4 x = *reinterpret_cast<const uint4 *>(p);
-    uint32_t w[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { v[2 * i] = bf2f((uint16_t)(w[i] & 0xffff)); v[2 * i + 1] = bf2f((uint16_t)(w[i] >> 16)); }
-  }
-  __device__ static void store(bf16_t *p, const float (&v)[8]) {
-    uint4 x;
-    x.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-    x.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-    x.z = (uint32_t)f2bf(v[4]) | ((uint32_t)f2bf(v[5]) << 16);
-    x.w = (uint32_t)f2bf(v[6]) | ((uint32_t)f2bf(v[7]) << 16);
-    *reinterpret_cast<uint4 *>(p) = x;
-  }
-  __device__ static void store_nt(bf16_t *p, const float (&v)[8]) {
-    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-    u4 x;
-    x.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-    x.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-    x.z = (uint32_t)f2bf(v[4]) | ((uint32_t)f2bf(v[5]) << 16);
-    x.w = (uint32_t)f2bf(v[6]) | ((uint32_t)f2bf(v[7]) << 16);
-    __builtin_nontemporal_store(x, reinterpret_cast<u4 *>(p));
-  }
-};
 
 constexpr int kNT = 256;
 
@@ -80,7 +31,7 @@ __global__ __launch_bounds__(kNT) void k_colreduce(const T *__restrict__ x, cons
                                                    const float *__restrict__ stats, const float *__restrict__ gamma,
                                                    const float *__restrict__ beta, int64_t n, int c, int relu,
                                                    int64_t rows_per_block, float *__restrict__ scratch, int64_t dy_ld, int64_t y_ld) {
-  constexpr int W = Vec<T>::W;
+  constexpr int W = Width<T>::V;
   const int G = c / W;              // channel groups per row
   const int RL = kNT / G;           // rows in flight per block iteration (G <= 256)
   const int cg = threadIdx.x % G, rl = threadIdx.x / G;
@@ -98,7 +49,7 @@ __global__ __launch_bounds__(kNT) void k_colreduce(const T *__restrict__ x, cons
   } else {
     // forward statistics are accumulated about a per-channel pivot (row 0, the same for every block) so that
     // var = E[(x-k)^2] - E[x-k]^2 does not cancel catastrophically when |mean| >> std
-    if (n > 0) Vec<T>::load(x + cg * W, mean);
+    if (n > 0) ldv<W>(x + cg * W, mean);
   }
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
   const int64_t r1 = min(r0 + rows_per_block, n);
@@ -128,10 +79,10 @@ __global__ __launch_bounds__(kNT) void k_colreduce(const T *__restrict__ x, cons
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int64_t o = (r + u * RL) * c + cg * W;
-        Vec<T>::load(x + o, xv[u]);
+        ldv<W>(x + o, xv[u]);
         if (MODE == 1) {
-          Vec<T>::load(dy + (r + u * RL) * dy_ld + cg * W, gv[u]);
-          if (relu == 1) Vec<T>::load(y + (r + u * RL) * y_ld + cg * W, yv[u]);
+          ldv<W>(dy + (r + u * RL) * dy_ld + cg * W, gv[u]);
+          if (relu == 1) ldv<W>(y + (r + u * RL) * y_ld + cg * W, yv[u]);
         }
       }
 #pragma unroll
@@ -140,10 +91,10 @@ __global__ __launch_bounds__(kNT) void k_colreduce(const T *__restrict__ x, cons
     for (; r < r1; r += RL) {
       float xv[W], gv[W], yv[W];
       const int64_t o = r * c + cg * W;
-      Vec<T>::load(x + o, xv);
+      ldv<W>(x + o, xv);
       if (MODE == 1) {
-        Vec<T>::load(dy + r * dy_ld + cg * W, gv);
-        if (relu == 1) Vec<T>::load(y + r * y_ld + cg * W, yv);
+        ldv<W>(dy + r * dy_ld + cg * W, gv);
+        if (relu == 1) ldv<W>(y + r * y_ld + cg * W, yv);
       }
       accumulate(xv, gv, yv);
     }
@@ -299,7 +250,7 @@ __global__ __launch_bounds__(kNT) void k_bn_apply(const T *__restrict__ x, const
                                                   const float *__restrict__ gamma, const float *__restrict__ beta,
                                                   const float *__restrict__ stats, int relu, T *__restrict__ y, int64_t y_ld) {
   // y_ld = row stride of the output (elements): > c when y is a column slice of a wider buffer (zero-copy ME.cat)
-  constexpr int W = Vec<T>::W;
+  constexpr int W = Width<T>::V;
   const int G = c / W, RL = kNT / G;
   const int cg = threadIdx.x % G, rl = threadIdx.x / G;
   if (rl >= RL) return;
@@ -316,16 +267,16 @@ __global__ __launch_bounds__(kNT) void k_bn_apply(const T *__restrict__ x, const
     const int64_t r2 = r + stride;
     const bool two = r2 < n;
     float xa[W], xb[W], ra[W], rb[W];
-    Vec<T>::load(x + r * c + cg * W, xa);
-    if (two) Vec<T>::load(x + r2 * c + cg * W, xb);
-    if (res) { Vec<T>::load(res + r * c + cg * W, ra); if (two) Vec<T>::load(res + r2 * c + cg * W, rb); }
+    ldv<W>(x + r * c + cg * W, xa);
+    if (two) ldv<W>(x + r2 * c + cg * W, xb);
+    if (res) { ldv<W>(res + r * c + cg * W, ra); if (two) ldv<W>(res + r2 * c + cg * W, rb); }
 #pragma unroll
     for (int k = 0; k < W; ++k) {
       float o = (xa[k] - mean[k]) * sc[k] + bt[k];   // keep this exact expression: the backward recomputes the ReLU mask from it
       if (res) o += ra[k];
       xa[k] = (relu && o < 0.f) ? 0.f : o;
     }
-    Vec<T>::store_nt(y + r * y_ld + cg * W, xa);
+    stv_nt<W>(y + r * y_ld + cg * W, xa);
     if (two) {
 #pragma unroll
       for (int k = 0; k < W; ++k) {
@@ -333,7 +284,7 @@ __global__ __launch_bounds__(kNT) void k_bn_apply(const T *__restrict__ x, const
         if (res) o += rb[k];
         xb[k] = (relu && o < 0.f) ? 0.f : o;
       }
-      Vec<T>::store_nt(y + r2 * y_ld + cg * W, xb);
+      stv_nt<W>(y + r2 * y_ld + cg * W, xb);
     }
   }
 }
@@ -346,7 +297,7 @@ __global__ __launch_bounds__(kNT) void k_bn_bwd_apply(const T *__restrict__ x, c
                                                       const float *__restrict__ stats, const float *__restrict__ sums,
                                                       float inv_n, int relu, T *__restrict__ dx, T *__restrict__ dres,
                                                       int64_t dy_ld, const float *__restrict__ inv_n_dev, int64_t y_ld) {
-  constexpr int W = Vec<T>::W;
+  constexpr int W = Width<T>::V;
   const int G = c / W, RL = kNT / G;
   const int cg = threadIdx.x % G, rl = threadIdx.x / G;
   if (rl >= RL) return;
@@ -365,24 +316,24 @@ __global__ __launch_bounds__(kNT) void k_bn_bwd_apply(const T *__restrict__ x, c
   for (int64_t r = (int64_t)blockIdx.x * RL + rl; r < n; r += stride) {
     const int64_t o = r * c + cg * W;
     float xv[W], gv[W];
-    Vec<T>::load(x + o, xv);
-    Vec<T>::load(dy + r * dy_ld + cg * W, gv);
+    ldv<W>(x + o, xv);
+    ldv<W>(dy + r * dy_ld + cg * W, gv);
     if (relu == 1) {
       float yv[W];
-      Vec<T>::load(y + r * y_ld + cg * W, yv);
+      ldv<W>(y + r * y_ld + cg * W, yv);
 #pragma unroll
       for (int k = 0; k < W; ++k) gv[k] = yv[k] > 0.f ? gv[k] : 0.f;
     } else if (relu == 2) {
 #pragma unroll
       for (int k = 0; k < W; ++k) gv[k] = ((xv[k] - mean[k]) * sc[k] + bt[k]) > 0.f ? gv[k] : 0.f;  // same expression as k_bn_apply
     }
-    if (dres) Vec<T>::store_nt(dres + o, gv);
+    if (dres) stv_nt<W>(dres + o, gv);
 #pragma unroll
     for (int k = 0; k < W; ++k) {
       const float xh = (xv[k] - mean[k]) * istd[k];
       xv[k] = gi[k] * (gv[k] - m1[k] - xh * m2[k]);
     }
-    Vec<T>::store_nt(dx + o, xv);
+    stv_nt<W>(dx + o, xv);
   }
 }
 
@@ -445,7 +396,7 @@ __device__ inline void fold_sums_coh(const float *scratch, int nblocks, int c, i
 template <typename T, int MODE>
 __device__ inline void colreduce_slab(const T *x, const T *y, const T *dy, const float *stats, const float *gamma, const float *beta,
                                       int64_t n, int c, int relu, int64_t r0, int64_t r1, float *dst, int64_t dy_ld, int64_t y_ld) {
-  constexpr int W = Vec<T>::W;
+  constexpr int W = Width<T>::V;
   const int G = c / W, RL = kNT / G;
   const int cg = threadIdx.x % G, rl = threadIdx.x / G;
   const bool active = rl < RL;
@@ -460,7 +411,7 @@ __device__ inline void colreduce_slab(const T *x, const T *y, const T *dy, const
       gm[i] = relu == 2 ? gamma[cg * W + i] : 0.f; bt[i] = relu == 2 ? beta[cg * W + i] : 0.f;
     }
   } else {
-    if (n > 0) Vec<T>::load(x + cg * W, mean);   // pivot = row 0, as in k_colreduce<T, 0>
+    if (n > 0) ldv<W>(x + cg * W, mean);   // pivot = row 0, as in k_colreduce<T, 0>
   }
   if (active) {
     int64_t r = r0 + rl;
@@ -485,10 +436,10 @@ __device__ inline void colreduce_slab(const T *x, const T *y, const T *dy, const
       float xv[U][W], gv[U][W], yv[U][W];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        Vec<T>::load(x + (r + u * RL) * c + cg * W, xv[u]);
+        ldv<W>(x + (r + u * RL) * c + cg * W, xv[u]);
         if (MODE == 1) {
-          Vec<T>::load(dy + (r + u * RL) * dy_ld + cg * W, gv[u]);
-          if (relu == 1) Vec<T>::load(y + (r + u * RL) * y_ld + cg * W, yv[u]);
+          ldv<W>(dy + (r + u * RL) * dy_ld + cg * W, gv[u]);
+          if (relu == 1) ldv<W>(y + (r + u * RL) * y_ld + cg * W, yv[u]);
         }
       }
 #pragma unroll
@@ -496,10 +447,10 @@ __device__ inline void colreduce_slab(const T *x, const T *y, const T *dy, const
     }
     for (; r < r1; r += RL) {
       float xv[W], gv[W], yv[W];
-      Vec<T>::load(x + r * c + cg * W, xv);
+      ldv<W>(x + r * c + cg * W, xv);
       if (MODE == 1) {
-        Vec<T>::load(dy + r * dy_ld + cg * W, gv);
-        if (relu == 1) Vec<T>::load(y + r * y_ld + cg * W, yv);
+        ldv<W>(dy + r * dy_ld + cg * W, gv);
+        if (relu == 1) ldv<W>(y + r * y_ld + cg * W, yv);
       }
       accumulate(xv, gv, yv);
     }
@@ -524,7 +475,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(4))) void k
                                                       long long *nbt, float *stats, int relu, T *y, int64_t y_ld, float *scratch,
                                                       const float *partials, int partial_rows, int partial_rpb, int nfoldrows,
                                                       const float *pivot_ptr, int64_t rows_per_block, unsigned *ctr) {
-  constexpr int W = Vec<T>::W;
+  constexpr int W = Width<T>::V;
   const unsigned nwg = gridDim.x;
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
   const int64_t r1 = min(r0 + rows_per_block, n);
@@ -595,8 +546,8 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(4))) void k
     for (int u = 0; u < U; ++u) {
       const int64_t ru = r - (int64_t)u * RL;
       if (ru >= r0) {
-        Vec<T>::load(x + ru * c + cg * W, xv[u]);
-        if (res) Vec<T>::load(res + ru * c + cg * W, rv[u]);
+        ldv<W>(x + ru * c + cg * W, xv[u]);
+        if (res) ldv<W>(res + ru * c + cg * W, rv[u]);
       }
     }
 #pragma unroll
@@ -609,7 +560,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(4))) void k
           if (res) o += rv[u][k];
           xv[u][k] = (relu && o < 0.f) ? 0.f : o;
         }
-        Vec<T>::store(y + ru * y_ld + cg * W, xv[u]);
+        stv<W>(y + ru * y_ld + cg * W, xv[u]);
       }
     }
   }
@@ -620,7 +571,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(4))) void k
                                                       const float *beta, const float *stats, int relu, T *dx, T *dres, float *dgamma,
                                                       float *dbeta, float *scratch, float *sums, int64_t dy_ld, int64_t y_ld,
                                                       int64_t rows_per_block, float inv_n, unsigned *ctr) {
-  constexpr int W = Vec<T>::W;
+  constexpr int W = Width<T>::V;
   const unsigned nwg = gridDim.x;
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
   const int64_t r1 = min(r0 + rows_per_block, n);
@@ -662,9 +613,9 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(4))) void k
     for (int u = 0; u < U; ++u) {
       const int64_t ru = r - (int64_t)u * RL;
       if (ru >= r0) {
-        Vec<T>::load(x + ru * c + cg * W, xv[u]);
-        Vec<T>::load(dy + ru * dy_ld + cg * W, gv[u]);
-        if (relu == 1) Vec<T>::load(y + ru * y_ld + cg * W, yv[u]);
+        ldv<W>(x + ru * c + cg * W, xv[u]);
+        ldv<W>(dy + ru * dy_ld + cg * W, gv[u]);
+        if (relu == 1) ldv<W>(y + ru * y_ld + cg * W, yv[u]);
       }
     }
 #pragma unroll
@@ -678,13 +629,13 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(4))) void k
 #pragma unroll
           for (int k = 0; k < W; ++k) gv[u][k] = ((xv[u][k] - mean[k]) * sc[k] + bt[k]) > 0.f ? gv[u][k] : 0.f;
         }
-        if (dres) Vec<T>::store(dres + ru * c + cg * W, gv[u]);
+        if (dres) stv<W>(dres + ru * c + cg * W, gv[u]);
 #pragma unroll
         for (int k = 0; k < W; ++k) {
           const float xh = (xv[u][k] - mean[k]) * istd[k];
           xv[u][k] = gi[k] * (gv[u][k] - m1[k] - xh * m2[k]);
         }
-        Vec<T>::store(dx + ru * c + cg * W, xv[u]);
+        stv<W>(dx + ru * c + cg * W, xv[u]);
       }
     }
   }
@@ -738,14 +689,14 @@ __global__ __launch_bounds__(kNT) void k_bn_apply_fold(const T *__restrict__ x, 
                                                        long long *__restrict__ nbt, float *__restrict__ stats,
                                                        const float *__restrict__ scratch, int nparts, int relu, T *__restrict__ y,
                                                        int64_t y_ld) {
-  constexpr int W = Vec<T>::W;
+  constexpr int W = Width<T>::V;
   const int G = c / W, RL = kNT / G;
   const int cg = threadIdx.x % G, rl = threadIdx.x / G;
   double t0[W], t1[W];
   fold_in_block<W>(scratch, nparts, c, G, RL, cg, rl, t0, t1);
   if (rl >= RL) return;
   float piv[W], sc[W], mean[W], bt[W];
-  if (n > 0) Vec<T>::load(x + cg * W, piv);          // the pivot of k_colreduce<T, 0>: row 0
+  if (n > 0) ldv<W>(x + cg * W, piv);          // the pivot of k_colreduce<T, 0>: row 0
 #pragma unroll
   for (int k = 0; k < W; ++k) {
     const int ch = cg * W + k;
@@ -770,16 +721,16 @@ __global__ __launch_bounds__(kNT) void k_bn_apply_fold(const T *__restrict__ x, 
     const int64_t r2 = r + stride;
     const bool two = r2 < n;
     float xa[W], xb[W], ra[W], rb[W];
-    Vec<T>::load(x + r * c + cg * W, xa);
-    if (two) Vec<T>::load(x + r2 * c + cg * W, xb);
-    if (res) { Vec<T>::load(res + r * c + cg * W, ra); if (two) Vec<T>::load(res + r2 * c + cg * W, rb); }
+    ldv<W>(x + r * c + cg * W, xa);
+    if (two) ldv<W>(x + r2 * c + cg * W, xb);
+    if (res) { ldv<W>(res + r * c + cg * W, ra); if (two) ldv<W>(res + r2 * c + cg * W, rb); }
 #pragma unroll
     for (int k = 0; k < W; ++k) {
       float o = (xa[k] - mean[k]) * sc[k] + bt[k];   // the exact expression of k_bn_apply (the backward recomputes the mask from it)
       if (res) o += ra[k];
       xa[k] = (relu && o < 0.f) ? 0.f : o;
     }
-    Vec<T>::store(y + r * y_ld + cg * W, xa);
+    stv<W>(y + r * y_ld + cg * W, xa);
     if (two) {
 #pragma unroll
       for (int k = 0; k < W; ++k) {
@@ -787,7 +738,7 @@ __global__ __launch_bounds__(kNT) void k_bn_apply_fold(const T *__restrict__ x, 
         if (res) o += rb[k];
         xb[k] = (relu && o < 0.f) ? 0.f : o;
       }
-      Vec<T>::store(y + r2 * y_ld + cg * W, xb);
+      stv<W>(y + r2 * y_ld + cg * W, xb);
     }
   }
 }
@@ -799,7 +750,7 @@ __global__ __launch_bounds__(kNT) void k_bn_bwd_apply_fold(const T *__restrict__
                                                            const float *__restrict__ scratch, int nparts, float inv_n, int relu,
                                                            T *__restrict__ dx, T *__restrict__ dres, float *__restrict__ dgamma,
                                                            float *__restrict__ dbeta, int64_t dy_ld, int64_t y_ld) {
-  constexpr int W = Vec<T>::W;
+  constexpr int W = Width<T>::V;
   const int G = c / W, RL = kNT / G;
   const int cg = threadIdx.x % G, rl = threadIdx.x / G;
   double t0[W], t1[W];
@@ -821,24 +772,24 @@ __global__ __launch_bounds__(kNT) void k_bn_bwd_apply_fold(const T *__restrict__
   for (int64_t r = (int64_t)blockIdx.x * RL + rl; r < n; r += stride) {
     const int64_t o = r * c + cg * W;
     float xv[W], gv[W];
-    Vec<T>::load(x + o, xv);
-    Vec<T>::load(dy + r * dy_ld + cg * W, gv);
+    ldv<W>(x + o, xv);
+    ldv<W>(dy + r * dy_ld + cg * W, gv);
     if (relu == 1) {
       float yv[W];
-      Vec<T>::load(y + r * y_ld + cg * W, yv);
+      ldv<W>(y + r * y_ld + cg * W, yv);
 #pragma unroll
       for (int k = 0; k < W; ++k) gv[k] = yv[k] > 0.f ? gv[k] : 0.f;
     } else if (relu == 2) {
 #pragma unroll
       for (int k = 0; k < W; ++k) gv[k] = ((xv[k] - mean[k]) * sc[k] + bt[k]) > 0.f ? gv[k] : 0.f;  // same expression as k_bn_apply
     }
-    if (dres) Vec<T>::store(dres + o, gv);
+    if (dres) stv<W>(dres + o, gv);
 #pragma unroll
     for (int k = 0; k < W; ++k) {
       const float xh = (xv[k] - mean[k]) * istd[k];
       xv[k] = gi[k] * (gv[k] - m1[k] - xh * m2[k]);
     }
-    Vec<T>::store(dx + o, xv);
+    stv<W>(dx + o, xv);
   }
 }
 
@@ -996,22 +947,15 @@ inline int fused_resident(const void *kernel) {
 }
 
 template <typename T> constexpr int dtype_of() { return sizeof(T) == 2 ? LGS_BF16 : LGS_F32; }
-// the element type of a call: its void pointers as T
-template <typename T> struct Elem {
-  static const T *in(const void *p) { return reinterpret_cast<const T *>(p); }
-  static T *out(void *p) { return reinterpret_cast<T *>(p); }
-};
-// dtype -> f(Elem<T>()), behind the family's one dtype and channel-count check
+// dtype -> f(RowType<T, true>()): the family takes 16-byte accesses only, so its channel-count check sits on the shared lift
 template <typename F>
 int with_elem(int dtype, int c, const char *who, F &&f) {
-  LGS_REQUIRE(dtype == LGS_F32 || dtype == LGS_BF16, std::string(who) + ": unknown dtype");
-  LGS_REQUIRE(c % epl(dtype) == 0 && c / epl(dtype) <= kNT && c <= 2048, std::string(who) + ": channel count unsupported");
-  return dtype == LGS_F32 ? f(Elem<float>()) : f(Elem<bf16_t>());
+  return with_row_type(dtype, true, who, [&](auto e) {
+    LGS_REQUIRE(c % epl(dtype) == 0 && c / epl(dtype) <= kNT && c <= 2048, std::string(who) + ": channel count unsupported");
+    return f(e);
+  });
 }
 // row stride of a [n, c] operand that may be a column slice of a wider row-major buffer: 0 = c; rows must start 16-byte aligned
-inline bool stride_ok(const void *p, int64_t ld, int c, int dtype) {
-  return ld >= c && ld % epl(dtype) == 0 && (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
-}
 #define LGS_BN_STRIDE(who, p, row_stride, ld)                \
   const int64_t ld = (row_stride) > 0 ? (row_stride) : c;    \
   LGS_REQUIRE(!(p) || stride_ok(p, ld, c, dtype), who ": " #p " rows must start 16-byte aligned (row stride a multiple of 16 bytes)")
@@ -1097,7 +1041,7 @@ int bn_stats_t(const T *x, int64_t n, int c, float *mean_m2, void *workspace, hi
 template <typename T>
 int bn_apply_t(const T *x, int64_t n, int c, const float *gamma, const float *beta, const float *stats, const T *res, int relu, T *y, hipStream_t s,
                int64_t y_ld) {
-  const int grid = apply_blocks(n, c, Vec<T>::W, 1, kApplyMaxBlocks);
+  const int grid = apply_blocks(n, c, Width<T>::V, 1, kApplyMaxBlocks);
   if (grid) LGS_KLAUNCH((k_bn_apply<T>), grid, kNT, 0, s, x, res, n, c, gamma, beta, stats, relu, y, y_ld);
   LGS_HIP(hipGetLastError());
   return 0;
@@ -1115,7 +1059,7 @@ int bn_bwd_reduce_t(const T *x, const T *y, const T *dy, int64_t n, int c, const
 template <typename T>
 int bn_bwd_apply_t(const T *x, const T *y, const T *dy, int64_t n, int c, const float *gamma, const float *beta, const float *stats, const float *sums,
                    float inv_n_total, const float *inv_n_dev, int relu, T *dx, T *dres, hipStream_t s, int64_t dy_ld, int64_t y_ld) {
-  const int grid = apply_blocks(n, c, Vec<T>::W, 1, kApplyMaxBlocks);
+  const int grid = apply_blocks(n, c, Width<T>::V, 1, kApplyMaxBlocks);
   if (grid) LGS_KLAUNCH((k_bn_bwd_apply<T>), grid, kNT, 0, s, x, y, dy, n, c, gamma, beta, stats, sums, inv_n_total, relu, dx, dres, dy_ld, inv_n_dev, y_ld);
   LGS_HIP(hipGetLastError());
   return 0;

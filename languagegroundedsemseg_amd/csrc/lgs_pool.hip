@@ -14,8 +14,9 @@
 //   k_seg_bcast    fine-stationary: copy / divide by the segment's row count / add / multiply, or a plain row copy (concat)
 //   k_seg_max_bwd  fine-stationary: dx[row][c] = (argmax[q][c] == row) ? dy[q][c] : 0
 // A group of 2^lg lanes owns one row; every lane moves 16 bytes per access (8 bf16 / 4 fp32) when the channel count and
-// the row strides allow it, one element otherwise (C % 8 != 0, e.g. C = 3).
-#include "lgs_common.h"
+// the row strides allow it, one element otherwise (C % 8 != 0, e.g. C = 3): the accesses, that rule and the lift from
+// (dtype, width, op) to template arguments are lgs_rows.h's.  Everything a call decides on the host comes from seg_plan().
+#include "lgs_rows.h"
 
 #include <climits>
 
@@ -24,46 +25,6 @@ namespace {
 
 enum { R_SUM = 0, R_AVG = 1, R_MAX = 2, R_PROD = 3 };
 enum { B_COPY = 0, B_SCALE = 1, B_ADD = 2, B_MUL = 3, B_COPYX = 4 };
-
-template <typename T, bool VEC> struct Width { static constexpr int V = VEC ? (int)(16 / sizeof(T)) : 1; };
-
-template <int V> __device__ inline void ldv(const float *p, float *v) {
-  if constexpr (V == 4) {
-    const float4 a = *reinterpret_cast<const float4 *>(p);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  } else {
-    v[0] = *p;
-  }
-}
-template <int V> __device__ inline void ldv(const bf16_t *p, float *v) {
-  if constexpr (V == 8) {
-    const uint4 a = *reinterpret_cast<const uint4 *>(p);
-    const uint32_t w[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[2 * i] = __uint_as_float(w[i] << 16);
-      v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  } else {
-    v[0] = bf16_to_f32(*p);
-  }
-}
-template <int V> __device__ inline void stv(float *p, const float *v) {
-  if constexpr (V == 4) *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else *p = v[0];
-}
-template <int V> __device__ inline void stv(bf16_t *p, const float *v) {
-  if constexpr (V == 8) {
-    uint32_t w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = (uint32_t)f32_to_bf16(v[2 * i]) | ((uint32_t)f32_to_bf16(v[2 * i + 1]) << 16);
-    *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-  } else {
-    *p = f32_to_bf16(v[0]);
-  }
-}
-__device__ inline void st1(float *p, float v) { *p = v; }
-__device__ inline void st1(bf16_t *p, float v) { *p = f32_to_bf16(v); }
 
 template <int OP, int V> __device__ inline void acc_init(float *acc, int32_t *arg) {
 #pragma unroll
@@ -176,7 +137,7 @@ __global__ __launch_bounds__(256) void k_seg_combine(SegMap sm, const float *__r
       }
     }
     if constexpr (OP == R_AVG) acc = acc / (float)(sm.seg_start[q + 1] - sm.seg_start[q]);
-    st1(out + q * c + col, acc);
+    stv<1>(out + q * c + col, &acc);
     if constexpr (OP == R_MAX) amax[q * c + col] = arg;
   }
 }
@@ -229,79 +190,72 @@ __global__ __launch_bounds__(256) void k_seg_max_bwd(SegMap sm, const T *__restr
   }
 }
 
-// lanes per row: enough 16-byte (or 1-element) accesses to cover the row once, at most a wave
-inline int lanes_log2(int c, int v) {
-  const int chunks = (c + v - 1) / v;
-  int lg = 0;
-  while ((1 << lg) < chunks && lg < 6) ++lg;
-  return lg;
-}
-inline unsigned grid_for(int64_t units, int lg) {
-  const int64_t threads = units << lg;
-  return (unsigned)((threads + 255) / 256 > 0 ? (threads + 255) / 256 : 1);
-}
-inline bool al16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
-template <typename T, bool VEC>
-int reduce_t(const SegMap &sm, int op, const void *xv, const void *x2v, int64_t x_ld, int c, void *outv, int32_t *amax, void *ws,
-             hipStream_t s) {
-  const T *x = (const T *)xv, *x2 = (const T *)x2v;
-  T *out = (T *)outv;
-  const int lg = lanes_log2(c, Width<T, VEC>::V);
-  if (sm.single_pass()) {
-    const unsigned g = grid_for(sm.n_coarse, lg);
-    const int64_t u = sm.n_coarse;
-    if (op == R_SUM) LGS_KLAUNCH((k_seg_reduce<T, VEC, R_SUM, false>), g, 256, 0, s, sm, x, x2, x_ld, c, lg, u, out, amax, nullptr, nullptr);
-    else if (op == R_AVG) LGS_KLAUNCH((k_seg_reduce<T, VEC, R_AVG, false>), g, 256, 0, s, sm, x, x2, x_ld, c, lg, u, out, amax, nullptr, nullptr);
-    else if (op == R_MAX) LGS_KLAUNCH((k_seg_reduce<T, VEC, R_MAX, false>), g, 256, 0, s, sm, x, x2, x_ld, c, lg, u, out, amax, nullptr, nullptr);
-    else LGS_KLAUNCH((k_seg_reduce<T, VEC, R_PROD, false>), g, 256, 0, s, sm, x, x2, x_ld, c, lg, u, out, amax, nullptr, nullptr);
-    LGS_HIP(hipGetLastError());
-    return 0;
-  }
-  float *part = (float *)ws;
-  int32_t *pam = (int32_t *)((char *)ws + align256(sm.n_items * (int64_t)c * 4));
-  const unsigned g = grid_for(sm.n_items, lg);
-  const int64_t u = sm.n_items;
-  const int lgc = lanes_log2(c, 1);
-  const unsigned gc = grid_for(sm.n_coarse, lgc);
-  if (op == R_SUM) {
-    LGS_KLAUNCH((k_seg_reduce<T, VEC, R_SUM, true>), g, 256, 0, s, sm, x, x2, x_ld, c, lg, u, out, amax, part, pam);
-    LGS_KLAUNCH((k_seg_combine<T, R_SUM>), gc, 256, 0, s, sm, part, pam, c, lgc, out, amax);
-  } else if (op == R_AVG) {
-    LGS_KLAUNCH((k_seg_reduce<T, VEC, R_AVG, true>), g, 256, 0, s, sm, x, x2, x_ld, c, lg, u, out, amax, part, pam);
-    LGS_KLAUNCH((k_seg_combine<T, R_AVG>), gc, 256, 0, s, sm, part, pam, c, lgc, out, amax);
-  } else if (op == R_MAX) {
-    LGS_KLAUNCH((k_seg_reduce<T, VEC, R_MAX, true>), g, 256, 0, s, sm, x, x2, x_ld, c, lg, u, out, amax, part, pam);
-    LGS_KLAUNCH((k_seg_combine<T, R_MAX>), gc, 256, 0, s, sm, part, pam, c, lgc, out, amax);
+}  // namespace
+
+// Everything a pooling / broadcast call decides on the host, from plain integers (no HIP call): the access width, the lanes per
+// row, the grids of the family's launches and the two-pass reduction's workspace regions.  `vec_ok`: every operand the call
+// dereferences passes stride_ok (rows_ok over the entry point's list).  lgs_debug_seg_plan returns it without a GPU.
+using SegPlan = lgs_seg_plan_info;
+enum SegFamily { kSegReduce = 0, kSegBcast = 1, kSegMaxBwd = 2 };
+SegPlan seg_plan(int family, int64_t n_fine, int64_t n_coarse, int64_t n_items, bool single_pass, int c, int dtype, bool vec_ok) {
+  SegPlan p = {};
+  const int es = esize(dtype);
+  p.vec = vec_ok && (c * es) % 16 == 0 ? 1 : 0;
+  p.lanes_log2 = lanes_log2(c, p.vec ? 16 / es : 1);
+  p.combine_lanes_log2 = lanes_log2(c, 1);
+  if (family == kSegReduce) {
+    p.reduce_grid = grid_for(single_pass ? n_coarse : n_items, p.lanes_log2);
+    if (!single_pass) {   // chunk items -> fp32 partials (+ their arg-max rows), folded per segment by k_seg_combine
+      p.combine_grid = grid_for(n_coarse, p.combine_lanes_log2);
+      int64_t used = 0;
+      p.partials = take_region(used, n_items * (int64_t)c * 4);
+      p.partial_argmax = take_region(used, n_items * (int64_t)c * 4);
+      p.bytes_total = used;
+    }
+  } else if (family == kSegBcast) {
+    p.bcast_grid = grid_for(n_fine, p.lanes_log2);
   } else {
-    LGS_KLAUNCH((k_seg_reduce<T, VEC, R_PROD, true>), g, 256, 0, s, sm, x, x2, x_ld, c, lg, u, out, amax, part, pam);
-    LGS_KLAUNCH((k_seg_combine<T, R_SUM>), gc, 256, 0, s, sm, part, pam, c, lgc, out, amax);
+    p.max_bwd_grid = grid_for(n_fine, p.lanes_log2);
+  }
+  p.workspace_bytes = single_pass ? 0 : 2 * align256(n_items * (int64_t)c * 4);   // of the map and c alone: every op, both dtypes
+  return p;
+}
+
+namespace {
+
+template <typename T, bool VEC, int OP>
+int reduce_t(const SegMap &sm, const SegPlan &p, const T *x, const T *x2, int64_t x_ld, int c, T *out, int32_t *amax, void *ws, hipStream_t s) {
+  const unsigned g = (unsigned)p.reduce_grid;
+  if (sm.single_pass()) {
+    LGS_KLAUNCH((k_seg_reduce<T, VEC, OP, false>), g, 256, 0, s, sm, x, x2, x_ld, c, p.lanes_log2, sm.n_coarse, out, amax, nullptr, nullptr);
+  } else {
+    constexpr int COMBINE = OP == R_PROD ? R_SUM : OP;   // the partials of a sum of products are sums
+    float *part = (float *)((char *)ws + p.partials.offset);
+    int32_t *pam = (int32_t *)((char *)ws + p.partial_argmax.offset);
+    LGS_KLAUNCH((k_seg_reduce<T, VEC, OP, true>), g, 256, 0, s, sm, x, x2, x_ld, c, p.lanes_log2, sm.n_items, out, amax, part, pam);
+    LGS_KLAUNCH((k_seg_combine<T, COMBINE>), (unsigned)p.combine_grid, 256, 0, s, sm, part, pam, c, p.combine_lanes_log2, out, amax);
   }
   LGS_HIP(hipGetLastError());
   return 0;
 }
 
-template <typename T, bool VEC>
-int bcast_t(const SegMap &sm, int op, const void *gv, int c, const void *xv, int64_t x_ld, void *outv, int64_t out_ld, hipStream_t s) {
-  const T *g = (const T *)gv, *x = (const T *)xv;
-  T *out = (T *)outv;
-  const int lg = lanes_log2(c, Width<T, VEC>::V);
-  const unsigned gr = grid_for(sm.n_fine, lg);
-  if (op == B_COPY) LGS_KLAUNCH((k_seg_bcast<T, VEC, B_COPY>), gr, 256, 0, s, sm, g, x, x_ld, c, lg, out, out_ld);
-  else if (op == B_SCALE) LGS_KLAUNCH((k_seg_bcast<T, VEC, B_SCALE>), gr, 256, 0, s, sm, g, x, x_ld, c, lg, out, out_ld);
-  else if (op == B_ADD) LGS_KLAUNCH((k_seg_bcast<T, VEC, B_ADD>), gr, 256, 0, s, sm, g, x, x_ld, c, lg, out, out_ld);
-  else if (op == B_MUL) LGS_KLAUNCH((k_seg_bcast<T, VEC, B_MUL>), gr, 256, 0, s, sm, g, x, x_ld, c, lg, out, out_ld);
-  else LGS_KLAUNCH((k_seg_bcast<T, VEC, B_COPYX>), gr, 256, 0, s, sm, g, x, x_ld, c, lg, out, out_ld);
+template <typename T, bool VEC, int OP>
+int bcast_t(const SegMap &sm, const SegPlan &p, const T *g, int c, const T *x, int64_t x_ld, T *out, int64_t out_ld, hipStream_t s) {
+  LGS_KLAUNCH((k_seg_bcast<T, VEC, OP>), (unsigned)p.bcast_grid, 256, 0, s, sm, g, x, x_ld, c, p.lanes_log2, out, out_ld);
   LGS_HIP(hipGetLastError());
   return 0;
 }
 
 template <typename T, bool VEC>
-int max_bwd_t(const SegMap &sm, const void *dy, const int32_t *amax, int c, void *dx, hipStream_t s) {
-  const int lg = lanes_log2(c, Width<T, VEC>::V);
-  LGS_KLAUNCH((k_seg_max_bwd<T, VEC>), grid_for(sm.n_fine, lg), 256, 0, s, sm, (const T *)dy, amax, c, lg, (T *)dx);
+int max_bwd_t(const SegMap &sm, const SegPlan &p, const T *dy, const int32_t *amax, int c, T *dx, hipStream_t s) {
+  LGS_KLAUNCH((k_seg_max_bwd<T, VEC>), (unsigned)p.max_bwd_grid, 256, 0, s, sm, dy, amax, c, p.lanes_log2, dx);
   LGS_HIP(hipGetLastError());
   return 0;
+}
+
+SegPlan plan_of(int family, const SegMap &sm, int c, int dtype, bool vec_ok) {
+  return seg_plan(family, sm.n_fine, sm.n_coarse, sm.n_items, sm.single_pass(), c, dtype, vec_ok);
 }
 
 }  // namespace
@@ -312,10 +266,12 @@ using namespace lgs;
 extern "C" {
 
 int64_t lgs_seg_workspace_bytes(const lgs_segmap *h, int c) {
-  if (!h || c <= 0 || h->sm.single_pass()) return 0;
-  return 2 * align256(h->sm.n_items * (int64_t)c * 4);
+  if (!h || c <= 0) return 0;
+  return plan_of(kSegReduce, h->sm, c, LGS_F32, true).workspace_bytes;
 }
 
+// Each entry point lists the operands it dereferences (pointer, row stride in elements); rows_ok over that list is the one
+// rule for 16-byte accesses.  Contiguous operands carry the stride c.
 int lgs_seg_reduce(lgs_segmap *h, int op, const void *x, const void *x2, int64_t x_ld, int c, void *out, int32_t *argmax,
                    int dtype, void *workspace, void *stream) {
   LGS_REQUIRE(h && c > 0 && (dtype == LGS_F32 || dtype == LGS_BF16), "lgs_seg_reduce: bad argument");
@@ -329,13 +285,14 @@ int lgs_seg_reduce(lgs_segmap *h, int op, const void *x, const void *x2, int64_t
   LGS_REQUIRE(sm.single_pass() || workspace, "lgs_seg_reduce: this map needs lgs_seg_workspace_bytes of workspace");
   hipStream_t s = (hipStream_t)stream;
   if (segmap_wait(h, s)) return 1;
-  const int es = esize(dtype), v = 16 / es;
-  const bool vec = c % v == 0 && (x_ld * es) % 16 == 0 && al16(x) && al16(out) && (op != R_PROD || al16(x2));
-  if (dtype == LGS_BF16)
-    return vec ? reduce_t<bf16_t, true>(sm, op, x, x2, x_ld, c, out, argmax, workspace, s)
-               : reduce_t<bf16_t, false>(sm, op, x, x2, x_ld, c, out, argmax, workspace, s);
-  return vec ? reduce_t<float, true>(sm, op, x, x2, x_ld, c, out, argmax, workspace, s)
-             : reduce_t<float, false>(sm, op, x, x2, x_ld, c, out, argmax, workspace, s);
+  const bool vec_ok = op == R_PROD ? rows_ok({{x, x_ld}, {out, c}, {x2, x_ld}}, c, dtype) : rows_ok({{x, x_ld}, {out, c}}, c, dtype);
+  const SegPlan p = plan_of(kSegReduce, sm, c, dtype, vec_ok);
+  return with_row_type(dtype, p.vec, "lgs_seg_reduce", [&](auto e) {
+    using E = decltype(e);
+    return with_op<R_PROD + 1>(op, [&](auto o) {
+      return reduce_t<typename E::T, E::vec, decltype(o)::value>(sm, p, e.in(x), e.in(x2), x_ld, c, e.out(out), argmax, workspace, s);
+    });
+  });
 }
 
 int lgs_seg_broadcast(lgs_segmap *h, int op, const void *g, int c, const void *x, int64_t x_ld, void *out, int64_t out_ld, int dtype,
@@ -350,12 +307,16 @@ int lgs_seg_broadcast(lgs_segmap *h, int op, const void *g, int c, const void *x
   LGS_REQUIRE(out && (op == B_COPYX || g) && (!needs_x || x), "lgs_seg_broadcast: null feature pointer");
   hipStream_t s = (hipStream_t)stream;
   if (segmap_wait(h, s)) return 1;
-  const int es = esize(dtype), v = 16 / es;
-  const bool vec = c % v == 0 && (out_ld * es) % 16 == 0 && al16(out) && (op == B_COPYX || al16(g)) &&
-                   (!needs_x || ((x_ld * es) % 16 == 0 && al16(x)));
-  if (dtype == LGS_BF16)
-    return vec ? bcast_t<bf16_t, true>(sm, op, g, c, x, x_ld, out, out_ld, s) : bcast_t<bf16_t, false>(sm, op, g, c, x, x_ld, out, out_ld, s);
-  return vec ? bcast_t<float, true>(sm, op, g, c, x, x_ld, out, out_ld, s) : bcast_t<float, false>(sm, op, g, c, x, x_ld, out, out_ld, s);
+  const bool vec_ok = op == B_COPYX ? rows_ok({{out, out_ld}, {x, x_ld}}, c, dtype)
+                      : needs_x     ? rows_ok({{out, out_ld}, {g, c}, {x, x_ld}}, c, dtype)
+                                    : rows_ok({{out, out_ld}, {g, c}}, c, dtype);
+  const SegPlan p = plan_of(kSegBcast, sm, c, dtype, vec_ok);
+  return with_row_type(dtype, p.vec, "lgs_seg_broadcast", [&](auto e) {
+    using E = decltype(e);
+    return with_op<B_COPYX + 1>(op, [&](auto o) {
+      return bcast_t<typename E::T, E::vec, decltype(o)::value>(sm, p, e.in(g), c, e.in(x), x_ld, e.out(out), out_ld, s);
+    });
+  });
 }
 
 int lgs_seg_max_backward(lgs_segmap *h, const void *dy, const int32_t *argmax, int c, void *dx, int dtype, void *stream) {
@@ -365,16 +326,26 @@ int lgs_seg_max_backward(lgs_segmap *h, const void *dy, const int32_t *argmax, i
   LGS_REQUIRE(dy && argmax && dx, "lgs_seg_max_backward: null pointer");
   hipStream_t s = (hipStream_t)stream;
   if (segmap_wait(h, s)) return 1;
-  const int es = esize(dtype), v = 16 / es;
-  const bool vec = c % v == 0 && al16(dy) && al16(dx);
-  if (dtype == LGS_BF16) return vec ? max_bwd_t<bf16_t, true>(sm, dy, argmax, c, dx, s) : max_bwd_t<bf16_t, false>(sm, dy, argmax, c, dx, s);
-  return vec ? max_bwd_t<float, true>(sm, dy, argmax, c, dx, s) : max_bwd_t<float, false>(sm, dy, argmax, c, dx, s);
+  const SegPlan p = plan_of(kSegMaxBwd, sm, c, dtype, rows_ok({{dy, c}, {dx, c}}, c, dtype));
+  return with_row_type(dtype, p.vec, "lgs_seg_max_backward", [&](auto e) {
+    using E = decltype(e);
+    return max_bwd_t<typename E::T, E::vec>(sm, p, e.in(dy), argmax, c, e.out(dx), s);
+  });
 }
 
 int lgs_segmap_size(const lgs_segmap *h, int64_t *n_fine, int64_t *n_coarse) {
   LGS_REQUIRE(h, "lgs_segmap_size: null handle");
   if (n_fine) *n_fine = h->sm.n_fine;
   if (n_coarse) *n_coarse = h->sm.n_coarse;
+  return 0;
+}
+
+// the plan of a call given by plain integers: no HIP call (tests/test_seg_plan_cpu.py)
+int lgs_debug_seg_plan(const lgs_seg_plan_query *q, lgs_seg_plan_info *out) {
+  LGS_REQUIRE(q && out && q->c > 0 && (q->dtype == LGS_F32 || q->dtype == LGS_BF16) && q->family >= kSegReduce && q->family <= kSegMaxBwd &&
+                  q->n_fine >= 0 && q->n_coarse >= 0 && q->n_items >= 0,
+              "lgs_debug_seg_plan: bad argument");
+  *out = seg_plan(q->family, q->n_fine, q->n_coarse, q->n_items, q->single_pass != 0, q->c, q->dtype, q->vec_ok != 0);
   return 0;
 }
 

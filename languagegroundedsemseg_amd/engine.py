@@ -92,6 +92,20 @@ class InstNormPlanInfo(ctypes.Structure):
                [("bytes_total", ctypes.c_int64), ("workspace_bytes", ctypes.c_int64)]
 
 
+class SegPlanQuery(ctypes.Structure):
+    """lgs_seg_plan_query"""
+    _fields_ = [(n, ctypes.c_int) for n in ("family", "c", "dtype", "single_pass", "vec_ok")] + \
+               [(n, ctypes.c_int64) for n in ("n_fine", "n_coarse", "n_items")]
+
+
+class SegPlanInfo(ctypes.Structure):
+    """lgs_seg_plan_info: what lgs_debug_seg_plan answers (no GPU needed)"""
+    _fields_ = [(n, ctypes.c_int) for n in ("vec", "lanes_log2", "combine_lanes_log2")] + \
+               [(n, ctypes.c_int64) for n in ("reduce_grid", "combine_grid", "bcast_grid", "max_bwd_grid")] + \
+               [(n, ConvPlanRegion) for n in ("partials", "partial_argmax")] + \
+               [("bytes_total", ctypes.c_int64), ("workspace_bytes", ctypes.c_int64)]
+
+
 class KmapRelationQuery(ctypes.Structure):
     """lgs_kmap_relation_query"""
     _fields_ = [(n, ctypes.c_int) for n in ("entry", "ks", "dilation", "link", "tensor_stride", "out_sorted", "in_origin", "out_origin")]
@@ -163,7 +177,7 @@ _lib = None
 EXPORTS = [
     "lgs_abi_version", "lgs_last_error",
     "lgs_tuning_set", "lgs_tuning_get", "lgs_tuning_describe", "lgs_debug_dispatch_counts", "lgs_debug_conv_plan", "lgs_debug_wgrad_plan",
-    "lgs_debug_norm_plan", "lgs_debug_instnorm_plan", "lgs_debug_kmap_relation",
+    "lgs_debug_norm_plan", "lgs_debug_instnorm_plan", "lgs_debug_seg_plan", "lgs_debug_kmap_relation",
     "lgs_manager_create", "lgs_manager_destroy", "lgs_manager_insert", "lgs_manager_stride2", "lgs_manager_check",
     "lgs_manager_parent_of", "lgs_manager_map_size", "lgs_manager_get_coords", "lgs_manager_kernel_map", "lgs_manager_kernel_map_ex",
     "lgs_kmap_export",
@@ -240,6 +254,7 @@ def lib():
         "lgs_debug_wgrad_plan": [ctypes.POINTER(WgradPlanQuery), ctypes.POINTER(WgradPlanInfo)],
         "lgs_debug_norm_plan": [ctypes.POINTER(NormPlanQuery), ctypes.POINTER(NormPlanInfo)],
         "lgs_debug_instnorm_plan": [ctypes.POINTER(InstNormPlanQuery), ctypes.POINTER(InstNormPlanInfo)],
+        "lgs_debug_seg_plan": [ctypes.POINTER(SegPlanQuery), ctypes.POINTER(SegPlanInfo)],
         "lgs_debug_kmap_relation": [ctypes.POINTER(KmapRelationQuery), ctypes.POINTER(KmapRelationInfo)],
         "lgs_conv_bn_partial_rows": [vp, ci, ci, ci],
         "lgs_conv_dgrad": [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, vp],

@@ -389,6 +389,13 @@ class HipSegmentMap:
     def __init__(self, mgr, handle, fine_key, coarse_key):
         self.mgr, self.h, self.fine_key, self.coarse_key = mgr, handle, fine_key, coarse_key
         self.n_fine, self.n_coarse = mgr.map_size(fine_key), mgr.map_size(coarse_key)
+        self._wsb = {}            # lgs_seg_workspace_bytes per c: a function of the map and c alone (no knob feeds it)
+
+    def _ws_bytes(self, L, c):
+        b = self._wsb.get(c)
+        if b is None:
+            b = self._wsb[c] = L.lgs_seg_workspace_bytes(self.h, c)
+        return b
 
 
 class HipManager:
@@ -588,7 +595,7 @@ class HipBackend:
         with _dev(x.device):
             out = torch.empty((sm.n_coarse, c), dtype=x.dtype, device=x.device)
             amax = torch.empty((sm.n_coarse, c), dtype=torch.int32, device=x.device) if op == "max" else None
-            wsb = L.lgs_seg_workspace_bytes(sm.h, c)
+            wsb = sm._ws_bytes(L, c)
             ws = _ws(wsb, x.device) if wsb > 0 else None
             engine.check(L.lgs_seg_reduce(sm.h, self.POOL_OPS[op], _ptr(x), _ptr(x2), max(x.stride(0), c), c, _ptr(out), _ptr(amax),
                                           dt, _ptr(ws), _stream()))

@@ -425,3 +425,60 @@ def test_at_size_bf16_pooling_is_deterministic_and_host_sync_free():
     dyr = dy1.double()[inv]
     want = dyr[idx] + max_backward(dyr, max_argrow(fd, idx, m), n) + (dy2.double() / torch.bincount(bidx).view(-1, 1))[bidx]
     assert float((grad.double() - want).abs().max() / want.abs().max()) < 2e-2
+
+
+@PARITY
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_misaligned_column_slice_takes_the_element_path_and_gives_the_same_bits(dtype):
+    """the one alignment rule of the three entry points (csrc/lgs_rows.h rows_ok): x as a column slice of a wider buffer whose
+    row stride is not a multiple of 16 bytes and whose start is misaligned goes through one-element accesses, the same data
+    contiguous through 16-byte ones.  About 1 400 rows in 2 scenes, c = 8: the origin map reduces in two passes (a scene holds
+    more than 512 rows), the stride-2 map in one.  Both meet the float64 reference, and -- the accumulation order does not
+    depend on the access width -- each other bit for bit (but for the fp32 sum of products, see below)."""
+    coords = _scene(61, n=1400, span=12)
+    n, c = coords.shape[0], 8
+    x0 = ME.SparseTensor(torch.zeros(n, 1, device=DEV), coords.to(DEV))
+    mgr, k0 = x0.coordinate_manager, x0.coordinate_map_key
+    be = ME.get_backend()
+    g = torch.Generator(device=DEV).manual_seed(9)
+    wide = torch.randn(n, c + 5, generator=g, device=DEV).to(dtype)
+    wide2 = torch.randn(n, c + 5, generator=g, device=DEV).to(dtype)
+    xs, x2s = wide[:, 3:3 + c], wide2[:, 3:3 + c]                 # case A: row stride 13 elements, start 3 elements in
+    xc, x2c = xs.contiguous(), x2s.contiguous()                   # case B
+    es = wide.element_size()
+    assert (xs.stride(0) * es) % 16 != 0 and xs.data_ptr() % 16 != 0 and xc.data_ptr() % 16 == 0 and (c * es) % 16 == 0
+    _, bidx = batches(x0.C.cpu())
+    uniq, cidx = cells(x0.C.cpu(), 2)
+    k1 = mgr.coarser_key(k0, 2)
+    rix = _match(mgr.get_coordinates(k1).cpu(), uniq)
+    for coarse_key, idx, order in ((mgr.origin_key(), bidx, None), (k1, cidx, rix)):
+        sm = mgr.segment_map_handle(k0, coarse_key)
+        idx = idx.to(DEV)
+        m = sm.n_coarse
+        assert (int(torch.bincount(idx).max()) > 512) == (order is None)      # two passes on the origin map, one on the stride-2 map
+        take = (lambda t: t) if order is None else (lambda t: t[order.to(DEV)])
+        cnt = take(torch.bincount(idx, minlength=m))
+        fd, f2d = xc.double(), x2c.double()
+        for op in ("sum", "avg", "max", "prod"):
+            a, arg_a = be.pool_reduce(sm, op, xs, x2s if op == "prod" else None)
+            b, arg_b = be.pool_reduce(sm, op, xc, x2c if op == "prod" else None)
+            src = fd * f2d if op == "prod" else fd
+            ref = take(seg_reduce(src, idx, m, "sum" if op == "prod" else op))
+            for h in (a, b):
+                if op == "max":
+                    assert torch.equal(h.double(), ref)
+                else:
+                    abs_sum = take(seg_reduce(src.abs(), idx, m, "sum"))
+                    _check_sum_like(h, ref, abs_sum / (cnt.view(-1, 1) if op == "avg" else 1), cnt)
+            # fp32 sum of products: the compiler contracts v * w + acc into an FMA in some places of the unrolled loop and not in
+            # others, differently per access width (the ISA of k_seg_reduce<float, VEC, 3, PART> shows it), so the two widths may
+            # differ in the last bit there -- it holds to the reference bound only; bf16 products are exact in fp32 either way
+            if not (op == "prod" and dtype == torch.float32):
+                assert torch.equal(a, b), op
+            if op == "max":
+                assert torch.equal(arg_a, arg_b)
+        gsrc = torch.randn(m, c, generator=g, device=DEV).to(dtype)
+        ya, yb = be.pool_broadcast(sm, "add", gsrc, xs), be.pool_broadcast(sm, "add", gsrc, xc)
+        inv = torch.arange(m, device=DEV) if order is None else torch.empty_like(order.to(DEV)).scatter_(0, order.to(DEV), torch.arange(m, device=DEV))
+        want = (fd + gsrc.double()[inv[idx]]).float().to(dtype)       # one rounding of an exact fp64 result (test_broadcast_ops)
+        assert torch.equal(ya, want) and torch.equal(yb, want)
