@@ -655,6 +655,23 @@ int lgs_split_stats(const float *loss_rows, const int64_t *labels, int64_t n, co
  * sync and without a chain of elementwise / reduction launches over the label tensor. */
 int lgs_ce_count_valid(const int64_t *labels, int64_t n, int c, int64_t ignore_index, int32_t *count, void *stream);
 
+/* ---- segmentation metrics (csrc/lgs_metrics.hip) ------------------------------------------------
+ * replaces: what eval_step runs on the [N, 200] scores after the loss, in every training and validation step
+ *   lib/train_test/pl_BaselineTrainer.py:357-378 (soutput.F.max(1)[1], softmax(soutput.F, 1), the confusion matrix behind
+ *   precision / recall / IoU and their head / common / tail variants), pl_RepresentationTrainer.py:238-239
+ * A NEW SYMBOL ONLY: LGS_ABI_VERSION stays 18; a library that lacks the symbol lacks the capability.
+ * One pass over scores[n, c] (float32 / bf16, contiguous rows; class counts as lgs_ce_forward_backward: <= 512 fp32, <= 1024 bf16):
+ *   pred[n]        int64, written for EVERY row: torch.max(scores, 1)[1] -- the lowest index among the maxima, the index of the
+ *                  first NaN if the row has one, 0 for a row of -inf only
+ *   prob[n, c]     float32 softmax of the values as stored, or NULL: then the pass writes 8 bytes per row and nothing else
+ *   confmat[c, c]  int64, ACCUMULATED INTO and never cleared: confmat[labels[i]][pred[i]] += 1 for the rows with
+ *                  labels[i] != ignore_index and 0 <= labels[i] < c (the `k` mask of lib/utils.py:97-99); every other row adds
+ *                  nothing.  Integer sums (combined per half-wave, per workgroup in LDS, then 64-bit global atomics): the result
+ *                  does not depend on the order, two calls give the same bits.
+ * ignore_index may be any value, also a class index (255). */
+int lgs_seg_metrics(const void *scores, int64_t n, int c, const int64_t *labels, int64_t ignore_index, int64_t *pred, float *prob,
+                    int64_t *confmat, int dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

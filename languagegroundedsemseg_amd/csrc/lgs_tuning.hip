@@ -73,6 +73,11 @@ const Knob kKnobs[T_COUNT] = {
     {T_INSTANCE_NORM, "INSTANCE_NORM", 1, "MinkowskiInstanceNorm on HIP tensors: 1 = the per-scene kernels of lgs_instnorm.hip (two passes per direction, no host "
                                           "synchronisation, reproducible); 0 = the torch lines the CPU path uses (index_add_ on fp32 copies, one .item() per "
                                           "call) -- read at call time: for timing the old path in the same process and for switching the kernels off in the field"},
+    {T_METRICS_BLOCKS, "METRICS_BLOCKS", 8192, "most workgroups of a k_seg_metrics launch (lgs_metrics.hip); each walks tiles blockIdx.x, + gridDim.x, ... and adds its "
+                                               "LDS table of (label, pred) counts to the confusion matrix once at its end, so a cell costs at most this many "
+                                               "global atomics per call.  1.2 M x 200 bf16, no prob, uniform / 90 %-on-one-cell labels: 2048 373 / 273 us (two "
+                                               "uneven rounds of resident workgroups), 4096 284 / 228, 8192 242 / 220, 16384 231 / 264, one tile per workgroup "
+                                               "234 / 497 (37 500 adds on one address); small values let a test walk many tiles per workgroup on a few thousand rows"},
 };
 std::atomic<int64_t> g_val[T_COUNT];
 std::once_flag g_once;

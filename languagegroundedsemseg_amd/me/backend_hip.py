@@ -1156,6 +1156,32 @@ class HipBackend:
                                            int(ignore_index), _ptr(partial), rows, _stream()))
         return partial.sum(0).view(3, 2)
 
+    # ---- segmentation metrics: lgs_seg_metrics
+    @staticmethod
+    def seg_metrics_supports(scores):
+        """the class counts one half-wave holds (the limits of lgs_ce_forward_backward): 512 fp32, 1024 bf16"""
+        return scores.dtype in (torch.float32, torch.bfloat16) and 1 <= scores.shape[1] <= (512 if scores.dtype == torch.float32 else 1024)
+
+    def seg_metrics(self, scores, labels, ignore_index, confmat, want_prob=False):
+        """one pass over scores [N, C]: -> (pred [N] int64 = scores.max(1)[1], prob [N, C] fp32 softmax or None); adds the rows with
+        a label in [0, C) other than ignore_index to confmat [C, C] (int64, contiguous, accumulated IN PLACE).  No host sync."""
+        _require_dev(scores, "scores")
+        _require_dev(confmat, "confmat")
+        L = engine.lib()
+        scores = scores.detach().contiguous()
+        labels = labels.contiguous().to(torch.int64)
+        n, c = scores.shape
+        if confmat.dtype != torch.int64 or tuple(confmat.shape) != (c, c) or not confmat.is_contiguous():
+            raise RuntimeError("seg_metrics: confmat must be a contiguous int64 [%d, %d] tensor" % (c, c))
+        if labels.shape[0] != n:
+            raise RuntimeError("seg_metrics: %d labels for %d rows" % (labels.shape[0], n))
+        with _dev(scores.device):
+            pred = torch.empty(n, dtype=torch.int64, device=scores.device)
+            prob = torch.empty(n, c, dtype=torch.float32, device=scores.device) if want_prob else None
+            engine.check(L.lgs_seg_metrics(_ptr(scores), n, c, _ptr(labels), int(ignore_index), _ptr(pred), _ptr(prob), _ptr(confmat),
+                                           _dtype_code(scores), _stream()))
+        return pred, prob
+
     def _one(self, device):
         """a device-resident 1.0f (the kernels take their scalar factors from device memory)"""
         cache = self.__dict__.setdefault("_one_cache", {})

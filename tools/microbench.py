@@ -1,5 +1,5 @@
 """Per-op timings on the GPU (HIP events on torch's current stream) for the hot layer shapes.
-usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided]"""
+usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics]"""
 import os
 import sys
 import time
@@ -440,7 +440,74 @@ def strided():
                 del f, g
 
 
+def metrics():
+    """lgs_seg_metrics on [1.2 M, 200] scores (bf16 / fp32, with and without prob, uniform labels and a skewed set where 90 % of the
+    rows share one (label, pred) cell) beside the torch composition it replaces (max(1) + softmax + masked bincount), all variants
+    alternating inside this process; then the grid knob METRICS_BLOCKS.  Algorithmic bytes: n c e + 8 n read, 8 n written, + 4 n c
+    for prob.  min / median over the rounds."""
+    from languagegroundedsemseg_amd import engine
+    from languagegroundedsemseg_amd.metrics import SegmentationMeter
+    n, c, peak, rounds = 1200000, 200, 8e12, 3
+    g = torch.Generator(device=DEV).manual_seed(0)
+    base = torch.randn(n, c, device=DEV, generator=g)
+    lab_u = torch.randint(0, c, (n,), device=DEV, generator=g)
+    lab_u[torch.rand(n, device=DEV, generator=g) < 0.1] = -1
+    hot = torch.rand(n, device=DEV, generator=g) < 0.9          # rows of the one hot cell (label 3, pred 7), scattered over the batch
+    skew = base.clone()
+    skew[hot, 7] = 10.0
+    lab_s = torch.where(hot, torch.full_like(lab_u, 3), lab_u)
+    meter = SegmentationMeter(c).to(DEV)
+
+    def torch_lines(x, lab, want_prob):
+        pred = x.max(1)[1]
+        prob = torch.softmax(x.float(), 1) if want_prob else None
+        k = (lab >= 0) & (lab < c) & (lab != -1)
+        meter.confmat += torch.bincount(c * lab[k] + pred[k], minlength=c * c).view(c, c)
+        return pred, prob
+
+    def report(name, ts, nbytes):
+        t, med = min(ts), sorted(ts)[len(ts) // 2]
+        print("%-58s %8.1f us (median %8.1f)  %7.1f MB  %.2f TB/s  %.2f of 8 TB/s" % (name, t * 1e3, med * 1e3, nbytes / 1e6, nbytes / t / 1e9,
+                                                                                     nbytes / t / 1e9 * 1e12 / peak))
+        return t
+
+    for dtype in (torch.bfloat16, torch.float32):
+        e = 2 if dtype == torch.bfloat16 else 4
+        xs = {"uniform": (base.to(dtype), lab_u), "skewed": (skew.to(dtype), lab_s)}
+        times = {}
+        for rnd in range(rounds):                      # alternating: every variant once per round
+            for want_prob in (False, True):
+                for dist_name, (x, lab) in xs.items():
+                    times.setdefault(("kernel", want_prob, dist_name), []).append(timeit(lambda: meter.update(x, lab, want_prob=want_prob), 20, 3))
+                    times.setdefault(("torch", want_prob, dist_name), []).append(timeit(lambda: torch_lines(x, lab, want_prob), 4, 1))
+        best = {}
+        for (who, want_prob, dist_name), ts in times.items():
+            nbytes = n * c * e + 16 * n + (4 * n * c if want_prob else 0)
+            label = "%s %s %s labels %s" % ("lgs_seg_metrics" if who == "kernel" else "torch max+softmax+bincount" if want_prob else "torch max+bincount",
+                                            str(dtype).split(".")[1], dist_name, "+ prob" if want_prob else "no prob")
+            best[(who, want_prob, dist_name)] = report(label, ts, nbytes)
+        for want_prob in (False, True):
+            print("  %s %s: kernel %.2f x faster than the torch lines (uniform), %.2f x (skewed); skewed / uniform = %.2f" % (
+                str(dtype).split(".")[1], "+ prob" if want_prob else "no prob",
+                best[("torch", want_prob, "uniform")] / best[("kernel", want_prob, "uniform")],
+                best[("torch", want_prob, "skewed")] / best[("kernel", want_prob, "skewed")],
+                best[("kernel", want_prob, "skewed")] / best[("kernel", want_prob, "uniform")]))
+        del xs
+    x_u, x_s = base.to(torch.bfloat16), skew.to(torch.bfloat16)
+    times = {}
+    for rnd in range(rounds):
+        for blocks in (512, 1024, 2048, 4096, 8192, 16384, 65536):
+            with engine.tuning(METRICS_BLOCKS=blocks):
+                times.setdefault((blocks, "uniform"), []).append(timeit(lambda: meter.update(x_u, lab_u), 20, 3))
+                times.setdefault((blocks, "skewed"), []).append(timeit(lambda: meter.update(x_s, lab_s), 20, 3))
+    for (blocks, dist_name), ts in times.items():
+        report("METRICS_BLOCKS=%d bfloat16 %s labels no prob" % (blocks, dist_name), ts, n * c * 2 + 16 * n)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "metrics":
+        metrics()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "strided":
         strided()
         sys.exit(0)
