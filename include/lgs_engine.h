@@ -655,6 +655,30 @@ int lgs_split_stats(const float *loss_rows, const int64_t *labels, int64_t n, co
  * sync and without a chain of elementwise / reduction launches over the label tensor. */
 int lgs_ce_count_valid(const int64_t *labels, int64_t n, int c, int64_t ignore_index, int32_t *count, void *stream);
 
+/* ---- focal loss and class-weighted cross-entropy (csrc/lgs_loss.hip, k_focal_fwd_bwd) -----------
+ * replaces: the other two outcomes of loss_by_name(config.loss_type, ...) (lib/utils.py:112-118, pl_BaselineTrainer.py:96-99,
+ *   downstream/insseg/lib/pl_Trainer.py:74): FocalLoss(alpha, gamma) (lib/losses/FocalLoss.py) and nn.CrossEntropyLoss(weight=...)
+ * NEW SYMBOLS ONLY: LGS_ABI_VERSION stays 18; a library that lacks them lacks the capability.
+ * Per row with label l, counted iff l != ignore_index and 0 <= l < c (the predicate of every loss entry above); p = softmax(z),
+ * pt = p_l, u = 1 - pt, a = alpha[l] (alpha: DEVICE float[c], or NULL = all ones):
+ *   loss_rows[n]   float32:  -a u^gamma log(pt);  0 for rows that are not counted
+ *   dlogits[n, c]  dtype of logits:  coef (p_j - [j == l]) * (*scale) * row_scale[n],  coef = a (u^gamma - gamma pt u^(gamma-1) log(pt));
+ *                  rows that are not counted are WRITTEN as zeros
+ * gamma == 0 is nn.CrossEntropyLoss(weight=alpha, reduction='none') and its gradient; gamma >= 0 is required.  float32 arithmetic
+ * whatever the dtype.  u is the exponential sum without the label's term over the full sum (no 1 - pt), log(pt) is log1p(-u) while
+ * u < 1/2, and a row with u == 0 takes the limit: loss 0, coef = a for gamma == 0 and 0 otherwise -- finite where the reference's
+ * autograd yields 0^(gamma-1) = NaN for gamma < 1.
+ * scale, row_scale (NULL = ones), the two modes (either output may be NULL, not both), class limits (<= 512 fp32, <= 1024 bf16) and
+ * the bytes moved are those of lgs_ce_forward_backward_rows, plus the 4-byte alpha[l] per row.  n == 0 launches nothing. */
+int lgs_focal_forward_backward(const void *logits, int64_t n, int c, const int64_t *labels, int64_t ignore_index,
+                               const float *alpha /* [c] or NULL */, float gamma, const float *scale,
+                               const float *row_scale /* [n] or NULL */, float *loss_rows, void *dlogits, int dtype, void *stream);
+/* sum of alpha[labels[i]] over the counted rows, the denominator of nn.CrossEntropyLoss(weight=alpha) 'mean':
+ * partial[partial_rows] (1 <= partial_rows <= 1024, DEVICE float, overwritten), one float per workgroup -- the caller adds them up in
+ * fixed order (deterministic; no float atomics; no host sync). */
+int lgs_ce_weight_sum(const int64_t *labels, int64_t n, int c, int64_t ignore_index, const float *alpha,
+                      float *partial, int partial_rows, void *stream);
+
 /* ---- segmentation metrics (csrc/lgs_metrics.hip) ------------------------------------------------
  * replaces: what eval_step runs on the [N, 200] scores after the loss, in every training and validation step
  *   lib/train_test/pl_BaselineTrainer.py:357-378 (soutput.F.max(1)[1], softmax(soutput.F, 1), the confusion matrix behind

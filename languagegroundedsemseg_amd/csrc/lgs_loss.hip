@@ -252,6 +252,199 @@ int lgs_ce_count_valid(const int64_t *labels, int64_t n, int c, int64_t ignore_i
   return 0;
 }
 
+// ---- focal loss and class-weighted cross-entropy (lib/losses/FocalLoss.py, lib/utils.py:112-118 `loss_by_name`)
+//   L = -a u^gamma log(pt),   dL/dz_j = coef (p_j - [j == l]),   coef = a (u^gamma - gamma pt u^(gamma-1) log(pt))
+// with p = softmax(z), pt = p_l, u = 1 - pt, a = alpha[l] (1 without a table).  gamma == 0 is nn.CrossEntropyLoss(weight=alpha).
+// The shape of k_ce_fwd_bwd (half a wave per row, R rows per half-wave with every load issued first, Q x R = 4, 16-byte accesses
+// when C % W == 0), the same two modes (loss_rows only / dlogits only) and the same bytes, plus alpha[label]: 4 B per row from a
+// [C] table that stays in L2.  What differs is the per-row scalar part:
+//   u       = se_excl / se, the exponential sum WITHOUT the label's term over the full one, accumulated in the same pass: never
+//             1 - exp(log pt), which is 0 from pt = 1 - 6e-8 on;
+//   log(pt) = log1p(-u) while u < 1/2 (the label dominates: (z_l - max) - log(se) is 0 - log(1 + 1e-11) = 0 there), else
+//             (z_l - max) - log(se) (pt small: 1 - u would cancel);
+//   the label's gradient entry is -coef u, not coef (pt - 1);
+//   u^gamma: GM = 0 -> 1 (no pow), GM = 2 -> u u, GM = 1 -> exp2(gamma log2(u)); u^(gamma-1) = u^gamma / u; u == 0 takes the limit
+//             (loss 0, coef = a for gamma == 0, else 0) where the reference's autograd gives 0^(gamma-1) = NaN for gamma < 1.
+namespace lgs {
+
+template <typename T, int Q, int R, int GM>
+__global__ __launch_bounds__(256) void k_focal_fwd_bwd(const T *__restrict__ logits, int64_t n, int c, const int64_t *__restrict__ labels,
+                                                       int64_t ignore_index, const float *__restrict__ alpha, float gamma,
+                                                       const float *__restrict__ scale_ptr, const float *__restrict__ row_scale,
+                                                       float *__restrict__ loss_rows, T *__restrict__ dlogits) {
+  constexpr int W = LVec<T>::W;
+  const int lane = threadIdx.x & 31;  // half-wave per row group
+  const int64_t row0 = (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 5) * R;
+  if (row0 >= n) return;
+  const bool vec = (c % W) == 0;      // kernel-uniform, as in k_ce_fwd_bwd: padding lanes of the element-wise rows hold -3e38 -> exp = 0
+  const int nchunk = (c + W - 1) / W;
+  float v[R][Q][W];
+  int lab32s[R];
+  float as[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int64_t row = row0 + r;
+    const int64_t lab = row < n ? labels[row] : -1;
+    const bool ignored = (lab == ignore_index) || lab < 0 || lab >= c;
+    lab32s[r] = ignored ? -1 : (int)lab;
+    as[r] = (alpha && !ignored) ? alpha[lab] : 1.f;    // (the only read of the table: at a label inside [0, C))
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const int ch = q * 32 + lane;
+      if (ch < nchunk && row < n) {
+        if (vec) {
+          LVec<T>::load(logits + row * c + ch * W, v[r][q]);
+        } else {
+#pragma unroll
+          for (int i = 0; i < W; ++i) v[r][q][i] = ch * W + i < c ? ld_elem(logits + row * c + ch * W + i) : -3.0e38f;
+        }
+      }
+    }
+  }
+  const float scale0 = dlogits ? *scale_ptr : 0.f;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int64_t row = row0 + r;
+    if (row >= n) break;              // (uniform per half-wave: the shuffles below stay inside it)
+    const int lab32 = lab32s[r];
+    const bool ignored = lab32 < 0;
+    float mx = -3.0e38f;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const int ch = q * 32 + lane;
+      if (ch < nchunk) {
+#pragma unroll
+        for (int i = 0; i < W; ++i) mx = fmaxf(mx, v[r][q][i]);
+      }
+    }
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 32));
+    float se = 0.f, sx = 0.f, xl = 0.f;     // sx: the sum without the label's term
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const int ch = q * 32 + lane;
+      if (ch < nchunk) {
+        const int rel = lab32 - ch * W;
+#pragma unroll
+        for (int i = 0; i < W; ++i) {
+          const float e = __expf(v[r][q][i] - mx);
+          se += e;
+          sx += i == rel ? 0.f : e;
+          if (i == rel) xl = v[r][q][i];
+          v[r][q][i] = e;
+        }
+      }
+    }
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) { se += __shfl_xor(se, o, 32); sx += __shfl_xor(sx, o, 32); xl += __shfl_xor(xl, o, 32); }
+    const float a = as[r];
+    const float rse = 1.f / se;
+    const float u = sx * rse;
+    const float log_pt = u < 0.5f ? log1pf(-u) : (xl - mx) - __logf(se);
+    float loss, coef;
+    if constexpr (GM == 0) {
+      loss = -a * log_pt;
+      coef = a;
+    } else if constexpr (GM == 2) {
+      const float pt = __expf(xl - mx) * rse;
+      loss = -a * u * u * log_pt;
+      coef = a * (u * u - 2.f * pt * u * log_pt);
+    } else {
+      const float pt = __expf(xl - mx) * rse;
+      const float ug = exp2f(gamma * __log2f(u));
+      loss = u > 0.f ? -a * ug * log_pt : 0.f;
+      coef = u > 0.f ? a * (ug - gamma * pt * (ug / u) * log_pt) : 0.f;
+    }
+    if (loss_rows && lane == 0) loss_rows[row] = ignored ? 0.f : loss;
+    if (!dlogits) continue;   // loss only (the gradient is produced by a second call in the backward pass)
+    // ignored rows: an exact 0 whatever coef came out of a row without a label (its pt is exp(-max) / se)
+    const float cs = ignored ? 0.f : coef * (row_scale ? scale0 * row_scale[row] : scale0);
+    const float inv = cs * rse, at_label = -cs * u;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const int ch = q * 32 + lane;
+      if (ch < nchunk) {
+        const int rel = lab32 - ch * W;
+#pragma unroll
+        for (int i = 0; i < W; ++i) v[r][q][i] = i == rel ? at_label : v[r][q][i] * inv;
+        if (vec) {
+          LVec<T>::store(dlogits + row * c + ch * W, v[r][q]);
+        } else {
+#pragma unroll
+          for (int i = 0; i < W; ++i)
+            if (ch * W + i < c) st_elem(dlogits + row * c + ch * W + i, v[r][q][i]);
+        }
+      }
+    }
+  }
+}
+
+// sum of alpha[label] over the counted rows: the denominator of nn.CrossEntropyLoss(weight=alpha) 'mean'.  Per workgroup one float
+// -> partial[block]; the caller adds the <= 1024 rows up in fixed order (the pattern of k_split_stats: deterministic, no float atomics)
+__global__ __launch_bounds__(256) void k_ce_weight_sum(const int64_t *__restrict__ labels, int64_t n, int c, int64_t ignore_index,
+                                                        const float *__restrict__ alpha, float *__restrict__ partial) {
+  __shared__ float l_acc[4];
+  float sum = 0.f;
+  for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
+    const int64_t lab = labels[r];
+    if (lab == ignore_index || lab < 0 || lab >= c) continue;
+    sum += alpha[lab];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o, 64);
+  if ((threadIdx.x & 63) == 0) l_acc[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = l_acc[0] + l_acc[1] + l_acc[2] + l_acc[3];
+}
+
+}  // namespace lgs
+
+extern "C" int lgs_focal_forward_backward(const void *logits, int64_t n, int c, const int64_t *labels, int64_t ignore_index,
+                                          const float *alpha, float gamma, const float *scale, const float *row_scale,
+                                          float *loss_rows, void *dlogits, int dtype, void *stream) {
+  LGS_REQUIRE(logits && labels && scale && (loss_rows || dlogits), "lgs_focal_forward_backward: null argument");
+  LGS_REQUIRE(gamma >= 0.f, "lgs_focal_forward_backward: gamma must be >= 0");
+  const int W = dtype == LGS_BF16 ? 8 : 4;
+  LGS_REQUIRE(c >= 1 && (c + W - 1) / W <= 32 * kMaxChunks, "lgs_focal_forward_backward: more classes than one half-wave holds (512 fp32 / 1024 bf16)");
+  LGS_REQUIRE(n >= 0, "lgs_focal_forward_backward: negative row count");
+  if (n == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  const int nchunk = (c + W - 1) / W, q = (nchunk + 31) / 32;
+  // 8 half-waves per workgroup, R rows per half-wave (Q x R = 4); GM: 0 = weighted cross-entropy, 2 = u u, 1 = any other gamma
+#define LGS_FOCAL_LAUNCH(T_, Q_, R_, GM_)                                                                                             \
+  LGS_KLAUNCH((k_focal_fwd_bwd<T_, Q_, R_, GM_>), (unsigned)((n + 8 * (R_) - 1) / (8 * (R_))), 256, 0, s, (const T_ *)logits, n, c, labels, \
+              ignore_index, alpha, gamma, scale, row_scale, loss_rows, (T_ *)dlogits)
+#define LGS_FOCAL_SHAPE(T_, GM_)                                                                                                      \
+  do {                                                                                                                                \
+    if (q <= 1) LGS_FOCAL_LAUNCH(T_, 1, 4, GM_); else if (q == 2) LGS_FOCAL_LAUNCH(T_, 2, 2, GM_); else LGS_FOCAL_LAUNCH(T_, 4, 1, GM_); \
+  } while (0)
+#define LGS_FOCAL_GAMMA(T_)                                                                                                           \
+  do {                                                                                                                                \
+    if (gamma == 0.f) LGS_FOCAL_SHAPE(T_, 0); else if (gamma == 2.f) LGS_FOCAL_SHAPE(T_, 2); else LGS_FOCAL_SHAPE(T_, 1);             \
+  } while (0)
+  if (dtype == LGS_F32) {
+    LGS_FOCAL_GAMMA(float);
+  } else if (dtype == LGS_BF16) {
+    LGS_FOCAL_GAMMA(bf16_t);
+  } else {
+    LGS_REQUIRE(false, "lgs_focal_forward_backward: unknown dtype");
+  }
+#undef LGS_FOCAL_GAMMA
+#undef LGS_FOCAL_SHAPE
+#undef LGS_FOCAL_LAUNCH
+  LGS_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int lgs_ce_weight_sum(const int64_t *labels, int64_t n, int c, int64_t ignore_index, const float *alpha, float *partial,
+                                 int partial_rows, void *stream) {
+  LGS_REQUIRE(partial && alpha && n >= 0 && c >= 1 && partial_rows >= 1 && partial_rows <= 1024 && (labels || n == 0),
+              "lgs_ce_weight_sum: bad argument");
+  LGS_KLAUNCH(k_ce_weight_sum, (unsigned)partial_rows, 256, 0, (hipStream_t)stream, labels, n, c, ignore_index, alpha, partial);
+  LGS_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---- backward of the fused CLIP text-anchor loss (lgs_clip_loss_forward)
 //   /root/reference/lib/losses/ContrastiveLanguageLoss.py:73-95 (feat_dist, cos branch) through autograd:
 // only 1 + K entries of a row of S = f^ . T^^T carry gradient, so instead of two dense [N, A] x [A, C] products

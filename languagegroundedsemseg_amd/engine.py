@@ -194,7 +194,7 @@ EXPORTS = [
     "lgs_clip_loss_workspace_bytes", "lgs_clip_loss_forward", "lgs_clip_loss_backward",
     "lgs_clip_anchor_grad_workspace_bytes", "lgs_clip_loss_backward_anchors",
     "lgs_ce_forward_backward", "lgs_ce_forward_backward_rows", "lgs_split_stats",
-    "lgs_ce_count_valid", "lgs_seg_metrics",
+    "lgs_ce_count_valid", "lgs_focal_forward_backward", "lgs_ce_weight_sum", "lgs_seg_metrics",
     "lgs_comm_unique_id", "lgs_comm_create", "lgs_comm_create_ipc", "lgs_comm_ipc_open", "lgs_comm_destroy", "lgs_comm_world", "lgs_bn_sync_workspace_bytes",
     "lgs_bn_forward_sync", "lgs_bn_backward_sync",
     "lgs_voxelize", "lgs_label_vote", "lgs_cluster_workspace_bytes", "lgs_cluster", "lgs_sgd_step",
@@ -278,6 +278,8 @@ def lib():
         "lgs_ce_forward_backward_rows": [vp, i64, ci, vp, i64, vp, vp, vp, vp, ci, vp],
         "lgs_split_stats": [vp, vp, i64, vp, ci, i64, vp, ci, vp],
         "lgs_ce_count_valid": [vp, i64, ci, i64, vp, vp],
+        "lgs_focal_forward_backward": [vp, i64, ci, vp, i64, vp, cf, vp, vp, vp, vp, ci, vp],
+        "lgs_ce_weight_sum": [vp, i64, ci, i64, vp, vp, ci, vp],
         "lgs_seg_metrics": [vp, i64, ci, vp, i64, vp, vp, vp, ci, vp],
         "lgs_comm_unique_id": [vp],
         "lgs_comm_create": [vp, ci, ci, ci, ctypes.POINTER(vp)],

@@ -3,6 +3,9 @@
 * fused_cross_entropy  -- nn.CrossEntropyLoss(ignore_index=-1, reduction='mean') on [N,200] logits
                           (/root/reference/lib/train_test/pl_BaselineTrainer.py:94-99,350): one kernel computes
                           the loss and the gradient.
+* fused_focal_loss, FocalLoss, loss_by_name -- the other two outcomes of the reference's loss selector
+                          (lib/utils.py:112-118 `loss_by_name`, lib/losses/FocalLoss.py): focal loss with per-category weights and
+                          nn.CrossEntropyLoss(weight=...), both on lgs_focal_forward_backward.
 * ContrastiveLanguageLoss -- the CLIP text-anchor hinge loss
                           (/root/reference/lib/losses/ContrastiveLanguageLoss.py:97-194, feat_dist :73-95) written
                           on the dense MFMA contraction S = normalize(F) . normalize(T)^T plus index gathers, which
@@ -48,21 +51,232 @@ class _FusedCERows(torch.autograd.Function):
         return get_backend().cross_entropy_rows(logits, labels, ctx.ignore_index, row_grad=g), None, None
 
 
-def fused_cross_entropy(logits, labels, ignore_index=-1, reduction="mean"):
+def fused_cross_entropy(logits, labels, ignore_index=-1, reduction="mean", weight=None):
     """softmax cross-entropy; logits may be bf16 or fp32, any class count the kernel's half-wave holds (512 fp32 / 1024 bf16);
     wider heads go through torch's device op.
     reduction='mean': over the non-ignored rows (pl_BaselineTrainer.py:350 with balanced_category_sampling off);
     reduction='none': per-row losses [N], 0 for ignored rows -- what `self.criterion` returns when the fine-tune script's
     --balanced_category_sampling True is on (scripts/train_models.sh:37, pl_BaselineTrainer.py:94), the input of
-    sample_categories_for_balancing."""
+    sample_categories_for_balancing.
+    weight: [C] per-class weights, nn.CrossEntropyLoss(weight=...) (lib/utils.py:116): rows are weight[label] * CE on the focal kernel
+    at gamma 0, and 'mean' divides by the sum of weight[label] over the counted rows (torch's rule; an all-ignored batch gives 0).
+    weight=None is the unweighted kernel, untouched."""
     if reduction not in ("mean", "none"):
         raise ValueError("fused_cross_entropy: reduction must be 'mean' or 'none'")
+    if weight is not None:
+        return _focal_dispatch(logits, labels, weight, 0.0, ignore_index, reduction, "weight")
     backend = get_backend()
     if hasattr(backend, "cross_entropy") and logits.shape[1] <= (1024 if logits.dtype == torch.bfloat16 else 512):
         if reduction == "none":
             return _FusedCERows.apply(logits, labels, ignore_index)
         return _FusedCE.apply(logits, labels, ignore_index)
     return torch.nn.functional.cross_entropy(logits.float(), labels, ignore_index=ignore_index, reduction=reduction)
+
+
+class _FusedFocal(torch.autograd.Function):
+    """reduced focal loss / weighted cross-entropy, shaped like _FusedCE: forward = the loss call, backward = the same kernel again
+    with the upstream gradient folded into its scale; nothing [N, C] is saved but the logits."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, alpha, gamma, ignore_index, denom):
+        loss, _, inv_denom = get_backend().focal_loss(logits, labels, ignore_index, alpha, gamma, denom=denom)
+        ctx.save_for_backward(logits, labels, inv_denom, alpha)
+        ctx.gamma, ctx.ignore_index, ctx.denom = gamma, ignore_index, denom
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, inv_denom, alpha = ctx.saved_tensors
+        _, dlogits, _ = get_backend().focal_loss(logits, labels, ctx.ignore_index, alpha, ctx.gamma, denom=ctx.denom, grad_scale=g,
+                                                 inv_denom=inv_denom)
+        return dlogits, None, None, None, None, None
+
+
+class _FusedFocalRows(torch.autograd.Function):
+    """reduction='none', shaped like _FusedCERows: the upstream per-row gradient is the kernel's row factor"""
+
+    @staticmethod
+    def forward(ctx, logits, labels, alpha, gamma, ignore_index):
+        ctx.save_for_backward(logits, labels, alpha)
+        ctx.gamma, ctx.ignore_index = gamma, ignore_index
+        return get_backend().focal_loss_rows(logits, labels, ignore_index, alpha, gamma)
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, alpha = ctx.saved_tensors
+        return get_backend().focal_loss_rows(logits, labels, ctx.ignore_index, alpha, ctx.gamma, row_grad=g), None, None, None, None
+
+
+class _FocalRowsTorch(torch.autograd.Function):
+    """the closed form of the focal kernel in plain torch (CPU tensors, a backend without focal_loss, heads wider than the kernel's
+    class limit): per-row losses [N] with the engine's conventions, gradient coef (p - onehot) -- not autograd through
+    (1 - pt) ** gamma, which is NaN at pt == 1 for gamma < 1.  float32 arithmetic (float64 logits stay float64)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, alpha, gamma, ignore_index):
+        z = logits if logits.dtype == torch.float64 else logits.float()
+        n, c = z.shape
+        valid = (labels != ignore_index) & (labels >= 0) & (labels < c)
+        lab = torch.where(valid, labels, torch.zeros_like(labels))[:, None]
+        mx = z.max(1, keepdim=True).values
+        e = torch.exp(z - mx)
+        se = e.sum(1)
+        at_label = torch.arange(c, device=z.device)[None, :] == lab
+        u = e.masked_fill(at_label, 0.0).sum(1) / se                   # 1 - pt without the subtraction
+        pt = e.gather(1, lab).squeeze(1) / se
+        log_pt = torch.where(u < 0.5, torch.log1p(-u), (z.gather(1, lab) - mx).squeeze(1) - torch.log(se))
+        a = alpha.to(z.dtype)[lab.squeeze(1)] if alpha is not None else torch.ones_like(se)
+        if gamma == 0:
+            ug, coef = torch.ones_like(u), a
+        else:
+            ug = u ** gamma
+            coef = a * (ug - gamma * pt * torch.where(u > 0, ug / u, torch.zeros_like(u)) * log_pt)
+        zero = torch.zeros_like(se)
+        ctx.save_for_backward(e / se[:, None], at_label, torch.where(valid, coef, zero), u)
+        ctx.dtype = logits.dtype
+        return torch.where(valid, -a * ug * log_pt, zero)
+
+    @staticmethod
+    def backward(ctx, g):
+        p, at_label, coef, u = ctx.saved_tensors
+        cs = (coef * g.to(coef.dtype))[:, None]
+        return torch.where(at_label, -cs * u[:, None], cs * p).to(ctx.dtype), None, None, None, None
+
+
+def _focal_class_limit(logits):
+    return 1024 if logits.dtype == torch.bfloat16 else 512
+
+
+def _focal_dispatch(logits, labels, alpha, gamma, ignore_index, reduction, mean_over):
+    """the one body of fused_focal_loss and fused_cross_entropy(weight=...): the kernel where it applies, else the torch closed form.
+    mean_over: what 'mean' divides by -- 'valid' (the counted rows) or 'weight' (the sum of alpha[label])."""
+    if logits.dim() != 2 or labels.dim() != 1 or labels.shape[0] != logits.shape[0]:
+        raise ValueError("logits must be [N, C] and labels [N], got %s and %s" % (tuple(logits.shape), tuple(labels.shape)))
+    c = logits.shape[1]
+    if alpha is not None:
+        if not isinstance(alpha, torch.Tensor):
+            alpha = torch.as_tensor(alpha, dtype=torch.float32)
+        if alpha.dim() != 1 or alpha.shape[0] != c:
+            raise ValueError("per-class weights must be [%d] (one per class), got %s" % (c, tuple(alpha.shape)))
+        alpha = alpha.detach().to(device=logits.device, dtype=torch.float32).contiguous()
+    gamma = float(gamma)
+    if not gamma >= 0.0:
+        raise ValueError("gamma must be >= 0, got %r" % (gamma,))
+    labels = labels.long()
+    backend = get_backend()
+    if (logits.is_cuda and hasattr(backend, "focal_loss") and logits.dtype in (torch.float32, torch.bfloat16)
+            and c <= _focal_class_limit(logits)):
+        if reduction == "none":
+            return _FusedFocalRows.apply(logits, labels, alpha, gamma, ignore_index)
+        denom = "sum" if reduction == "sum" else mean_over
+        return _FusedFocal.apply(logits, labels, alpha, gamma, ignore_index, denom)
+    rows = _FocalRowsTorch.apply(logits, labels, alpha, gamma, ignore_index)
+    if reduction == "none":
+        return rows
+    total = rows.sum()
+    if reduction == "sum":
+        return total
+    valid = (labels != ignore_index) & (labels >= 0) & (labels < c)
+    if mean_over == "valid":
+        return total / valid.sum().clamp_min(1).to(total.dtype)
+    s = (alpha[labels.clamp(0, c - 1)] * valid).sum().to(total.dtype)
+    return total / torch.where(s > 0, s, torch.ones_like(s))
+
+
+def fused_focal_loss(logits, labels, alpha=None, gamma=2.0, ignore_index=-1, reduction="mean"):
+    """FocalLoss(alpha, gamma) of lib/losses/FocalLoss.py on the engine: per row -alpha[l] (1 - pt)^gamma log(pt) and its gradient
+    from one kernel per direction (lgs_focal_forward_backward; gamma == 0 is class-weighted cross-entropy), bf16 or fp32 logits.
+    A row is counted iff its label is neither ignore_index nor outside [0, C) -- the predicate of every loss of the engine.
+    reduction='mean': the mean over the counted rows, the reference's `loss.mean()` after its mask (NOT a weighted mean);
+    reduction='sum':  the plain sum;
+    reduction='none': [N] fp32 with 0 at ignored rows, the convention of fused_cross_entropy(reduction='none') and what
+        sample_categories_for_balancing takes.  The reference returns the compacted counted rows instead (its caller handles both
+        shapes, pl_BaselineTrainer.py:344-347): ours[labels != ignore_index] == reference.
+    An all-ignored or empty batch gives 0 as a device tensor (the reference: the Python float 0.).
+    Rows whose label's probability rounds to 1 take the limit: loss 0, gradient 0 (gamma > 0).  The reference computes 1 - exp(log pt),
+    rounds the loss to exactly 0 from pt = 1 - 6e-8 on and yields NaN gradients there for gamma < 1 (0^(gamma-1)); here 1 - pt is
+    the exponential sum without the label's term over the full sum, so the result is finite and slightly more accurate.
+    CPU tensors, a backend without the kernel and heads wider than 512 (fp32) / 1024 (bf16) classes take the same closed form in
+    plain torch.  gamma < 0 or an alpha that is not [C] raises ValueError."""
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError('Reduction must be one of: "mean", "sum", "none".')
+    return _focal_dispatch(logits, labels, alpha, gamma, ignore_index, reduction, "valid")
+
+
+def _flatten_scores(x, y):
+    """(N, C, d1, ..., dK) scores and (N, d1, ..., dK) labels -> [M, C] and [M] (FocalLoss.py:59-64)"""
+    if x.dim() > 2:
+        c = x.shape[1]
+        x = x.permute(0, *range(2, x.dim()), 1).reshape(-1, c)
+        y = y.reshape(-1)
+    return x, y
+
+
+class FocalLoss(nn.Module):
+    """Drop-in for lib/losses/FocalLoss.py: the same constructor, `__repr__` and forward(x, y), on fused_focal_loss (see there for
+    the reduction='none' shape and the saturated rows).  alpha is a buffer, so it follows `.to()`."""
+
+    def __init__(self, alpha=None, gamma=0., reduction='mean', ignore_index=-100):
+        if reduction not in ('mean', 'sum', 'none'):
+            raise ValueError('Reduction must be one of: "mean", "sum", "none".')
+        super().__init__()
+        if alpha is not None and not isinstance(alpha, torch.Tensor):
+            if not hasattr(alpha, "__len__"):
+                raise TypeError("alpha must be a [C] tensor of per-class weights or None (as nn.NLLLoss(weight=...) in the "
+                                "reference), got %r" % (alpha,))
+            alpha = torch.as_tensor(alpha, dtype=torch.float32)
+        if float(gamma) < 0:
+            raise ValueError("gamma must be >= 0, got %r" % (gamma,))
+        self.register_buffer("alpha", alpha)
+        self.gamma = gamma
+        self.ignore_index = ignore_index
+        self.reduction = reduction
+
+    def __repr__(self):
+        arg_keys = ['alpha', 'gamma', 'ignore_index', 'reduction']
+        arg_strs = [f'{k}={getattr(self, k)}' for k in arg_keys]
+        return f'{type(self).__name__}({", ".join(arg_strs)})'
+
+    def forward(self, x, y):
+        x, y = _flatten_scores(x, y)
+        return fused_focal_loss(x, y, alpha=self.alpha, gamma=self.gamma, ignore_index=self.ignore_index, reduction=self.reduction)
+
+
+class FusedCrossEntropyLoss(nn.Module):
+    """nn.CrossEntropyLoss(weight, ignore_index, reduction) as loss_by_name builds it, on fused_cross_entropy; `weight` is a buffer.
+    Labels outside [0, C) are ignored rows (nn.CrossEntropyLoss raises) and a batch without a counted row gives 0 (there: NaN)."""
+
+    def __init__(self, weight=None, ignore_index=-100, reduction='mean'):
+        if reduction not in ('mean', 'sum', 'none'):
+            raise ValueError('Reduction must be one of: "mean", "sum", "none".')
+        super().__init__()
+        if weight is not None and not isinstance(weight, torch.Tensor):
+            weight = torch.as_tensor(weight, dtype=torch.float32)
+        self.register_buffer("weight", weight)
+        self.ignore_index = ignore_index
+        self.reduction = reduction
+
+    def extra_repr(self):
+        return "ignore_index=%s, reduction=%r, weighted=%s" % (self.ignore_index, self.reduction, self.weight is not None)
+
+    def forward(self, x, y):
+        x, y = _flatten_scores(x, y)
+        if self.reduction == 'sum':            # (the unweighted kernel has no 'sum': gamma 0 of the focal kernel is the same rows)
+            return fused_focal_loss(x, y, alpha=self.weight, gamma=0.0, ignore_index=self.ignore_index, reduction='sum')
+        return fused_cross_entropy(x, y, ignore_index=self.ignore_index, reduction=self.reduction, weight=self.weight)
+
+
+def loss_by_name(loss_name, ignore_index=0, alpha=0.5, gamma=2.0, reduction='mean', weight=None):
+    """lib/utils.py:112-118, what `init_criterions` calls (pl_BaselineTrainer.py:96-99, downstream/insseg/lib/pl_Trainer.py:74):
+    'focal' -> FocalLoss(alpha, gamma), 'cross_entropy' -> the weighted / unweighted cross-entropy module, anything else -> None.
+    Both modules run the fused kernels in forward(x, y).  As in the reference, alpha must be the per-class weight tensor
+    (`dataset.category_weights`) or None: the signature's default 0.5 is rejected there by nn.NLLLoss and here by FocalLoss."""
+    if loss_name == 'focal':
+        return FocalLoss(alpha, gamma, reduction=reduction, ignore_index=ignore_index)
+    elif loss_name == 'cross_entropy':
+        return FusedCrossEntropyLoss(weight=weight, ignore_index=ignore_index, reduction=reduction)
+    else:
+        return None
 
 
 class _ClipSimilarity(torch.autograd.Function):

@@ -1141,6 +1141,85 @@ class HipBackend:
                                                         None, _ptr(dlogits), _dtype_code(logits), _stream()))
             return dlogits
 
+    # ---- focal loss / class-weighted cross-entropy: lgs_focal_forward_backward, lgs_ce_weight_sum
+    def ce_weight_sum(self, labels, n_classes, ignore_index, alpha):
+        """sum of alpha[label] over the counted rows -> device scalar (lgs_ce_weight_sum: per-workgroup partials added up in fixed
+        order), the denominator of nn.CrossEntropyLoss(weight=alpha) 'mean'.  No host sync."""
+        _require_dev(alpha, "alpha")
+        L = engine.lib()
+        labels = labels.contiguous().to(torch.int64)
+        n = labels.shape[0]
+        if n == 0:
+            return self._one(alpha.device) * 0.0
+        rows = max(1, min(1024, (n + 2047) // 2048))
+        with _dev(alpha.device):
+            partial = torch.empty(rows, dtype=torch.float32, device=alpha.device)
+            engine.check(L.lgs_ce_weight_sum(_ptr(labels), n, int(n_classes), int(ignore_index), _ptr(alpha), _ptr(partial), rows, _stream()))
+        return partial.sum()
+
+    def focal_loss(self, logits, labels, ignore_index, alpha, gamma, denom="valid", grad_scale=None, inv_denom=None):
+        """reduced focal loss -a u^gamma log(pt) (gamma == 0: class-weighted cross-entropy), the two halves of one kernel like
+        cross_entropy: grad_scale=None -> the loss; grad_scale (device scalar) -> d(logits), already multiplied by it.
+        alpha: [C] fp32 on the device, or None.  denom: 'valid' = mean over the counted rows (lgs_ce_count_valid; FocalLoss 'mean'),
+        'weight' = over the sum of alpha[label] (nn.CrossEntropyLoss(weight) 'mean'; a zero sum counts as 1), 'sum' = none.
+        inv_denom: the forward's, reused by the backward.  -> (loss, dlogits, inv_denom)"""
+        _require_dev(logits, "logits")
+        L = engine.lib()
+        logits = logits.contiguous()
+        labels = labels.contiguous().to(torch.int64)
+        n, c = logits.shape
+        dt = _dtype_code(logits)
+        one = self._one(logits.device)
+        if n == 0:      # empty batch: the conventions of cross_entropy
+            return (one * 0.0 if grad_scale is None else None), (torch.empty_like(logits) if grad_scale is not None else None), \
+                (inv_denom if inv_denom is not None else one)
+        with _dev(logits.device):
+            if inv_denom is None:
+                if denom == "valid":
+                    cnt = torch.empty(1, dtype=torch.int32, device=logits.device)
+                    engine.check(L.lgs_ce_count_valid(_ptr(labels), n, c, int(ignore_index), _ptr(cnt), _stream()))
+                    inv_denom = cnt.to(torch.float32).clamp_min_(1.0).reciprocal_().reshape(())
+                elif denom == "weight":
+                    s = self.ce_weight_sum(labels, c, ignore_index, alpha)
+                    inv_denom = torch.where(s > 0, s, one).reciprocal_()
+                elif denom == "sum":
+                    inv_denom = one
+                else:
+                    raise ValueError("focal_loss: denom must be 'valid', 'weight' or 'sum'")
+            if grad_scale is None:
+                loss_rows = torch.empty(n, dtype=torch.float32, device=logits.device)
+                engine.check(L.lgs_focal_forward_backward(_ptr(logits), n, c, _ptr(labels), int(ignore_index), _ptr(alpha), float(gamma),
+                                                          _ptr(one), None, _ptr(loss_rows), None, dt, _stream()))
+                return loss_rows.sum() * inv_denom, None, inv_denom
+            scale = inv_denom * grad_scale.to(torch.float32).reshape(())
+            dlogits = torch.empty_like(logits)
+            engine.check(L.lgs_focal_forward_backward(_ptr(logits), n, c, _ptr(labels), int(ignore_index), _ptr(alpha), float(gamma),
+                                                      _ptr(scale), None, None, _ptr(dlogits), dt, _stream()))
+        return None, dlogits, inv_denom
+
+    def focal_loss_rows(self, logits, labels, ignore_index, alpha, gamma, row_grad=None):
+        """reduction='none': row_grad=None -> the per-row losses [N] fp32 (0 for ignored rows); row_grad [N] = the upstream gradient
+        -> d(logits); one pass either way, like cross_entropy_rows."""
+        _require_dev(logits, "logits")
+        L = engine.lib()
+        logits = logits.contiguous()
+        labels = labels.contiguous().to(torch.int64)
+        n, c = logits.shape
+        if n == 0:
+            return torch.empty(0, dtype=torch.float32, device=logits.device) if row_grad is None else torch.empty_like(logits)
+        with _dev(logits.device):
+            one = self._one(logits.device)
+            if row_grad is None:
+                loss_rows = torch.empty(n, dtype=torch.float32, device=logits.device)
+                engine.check(L.lgs_focal_forward_backward(_ptr(logits), n, c, _ptr(labels), int(ignore_index), _ptr(alpha), float(gamma),
+                                                          _ptr(one), None, _ptr(loss_rows), None, _dtype_code(logits), _stream()))
+                return loss_rows
+            row_grad = row_grad.contiguous().to(torch.float32)
+            dlogits = torch.empty_like(logits)
+            engine.check(L.lgs_focal_forward_backward(_ptr(logits), n, c, _ptr(labels), int(ignore_index), _ptr(alpha), float(gamma),
+                                                      _ptr(one), _ptr(row_grad), None, _ptr(dlogits), _dtype_code(logits), _stream()))
+            return dlogits
+
     def split_stats(self, loss_rows, labels, group_of_class, ignore_index):
         """-> [3, 2] fp32: (sum of loss_rows, number of rows) of the head / common / tail points (lgs_split_stats), no host sync"""
         _require_dev(loss_rows, "loss_rows")

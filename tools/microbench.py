@@ -1,5 +1,5 @@
 """Per-op timings on the GPU (HIP events on torch's current stream) for the hot layer shapes.
-usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics]"""
+usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal]"""
 import os
 import sys
 import time
@@ -504,7 +504,49 @@ def metrics():
         report("METRICS_BLOCKS=%d bfloat16 %s labels no prob" % (blocks, dist_name), ts, n * c * 2 + 16 * n)
 
 
+def focal():
+    """k_focal_fwd_bwd (gamma 0 / 2 / 2.5, with and without alpha) beside k_ce_fwd_bwd on the same [1.2 M, 200] scores, bf16 and fp32,
+    forward (loss rows) and backward (d logits) calls, all variants alternating inside this process; min / median over the rounds.
+    Byte model: forward n c e + 8 n labels + 4 n loss rows, backward 2 n c e + 8 n + 4 n row factors; the focal kernel adds 4 n
+    (alpha[label]) when it has a table."""
+    be = ME.get_backend()
+    n, c, rounds = 1200000, 200, 5
+    g = torch.Generator(device=DEV).manual_seed(0)
+    base = torch.randn(n, c, device=DEV, generator=g) * 3
+    lab = torch.randint(-1, c, (n,), device=DEV, generator=g)
+    alpha = torch.rand(c, device=DEV, generator=g) * 2 + 0.1
+    up = torch.rand(n, device=DEV, generator=g)
+    for dtype in (torch.bfloat16, torch.float32):
+        e = 2 if dtype == torch.bfloat16 else 4
+        x = base.to(dtype)
+        variants = [("k_ce_fwd_bwd", None, None)] + [("k_focal_fwd_bwd gamma %g %s" % (gm, "alpha" if a is not None else "no alpha"), gm, a)
+                                                     for gm in (0.0, 2.0, 2.5) for a in (None, alpha)]
+        times = {}
+        for rnd in range(rounds):
+            for name, gm, a in variants:
+                if gm is None:
+                    fwd = lambda: be.cross_entropy_rows(x, lab, -1)
+                    bwd = lambda: be.cross_entropy_rows(x, lab, -1, row_grad=up)
+                else:
+                    fwd = lambda: be.focal_loss_rows(x, lab, -1, a, gm)
+                    bwd = lambda: be.focal_loss_rows(x, lab, -1, a, gm, row_grad=up)
+                times.setdefault((name, "fwd"), []).append(timeit(fwd, 20, 3))
+                times.setdefault((name, "bwd"), []).append(timeit(bwd, 20, 3))
+        ref = {d: min(times[("k_ce_fwd_bwd", d)]) for d in ("fwd", "bwd")}
+        for name, gm, a in variants:
+            for d in ("fwd", "bwd"):
+                ts = times[(name, d)]
+                t, med = min(ts), sorted(ts)[len(ts) // 2]
+                nbytes = n * c * e * (1 if d == "fwd" else 2) + 12 * n + (4 * n if a is not None else 0)
+                print("%-8s %-36s %s %8.1f us (median %8.1f)  %7.1f MB  %.2f TB/s  x k_ce_fwd_bwd %.3f" % (
+                    str(dtype).split(".")[1], name, d, t * 1e3, med * 1e3, nbytes / 1e6, nbytes / t / 1e9, t / ref[d]))
+        del x
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "focal":
+        focal()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "metrics":
         metrics()
         sys.exit(0)
