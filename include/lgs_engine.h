@@ -44,6 +44,7 @@ extern "C" {
 #define LGS_ABI_VERSION 18
 
 enum lgs_dtype { LGS_F32 = 0, LGS_BF16 = 1 };
+enum lgs_supcon_distance { LGS_SUPCON_COS = 0, LGS_SUPCON_L2 = 1 };   /* `distance` of lgs_supcon_forward / lgs_supcon_backward */
 
 typedef struct lgs_manager lgs_manager; /* coordinate manager: owns coordinate maps + kernel maps */
 typedef struct lgs_kmap lgs_kmap;       /* one cached kernel map (owned by its manager) */
@@ -695,6 +696,47 @@ int lgs_ce_weight_sum(const int64_t *labels, int64_t n, int c, int64_t ignore_in
  * ignore_index may be any value, also a class index (255). */
 int lgs_seg_metrics(const void *scores, int64_t n, int c, const int64_t *labels, int64_t ignore_index, int64_t *pred, float *prob,
                     int64_t *confmat, int dtype, void *stream);
+
+/* ---- supervised point-contrastive loss (csrc/lgs_supcon.hip) -------------------------------------
+ * replaces: PointSupConLoss.forward (lib/losses/PointSupConLoss.py:74-154), the third embedding criterion of
+ *   BaselineTrainerModule.init_criterions (lib/train_test/pl_BaselineTrainer.py:92-108): per class of the batch three device -> host
+ *   copies and two np.random.choice calls over all N points in a joblib pool, then [N, P, C] + [N, K, C] fp32 sample tensors and a bmm
+ * NEW SYMBOLS ONLY: LGS_ABI_VERSION stays 18; a library that lacks them lacks the capability.
+ * A row is counted iff its label is not ignore_label and inside [0, n_labels).  P = p and K = k are 1 .. 8 each.  A sample index
+ * outside [0, n) (the sampler writes -1) is "no sample": the all-zero row.  n == 0 launches nothing.  No LDS, atomics or workspace.
+ *
+ * lgs_supcon_sample: pos_idx[n, p], neg_idx[n, k] (int64) from tables the caller builds with device ops (all DEVICE int64):
+ *   order[n]            row numbers sorted (stably) by the key 2 * label + (not eligible), rows that are not counted last
+ *   seg_start[n_labels] first position of class c in `order`;  cls_count[c] its points;  elig_count[c] = m[c], the eligible ones
+ *                       (counted and, with predictions, correctly predicted), which come first in the segment
+ *   cum[n_labels, n_labels]  INT64 cumulative sums along each row of w[u, c] = hist[u, c] * m[c] * [c != u], hist >= 0
+ *   A positive is order[seg_start[u] + U(cls_count[u])] for the row's class u (uniform, with replacement, the row itself and
+ *   mispredicted points included, :120).  A negative draws x = U(cum[u, L-1]), takes the first class c with cum[u, c] > x (binary
+ *   search; a class of weight 0 owns no integer and is never drawn) and then order[seg_start[c] + U(m[c])] -- the two-level form of
+ *   np.random.choice(N, p = hist[u, label_j] * eligible_j / sum) (:124-139).  A row that is not counted gets -1 everywhere, a row whose
+ *   total weight is 0 gets -1 negatives.  U(t) = high 64 bits of r * t with r 64 random bits from Philox-4x32-10, key = seed,
+ *   counter = (row, slot): the indices depend on (seed, row, slot) only.  `seed` is a HOST integer.
+ *
+ * lgs_supcon_forward: one wavefront per row reads feat[n, c] (float32 / bf16; 16-byte loads when c * elemsize and the base address
+ *   are multiples of 16, element loads otherwise) and its p + k sampled rows: (1 + p + k) * n * c * elemsize bytes.  fp32 arithmetic.
+ *   LGS_SUPCON_COS: sim[n, p + k] = <a^, b^_j>, x^ = x / max(|x|, 1e-12);   d = 1 - mean_j sim_j  over the p / the k slots
+ *   LGS_SUPCON_L2:  sim[n, p + k] = sqrt(sum_c (a_c - b_jc)^2 + 1e-7), on the differences;   d = mean_j sim_j
+ *   d_pos[n], d_neg[n], sim (all float32) are 0 for rows that are not counted (:70);  inv_norm[n] = 1 / max(|a_n|, 1e-12) for EVERY row.
+ * lgs_supcon_backward: grad_feat[n, c] (dtype of feat; one round-to-nearest-even store for bf16) from the upstream g_dpos[n],
+ *   g_dneg[n] (float32, either may be NULL = zeros) and the forward's sim / inv_norm.  The sampled rows are constants (:77):
+ *   COS: gf = 1/|a| * sum_j gs_j (b^_j - s_j a^), gs_j = -g_dpos / p | -g_dneg / k, b^_j = b_j * inv_norm[idx_j] (|a| <= 1e-12: the
+ *        gradient of a / 1e-12, no projection term);   L2: gf = sum_j g_j (a - b_j) / (S sim_j), S = p | k.
+ *   Rows that are not counted are WRITTEN as zeros.  Reads as the forward, writes n * c * elemsize. */
+int lgs_supcon_sample(const int64_t *labels, int64_t n, int n_labels, int64_t ignore_label, const int64_t *cum,
+                      const int64_t *order, const int64_t *seg_start, const int64_t *cls_count, const int64_t *elig_count,
+                      int p, int k, int64_t seed, int64_t *pos_idx, int64_t *neg_idx, void *stream);
+int lgs_supcon_forward(const void *feat, int64_t n, int c, const int64_t *labels, const int64_t *pos_idx, int p,
+                       const int64_t *neg_idx, int k, int64_t ignore_label, int n_labels, int distance, float *d_pos,
+                       float *d_neg, float *sim, float *inv_norm, int dtype, void *stream);
+int lgs_supcon_backward(const void *feat, int64_t n, int c, const int64_t *labels, const int64_t *pos_idx, int p,
+                        const int64_t *neg_idx, int k, int64_t ignore_label, int n_labels, int distance, const float *sim,
+                        const float *inv_norm, const float *g_dpos, const float *g_dneg, void *grad_feat, int dtype,
+                        void *stream);
 
 #ifdef __cplusplus
 }

@@ -78,6 +78,10 @@ const Knob kKnobs[T_COUNT] = {
                                                "global atomics per call.  1.2 M x 200 bf16, no prob, uniform / 90 %-on-one-cell labels: 2048 373 / 273 us (two "
                                                "uneven rounds of resident workgroups), 4096 284 / 228, 8192 242 / 220, 16384 231 / 264, one tile per workgroup "
                                                "234 / 497 (37 500 adds on one address); small values let a test walk many tiles per workgroup on a few thousand rows"},
+    {T_SUPCON_FUSED, "SUPCON_FUSED", 1, "PointSupConLoss on HIP tensors: 1 = the kernels of lgs_supcon.hip (k_supcon_sample, k_supcon_fwd, k_supcon_bwd: (1 + P + K) row "
+                                        "reads per point, no [N, P + K, C] tensor); 0 = the torch gather path CPU tensors take (index gathers, normalise, mean) and "
+                                        "the torch restatement of the sampler -- read at call time: for timing the two next to each other and for switching "
+                                        "the kernels off in the field"},
 };
 std::atomic<int64_t> g_val[T_COUNT];
 std::once_flag g_once;

@@ -10,6 +10,7 @@ import os
 from . import build as _build
 
 LGS_F32, LGS_BF16 = 0, 1
+LGS_SUPCON_COS, LGS_SUPCON_L2 = 0, 1     # `distance` of lgs_supcon_forward / lgs_supcon_backward
 ABI_VERSION = 18     # LGS_ABI_VERSION of include/lgs_engine.h
 
 
@@ -195,6 +196,7 @@ EXPORTS = [
     "lgs_clip_anchor_grad_workspace_bytes", "lgs_clip_loss_backward_anchors",
     "lgs_ce_forward_backward", "lgs_ce_forward_backward_rows", "lgs_split_stats",
     "lgs_ce_count_valid", "lgs_focal_forward_backward", "lgs_ce_weight_sum", "lgs_seg_metrics",
+    "lgs_supcon_sample", "lgs_supcon_forward", "lgs_supcon_backward",
     "lgs_comm_unique_id", "lgs_comm_create", "lgs_comm_create_ipc", "lgs_comm_ipc_open", "lgs_comm_destroy", "lgs_comm_world", "lgs_bn_sync_workspace_bytes",
     "lgs_bn_forward_sync", "lgs_bn_backward_sync",
     "lgs_voxelize", "lgs_label_vote", "lgs_cluster_workspace_bytes", "lgs_cluster", "lgs_sgd_step",
@@ -281,6 +283,9 @@ def lib():
         "lgs_focal_forward_backward": [vp, i64, ci, vp, i64, vp, cf, vp, vp, vp, vp, ci, vp],
         "lgs_ce_weight_sum": [vp, i64, ci, i64, vp, vp, ci, vp],
         "lgs_seg_metrics": [vp, i64, ci, vp, i64, vp, vp, vp, ci, vp],
+        "lgs_supcon_sample": [vp, i64, ci, i64, vp, vp, vp, vp, vp, ci, ci, i64, vp, vp, vp],
+        "lgs_supcon_forward": [vp, i64, ci, vp, vp, ci, vp, ci, i64, ci, ci, vp, vp, vp, vp, ci, vp],
+        "lgs_supcon_backward": [vp, i64, ci, vp, vp, ci, vp, ci, i64, ci, ci, vp, vp, vp, vp, vp, ci, vp],
         "lgs_comm_unique_id": [vp],
         "lgs_comm_create": [vp, ci, ci, ci, ctypes.POINTER(vp)],
         "lgs_comm_create_ipc": [ci, ci, ci, ctypes.POINTER(vp), vp],

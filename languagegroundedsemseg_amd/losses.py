@@ -10,6 +10,8 @@
                           (/root/reference/lib/losses/ContrastiveLanguageLoss.py:97-194, feat_dist :73-95) written
                           on the dense MFMA contraction S = normalize(F) . normalize(T)^T plus index gathers, which
                           is mathematically the reference's [N,1+K,C] gather + bmm.
+* PointSupConLoss         -- the supervised point-contrastive baseline (lib/losses/PointSupConLoss.py): samples drawn on the device
+                          (k_supcon_sample), distances and their gradient from (1 + P + K) row reads per point (lgs_supcon.hip).
 """
 import torch
 import torch.nn as nn
@@ -587,6 +589,238 @@ class ReferenceContrastiveLanguageLoss(ContrastiveLanguageLoss):
                                   ignore_label=-1)
             return out[:3]
         return super().forward(features, labels, anchor_feats, neg_indices=neg_indices)[:3]
+
+
+def _supcon_gather(src, idx):
+    """rows src[idx] with the all-zero row where idx is outside [0, N) (-1 = "no sample"): [N, S, C]"""
+    n = src.shape[0]
+    ok = (idx >= 0) & (idx < n)
+    return src[idx.clamp(0, max(n - 1, 0))] * ok[..., None].to(src.dtype)
+
+
+def supcon_distances_torch(features, labels, pos_idx, neg_idx, ignore_label, num_labels, distance_type):
+    """The gather path of PointSupConLoss in plain torch, PointSupConLoss.py:44-71 line by line: gather the (detached) sampled
+    rows into [N, S, C], F.normalize both sides and average the dot products ('cos'), or average sqrt(|a - b|^2 + 1e-7) ('l2');
+    rows that are not counted get distance 0.  -> (d_pos [N], d_neg [N]); float32 arithmetic (float64 features stay float64).
+    CPU tensors, a backend without the kernels, P or K outside 1 .. 8 and SUPCON_FUSED=0 take it; the GPU tests restate the
+    kernels with it in float64."""
+    f = features if features.dtype == torch.float64 else features.float()
+    n = f.shape[0]
+    if n == 0:
+        z = f.sum(1)
+        return z, z
+    src = f.detach()
+    valid = (labels != ignore_label) & (labels >= 0) & (labels < num_labels)
+    out = []
+    for idx in (pos_idx, neg_idx):
+        b = _supcon_gather(src, idx)
+        if distance_type == "l2":
+            d = torch.sqrt((f[:, None, :] - b).pow(2).sum(-1) + 1e-7).mean(1)
+        else:
+            an = torch.nn.functional.normalize(f, p=2, dim=1)
+            bn = torch.nn.functional.normalize(b, p=2, dim=2)
+            d = 1 - (an[:, None, :] * bn).sum(-1).mean(1)
+        out.append(torch.where(valid, d, torch.zeros_like(d)))
+    return out[0], out[1]
+
+
+class _SupConFused(torch.autograd.Function):
+    """(d_pos, d_neg) of the supervised point-contrastive loss in one pass over the features and their P + K sampled rows
+    (lgs_supcon_forward); backward = lgs_supcon_backward from the saved per-sample similarities and 1 / |row|.  The sampled rows are
+    constants, as in the reference (`comp_feats = features.clone().detach()`)."""
+
+    @staticmethod
+    def forward(ctx, feats, labels, pos_idx, neg_idx, ignore_label, num_labels, distance):
+        d_pos, d_neg, saved = get_backend().supcon_forward(feats.detach(), labels, pos_idx, neg_idx, ignore_label, num_labels, distance)
+        ctx.args = (ignore_label, num_labels, distance)
+        ctx.save_for_backward(*saved)
+        ctx.set_materialize_grads(False)
+        return d_pos, d_neg
+
+    @staticmethod
+    def backward(ctx, g_dpos, g_dneg):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        return (get_backend().supcon_backward(tuple(ctx.saved_tensors), g_dpos, g_dneg, *ctx.args),) + (None,) * 6
+
+
+class PointSupConLoss(nn.Module):
+    """The supervised point-contrastive criterion of lib/losses/PointSupConLoss.py, the baseline the language-grounded pre-training
+    is compared against: per point P positives drawn from its own class and K negatives drawn from the other classes of the
+    batch in proportion to the confusion matrix (hardest-negative mining),
+        d = 1 - mean_j <f^, b^_j>  ('cos')   or   mean_j sqrt(|f - b_j|^2 + 1e-7)  ('l2');
+        loss = relu(d_pos - pos_thresh) + neg_weight * relu(neg_thresh - d_neg)
+    with the sampled rows b_j detached.  Kept as the reference is written: a row whose label is ignore_label (here also: outside
+    [0, num_labels), the predicate of every loss of the engine) gets distance 0 -- pos_loss relu(-pos_thresh) and neg_loss
+    relu(neg_thresh), so an ignored row adds 0.6 to neg_loss by default -- and counts in the mean.
+    Sample indices: int64 [N, P] / [N, K]; -1 (anything outside [0, N)) is "no sample", the all-zero row the reference's
+    zero-initialised sample buffers hold where nothing was drawn: cosine similarity 0, l2 distance sqrt(|f|^2 + 1e-7).
+    `sample` draws them on the device without a host synchronisation (k_supcon_sample); HIP tensors in fp32 / bf16 with P, K in
+    1 .. 8 run lgs_supcon_forward / lgs_supcon_backward, everything else supcon_distances_torch (tuning knob SUPCON_FUSED=0: that
+    path and the torch sampler on HIP tensors too).
+    `confusion_hist` starts as update_confusion_hist(0) = all ones (the reference starts at zeros, with which its np.random.choice
+    raises until the first update)."""
+
+    def __init__(self, num_labels, num_pos_samples=1, num_negative_samples=3, pos_thresh=0.0, neg_thresh=0.6, neg_weight=1.0,
+                 ignore_label=-1, reduction='mean', distance_type='cos'):
+        super().__init__()
+        if distance_type not in ("cos", "l2"):
+            raise ValueError("representation_distance_type must be 'cos' or 'l2' (PointSupConLoss.py:52-68), got %r" % (distance_type,))
+        if int(num_pos_samples) < 1 or int(num_negative_samples) < 1:
+            raise ValueError("num_pos_samples and num_negative_samples must be >= 1")
+        self.num_labels = int(num_labels)
+        self.num_pos_samples, self.num_negative_samples = int(num_pos_samples), int(num_negative_samples)
+        self.pos_thresh, self.neg_thresh, self.neg_weight = pos_thresh, neg_thresh, neg_weight
+        self.ignore_label, self.reduction, self.distance_type = ignore_label, reduction, distance_type
+        self.register_buffer("confusion_hist", torch.ones((self.num_labels, self.num_labels), dtype=torch.int64))
+        self._generator = None
+
+    @classmethod
+    def from_config(cls, config, num_labels, reduction="mean"):
+        """the reference's constructor arguments (PointSupConLoss.py:17) -> ReferencePointSupConLoss"""
+        return ReferencePointSupConLoss(config, num_labels, reduction=reduction)
+
+    def update_confusion_hist(self, new_confusion_hist):
+        """PointSupConLoss.py:41-42: hist + 1, so that no pair of classes has weight 0.  Takes SegmentationMeter.confmat as it is
+        (int64, on the device)."""
+        hist = torch.as_tensor(new_confusion_hist).detach().to(device=self.confusion_hist.device, dtype=torch.int64)
+        if tuple(hist.shape) != (self.num_labels, self.num_labels):
+            raise ValueError("confusion histogram must be [%d, %d], got %s" % (self.num_labels, self.num_labels, tuple(hist.shape)))
+        self.confusion_hist = hist + 1
+
+    def _seed_generator(self, generator):
+        if generator is not None:
+            if generator.device.type != "cpu":
+                raise ValueError("PointSupConLoss.sample takes a CPU torch.Generator (its seed is drawn on the host)")
+            return generator
+        if self._generator is None:
+            self._generator = torch.Generator().manual_seed(torch.initial_seed())
+        return self._generator
+
+    def sampling_tables(self, labels, preds=None):
+        """The two-level form of the reference's draw, in device ops without a host synchronisation.  The reference draws a negative
+        for class u among all points j with p_j ~ confusion_hist[u, label_j], zero where label_j == u, label_j is ignored or (with
+        preds) label_j != preds_j (:124-139).  That is: class c with weight w[u, c] = hist[u, c] * m[c] * [c != u], m[c] = eligible
+        points of c, then a uniform point among those m[c].
+        -> (cum [L, L], order [N], seg_start [L], cls_count [L], elig_count [L]), all int64:
+        one stable sort of 2 * label + (not eligible) (rows that are not counted: 2 L, last) gives `order`; binary searches for the
+        2 L + 1 key boundaries give the segment starts and sizes; cum is the INT64 running sum of w along each row (exact: a class of
+        weight 0 adds nothing and cannot be drawn)."""
+        L = self.num_labels
+        labels = labels.long()
+        valid = (labels != self.ignore_label) & (labels >= 0) & (labels < L)
+        elig = valid if preds is None else valid & (labels == preds.to(labels.device).long())
+        key = torch.where(valid, 2 * labels + (~elig).long(), torch.full_like(labels, 2 * L))
+        skey, order = torch.sort(key, stable=True)
+        bounds = torch.searchsorted(skey, torch.arange(2 * L + 1, device=labels.device, dtype=skey.dtype))
+        seg_start = bounds[0:2 * L:2]
+        elig_count = bounds[1:2 * L:2] - seg_start
+        cls_count = bounds[2:2 * L + 1:2] - seg_start
+        hist = self.confusion_hist.to(labels.device).clamp_min(0)
+        w = hist * elig_count[None, :]
+        w = w - torch.diag_embed(w.diagonal())
+        return torch.cumsum(w, 1), order, seg_start.contiguous(), cls_count.contiguous(), elig_count.contiguous()
+
+    def sample(self, labels, preds=None, generator=None):
+        """-> (pos_idx [N, P], neg_idx [N, K]) int64 on the labels' device, -1 = no sample: every slot of a row that is not counted,
+        and the negative slots of a row whose class has no eligible negative in the batch (the reference raises inside
+        np.random.choice there).  Positives are uniform, with replacement, over ALL points of the row's class -- the row itself and,
+        with preds, the mispredicted points included (the reference's filter is commented out, :112-117).
+        generator: a CPU torch.Generator (default: one the module owns, seeded from torch.initial_seed()).  HIP tensors: one 63-bit
+        seed is drawn from it on the host and k_supcon_sample derives every index from (seed, row, slot).  CPU tensors (and
+        SUPCON_FUSED=0): the same two-level draw with torch.rand from that generator -- the same distribution, other numbers."""
+        if labels.dim() != 1:
+            raise ValueError("labels must be [N]")
+        labels = labels.long()
+        n, L, P, K = labels.shape[0], self.num_labels, self.num_pos_samples, self.num_negative_samples
+        gen = self._seed_generator(generator)
+        be = get_backend()
+        tables = self.sampling_tables(labels, preds)
+        if (labels.is_cuda and hasattr(be, "supcon_sample") and be.supcon_enabled()
+                and 1 <= P <= be.SUPCON_MAX_SAMPLES and 1 <= K <= be.SUPCON_MAX_SAMPLES):
+            seed = int(torch.randint(0, 2 ** 62, (1,), generator=gen).item())       # a CPU tensor: no device synchronisation
+            return be.supcon_sample(labels, L, self.ignore_label, tables, P, K, seed)
+        cum, order, seg_start, cls_count, elig_count = tables
+        dev = labels.device
+        if n == 0:
+            return labels.new_empty((0, P)), labels.new_empty((0, K))
+        u = torch.rand((3, n, max(P, K)), generator=gen, dtype=torch.float64).to(dev)
+        valid = (labels != self.ignore_label) & (labels >= 0) & (labels < L)
+        lab = torch.where(valid, labels, torch.zeros_like(labels))
+        none = torch.full((), -1, dtype=torch.int64, device=dev)
+        def below(r, t):                       # uniform integer in [0, t), t >= 1 (int64 tensors)
+            return torch.minimum((r * t.double()).long(), t - 1).clamp_min(0)
+
+        def pick(cls, count, r):               # a uniform member of the first `count` entries of a class's segment
+            at = (seg_start[cls] + below(r, count.clamp_min(1))).clamp(0, n - 1)
+            return order[at]
+        pos = pick(lab[:, None].expand(n, P), cls_count[lab][:, None].expand(n, P), u[0, :, :P])
+        pos = torch.where(valid[:, None], pos, none)
+        row_cum = cum[lab]                                                              # [N, L]
+        total = row_cum[:, -1:]
+        x = below(u[1, :, :K], total.clamp_min(1).expand(n, K))
+        cls = torch.searchsorted(row_cum, x, right=True).clamp_max(L - 1)               # the first class with cum > x
+        neg = pick(cls, elig_count[cls], u[2, :, :K])
+        neg = torch.where(valid[:, None] & (total > 0) & (elig_count[cls] > 0), neg, none)
+        return pos, neg
+
+    def forward(self, features, labels, anchor_feats=None, preds=None, pos_indices=None, neg_indices=None):
+        """-> (loss, pos_loss [N], neg_loss [N]); the reference's call signature (anchor_feats is accepted and unused there too).
+        preds: the model's predictions; negatives are then drawn among the correctly predicted points only (:133-135).
+        pos_indices / neg_indices: explicit samples instead of a draw."""
+        if features.dim() != 2:
+            raise ValueError("`features` needs to be [n_points, feat_dim]")
+        labels = labels.long()
+        if pos_indices is None or neg_indices is None:
+            drawn = self.sample(labels, preds)
+            pos_indices = drawn[0] if pos_indices is None else pos_indices
+            neg_indices = drawn[1] if neg_indices is None else neg_indices
+        pos_indices, neg_indices = pos_indices.to(features.device).long(), neg_indices.to(features.device).long()
+        be = get_backend()
+        fused = (features.is_cuda and hasattr(be, "supcon_forward") and features.dtype in (torch.float32, torch.bfloat16)
+                 and 1 <= pos_indices.shape[1] <= be.SUPCON_MAX_SAMPLES and 1 <= neg_indices.shape[1] <= be.SUPCON_MAX_SAMPLES
+                 and features.shape[0] > 0 and be.supcon_enabled())
+        if fused:
+            d_pos, d_neg = _SupConFused.apply(features, labels, pos_indices, neg_indices, self.ignore_label, self.num_labels,
+                                              self.distance_type)
+        else:
+            d_pos, d_neg = supcon_distances_torch(features, labels, pos_indices, neg_indices, self.ignore_label, self.num_labels,
+                                                  self.distance_type)
+        return self._hinge(d_pos, d_neg)
+
+    def _hinge(self, d_pos, d_neg):
+        """PointSupConLoss.py:144-154"""
+        pos_loss = torch.relu(d_pos - self.pos_thresh)
+        neg_loss = torch.relu(self.neg_thresh - d_neg)
+        if self.reduction == "mean":
+            loss = pos_loss.mean() + neg_loss.mean() * self.neg_weight
+        else:
+            loss = pos_loss + neg_loss * self.neg_weight
+        return (loss, pos_loss, neg_loss)
+
+
+class ReferencePointSupConLoss(PointSupConLoss):
+    """Drop-in for the reference class, same constructor and call signature:
+        lib/losses/PointSupConLoss.py:17   __init__(config, num_labels, temperature, base_temperature, reduction)
+        lib/losses/PointSupConLoss.py:74   forward(features, labels, anchor_feats=None, preds=None) -> (loss, pos_loss, neg_loss)
+    as built by BaselineTrainerModule.init_criterions (lib/train_test/pl_BaselineTrainer.py:92-108) for every embedding_loss_type
+    other than MSE and 'contrast'.  It reads the same config fields (ignore_label, num_pos_samples, num_negative_samples,
+    contrast_pos_thresh / contrast_neg_thresh / contrast_neg_weight, representation_distance_type) and keeps `confusion_hist` and
+    update_confusion_hist (:165 feeds it `iou_scores.confmat.long()`, which metrics.SegmentationMeter keeps on the device).
+    temperature / base_temperature are stored and unused, as in the reference."""
+
+    def __init__(self, config, num_labels, temperature=0.07, base_temperature=0.07, reduction="mean"):
+        super().__init__(num_labels=num_labels, num_pos_samples=int(config.num_pos_samples),
+                         num_negative_samples=int(config.num_negative_samples),
+                         pos_thresh=float(config.contrast_pos_thresh), neg_thresh=float(config.contrast_neg_thresh),
+                         neg_weight=float(config.contrast_neg_weight), ignore_label=int(config.ignore_label), reduction=reduction,
+                         distance_type=config.representation_distance_type)
+        self.config = config
+        self.temperature, self.base_temperature = temperature, base_temperature
+        self.eps = 10e-5
+
+    def forward(self, features, labels, anchor_feats=None, preds=None):
+        return super().forward(features, labels, anchor_feats=anchor_feats, preds=preds)
 
 
 class _ClipCE(torch.autograd.Function):

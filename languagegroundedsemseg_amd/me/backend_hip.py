@@ -1261,6 +1261,69 @@ class HipBackend:
                                            _dtype_code(scores), _stream()))
         return pred, prob
 
+    # ---- supervised point-contrastive loss: lgs_supcon_sample / lgs_supcon_forward / lgs_supcon_backward
+    SUPCON_MAX_SAMPLES = 8
+    _SUPCON_DISTANCE = {"cos": engine.LGS_SUPCON_COS, "l2": engine.LGS_SUPCON_L2}
+
+    @staticmethod
+    def supcon_enabled():
+        """tuning knob SUPCON_FUSED, read at call time (0 = the torch gather path, also on HIP tensors)"""
+        return engine.tuning_get("SUPCON_FUSED") != 0
+
+    def supcon_sample(self, labels, n_labels, ignore_label, tables, p, k, seed):
+        """-> (pos_idx [N, P], neg_idx [N, K]) int64, -1 = no sample (k_supcon_sample).  tables = (cum [L, L], order [N],
+        seg_start [L], cls_count [L], elig_count [L]), device int64; seed: a host integer.  No host sync."""
+        _require_dev(labels, "labels")
+        L = engine.lib()
+        labels = labels.contiguous().to(torch.int64)
+        cum, order, seg_start, cls_count, elig_count = (t.contiguous().to(torch.int64) for t in tables)
+        n = labels.shape[0]
+        if tuple(cum.shape) != (n_labels, n_labels) or order.shape[0] != n or any(t.shape[0] != n_labels for t in (seg_start, cls_count, elig_count)):
+            raise RuntimeError("supcon_sample: tables do not match %d rows and %d labels" % (n, n_labels))
+        with _dev(labels.device):
+            pos = torch.empty(n, p, dtype=torch.int64, device=labels.device)
+            neg = torch.empty(n, k, dtype=torch.int64, device=labels.device)
+            engine.check(L.lgs_supcon_sample(_ptr(labels), n, int(n_labels), int(ignore_label), _ptr(cum), _ptr(order), _ptr(seg_start),
+                                             _ptr(cls_count), _ptr(elig_count), int(p), int(k), int(seed) & 0x7fffffffffffffff,
+                                             _ptr(pos), _ptr(neg), _stream()))
+        return pos, neg
+
+    def supcon_forward(self, feats, labels, pos_idx, neg_idx, ignore_label, n_labels, distance):
+        """one pass: -> (d_pos [N], d_neg [N], saved-for-backward tuple); sim [N, P + K] and inv_norm [N] are in the tuple"""
+        _require_dev(feats, "features")
+        L = engine.lib()
+        feats = feats.contiguous()
+        labels = labels.contiguous().to(torch.int64)
+        pos_idx, neg_idx = pos_idx.contiguous().to(torch.int64), neg_idx.contiguous().to(torch.int64)
+        n, c = feats.shape
+        p, k = pos_idx.shape[1], neg_idx.shape[1]
+        if labels.shape[0] != n or pos_idx.shape[0] != n or neg_idx.shape[0] != n:
+            raise RuntimeError("supcon_forward: labels / sample indices do not match %d rows" % n)
+        dev = feats.device
+        with _dev(dev):
+            d_pos = torch.empty(n, dtype=torch.float32, device=dev)
+            d_neg = torch.empty(n, dtype=torch.float32, device=dev)
+            sim = torch.empty(n, p + k, dtype=torch.float32, device=dev)
+            inv = torch.empty(n, dtype=torch.float32, device=dev)
+            engine.check(L.lgs_supcon_forward(_ptr(feats), n, c, _ptr(labels), _ptr(pos_idx), p, _ptr(neg_idx), k, int(ignore_label),
+                                              int(n_labels), self._SUPCON_DISTANCE[distance], _ptr(d_pos), _ptr(d_neg), _ptr(sim), _ptr(inv),
+                                              _dtype_code(feats), _stream()))
+        return d_pos, d_neg, (feats, labels, pos_idx, neg_idx, sim, inv)
+
+    def supcon_backward(self, saved, g_dpos, g_dneg, ignore_label, n_labels, distance):
+        """-> d loss / d features [N, C] in the features' dtype; g_dpos / g_dneg [N] or None"""
+        L = engine.lib()
+        feats, labels, pos_idx, neg_idx, sim, inv = saved
+        n, c = feats.shape
+        with _dev(feats.device):
+            gf = torch.empty_like(feats)
+            gp = g_dpos.contiguous().float() if g_dpos is not None else None
+            gn = g_dneg.contiguous().float() if g_dneg is not None else None
+            engine.check(L.lgs_supcon_backward(_ptr(feats), n, c, _ptr(labels), _ptr(pos_idx), pos_idx.shape[1], _ptr(neg_idx),
+                                               neg_idx.shape[1], int(ignore_label), int(n_labels), self._SUPCON_DISTANCE[distance],
+                                               _ptr(sim), _ptr(inv), _ptr(gp), _ptr(gn), _ptr(gf), _dtype_code(feats), _stream()))
+        return gf
+
     def _one(self, device):
         """a device-resident 1.0f (the kernels take their scalar factors from device memory)"""
         cache = self.__dict__.setdefault("_one_cache", {})

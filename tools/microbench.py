@@ -1,5 +1,5 @@
 """Per-op timings on the GPU (HIP events on torch's current stream) for the hot layer shapes.
-usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal]"""
+usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal | supcon]"""
 import os
 import sys
 import time
@@ -543,7 +543,65 @@ def focal():
         del x
 
 
+def supcon():
+    """PointSupConLoss (P = 1, K = 3, 'cos', 200 labels) at the benchmark batch's 1.2 M rows, bf16, C = 96 and C = 512: the device
+    sampler (table plumbing in torch device ops + k_supcon_sample), k_supcon_fwd and k_supcon_bwd, beside the torch gather path on the
+    same device (SUPCON_FUSED=0: index gathers into [N, S, C] fp32, F.normalize, mean, autograd) with the same indices.
+    Byte model: forward (1 + P + K) n c e, backward the same reads + n c e written; the fraction is of 8 TB/s."""
+    from languagegroundedsemseg_amd import engine
+    from languagegroundedsemseg_amd.losses import PointSupConLoss
+    be = ME.get_backend()
+    n, L, P, K, rounds = 1200000, 200, 1, 3, 3
+    g = torch.Generator(device=DEV).manual_seed(0)
+    lab = torch.randint(-1, L, (n,), device=DEV, generator=g)
+    preds = torch.where(torch.rand(n, device=DEV, generator=g) < 0.7, lab, torch.randint(0, L, (n,), device=DEV, generator=g))
+    crit = PointSupConLoss(L, P, K).to(DEV)
+    crit.update_confusion_hist(torch.randint(0, 1000, (L, L), device=DEV, generator=g))
+    gen = torch.Generator().manual_seed(1)
+    pos, neg = crit.sample(lab, preds, generator=gen)
+    tables = crit.sampling_tables(lab, preds)
+    up = torch.rand(n, device=DEV, generator=g)
+    t_sample = min(timeit(lambda: crit.sample(lab, preds, generator=gen), 10, 2) for _ in range(rounds))
+    t_kernel = min(timeit(lambda: be.supcon_sample(lab, L, -1, tables, P, K, 12345), 10, 2) for _ in range(rounds))
+    print("sample: tables + k_supcon_sample %8.1f us, k_supcon_sample alone %8.1f us  (n = %d, %d labels, P = %d, K = %d)" % (
+        t_sample * 1e3, t_kernel * 1e3, n, L, P, K))
+    with engine.tuning(SUPCON_FUSED=0):
+        t_torch_sample = timeit(lambda: crit.sample(lab, preds, generator=gen), 3, 1)
+    print("sample: torch restatement (SUPCON_FUSED=0) %8.1f us" % (t_torch_sample * 1e3))
+    for c in (96, 512):
+        x = torch.randn(n, c, device=DEV, generator=g).to(torch.bfloat16)
+        e = 2
+        _, _, saved = be.supcon_forward(x, lab, pos, neg, -1, L, "cos")
+        t_fwd = min(timeit(lambda: be.supcon_forward(x, lab, pos, neg, -1, L, "cos"), 10, 2) for _ in range(rounds))
+        t_bwd = min(timeit(lambda: be.supcon_backward(saved, up, up, -1, L, "cos"), 10, 2) for _ in range(rounds))
+        fb, bb = (1 + P + K) * n * c * e, (2 + P + K) * n * c * e
+        print("C = %3d bf16  k_supcon_fwd %8.1f us  %7.1f MB  %.2f TB/s (%.0f %% of 8 TB/s)" % (c, t_fwd * 1e3, fb / 1e6, fb / t_fwd / 1e9, fb / t_fwd / 8e7))
+        print("C = %3d bf16  k_supcon_bwd %8.1f us  %7.1f MB  %.2f TB/s (%.0f %% of 8 TB/s)" % (c, t_bwd * 1e3, bb / 1e6, bb / t_bwd / 1e9, bb / t_bwd / 8e7))
+        xr = x.clone().requires_grad_(True)
+
+        def step():
+            xr.grad = None
+            crit(xr, lab, pos_indices=pos, neg_indices=neg)[0].backward()
+        t_mod = min(timeit(step, 5, 2) for _ in range(rounds))
+        torch.cuda.reset_peak_memory_stats()
+        step()
+        torch.cuda.synchronize()
+        m_fused = torch.cuda.max_memory_allocated()
+        with engine.tuning(SUPCON_FUSED=0):
+            t_torch = min(timeit(step, 2, 1) for _ in range(2))
+            torch.cuda.reset_peak_memory_stats()
+            step()
+            torch.cuda.synchronize()
+            m_torch = torch.cuda.max_memory_allocated()
+        print("C = %3d bf16  module forward + backward (hinge and means included): kernels %8.1f us, torch gather path %8.1f us (x %.1f); "
+              "peak memory %.2f GB against %.2f GB" % (c, t_mod * 1e3, t_torch * 1e3, t_torch / t_mod, m_fused / 1e9, m_torch / 1e9))
+        del x, xr, saved
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "supcon":
+        supcon()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "focal":
         focal()
         sys.exit(0)
