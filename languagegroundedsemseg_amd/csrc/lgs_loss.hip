@@ -4,48 +4,18 @@
 //   /root/reference/lib/train_test/pl_BaselineTrainer.py:94-99,350
 // HBM-bound: logits are read once (16-byte loads, half a wavefront per row), the per-row loss and the
 // gradient (softmax - onehot) * scale are written in the same pass; ignored rows produce 0 / zeros.
-#include "lgs_common.h"
+#include "lgs_classrows.h"
 
 namespace lgs {
 
-template <typename T> struct LVec;
-template <> struct LVec<float> {
-  static constexpr int W = 4;
-  __device__ static void load(const float *p, float (&v)[4]) { float4 x = *reinterpret_cast<const float4 *>(p); v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w; }
-  __device__ static void store(float *p, const float (&v)[4]) { *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-};
-template <> struct LVec<bf16_t> {
-  static constexpr int W = 8;
-  __device__ static void load(const bf16_t *p, float (&v)[8]) {
-    uint4 x = *reinterpret_cast<const uint4 *>(p);
-    uint32_t w[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { v[2 * i] = bf16_to_f32((uint16_t)(w[i] & 0xffff)); v[2 * i + 1] = bf16_to_f32((uint16_t)(w[i] >> 16)); }
-  }
-  __device__ static void store(bf16_t *p, const float (&v)[8]) {
-    uint4 x;
-    x.x = (uint32_t)f32_to_bf16(v[0]) | ((uint32_t)f32_to_bf16(v[1]) << 16);
-    x.y = (uint32_t)f32_to_bf16(v[2]) | ((uint32_t)f32_to_bf16(v[3]) << 16);
-    x.z = (uint32_t)f32_to_bf16(v[4]) | ((uint32_t)f32_to_bf16(v[5]) << 16);
-    x.w = (uint32_t)f32_to_bf16(v[6]) | ((uint32_t)f32_to_bf16(v[7]) << 16);
-    *reinterpret_cast<uint4 *>(p) = x;
-  }
-};
-
-constexpr int kMaxChunks = 4;  // 16-byte chunks per lane per row: C <= 32 * 4 * W
-__device__ inline void st_elem(float *p, float v) { *p = v; }
-__device__ inline void st_elem(bf16_t *p, float v) { *p = f32_to_bf16(v); }
-
-// Half a wavefront per row; a half-wave takes R consecutive rows and issues the loads of ALL of them before it touches the first
-// (round 6: with one 400-byte row in flight per half-wave the 1.2 M x 200 launch ran at 2.8 TB/s -- 32 waves per CU x 800 bytes is
-// not enough outstanding traffic; Q = 16-byte chunks per lane and row, Q x R = 4 keeps the register count where it was).
-// The arithmetic per row is unchanged (same reduction tree, same order): results are bit-identical to the one-row kernel.
+// The access shape of lgs_classrows.h (half a wave per row, R rows per half-wave with every load issued first, Q x R = 4) plus the
+// per-row lse - z_l and the gradient (softmax - onehot) * scale.  Element-wise rows pad with -3e38 -> exp = 0.
 template <typename T, int Q, int R>
 __global__ __launch_bounds__(256) void k_ce_fwd_bwd(const T *__restrict__ logits, int64_t n, int c, const int64_t *__restrict__ labels,
                                                     int64_t ignore_index, const float *__restrict__ scale_ptr,
                                                     const float *__restrict__ row_scale, float *__restrict__ loss_rows,
                                                     T *__restrict__ dlogits) {
-  constexpr int W = LVec<T>::W;
+  constexpr int W = Width<T>::V;
   const int lane = threadIdx.x & 31;  // half-wave per row group
   const int64_t row0 = (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 5) * R;
   if (row0 >= n) return;
@@ -64,7 +34,7 @@ __global__ __launch_bounds__(256) void k_ce_fwd_bwd(const T *__restrict__ logits
       const int ch = q * 32 + lane;
       if (ch < nchunk && row < n) {
         if (vec) {
-          LVec<T>::load(logits + row * c + ch * W, v[r][q]);
+          ldv<W>(logits + row * c + ch * W, v[r][q]);
         } else {
 #pragma unroll
           for (int i = 0; i < W; ++i) v[r][q][i] = ch * W + i < c ? ld_elem(logits + row * c + ch * W + i) : -3.0e38f;
@@ -126,11 +96,11 @@ __global__ __launch_bounds__(256) void k_ce_fwd_bwd(const T *__restrict__ logits
           v[r][q][i] = g;
         }
         if (vec) {
-          LVec<T>::store(dlogits + row * c + ch * W, v[r][q]);
+          stv<W>(dlogits + row * c + ch * W, v[r][q]);
         } else {
 #pragma unroll
           for (int i = 0; i < W; ++i)
-            if (ch * W + i < c) st_elem(dlogits + row * c + ch * W + i, v[r][q][i]);
+            if (ch * W + i < c) stv<1>(dlogits + row * c + ch * W + i, &v[r][q][i]);
         }
       }
     }
@@ -216,23 +186,17 @@ extern "C" int lgs_ce_forward_backward_rows(const void *logits, int64_t n, int c
                                             const float *scale, const float *row_scale, float *loss_rows, void *dlogits, int dtype,
                                             void *stream) {
   LGS_REQUIRE(logits && labels && scale && (loss_rows || dlogits), "lgs_ce_forward_backward: null argument");
-  const int W = dtype == LGS_BF16 ? 8 : 4;
-  LGS_REQUIRE(c >= 1 && (c + W - 1) / W <= 32 * kMaxChunks, "lgs_ce_forward_backward: more classes than one half-wave holds (512 fp32 / 1024 bf16)");
+  int q;
+  if (int rc = class_shape(c, dtype, "lgs_ce_forward_backward", &q)) return rc;
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  const int nchunk = (c + W - 1) / W, q = (nchunk + 31) / 32;
-  // 8 half-waves per workgroup, R rows per half-wave (Q x R = 4)
-#define LGS_CE_LAUNCH(T_, Q_, R_)                                                                                              \
-  LGS_KLAUNCH((k_ce_fwd_bwd<T_, Q_, R_>), (unsigned)((n + 8 * (R_) - 1) / (8 * (R_))), 256, 0, s, (const T_ *)logits, n, c, labels, \
-              ignore_index, scale, row_scale, loss_rows, (T_ *)dlogits)
-  if (dtype == LGS_F32) {
-    if (q <= 1) LGS_CE_LAUNCH(float, 1, 4); else if (q == 2) LGS_CE_LAUNCH(float, 2, 2); else LGS_CE_LAUNCH(float, 4, 1);
-  } else if (dtype == LGS_BF16) {
-    if (q <= 1) LGS_CE_LAUNCH(bf16_t, 1, 4); else if (q == 2) LGS_CE_LAUNCH(bf16_t, 2, 2); else LGS_CE_LAUNCH(bf16_t, 4, 1);
-  } else {
-    LGS_REQUIRE(false, "lgs_ce_forward_backward: unknown dtype");
-  }
-#undef LGS_CE_LAUNCH
+  const int rc = with_class_rows<1>(dtype, q, 0, "lgs_ce_forward_backward", [&](auto e, auto) {
+    using E = decltype(e);
+    LGS_KLAUNCH((k_ce_fwd_bwd<typename E::T, E::Q, E::R>), (unsigned)e.tiles(n), 256, 0, s, e.in(logits), n, c, labels, ignore_index, scale,
+                row_scale, loss_rows, e.out(dlogits));
+    return 0;
+  });
+  if (rc) return rc;
   LGS_HIP(hipGetLastError());
   return 0;
 }
@@ -255,9 +219,8 @@ int lgs_ce_count_valid(const int64_t *labels, int64_t n, int c, int64_t ignore_i
 // ---- focal loss and class-weighted cross-entropy (lib/losses/FocalLoss.py, lib/utils.py:112-118 `loss_by_name`)
 //   L = -a u^gamma log(pt),   dL/dz_j = coef (p_j - [j == l]),   coef = a (u^gamma - gamma pt u^(gamma-1) log(pt))
 // with p = softmax(z), pt = p_l, u = 1 - pt, a = alpha[l] (1 without a table).  gamma == 0 is nn.CrossEntropyLoss(weight=alpha).
-// The shape of k_ce_fwd_bwd (half a wave per row, R rows per half-wave with every load issued first, Q x R = 4, 16-byte accesses
-// when C % W == 0), the same two modes (loss_rows only / dlogits only) and the same bytes, plus alpha[label]: 4 B per row from a
-// [C] table that stays in L2.  What differs is the per-row scalar part:
+// The access shape of lgs_classrows.h like k_ce_fwd_bwd, the same two modes (loss_rows only / dlogits only) and the same bytes, plus
+// alpha[label]: 4 B per row from a [C] table that stays in L2.  What differs is the per-row scalar part:
 //   u       = se_excl / se, the exponential sum WITHOUT the label's term over the full one, accumulated in the same pass: never
 //             1 - exp(log pt), which is 0 from pt = 1 - 6e-8 on;
 //   log(pt) = log1p(-u) while u < 1/2 (the label dominates: (z_l - max) - log(se) is 0 - log(1 + 1e-11) = 0 there), else
@@ -272,7 +235,7 @@ __global__ __launch_bounds__(256) void k_focal_fwd_bwd(const T *__restrict__ log
                                                        int64_t ignore_index, const float *__restrict__ alpha, float gamma,
                                                        const float *__restrict__ scale_ptr, const float *__restrict__ row_scale,
                                                        float *__restrict__ loss_rows, T *__restrict__ dlogits) {
-  constexpr int W = LVec<T>::W;
+  constexpr int W = Width<T>::V;
   const int lane = threadIdx.x & 31;  // half-wave per row group
   const int64_t row0 = (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 5) * R;
   if (row0 >= n) return;
@@ -293,7 +256,7 @@ __global__ __launch_bounds__(256) void k_focal_fwd_bwd(const T *__restrict__ log
       const int ch = q * 32 + lane;
       if (ch < nchunk && row < n) {
         if (vec) {
-          LVec<T>::load(logits + row * c + ch * W, v[r][q]);
+          ldv<W>(logits + row * c + ch * W, v[r][q]);
         } else {
 #pragma unroll
           for (int i = 0; i < W; ++i) v[r][q][i] = ch * W + i < c ? ld_elem(logits + row * c + ch * W + i) : -3.0e38f;
@@ -368,11 +331,11 @@ __global__ __launch_bounds__(256) void k_focal_fwd_bwd(const T *__restrict__ log
 #pragma unroll
         for (int i = 0; i < W; ++i) v[r][q][i] = i == rel ? at_label : v[r][q][i] * inv;
         if (vec) {
-          LVec<T>::store(dlogits + row * c + ch * W, v[r][q]);
+          stv<W>(dlogits + row * c + ch * W, v[r][q]);
         } else {
 #pragma unroll
           for (int i = 0; i < W; ++i)
-            if (ch * W + i < c) st_elem(dlogits + row * c + ch * W + i, v[r][q][i]);
+            if (ch * W + i < c) stv<1>(dlogits + row * c + ch * W + i, &v[r][q][i]);
         }
       }
     }
@@ -404,34 +367,19 @@ extern "C" int lgs_focal_forward_backward(const void *logits, int64_t n, int c, 
                                           float *loss_rows, void *dlogits, int dtype, void *stream) {
   LGS_REQUIRE(logits && labels && scale && (loss_rows || dlogits), "lgs_focal_forward_backward: null argument");
   LGS_REQUIRE(gamma >= 0.f, "lgs_focal_forward_backward: gamma must be >= 0");
-  const int W = dtype == LGS_BF16 ? 8 : 4;
-  LGS_REQUIRE(c >= 1 && (c + W - 1) / W <= 32 * kMaxChunks, "lgs_focal_forward_backward: more classes than one half-wave holds (512 fp32 / 1024 bf16)");
+  int q;
+  if (int rc = class_shape(c, dtype, "lgs_focal_forward_backward", &q)) return rc;
   LGS_REQUIRE(n >= 0, "lgs_focal_forward_backward: negative row count");
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  const int nchunk = (c + W - 1) / W, q = (nchunk + 31) / 32;
-  // 8 half-waves per workgroup, R rows per half-wave (Q x R = 4); GM: 0 = weighted cross-entropy, 2 = u u, 1 = any other gamma
-#define LGS_FOCAL_LAUNCH(T_, Q_, R_, GM_)                                                                                             \
-  LGS_KLAUNCH((k_focal_fwd_bwd<T_, Q_, R_, GM_>), (unsigned)((n + 8 * (R_) - 1) / (8 * (R_))), 256, 0, s, (const T_ *)logits, n, c, labels, \
-              ignore_index, alpha, gamma, scale, row_scale, loss_rows, (T_ *)dlogits)
-#define LGS_FOCAL_SHAPE(T_, GM_)                                                                                                      \
-  do {                                                                                                                                \
-    if (q <= 1) LGS_FOCAL_LAUNCH(T_, 1, 4, GM_); else if (q == 2) LGS_FOCAL_LAUNCH(T_, 2, 2, GM_); else LGS_FOCAL_LAUNCH(T_, 4, 1, GM_); \
-  } while (0)
-#define LGS_FOCAL_GAMMA(T_)                                                                                                           \
-  do {                                                                                                                                \
-    if (gamma == 0.f) LGS_FOCAL_SHAPE(T_, 0); else if (gamma == 2.f) LGS_FOCAL_SHAPE(T_, 2); else LGS_FOCAL_SHAPE(T_, 1);             \
-  } while (0)
-  if (dtype == LGS_F32) {
-    LGS_FOCAL_GAMMA(float);
-  } else if (dtype == LGS_BF16) {
-    LGS_FOCAL_GAMMA(bf16_t);
-  } else {
-    LGS_REQUIRE(false, "lgs_focal_forward_backward: unknown dtype");
-  }
-#undef LGS_FOCAL_GAMMA
-#undef LGS_FOCAL_SHAPE
-#undef LGS_FOCAL_LAUNCH
+  // GM: 0 = weighted cross-entropy, 2 = u u, 1 = any other gamma
+  const int rc = with_class_rows<3>(dtype, q, gamma == 0.f ? 0 : gamma == 2.f ? 2 : 1, "lgs_focal_forward_backward", [&](auto e, auto gm) {
+    using E = decltype(e);
+    LGS_KLAUNCH((k_focal_fwd_bwd<typename E::T, E::Q, E::R, decltype(gm)::value>), (unsigned)e.tiles(n), 256, 0, s, e.in(logits), n, c,
+                labels, ignore_index, alpha, gamma, scale, row_scale, loss_rows, e.out(dlogits));
+    return 0;
+  });
+  if (rc) return rc;
   LGS_HIP(hipGetLastError());
   return 0;
 }
@@ -459,14 +407,14 @@ __global__ __launch_bounds__(256) void k_clip_loss_bwd(const T *__restrict__ fea
                                                        const float *__restrict__ inv_norm, const float *__restrict__ d_pos,
                                                        const float *__restrict__ d_neg, const float *__restrict__ g_dpos,
                                                        const float *__restrict__ g_dneg, T *__restrict__ gf) {
-  constexpr int W = LVec<T>::W;
+  constexpr int W = Width<T>::V;
   const int G = c / W;                       // 16-byte channel groups per row
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t row = idx / G;
   const int g = (int)(idx - row * G);
   if (row >= n) return;
   float fv[W], out[W];
-  LVec<T>::load(feat + row * c + g * W, fv);
+  ldv<W>(feat + row * c + g * W, fv);
   const int64_t lab = labels[row];
   const bool valid = lab != ignore && lab >= 0 && lab < n_anchor;
 #pragma unroll
@@ -496,7 +444,7 @@ __global__ __launch_bounds__(256) void k_clip_loss_bwd(const T *__restrict__ fea
 #pragma unroll
     for (int i = 0; i < W; ++i) out[i] = (out[i] - si * fv[i]) * inv;
   }
-  LVec<T>::store(gf + row * c + g * W, out);
+  stv<W>(gf + row * c + g * W, out);
 }
 }  // namespace lgs
 

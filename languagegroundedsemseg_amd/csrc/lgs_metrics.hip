@@ -2,7 +2,7 @@
 //
 // Replaces what the reference's eval_step runs after the loss on every training and validation step
 //   lib/train_test/pl_BaselineTrainer.py:357-378 (pred = soutput.F.max(1)[1], prob = softmax(soutput.F, 1), the confusion matrix)
-// HBM-bound like k_ce_fwd_bwd (lgs_loss.hip), whose access pattern it copies: half a wavefront per row, 16-byte loads, Q x R = 4
+// HBM-bound like k_ce_fwd_bwd (lgs_loss.hip), with the same access shape (lgs_classrows.h): half a wavefront per row, 16-byte loads, Q x R = 4
 // chunks in flight per lane.  The scores are read once; the pass writes pred[n] (8 bytes per row), prob[n, c] if asked, and adds the
 // rows' (label, pred) cells to an int64 [c, c] matrix that lives on the device across steps.
 //
@@ -19,31 +19,15 @@
 
 #include <algorithm>
 
-#include "lgs_common.h"
+#include "lgs_classrows.h"
 
 namespace lgs {
 
 namespace {
 
-constexpr int kMetMaxChunks = 4;   // 16-byte chunks per lane per row: c <= 32 * 4 * W, as in lgs_loss.hip
 constexpr int kSlots = 256;        // LDS table entries per workgroup (one per thread for the flush)
 constexpr int kProbe = 8;          // linear probes before a key goes to global memory
 constexpr float kNegInf = -__builtin_huge_valf();
-
-template <typename T> struct MVec;
-template <> struct MVec<float> {
-  static constexpr int W = 4;
-  __device__ static void load(const float *p, float (&v)[4]) { float4 x = *reinterpret_cast<const float4 *>(p); v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w; }
-};
-template <> struct MVec<bf16_t> {
-  static constexpr int W = 8;
-  __device__ static void load(const bf16_t *p, float (&v)[8]) {
-    uint4 x = *reinterpret_cast<const uint4 *>(p);
-    uint32_t w[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { v[2 * i] = bf16_to_f32((uint16_t)(w[i] & 0xffff)); v[2 * i + 1] = bf16_to_f32((uint16_t)(w[i] >> 16)); }
-  }
-};
 
 // count `add` rows of cell `key`: the workgroup's table first, global memory when the probe sequence is taken by other keys
 __device__ inline void cell_add(int32_t *l_key, uint32_t *l_cnt, int32_t key, uint32_t add, unsigned long long *confmat) {
@@ -66,7 +50,7 @@ template <typename T, int Q, int R, bool PROB>
 __global__ __launch_bounds__(256) void k_seg_metrics(const T *__restrict__ scores, int64_t n, int c, const int64_t *__restrict__ labels,
                                                      int64_t ignore_index, int64_t *__restrict__ pred, float *__restrict__ prob,
                                                      unsigned long long *__restrict__ confmat) {
-  constexpr int W = MVec<T>::W;
+  constexpr int W = Width<T>::V;
   __shared__ int32_t l_key[kSlots];
   __shared__ uint32_t l_cnt[kSlots];
   l_key[threadIdx.x] = -1;
@@ -92,7 +76,7 @@ __global__ __launch_bounds__(256) void k_seg_metrics(const T *__restrict__ score
         const int ch = q * 32 + lane;
         if (ch < nchunk && row < n) {
           if (vec) {
-            MVec<T>::load(scores + row * c + ch * W, v[r][q]);
+            ldv<W>(scores + row * c + ch * W, v[r][q]);
           } else {
 #pragma unroll
             for (int i = 0; i < W; ++i) v[r][q][i] = ch * W + i < c ? ld_elem(scores + row * c + ch * W + i) : kNegInf;
@@ -193,29 +177,21 @@ using namespace lgs;
 extern "C" int lgs_seg_metrics(const void *scores, int64_t n, int c, const int64_t *labels, int64_t ignore_index, int64_t *pred,
                                float *prob, int64_t *confmat, int dtype, void *stream) {
   LGS_REQUIRE(confmat && n >= 0 && ((scores && labels && pred) || n == 0), "lgs_seg_metrics: null argument");
-  const int W = dtype == LGS_BF16 ? 8 : 4;
   LGS_REQUIRE(dtype == LGS_F32 || dtype == LGS_BF16, "lgs_seg_metrics: unknown dtype");
-  LGS_REQUIRE(c >= 1 && (c + W - 1) / W <= 32 * kMetMaxChunks, "lgs_seg_metrics: more classes than one half-wave holds (512 fp32 / 1024 bf16)");
+  int q;
+  if (int rc = class_shape(c, dtype, "lgs_seg_metrics", &q)) return rc;
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  const int nchunk = (c + W - 1) / W, q = (nchunk + 31) / 32;
   const int64_t max_blocks = std::min<int64_t>(std::max<int64_t>(tune(T_METRICS_BLOCKS), 1), 65536);
   unsigned long long *cm = reinterpret_cast<unsigned long long *>(confmat);
-  // 8 half-waves per workgroup, R rows per half-wave (Q x R = 4): a tile is 32 / 16 / 8 rows
-#define LGS_MET_LAUNCH2(T_, Q_, R_, P_)                                                                                          \
-  LGS_KLAUNCH((k_seg_metrics<T_, Q_, R_, P_>), (unsigned)std::min<int64_t>((n + 8 * (R_) - 1) / (8 * (R_)), max_blocks), 256, 0, s, \
-              (const T_ *)scores, n, c, labels, ignore_index, pred, prob, cm)
-#define LGS_MET_LAUNCH(T_, Q_, R_)                                                        \
-  do {                                                                                    \
-    if (prob) LGS_MET_LAUNCH2(T_, Q_, R_, true); else LGS_MET_LAUNCH2(T_, Q_, R_, false); \
-  } while (0)
-  if (dtype == LGS_F32) {
-    if (q <= 1) LGS_MET_LAUNCH(float, 1, 4); else if (q == 2) LGS_MET_LAUNCH(float, 2, 2); else LGS_MET_LAUNCH(float, 4, 1);
-  } else {
-    if (q <= 1) LGS_MET_LAUNCH(bf16_t, 1, 4); else if (q == 2) LGS_MET_LAUNCH(bf16_t, 2, 2); else LGS_MET_LAUNCH(bf16_t, 4, 1);
-  }
-#undef LGS_MET_LAUNCH
-#undef LGS_MET_LAUNCH2
+  // a tile is 32 / 16 / 8 rows
+  const int rc = with_class_rows<2>(dtype, q, prob ? 1 : 0, "lgs_seg_metrics", [&](auto e, auto want_prob) {
+    using E = decltype(e);
+    LGS_KLAUNCH((k_seg_metrics<typename E::T, E::Q, E::R, decltype(want_prob)::value != 0>), (unsigned)std::min<int64_t>(e.tiles(n), max_blocks),
+                256, 0, s, e.in(scores), n, c, labels, ignore_index, pred, prob, cm);
+    return 0;
+  });
+  if (rc) return rc;
   LGS_HIP(hipGetLastError());
   return 0;
 }

@@ -1,10 +1,12 @@
-// lgs_rows.h -- the row-streaming operators' one access layer (lgs_pool.hip, lgs_instnorm.hip, lgs_norm.hip; gfx950).
+// lgs_rows.h -- the row-streaming operators' one access layer (lgs_pool.hip, lgs_instnorm.hip, lgs_norm.hip; the
+// class-score kernels and k_clip_loss_bwd of lgs_loss.hip, k_seg_metrics of lgs_metrics.hip; gfx950).
 //
 // Features are [rows, C] row-major, fp32 or bf16.  A lane moves V = Width<T, VEC>::V adjacent channels per access: 16 bytes
 // (4 fp32 / 8 bf16) where the channel count, the row strides and the pointers allow it, one element otherwise; values are
 // widened to fp32 on load and rounded once (nearest even) on store.  Device side: ldv / stv / stv_nt / ldf.  Host side: the
 // alignment rule (al16, stride_ok, rows_ok), lanes per row and grids (lanes_log2, grid_for), and the two lifts from run-time
-// values to template arguments (with_row_type, with_op).  The MFMA kernels keep their own packing code.
+// values to template arguments (with_row_type, with_op).  lgs_classrows.h builds the class-score kernels' own lift on with_op.
+// The MFMA kernels keep their own packing code.
 #pragma once
 #include "lgs_common.h"
 

@@ -19,42 +19,58 @@ import torch.nn as nn
 from .me.core import get_backend
 
 
-class _FusedCE(torch.autograd.Function):
-    """forward: loss only; backward: the same kernel again writes d(logits) already scaled by the upstream gradient
-    (one read of the logits instead of a write + read-modify-write of an [N,200] gradient tensor)."""
+def _reduced(logits, labels, ignore_index, alpha, gamma, denom, grad_scale=None, inv_denom=None):
+    """one backend call of a reduced loss -> (loss, dlogits, inv_denom).  gamma None: the unweighted kernel (cross_entropy)"""
+    be = get_backend()
+    if gamma is None:
+        return be.cross_entropy(logits, labels, ignore_index, want_grad=False, grad_scale=grad_scale, inv_valid=inv_denom)
+    return be.focal_loss(logits, labels, ignore_index, alpha, gamma, denom=denom, grad_scale=grad_scale, inv_denom=inv_denom)
+
+
+def _rows(logits, labels, ignore_index, alpha, gamma, row_grad=None):
+    be = get_backend()
+    if gamma is None:
+        return be.cross_entropy_rows(logits, labels, ignore_index, row_grad=row_grad)
+    return be.focal_loss_rows(logits, labels, ignore_index, alpha, gamma, row_grad=row_grad)
+
+
+class _FusedReduced(torch.autograd.Function):
+    """reduced cross-entropy (gamma None: k_ce_fwd_bwd) or focal loss / weighted cross-entropy (k_focal_fwd_bwd).  forward: loss only;
+    backward: the same kernel again writes d(logits) already scaled by the upstream gradient (one read of the logits instead of a
+    write + read-modify-write of an [N, C] gradient tensor); nothing [N, C] is saved but the logits."""
 
     @staticmethod
-    def forward(ctx, logits, labels, ignore_index):
-        loss, _, inv_valid = get_backend().cross_entropy(logits, labels, ignore_index, want_grad=False)
-        ctx.save_for_backward(logits, labels, inv_valid)
-        ctx.ignore_index = ignore_index
+    def forward(ctx, logits, labels, alpha, gamma, ignore_index, denom):
+        loss, _, inv_denom = _reduced(logits, labels, ignore_index, alpha, gamma, denom)
+        ctx.save_for_backward(logits, labels, inv_denom, alpha)
+        ctx.gamma, ctx.ignore_index, ctx.denom = gamma, ignore_index, denom
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        logits, labels, inv_valid = ctx.saved_tensors
-        _, dlogits, _ = get_backend().cross_entropy(logits, labels, ctx.ignore_index, grad_scale=g, inv_valid=inv_valid)
-        return dlogits, None, None
+        logits, labels, inv_denom, alpha = ctx.saved_tensors
+        _, dlogits, _ = _reduced(logits, labels, ctx.ignore_index, alpha, ctx.gamma, ctx.denom, grad_scale=g, inv_denom=inv_denom)
+        return dlogits, None, None, None, None, None
 
 
-class _FusedCERows(torch.autograd.Function):
-    """reduction='none': forward = the per-row losses, backward = the same kernel with the upstream per-row gradient as its
-    row factor (lgs_ce_forward_backward_rows) -- no [N, C] softmax is kept between the two."""
+class _FusedRows(torch.autograd.Function):
+    """reduction='none' of either kernel: forward = the per-row losses, backward = the same kernel with the upstream per-row gradient
+    as its row factor (lgs_ce_forward_backward_rows, lgs_focal_forward_backward) -- no [N, C] softmax is kept between the two."""
 
     @staticmethod
-    def forward(ctx, logits, labels, ignore_index):
-        ctx.save_for_backward(logits, labels)
-        ctx.ignore_index = ignore_index
-        return get_backend().cross_entropy_rows(logits, labels, ignore_index)
+    def forward(ctx, logits, labels, alpha, gamma, ignore_index):
+        ctx.save_for_backward(logits, labels, alpha)
+        ctx.gamma, ctx.ignore_index = gamma, ignore_index
+        return _rows(logits, labels, ignore_index, alpha, gamma)
 
     @staticmethod
     def backward(ctx, g):
-        logits, labels = ctx.saved_tensors
-        return get_backend().cross_entropy_rows(logits, labels, ctx.ignore_index, row_grad=g), None, None
+        logits, labels, alpha = ctx.saved_tensors
+        return _rows(logits, labels, ctx.ignore_index, alpha, ctx.gamma, row_grad=g), None, None, None, None
 
 
 def fused_cross_entropy(logits, labels, ignore_index=-1, reduction="mean", weight=None):
-    """softmax cross-entropy; logits may be bf16 or fp32, any class count the kernel's half-wave holds (512 fp32 / 1024 bf16);
+    """softmax cross-entropy; logits may be bf16 or fp32, any class count the kernel's half-wave holds (the backend's class_limit);
     wider heads go through torch's device op.
     reduction='mean': over the non-ignored rows (pl_BaselineTrainer.py:350 with balanced_category_sampling off);
     reduction='none': per-row losses [N], 0 for ignored rows -- what `self.criterion` returns when the fine-tune script's
@@ -68,45 +84,12 @@ def fused_cross_entropy(logits, labels, ignore_index=-1, reduction="mean", weigh
     if weight is not None:
         return _focal_dispatch(logits, labels, weight, 0.0, ignore_index, reduction, "weight")
     backend = get_backend()
-    if hasattr(backend, "cross_entropy") and logits.shape[1] <= (1024 if logits.dtype == torch.bfloat16 else 512):
+    # (a dtype the kernel does not take goes to it within the fp32 limit and gets its refusal, not the torch path)
+    if hasattr(backend, "cross_entropy") and logits.shape[1] <= (backend.class_limit(logits.dtype) or backend.class_limit(torch.float32)):
         if reduction == "none":
-            return _FusedCERows.apply(logits, labels, ignore_index)
-        return _FusedCE.apply(logits, labels, ignore_index)
+            return _FusedRows.apply(logits, labels, None, None, ignore_index)
+        return _FusedReduced.apply(logits, labels, None, None, ignore_index, "valid")
     return torch.nn.functional.cross_entropy(logits.float(), labels, ignore_index=ignore_index, reduction=reduction)
-
-
-class _FusedFocal(torch.autograd.Function):
-    """reduced focal loss / weighted cross-entropy, shaped like _FusedCE: forward = the loss call, backward = the same kernel again
-    with the upstream gradient folded into its scale; nothing [N, C] is saved but the logits."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, alpha, gamma, ignore_index, denom):
-        loss, _, inv_denom = get_backend().focal_loss(logits, labels, ignore_index, alpha, gamma, denom=denom)
-        ctx.save_for_backward(logits, labels, inv_denom, alpha)
-        ctx.gamma, ctx.ignore_index, ctx.denom = gamma, ignore_index, denom
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, labels, inv_denom, alpha = ctx.saved_tensors
-        _, dlogits, _ = get_backend().focal_loss(logits, labels, ctx.ignore_index, alpha, ctx.gamma, denom=ctx.denom, grad_scale=g,
-                                                 inv_denom=inv_denom)
-        return dlogits, None, None, None, None, None
-
-
-class _FusedFocalRows(torch.autograd.Function):
-    """reduction='none', shaped like _FusedCERows: the upstream per-row gradient is the kernel's row factor"""
-
-    @staticmethod
-    def forward(ctx, logits, labels, alpha, gamma, ignore_index):
-        ctx.save_for_backward(logits, labels, alpha)
-        ctx.gamma, ctx.ignore_index = gamma, ignore_index
-        return get_backend().focal_loss_rows(logits, labels, ignore_index, alpha, gamma)
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, labels, alpha = ctx.saved_tensors
-        return get_backend().focal_loss_rows(logits, labels, ctx.ignore_index, alpha, ctx.gamma, row_grad=g), None, None, None, None
 
 
 class _FocalRowsTorch(torch.autograd.Function):
@@ -145,10 +128,6 @@ class _FocalRowsTorch(torch.autograd.Function):
         return torch.where(at_label, -cs * u[:, None], cs * p).to(ctx.dtype), None, None, None, None
 
 
-def _focal_class_limit(logits):
-    return 1024 if logits.dtype == torch.bfloat16 else 512
-
-
 def _focal_dispatch(logits, labels, alpha, gamma, ignore_index, reduction, mean_over):
     """the one body of fused_focal_loss and fused_cross_entropy(weight=...): the kernel where it applies, else the torch closed form.
     mean_over: what 'mean' divides by -- 'valid' (the counted rows) or 'weight' (the sum of alpha[label])."""
@@ -166,12 +145,11 @@ def _focal_dispatch(logits, labels, alpha, gamma, ignore_index, reduction, mean_
         raise ValueError("gamma must be >= 0, got %r" % (gamma,))
     labels = labels.long()
     backend = get_backend()
-    if (logits.is_cuda and hasattr(backend, "focal_loss") and logits.dtype in (torch.float32, torch.bfloat16)
-            and c <= _focal_class_limit(logits)):
+    if logits.is_cuda and hasattr(backend, "focal_loss") and c <= backend.class_limit(logits.dtype):
         if reduction == "none":
-            return _FusedFocalRows.apply(logits, labels, alpha, gamma, ignore_index)
+            return _FusedRows.apply(logits, labels, alpha, gamma, ignore_index)
         denom = "sum" if reduction == "sum" else mean_over
-        return _FusedFocal.apply(logits, labels, alpha, gamma, ignore_index, denom)
+        return _FusedReduced.apply(logits, labels, alpha, gamma, ignore_index, denom)
     rows = _FocalRowsTorch.apply(logits, labels, alpha, gamma, ignore_index)
     if reduction == "none":
         return rows
@@ -198,7 +176,7 @@ def fused_focal_loss(logits, labels, alpha=None, gamma=2.0, ignore_index=-1, red
     Rows whose label's probability rounds to 1 take the limit: loss 0, gradient 0 (gamma > 0).  The reference computes 1 - exp(log pt),
     rounds the loss to exactly 0 from pt = 1 - 6e-8 on and yields NaN gradients there for gamma < 1 (0^(gamma-1)); here 1 - pt is
     the exponential sum without the label's term over the full sum, so the result is finite and slightly more accurate.
-    CPU tensors, a backend without the kernel and heads wider than 512 (fp32) / 1024 (bf16) classes take the same closed form in
+    CPU tensors, a backend without the kernel and heads wider than the backend's class_limit take the same closed form in
     plain torch.  gamma < 0 or an alpha that is not [C] raises ValueError."""
     if reduction not in ("mean", "sum", "none"):
         raise ValueError('Reduction must be one of: "mean", "sum", "none".')

@@ -1085,63 +1085,81 @@ class HipBackend:
                                                           _stream()))
         return gt[:, :na].t()
 
-    # ---- fused softmax cross-entropy: lgs_ce_forward_backward
+    # ---- the class-row losses (csrc/lgs_classrows.h): fused softmax cross-entropy lgs_ce_forward_backward_rows, focal loss /
+    # class-weighted cross-entropy lgs_focal_forward_backward
+    @staticmethod
+    def class_limit(dtype):
+        """the widest [N, C] head half a wavefront holds (lgs_classrows.h: 32 lanes x 4 chunks of 16 bytes): 512 classes in fp32, 1024
+        in bf16; 0 for a dtype the class-row kernels do not take"""
+        return {torch.float32: 512, torch.bfloat16: 1024}.get(dtype, 0)
+
+    def _class_rows(self, logits, labels, ignore_index, focal, want_rows, want_grad, scale=None, row_grad=None):
+        """the one launch behind the four loss methods -> (loss_rows [N] fp32 or None, dlogits or None).  focal: None = k_ce_fwd_bwd,
+        (alpha, gamma) = k_focal_fwd_bwd.  The gradient is multiplied by scale (device scalar, default 1) and row_grad [N].
+        An empty batch gives empty results without a launch."""
+        _require_dev(logits, "logits")
+        L = engine.lib()
+        logits = logits.contiguous()
+        labels = labels.contiguous().to(torch.int64)
+        n, c = logits.shape
+        dev = logits.device
+        with _dev(dev):
+            loss_rows = torch.empty(n, dtype=torch.float32, device=dev) if want_rows else None
+            dlogits = torch.empty_like(logits) if want_grad else None
+            if n == 0:
+                return loss_rows, dlogits
+            if row_grad is not None:
+                row_grad = row_grad.contiguous().to(torch.float32)
+            args = (_ptr(scale if scale is not None else self._one(dev)), _ptr(row_grad), _ptr(loss_rows), _ptr(dlogits),
+                    _dtype_code(logits), _stream())
+            if focal is None:
+                engine.check(L.lgs_ce_forward_backward_rows(_ptr(logits), n, c, _ptr(labels), int(ignore_index), *args))
+            else:
+                engine.check(L.lgs_focal_forward_backward(_ptr(logits), n, c, _ptr(labels), int(ignore_index), _ptr(focal[0]),
+                                                          float(focal[1]), *args))
+        return loss_rows, dlogits
+
+    def _class_reduced(self, logits, labels, ignore_index, focal, denom, want_grad, grad_scale, inv_denom):
+        """a reduced loss on _class_rows -> (loss or None, dlogits or None, inv_denom).  grad_scale (device scalar): gradient only,
+        already multiplied by it.  inv_denom: 1 / the denominator, from an earlier call on the same labels or computed here from
+        denom: 'valid' = the counted rows (lgs_ce_count_valid: the kernel's predicate, a label outside [0, C) is an ignored row),
+        'weight' = the sum of alpha[label] (ce_weight_sum; a zero sum counts as 1), 'sum' = 1.  An empty batch: loss 0, 1."""
+        _require_dev(logits, "logits")
+        labels = labels.contiguous().to(torch.int64)
+        n, c = logits.shape
+        one = self._one(logits.device)
+        if inv_denom is None:
+            if n == 0 or denom == "sum":
+                inv_denom = one
+            elif denom == "valid":
+                with _dev(logits.device):
+                    cnt = torch.empty(1, dtype=torch.int32, device=logits.device)
+                    engine.check(engine.lib().lgs_ce_count_valid(_ptr(labels), n, c, int(ignore_index), _ptr(cnt), _stream()))
+                inv_denom = cnt.to(torch.float32).clamp_min_(1.0).reciprocal_().reshape(())
+            elif denom == "weight":
+                s = self.ce_weight_sum(labels, c, ignore_index, focal[0])
+                inv_denom = torch.where(s > 0, s, one).reciprocal_()
+            else:
+                raise ValueError("focal_loss: denom must be 'valid', 'weight' or 'sum'")
+        scale = inv_denom if grad_scale is None else inv_denom * grad_scale.to(torch.float32).reshape(())
+        loss_rows, dlogits = self._class_rows(logits, labels, ignore_index, focal, grad_scale is None, want_grad or grad_scale is not None,
+                                              scale=scale)
+        return (loss_rows.sum() * inv_denom if loss_rows is not None else None), dlogits, inv_denom
+
     def cross_entropy(self, logits, labels, ignore_index, want_grad=True, grad_scale=None, inv_valid=None):
         """mean CE over the non-ignored rows.  want_grad=False: loss only; grad_scale (device scalar): gradient only,
         already multiplied by it (the two halves of one kernel, so the upstream gradient never needs its own pass).
         inv_valid: 1 / #counted rows from an earlier call on the same labels (the forward's, reused by the backward).
         -> (loss, dlogits, inv_valid)"""
-        _require_dev(logits, "logits")
-        L = engine.lib()
-        logits = logits.contiguous()
-        labels = labels.contiguous().to(torch.int64)
-        n, c = logits.shape
-        dt = _dtype_code(logits)
-        if n == 0:      # empty batch: loss 0 (the convention of the all-ignored batch), an empty gradient
-            one = self._one(logits.device)
-            return (one * 0.0 if grad_scale is None else None), (torch.empty_like(logits) if (want_grad or grad_scale is not None) else None), \
-                (inv_valid if inv_valid is not None else one)
-        with _dev(logits.device):
-            if inv_valid is None:
-                # the same predicate the kernel uses: a label outside [0, C) is an ignored row, not a counted one
-                cnt = torch.empty(1, dtype=torch.int32, device=logits.device)
-                engine.check(L.lgs_ce_count_valid(_ptr(labels), n, c, int(ignore_index), _ptr(cnt), _stream()))
-                inv_valid = cnt.to(torch.float32).clamp_min_(1.0).reciprocal_().reshape(())
-            scale = inv_valid
-            if grad_scale is not None:
-                scale = scale * grad_scale.to(torch.float32).reshape(())
-            loss_rows = torch.empty(max(n, 1), dtype=torch.float32, device=logits.device) if grad_scale is None else None
-            dlogits = torch.empty_like(logits) if (want_grad or grad_scale is not None) else None
-            engine.check(L.lgs_ce_forward_backward(_ptr(logits), n, c, _ptr(labels), int(ignore_index), _ptr(scale),
-                                                   _ptr(loss_rows), _ptr(dlogits), dt, _stream()))
-        loss = loss_rows[:n].sum() * inv_valid if loss_rows is not None else None
-        return loss, dlogits, inv_valid
+        return self._class_reduced(logits, labels, ignore_index, None, "valid", want_grad, grad_scale, inv_valid)
 
     def cross_entropy_rows(self, logits, labels, ignore_index, row_grad=None):
         """nn.CrossEntropyLoss(reduction='none') (pl_BaselineTrainer.py:94 under balanced_category_sampling): row_grad=None ->
-        the per-row losses [N] (0 for ignored rows); row_grad [N] fp32 = the upstream gradient -> d(logits), one pass either way
-        (lgs_ce_forward_backward_rows).  No denominator: the caller's reduction owns it."""
-        _require_dev(logits, "logits")
-        L = engine.lib()
-        logits = logits.contiguous()
-        labels = labels.contiguous().to(torch.int64)
-        n, c = logits.shape
-        if n == 0:
-            return torch.empty(0, dtype=torch.float32, device=logits.device) if row_grad is None else torch.empty_like(logits)
-        with _dev(logits.device):
-            one = self._one(logits.device)
-            if row_grad is None:
-                loss_rows = torch.empty(n, dtype=torch.float32, device=logits.device)
-                engine.check(L.lgs_ce_forward_backward_rows(_ptr(logits), n, c, _ptr(labels), int(ignore_index), _ptr(one), None,
-                                                            _ptr(loss_rows), None, _dtype_code(logits), _stream()))
-                return loss_rows
-            row_grad = row_grad.contiguous().to(torch.float32)
-            dlogits = torch.empty_like(logits)
-            engine.check(L.lgs_ce_forward_backward_rows(_ptr(logits), n, c, _ptr(labels), int(ignore_index), _ptr(one), _ptr(row_grad),
-                                                        None, _ptr(dlogits), _dtype_code(logits), _stream()))
-            return dlogits
+        the per-row losses [N] (0 for ignored rows); row_grad [N] fp32 = the upstream gradient -> d(logits), one pass either way.
+        No denominator: the caller's reduction owns it."""
+        loss_rows, dlogits = self._class_rows(logits, labels, ignore_index, None, row_grad is None, row_grad is not None, row_grad=row_grad)
+        return loss_rows if row_grad is None else dlogits
 
-    # ---- focal loss / class-weighted cross-entropy: lgs_focal_forward_backward, lgs_ce_weight_sum
     def ce_weight_sum(self, labels, n_classes, ignore_index, alpha):
         """sum of alpha[label] over the counted rows -> device scalar (lgs_ce_weight_sum: per-workgroup partials added up in fixed
         order), the denominator of nn.CrossEntropyLoss(weight=alpha) 'mean'.  No host sync."""
@@ -1160,65 +1178,17 @@ class HipBackend:
     def focal_loss(self, logits, labels, ignore_index, alpha, gamma, denom="valid", grad_scale=None, inv_denom=None):
         """reduced focal loss -a u^gamma log(pt) (gamma == 0: class-weighted cross-entropy), the two halves of one kernel like
         cross_entropy: grad_scale=None -> the loss; grad_scale (device scalar) -> d(logits), already multiplied by it.
-        alpha: [C] fp32 on the device, or None.  denom: 'valid' = mean over the counted rows (lgs_ce_count_valid; FocalLoss 'mean'),
-        'weight' = over the sum of alpha[label] (nn.CrossEntropyLoss(weight) 'mean'; a zero sum counts as 1), 'sum' = none.
-        inv_denom: the forward's, reused by the backward.  -> (loss, dlogits, inv_denom)"""
-        _require_dev(logits, "logits")
-        L = engine.lib()
-        logits = logits.contiguous()
-        labels = labels.contiguous().to(torch.int64)
-        n, c = logits.shape
-        dt = _dtype_code(logits)
-        one = self._one(logits.device)
-        if n == 0:      # empty batch: the conventions of cross_entropy
-            return (one * 0.0 if grad_scale is None else None), (torch.empty_like(logits) if grad_scale is not None else None), \
-                (inv_denom if inv_denom is not None else one)
-        with _dev(logits.device):
-            if inv_denom is None:
-                if denom == "valid":
-                    cnt = torch.empty(1, dtype=torch.int32, device=logits.device)
-                    engine.check(L.lgs_ce_count_valid(_ptr(labels), n, c, int(ignore_index), _ptr(cnt), _stream()))
-                    inv_denom = cnt.to(torch.float32).clamp_min_(1.0).reciprocal_().reshape(())
-                elif denom == "weight":
-                    s = self.ce_weight_sum(labels, c, ignore_index, alpha)
-                    inv_denom = torch.where(s > 0, s, one).reciprocal_()
-                elif denom == "sum":
-                    inv_denom = one
-                else:
-                    raise ValueError("focal_loss: denom must be 'valid', 'weight' or 'sum'")
-            if grad_scale is None:
-                loss_rows = torch.empty(n, dtype=torch.float32, device=logits.device)
-                engine.check(L.lgs_focal_forward_backward(_ptr(logits), n, c, _ptr(labels), int(ignore_index), _ptr(alpha), float(gamma),
-                                                          _ptr(one), None, _ptr(loss_rows), None, dt, _stream()))
-                return loss_rows.sum() * inv_denom, None, inv_denom
-            scale = inv_denom * grad_scale.to(torch.float32).reshape(())
-            dlogits = torch.empty_like(logits)
-            engine.check(L.lgs_focal_forward_backward(_ptr(logits), n, c, _ptr(labels), int(ignore_index), _ptr(alpha), float(gamma),
-                                                      _ptr(scale), None, None, _ptr(dlogits), dt, _stream()))
-        return None, dlogits, inv_denom
+        alpha: [C] fp32 on the device, or None.  denom: 'valid' = mean over the counted rows (FocalLoss 'mean'), 'weight' = over the
+        sum of alpha[label] (nn.CrossEntropyLoss(weight) 'mean'), 'sum' = none.  inv_denom: the forward's, reused by the backward.
+        -> (loss, dlogits, inv_denom)"""
+        return self._class_reduced(logits, labels, ignore_index, (alpha, gamma), denom, False, grad_scale, inv_denom)
 
     def focal_loss_rows(self, logits, labels, ignore_index, alpha, gamma, row_grad=None):
         """reduction='none': row_grad=None -> the per-row losses [N] fp32 (0 for ignored rows); row_grad [N] = the upstream gradient
         -> d(logits); one pass either way, like cross_entropy_rows."""
-        _require_dev(logits, "logits")
-        L = engine.lib()
-        logits = logits.contiguous()
-        labels = labels.contiguous().to(torch.int64)
-        n, c = logits.shape
-        if n == 0:
-            return torch.empty(0, dtype=torch.float32, device=logits.device) if row_grad is None else torch.empty_like(logits)
-        with _dev(logits.device):
-            one = self._one(logits.device)
-            if row_grad is None:
-                loss_rows = torch.empty(n, dtype=torch.float32, device=logits.device)
-                engine.check(L.lgs_focal_forward_backward(_ptr(logits), n, c, _ptr(labels), int(ignore_index), _ptr(alpha), float(gamma),
-                                                          _ptr(one), None, _ptr(loss_rows), None, _dtype_code(logits), _stream()))
-                return loss_rows
-            row_grad = row_grad.contiguous().to(torch.float32)
-            dlogits = torch.empty_like(logits)
-            engine.check(L.lgs_focal_forward_backward(_ptr(logits), n, c, _ptr(labels), int(ignore_index), _ptr(alpha), float(gamma),
-                                                      _ptr(one), _ptr(row_grad), None, _ptr(dlogits), _dtype_code(logits), _stream()))
-            return dlogits
+        loss_rows, dlogits = self._class_rows(logits, labels, ignore_index, (alpha, gamma), row_grad is None, row_grad is not None,
+                                              row_grad=row_grad)
+        return loss_rows if row_grad is None else dlogits
 
     def split_stats(self, loss_rows, labels, group_of_class, ignore_index):
         """-> [3, 2] fp32: (sum of loss_rows, number of rows) of the head / common / tail points (lgs_split_stats), no host sync"""
@@ -1238,8 +1208,8 @@ class HipBackend:
     # ---- segmentation metrics: lgs_seg_metrics
     @staticmethod
     def seg_metrics_supports(scores):
-        """the class counts one half-wave holds (the limits of lgs_ce_forward_backward): 512 fp32, 1024 bf16"""
-        return scores.dtype in (torch.float32, torch.bfloat16) and 1 <= scores.shape[1] <= (512 if scores.dtype == torch.float32 else 1024)
+        """fp32 or bf16 scores of at most class_limit classes"""
+        return 1 <= scores.shape[1] <= HipBackend.class_limit(scores.dtype)
 
     def seg_metrics(self, scores, labels, ignore_index, confmat, want_prob=False):
         """one pass over scores [N, C]: -> (pred [N] int64 = scores.max(1)[1], prob [N, C] fp32 softmax or None); adds the rows with
