@@ -738,6 +738,76 @@ int lgs_supcon_backward(const void *feat, int64_t n, int c, const int64_t *label
                         const float *inv_norm, const float *g_dpos, const float *g_dneg, void *grad_feat, int dtype,
                         void *stream);
 
+/* ---- train-time augmentation chain (csrc/lgs_augment.hip) ---------------------------
+ * replaces: the numpy / scipy transforms the reference runs in DataLoader workers (lib/transforms.py, wired up in
+ *   lib/dataset.py:355-389): ElasticDistortion before the voxeliser, RandomHorizontalFlip, ChromaticAutoContrast,
+ *   ChromaticTranslation, ChromaticJitter and ChromaticScale after it, plus the voxeliser's per-scene rigid matrix.
+ * NEW SYMBOLS ONLY: LGS_ABI_VERSION stays 18; a library that lacks them lacks the capability.
+ * A batch is b <= LGS_AUG_MAX_SCENES scenes concatenated; rows of one scene are contiguous and scene_offsets[b + 1] (DEVICE int64,
+ * scene_offsets[0] = 0, non-decreasing, scene_offsets[b] = n) says where each begins.  An empty scene is legal everywhere.  Nothing
+ * here reads device memory back except lgs_aug_status.  Per-scene parameters are HOST arrays, passed to the kernels by value.
+ *
+ * lgs_aug_bounds: bounds[b, 6] = per scene (min of 3 columns, max of 3 columns), DEVICE, the table's own 32-bit type.
+ *   LGS_AUG_F32X3: table = float32 [n, 3]; scene_offsets is READ.  Floats are compared through an order-preserving integer key
+ *                  (-0.0 sorts below +0.0); an empty scene gets (+inf, -inf).
+ *   LGS_AUG_I32X4: table = int32 [n, 4], scene id in column 0 (ascending), columns 1..3 reduced; scene_offsets is WRITTEN first
+ *                  (derived from column 0) and may be handed to the calls below.  An empty scene gets (INT32_MAX, INT32_MIN).
+ *   Reduced in the wave, then the workgroup; one global atomic min / max per workgroup, scene and column.
+ *
+ * lgs_elastic_distort: ONE stage of ElasticDistortion.elastic_distortion(granularity, magnitude) on points[n, 3] in place, for every
+ *   scene whose bit is set in apply_mask.  bounds_in[b, 6]: the cloud's bounds (lgs_aug_bounds, or the previous stage's
+ *   bounds_out).  Per scene, on the device: noise_dim = ((max - min) // granularity) + 3 in float32 as numpy does it; a grid of more
+ *   than max_cells cells leaves the scene untouched and sets bit `scene` of *status (DEVICE int32, OR-ed, never cleared here).
+ *   Noise: noise (DEVICE float32 [b, max_cells * 3], each scene's [dx, dy, dz, 3] block packed at the start of its slot) if not NULL,
+ *   else N(0, 1) by Box-Muller from Philox-4x32-10 with counter = (cell, component, stage, seed >> 32) and key = (seed & 2^32-1,
+ *   scene_seeds[scene]): a scene's field does not depend on the batch around it.  scene_seeds: HOST int32[b] or NULL (zeros).
+ *   Field: two rounds of zero-padded 3-tap box blurs along x, y, z = per axis T^2 of the d x d tridiagonal(1/3) matrix, weights
+ *   count(i, j) / 9 (the interior row is [1,2,3,2,1]/9, the edge rows are smaller), applied as one 125-tap pass with exact integer
+ *   weights.  Apply: trilinear sample on the axes min - g + i g (0 outside), p += sample * magnitude, evaluated in double and rounded
+ *   once.  bounds_out[b, 6] (must not alias bounds_in) = bounds of the cloud after this stage, for the next one.
+ *   workspace: lgs_elastic_workspace_bytes(b, max_cells) bytes.
+ *
+ * lgs_voxelize_batched: lgs_voxelize with one affine per scene (affines: HOST double [b, 12]); column 0 = batch_base + scene.
+ * lgs_coords_flip_shift: coords int32 [n, 4] in place: axis a of scene s becomes max - c where bit a of flip_axes[s] (HOST int32[b])
+ *   is set, max = bounds[s, 3 + a] (lgs_aug_bounds, LGS_AUG_I32X4); then shift[a] (HOST int32[3] or NULL) is added in every scene.
+ * lgs_color_augment: colors float32 [n, 3] in place, per scene by lgs_color_scene, in the reference's order:
+ *   LGS_COLOR_AUTOCONTRAST  f = (1 - blend) f + blend (f - lo) 255 / (hi - lo), lo / hi = bounds[s] (lgs_aug_bounds over these rows).
+ *                           A channel with hi == lo is left unblended (the reference yields inf / NaN there): the one deviation.
+ *   LGS_COLOR_TRANSLATION   f = clip(f + translation, 0, 255)
+ *   LGS_COLOR_JITTER        f = clip(f + jitter_std 255 z, 0, 255), z = noise[n, 3] (DEVICE float32) if not NULL, else Philox with
+ *                           counter = (row within the scene (64 bit), channel, LGS_AUG_STAGE_COLOR ^ seed >> 32), key as above with `seed`
+ *   then f *= scale, then f = f / 255 - 0.5 if normalize.
+ * lgs_aug_status: copies *status to the host and SYNCHRONISES the stream (the lgs_manager_check pattern).
+ * lgs_debug_philox: out[n, 4] = Philox-4x32-10(counter[n, 4], key = (key & 2^32-1, key >> 32)), DEVICE int32 words (tests). */
+#define LGS_AUG_MAX_SCENES 32
+#define LGS_AUG_F32X3 0
+#define LGS_AUG_I32X4 1
+#define LGS_AUG_STAGE_COLOR 16
+#define LGS_COLOR_AUTOCONTRAST 1
+#define LGS_COLOR_TRANSLATION 2
+#define LGS_COLOR_JITTER 4
+typedef struct lgs_color_scene {
+  int32_t flags;          /* LGS_COLOR_* */
+  int32_t seed;           /* the scene's Philox key word */
+  float blend;
+  float translation[3];
+  float jitter_std;
+  float reserved;
+} lgs_color_scene;
+int lgs_aug_bounds(const void *table, int64_t n, int form, int64_t *scene_offsets, int b, void *bounds, void *stream);
+int64_t lgs_elastic_workspace_bytes(int b, int64_t max_cells);
+int lgs_elastic_distort(float *points, int64_t n, const int64_t *scene_offsets, int b, const float *bounds_in, double granularity,
+                        double magnitude, int64_t seed, const int32_t *scene_seeds, int apply_mask, int stage, const float *noise,
+                        int64_t max_cells, void *workspace, float *bounds_out, int32_t *status, void *stream);
+int lgs_voxelize_batched(const float *points, int64_t n, const int64_t *scene_offsets, int b, const double *affines,
+                         int batch_base, int32_t *coords, void *stream);
+int lgs_coords_flip_shift(int32_t *coords, int64_t n, const int64_t *scene_offsets, int b, const int32_t *bounds,
+                          const int32_t *flip_axes, const int32_t *shift, void *stream);
+int lgs_color_augment(float *colors, int64_t n, const int64_t *scene_offsets, int b, const float *bounds,
+                      const lgs_color_scene *scenes, float scale, int normalize, int64_t seed, const float *noise, void *stream);
+int lgs_aug_status(const int32_t *status, int *flags, void *stream);
+int lgs_debug_philox(const int32_t *counters, int64_t n, int64_t key, int32_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

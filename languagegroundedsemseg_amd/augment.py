@@ -1,0 +1,450 @@
+"""The reference's train-time augmentation chain on the device (csrc/lgs_augment.hip).
+
+The reference runs these transforms as numpy / scipy code in DataLoader workers (lib/transforms.py, wired up in
+lib/dataset.py:355-389): ElasticDistortion before the voxeliser; RandomHorizontalFlip, ChromaticAutoContrast, ChromaticTranslation,
+ChromaticJitter (ChromaticScale when configured) after it.  Here a batch is B scenes concatenated on the device, rows of a scene
+contiguous, `scene_offsets` (B + 1 host integers) saying where each begins.
+
+    aug = DeviceAugmentation.from_dataset(ScannetVoxelization2cmDataset, config)      # the one-line switch
+    coords, feats, labels = aug(points, colors, labels, scene_offsets)                 # HIP tensors in, HIP tensors out
+
+Scalar decisions (apply or not, blend factor, translation vector, rigid matrix, seeds) are drawn on the host by `draw`; everything
+per point, per voxel and per noise cell runs in HIP kernels, and nothing before the dedup's own row count synchronises.
+Host tensors raise RuntimeError: there is no CPU path.
+
+Out of scope, refused by name: RandomDropout, HueSaturationTranslation, the clip bound, instance augmentation,
+the paired voxeliser."""
+import ctypes
+import dataclasses
+
+import numpy as np
+import torch
+
+from . import engine
+
+MAX_SCENES = engine.LGS_AUG_MAX_SCENES
+DEFAULT_MAX_CELLS = 1 << 16           # 43 x 40 x 16 = 27 520 cells for an 8 m room at granularity 0.2
+
+
+def _vp(t):
+    return ctypes.c_void_p(t.data_ptr() if t is not None else None)
+
+
+def _stream(device):
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _i32(v):
+    """the low 32 bits of an integer as a C int32"""
+    v = int(v) & 0xffffffff
+    return v - (1 << 32) if v >= (1 << 31) else v
+
+
+def _i64(v):
+    v = int(v) & 0xffffffffffffffff
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def _require_hip(t, what):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise RuntimeError("languagegroundedsemseg_amd.augment runs on the MI355X engine: %s must be a HIP tensor" % what)
+
+
+def _upload(array, device):
+    """host array -> device without a synchronising copy (pinned staging buffer, asynchronous copy)"""
+    return torch.from_numpy(np.ascontiguousarray(array)).pin_memory().to(device, non_blocking=True)
+
+
+def _host_offsets(scene_offsets, n):
+    off = [int(v) for v in (scene_offsets.tolist() if hasattr(scene_offsets, "tolist") else scene_offsets)]
+    if len(off) < 2 or off[0] != 0 or off[-1] != n or any(a > b for a, b in zip(off, off[1:])):
+        raise ValueError("scene_offsets must be B + 1 non-decreasing integers from 0 to the number of rows (%d): %r" % (n, off[:8]))
+    return off
+
+
+def _chunks(off):
+    """scenes in groups of MAX_SCENES -> (first scene, last scene + 1)"""
+    b = len(off) - 1
+    return [(s, min(s + MAX_SCENES, b)) for s in range(0, b, MAX_SCENES)]
+
+
+def aug_bounds(table, scene_offsets=None, batch_size=None):
+    """Per-scene min / max of three columns -> (bounds [B, 6] on the device, device scene offsets [B + 1]).
+    float32 [N, 3] with `scene_offsets` (a device int64 tensor, B <= 32), or int32 [N, 4] coordinates with `batch_size`: the scene
+    id is column 0 and the offsets are derived from it on the device."""
+    _require_hip(table, "table")
+    t = table.contiguous()
+    dev = t.device
+    with torch.cuda.device(dev):
+        if t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 3:
+            _require_hip(scene_offsets, "scene_offsets (device form)")
+            b, form, off = scene_offsets.shape[0] - 1, engine.LGS_AUG_F32X3, scene_offsets
+        elif t.dtype == torch.int32 and t.dim() == 2 and t.shape[1] == 4:
+            b, form = int(batch_size), engine.LGS_AUG_I32X4
+            off = torch.empty(b + 1, dtype=torch.int64, device=dev)
+        else:
+            raise ValueError("aug_bounds takes float32 [N, 3] or int32 [N, 4]")
+        bounds = torch.empty((b, 6), dtype=t.dtype, device=dev)
+        engine.check(engine.lib().lgs_aug_bounds(_vp(t), t.shape[0], form, _vp(off), b, _vp(bounds), _stream(dev)))
+    return bounds, off
+
+
+def aug_status(status):
+    """Reads the device status words of an elastic call (this SYNCHRONISES) -> scenes whose noise grid exceeded max_cells"""
+    out = []
+    for chunk, word in enumerate(status):
+        f = ctypes.c_int(0)
+        with torch.cuda.device(word.device):
+            engine.check(engine.lib().lgs_aug_status(_vp(word), ctypes.byref(f), _stream(word.device)))
+        out += [chunk * MAX_SCENES + s for s in range(MAX_SCENES) if (f.value >> s) & 1]
+    return out
+
+
+def _pack_noise(noise, b, max_cells, device):
+    host = np.zeros((b, max_cells * 3), np.float32)
+    for s, a in enumerate(noise):
+        if a is None:
+            continue
+        a = np.asarray(a, np.float32).reshape(-1)
+        if a.size > max_cells * 3:
+            raise ValueError("noise of scene %d has %d values, more than max_cells * 3" % (s, a.size))
+        host[s, :a.size] = a
+    return _upload(host, device)
+
+
+def _elastic_stage(points, off_dev, b, bounds_in, granularity, magnitude, seed, scene_seeds, apply, stage, noise_dev, max_cells,
+                   workspace, status):
+    """one stage on at most MAX_SCENES scenes, in place -> bounds of the displaced cloud"""
+    dev = points.device
+    L = engine.lib()
+    bounds_out = torch.empty((b, 6), dtype=torch.float32, device=dev)
+    seeds = (ctypes.c_int32 * b)(*[_i32(v) for v in scene_seeds])
+    mask = sum(1 << s for s in range(b) if apply[s])
+    mask = mask - (1 << 32) if mask >= (1 << 31) else mask
+    engine.check(L.lgs_elastic_distort(_vp(points), points.shape[0], _vp(off_dev), b, _vp(bounds_in), float(granularity), float(magnitude),
+                                       _i64(seed), seeds, mask, int(stage), _vp(noise_dev),
+                                       int(max_cells), _vp(workspace), _vp(bounds_out), _vp(status), _stream(dev)))
+    return bounds_out
+
+
+def _elastic_workspace(b, max_cells, device):
+    nbytes = int(engine.lib().lgs_elastic_workspace_bytes(b, int(max_cells)))
+    if nbytes <= 0:
+        raise ValueError("max_cells must be 27 .. 2^26")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def elastic_distortion(points, scene_offsets, granularity, magnitude, seed, noise=None, max_cells=DEFAULT_MAX_CELLS, scene_seeds=None,
+                       apply=None, stage=0, return_state=False):
+    """ElasticDistortion.elastic_distortion(granularity, magnitude) on every scene of a batch -> the displaced points (a new tensor).
+    noise: None (Philox, keyed by seed / scene_seeds / stage) or one array per scene, [dx, dy, dz, 3] in C order (teacher-forced).
+    A scene whose noise grid has more than max_cells cells is left as it is; aug_status(state["status"]) names such scenes.
+    return_state: also return {"status", "bounds", "noise", "field"} (device tensors, per chunk of 32 scenes)."""
+    _require_hip(points, "points")
+    pts = points.detach().to(torch.float32).contiguous().clone()
+    assert pts.dim() == 2 and pts.shape[1] == 3
+    off = _host_offsets(scene_offsets, pts.shape[0])
+    B = len(off) - 1
+    scene_seeds = [0] * B if scene_seeds is None else list(scene_seeds)
+    apply = [True] * B if apply is None else list(apply)
+    dev = pts.device
+    state = {"status": [], "bounds": [], "noise": [], "field": []}
+    with torch.cuda.device(dev):
+        for s0, s1 in _chunks(off):
+            b = s1 - s0
+            rows = pts[off[s0]:off[s1]]
+            off_dev = _upload(np.asarray(off[s0:s1 + 1], np.int64) - off[s0], dev)
+            bounds, _ = aug_bounds(rows, off_dev)
+            ws = _elastic_workspace(b, max_cells, dev)
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+            noise_dev = None if noise is None else _pack_noise(noise[s0:s1], b, max_cells, dev)
+            out = _elastic_stage(rows, off_dev, b, bounds, granularity, magnitude, seed, scene_seeds[s0:s1], apply[s0:s1], stage, noise_dev,
+                                 max_cells, ws, status)
+            state["status"].append(status)
+            state["bounds"].append(out)
+            half = ws.numel() // 2
+            state["noise"].append(noise_dev if noise_dev is not None else ws[:half].view(torch.float32)[:b * max_cells * 3].view(b, -1))
+            state["field"].append(ws[half:].view(torch.float32)[:b * max_cells * 3].view(b, -1))
+    return (pts, state) if return_state else pts
+
+
+def voxelize_batched(points, scene_offsets, matrices, batch_base=0, offsets_dev=None):
+    """ME.utils.voxelize with one rigid matrix per scene: points [N, 3] -> int32 [N, 4] = (scene, floor(M_s (x, y, z, 1))).
+    matrices: [B, 4, 4] or [B, 3, 4] (host).  More than 32 scenes are split into several launches."""
+    _require_hip(points, "points")
+    pts = points.detach().to(torch.float32).contiguous()
+    assert pts.dim() == 2 and pts.shape[1] == 3
+    off = _host_offsets(scene_offsets, pts.shape[0])
+    B = len(off) - 1
+    m = np.asarray(matrices, dtype=np.float64)
+    assert m.shape[0] == B and m.shape[1] in (3, 4) and m.shape[2] == 4
+    dev = pts.device
+    out = torch.empty((pts.shape[0], 4), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        for s0, s1 in _chunks(off):
+            b = s1 - s0
+            rows, dst = pts[off[s0]:off[s1]], out[off[s0]:off[s1]]
+            if offsets_dev is not None and B <= MAX_SCENES:
+                off_dev = offsets_dev
+            else:
+                off_dev = _upload(np.asarray(off[s0:s1 + 1], np.int64) - off[s0], dev)
+            a = np.ascontiguousarray(m[s0:s1, :3, :4]).reshape(-1)
+            a12 = (ctypes.c_double * (12 * b))(*a.tolist())
+            engine.check(engine.lib().lgs_voxelize_batched(_vp(rows), rows.shape[0], _vp(off_dev), b, a12, int(batch_base) + s0, _vp(dst),
+                                                           _stream(dev)))
+    return out
+
+
+def _flip_words(flip_axes, b):
+    f = np.asarray(flip_axes)
+    if f.ndim == 2:                   # [B, 3] booleans
+        f = (f.astype(bool) * np.array([1, 2, 4])).sum(1)
+    f = f.astype(np.int64).reshape(-1)
+    assert f.shape[0] == b
+    return (ctypes.c_int32 * b)(*[int(v) & 7 for v in f])
+
+
+def horizontal_flip(coords, flip_axes, shift=None, batch_size=None, return_offsets=False):
+    """RandomHorizontalFlip's coordinate step on int32 [n, 4] batch-tagged coordinates -> new coordinates.
+    flip_axes: per scene a bit mask (bit a = axis a) or [B, 3] booleans; a flipped axis becomes max - c, the max over the scene's
+    rows.  shift: three integers added to every scene afterwards (the trainer's per-batch coordinate shift)."""
+    _require_hip(coords, "coords")
+    assert coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 4
+    c = coords.contiguous().clone()
+    b = int(batch_size) if batch_size is not None else len(np.asarray(flip_axes))
+    if b > MAX_SCENES:
+        raise ValueError("horizontal_flip takes at most %d scenes per call" % MAX_SCENES)
+    with torch.cuda.device(c.device):
+        bounds, off = aug_bounds(c, batch_size=b)
+        sh = None if shift is None else (ctypes.c_int32 * 3)(*[int(v) for v in shift])
+        engine.check(engine.lib().lgs_coords_flip_shift(_vp(c), c.shape[0], _vp(off), b, _vp(bounds), _flip_words(flip_axes, b), sh,
+                                                        _stream(c.device)))
+    return (c, off) if return_offsets else c       # off: the voxel rows' scene offsets, derived on the device from column 0
+
+
+@dataclasses.dataclass
+class ColorParams:
+    """one scene's colour decisions; None = that transform is not applied"""
+    blend: float = None               # ChromaticAutoContrast's blend factor
+    translation: tuple = None         # ChromaticTranslation's vector (3 floats, in 0 .. 255 units)
+    jitter_std: float = None          # ChromaticJitter's std (a fraction of 255)
+    seed: int = 0
+
+
+def chromatic_augment(colors, scene_offsets, scenes, scale=1.0, normalize=False, seed=0, noise=None):
+    """ChromaticAutoContrast -> ChromaticTranslation -> ChromaticJitter -> ChromaticScale -> (f / 255 - 0.5) on float32 [n, 3] colours
+    -> new colours.  scene_offsets: B + 1 host integers, or a device int64 tensor (e.g. the one aug_bounds derives from coordinates).
+    scenes: one ColorParams per scene.  noise: device float32 [n, 3] standard normals for the jitter (teacher-forced) or None (Philox).
+    A channel whose min equals its max over the scene is left unblended by the autocontrast (the reference yields inf / NaN)."""
+    _require_hip(colors, "colors")
+    f = colors.detach().to(torch.float32).contiguous().clone()
+    assert f.dim() == 2 and f.shape[1] == 3
+    dev = f.device
+    b = len(scenes)
+    if b > MAX_SCENES:
+        raise ValueError("chromatic_augment takes at most %d scenes per call" % MAX_SCENES)
+    rec = (engine.ColorScene * b)()
+    for s, p in enumerate(scenes):
+        flags = 0
+        if p.blend is not None:
+            flags |= engine.LGS_COLOR_AUTOCONTRAST
+            rec[s].blend = float(p.blend)
+        if p.translation is not None:
+            flags |= engine.LGS_COLOR_TRANSLATION
+            for a in range(3):
+                rec[s].translation[a] = float(p.translation[a])
+        if p.jitter_std is not None:
+            flags |= engine.LGS_COLOR_JITTER
+            rec[s].jitter_std = float(p.jitter_std)
+        rec[s].flags = flags
+        rec[s].seed = _i32(p.seed)
+    with torch.cuda.device(dev):
+        if isinstance(scene_offsets, torch.Tensor) and scene_offsets.is_cuda:
+            off_dev = scene_offsets
+        else:
+            off_dev = _upload(np.asarray(_host_offsets(scene_offsets, f.shape[0]), np.int64), dev)
+        assert off_dev.shape[0] == b + 1
+        bounds, _ = aug_bounds(f, off_dev)
+        nz = None
+        if noise is not None:
+            _require_hip(noise, "noise")
+            nz = noise.to(torch.float32).contiguous()
+            assert nz.shape == f.shape
+        engine.check(engine.lib().lgs_color_augment(_vp(f), f.shape[0], _vp(off_dev), b, _vp(bounds), rec, float(scale), int(bool(normalize)),
+                                                    _i64(seed), _vp(nz), _stream(dev)))
+    return f
+
+
+def philox_words(counters, key):
+    """Philox-4x32-10 blocks of the device generator: counters uint32-valued [n, 4] (device int32) -> int32 [n, 4] words (tests)"""
+    _require_hip(counters, "counters")
+    c = counters.to(torch.int32).contiguous()
+    out = torch.empty_like(c)
+    with torch.cuda.device(c.device):
+        engine.check(engine.lib().lgs_debug_philox(_vp(c), c.shape[0], _i64(key), _vp(out),
+                                                   _stream(c.device)))
+    return out
+
+
+# ---- the chain
+@dataclasses.dataclass
+class AugmentPlan:
+    """every scalar decision of one batch (host values); see DeviceAugmentation.draw"""
+    elastic: np.ndarray               # [B] bool       ElasticDistortion applies (p = 0.95)
+    flip_axes: np.ndarray             # [B] int        bit a set = horizontal axis a is flipped (0.95, then 0.5 per axis)
+    autocontrast: np.ndarray          # [B] bool       (p = 0.2)
+    blend: np.ndarray                 # [B] float      its blend factor
+    translate: np.ndarray             # [B] bool       (p = 0.95)
+    translation: np.ndarray           # [B, 3] float   (rand - 0.5) * 255 * 2 * ratio
+    jitter: np.ndarray                # [B] bool       (p = 0.95)
+    angles: np.ndarray                # [B, 3] float   rotation angle about x, y, z
+    order: np.ndarray                 # [B, 3] int     the order in which the three rotations are multiplied
+    scale: np.ndarray                 # [B] float      1 / voxel_size * U(scale bounds)
+    matrices: np.ndarray              # [B, 4, 4]      M_r @ M_v of Voxelizer.get_transformation_matrix
+    scene_seeds: np.ndarray           # [B] uint32     per-scene Philox key word
+    seed: int                         # the batch's 64-bit Philox seed
+    shift: np.ndarray                 # [3] int        the trainer's per-batch coordinate shift (zeros unless coordinate_shift)
+
+
+def axis_rotation(axis, theta):
+    """expm(cross(eye(3), e_axis * theta)), lib/voxelizer.py:9-10, in closed form"""
+    c, s = np.cos(theta), np.sin(theta)
+    i, j = (axis + 1) % 3, (axis + 2) % 3
+    r = np.eye(3)
+    r[i, i], r[i, j], r[j, i], r[j, j] = c, -s, s, c
+    return r
+
+
+_REFUSED = ("random_dropout", "hue_saturation", "clip_bound", "instance_augmentation")
+
+
+class DeviceAugmentation:
+    """The reference's default train-time chain for one batch: elastic stages -> per-scene rigid matrix + floor -> dedup (first
+    occurrence wins) -> flip on the voxel rows -> colour on the voxel rows.  `draw` makes the host decisions, `__call__` runs the
+    kernels.  At most 32 scenes per batch."""
+
+    def __init__(self, voxel_size, elastic_params=((0.2, 0.4), (0.8, 1.6)), rotation_bound=None, scale_bound=None, rotation_axis="z",
+                 color_trans_ratio=0.1, color_jitter_std=0.05, color_scale=1.0, normalize_color=False, coordinate_shift=False,
+                 max_cells=DEFAULT_MAX_CELLS, seed=0, random_dropout=None, hue_saturation=None, clip_bound=None,
+                 instance_augmentation=None, num_pairs=1):
+        given = dict(random_dropout=random_dropout, hue_saturation=hue_saturation, clip_bound=clip_bound,
+                     instance_augmentation=instance_augmentation)
+        for name in _REFUSED:
+            if given[name] is not None:
+                raise NotImplementedError("DeviceAugmentation: %s is not part of the device chain (DESIGN.md section 8)" % name)
+        if num_pairs != 1:
+            raise NotImplementedError("DeviceAugmentation: the paired voxeliser (num_pairs == 2) is not part of the device chain")
+        self.voxel_size = float(voxel_size)
+        self.elastic_params = tuple((float(g), float(m)) for g, m in elastic_params) if elastic_params is not None else ()
+        self.rotation_bound = rotation_bound
+        self.scale_bound = scale_bound
+        self.upright = {"x": 0, "y": 1, "z": 2}[rotation_axis.lower()]
+        self.color_trans_ratio = float(color_trans_ratio)
+        self.color_jitter_std = float(color_jitter_std)
+        self.color_scale = float(color_scale)
+        self.normalize_color = bool(normalize_color)
+        self.coordinate_shift = bool(coordinate_shift)
+        self.max_cells = int(max_cells)
+        self.rng = np.random.default_rng(seed)
+
+    @classmethod
+    def from_dataset(cls, DatasetClass, config, **kw):
+        """The chain a reference dataset class and config describe (lib/dataset.py:337-389, lib/datasets/scannet.py)."""
+        if getattr(DatasetClass, "CLIP_BOUND", None) is not None:
+            kw.setdefault("clip_bound", DatasetClass.CLIP_BOUND)
+        if float(getattr(config, "data_aug_patch_dropout_ratio", 0.35)) == 0.0:
+            kw.setdefault("random_dropout", 0.2)          # lib/dataset.py:385 adds RandomDropout in that case only
+        elastic = DatasetClass.ELASTIC_DISTORT_PARAMS if getattr(config, "elastic_distortion", True) else None
+        return cls(voxel_size=DatasetClass.VOXEL_SIZE, elastic_params=elastic,
+                   rotation_bound=DatasetClass.ROTATION_AUGMENTATION_BOUND, scale_bound=DatasetClass.SCALE_AUGMENTATION_BOUND,
+                   rotation_axis=DatasetClass.ROTATION_AXIS, color_trans_ratio=config.data_aug_color_trans_ratio,
+                   color_jitter_std=config.data_aug_color_jitter_std, color_scale=config.data_aug_color_scaling_factor,
+                   normalize_color=config.normalize_color, **kw)
+
+    def draw(self, batch_size):
+        """Every decision the reference draws with random.random() / np.random.uniform, for each scene of a batch."""
+        B, r = int(batch_size), self.rng
+        horz = [a for a in range(3) if a != self.upright]
+        elastic = r.random(B) < 0.95
+        flip_on, flip_ax = r.random(B) < 0.95, r.random((B, 3)) < 0.5
+        flip_axes = np.zeros(B, np.int64)
+        for a in horz:
+            flip_axes |= (flip_on & flip_ax[:, a]).astype(np.int64) << a
+        autocontrast, blend = r.random(B) < 0.2, r.random(B)
+        translate = r.random(B) < 0.95
+        translation = (r.random((B, 3)) - 0.5) * 255 * 2 * self.color_trans_ratio
+        jitter = r.random(B) < 0.95
+        angles = np.zeros((B, 3))
+        if self.rotation_bound is not None:
+            for a, bound in enumerate(self.rotation_bound):
+                if bound is not None:
+                    angles[:, a] = r.uniform(bound[0], bound[1], B)
+        order = np.stack([r.permutation(3) for _ in range(B)]) if B else np.zeros((0, 3), np.int64)
+        scale = np.full(B, 1.0 / self.voxel_size)
+        if self.scale_bound is not None:
+            scale = scale * r.uniform(self.scale_bound[0], self.scale_bound[1], B)
+        matrices = np.zeros((B, 4, 4))
+        for s in range(B):
+            rots = [axis_rotation(a, angles[s, a]) for a in range(3)]
+            m_r, m_v = np.eye(4), np.eye(4)
+            m_r[:3, :3] = rots[order[s, 0]] @ rots[order[s, 1]] @ rots[order[s, 2]]
+            np.fill_diagonal(m_v[:3, :3], scale[s])
+            matrices[s] = m_r @ m_v
+        scene_seeds = r.integers(0, 1 << 32, B, dtype=np.uint64).astype(np.uint32)
+        seed = int(r.integers(0, 1 << 63))
+        shift = np.floor(r.random(3) * 100).astype(np.int64) if self.coordinate_shift else np.zeros(3, np.int64)
+        return AugmentPlan(elastic, flip_axes, autocontrast, blend, translate, translation, jitter, angles, order, scale, matrices,
+                           scene_seeds, seed, shift)
+
+    def color_params(self, plan):
+        return [ColorParams(blend=float(plan.blend[s]) if plan.autocontrast[s] else None,
+                            translation=tuple(plan.translation[s]) if plan.translate[s] else None,
+                            jitter_std=self.color_jitter_std if plan.jitter[s] else None, seed=int(plan.scene_seeds[s]))
+                for s in range(len(plan.elastic))]
+
+    def __call__(self, points, colors, labels, scene_offsets, plan=None, elastic_noise=None, jitter_noise=None, return_state=False):
+        """points [N, 3], colors [N, 3], labels [N] (HIP tensors), scene_offsets (B + 1 host integers)
+        -> (coords [n, 4] int32, feats [n, 3] float32, labels [n]) of the surviving voxel rows.
+        elastic_noise: per stage a list of per-scene noise arrays; jitter_noise: callable(n) or device [n, 3] normals (teacher-forced)."""
+        for t, what in ((points, "points"), (colors, "colors"), (labels, "labels")):
+            _require_hip(t, what)
+        dev = points.device
+        off = _host_offsets(scene_offsets, points.shape[0])
+        B = len(off) - 1
+        if B > MAX_SCENES:
+            raise ValueError("DeviceAugmentation takes at most %d scenes per batch" % MAX_SCENES)
+        plan = self.draw(B) if plan is None else plan
+        state = {"status": [], "stages": []}
+        previous = torch.cuda.get_sync_debug_mode()
+        torch.cuda.set_sync_debug_mode("error")        # nothing before the dedup's own row count may synchronise
+        try:
+            with torch.cuda.device(dev):
+                pts = points.detach().to(torch.float32).contiguous().clone()
+                off_dev = _upload(np.asarray(off, np.int64), dev)
+                if self.elastic_params and plan.elastic.any():
+                    bounds, _ = aug_bounds(pts, off_dev)
+                    ws = _elastic_workspace(B, self.max_cells, dev)
+                    status = torch.zeros(1, dtype=torch.int32, device=dev)
+                    for stage, (g, m) in enumerate(self.elastic_params):
+                        nz = None if elastic_noise is None else _pack_noise(elastic_noise[stage], B, self.max_cells, dev)
+                        bounds = _elastic_stage(pts, off_dev, B, bounds, g, m, plan.seed, plan.scene_seeds, plan.elastic, stage, nz,
+                                                self.max_cells, ws, status)
+                        if return_state:
+                            state["stages"].append(pts.clone())
+                    state["status"].append(status)
+                coords = voxelize_batched(pts, off, plan.matrices, offsets_dev=off_dev)
+        finally:
+            torch.cuda.set_sync_debug_mode(previous)
+        from .me.utils import sparse_quantize
+        keep = sparse_quantize(coords, return_maps_only=True)          # first occurrence wins, indices ascending (one host sync)
+        coords, off_vox = horizontal_flip(coords.index_select(0, keep), plan.flip_axes, shift=plan.shift, batch_size=B, return_offsets=True)
+        feats = colors.detach().to(torch.float32).index_select(0, keep)
+        if callable(jitter_noise):
+            jitter_noise = jitter_noise(feats.shape[0])
+        feats = chromatic_augment(feats, off_vox, self.color_params(plan), scale=self.color_scale, normalize=self.normalize_color,
+                                  seed=plan.seed, noise=jitter_noise)
+        out = (coords, feats, labels.index_select(0, keep))
+        if return_state:
+            state["points"], state["keep"] = pts, keep
+            return out + (state,)
+        return out

@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "lgs_common.h"
+#include "lgs_philox.h"
 
 namespace lgs {
 
@@ -30,20 +31,6 @@ constexpr int kSupWaves = 4;           // rows (wavefronts) per workgroup
 constexpr float kNormEps = 1e-12f;     // F.normalize's eps
 constexpr float kL2Eps = 1e-7f;        // PointSupConLoss.py:56
 
-// ---- Philox-4x32-10 (Salmon et al., SC'11), plain C++
-__device__ inline void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[1] = (uint32_t)p1;
-    c[3] = (uint32_t)p0;
-    c[0] = n0;
-    c[2] = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
 // uniform integer in [0, t), t >= 1
 __device__ inline int64_t below(uint64_t r, int64_t t) { return (int64_t)__umul64hi(r, (uint64_t)t); }
 

@@ -11,6 +11,9 @@ from . import build as _build
 
 LGS_F32, LGS_BF16 = 0, 1
 LGS_SUPCON_COS, LGS_SUPCON_L2 = 0, 1     # `distance` of lgs_supcon_forward / lgs_supcon_backward
+LGS_AUG_MAX_SCENES = 32                  # scenes per call of the lgs_aug_* / lgs_elastic_* / lgs_color_* entry points
+LGS_AUG_F32X3, LGS_AUG_I32X4 = 0, 1      # `form` of lgs_aug_bounds
+LGS_COLOR_AUTOCONTRAST, LGS_COLOR_TRANSLATION, LGS_COLOR_JITTER = 1, 2, 4     # lgs_color_scene.flags
 ABI_VERSION = 18     # LGS_ABI_VERSION of include/lgs_engine.h
 
 
@@ -118,6 +121,12 @@ class KmapRelationInfo(ctypes.Structure):
                [("pairs_only", ctypes.c_int * 2), ("served_by_old_entry", ctypes.c_int)]
 
 
+class ColorScene(ctypes.Structure):
+    """lgs_color_scene: one scene's record of lgs_color_augment"""
+    _fields_ = [("flags", ctypes.c_int32), ("seed", ctypes.c_int32), ("blend", ctypes.c_float), ("translation", ctypes.c_float * 3),
+                ("jitter_std", ctypes.c_float), ("reserved", ctypes.c_float)]
+
+
 class BnParams(ctypes.Structure):
     """lgs_bn_params"""
     _fields_ = [("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p), ("running_mean", ctypes.c_void_p), ("running_var", ctypes.c_void_p),
@@ -200,6 +209,8 @@ EXPORTS = [
     "lgs_comm_unique_id", "lgs_comm_create", "lgs_comm_create_ipc", "lgs_comm_ipc_open", "lgs_comm_destroy", "lgs_comm_world", "lgs_bn_sync_workspace_bytes",
     "lgs_bn_forward_sync", "lgs_bn_backward_sync",
     "lgs_voxelize", "lgs_label_vote", "lgs_cluster_workspace_bytes", "lgs_cluster", "lgs_sgd_step",
+    "lgs_aug_bounds", "lgs_elastic_workspace_bytes", "lgs_elastic_distort", "lgs_voxelize_batched", "lgs_coords_flip_shift",
+    "lgs_color_augment", "lgs_aug_status", "lgs_debug_philox",
 ]
 
 
@@ -286,6 +297,13 @@ def lib():
         "lgs_supcon_sample": [vp, i64, ci, i64, vp, vp, vp, vp, vp, ci, ci, i64, vp, vp, vp],
         "lgs_supcon_forward": [vp, i64, ci, vp, vp, ci, vp, ci, i64, ci, ci, vp, vp, vp, vp, ci, vp],
         "lgs_supcon_backward": [vp, i64, ci, vp, vp, ci, vp, ci, i64, ci, ci, vp, vp, vp, vp, vp, ci, vp],
+        "lgs_aug_bounds": [vp, i64, ci, vp, ci, vp, vp],
+        "lgs_elastic_distort": [vp, i64, vp, ci, vp, ctypes.c_double, ctypes.c_double, i64, vp, ci, ci, vp, i64, vp, vp, vp, vp],
+        "lgs_voxelize_batched": [vp, i64, vp, ci, ctypes.POINTER(ctypes.c_double), ci, vp, vp],
+        "lgs_coords_flip_shift": [vp, i64, vp, ci, vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), vp],
+        "lgs_color_augment": [vp, i64, vp, ci, vp, ctypes.POINTER(ColorScene), cf, ci, i64, vp, vp],
+        "lgs_aug_status": [vp, pi, vp],
+        "lgs_debug_philox": [vp, i64, i64, vp, vp],
         "lgs_comm_unique_id": [vp],
         "lgs_comm_create": [vp, ci, ci, ci, ctypes.POINTER(vp)],
         "lgs_comm_create_ipc": [ci, ci, ci, ctypes.POINTER(vp), vp],
@@ -312,6 +330,8 @@ def lib():
     L.lgs_seg_workspace_bytes.argtypes = [vp, ci]
     L.lgs_in_workspace_bytes.restype = i64
     L.lgs_in_workspace_bytes.argtypes = [vp, ci]
+    L.lgs_elastic_workspace_bytes.restype = i64
+    L.lgs_elastic_workspace_bytes.argtypes = [ci, i64]
     L.lgs_cluster_workspace_bytes.restype = i64
     L.lgs_cluster_workspace_bytes.argtypes = [i64]
     L.lgs_conv_workspace_bytes.restype = i64

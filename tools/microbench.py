@@ -1,5 +1,5 @@
 """Per-op timings on the GPU (HIP events on torch's current stream) for the hot layer shapes.
-usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal | supcon]"""
+usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal | supcon | augment]"""
 import os
 import sys
 import time
@@ -598,7 +598,78 @@ def supcon():
         del x, xr, saved
 
 
+def augment():
+    """the train-time augmentation chain on the benchmark's 8-scene batch, raw points before the dedup; the numpy
+    restatement of the same stages (tests/augment_reference.py, one scene, one thread) beside it"""
+    from languagegroundedsemseg_amd import augment as A
+    coords, feats, labels = make_batch(list(range(8)), n_target=150000, shift_seed=0)
+    rng = np.random.default_rng(0)
+    order = np.argsort(coords[:, 0], kind="stable")
+    coords, labels = coords[order], labels[order]
+    rep = np.repeat(coords, 2, 0)                                   # ~2 points per voxel, like a 2 cm voxelisation of ScanNet
+    pts = ((rep[:, 1:].astype(np.float64) + rng.uniform(0.05, 0.95, (rep.shape[0], 3))) * 0.02).astype(np.float32)
+    off = np.concatenate([[0], np.cumsum(np.bincount(rep[:, 0], minlength=8))]).tolist()
+    for s in range(8):                                              # every scene at its own origin, as a dataset hands it over
+        pts[off[s]:off[s + 1]] -= pts[off[s]:off[s + 1]].min(0)
+    cols = np.floor(rng.random(pts.shape) * 256).astype(np.float32)
+    p, c, lab = torch.from_numpy(pts).to(DEV), torch.from_numpy(cols).to(DEV), torch.from_numpy(np.repeat(labels, 2)).to(DEV)
+    n = p.shape[0]
+    aug = A.DeviceAugmentation(voxel_size=0.02, rotation_bound=((-np.pi / 64, np.pi / 64), (-np.pi / 64, np.pi / 64), (-np.pi, np.pi)),
+                               scale_bound=(0.9, 1.1), normalize_color=True, seed=1)
+    plan = aug.draw(8)
+    plan.elastic[:], plan.autocontrast[:], plan.translate[:], plan.jitter[:] = True, True, True, True
+    plan.flip_axes[:] = 3
+    print("%d points in 8 scenes, extents up to %s m" % (n, np.round(max(pts[off[s]:off[s + 1]].max(0).max() for s in range(8)), 2)))
+    off_dev = torch.tensor(off, dtype=torch.int64, device=DEV)
+
+    def show(name, ms, rows=n):
+        print("%-44s %8.3f ms per batch  %8.1f M points/s" % (name, ms, rows / ms / 1e3))
+    show("bounds (fp32 [N, 3])", timeit(lambda: A.aug_bounds(p, off_dev)))
+    for stage, (g, m) in enumerate(aug.elastic_params):
+        show("elastic stage %d (granularity %.1f), incl. bounds" % (stage + 1, g),
+             timeit(lambda: A.elastic_distortion(p, off, g, m, seed=3, scene_seeds=plan.scene_seeds, stage=stage)))
+    show("batched voxelise", timeit(lambda: A.voxelize_batched(p, off, plan.matrices)))
+    vox = A.voxelize_batched(p, off, plan.matrices)
+    keep = ME.utils.sparse_quantize(vox, return_maps_only=True)
+    show("dedup (engine insert, existing)", timeit(lambda: ME.utils.sparse_quantize(vox, return_maps_only=True)))
+    vc, vf = vox.index_select(0, keep), c.index_select(0, keep)
+    nv = vc.shape[0]
+    show("flip + shift on %d voxel rows, incl. bounds" % nv, timeit(lambda: A.horizontal_flip(vc, plan.flip_axes, batch_size=8)), nv)
+    _, off_v = A.aug_bounds(vc, batch_size=8)
+    show("colour on %d voxel rows, incl. bounds" % nv, timeit(lambda: A.chromatic_augment(vf, off_v, aug.color_params(plan), normalize=True, seed=5)), nv)
+    t_chain = timeit(lambda: aug(p, c, lab, off, plan=plan))
+    show("chain (elastic x2, voxelise, dedup, flip, colour)", t_chain)
+    print("chain = %.1f %% of a 27 ms training step" % (100 * t_chain / 27.0))
+    assert A.aug_status([torch.zeros(1, dtype=torch.int32, device=DEV)]) == []
+    # the numpy restatement on scene 0, one thread
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import augment_reference as ar
+    torch.set_num_threads(1)
+    s0 = pts[off[0]:off[1]]
+    t_cpu = {}
+    cur = s0
+    for stage, (g, m) in enumerate(aug.elastic_params):
+        t0 = time.perf_counter()
+        noise = np.random.default_rng(stage).standard_normal(tuple(ar.noise_dims(cur, g)) + (3,)).astype(np.float32)
+        cur = ar.elastic_stage(cur, noise, g, m).astype(np.float32)
+        t_cpu["elastic stage %d" % (stage + 1)] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    ar.color_chain(cols[off[0]:off[1]], blend=0.5, translation=(3.0, -4.0, 5.0), jitter_std=0.05,
+                   jitter_noise=np.random.default_rng(9).standard_normal((len(s0), 3)), normalize=True)
+    t_cpu["colour"] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    ar.flip(np.floor(cur / 0.02), (0, 1))
+    t_cpu["flip"] = time.perf_counter() - t0
+    for k, v in t_cpu.items():
+        print("numpy restatement, scene 0 (%d points), 1 thread: %-16s %8.1f ms" % (len(s0), k, v * 1e3))
+    print("numpy restatement, scene 0, these stages together: %.1f ms (x 8 scenes = %.0f ms per batch; device chain %.2f ms)"
+          % (sum(t_cpu.values()) * 1e3, 8 * sum(t_cpu.values()) * 1e3, t_chain))
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "augment":
+        augment()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "supcon":
         supcon()
         sys.exit(0)
