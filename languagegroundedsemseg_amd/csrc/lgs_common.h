@@ -107,6 +107,15 @@ __device__ inline uint16_t f32_to_bf16(float f) {  // round to nearest even
 }
 __device__ inline float ld_elem(const float *p) { return *p; }
 __device__ inline float ld_elem(const bf16_t *p) { return bf16_to_f32(*p); }
+// pad rows [n, c] -> [n, cpad] (zero fill) for channel counts that are not a multiple of the load width (lgs_conv.hip, lgs_wgrad.hip)
+template <typename T>
+__global__ void k_pad_rows(const T *__restrict__ src, int64_t n, int c, int cpad, T *__restrict__ dst) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * cpad) return;
+  int64_t r = i / cpad;
+  int ch = (int)(i % cpad);
+  dst[i] = ch < c ? src[r * c + ch] : (T)0;
+}
 // LDS-DMA kernels: the LDS destination of a buffer_load ... lds, and s_waitcnt vmcnt(n) with expcnt / lgkmcnt left alone (gfx9 encoding)
 #define LGS_AS3(p) ((__attribute__((address_space(3))) void *)(p))
 #define LGS_VMCNT(n) __builtin_amdgcn_s_waitcnt((((n) & 15) | (7 << 4) | (15 << 8) | (((n) >> 4) << 14)))

@@ -177,17 +177,7 @@ __global__ void k_pack_weights_batch(const lgs_pack_desc *__restrict__ descs) {
   else dst[idx] = pack_one<float>(e.weight, e.K, e.cin_w, e.cout_w, e.transposed, e.mirror, e.g_real, e.o_real, e.ncp, e.nbp, idx);
 }
 
-// pad rows [n, c] -> [n, cpad] (zero fill) for channel counts that are not a multiple of the load width
-template <typename T>
-__global__ void k_pad_rows(const T *__restrict__ src, int64_t n, int c, int cpad, T *__restrict__ dst) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n * cpad) return;
-  int64_t r = i / cpad;
-  int ch = (int)(i % cpad);
-  dst[i] = ch < c ? src[r * c + ch] : (T)0;
-}
-
-// inverse of k_pad_rows: [n, cpad] -> [n, c]
+// inverse of k_pad_rows (lgs_common.h): [n, cpad] -> [n, c]
 template <typename T>
 __global__ void k_unpad_rows(const T *__restrict__ src, int64_t n, int c, int cpad, T *__restrict__ dst) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

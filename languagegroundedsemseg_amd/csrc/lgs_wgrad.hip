@@ -14,8 +14,7 @@
 // 32x32x16 bf16 MFMA operand layout; the row stride is chosen = 64 (mod 256) bytes so the transposing
 // reads are bank-conflict free.  No workgroup barriers.  Partials per wave slot are written once and folded
 // by k_wgrad_reduce in a fixed order (deterministic, no float atomics).
-// fp32 path (k_wgrad_f32): v_mfma_f32_32x32x2_f32 takes ONE element per lane, so rows are read straight
-// from HBM in operand order (32 consecutive channels of 2 pairs per instruction) -- exact fp32.
+// fp32 path: three kernels over one pair-list skeleton, described with the skeleton below.
 #include "lgs_common.h"
 
 #include <stdlib.h>
@@ -23,152 +22,135 @@
 
 namespace lgs {
 
-// ------------------------------------------------------------------------------------ fp32 (exact) path
+// ------------------------------------------------------------------------------------ fp32 path: the pair-list skeleton
+// Grid (S slots, K offsets, column tiles x groups of 4 input blocks), 256 threads.  A workgroup owns the positions
+// [blockIdx.x * span, + span) of one kernel offset k and a tile of 128 input channels (one 32-channel block per wave; waves past
+// cin_pad idle but keep the barriers) by NCB x 32 gradient channels.  It walks its positions in chunks of kWgChunk: compact_pairs
+// leaves the chunk's valid (input row, gradient row) pairs in LDS in position order, the kernel multiplies them into the
+// accumulators, and store_partial_tiles writes the NCB 32 x 32 tiles into the (slot, k) slab that k_wgrad_reduce folds in a fixed
+// order.  The three kernels differ only in where the MFMA operands come from and which MFMA takes them:
+//   k_wgrad_f32       v_mfma_f32_32x32x2_f32 takes ONE element per lane, so rows are read straight from HBM in operand order (32
+//                     consecutive channels of 2 pairs per instruction): one 4-byte load per lane and operand.  Exact fp32; any row
+//                     width and alignment (the 3-channel input layer under WGRAD_F32_LDS = 0, odd head widths, operands off the
+//                     16-byte grid).
+//   k_wgrad_f32_lds   the same MFMA sequence fed from LDS: StagedRows brings the rows of 16 pairs in with 16-byte loads (every
+//                     byte once per workgroup instead of once per wave) while the previous 16 are multiplied.  Bit-identical to
+//                     k_wgrad_f32.
+//   k_wgrad_f32s_lds  the same staged rows, split exactly into three bf16 planes as they are staged, read back transposed as
+//                     32x32x16 bf16 operands: six bf16 MFMAs per 16 pairs instead of eight fp32 ones at half the rate.
+// The staged two dispatch the heavy offsets of a 3^3 map first (the centre offset pairs every position, a corner ~15 % of them).
+// Every shared piece is force-inlined: the staged kernels hold the next sub-chunk's rows in registers across the multiply, and a
+// call boundary there changes the register allocation (profiles/wgrad_f32_skeleton.txt holds the per-instantiation table).
 constexpr int kWgChunk = 512;  // positions compacted per iteration
+#define LGS_WG_INLINE __device__ __attribute__((always_inline)) inline
 
-template <typename T, int NCB>
-__global__ __launch_bounds__(256) void k_wgrad_f32(View v, const T *__restrict__ in, int cin_real, const T *__restrict__ gout,
-                                                   int cout_real, int cin_pad, int cout_pad, int64_t span,
-                                                   float *__restrict__ partial) {
-  __shared__ int32_t l_in[kWgChunk], l_out[kWgChunk];
-  __shared__ int32_t l_cnt[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int vx = lane & 31, h = lane >> 5;
-  const int k = blockIdx.y;
+struct F32Block {
+  int vx, h;                 // MFMA lane: column / row vx of the 32 x 32 tile, pair (k index) h of the instruction
+  int k, slot;               // kernel offset and its slot in the view
+  int cot, cib;              // column tile (NCB blocks), this wave's 32-channel input block
+  int ca0, cb0;              // first input channel of the workgroup's 128, first gradient channel of its NCB x 32
+  bool wave_active;
+  int64_t p_begin, p_end;    // positions of this slot
+};
+template <int NCB, bool HEAVY_FIRST>
+LGS_WG_INLINE F32Block f32_block_of(const View &v, int cin_pad, int cout_pad, int64_t span) {
+  F32Block b;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  b.vx = lane & 31; b.h = lane >> 5;
+  const int y = blockIdx.y;
+  b.k = (HEAVY_FIRST && v.K == 27) ? (y == 0 ? 13 : (y & 1) ? 13 - (y + 1) / 2 : 13 + y / 2) : y;
   const int n_cot = cout_pad / (32 * NCB);
-  const int cot = blockIdx.z % n_cot, cig = blockIdx.z / n_cot;
-  const int cib = cig * 4 + wave;
-  const bool wave_active = cib * 32 < cin_pad;
-  const int slot = v.KS > 1 ? k : 0;
+  b.cot = blockIdx.z % n_cot;
+  const int cig = blockIdx.z / n_cot;
+  b.cib = cig * 4 + wave;
+  b.wave_active = b.cib * 32 < cin_pad;
+  b.slot = v.KS > 1 ? b.k : 0;
+  b.ca0 = cig * 128; b.cb0 = b.cot * NCB * 32;
+  b.p_begin = (int64_t)blockIdx.x * span;
+  b.p_end = min(b.p_begin + span, v.n_pad);
+  return b;
+}
 
-  f32x16 acc[NCB];
+// The valid pairs of positions [base, base + kWgChunk) below p_end -> l_in / l_out, in position order (two positions per thread,
+// fixed wave order); returns their number.  Called uniformly by all 256 threads: two barriers, the second one publishes the lists.
+LGS_WG_INLINE int compact_pairs(const View &v, int k, int slot, int64_t base, int64_t p_end, int32_t *l_in, int32_t *l_out, int32_t *l_cnt) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int32_t my_in[2], my_out[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    int64_t p = base + wave * 128 + u * 64 + lane;
+    int32_t i = -1, o = -1;
+    if (p < p_end) {
+      bool grp_ok = true;
+      if (v.KS > 1) grp_ok = (v.mask64[p >> 6] >> slot) & 1u;
+      else if (v.tile_k) grp_ok = v.tile_k[p >> 6] == k;
+      if (grp_ok) {
+        o = v.out_row ? v.out_row[p] : (p < v.n_out ? (int32_t)p : -1);
+        i = v.nbr ? v.nbr[(int64_t)slot * v.n_pad + p] : (p < v.n_in ? (int32_t)p : -1);
+      }
+    }
+    my_in[u] = (i >= 0 && o >= 0) ? i : -1;
+    my_out[u] = o;
+  }
+  unsigned long long bal0 = __ballot(my_in[0] >= 0), bal1 = __ballot(my_in[1] >= 0);
+  int c0 = (int)__builtin_popcountll(bal0), c1 = (int)__builtin_popcountll(bal1);
+  if (lane == 0) l_cnt[wave] = c0 + c1;
+  __syncthreads();
+  int wbase = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    int c = l_cnt[w];
+    if (w < wave) wbase += c;
+    total += c;
+  }
+  if (my_in[0] >= 0) {
+    int at = wbase + (int)__builtin_popcountll(bal0 & ((1ull << lane) - 1ull));
+    l_in[at] = my_in[0]; l_out[at] = my_out[0];
+  }
+  if (my_in[1] >= 0) {
+    int at = wbase + c0 + (int)__builtin_popcountll(bal1 & ((1ull << lane) - 1ull));
+    l_in[at] = my_in[1]; l_out[at] = my_out[1];
+  }
+  __syncthreads();
+  return total;
+}
+
+template <int NCB>
+LGS_WG_INLINE void zero_tiles(f32x16 (&acc)[NCB]) {
 #pragma unroll
   for (int nb = 0; nb < NCB; ++nb)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-
-  const int64_t p_begin = (int64_t)blockIdx.x * span;
-  const int64_t p_end = min(p_begin + span, v.n_pad);
-  for (int64_t base = p_begin; base < p_end; base += kWgChunk) {
-    // ---- compact valid pairs of this chunk (two positions per thread, fixed wave order)
-    int32_t my_in[2], my_out[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      int64_t p = base + wave * 128 + u * 64 + lane;
-      int32_t i = -1, o = -1;
-      if (p < p_end) {
-        bool grp_ok = true;
-        if (v.KS > 1) grp_ok = (v.mask64[p >> 6] >> slot) & 1u;
-        else if (v.tile_k) grp_ok = v.tile_k[p >> 6] == k;
-        if (grp_ok) {
-          o = v.out_row ? v.out_row[p] : (p < v.n_out ? (int32_t)p : -1);
-          i = v.nbr ? v.nbr[(int64_t)slot * v.n_pad + p] : (p < v.n_in ? (int32_t)p : -1);
-        }
-      }
-      my_in[u] = (i >= 0 && o >= 0) ? i : -1;
-      my_out[u] = o;
-    }
-    unsigned long long bal0 = __ballot(my_in[0] >= 0), bal1 = __ballot(my_in[1] >= 0);
-    int c0 = (int)__builtin_popcountll(bal0), c1 = (int)__builtin_popcountll(bal1);
-    if (lane == 0) l_cnt[wave] = c0 + c1;
-    __syncthreads();
-    int wbase = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      int c = l_cnt[w];
-      if (w < wave) wbase += c;
-      total += c;
-    }
-    if (my_in[0] >= 0) {
-      int at = wbase + (int)__builtin_popcountll(bal0 & ((1ull << lane) - 1ull));
-      l_in[at] = my_in[0]; l_out[at] = my_out[0];
-    }
-    if (my_in[1] >= 0) {
-      int at = wbase + c0 + (int)__builtin_popcountll(bal1 & ((1ull << lane) - 1ull));
-      l_in[at] = my_in[1]; l_out[at] = my_out[1];
-    }
-    __syncthreads();
-    // ---- MFMA over the compacted pairs, two pairs (k = h) per 32x32x2 instruction
-    if (wave_active) {
-      const int ci = cib * 32 + vx;
-      for (int j = 0; j < total; j += 8) {
-        float a[4], b[4][NCB];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          int pr = j + 2 * u + h;
-          bool ok = pr < total;
-          int32_t irow = ok ? l_in[pr] : 0, orow = ok ? l_out[pr] : 0;
-          a[u] = (ok && ci < cin_real) ? ld_elem(in + (int64_t)irow * cin_real + ci) : 0.f;
-#pragma unroll
-          for (int nb = 0; nb < NCB; ++nb) {
-            int co = (cot * NCB + nb) * 32 + vx;
-            b[u][nb] = (ok && co < cout_real) ? ld_elem(gout + (int64_t)orow * cout_real + co) : 0.f;
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int nb = 0; nb < NCB; ++nb)
-            acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u][nb], acc[nb], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-  if (!wave_active) return;
-  // D[i = ci][j = co]: lane holds column j = vx, rows (r&3) + 8*(r>>2) + 4*h
-  float *dst = partial + (((int64_t)blockIdx.x * v.K + k) * cin_pad) * cout_pad;
+}
+// D[i = ci][j = co] of each tile: the lane holds column j = vx, rows (r & 3) + 8 (r >> 2) + 4 h
+template <int NCB>
+LGS_WG_INLINE void store_partial_tiles(const f32x16 (&acc)[NCB], float *__restrict__ partial, const View &v, const F32Block &b, int cin_pad, int cout_pad) {
+  float *dst = partial + (((int64_t)blockIdx.x * v.K + b.k) * cin_pad) * cout_pad;
 #pragma unroll
   for (int nb = 0; nb < NCB; ++nb) {
-    int co = (cot * NCB + nb) * 32 + vx;
+    int co = (b.cot * NCB + nb) * 32 + b.vx;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      int ci = cib * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+      int ci = b.cib * 32 + (r & 3) + 8 * (r >> 2) + 4 * b.h;
       dst[(int64_t)ci * cout_pad + co] = acc[nb][r];
     }
   }
 }
 
-// fp32 rows staged through LDS (round 5).  k_wgrad_f32 above feeds v_mfma_f32_32x32x2_f32 with one 4-byte load per lane and
-// operand: 16 wave-wide load instructions per 12 MFMAs and wave, ~6 per pair at 96 x 96 channels -- the fp32 training step spent
-// 75 ms per step in it (profiles/r05_bench.json, fp32.roofline.discovery_step.wgrad), all of it on the CU's vector-memory
-// instruction rate.  Here the workgroup brings the rows of 32 compacted pairs into LDS with 16-byte loads (input rows: the 128
-// channels of the workgroup's four waves, gradient rows: the NCB x 32 channels of its column tile; every byte once per workgroup
-// instead of once per wave), the next 32 pairs are in flight in registers while the current ones are multiplied, and the MFMA
-// operands are 4-byte LDS reads (row pitch + 32 floats: the two pair rows of one instruction fall on different banks).  The
-// MFMA sequence -- pairs in compacted order, two per instruction -- is k_wgrad_f32's, so the partial slabs are bit-identical.
-// Needs rows on the 16-byte grid (the 3-channel input layer and odd head widths keep k_wgrad_f32).
-template <int NCB>
-__global__ __launch_bounds__(256) void k_wgrad_f32_lds(View v, const float *__restrict__ in, int cin_real, const float *__restrict__ gout,
-                                                       int cout_real, int cin_pad, int cout_pad, int64_t span,
-                                                       float *__restrict__ partial) {
-  constexpr int PB = 16;                       // pairs per staged sub-chunk (16 / 32 / 64 at level 0, 96 x 96: 3.1 / 3.5 / 3.7 ms)
-  constexpr int AS = 128 + 32, BS = NCB * 32 + 32;
-  constexpr int NB4 = NCB * 8;                 // float4 pieces per gradient row
-  __shared__ int32_t l_in[kWgChunk], l_out[kWgChunk];
-  __shared__ int32_t l_cnt[4];
-  __shared__ __attribute__((aligned(16))) float sA[PB * AS];
-  __shared__ __attribute__((aligned(16))) float sB[PB * BS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int vx = lane & 31, h = lane >> 5;
-  // 3^3 maps: the centre offset pairs every position, a corner offset ~15 % of them -- the heavy offsets are dispatched first
-  const int y = blockIdx.y;
-  const int k = v.K == 27 ? (y == 0 ? 13 : (y & 1) ? 13 - (y + 1) / 2 : 13 + y / 2) : y;
-  const int n_cot = cout_pad / (32 * NCB);
-  const int cot = blockIdx.z % n_cot, cig = blockIdx.z / n_cot;
-  const int cib = cig * 4 + wave;
-  const bool wave_active = cib * 32 < cin_pad;
-  const int slot = v.KS > 1 ? k : 0;
-  const int ca0 = cig * 128, cb0 = cot * NCB * 32;
-
-  f32x16 acc[NCB];
-#pragma unroll
-  for (int nb = 0; nb < NCB; ++nb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-
-  constexpr int NA = PB * 32 / 256, NBQ = (PB * NB4 + 255) / 256;
+// The rows of one sub-chunk of PB compacted pairs, on their way from HBM to LDS: 16-byte pieces of the workgroup's 128 input
+// channels and NCB x 32 gradient channels, held in registers between fetch (issued before the previous sub-chunk is multiplied)
+// and stage.  Pieces behind `total` or behind the real row width are zeros.  Needs rows on the 16-byte grid.
+template <int NCB, int PB>
+struct StagedRows {
+  static constexpr int NB4 = NCB * 8;                                        // float4 pieces per gradient row
+  static constexpr int NA = PB * 32 / 256, NBQ = (PB * NB4 + 255) / 256;     // pieces per thread
   float4 ra[NA], rb[NBQ];
-  auto fetch = [&](int sub, int total) __attribute__((always_inline)) {
+
+  // the operands and lists are arguments, not members bound once: with them held in the struct the compiler allocated two more
+  // SGPRs in five of the eight staged instantiations and rescheduled all eight (profiles/wgrad_f32_skeleton.txt)
+  LGS_WG_INLINE void fetch(int sub, int total, const float *__restrict__ in, int cin_real, int ca0, const float *__restrict__ gout,
+                           int cout_real, int cb0, const int32_t *l_in, const int32_t *l_out) {
+    const int tid = threadIdx.x;
 #pragma unroll
     for (int u = 0; u < NA; ++u) {
       const int idx = tid + 256 * u, r = idx >> 5, c4 = idx & 31;
@@ -183,99 +165,116 @@ __global__ __launch_bounds__(256) void k_wgrad_f32_lds(View v, const float *__re
       rb[u] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (idx < PB * NB4 && pr < total && ch < cout_real) rb[u] = *reinterpret_cast<const float4 *>(gout + (int64_t)l_out[pr] * cout_real + ch);
     }
-  };
-  auto stage = [&]() __attribute__((always_inline)) {
+  }
+  // put_a / put_b(row of the sub-chunk, 4-channel piece of the row, its values): the kernel's LDS layout
+  template <typename PutA, typename PutB>
+  LGS_WG_INLINE void stage(PutA &&put_a, PutB &&put_b) const {
+    const int tid = threadIdx.x;
 #pragma unroll
     for (int u = 0; u < NA; ++u) {
-      const int idx = tid + 256 * u, r = idx >> 5, c4 = idx & 31;
-      *reinterpret_cast<float4 *>(sA + r * AS + 4 * c4) = ra[u];
+      const int idx = tid + 256 * u;
+      put_a(idx >> 5, idx & 31, ra[u]);
     }
 #pragma unroll
     for (int u = 0; u < NBQ; ++u) {
-      const int idx = tid + 256 * u, r = idx / NB4, c4 = idx % NB4;
-      if (idx < PB * NB4) *reinterpret_cast<float4 *>(sB + r * BS + 4 * c4) = rb[u];
+      const int idx = tid + 256 * u;
+      if (idx < PB * NB4) put_b(idx / NB4, idx % NB4, rb[u]);
     }
-  };
+  }
+};
 
-  const int64_t p_begin = (int64_t)blockIdx.x * span;
-  const int64_t p_end = min(p_begin + span, v.n_pad);
-  for (int64_t base = p_begin; base < p_end; base += kWgChunk) {
-    // ---- compact valid pairs of this chunk (two positions per thread, fixed wave order): as k_wgrad_f32
-    int32_t my_in[2], my_out[2];
+template <int NCB>
+__global__ __launch_bounds__(256) void k_wgrad_f32(View v, const float *__restrict__ in, int cin_real, const float *__restrict__ gout,
+                                                   int cout_real, int cin_pad, int cout_pad, int64_t span,
+                                                   float *__restrict__ partial) {
+  __shared__ int32_t l_in[kWgChunk], l_out[kWgChunk];
+  __shared__ int32_t l_cnt[4];
+  const F32Block b = f32_block_of<NCB, false>(v, cin_pad, cout_pad, span);
+  f32x16 acc[NCB];
+  zero_tiles<NCB>(acc);
+  for (int64_t base = b.p_begin; base < b.p_end; base += kWgChunk) {
+    const int total = compact_pairs(v, b.k, b.slot, base, b.p_end, l_in, l_out, l_cnt);
+    // ---- MFMA over the compacted pairs, two pairs (k = h) per 32x32x2 instruction
+    if (b.wave_active) {
+      const int ci = b.cib * 32 + b.vx;
+      for (int j = 0; j < total; j += 8) {
+        float a[4], g[4][NCB];
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      int64_t p = base + wave * 128 + u * 64 + lane;
-      int32_t i = -1, o = -1;
-      if (p < p_end) {
-        bool grp_ok = true;
-        if (v.KS > 1) grp_ok = (v.mask64[p >> 6] >> slot) & 1u;
-        else if (v.tile_k) grp_ok = v.tile_k[p >> 6] == k;
-        if (grp_ok) {
-          o = v.out_row ? v.out_row[p] : (p < v.n_out ? (int32_t)p : -1);
-          i = v.nbr ? v.nbr[(int64_t)slot * v.n_pad + p] : (p < v.n_in ? (int32_t)p : -1);
+        for (int u = 0; u < 4; ++u) {
+          int pr = j + 2 * u + b.h;
+          bool ok = pr < total;
+          int32_t irow = ok ? l_in[pr] : 0, orow = ok ? l_out[pr] : 0;
+          a[u] = (ok && ci < cin_real) ? in[(int64_t)irow * cin_real + ci] : 0.f;
+#pragma unroll
+          for (int nb = 0; nb < NCB; ++nb) {
+            int co = (b.cot * NCB + nb) * 32 + b.vx;
+            g[u][nb] = (ok && co < cout_real) ? gout[(int64_t)orow * cout_real + co] : 0.f;
+          }
         }
-      }
-      my_in[u] = (i >= 0 && o >= 0) ? i : -1;
-      my_out[u] = o;
-    }
-    unsigned long long bal0 = __ballot(my_in[0] >= 0), bal1 = __ballot(my_in[1] >= 0);
-    int c0 = (int)__builtin_popcountll(bal0), c1 = (int)__builtin_popcountll(bal1);
-    if (lane == 0) l_cnt[wave] = c0 + c1;
-    __syncthreads();
-    int wbase = 0, total = 0;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      int c = l_cnt[w];
-      if (w < wave) wbase += c;
-      total += c;
-    }
-    if (my_in[0] >= 0) {
-      int at = wbase + (int)__builtin_popcountll(bal0 & ((1ull << lane) - 1ull));
-      l_in[at] = my_in[0]; l_out[at] = my_out[0];
-    }
-    if (my_in[1] >= 0) {
-      int at = wbase + c0 + (int)__builtin_popcountll(bal1 & ((1ull << lane) - 1ull));
-      l_in[at] = my_in[1]; l_out[at] = my_out[1];
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int nb = 0; nb < NCB; ++nb)
+            acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], g[u][nb], acc[nb], 0, 0, 0);
+      }
     }
     __syncthreads();
+  }
+  if (b.wave_active) store_partial_tiles<NCB>(acc, partial, v, b, cin_pad, cout_pad);
+}
+
+// Measured when the rows were first staged (round 5): k_wgrad_f32 issues 16 wave-wide load instructions per 12 MFMAs and wave, ~6
+// per pair at 96 x 96 channels -- the fp32 training step spent 75 ms per step in it (profiles/r05_bench.json,
+// fp32.roofline.discovery_step.wgrad), all of it on the CU's vector-memory instruction rate.  LDS row pitch + 32 floats: the two pair
+// rows of one instruction fall on different banks.
+template <int NCB>
+__global__ __launch_bounds__(256) void k_wgrad_f32_lds(View v, const float *__restrict__ in, int cin_real, const float *__restrict__ gout,
+                                                       int cout_real, int cin_pad, int cout_pad, int64_t span,
+                                                       float *__restrict__ partial) {
+  constexpr int PB = 16;                       // pairs per staged sub-chunk (16 / 32 / 64 at level 0, 96 x 96: 3.1 / 3.5 / 3.7 ms)
+  constexpr int AS = 128 + 32, BS = NCB * 32 + 32;
+  __shared__ int32_t l_in[kWgChunk], l_out[kWgChunk];
+  __shared__ int32_t l_cnt[4];
+  __shared__ __attribute__((aligned(16))) float sA[PB * AS];
+  __shared__ __attribute__((aligned(16))) float sB[PB * BS];
+  const F32Block b = f32_block_of<NCB, true>(v, cin_pad, cout_pad, span);
+  const int wave = threadIdx.x >> 6;
+  f32x16 acc[NCB];
+  zero_tiles<NCB>(acc);
+  StagedRows<NCB, PB> rows;
+  auto put_a = [&](int r, int c4, const float4 &x) __attribute__((always_inline)) { *reinterpret_cast<float4 *>(sA + r * AS + 4 * c4) = x; };
+  auto put_b = [&](int r, int c4, const float4 &x) __attribute__((always_inline)) { *reinterpret_cast<float4 *>(sB + r * BS + 4 * c4) = x; };
+
+  for (int64_t base = b.p_begin; base < b.p_end; base += kWgChunk) {
+    const int total = compact_pairs(v, b.k, b.slot, base, b.p_end, l_in, l_out, l_cnt);
     const int nsub = (total + PB - 1) / PB;
-    if (nsub > 0) fetch(0, total);
+    if (nsub > 0) rows.fetch(0, total, in, cin_real, b.ca0, gout, cout_real, b.cb0, l_in, l_out);
     for (int sub = 0; sub < nsub; ++sub) {
-      stage();
+      rows.stage(put_a, put_b);
       __syncthreads();
-      if (sub + 1 < nsub) fetch(sub + 1, total);             // in flight while this sub-chunk is multiplied
-      if (wave_active) {
+      if (sub + 1 < nsub) rows.fetch(sub + 1, total, in, cin_real, b.ca0, gout, cout_real, b.cb0, l_in, l_out);   // in flight while this sub-chunk is multiplied
+      if (b.wave_active) {
         const int np = min(PB, (total - sub * PB + 7) & ~7);     // rows behind `total` are staged as zeros: whole groups of 8 pairs
-        const float *pa = sA + h * AS + wave * 32 + vx;
-        const float *pb = sB + h * BS + vx;
+        const float *pa = sA + b.h * AS + wave * 32 + b.vx;
+        const float *pb = sB + b.h * BS + b.vx;
         for (int p8 = 0; p8 < np; p8 += 8) {
-          float a[4], b[4][NCB];
+          float a[4], g[4][NCB];
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             a[q] = pa[(p8 + 2 * q) * AS];
 #pragma unroll
-            for (int nb = 0; nb < NCB; ++nb) b[q][nb] = pb[(p8 + 2 * q) * BS + nb * 32];
+            for (int nb = 0; nb < NCB; ++nb) g[q][nb] = pb[(p8 + 2 * q) * BS + nb * 32];
           }
 #pragma unroll
           for (int q = 0; q < 4; ++q)
 #pragma unroll
-            for (int nb = 0; nb < NCB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q], b[q][nb], acc[nb], 0, 0, 0);
+            for (int nb = 0; nb < NCB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q], g[q][nb], acc[nb], 0, 0, 0);
         }
       }
       __syncthreads();
     }
   }
-  if (!wave_active) return;
-  float *dst = partial + (((int64_t)blockIdx.x * v.K + k) * cin_pad) * cout_pad;
-#pragma unroll
-  for (int nb = 0; nb < NCB; ++nb) {
-    int co = (cot * NCB + nb) * 32 + vx;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int ci = cib * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-      dst[(int64_t)ci * cout_pad + co] = acc[nb][r];
-    }
-  }
+  if (b.wave_active) store_partial_tiles<NCB>(acc, partial, v, b, cin_pad, cout_pad);
 }
 
 // ------------------------------------------------------------------------------------ bf16 MFMA path
@@ -291,10 +290,10 @@ __host__ __device__ constexpr int tile_stride(int c) {
 
 typedef short short4v __attribute__((ext_vector_type(4)));
 
-// fp32 rows, bf16 products (round 5, knob WGRAD_F32_LDS = 2): k_wgrad_f32_lds's structure -- compacted pairs, rows staged in LDS
-// by the whole workgroup, the next 16 pairs in flight during the multiply -- with every fp32 element split exactly into three bf16
-// pieces (x = hi + mid + lo by truncation, as in k_conv_gather's Tr<f32s_t>) WHEN IT IS STAGED, once per workgroup: three
-// row-major bf16 planes per operand, read back transposed (ds_read_b64_tr_b16, the idiom of k_wgrad_bf16) as 32x32x16 operands.
+// fp32 rows, bf16 products (k_wgrad_f32s_lds of the fp32 skeleton above, knob WGRAD_F32_LDS = 2; it sits here because it needs
+// tile_stride and the transposing read): every fp32 element of the staged rows is split exactly into three bf16 pieces
+// (x = hi + mid + lo by truncation, as in k_conv_gather's Tr<f32s_t>) WHEN IT IS STAGED, once per workgroup: three row-major
+// bf16 planes per operand, read back transposed (ds_read_b64_tr_b16, the idiom of k_wgrad_bf16) as 32x32x16 operands.
 // Per 16 pairs and 32 x 32 tile: six bf16 MFMAs (hi*hi, hi*mid, mid*hi, hi*lo, lo*hi, mid*mid; 6 x 32 cycles) instead of eight
 // v_mfma_f32_32x32x2_f32 (8 x 64 cycles); dropped terms < 2^-24 |x g|, fp32 accumulation.
 __device__ inline void split3_bf16(float x, uint32_t &hi, uint32_t &mid, uint32_t &lo) {
@@ -330,112 +329,33 @@ __global__ __launch_bounds__(256) void k_wgrad_f32s_lds(View v, const float *__r
   constexpr int PB = 16;                                   // one 32x32x16 k-group of pairs per staged sub-chunk
   constexpr int SA = tile_stride(128), SG = tile_stride(NCB * 32);   // row pitch (bytes) of the bf16 planes
   constexpr int PA = PB * SA, PG = PB * SG;                // bytes per plane
-  constexpr int NB4 = NCB * 8;
-  constexpr int NA = PB * 32 / 256, NBQ = (PB * NB4 + 255) / 256;
   __shared__ int32_t l_in[kWgChunk], l_out[kWgChunk];
   __shared__ int32_t l_cnt[4];
   __shared__ __attribute__((aligned(16))) char sA[3 * PA];
   __shared__ __attribute__((aligned(16))) char sB[3 * PG];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int vx = lane & 31, h = lane >> 5;
-  const int y = blockIdx.y;
-  const int k = v.K == 27 ? (y == 0 ? 13 : (y & 1) ? 13 - (y + 1) / 2 : 13 + y / 2) : y;     // heavy offsets first (k_wgrad_f32_lds)
-  const int n_cot = cout_pad / (32 * NCB);
-  const int cot = blockIdx.z % n_cot, cig = blockIdx.z / n_cot;
-  const int cib = cig * 4 + wave;
-  const bool wave_active = cib * 32 < cin_pad;
-  const int slot = v.KS > 1 ? k : 0;
-  const int ca0 = cig * 128, cb0 = cot * NCB * 32;
+  const F32Block b = f32_block_of<NCB, true>(v, cin_pad, cout_pad, span);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // transposing read: 16-lane group g = lane >> 4: cb = g & 1 (16-channel half), pairs 8 (g >> 1) ..; lane i = lane & 15 supplies
   // the 8-byte address (row 8 (g >> 1) + i / 4 [+ 4], channel 16 cb + 4 (i % 4)) -- see k_wgrad_bf16
   const int g16 = lane >> 4, i16 = lane & 15;
   const int tr_row = 8 * (g16 >> 1) + (i16 >> 2), tr_col = 16 * (g16 & 1) + 4 * (i16 & 3);
   const char *pa = sA + tr_row * SA + (32 * wave + tr_col) * 2;
   const char *pg = sB + tr_row * SG + tr_col * 2;
-
   f32x16 acc[NCB];
-#pragma unroll
-  for (int nb = 0; nb < NCB; ++nb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
+  zero_tiles<NCB>(acc);
+  StagedRows<NCB, PB> rows;
+  auto put_a = [&](int r, int c4, const float4 &x) __attribute__((always_inline)) { split3_store(sA, PA, r * SA + 8 * c4, x); };
+  auto put_b = [&](int r, int c4, const float4 &x) __attribute__((always_inline)) { split3_store(sB, PG, r * SG + 8 * c4, x); };
 
-  float4 ra[NA], rb[NBQ];
-  auto fetch = [&](int sub, int total) __attribute__((always_inline)) {
-#pragma unroll
-    for (int u = 0; u < NA; ++u) {
-      const int idx = tid + 256 * u, r = idx >> 5, c4 = idx & 31;
-      const int pr = sub * PB + r, ch = ca0 + 4 * c4;
-      ra[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (pr < total && ch < cin_real) ra[u] = *reinterpret_cast<const float4 *>(in + (int64_t)l_in[pr] * cin_real + ch);
-    }
-#pragma unroll
-    for (int u = 0; u < NBQ; ++u) {
-      const int idx = tid + 256 * u, r = idx / NB4, c4 = idx % NB4;
-      const int pr = sub * PB + r, ch = cb0 + 4 * c4;
-      rb[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (idx < PB * NB4 && pr < total && ch < cout_real) rb[u] = *reinterpret_cast<const float4 *>(gout + (int64_t)l_out[pr] * cout_real + ch);
-    }
-  };
-  auto stage = [&]() __attribute__((always_inline)) {
-#pragma unroll
-    for (int u = 0; u < NA; ++u) {
-      const int idx = tid + 256 * u, r = idx >> 5, c4 = idx & 31;
-      split3_store(sA, PA, r * SA + 8 * c4, ra[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < NBQ; ++u) {
-      const int idx = tid + 256 * u, r = idx / NB4, c4 = idx % NB4;
-      if (idx < PB * NB4) split3_store(sB, PG, r * SG + 8 * c4, rb[u]);
-    }
-  };
-
-  const int64_t p_begin = (int64_t)blockIdx.x * span;
-  const int64_t p_end = min(p_begin + span, v.n_pad);
-  for (int64_t base = p_begin; base < p_end; base += kWgChunk) {
-    int32_t my_in[2], my_out[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      int64_t p = base + wave * 128 + u * 64 + lane;
-      int32_t i = -1, o = -1;
-      if (p < p_end) {
-        bool grp_ok = true;
-        if (v.KS > 1) grp_ok = (v.mask64[p >> 6] >> slot) & 1u;
-        else if (v.tile_k) grp_ok = v.tile_k[p >> 6] == k;
-        if (grp_ok) {
-          o = v.out_row ? v.out_row[p] : (p < v.n_out ? (int32_t)p : -1);
-          i = v.nbr ? v.nbr[(int64_t)slot * v.n_pad + p] : (p < v.n_in ? (int32_t)p : -1);
-        }
-      }
-      my_in[u] = (i >= 0 && o >= 0) ? i : -1;
-      my_out[u] = o;
-    }
-    unsigned long long bal0 = __ballot(my_in[0] >= 0), bal1 = __ballot(my_in[1] >= 0);
-    int c0 = (int)__builtin_popcountll(bal0), c1 = (int)__builtin_popcountll(bal1);
-    if (lane == 0) l_cnt[wave] = c0 + c1;
-    __syncthreads();
-    int wbase = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      int c = l_cnt[w];
-      if (w < wave) wbase += c;
-      total += c;
-    }
-    if (my_in[0] >= 0) {
-      int at = wbase + (int)__builtin_popcountll(bal0 & ((1ull << lane) - 1ull));
-      l_in[at] = my_in[0]; l_out[at] = my_out[0];
-    }
-    if (my_in[1] >= 0) {
-      int at = wbase + c0 + (int)__builtin_popcountll(bal1 & ((1ull << lane) - 1ull));
-      l_in[at] = my_in[1]; l_out[at] = my_out[1];
-    }
-    __syncthreads();
+  for (int64_t base = b.p_begin; base < b.p_end; base += kWgChunk) {
+    const int total = compact_pairs(v, b.k, b.slot, base, b.p_end, l_in, l_out, l_cnt);
     const int nsub = (total + PB - 1) / PB;
-    if (nsub > 0) fetch(0, total);
+    if (nsub > 0) rows.fetch(0, total, in, cin_real, b.ca0, gout, cout_real, b.cb0, l_in, l_out);
     for (int sub = 0; sub < nsub; ++sub) {
-      stage();
+      rows.stage(put_a, put_b);
       __syncthreads();
-      if (sub + 1 < nsub) fetch(sub + 1, total);
-      if (wave_active) {
+      if (sub + 1 < nsub) rows.fetch(sub + 1, total, in, cin_real, b.ca0, gout, cout_real, b.cb0, l_in, l_out);   // in flight while this sub-chunk is multiplied
+      if (b.wave_active) {
         bf16x8 fa[3], fg[3][NCB];
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
@@ -456,18 +376,10 @@ __global__ __launch_bounds__(256) void k_wgrad_f32s_lds(View v, const float *__r
       __syncthreads();
     }
   }
-  if (!wave_active) return;
-  float *dst = partial + (((int64_t)blockIdx.x * v.K + k) * cin_pad) * cout_pad;
-#pragma unroll
-  for (int nb = 0; nb < NCB; ++nb) {
-    int co = (cot * NCB + nb) * 32 + vx;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int ci = cib * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-      dst[(int64_t)ci * cout_pad + co] = acc[nb][r];
-    }
-  }
+  if (b.wave_active) store_partial_tiles<NCB>(acc, partial, v, b, cin_pad, cout_pad);
 }
+
+#undef LGS_WG_INLINE
 
 // Grid: 1-D.  Workgroup L runs on XCD L % 8 (dispatcher behaviour, used for speed only).  A workgroup owns ONE
 // position range (a few thousand Morton-consecutive voxels: its rows + halo fit the XCD's L2) and its four waves
@@ -1383,15 +1295,7 @@ int with_blocks(int n, F &&f) {
   LGS_REQUIRE(false, "weight gradient: no kernel instance for this tile");
 }
 
-template <typename T>
-__global__ void k_pad_rows(const T *__restrict__ src, int64_t n, int c, int cpad, T *__restrict__ dst) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n * cpad) return;
-  int64_t r = i / cpad;
-  int ch = (int)(i % cpad);
-  dst[i] = ch < c ? src[r * c + ch] : (T)0;
-}
-// rows [n][c] -> region r of the workspace as [n][cpad], zero-padded
+// rows [n][c] -> region r of the workspace as [n][cpad], zero-padded (k_pad_rows: lgs_common.h)
 template <typename T>
 const T *pad_rows_into(void *workspace, const lgs_conv_plan_region &r, const void *src, int64_t n, int c, int cpad, hipStream_t s) {
   T *dst = reinterpret_cast<T *>(reinterpret_cast<char *>(workspace) + r.offset);
@@ -1442,7 +1346,7 @@ int launch_wgrad_f32(const View &v, const WgradPlan &p, const float *in, int cin
   const bool aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(go)) & 15u) == 0;
   if (aligned && p.f32_kernel == 2) LGS_KLAUNCH((k_wgrad_f32s_lds<NCB>), grid, 256, 0, s, v, in, cin, go, cout, p.pad_a, p.pad_b, p.span, partial);
   else if (aligned && p.f32_kernel == 1) LGS_KLAUNCH((k_wgrad_f32_lds<NCB>), grid, 256, 0, s, v, in, cin, go, cout, p.pad_a, p.pad_b, p.span, partial);
-  else LGS_KLAUNCH((k_wgrad_f32<float, NCB>), grid, 256, 0, s, v, in, cin, go, cout, p.pad_a, p.pad_b, p.span, partial);
+  else LGS_KLAUNCH((k_wgrad_f32<NCB>), grid, 256, 0, s, v, in, cin, go, cout, p.pad_a, p.pad_b, p.span, partial);
   return 0;
 }
 
