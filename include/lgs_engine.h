@@ -420,6 +420,48 @@ typedef struct lgs_norm_plan_info {
 } lgs_norm_plan_info;
 int lgs_debug_norm_plan(const lgs_norm_plan_query *q, lgs_norm_plan_info *out);
 
+/* ---- two norms on the same rows: the residual block's norm2 and its downsample-branch norm (csrc/lgs_norm.hip) ----
+ *   /root/reference/models/modules/resnet_block.py:41-57, models/resnet.py:93-103   (out = relu?(norm2(conv2) + norm_d(conv_d(x))))
+ * norm a = the main norm (adds the branch, optional ReLU), norm b = the branch norm (no ReLU); both [n, c] of one dtype.
+ *   lgs_bn_forward_pair : y = relu?(bn_a(xa) + bn_b(xb)); both norms' saved statistics, running statistics and num_batches_tracked
+ *                         exactly as two lgs_bn_forward calls leave them.  res (may be NULL): the branch output bn_b(xb), written
+ *                         only when asked for -- the sum uses its value as stored in `dtype`, so y is bit-identical to the two calls.
+ *   lgs_bn_backward_pair: both norms receive dy' = dy masked by norm a's ReLU (relu 0 = none, 1 = the mask from ya); writes
+ *                         dxa, dxb, both dgamma / dbeta, and dy' to dresidual when it is not NULL.
+ * Each direction reads every operand once: one statistics launch for both norms, one fold launch, one apply (`three`: 3 launches;
+ * `fold`: 2) instead of the 6 (4) of the single calls, 5 instead of 7 tensor passes forward and 10 instead of 13 backward, same
+ * per-element expressions and summation orders (bit-identical results).  The path is the single-norm plan's (lgs_debug_norm_plan)
+ * for (direction, n, c, dtype); where that is the grid-barrier `fused` path, where the tuning knob BN_PAIR is 0, and for n == 0 the
+ * entry points issue the two single calls (path 0) -- which need their intermediate: res / dresidual must then be given.
+ * lgs_bn_pair_plan answers which it is for a call on the current device (it asks the device what lgs_bn_forward / backward ask, and
+ * launches nothing); lgs_debug_norm_pair_plan is the same for a resident-workgroup bound given by the caller (no HIP call: it runs
+ * without a GPU, tests/test_norm_pair_plan_cpu.py).
+ * workspace: lgs_bn_pair_workspace_bytes(n, c) (the bound over every path and knob setting, as lgs_bn_workspace_bytes is).
+ * NEW SYMBOLS ONLY: LGS_ABI_VERSION stays 18; a library that lacks them lacks the capability. */
+struct lgs_bn_params;
+typedef struct lgs_norm_pair_plan_info {
+  int path;                /* 0 the two single calls; 1 fold pair (two launches); 3 three-launch pair */
+  int single_path;         /* lgs_norm_plan_info.path of the single-norm plan it was derived from */
+  int launches;            /* launches of this direction (path 0: of both single calls) */
+  int reduce_grid;         /* workgroups (x) of the statistics launch; forward: y = 2, one slice per norm */
+  int64_t rows_per_block;
+  int fold_rows, fold_grid, apply_grid;   /* as in lgs_norm_plan_info; the fold launch has y = 2 */
+  lgs_conv_plan_region partials_a, partials_b, sums_a, sums_b;   /* both norms' partial rows, then (backward, path 3) their [2c] sums */
+  int64_t bytes_total;
+  int64_t workspace_bytes; /* lgs_bn_pair_workspace_bytes(n, c) */
+} lgs_norm_pair_plan_info;
+int64_t lgs_bn_pair_workspace_bytes(int64_t n, int c);
+int lgs_bn_pair_plan(int direction /* 0 forward, 1 backward */, int64_t n, int c, int dtype, lgs_norm_pair_plan_info *out);
+int lgs_debug_norm_pair_plan(const lgs_norm_plan_query *q /* direction 0 or 1; conv_partial_rows ignored */, lgs_norm_pair_plan_info *out);
+int lgs_bn_forward_pair(const void *xa, const struct lgs_bn_params *norm_a, float *stats_a, const void *xb,
+                        const struct lgs_bn_params *norm_b, float *stats_b, int64_t n, int c, int relu, void *y,
+                        int64_t y_row_stride /* elements; 0 = c */, void *res /* may be NULL */, int dtype, void *workspace, void *stream);
+int lgs_bn_backward_pair(const void *xa, const void *ya, const float *gamma_a, const float *beta_a, const float *stats_a, int relu,
+                         const void *xb, const float *gamma_b, const float *stats_b, const void *dy, int64_t dy_row_stride,
+                         int64_t n, int c, void *dxa, void *dxb, float *dgamma_a, float *dbeta_a, float *dgamma_b, float *dbeta_b,
+                         void *dresidual /* may be NULL */, int dtype, void *workspace, int64_t ya_row_stride /* of ya; 0 = c */,
+                         void *stream);
+
 /* lgs_debug_instnorm_plan (ABI 18): what an instance-norm call decides on the host, for a call given by plain integers (the sizes
  * of the origin segment map: fine rows, scenes, chunk items).  No HIP call: it runs without a GPU (tests/test_instnorm_cpu.py). */
 typedef struct lgs_instnorm_plan_query {
@@ -522,7 +564,10 @@ typedef struct lgs_block_fwd {
   lgs_bn_params n1, n2, nd;
   void *o1, *y1, *o2, *od, *res, *y2;    /* [n, planes] outputs: conv1, norm1+relu, conv2, downsample conv, its norm, block output */
   float *st1, *st2, *std_;               /* [2 planes] mean | invstd of the three norms (saved for backward) */
-  void *conv_ws, *bn_ws;                 /* lgs_block_workspace_bytes / lgs_bn_workspace_bytes(n, planes) */
+  void *conv_ws, *bn_ws;                 /* lgs_block_workspace_bytes / lgs_bn_workspace_bytes(n, planes); with km1 the branch norm
+                                            and norm2 run as lgs_bn_forward_pair / lgs_bn_backward_pair: bn_ws is then
+                                            lgs_bn_pair_workspace_bytes(n, planes), and res (forward) / dres (backward) may be NULL
+                                            unless lgs_bn_pair_plan answers path 0 for the direction */
 } lgs_block_fwd;
 typedef struct lgs_block_bwd {
   lgs_kmap *km3, *km1;

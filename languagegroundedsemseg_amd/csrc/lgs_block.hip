@@ -2,7 +2,8 @@
 //
 // A BasicBlock (/root/reference/models/modules/resnet_block.py:41-57: conv3-norm-relu-conv3-norm-(+residual)-relu, with the
 // optional 1x1 conv + norm downsample branch of /root/reference/models/resnet.py:93-103) is a FIXED sequence of engine calls:
-// forward 2-3 lgs_conv_forward + 2-3 lgs_bn_forward, backward 2-3 each of lgs_bn_backward / lgs_conv_wgrad / lgs_conv_dgrad.
+// forward 2-3 lgs_conv_forward + 2-3 lgs_bn_forward, backward 2-3 each of lgs_bn_backward / lgs_conv_wgrad / lgs_conv_dgrad
+// (the two norms that meet at the residual add of a downsample block: one lgs_bn_forward_pair / lgs_bn_backward_pair).
 // At one ~150 k-voxel scene per step the training step is bound by the host enqueueing those ~250 calls (~40 us each through
 // Python + ctypes: host 10.2 ms against 9.0 ms of GPU work), not by the GPU.  These two entry points
 // issue exactly the same launches, in the same order, with the same arguments as the call-by-call path (bit-identical results:
@@ -36,8 +37,14 @@ int lgs_block_forward(const lgs_block_fwd *a, void *stream) {
   if ((rc = lgs_conv_forward(a->km3, 0, a->y1, c, a->w2, c, nullptr, a->o2, dt, a->conv_ws, nullptr, nullptr, a->pk2, a->pm2, 0, stream))) return rc;
   const void *res = a->x;
   if (a->km1) {
-    LGS_REQUIRE(a->od && a->res && a->std_, "lgs_block_forward: downsample branch outputs missing");
+    LGS_REQUIRE(a->od && a->std_, "lgs_block_forward: downsample branch outputs missing");
     if ((rc = lgs_conv_forward(a->km1, 0, a->x, a->cin, a->wd, c, nullptr, a->od, dt, a->conv_ws, nullptr, nullptr, a->pkd, a->pmd, 0, stream))) return rc;
+    // the branch norm and norm2 share their passes (lgs_bn_forward_pair: bit-identical to the two calls below); the branch output
+    // is then not needed, a->res may be NULL.  bn_ws: lgs_bn_pair_workspace_bytes(n, planes) for such blocks
+    lgs_norm_pair_plan_info q;
+    if ((rc = lgs_bn_pair_plan(0, a->n, c, dt, &q))) return rc;
+    if (q.path != 0) return lgs_bn_forward_pair(a->o2, &a->n2, a->st2, a->od, &a->nd, a->std_, a->n, c, a->relu_final, a->y2, 0, a->res, dt, a->bn_ws, stream);
+    LGS_REQUIRE(a->res, "lgs_block_forward: the norms of this block run as single calls (lgs_bn_pair_plan: path 0) and need the res buffer");
     if ((rc = lgs_bn_forward(a->od, a->n, c, a->nd.gamma, a->nd.beta, a->nd.eps, a->nd.momentum, a->nd.running_mean, a->nd.running_var,
                              a->nd.num_batches_tracked, nullptr, 0, a->res, a->std_, dt, a->bn_ws, nullptr, 0, nullptr, 0, stream))) return rc;
     res = a->res;
@@ -49,7 +56,7 @@ int lgs_block_forward(const lgs_block_fwd *a, void *stream) {
 }
 
 int lgs_block_backward(const lgs_block_bwd *a, void *stream) {
-  LGS_REQUIRE(a && a->km3 && a->x && a->dy && a->o1 && a->y1 && a->o2 && a->st1 && a->st2 && a->w1 && a->w2 && a->dx2 && a->dres && a->dy1 &&
+  LGS_REQUIRE(a && a->km3 && a->x && a->dy && a->o1 && a->y1 && a->o2 && a->st1 && a->st2 && a->w1 && a->w2 && a->dx2 && a->dy1 &&
                   a->dx1 && a->gw1 && a->gw2 && a->conv_ws && a->bn_ws,
               "lgs_block_backward: null argument");
   LGS_REQUIRE(!a->relu_final || a->y2, "lgs_block_backward: the ReLU mask of the block output needs y2");
@@ -66,9 +73,23 @@ int lgs_block_backward(const lgs_block_bwd *a, void *stream) {
     if (ev) LGS_HIP(hipEventRecord((hipEvent_t)ev, (hipStream_t)a->wgrad_stream));
     return 0;
   };
-  // norm2 (+ residual) (+ ReLU): mask from the saved output when there is a ReLU (a residual was added)
-  if ((rc = lgs_bn_backward(a->o2, a->relu_final ? a->y2 : nullptr, a->dy, a->dy_row_stride, a->n, c, a->gamma2, a->beta2, a->st2,
-                            a->relu_final ? 1 : 0, a->dx2, a->dres, a->dgamma2, a->dbeta2, dt, a->bn_ws, 0, stream))) return rc;
+  // norm2 (+ residual) (+ ReLU): mask from the saved output when there is a ReLU (a residual was added).  With a downsample branch
+  // its norm receives the same masked gradient: both backward norms in shared passes (lgs_bn_backward_pair, bit-identical to the
+  // two calls); nothing else reads the masked gradient then, a->dres may be NULL
+  bool pair = false;
+  if (a->km1) {
+    LGS_REQUIRE(a->od && a->std_ && a->wd && a->dxd && a->gwd && a->gind, "lgs_block_backward: downsample branch tensors missing");
+    lgs_norm_pair_plan_info q;
+    if ((rc = lgs_bn_pair_plan(1, a->n, c, dt, &q))) return rc;
+    pair = q.path != 0;
+  }
+  LGS_REQUIRE(pair || a->dres, "lgs_block_backward: the norms of this block run as single calls and need the dres buffer");
+  if (pair) {
+    if ((rc = lgs_bn_backward_pair(a->o2, a->relu_final ? a->y2 : nullptr, a->gamma2, a->beta2, a->st2, a->relu_final ? 1 : 0, a->od, a->gammad, a->std_,
+                                   a->dy, a->dy_row_stride, a->n, c, a->dx2, a->dxd, a->dgamma2, a->dbeta2, a->dgammad, a->dbetad, nullptr, dt, a->bn_ws,
+                                   0, stream))) return rc;
+  } else if ((rc = lgs_bn_backward(a->o2, a->relu_final ? a->y2 : nullptr, a->dy, a->dy_row_stride, a->n, c, a->gamma2, a->beta2, a->st2,
+                                   a->relu_final ? 1 : 0, a->dx2, a->dres, a->dgamma2, a->dbeta2, dt, a->bn_ws, 0, stream))) return rc;
   if ((rc = wgrad(a->km3, a->y1, c, a->dx2, a->gw2, 0, a->ev_w2))) return rc;
   if ((rc = lgs_conv_dgrad(a->km3, 0, a->dx2, c, a->w2, c, a->dy1, dt, a->conv_ws, a->pk2, a->pm2, stream))) return rc;
   // norm1 + ReLU: mask recomputed from its input
@@ -79,9 +100,8 @@ int lgs_block_backward(const lgs_block_bwd *a, void *stream) {
   if (!late && (rc = wgrad(a->km3, a->x, a->cin, a->dx1, a->gw1, a->x_row_stride, a->ev_w1))) return rc;
   void *acc = a->dres;       // the residual branch's gradient w.r.t. x
   if (a->km1) {
-    LGS_REQUIRE(a->od && a->std_ && a->wd && a->dxd && a->gwd && a->gind, "lgs_block_backward: downsample branch tensors missing");
-    if ((rc = lgs_bn_backward(a->od, nullptr, a->dres, 0, a->n, c, a->gammad, a->betad, a->std_, 0, a->dxd, nullptr, a->dgammad, a->dbetad, dt,
-                              a->bn_ws, 0, stream))) return rc;
+    if (!pair && (rc = lgs_bn_backward(a->od, nullptr, a->dres, 0, a->n, c, a->gammad, a->betad, a->std_, 0, a->dxd, nullptr, a->dgammad, a->dbetad, dt,
+                                       a->bn_ws, 0, stream))) return rc;
     if ((rc = wgrad(a->km1, a->x, a->cin, a->dxd, a->gwd, a->x_row_stride, a->ev_wd))) return rc;
     if (a->want_gin) {
       if ((rc = lgs_conv_dgrad(a->km1, 0, a->dxd, c, a->wd, a->cin, a->gind, dt, a->conv_ws, a->pkd, a->pmd, stream))) return rc;

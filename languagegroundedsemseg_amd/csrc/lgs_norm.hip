@@ -11,6 +11,10 @@
 // so every wave instruction is a fully coalesced 1 KiB access.  Statistics
 // are reduced per block in LDS, then across blocks through a [blocks, 2C] fp32 scratch that a small fold
 // kernel sums in a fixed order (double accumulation) -> deterministic, no float atomics.
+// Passes over a [N, C] tensor per call (`three` / `fold` paths): forward 3 (read x twice, write y; 4 with a residual), backward 5
+// (x, dy twice, dx written), 7 with a ReLU mask from y and a residual gradient out -- the reduce launch writes the masked
+// gradient and the apply reads it back, so y is read and dy masked once.  The two norms that meet at the residual add of a
+// downsample block share their passes (lgs_bn_forward_pair / lgs_bn_backward_pair, below): 5 forward and 10 backward for both.
 #include "lgs_rows.h"
 #include <algorithm>
 #include <atomic>
@@ -20,17 +24,29 @@ namespace lgs {
 
 constexpr int kNT = 256;
 
+// a value as it reads back after a store in T (bf16: rounded; fp32: itself)
+template <typename T> __device__ inline float stored_value(float x);
+template <> __device__ inline float stored_value<float>(float x) { return x; }
+template <> __device__ inline float stored_value<bf16_t>(float x) { return bf16_to_f32(f32_to_bf16(x)); }
+
 // Column reduction of up to two per-element quantities.  MODE 0: (x, x*x)  [forward statistics]
 // MODE 1: (dy', dy' * xhat) where dy' = dy masked by (y > 0) when relu  [backward reductions]
 // Each block handles a contiguous slab of rows; thread layout: cg = tid % G channel groups, rl = tid / G.
 // out: scratch[blocks][2][C]
 // relu: 0 = none, 1 = mask from the saved output y (needed when a residual was added), 2 = mask recomputed from x
 // as (xhat * gamma + beta > 0) -- one tensor read fewer.
-template <typename T, int MODE>
-__global__ __launch_bounds__(kNT) void k_colreduce(const T *__restrict__ x, const T *__restrict__ y, const T *__restrict__ dy,
-                                                   const float *__restrict__ stats, const float *__restrict__ gamma,
-                                                   const float *__restrict__ beta, int64_t n, int c, int relu,
-                                                   int64_t rows_per_block, float *__restrict__ scratch, int64_t dy_ld, int64_t y_ld) {
+// gout (MODE 1, may be NULL): the masked gradient dy' is also written there, [n, c] contiguous -- exact in T (it is dy or 0), so
+// the apply launch can read it back instead of masking dy a second time.
+// PAIR (MODE 1): a second norm xb / stats_b (no ReLU of its own) receives the same dy': its two sums go to scratch_b; every
+// operand is read once, and each norm's sums are taken exactly as a launch of its own would take them.
+template <typename T, int MODE, bool PAIR>
+__device__ inline void colreduce_rows(const T *__restrict__ x, const T *__restrict__ y, const T *__restrict__ dy,
+                                      const float *__restrict__ stats, const float *__restrict__ gamma,
+                                      const float *__restrict__ beta, int64_t n, int c, int relu,
+                                      int64_t rows_per_block, float *__restrict__ scratch, int64_t dy_ld, int64_t y_ld,
+                                      T *__restrict__ gout, const T *__restrict__ xb, const float *__restrict__ stats_b,
+                                      float *__restrict__ scratch_b) {
+  static_assert(!PAIR || MODE == 1, "the forward pair reduces its two inputs in separate workgroups");
   constexpr int W = Width<T>::V;
   const int G = c / W;              // channel groups per row
   const int RL = kNT / G;           // rows in flight per block iteration (G <= 256)
@@ -40,11 +56,13 @@ __global__ __launch_bounds__(kNT) void k_colreduce(const T *__restrict__ x, cons
 #pragma unroll
   for (int i = 0; i < W; ++i) s0[i] = s1[i] = 0.f;
   float mean[W], istd[W], gm[W], bt[W];
+  float q0[PAIR ? W : 1], q1[PAIR ? W : 1], mean_b[PAIR ? W : 1], istd_b[PAIR ? W : 1];   // the second norm's sums and statistics
   if (MODE == 1) {
 #pragma unroll
     for (int i = 0; i < W; ++i) {
       mean[i] = stats[cg * W + i]; istd[i] = stats[c + cg * W + i];
       gm[i] = relu == 2 ? gamma[cg * W + i] : 0.f; bt[i] = relu == 2 ? beta[cg * W + i] : 0.f;
+      if constexpr (PAIR) { q0[i] = q1[i] = 0.f; mean_b[i] = stats_b[cg * W + i]; istd_b[i] = stats_b[c + cg * W + i]; }
     }
   } else {
     // forward statistics are accumulated about a per-channel pivot (row 0, the same for every block) so that
@@ -58,7 +76,7 @@ __global__ __launch_bounds__(kNT) void k_colreduce(const T *__restrict__ x, cons
     // U rows per thread are in flight before the first is consumed (a streaming reduction needs ~50 KB of loads in
     // flight per CU to cover the HBM latency); sums are then taken in row order, i.e. exactly as a 1-row loop would
     constexpr int U = MODE == 0 ? 4 : 2;
-    auto accumulate = [&](const float (&xv)[W], float (&gv)[W], const float (&yv)[W]) __attribute__((always_inline)) {
+    auto accumulate = [&](const float (&xv)[W], float (&gv)[W], const float (&yv)[W], const float (&xbv)[W], int64_t row) __attribute__((always_inline)) {
       if (MODE == 0) {
 #pragma unroll
         for (int i = 0; i < W; ++i) { const float d = xv[i] - mean[i]; s0[i] += d; s1[i] += d * d; }
@@ -72,10 +90,15 @@ __global__ __launch_bounds__(kNT) void k_colreduce(const T *__restrict__ x, cons
         }
 #pragma unroll
         for (int i = 0; i < W; ++i) { s0[i] += gv[i]; s1[i] += gv[i] * (xv[i] - mean[i]) * istd[i]; }
+        if constexpr (PAIR) {
+#pragma unroll
+          for (int i = 0; i < W; ++i) { q0[i] += gv[i]; q1[i] += gv[i] * (xbv[i] - mean_b[i]) * istd_b[i]; }
+        }
+        if (gout) stv<W>(gout + row * c + cg * W, gv);
       }
     };
     for (; r + (U - 1) * RL < r1; r += U * RL) {
-      float xv[U][W], gv[U][W], yv[U][W];
+      float xv[U][W], gv[U][W], yv[U][W], xbv[U][W];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int64_t o = (r + u * RL) * c + cg * W;
@@ -83,20 +106,22 @@ __global__ __launch_bounds__(kNT) void k_colreduce(const T *__restrict__ x, cons
         if (MODE == 1) {
           ldv<W>(dy + (r + u * RL) * dy_ld + cg * W, gv[u]);
           if (relu == 1) ldv<W>(y + (r + u * RL) * y_ld + cg * W, yv[u]);
+          if constexpr (PAIR) ldv<W>(xb + o, xbv[u]);
         }
       }
 #pragma unroll
-      for (int u = 0; u < U; ++u) accumulate(xv[u], gv[u], yv[u]);
+      for (int u = 0; u < U; ++u) accumulate(xv[u], gv[u], yv[u], xbv[u], r + u * RL);
     }
     for (; r < r1; r += RL) {
-      float xv[W], gv[W], yv[W];
+      float xv[W], gv[W], yv[W], xbv[W];
       const int64_t o = r * c + cg * W;
       ldv<W>(x + o, xv);
       if (MODE == 1) {
         ldv<W>(dy + r * dy_ld + cg * W, gv);
         if (relu == 1) ldv<W>(y + r * y_ld + cg * W, yv);
+        if constexpr (PAIR) ldv<W>(xb + o, xbv);
       }
-      accumulate(xv, gv, yv);
+      accumulate(xv, gv, yv, xbv, r);
     }
   }
   // block reduction over rl through LDS
@@ -113,6 +138,44 @@ __global__ __launch_bounds__(kNT) void k_colreduce(const T *__restrict__ x, cons
 #pragma unroll
     for (int i = 0; i < W; ++i) { dst[cg * W + i] = s0[i]; dst[c + cg * W + i] = s1[i]; }
   }
+  if constexpr (PAIR) {       // the same block reduction for the second norm's sums, through the same LDS
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < W; ++i) { red[0][threadIdx.x][i] = q0[i]; red[1][threadIdx.x][i] = q1[i]; }
+    __syncthreads();
+    if (rl == 0) {
+      for (int j = 1; j < RL; ++j) {
+#pragma unroll
+        for (int i = 0; i < W; ++i) { q0[i] += red[0][j * G + cg][i]; q1[i] += red[1][j * G + cg][i]; }
+      }
+      float *dst = scratch_b + (int64_t)blockIdx.x * 2 * c;
+#pragma unroll
+      for (int i = 0; i < W; ++i) { dst[cg * W + i] = q0[i]; dst[c + cg * W + i] = q1[i]; }
+    }
+  }
+}
+template <typename T, int MODE>
+__global__ __launch_bounds__(kNT) void k_colreduce(const T *__restrict__ x, const T *__restrict__ y, const T *__restrict__ dy,
+                                                   const float *__restrict__ stats, const float *__restrict__ gamma,
+                                                   const float *__restrict__ beta, int64_t n, int c, int relu,
+                                                   int64_t rows_per_block, float *__restrict__ scratch, int64_t dy_ld, int64_t y_ld,
+                                                   T *__restrict__ gout) {
+  colreduce_rows<T, MODE, false>(x, y, dy, stats, gamma, beta, n, c, relu, rows_per_block, scratch, dy_ld, y_ld, gout, nullptr, nullptr, nullptr);
+}
+// the two norms of a pair in one launch.  MODE 0: blockIdx.y picks the norm (two independent reductions, each exactly k_colreduce<T, 0>);
+// MODE 1: both norms' sums from one read of xa, ya, dy, xb
+template <typename T, int MODE>
+__global__ __launch_bounds__(kNT) void k_colreduce_pair(const T *__restrict__ xa, const T *__restrict__ ya, const T *__restrict__ dy,
+                                                        const float *__restrict__ stats_a, const float *__restrict__ gamma_a,
+                                                        const float *__restrict__ beta_a, int64_t n, int c, int relu,
+                                                        int64_t rows_per_block, float *__restrict__ scratch_a, int64_t dy_ld, int64_t y_ld,
+                                                        T *__restrict__ gout, const T *__restrict__ xb, const float *__restrict__ stats_b,
+                                                        float *__restrict__ scratch_b) {
+  if constexpr (MODE == 0)
+    colreduce_rows<T, 0, false>(blockIdx.y ? xb : xa, nullptr, nullptr, nullptr, nullptr, nullptr, n, c, 0, rows_per_block,
+                                blockIdx.y ? scratch_b : scratch_a, c, c, nullptr, nullptr, nullptr, nullptr);
+  else
+    colreduce_rows<T, 1, true>(xa, ya, dy, stats_a, gamma_a, beta_a, n, c, relu, rows_per_block, scratch_a, dy_ld, y_ld, gout, xb, stats_b, scratch_b);
 }
 
 // fold the per-block partials (fixed order, deterministic) and finish: forward -> mean / invstd / running stats,
@@ -154,10 +217,10 @@ __global__ __launch_bounds__(256) void k_partial_reduce(const float *__restrict_
 
 // pivot_mode 0: the per-channel pivot is row 0 of x (k_colreduce<0>); 1: pivot_ptr[ch] (or 0 if NULL) -- conv-epilogue partials
 template <typename T>
-__global__ __launch_bounds__(256) void k_fold_fwd(const float *__restrict__ scratch, const T *__restrict__ x, int nblocks, int c,
-                                                  int64_t n, float eps, float momentum, float *__restrict__ running_mean,
-                                                  float *__restrict__ running_var, long long *__restrict__ nbt,
-                                                  float *__restrict__ stats, int pivot_mode, const float *__restrict__ pivot_ptr) {
+__device__ inline void fold_fwd_body(const float *__restrict__ scratch, const T *__restrict__ x, int nblocks, int c,
+                                     int64_t n, float eps, float momentum, float *__restrict__ running_mean,
+                                     float *__restrict__ running_var, long long *__restrict__ nbt,
+                                     float *__restrict__ stats, int pivot_mode, const float *__restrict__ pivot_ptr) {
   __shared__ double red[kFoldSl][2][kFoldCh];
   const int ch = blockIdx.x * kFoldCh + (threadIdx.x % kFoldCh), part = threadIdx.x / kFoldCh;
   double s, ss;
@@ -176,6 +239,29 @@ __global__ __launch_bounds__(256) void k_fold_fwd(const float *__restrict__ scra
     running_mean[ch] = (float)((1.0 - momentum) * running_mean[ch] + momentum * mean);
     running_var[ch] = (float)((1.0 - momentum) * running_var[ch] + momentum * unb);
   }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_fold_fwd(const float *__restrict__ scratch, const T *__restrict__ x, int nblocks, int c,
+                                                  int64_t n, float eps, float momentum, float *__restrict__ running_mean,
+                                                  float *__restrict__ running_var, long long *__restrict__ nbt,
+                                                  float *__restrict__ stats, int pivot_mode, const float *__restrict__ pivot_ptr) {
+  fold_fwd_body<T>(scratch, x, nblocks, c, n, eps, momentum, running_mean, running_var, nbt, stats, pivot_mode, pivot_ptr);
+}
+// one norm of a forward pair as the kernels see it: input, parameters, buffers, and where its partial rows / statistics lie
+template <typename T> struct PairFwdNorm {
+  const T *x;
+  const float *gamma, *beta;
+  float *running_mean, *running_var;
+  long long *nbt;
+  float *stats;
+  const float *scratch;
+  float eps, momentum;
+};
+// k_fold_fwd for the two norms of a pair: blockIdx.y picks the norm
+template <typename T>
+__global__ __launch_bounds__(256) void k_fold_fwd_pair(PairFwdNorm<T> a, PairFwdNorm<T> b, int nblocks, int c, int64_t n) {
+  const PairFwdNorm<T> &p = blockIdx.y ? b : a;
+  fold_fwd_body<T>(p.scratch, p.x, nblocks, c, n, p.eps, p.momentum, p.running_mean, p.running_var, p.nbt, p.stats, 0, nullptr);
 }
 // split API (SyncBN): local mean and M2 = sum (x - mean)^2, to be combined across ranks with Chan's formula
 template <typename T>
@@ -196,8 +282,8 @@ __global__ __launch_bounds__(256) void k_fold_stats(const float *__restrict__ sc
   if (ch == 0) mean_m2[2 * c] = (float)n;   // [mean | M2 | count]: one packed all-gather per layer
 }
 
-__global__ __launch_bounds__(256) void k_fold_bwd(const float *__restrict__ scratch, int nblocks, int c, float *__restrict__ dgamma,
-                                                  float *__restrict__ dbeta, float *__restrict__ sums) {
+__device__ inline void fold_bwd_body(const float *__restrict__ scratch, int nblocks, int c, float *__restrict__ dgamma,
+                                     float *__restrict__ dbeta, float *__restrict__ sums) {
   __shared__ double red[kFoldSl][2][kFoldCh];
   const int ch = blockIdx.x * kFoldCh + (threadIdx.x % kFoldCh), part = threadIdx.x / kFoldCh;
   double s, ss;
@@ -207,6 +293,18 @@ __global__ __launch_bounds__(256) void k_fold_bwd(const float *__restrict__ scra
   dgamma[ch] = (float)ss;
   sums[ch] = (float)s;
   sums[c + ch] = (float)ss;
+}
+__global__ __launch_bounds__(256) void k_fold_bwd(const float *__restrict__ scratch, int nblocks, int c, float *__restrict__ dgamma,
+                                                  float *__restrict__ dbeta, float *__restrict__ sums) {
+  fold_bwd_body(scratch, nblocks, c, dgamma, dbeta, sums);
+}
+// k_fold_bwd for the two norms of a pair: blockIdx.y picks the norm
+__global__ __launch_bounds__(256) void k_fold_bwd_pair(const float *__restrict__ scratch_a, const float *__restrict__ scratch_b, int nblocks,
+                                                       int c, float *__restrict__ dgamma_a, float *__restrict__ dbeta_a,
+                                                       float *__restrict__ sums_a, float *__restrict__ dgamma_b,
+                                                       float *__restrict__ dbeta_b, float *__restrict__ sums_b) {
+  if (blockIdx.y) fold_bwd_body(scratch_b, nblocks, c, dgamma_b, dbeta_b, sums_b);
+  else fold_bwd_body(scratch_a, nblocks, c, dgamma_a, dbeta_a, sums_a);
 }
 
 // SyncBN: combine the per-rank [mean | M2 | count] records (Chan's parallel formula, double) into the global
@@ -793,6 +891,184 @@ __global__ __launch_bounds__(kNT) void k_bn_bwd_apply_fold(const T *__restrict__
   }
 }
 
+// ------------------------------------------------------------------------------------------------ two norms, shared passes
+// A residual block with a downsample branch runs two norms on the same rows: forward y = relu?(bn_a(xa) + bn_b(xb)), backward
+// both receive the same masked gradient.  As single calls the branch output is written and read back only to be added (7 tensor
+// passes forward), and the masked gradient is written and read back twice (13 backward).  The pair kernels read every operand
+// once per step -- statistics of both norms in one launch, one fold launch (blockIdx.y = the norm), one apply -- 5 passes forward
+// and 10 backward.  Every per-element expression and every summation order is the single kernels': results are bit-identical.
+// FOLD: the `fold` path -- every workgroup folds both norms' partial rows itself, as k_bn_apply_fold / k_bn_bwd_apply_fold do.
+template <typename T, bool FOLD>
+__device__ inline void pair_fwd_consts(const PairFwdNorm<T> &p, int64_t n, int c, int nparts, int G, int RL, int cg, int rl,
+                                       float (&mean)[Width<T>::V], float (&sc)[Width<T>::V], float (&bt)[Width<T>::V]) {
+  constexpr int W = Width<T>::V;
+  if constexpr (FOLD) {
+    double t0[W], t1[W];
+    fold_in_block<W>(p.scratch, nparts, c, G, RL, cg, rl, t0, t1);
+    if (rl < RL) {
+      float piv[W];
+      if (n > 0) ldv<W>(p.x + cg * W, piv);          // the pivot of k_colreduce<T, 0>: row 0
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        const int ch = cg * W + k;
+        const double dm = n > 0 ? t0[k] / (double)n : 0.0;
+        double var = n > 0 ? t1[k] / (double)n - dm * dm : 0.0;
+        if (var < 0.0) var = 0.0;
+        const double m = (n > 0 ? (double)piv[k] : 0.0) + dm;
+        const float mf = (float)m, isf = (float)(1.0 / sqrt(var + (double)p.eps));
+        mean[k] = mf; sc[k] = isf * p.gamma[ch]; bt[k] = p.beta[ch];
+        if (blockIdx.x == 0 && rl == 0) {
+          p.stats[ch] = mf; p.stats[c + ch] = isf;
+          if (p.running_mean) {
+            const double unb = n > 1 ? var * (double)n / (double)(n - 1) : var;
+            p.running_mean[ch] = (float)((1.0 - p.momentum) * p.running_mean[ch] + p.momentum * m);
+            p.running_var[ch] = (float)((1.0 - p.momentum) * p.running_var[ch] + p.momentum * unb);
+          }
+        }
+      }
+    }
+    if (p.nbt && blockIdx.x == 0 && threadIdx.x == 0) *p.nbt += 1;
+  } else {
+    if (rl < RL) {
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        const int ch = cg * W + k;
+        sc[k] = p.stats[c + ch] * p.gamma[ch];
+        mean[k] = p.stats[ch];
+        bt[k] = p.beta[ch];
+      }
+    }
+  }
+}
+
+// y = relu?(bn_a(xa) + stored(bn_b(xb))); res (may be NULL) = bn_b(xb), the branch output the single calls materialise
+template <typename T, bool FOLD>
+__global__ __launch_bounds__(kNT) void k_bn_apply_pair(PairFwdNorm<T> a, PairFwdNorm<T> b, int64_t n, int c, int nparts, int relu,
+                                                       T *__restrict__ y, int64_t y_ld, T *__restrict__ res) {
+  // the single kernels' arithmetic, spelled out: the compiler contracts (x - mean) * sc + bt to one fma in every instance of
+  // k_bn_apply / k_bn_apply_fold, and what it contracts in a kernel with two norms in flight is its own choice otherwise
+#pragma clang fp contract(off)
+  constexpr int W = Width<T>::V;
+  const int G = c / W, RL = kNT / G;
+  const int cg = threadIdx.x % G, rl = threadIdx.x / G;
+  float sca[W], ma[W], bta[W], scb[W], mb[W], btb[W];
+  pair_fwd_consts<T, FOLD>(a, n, c, nparts, G, RL, cg, rl, ma, sca, bta);
+  if constexpr (FOLD) __syncthreads();             // fold_in_block's LDS is read by the first fold until here
+  pair_fwd_consts<T, FOLD>(b, n, c, nparts, G, RL, cg, rl, mb, scb, btb);
+  if (rl >= RL) return;
+  const int64_t stride = (int64_t)gridDim.x * RL;
+  for (int64_t r = (int64_t)blockIdx.x * RL + rl; r < n; r += 2 * stride) {
+    const int64_t r2 = r + stride;
+    const bool two = r2 < n;
+    float xa[W], xa2[W], xb[W], xb2[W];
+    ldv<W>(a.x + r * c + cg * W, xa);
+    ldv<W>(b.x + r * c + cg * W, xb);
+    if (two) { ldv<W>(a.x + r2 * c + cg * W, xa2); ldv<W>(b.x + r2 * c + cg * W, xb2); }
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      xb[k] = __builtin_fmaf(xb[k] - mb[k], scb[k], btb[k]);     // the expressions of k_bn_apply, the branch rounded as its store would
+      float o = __builtin_fmaf(xa[k] - ma[k], sca[k], bta[k]);
+      o += stored_value<T>(xb[k]);
+      xa[k] = (relu && o < 0.f) ? 0.f : o;
+    }
+    if (res) stv_nt<W>(res + r * c + cg * W, xb);
+    stv_nt<W>(y + r * y_ld + cg * W, xa);
+    if (two) {
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        xb2[k] = __builtin_fmaf(xb2[k] - mb[k], scb[k], btb[k]);
+        float o = __builtin_fmaf(xa2[k] - ma[k], sca[k], bta[k]);
+        o += stored_value<T>(xb2[k]);
+        xa2[k] = (relu && o < 0.f) ? 0.f : o;
+      }
+      if (res) stv_nt<W>(res + r2 * c + cg * W, xb2);
+      stv_nt<W>(y + r2 * y_ld + cg * W, xa2);
+    }
+  }
+}
+
+// one norm of a backward pair as the kernels see it
+template <typename T> struct PairBwdNorm {
+  const T *x;
+  const float *gamma, *beta, *stats;
+  const float *scratch;     // partial rows (FOLD)
+  const float *sums;        // folded sums (three launches)
+  float *dgamma, *dbeta;    // FOLD: workgroup 0 writes them
+  T *dx;
+};
+template <typename T, bool FOLD>
+__device__ inline void pair_bwd_consts(const PairBwdNorm<T> &p, int c, int nparts, float inv_n, int relu, int G, int RL, int cg, int rl,
+                                       float (&mean)[Width<T>::V], float (&istd)[Width<T>::V], float (&sc)[Width<T>::V],
+                                       float (&bt)[Width<T>::V], float (&gi)[Width<T>::V], float (&m1)[Width<T>::V],
+                                       float (&m2)[Width<T>::V]) {
+  constexpr int W = Width<T>::V;
+  double t0[W], t1[W];
+  if constexpr (FOLD) fold_in_block<W>(p.scratch, nparts, c, G, RL, cg, rl, t0, t1);
+  if (rl >= RL) return;
+#pragma unroll
+  for (int k = 0; k < W; ++k) {
+    const int ch = cg * W + k;
+    float s, ss;
+    if constexpr (FOLD) {
+      s = (float)t0[k]; ss = (float)t1[k];            // what k_fold_bwd stores
+      if (blockIdx.x == 0 && rl == 0) { p.dbeta[ch] = s; p.dgamma[ch] = ss; }
+    } else {
+      s = p.sums[ch]; ss = p.sums[c + ch];
+    }
+    mean[k] = p.stats[ch]; istd[k] = p.stats[c + ch];
+    sc[k] = istd[k] * (relu == 2 ? p.gamma[ch] : 0.f);
+    bt[k] = relu == 2 ? p.beta[ch] : 0.f;
+    gi[k] = p.gamma[ch] * istd[k];
+    m1[k] = s * inv_n; m2[k] = ss * inv_n;
+  }
+}
+
+// dxa, dxb from one read of xa, ya, dy, xb: both norms receive dy' = dy masked by norm a's ReLU (relu: 0 or 1 -- a mask recomputed
+// from xa alone would ignore the branch that was added); dres (may be NULL) = dy'
+template <typename T, bool FOLD>
+__global__ __launch_bounds__(kNT) void k_bn_bwd_apply_pair(PairBwdNorm<T> a, PairBwdNorm<T> b, const T *__restrict__ y,
+                                                           const T *__restrict__ dy, int64_t n, int c, int nparts, float inv_n, int relu,
+                                                           T *__restrict__ dres, int64_t dy_ld, int64_t y_ld) {
+  // the single kernels' arithmetic, spelled out.  In dy' - m1 - xhat * m2 the compiler contracts the last two operations to one
+  // fma in k_bn_bwd_apply<bf16> and in both k_bn_bwd_apply_fold, and not in k_bn_bwd_apply<float>; what it would choose with two
+  // norms in flight is something else again.  tests/test_gpu_norm_pair.py holds each instance to its single kernel bit for bit.
+#pragma clang fp contract(off)
+  constexpr bool kFma = FOLD || sizeof(T) == 2;
+  constexpr int W = Width<T>::V;
+  const int G = c / W, RL = kNT / G;
+  const int cg = threadIdx.x % G, rl = threadIdx.x / G;
+  float mean[W], istd[W], sc[W], bt[W], gi[W], m1[W], m2[W];
+  float mean_b[W], istd_b[W], sc_b[W], bt_b[W], gi_b[W], m1_b[W], m2_b[W];
+  pair_bwd_consts<T, FOLD>(a, c, nparts, inv_n, relu, G, RL, cg, rl, mean, istd, sc, bt, gi, m1, m2);
+  if constexpr (FOLD) __syncthreads();             // fold_in_block's LDS is read by the first fold until here
+  pair_bwd_consts<T, FOLD>(b, c, nparts, inv_n, 0, G, RL, cg, rl, mean_b, istd_b, sc_b, bt_b, gi_b, m1_b, m2_b);
+  if (rl >= RL) return;
+  const int64_t stride = (int64_t)gridDim.x * RL;
+  for (int64_t r = (int64_t)blockIdx.x * RL + rl; r < n; r += stride) {
+    const int64_t o = r * c + cg * W;
+    float xv[W], gv[W], xbv[W];
+    ldv<W>(a.x + o, xv);
+    ldv<W>(b.x + o, xbv);
+    ldv<W>(dy + r * dy_ld + cg * W, gv);
+    if (relu == 1) {
+      float yv[W];
+      ldv<W>(y + r * y_ld + cg * W, yv);
+#pragma unroll
+      for (int k = 0; k < W; ++k) gv[k] = yv[k] > 0.f ? gv[k] : 0.f;
+    }
+    if (dres) stv_nt<W>(dres + o, gv);
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const float xh = (xv[k] - mean[k]) * istd[k], u = gv[k] - m1[k];
+      xv[k] = gi[k] * (kFma ? __builtin_fmaf(-xh, m2[k], u) : u - xh * m2[k]);
+      const float xhb = (xbv[k] - mean_b[k]) * istd_b[k], ub = gv[k] - m1_b[k];
+      xbv[k] = gi_b[k] * (kFma ? __builtin_fmaf(-xhb, m2_b[k], ub) : ub - xhb * m2_b[k]);
+    }
+    stv_nt<W>(a.dx + o, xv);
+    stv_nt<W>(b.dx + o, xbv);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ host: one plan per call
 // Everything a BatchNorm call decides on the host is computed ONCE by norm_plan() from (direction, n, c, element size, conv
 // partial rows, resident-workgroup cap, tuning table): the path, every grid and rows-per-block, and where each workspace region
@@ -966,7 +1242,7 @@ void stats_rows(const NormPlan &p, const T *x, int64_t n, int c, const float *pa
   const T *no = nullptr;
   const float *nof = nullptr;
   if (p.from_partials) LGS_KLAUNCH(k_partial_reduce, p.fold_rows, 256, 0, s, partials, partial_rows, 2 * c, p.partial_rpb, rows);
-  else LGS_KLAUNCH((k_colreduce<T, 0>), p.reduce_grid, kNT, 0, s, x, no, no, nof, nof, nof, n, c, 0, p.rows_per_block, rows, (int64_t)c, (int64_t)c);
+  else LGS_KLAUNCH((k_colreduce<T, 0>), p.reduce_grid, kNT, 0, s, x, no, no, nof, nof, nof, n, c, 0, p.rows_per_block, rows, (int64_t)c, (int64_t)c, (T *)nullptr);
 }
 
 template <typename T>
@@ -980,7 +1256,7 @@ int bn_forward_t(const T *x, int64_t n, int c, const float *gamma, const float *
   const float *nof = nullptr;
   switch (p.path) {
     case kNormFold:
-      LGS_KLAUNCH((k_colreduce<T, 0>), p.reduce_grid, kNT, 0, s, x, no, no, nof, nof, nof, n, c, 0, p.rows_per_block, rows, (int64_t)c, (int64_t)c);
+      LGS_KLAUNCH((k_colreduce<T, 0>), p.reduce_grid, kNT, 0, s, x, no, no, nof, nof, nof, n, c, 0, p.rows_per_block, rows, (int64_t)c, (int64_t)c, (T *)nullptr);
       LGS_KLAUNCH((k_bn_apply_fold<T>), p.apply_grid, kNT, 0, s, x, res, n, c, gamma, beta, eps, momentum, rm, rv, nbt, stats, rows, p.fold_rows, relu, y, y_ld);
       break;
     case kNormFused: {
@@ -999,17 +1275,26 @@ int bn_forward_t(const T *x, int64_t n, int c, const float *gamma, const float *
   return 0;
 }
 
+// relu mode 1 with a dresidual output, paths `three` and `fold`: the reduce launch writes the masked gradient to dres while it sums,
+// and the apply launch reads it back as an unmasked dy -- y is read once and dy masked once (7 tensor passes instead of 8; the
+// value is dy or 0, exact in T, so dx and dres are what the two-mask launches give).  Knob BN_PAIR = 0: mask in both launches.
 template <typename T>
 int bn_backward_t(const T *x, const T *y, const T *dy, int64_t n, int c, const float *gamma, const float *beta, const float *stats, int relu,
                   T *dx, T *dres, float *dgamma, float *dbeta, void *workspace, hipStream_t s, int64_t dy_ld, int64_t y_ld) {
   const NormPlan p = norm_plan(kNormBwd, n, c, dtype_of<T>(), 0, [] { return fused_resident(reinterpret_cast<const void *>(&k_bn_bwd_fused<T>)); });
   float *rows = region(workspace, p.partials), *sums = region(workspace, p.sums);
   const float inv_n = n > 0 ? 1.f / (float)n : 0.f;
+  const bool once = relu == 1 && dres && n > 0 && p.path != kNormFused && tune(T_BN_PAIR) != 0;
+  T *gout = once ? dres : nullptr;
+  const T *ay = once ? nullptr : y, *ady = once ? dres : dy;      // what the apply launch reads
+  T *adres = once ? nullptr : dres;
+  const int arelu = once ? 0 : relu;
+  const int64_t ady_ld = once ? c : dy_ld;
   switch (p.path) {
     case kNormFold:
-      LGS_KLAUNCH((k_colreduce<T, 1>), p.reduce_grid, kNT, 0, s, x, y, dy, stats, gamma, beta, n, c, relu, p.rows_per_block, rows, dy_ld, y_ld);
-      LGS_KLAUNCH((k_bn_bwd_apply_fold<T>), p.apply_grid, kNT, 0, s, x, y, dy, n, c, gamma, beta, stats, rows, p.fold_rows, inv_n, relu, dx, dres, dgamma,
-                  dbeta, dy_ld, y_ld);
+      LGS_KLAUNCH((k_colreduce<T, 1>), p.reduce_grid, kNT, 0, s, x, y, dy, stats, gamma, beta, n, c, relu, p.rows_per_block, rows, dy_ld, y_ld, gout);
+      LGS_KLAUNCH((k_bn_bwd_apply_fold<T>), p.apply_grid, kNT, 0, s, x, ay, ady, n, c, gamma, beta, stats, rows, p.fold_rows, inv_n, arelu, dx, adres, dgamma,
+                  dbeta, ady_ld, y_ld);
       break;
     case kNormFused: {
       unsigned *ctr = fused_counter(s);
@@ -1019,9 +1304,9 @@ int bn_backward_t(const T *x, const T *y, const T *dy, int64_t n, int c, const f
       break;
     }
     default:
-      LGS_KLAUNCH((k_colreduce<T, 1>), p.reduce_grid, kNT, 0, s, x, y, dy, stats, gamma, beta, n, c, relu, p.rows_per_block, rows, dy_ld, y_ld);
+      LGS_KLAUNCH((k_colreduce<T, 1>), p.reduce_grid, kNT, 0, s, x, y, dy, stats, gamma, beta, n, c, relu, p.rows_per_block, rows, dy_ld, y_ld, gout);
       LGS_KLAUNCH(k_fold_bwd, p.fold_grid, 256, 0, s, rows, p.fold_rows, c, dgamma, dbeta, sums);
-      if (p.apply_grid) LGS_KLAUNCH((k_bn_bwd_apply<T>), p.apply_grid, kNT, 0, s, x, y, dy, n, c, gamma, beta, stats, sums, inv_n, relu, dx, dres, dy_ld,
+      if (p.apply_grid) LGS_KLAUNCH((k_bn_bwd_apply<T>), p.apply_grid, kNT, 0, s, x, ay, ady, n, c, gamma, beta, stats, sums, inv_n, arelu, dx, adres, ady_ld,
                                     (const float *)nullptr, y_ld);
   }
   LGS_HIP(hipGetLastError());
@@ -1051,7 +1336,7 @@ int bn_bwd_reduce_t(const T *x, const T *y, const T *dy, int64_t n, int c, const
                     float *sums, float *dgamma, float *dbeta, void *workspace, hipStream_t s, int64_t dy_ld, int64_t y_ld) {
   const NormPlan p = norm_plan(kNormBwdReduce, n, c, dtype_of<T>(), 0, [] { return 0; });
   float *rows = region(workspace, p.partials), *spill = region(workspace, p.spill);  // dgamma / dbeta land there when the caller does not want them
-  LGS_KLAUNCH((k_colreduce<T, 1>), p.reduce_grid, kNT, 0, s, x, y, dy, stats, gamma, beta, n, c, relu, p.rows_per_block, rows, dy_ld, y_ld);
+  LGS_KLAUNCH((k_colreduce<T, 1>), p.reduce_grid, kNT, 0, s, x, y, dy, stats, gamma, beta, n, c, relu, p.rows_per_block, rows, dy_ld, y_ld, (T *)nullptr);
   LGS_KLAUNCH(k_fold_bwd, p.fold_grid, 256, 0, s, rows, p.fold_rows, c, dgamma ? dgamma : spill + c, dbeta ? dbeta : spill, sums);
   LGS_HIP(hipGetLastError());
   return 0;
@@ -1061,6 +1346,87 @@ int bn_bwd_apply_t(const T *x, const T *y, const T *dy, int64_t n, int c, const 
                    float inv_n_total, const float *inv_n_dev, int relu, T *dx, T *dres, hipStream_t s, int64_t dy_ld, int64_t y_ld) {
   const int grid = apply_blocks(n, c, Width<T>::V, 1, kApplyMaxBlocks);
   if (grid) LGS_KLAUNCH((k_bn_bwd_apply<T>), grid, kNT, 0, s, x, y, dy, n, c, gamma, beta, stats, sums, inv_n_total, relu, dx, dres, dy_ld, inv_n_dev, y_ld);
+  LGS_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- a pair of norms on the same rows (lgs_bn_forward_pair / lgs_bn_backward_pair)
+// The pair asks norm_plan() for the SINGLE-norm plan of (direction, n, c, dtype) and derives everything from it: the same
+// grids and rows per workgroup (so every sum is taken in the single call's order), and two sets of partial rows / `sums` rows
+// behind one another.  Where that plan says `fused`, the knob BN_PAIR is 0, or the tensor is empty, the pair entry points issue
+// today's two single calls (path 0).
+using NormPairPlan = lgs_norm_pair_plan_info;
+inline int64_t norm_pair_workspace_bytes(int64_t n, int c) { return 2 * ((norm_workspace_bytes(n, c) + 255) / 256 * 256); }
+inline int single_launches(const NormPlan &p) { return p.path == kNormFold ? 2 : p.path == kNormFused ? 1 : (p.apply_grid ? 3 : 2); }
+template <typename Cap>
+NormPairPlan norm_pair_plan(int dir, int64_t n, int c, int dtype, Cap &&resident_cap) {
+  NormPairPlan q = {};
+  const NormPlan p = norm_plan(dir, n, c, dtype, 0, resident_cap);
+  q.single_path = p.path;
+  q.workspace_bytes = norm_pair_workspace_bytes(n, c);
+  if (p.path == kNormFused || tune(T_BN_PAIR) == 0 || n <= 0) {
+    q.path = 0;
+    q.launches = 2 * single_launches(p);
+    return q;
+  }
+  q.path = p.path;
+  q.launches = p.path == kNormFold ? 2 : 3;
+  q.reduce_grid = p.reduce_grid; q.rows_per_block = p.rows_per_block; q.fold_rows = p.fold_rows;
+  q.fold_grid = p.fold_grid; q.apply_grid = p.apply_grid;
+  q.partials_a = p.partials;
+  q.partials_b = {q.partials_a.offset + q.partials_a.bytes, p.partials.bytes};
+  q.bytes_total = q.partials_b.offset + q.partials_b.bytes;
+  if (p.sums.bytes) {
+    q.sums_a = {q.bytes_total, p.sums.bytes};
+    q.sums_b = {q.sums_a.offset + q.sums_a.bytes, p.sums.bytes};
+    q.bytes_total = q.sums_b.offset + q.sums_b.bytes;
+  }
+  return q;
+}
+
+template <typename T>
+int bn_forward_pair_t(const PairFwdNorm<T> &a0, const PairFwdNorm<T> &b0, int64_t n, int c, int relu, T *y, int64_t y_ld, T *res,
+                      const NormPairPlan &q, void *workspace, hipStream_t s) {
+  PairFwdNorm<T> a = a0, b = b0;
+  a.scratch = region(workspace, q.partials_a);
+  b.scratch = region(workspace, q.partials_b);
+  const T *no = nullptr;
+  const float *nof = nullptr;
+  LGS_KLAUNCH((k_colreduce_pair<T, 0>), dim3(q.reduce_grid, 2), kNT, 0, s, a.x, no, no, nof, nof, nof, n, c, 0, q.rows_per_block,
+              const_cast<float *>(a.scratch), (int64_t)c, (int64_t)c, (T *)nullptr, b.x, nof, const_cast<float *>(b.scratch));
+  if (q.path == kNormFold) {
+    LGS_KLAUNCH((k_bn_apply_pair<T, true>), q.apply_grid, kNT, 0, s, a, b, n, c, q.fold_rows, relu, y, y_ld, res);
+  } else {
+    LGS_KLAUNCH((k_fold_fwd_pair<T>), dim3(q.fold_grid, 2), 256, 0, s, a, b, q.fold_rows, c, n);
+    LGS_KLAUNCH((k_bn_apply_pair<T, false>), q.apply_grid, kNT, 0, s, a, b, n, c, q.fold_rows, relu, y, y_ld, res);
+  }
+  LGS_HIP(hipGetLastError());
+  return 0;
+}
+
+template <typename T>
+int bn_backward_pair_t(const PairBwdNorm<T> &a0, const PairBwdNorm<T> &b0, const T *y, const T *dy, int64_t n, int c, int relu, T *dres,
+                       int64_t dy_ld, int64_t y_ld, const NormPairPlan &q, void *workspace, hipStream_t s) {
+  PairBwdNorm<T> a = a0, b = b0;
+  float *rows_a = region(workspace, q.partials_a), *rows_b = region(workspace, q.partials_b);
+  a.scratch = rows_a; b.scratch = rows_b;
+  const float inv_n = 1.f / (float)n;
+  // the masked gradient, where the caller wants it, is written by the reduce launch and read back by the apply (see bn_backward_t)
+  const bool once = relu == 1 && dres;
+  LGS_KLAUNCH((k_colreduce_pair<T, 1>), q.reduce_grid, kNT, 0, s, a.x, y, dy, a.stats, a.gamma, a.beta, n, c, relu, q.rows_per_block, rows_a, dy_ld,
+              y_ld, once ? dres : (T *)nullptr, b.x, b.stats, rows_b);
+  const T *ay = once ? nullptr : y, *ady = once ? dres : dy;
+  T *adres = once ? nullptr : dres;
+  const int arelu = once ? 0 : relu;
+  const int64_t ady_ld = once ? c : dy_ld;
+  if (q.path == kNormFold) {
+    LGS_KLAUNCH((k_bn_bwd_apply_pair<T, true>), q.apply_grid, kNT, 0, s, a, b, ay, ady, n, c, q.fold_rows, inv_n, arelu, adres, ady_ld, y_ld);
+  } else {
+    float *sums_a = region(workspace, q.sums_a), *sums_b = region(workspace, q.sums_b);
+    a.sums = sums_a; b.sums = sums_b;
+    LGS_KLAUNCH(k_fold_bwd_pair, dim3(q.fold_grid, 2), 256, 0, s, rows_a, rows_b, q.fold_rows, c, a.dgamma, a.dbeta, sums_a, b.dgamma, b.dbeta, sums_b);
+    LGS_KLAUNCH((k_bn_bwd_apply_pair<T, false>), q.apply_grid, kNT, 0, s, a, b, ay, ady, n, c, q.fold_rows, inv_n, arelu, adres, ady_ld, y_ld);
+  }
   LGS_HIP(hipGetLastError());
   return 0;
 }
@@ -1146,6 +1512,79 @@ int lgs_bn_backward(const void *x, const void *y, const void *dy, int64_t dy_row
   return with_elem(dtype, c, "lgs_bn_backward", [&](auto e) {
     return bn_backward_t(e.in(x), e.in(y), e.in(dy), n, c, gamma, beta, stats, relu, e.out(dx), e.out(dresidual), dgamma, dbeta, workspace,
                          (hipStream_t)stream, dy_ld, y_ld);
+  });
+}
+
+int64_t lgs_bn_pair_workspace_bytes(int64_t n, int c) { return norm_pair_workspace_bytes(n, c); }
+
+// the pair's plan for a call on the current device (asks it for the resident-workgroup bound where the single plan would)
+int lgs_bn_pair_plan(int direction, int64_t n, int c, int dtype, lgs_norm_pair_plan_info *out) {
+  LGS_REQUIRE(out && (direction == kNormFwd || direction == kNormBwd) && n >= 0, "lgs_bn_pair_plan: bad argument");
+  return with_elem(dtype, c, "lgs_bn_pair_plan", [&](auto e) {
+    using T = typename decltype(e)::T;
+    *out = norm_pair_plan(direction, n, c, dtype, [&] {
+      return fused_resident(direction == kNormFwd ? reinterpret_cast<const void *>(&k_bn_fwd_fused<T>) : reinterpret_cast<const void *>(&k_bn_bwd_fused<T>));
+    });
+    return 0;
+  });
+}
+int lgs_debug_norm_pair_plan(const lgs_norm_plan_query *q, lgs_norm_pair_plan_info *out) {
+  LGS_REQUIRE(q && out && (q->direction == kNormFwd || q->direction == kNormBwd) && q->n >= 0, "lgs_debug_norm_pair_plan: bad argument");
+  return with_elem(q->dtype, q->c, "lgs_debug_norm_pair_plan", [&](auto) {
+    *out = norm_pair_plan(q->direction, q->n, q->c, q->dtype, [&] { return q->resident_cap; });
+    return 0;
+  });
+}
+
+int lgs_bn_forward_pair(const void *xa, const lgs_bn_params *na, float *stats_a, const void *xb, const lgs_bn_params *nb, float *stats_b,
+                        int64_t n, int c, int relu, void *y, int64_t y_row_stride, void *res, int dtype, void *workspace, void *stream) {
+  LGS_REQUIRE(xa && xb && na && nb && na->gamma && na->beta && nb->gamma && nb->beta && stats_a && stats_b && y && workspace && n >= 0,
+              "lgs_bn_forward_pair: null argument");
+  LGS_BN_STRIDE("lgs_bn_forward_pair", y, y_row_stride, y_ld);
+  lgs_norm_pair_plan_info q;
+  int rc;
+  if ((rc = lgs_bn_pair_plan(kNormFwd, n, c, dtype, &q))) return rc;
+  if (q.path == 0) {      // today's two calls; the branch output is their intermediate
+    LGS_REQUIRE(res, "lgs_bn_forward_pair: this call runs as two single norms (lgs_bn_pair_plan: path 0) and needs the res buffer");
+    if ((rc = lgs_bn_forward(xb, n, c, nb->gamma, nb->beta, nb->eps, nb->momentum, nb->running_mean, nb->running_var, nb->num_batches_tracked,
+                             nullptr, 0, res, stats_b, dtype, workspace, nullptr, 0, nullptr, 0, stream))) return rc;
+    return lgs_bn_forward(xa, n, c, na->gamma, na->beta, na->eps, na->momentum, na->running_mean, na->running_var, na->num_batches_tracked,
+                          res, relu, y, stats_a, dtype, workspace, nullptr, 0, nullptr, y_row_stride, stream);
+  }
+  return with_elem(dtype, c, "lgs_bn_forward_pair", [&](auto e) {
+    using T = typename decltype(e)::T;
+    const PairFwdNorm<T> a = {e.in(xa), na->gamma, na->beta, na->running_mean, na->running_var, reinterpret_cast<long long *>(na->num_batches_tracked),
+                              stats_a, nullptr, na->eps, na->momentum};
+    const PairFwdNorm<T> b = {e.in(xb), nb->gamma, nb->beta, nb->running_mean, nb->running_var, reinterpret_cast<long long *>(nb->num_batches_tracked),
+                              stats_b, nullptr, nb->eps, nb->momentum};
+    return bn_forward_pair_t<T>(a, b, n, c, relu, e.out(y), y_ld, e.out(res), q, workspace, (hipStream_t)stream);
+  });
+}
+
+int lgs_bn_backward_pair(const void *xa, const void *ya, const float *gamma_a, const float *beta_a, const float *stats_a, int relu,
+                         const void *xb, const float *gamma_b, const float *stats_b, const void *dy, int64_t dy_row_stride, int64_t n, int c,
+                         void *dxa, void *dxb, float *dgamma_a, float *dbeta_a, float *dgamma_b, float *dbeta_b, void *dresidual, int dtype,
+                         void *workspace, int64_t ya_row_stride, void *stream) {
+  LGS_REQUIRE(xa && xb && dy && dxa && dxb && gamma_a && gamma_b && stats_a && stats_b && dgamma_a && dbeta_a && dgamma_b && dbeta_b && workspace &&
+                  n >= 0, "lgs_bn_backward_pair: null argument");
+  LGS_BN_STRIDE("lgs_bn_backward_pair", dy, dy_row_stride, dy_ld);
+  LGS_BN_STRIDE("lgs_bn_backward_pair", ya, ya_row_stride, y_ld);
+  LGS_REQUIRE(relu == 0 || relu == 1, "lgs_bn_backward_pair: relu is 0 or 1 (a mask recomputed from xa alone would ignore the added branch)");
+  LGS_REQUIRE(relu != 1 || ya, "lgs_bn_backward_pair: relu mode 1 needs the forward output");
+  lgs_norm_pair_plan_info q;
+  int rc;
+  if ((rc = lgs_bn_pair_plan(kNormBwd, n, c, dtype, &q))) return rc;
+  if (q.path == 0) {      // today's two calls; the masked gradient is their intermediate
+    LGS_REQUIRE(dresidual, "lgs_bn_backward_pair: this call runs as two single norms (lgs_bn_pair_plan: path 0) and needs the dresidual buffer");
+    if ((rc = lgs_bn_backward(xa, ya, dy, dy_row_stride, n, c, gamma_a, beta_a, stats_a, relu, dxa, dresidual, dgamma_a, dbeta_a, dtype, workspace,
+                              ya_row_stride, stream))) return rc;
+    return lgs_bn_backward(xb, nullptr, dresidual, 0, n, c, gamma_b, nullptr, stats_b, 0, dxb, nullptr, dgamma_b, dbeta_b, dtype, workspace, 0, stream);
+  }
+  return with_elem(dtype, c, "lgs_bn_backward_pair", [&](auto e) {
+    using T = typename decltype(e)::T;
+    const PairBwdNorm<T> a = {e.in(xa), gamma_a, beta_a, stats_a, nullptr, nullptr, dgamma_a, dbeta_a, e.out(dxa)};
+    const PairBwdNorm<T> b = {e.in(xb), gamma_b, nullptr, stats_b, nullptr, nullptr, dgamma_b, dbeta_b, e.out(dxb)};
+    return bn_backward_pair_t<T>(a, b, e.in(ya), e.in(dy), n, c, relu, e.out(dresidual), dy_ld, y_ld, q, workspace, (hipStream_t)stream);
   });
 }
 

@@ -82,6 +82,11 @@ const Knob kKnobs[T_COUNT] = {
                                         "reads per point, no [N, P + K, C] tensor); 0 = the torch gather path CPU tensors take (index gathers, normalise, mean) and "
                                         "the torch restatement of the sampler -- read at call time: for timing the two next to each other and for switching "
                                         "the kernels off in the field"},
+    {T_BN_PAIR, "BN_PAIR", 1, "BatchNorm passes shared inside a residual block (paths `three` and `fold`; A/B): 1 = lgs_bn_backward masks dy ONCE when it "
+                              "also returns the residual gradient (the reduce launch writes the masked gradient, the apply reads it back: 7 tensor "
+                              "passes instead of 8), and lgs_bn_forward_pair / lgs_bn_backward_pair run the two norms of a downsample block on shared "
+                              "reads (5 instead of 7 passes forward, 10 instead of 13 backward, 3 launches instead of 6); 0 = the single calls, dy "
+                              "masked in both launches.  Bit-identical either way"},
 };
 std::atomic<int64_t> g_val[T_COUNT];
 std::once_flag g_once;

@@ -83,6 +83,14 @@ class NormPlanInfo(ctypes.Structure):
                [("bytes_total", ctypes.c_int64), ("workspace_bytes", ctypes.c_int64)]
 
 
+class NormPairPlanInfo(ctypes.Structure):
+    """lgs_norm_pair_plan_info: what lgs_bn_pair_plan / lgs_debug_norm_pair_plan answer"""
+    _fields_ = [(n, ctypes.c_int) for n in ("path", "single_path", "launches", "reduce_grid")] + [("rows_per_block", ctypes.c_int64)] + \
+               [(n, ctypes.c_int) for n in ("fold_rows", "fold_grid", "apply_grid")] + \
+               [(n, ConvPlanRegion) for n in ("partials_a", "partials_b", "sums_a", "sums_b")] + \
+               [("bytes_total", ctypes.c_int64), ("workspace_bytes", ctypes.c_int64)]
+
+
 class InstNormPlanQuery(ctypes.Structure):
     """lgs_instnorm_plan_query"""
     _fields_ = [(n, ctypes.c_int) for n in ("direction", "c", "dtype")] + [(n, ctypes.c_int64) for n in ("n_fine", "n_seg", "n_items")]
@@ -198,6 +206,7 @@ EXPORTS = [
     "lgs_conv_wgrad_supports_stride", "lgs_conv_dgrad_can_accumulate", "lgs_conv_dgrad_accumulate",
     "lgs_conv_pack_desc", "lgs_pack_weights_batch",
     "lgs_bn_workspace_bytes", "lgs_bn_forward", "lgs_bn_backward",
+    "lgs_bn_pair_workspace_bytes", "lgs_bn_pair_plan", "lgs_debug_norm_pair_plan", "lgs_bn_forward_pair", "lgs_bn_backward_pair",
     "lgs_block_workspace_bytes", "lgs_block_forward", "lgs_block_backward",
     "lgs_bn_stats", "lgs_bn_sync_combine", "lgs_bn_apply", "lgs_bn_backward_reduce", "lgs_bn_backward_apply",
     "lgs_clip_similarity", "lgs_clip_workspace_bytes",
@@ -281,6 +290,10 @@ def lib():
         "lgs_conv_dgrad_accumulate": [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, vp],
         "lgs_bn_forward": [vp, i64, ci, vp, vp, cf, cf, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, i64, vp],
         "lgs_bn_backward": [vp, vp, vp, i64, i64, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, vp, i64, vp],
+        "lgs_bn_pair_plan": [ci, i64, ci, ci, ctypes.POINTER(NormPairPlanInfo)],
+        "lgs_debug_norm_pair_plan": [ctypes.POINTER(NormPlanQuery), ctypes.POINTER(NormPairPlanInfo)],
+        "lgs_bn_forward_pair": [vp, ctypes.POINTER(BnParams), vp, vp, ctypes.POINTER(BnParams), vp, i64, ci, ci, vp, i64, vp, ci, vp, vp],
+        "lgs_bn_backward_pair": [vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, i64, i64, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, i64, vp],
         "lgs_bn_stats": [vp, i64, ci, vp, ci, vp, vp, ci, vp, vp],
         "lgs_bn_apply": [vp, i64, ci, vp, vp, vp, vp, ci, vp, ci, i64, vp],
         "lgs_bn_backward_reduce": [vp, vp, vp, i64, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, i64, i64, vp],
@@ -338,6 +351,8 @@ def lib():
     L.lgs_conv_workspace_bytes.argtypes = [vp, ci, ci, ci, ci]
     L.lgs_bn_workspace_bytes.restype = i64
     L.lgs_bn_workspace_bytes.argtypes = [i64, ci]
+    L.lgs_bn_pair_workspace_bytes.restype = i64
+    L.lgs_bn_pair_workspace_bytes.argtypes = [i64, ci]
     L.lgs_bn_sync_workspace_bytes.restype = i64
     L.lgs_bn_sync_workspace_bytes.argtypes = [i64, ci, ci]
     L.lgs_clip_workspace_bytes.restype = i64

@@ -94,6 +94,23 @@ def _bn_ws_bytes(L, n, c):
             _BN_WSB.clear()
         b = _BN_WSB[(n, c)] = L.lgs_bn_workspace_bytes(n, c)
     return b
+
+
+_BN_PAIR = {}
+
+
+def _bn_pair_plan(L, direction, n, c, dt):
+    """-> (path, workspace bytes) of lgs_bn_forward_pair (direction 0) / lgs_bn_backward_pair (1) for this call on the current device;
+    path 0 = the engine issues the two single norms and needs their intermediate (res / dres) from the caller"""
+    key = (direction, n, c, dt, engine.TUNING_EPOCH)
+    v = _BN_PAIR.get(key)
+    if v is None:
+        if len(_BN_PAIR) > 4096:
+            _BN_PAIR.clear()
+        info = engine.NormPairPlanInfo()
+        engine.check(L.lgs_bn_pair_plan(direction, n, c, dt, ctypes.byref(info)))
+        v = _BN_PAIR[key] = (int(info.path), int(info.workspace_bytes))
+    return v
 # input voxels per batch below which weight gradients are not moved to the side stream (LGS_WGRAD_INLINE_BELOW: tuning knob;
 # one 145 k-voxel scene per step: 11.2 -> 10.4 ms, the 1.2 M-voxel batch keeps the side stream: 29.9 vs 30.9 ms)
 _WGRAD_INLINE_BELOW = _tuning.host("WGRAD_INLINE_BELOW")
@@ -719,6 +736,59 @@ class HipBackend:
                                            _ptr(dres), _ptr(dgamma), _ptr(dbeta), dt, _ptr(ws), int(y_ld), _stream()))
         return dx, dres, dgamma, dbeta
 
+    # ---- the two norms that meet at a residual add, on shared passes: lgs_bn_forward_pair / lgs_bn_backward_pair
+    @staticmethod
+    def _bn_params(m, gamma, beta):
+        return engine.BnParams(_ptr(gamma), _ptr(beta), _ptr(m.running_mean), _ptr(m.running_var), _ptr(m.num_batches_tracked),
+                               float(m.eps), float(m.momentum))
+
+    def bn_forward_pair(self, xa, bn_a, gamma_a, beta_a, xb, bn_b, gamma_b, beta_b, relu, want_res=False):
+        """y = relu?(bn_a(xa) + bn_b(xb)) -> y, stats_a, stats_b, res.  bn_a / bn_b: the nn.BatchNorm1d modules (running statistics,
+        eps, momentum).  res = bn_b(xb) only when want_res, or when the engine runs the two single norms (then it is their
+        intermediate); otherwise None -- lgs_bn_apply on xb and stats_b gives it to a caller that wants it later."""
+        _require_dev(xa, "features")
+        L = engine.lib()
+        xa, xb = xa.contiguous(), xb.contiguous()
+        n, c = xa.shape
+        if n == 0:
+            raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (list(xa.shape),))
+        dt = _dtype_code(xa)
+        with _dev(xa.device):
+            path, wsb = _bn_pair_plan(L, 0, n, c, dt)
+            y = torch.empty_like(xa)
+            res = torch.empty_like(xa) if (want_res or path == 0) else None
+            st = torch.empty((2, 2 * c), dtype=torch.float32, device=xa.device)
+            pa, pb = self._bn_params(bn_a, gamma_a, beta_a), self._bn_params(bn_b, gamma_b, beta_b)
+            ws = _ws(wsb, xa.device)
+            engine.check(L.lgs_bn_forward_pair(_ptr(xa), ctypes.byref(pa), _ptr(st[0]), _ptr(xb), ctypes.byref(pb), _ptr(st[1]), n, c, int(relu),
+                                               _ptr(y), 0, _ptr(res), dt, _ptr(ws), _stream()))
+        _written_by_engine(bn_a.running_mean, bn_a.running_var, bn_a.num_batches_tracked, bn_b.running_mean, bn_b.running_var,
+                           bn_b.num_batches_tracked)
+        return y, st[0], st[1], res
+
+    def bn_backward_pair(self, xa, ya, gamma_a, beta_a, stats_a, relu, xb, gamma_b, stats_b, dy, want_residual=False, grads_out=None):
+        """both norms receive dy masked by norm a's ReLU -> dxa, dxb, dres (None unless asked for or needed by the engine),
+        (dgamma_a, dbeta_a, dgamma_b, dbeta_b); grads_out: four fp32 [c] buffers to write those into"""
+        L = engine.lib()
+        n, c = xa.shape
+        dt = _dtype_code(xa)
+        dy, dy_ld = self._strided_in(dy, c) if dy.dtype == xa.dtype else (dy.contiguous(), 0)
+        dy_ld = dy_ld or c
+        ya, ya_ld = self._strided_in(ya, c)
+        with _dev(xa.device):
+            path, wsb = _bn_pair_plan(L, 1, n, c, dt)
+            dx = torch.empty((2,) + tuple(xa.shape), dtype=xa.dtype, device=xa.device)
+            dres = torch.empty(xa.shape, dtype=xa.dtype, device=xa.device) if (want_residual or path == 0) else None
+            if grads_out is None:
+                g = torch.empty((4, c), dtype=torch.float32, device=xa.device)
+                grads_out = (g[0], g[1], g[2], g[3])
+            ws = _ws(wsb, xa.device)
+            engine.check(L.lgs_bn_backward_pair(_ptr(xa), _ptr(ya), _ptr(gamma_a), _ptr(beta_a), _ptr(stats_a), int(relu), _ptr(xb), _ptr(gamma_b),
+                                                _ptr(stats_b), _ptr(dy), int(dy_ld), n, c, _ptr(dx[0]), _ptr(dx[1]), _ptr(grads_out[0]),
+                                                _ptr(grads_out[1]), _ptr(grads_out[2]), _ptr(grads_out[3]), _ptr(dres), dt, _ptr(ws), int(ya_ld),
+                                                _stream()))
+        return dx[0], dx[1], dres, tuple(grads_out)
+
     # ---- a whole BasicBlock per call (csrc/lgs_block.hip): small batches, everything on the compute stream
     # host staging of lgs_block_fwd / lgs_block_bwd: one buffer per direction and THREAD (ctypes releases the GIL during the call,
     # so a second Python / autograd thread -- multi-device backward, two models driven from two threads -- must not be able to
@@ -742,7 +812,8 @@ class HipBackend:
             b = kmap3._wsb[key] = L.lgs_block_workspace_bytes(kmap3.h, kmap1.h if kmap1 is not None else None, cin, planes, dt)
         # conv scratch and BatchNorm scratch are never live at the same time inside the sequence (as in the call-by-call path,
         # where both are the stream's one grow-only buffer): one buffer, sized for the larger
-        return _ws(max(b, _bn_ws_bytes(L, n, planes)), device)
+        # (a block with a downsample branch runs two of its norms as a pair: lgs_bn_pair_workspace_bytes)
+        return _ws(max(b, _bn_pair_plan(L, 0, n, planes, dt)[1] if kmap1 is not None else _bn_ws_bytes(L, n, planes)), device)
 
     def block_forward(self, x, kmap3, kmap1, ws3, pcs, norms, affines, relu_final):
         """BasicBlock forward through lgs_block_forward -> (o1, st1, y1, o2, st2, y2, od, std).  The argument struct is packed
@@ -757,7 +828,9 @@ class HipBackend:
         ds = wd is not None
         pk = get_packed()
         with _dev(dev):
-            buf = torch.empty((6 if ds else 4, n, planes), dtype=x.dtype, device=dev)
+            # the branch norm's output is formed only where the engine runs the norms as single calls (lgs_bn_pair_plan: path 0)
+            want_res = ds and _bn_pair_plan(L, 0, n, planes, dt)[0] == 0
+            buf = torch.empty(((6 if want_res else 5) if ds else 4, n, planes), dtype=x.dtype, device=dev)
             st = torch.empty((3 if ds else 2, 2 * planes), dtype=torch.float32, device=dev)
             p1, pm1 = pk.lookup(pcs[0], kmap3, 0, False, w1, w1, cin, planes, dt)
             p2, pm2 = pk.lookup(pcs[1], kmap3, 0, False, w2, w2, planes, planes, dt)
@@ -781,7 +854,7 @@ class HipBackend:
                 args, 0, kmap3.h.value, kmap1.h.value if ds else 0, dt, int(relu_final), cin, planes, n, x.data_ptr(),
                 w1.data_ptr(), w2.data_ptr(), wd.data_ptr() if ds else 0,
                 _ptr(p1) or 0, _ptr(p2) or 0, _ptr(pd) or 0, int(pm1), int(pm2), int(pmd), *bn,
-                b0, b0 + row, b0 + 2 * row, (b0 + 4 * row) if ds else 0, (b0 + 5 * row) if ds else 0, b0 + 3 * row,
+                b0, b0 + row, b0 + 2 * row, (b0 + 4 * row) if ds else 0, (b0 + 5 * row) if want_res else 0, b0 + 3 * row,
                 s0, s0 + srow, (s0 + 2 * srow) if ds else 0, cws, cws)
             engine.check(L.lgs_block_forward(addr, _stream()))
         _written_by_engine(*touched)
@@ -812,9 +885,14 @@ class HipBackend:
             p1, pm1 = pk.lookup(pcs[0], kmap3, 1, False, w1, w1, cin, planes, dt)
             p2, pm2 = pk.lookup(pcs[1], kmap3, 1, False, w2, w2, planes, planes, dt)
             pd, pmd = pk.lookup(pcs[2], kmap1, 1, False, wd, wd, cin, planes, dt) if ds else (None, 0)
-            buf = torch.empty((5 if ds else 4, n, planes), dtype=x.dtype, device=dev)
+            # the masked gradient is formed only where something reads it: blocks without a branch (it is the residual's gradient),
+            # or norms that run as single calls (lgs_bn_pair_plan: path 0)
+            want_dres = (not ds) or _bn_pair_plan(L, 1, n, planes, dt)[0] == 0
+            buf = torch.empty((5 if want_dres else 4, n, planes) if ds else (4, n, planes), dtype=x.dtype, device=dev)
             b0 = buf.data_ptr()
             row = n * planes * x.element_size()
+            b_dres, b_dy1, b_dx1, b_dxd = (b0 + row, b0 + 2 * row, b0 + 3 * row, (b0 + 4 * row) if ds else 0) if want_dres else \
+                (0, b0 + row, b0 + 2 * row, b0 + 3 * row)
 
             slots = [True]
 
@@ -863,7 +941,7 @@ class HipBackend:
                 w1.data_ptr(), w2.data_ptr(), wd.data_ptr() if ds else 0,
                 _ptr(p1) or 0, _ptr(p2) or 0, _ptr(pd) or 0, int(pm1), int(pm2), int(pmd),
                 g1.data_ptr(), b1.data_ptr(), g2.data_ptr(), b2.data_ptr(), gd.data_ptr() if ds else 0, bd.data_ptr() if ds else 0,
-                b0, b0 + row, b0 + 2 * row, b0 + 3 * row, (b0 + 4 * row) if ds else 0, gind.data_ptr() if ds else 0,
+                b0, b_dres, b_dy1, b_dx1, b_dxd, gind.data_ptr() if ds else 0,
                 gw1.data_ptr(), gw2.data_ptr(), gwd.data_ptr() if ds else 0,
                 dg1.data_ptr(), db1.data_ptr(), dg2.data_ptr(), db2.data_ptr(), dgd.data_ptr() if ds else 0, dbd.data_ptr() if ds else 0,
                 cws, cws, s_raw, s_ws, s_fork, e1, e2, ed)

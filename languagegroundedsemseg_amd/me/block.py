@@ -18,7 +18,7 @@ from . import deferred as _d
 # way; at one scene per step (~150 k voxels) the training step is bound by exactly that host work.
 # The fast path issues the same engine calls, in the same order, with the same arguments, from ONE autograd node:
 #   forward   conv1 -> norm1+ReLU -> conv2 -> [downsample conv 1x1
-#             -> its norm] -> norm2 + residual (+ ReLU)
+#             -> its norm] -> norm2 + residual (+ ReLU)        (the two norms of a downsample block: one call on shared passes)
 #   backward  norm2 -> {wgrad2 on the side stream, dgrad2} -> norm1 -> {wgrad1, dgrad1} [-> downsample norm -> {wgrad, dgrad}]
 #             with the residual branch's gradient added in dgrad1's epilogue (lgs_conv_dgrad_accumulate: autograd's
 #             accumulation of the two branches, same rounding, without the elementwise pass)
@@ -180,11 +180,19 @@ class _BasicBlockFunction(torch.autograd.Function):
             pcd = blk.downsample[0]._cache_for(x)
             od, sd = kmap1.conv_forward(x, wd, None, False, bn_pivot=nd.running_mean, want_bn_stats=True, pack_cache=pcd) if want else \
                 (kmap1.conv_forward(x, wd, None, False, pack_cache=pcd), None)
-            res, std, invd = _bn_fwd(be, od, nd, gd, bd, None, False, sd, sync)
-        else:
-            res, invd = x, None
         relu = bool(blk.final_relu)
-        y2, st2, inv2 = _bn_fwd(be, o2, n2, g2, b2, res, relu, s2, sync)
+        # the branch norm and norm2 meet at the residual add: one engine call on shared passes, the branch output is not formed
+        # (what the one-call path does; bit-identical to the two calls).  SyncBN and conv-epilogue statistics keep the single calls
+        ctx.pair = ctx.has_ds and not sync[0] and s2 is None and sd is None and hasattr(be, "bn_forward_pair")
+        if ctx.pair:
+            y2, st2, std, _ = be.bn_forward_pair(o2, n2, g2, b2, od, nd, gd, bd, relu)
+            inv2 = invd = None
+        else:
+            if ctx.has_ds:
+                res, std, invd = _bn_fwd(be, od, nd, gd, bd, None, False, sd, sync)
+            else:
+                res, invd = x, None
+            y2, st2, inv2 = _bn_fwd(be, o2, n2, g2, b2, res, relu, s2, sync)
         ctx.kmap3, ctx.kmap1, ctx.relu, ctx.pc = kmap3, kmap1, relu, (pc1, pc2, pcd if ctx.has_ds else None)
         ctx.params = tuple(t if isinstance(t, nn.Parameter) else None for t in (w1, g1, b1, w2, g2, b2, wd, gd, bd))
         inv = ((inv1, inv2, invd) if ctx.has_ds else (inv1, inv2)) if sync[0] else ()
@@ -211,8 +219,21 @@ class _BasicBlockFunction(torch.autograd.Function):
         n_base = 18 if ctx.has_ds else 13
         inv1, inv2, invd = (tuple(sv[n_base:]) + (None,))[:3] if sync[0] else (None, None, None)
         # norm2 (+ residual) (+ ReLU): mask from the saved output when there is a ReLU (a residual was added)
-        dx2, dres, dg2, db2 = _bn_bwd(be, o2, y2 if ctx.relu else None, dy, g2, b2, pg2, pb2, st2, 1 if ctx.relu else 0, True,
-                                      need[8] or need[9], sync, inv2)
+        pair = ctx.has_ds and getattr(ctx, "pair", False)
+        if pair:
+            from .modules import grad_slot_view
+            wd, gd, bd, od, std = sv[13:18]
+            slots = [grad_slot_view(p_) if p_ is not None else None for p_ in (pg2, pb2, pgd, pbd)]
+            if any(v is None for v in slots):
+                slots = None
+            dx2, dxd, _, (dg2, db2, dgd, dbd) = be.bn_backward_pair(o2, y2 if ctx.relu else None, g2, b2, st2, 1 if ctx.relu else 0, od, gd, std, dy,
+                                                                    False, slots)
+            if slots is None:
+                dg2, db2 = ((dg2.to(g2.dtype), db2.to(g2.dtype)) if (need[8] or need[9]) else (None, None))
+                dgd, dbd = ((dgd.to(gd.dtype), dbd.to(gd.dtype)) if (need[11] or need[12]) else (None, None))
+        else:
+            dx2, dres, dg2, db2 = _bn_bwd(be, o2, y2 if ctx.relu else None, dy, g2, b2, pg2, pb2, st2, 1 if ctx.relu else 0, True,
+                                          need[8] or need[9], sync, inv2)
         gw2 = conv_weight_grad(kmap3, y1, dx2, False, pw2, w2.shape, w2.dtype) if need[7] else None
         dy1 = kmap3.conv_dgrad(dx2, w2, False, pack_cache=pc2)
         dx1, _, dg1, db1 = _bn_bwd(be, o1, None, dy1, g1, b1, pg1, pb1, st1, 2, False, need[5] or need[6], sync, inv1)
@@ -220,7 +241,8 @@ class _BasicBlockFunction(torch.autograd.Function):
         gin = None
         if ctx.has_ds:
             wd, gd, bd, od, std = sv[13:18]
-            dxd, _, dgd, dbd = _bn_bwd(be, od, None, dres, gd, bd, pgd, pbd, std, 0, False, need[11] or need[12], sync, invd)
+            if not pair:
+                dxd, _, dgd, dbd = _bn_bwd(be, od, None, dres, gd, bd, pgd, pbd, std, 0, False, need[11] or need[12], sync, invd)
             gwd = conv_weight_grad(ctx.kmap1, x, dxd, False, pwd, wd.shape, wd.dtype) if need[10] else None
             if need[0]:
                 gin = kmap3.conv_dgrad(dx1, w1, False, pack_cache=pc1,
