@@ -93,7 +93,8 @@ int lgs_manager_stride2(lgs_manager *mgr, int in_key, void *stream, int *out_key
  * (test / debug infrastructure: the map builders size coarse maps from counts taken at insert time and never synchronise;
  * a builder that finds its own count disagreeing raises the flag instead of writing past its arrays).  *flags: 0 = consistent,
  * bit 0 = coordinate out of the key range at insert, bit 1 = a coarse map's row count differs from the insert-time count,
- * bit 2 = the origin map's row count differs from the insert-time batch count.
+ * bit 2 = the origin map's row count differs from the insert-time batch count, bit 3 = a map's block directory (3^3 neighbour lookup)
+ * found its table full, which its sizing from the insert-time counts rules out.
  * Same call sites as lgs_manager_stride2.                                                                             */
 int lgs_manager_check(lgs_manager *mgr, int *flags);
 
@@ -161,6 +162,14 @@ int lgs_debug_kmap_relation(const lgs_kmap_relation_query *q, lgs_kmap_relation_
 /* Export the map as (k, in_row, out_row) triples for set-equality parity tests.
  * Pass NULL buffers to query *m only (synchronises). Buffers are device int32[*m]. */
 int lgs_kmap_export(lgs_kmap *km, int32_t *k, int32_t *in_row, int32_t *out_row, void *stream, int64_t *m);
+
+/* lgs_debug_kmap_tables: read-only copy of one view's gather tables exactly as the conv kernels read them (bwd = 0: the forward view,
+ * 1: the dgrad view), for tests that compare two ways of building the same map element by element (the tuning knobs MAP_WINDOW_SORT
+ * and MAP_BLOCK_DIR).  Always answers *n_pad (positions of the view), *slots (27 / 8 / 1) and *present (bit 0 nbr, bit 1 out_row,
+ * bit 2 mask64: which tables the view has).  Non-NULL device buffers nbr int32[slots * n_pad], out_row int32[n_pad] and
+ * mask64 uint32[n_pad / 64] receive the tables that are present, ordered on `stream`.  No counterpart in the reference.              */
+int lgs_debug_kmap_tables(lgs_kmap *km, int bwd, int32_t *nbr, int32_t *out_row, uint32_t *mask64, void *stream, int64_t *n_pad,
+                          int *slots, int *present);
 
 /* ---- pooling, global pooling and broadcast (ABI 14; csrc/lgs_pool.hip) ----------------------
  * replaces MinkowskiSumPooling / AvgPooling / MaxPooling / PoolingTranspose / AvgUnpooling (kernel_size == stride == 2^k),

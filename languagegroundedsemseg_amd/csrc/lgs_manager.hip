@@ -11,14 +11,17 @@
 // carries its rows in Morton order (`order`: sorted position -> row).  Consequences:
 //   * coarsening by 2 is a bit-mask on the key and preserves the sort, so a strided map and its
 //     2x2x2 kernel map come from one flag+scan over the sorted keys -- no hashing;
-//   * 3x3x3 maps come from 27 probes per voxel into an open-addressing hash (64-bit atomicCAS build);
+//   * 3x3x3 maps come from 27 probes per voxel into a directory of the occupied 4x4x4 blocks of the sorted keys (DirRef; the
+//     per-voxel open-addressing hash, HashRef, stays behind the knob MAP_BLOCK_DIR = 0);
 //   * conv tiles are runs of 64 Morton-consecutive voxels, so a wavefront ballot gives the per-tile
 //     bitmask of kernel offsets that have any neighbour at all (planar surfaces miss most
 //     out-of-plane offsets), which the conv kernels use to skip work.
 #include "lgs_common.h"
 
 #include <cstring>
+#include <initializer_list>
 #include <memory>
+#include <tuple>
 #include <rocprim/rocprim.hpp>
 
 namespace lgs {
@@ -195,34 +198,22 @@ __global__ __launch_bounds__(256) void k_count_levels(const uint64_t *__restrict
   if (threadIdx.x <= kPreLevels && l_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], l_cnt[threadIdx.x]);
 }
 
-// 3x3x3 stride-1 map: one thread per sorted position, 27 probes; nbr is offset-major [27][n_pad].
-// Round 6: the probes of one z-plane (nine offsets) are issued TOGETHER -- nine hash slots computed, nine key loads in flight, then
-// the (rare) continued probes, then nine value loads in flight -- instead of 27 dependent load chains one after the other: the
-// kernel is bound by the latency of its random accesses into the 20 - 30 MB table, not by their number (level 0 of the 8-scene
-// batch: 0.87 -> see profiles/r06_experiments.txt).  Same table, same probe sequence per offset: the map is bit-identical.
-__global__ void k_build_map3(const uint64_t *skeys, int64_t n, int64_t n_pad, int ts, const uint64_t *hkeys,
-                             const int32_t *hvals, uint64_t capm1, int32_t *nbr, uint32_t *pmask) {
-  int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // blockDim multiple of 64; p < n_pad by grid
-  bool live = p < n;
-  int b = 0, x = 0, y = 0, z = 0;
-  if (live) unpack_key(skeys[p], b, x, y, z);
-  uint32_t m = 0;
-#pragma unroll 1
-  for (int g = 0; g < 3; ++g) {
-    uint64_t key[9], slot[9], hk[9];
-    bool ok[9];
-    const int zz = z + (g - 1) * ts;
+// ---- neighbour lookup: "which row of the probed map has this key?" for NP keys at once, all NP loads of a step in flight together
+// (the probe kernels are bound by the latency of their random accesses, not by their number: profiles/r06_experiments.txt).
+// HashRef (MAP_BLOCK_DIR = 0): the open-addressing table with one slot per voxel.
+struct HashRef {
+  const uint64_t *hkeys;
+  const int32_t *hvals;
+  uint64_t capm1;
+  template <int NP>
+  __device__ inline void find(const uint64_t (&key)[NP], bool (&ok)[NP], int32_t (&r)[NP]) const {
+    uint64_t slot[NP], hk[NP];
 #pragma unroll
-    for (int j = 0; j < 9; ++j) {
-      const int xx = x + (j % 3 - 1) * ts, yy = y + (j / 3 - 1) * ts;
-      ok[j] = live && (((unsigned)xx | (unsigned)yy | (unsigned)zz) < (1u << kCoordBits));
-      key[j] = ok[j] ? pack_key(b, xx, yy, zz) : 0ull;
-      slot[j] = hash64(key[j]) & capm1;
-    }
+    for (int j = 0; j < NP; ++j) slot[j] = hash64(key[j]) & capm1;
 #pragma unroll
-    for (int j = 0; j < 9; ++j) hk[j] = ok[j] ? hkeys[slot[j]] : kEmpty;
+    for (int j = 0; j < NP; ++j) hk[j] = ok[j] ? hkeys[slot[j]] : kEmpty;
 #pragma unroll
-    for (int j = 0; j < 9; ++j) {
+    for (int j = 0; j < NP; ++j) {
       if (ok[j]) {
         uint64_t cur = hk[j], sl = slot[j];
         while (cur != key[j] && cur != kEmpty) {
@@ -233,9 +224,109 @@ __global__ void k_build_map3(const uint64_t *skeys, int64_t n, int64_t n_pad, in
         ok[j] = cur == key[j];
       }
     }
-    int32_t r[9];
 #pragma unroll
-    for (int j = 0; j < 9; ++j) r[j] = ok[j] ? hvals[slot[j]] : -1;
+    for (int j = 0; j < NP; ++j) r[j] = ok[j] ? hvals[slot[j]] : -1;
+  }
+};
+// DirRef (MAP_BLOCK_DIR = 1): the block directory.  The rows are Morton-sorted, so the keys of one 4 x 4 x 4 block of cells (cells
+// of the map's own grid: the key above bit 3 log2ts + 6) are ONE run of the sorted order, and inside the run the order is the order
+// of the 6-bit cell index.  One entry per occupied block therefore answers the lookup exactly: present = the cell's occupancy bit,
+// sorted position = first + popcount(occupancy below that bit), row = order[position].  The table has one entry per ~16 rows
+// instead of two slots per row (level 0 of the 8-scene batch: 8 MB instead of 48 MB), and the 64 Morton-consecutive rows of a
+// wave ask for a few dozen entries between them instead of 1 728 unrelated slots.
+struct DirEnt { uint64_t id, occ; int32_t first, pad[3]; };   // 32 bytes: a probe reads one aligned half cache line
+static_assert(sizeof(DirEnt) == 32, "DirEnt is read as two 16-byte halves");
+struct DirRef {
+  const DirEnt *ent;
+  uint64_t capm1;
+  int sh;                 // 3 log2ts of the probed map: the cell index is key bits [sh, sh + 6), the block id the bits above
+  const int32_t *order;   // the probed map's sorted position -> row (nullptr: identity)
+  template <int NP>
+  __device__ inline void find(const uint64_t (&key)[NP], bool (&ok)[NP], int32_t (&r)[NP]) const {
+    uint32_t slot[NP];     // the table has at most 2^31 entries (n < 2^31)
+    ulonglong2 e[NP];      // (id, occ)
+    int32_t first[NP];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) slot[j] = (uint32_t)(hash64(key[j] >> (sh + 6)) & capm1);
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      e[j] = ok[j] ? *reinterpret_cast<const ulonglong2 *>(ent + slot[j]) : make_ulonglong2(kEmpty, 0ull);
+      first[j] = ok[j] ? ent[slot[j]].first : 0;
+    }
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      if (ok[j]) {
+        const uint64_t id = key[j] >> (sh + 6);
+        uint32_t sl = slot[j];
+        while (e[j].x != id && e[j].x != kEmpty) {
+          sl = (sl + 1) & (uint32_t)capm1;
+          e[j] = *reinterpret_cast<const ulonglong2 *>(ent + sl);
+          first[j] = ent[sl].first;
+        }
+        const int cell = (int)((key[j] >> sh) & 63);
+        ok[j] = e[j].x == id && ((e[j].y >> cell) & 1ull);
+        first[j] += __popcll(e[j].y & ((1ull << cell) - 1ull));
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NP; ++j) r[j] = ok[j] ? (order ? order[first[j]] : first[j]) : -1;
+  }
+};
+__global__ void k_dir_fill(DirEnt *dir, int64_t cap) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= cap) return;
+  ulonglong2 *q = reinterpret_cast<ulonglong2 *>(dir + i);
+  q[0] = make_ulonglong2(kEmpty, 0ull);
+  q[1] = make_ulonglong2(0ull, 0ull);
+}
+// one pass: the thread at a block head (the pattern of k_heads) walks its run of at most 64 keys, ORs the occupancy and inserts
+// the entry with k_hash_insert's atomicCAS idiom (block ids are unique among the heads).  The table holds at least twice the
+// block count, so the probe sequence ends; a full table (impossible by that sizing) sets d_err bit 3 instead of spinning.
+__global__ void k_dir_build(const uint64_t *skeys, int64_t n, int sh, DirEnt *dir, uint64_t capm1, int *d_err) {
+  int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const uint64_t id = skeys[p] >> (sh + 6);
+  if (p > 0 && (skeys[p - 1] >> (sh + 6)) == id) return;
+  uint64_t occ = 0;
+  for (int64_t q = p; q < n && q < p + 64; ++q) {
+    const uint64_t k = skeys[q];
+    if ((k >> (sh + 6)) != id) break;
+    occ |= 1ull << ((k >> sh) & 63);
+  }
+  uint64_t s = hash64(id) & capm1;
+  for (uint64_t tries = 0; tries <= capm1; ++tries) {
+    unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&dir[s].id), (unsigned long long)kEmpty, (unsigned long long)id);
+    if (prev == kEmpty) { dir[s].occ = occ; dir[s].first = (int32_t)p; return; }
+    s = (s + 1) & capm1;
+  }
+  if (d_err) atomicOr(d_err, 8);
+}
+
+// 3x3x3 stride-1 map: one thread per sorted position, 27 probes; nbr is offset-major [27][n_pad].
+// Round 6: the probes of one z-plane (nine offsets) are issued TOGETHER -- nine slots computed, nine table loads in flight, then
+// the (rare) continued probes, then nine value loads in flight -- instead of 27 dependent load chains one after the other (level 0
+// of the 8-scene batch: 0.87 -> see profiles/r06_experiments.txt).  Same probe sequence per offset in either table: the map is
+// bit-identical.
+template <typename L>
+__global__ __launch_bounds__(256) void k_build_map3(const uint64_t *skeys, int64_t n, int64_t n_pad, int ts, L look, int32_t *nbr, uint32_t *pmask) {
+  int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // blockDim multiple of 64; p < n_pad by grid
+  bool live = p < n;
+  int b = 0, x = 0, y = 0, z = 0;
+  if (live) unpack_key(skeys[p], b, x, y, z);
+  uint32_t m = 0;
+#pragma unroll 1
+  for (int g = 0; g < 3; ++g) {
+    uint64_t key[9];
+    bool ok[9];
+    const int zz = z + (g - 1) * ts;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+      const int xx = x + (j % 3 - 1) * ts, yy = y + (j / 3 - 1) * ts;
+      ok[j] = live && (((unsigned)xx | (unsigned)yy | (unsigned)zz) < (1u << kCoordBits));
+      key[j] = ok[j] ? pack_key(b, xx, yy, zz) : 0ull;
+    }
+    int32_t r[9];
+    look.template find<9>(key, ok, r);
 #pragma unroll
     for (int j = 0; j < 9; ++j) {
       const int k = 9 * g + j;
@@ -288,6 +379,126 @@ inline unsigned mask_sort_bits(int64_t n_pad, int window) {
   while ((1ull << wb) - 1 < nw) ++wb;
   return 32u + wb > 64u ? 64u : 32u + wb;
 }
+// MAP_WINDOW_SORT: the same permutation without the global sort.  The window index is the high part of the radix key and p is
+// already ascending, so the result is an independent stable sort of every window by its 32-bit code -- and sorting the composite
+// (code, index in window), padding rows under the code 0xffffffff that no real code reaches (order 3 tops out at 0xdfffffff), by
+// ANY correct sort gives that stable order, because composites are unique.  One workgroup per window: 16 composites per thread,
+// a bitonic network whose stages are taken four at a time in registers (the 16 elements of a thread differ in four index bits
+// [B, B + 4), so the compare-exchanges at distances 2^(B+3) .. 2^B need no other thread); between such passes the window goes
+// through LDS once, and every thread writes back exactly the slots it read, so one workgroup barrier per pass suffices.  The
+// first four merge sizes and the last pass have B = 0: the codes come from global memory and the permutation goes to it straight
+// from registers.  29 passes for 16 384 positions.  Only workgroup barriers, no hand-off between workgroups.
+// One CU's vector ALU is the bound (a window is one workgroup), so the network is kept cheap per comparator: the 46-bit composite
+// sits in the mantissa of a double in [1, 2), where the order of the numbers is the order of the bit patterns, and a
+// compare-exchange is v_min_f64 + v_max_f64 (both return an operand unchanged); the direction of a merge is the same for all 16
+// elements of a thread once the merge is wider than a thread's span, so a descending thread complements the mantissas on the way
+// in and out instead of steering every comparator; B is a template parameter, so the LDS offsets are immediates.
+constexpr int kWsMinLog2 = 10, kWsMaxLog2 = 14;
+inline int window_sort_log2(int64_t window) {   // -> log2(window) where k_window_sort serves it, else -1 (the radix sort does)
+  for (int l = kWsMinLog2; l <= kWsMaxLog2; ++l)
+    if (window == (1ll << l)) return l;
+  return -1;
+}
+inline size_t window_sort_lds(int log2w) { return (((size_t)1 << log2w) + ((size_t)1 << (log2w - 4))) * sizeof(double); }
+static_assert((((size_t)1 << kWsMaxLog2) + ((size_t)1 << (kWsMaxLog2 - 4))) * 8 <= 160 * 1024, "k_window_sort: LDS budget of one CU");
+constexpr unsigned long long kWsOne = 0x3ff0000000000000ull, kWsMant = 0x000fffffffffffffull;
+// (the instructions by name: fmin / fmax would first quiet a possible signalling NaN of each operand, two more v_max_f64 per comparator)
+__device__ inline double ws_min(double x, double y) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y)); return r; }
+__device__ inline double ws_max(double x, double y) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y)); return r; }
+__device__ inline void ws_cmpx(double &lo, double &hi) {
+  double a;
+  asm("v_min_f64 %0, %1, %2\n\tv_max_f64 %1, %1, %2" : "=&v"(a), "+v"(hi) : "v"(lo));
+  lo = a;
+}
+// LDS slot of index i: i + i / 16 (one pad slot per 16: the B = 0 passes walk 16-element rows).  For a thread's elements
+// base | r << B the two terms split without a carry, so the slot is slot(base) + a compile-time offset
+template <int B>
+__device__ inline int ws_base(int t) { return ((t >> B) << (B + 4)) | (t & ((1 << B) - 1)); }
+template <int B>
+__device__ inline void ws_store(double *lds, const double (&e)[16], int t) {
+  const int base = ws_base<B>(t);
+  double *q = lds + base + (base >> 4);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) q[(r << B) + ((r << B) >> 4)] = e[r];
+}
+// one pass: load the 16 elements at index bits [B, B + 4), the stages at distances 2^hi .. 2^B of the merge to runs of 2^m (m >= B + 4:
+// ascending where the thread's base has bit m clear), store unless it is the last pass of the sort
+template <int B>
+__device__ inline void ws_pass(double *lds, double (&e)[16], int t, int hi, int m, bool store) {
+  const int base = ws_base<B>(t);
+  const double *q = lds + base + (base >> 4);
+  const unsigned long long flip = ((base >> m) & 1) ? kWsMant : 0ull;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) e[r] = __longlong_as_double((long long)((unsigned long long)__double_as_longlong(q[(r << B) + ((r << B) >> 4)]) ^ flip));
+#pragma unroll
+  for (int s = 3; s >= 0; --s) {
+    if (B + s > hi) continue;
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      if (!(r & (1 << s))) ws_cmpx(e[r], e[r | (1 << s)]);
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) e[r] = __longlong_as_double((long long)((unsigned long long)__double_as_longlong(e[r]) ^ flip));
+  if (store) ws_store<B>(lds, e, t);
+}
+__global__ __launch_bounds__(1024) void k_window_sort(const uint32_t *__restrict__ pmask, int64_t n, int64_t n_pad, int log2w, int order,
+                                                      int32_t *__restrict__ perm) {
+  extern __shared__ double ws_lds[];     // [window + window / 16]
+  const int t = threadIdx.x;             // blockDim = window / 16
+  const int64_t w0 = (int64_t)blockIdx.x << log2w;
+  double e[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int64_t p = w0 + 16 * t + r;
+    const uint32_t code = p < n ? mask_sort_code(pmask[p], order) : 0xffffffffu;
+    e[r] = __longlong_as_double((long long)(kWsOne | ((unsigned long long)code << 14) | (unsigned)(16 * t + r)));
+  }
+  // merges to runs of 2, 4, 8, 16 inside the thread: the direction bit m is a bit of r (or, for m = 4, of t)
+#pragma unroll
+  for (int m = 1; m <= 4; ++m) {
+#pragma unroll
+    for (int s = m - 1; s >= 0; --s) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (r & (1 << s)) continue;
+        const bool up = (((16 * t) | r) & (1 << m)) == 0;
+        const double a = ws_min(e[r], e[r | (1 << s)]), b = ws_max(e[r], e[r | (1 << s)]);
+        e[r] = up ? a : b; e[r | (1 << s)] = up ? b : a;
+      }
+    }
+  }
+  ws_store<0>(ws_lds, e, t);
+  __syncthreads();
+  for (int m = 5; m <= log2w; ++m) {
+    for (int hi = m - 1; hi >= 0;) {
+      const int b = hi >= 3 ? hi - 3 : 0;
+      const bool store = !(m == log2w && b == 0);
+      switch (b) {
+        case 0: ws_pass<0>(ws_lds, e, t, hi, m, store); break;
+        case 1: ws_pass<1>(ws_lds, e, t, hi, m, store); break;
+        case 2: ws_pass<2>(ws_lds, e, t, hi, m, store); break;
+        case 3: ws_pass<3>(ws_lds, e, t, hi, m, store); break;
+        case 4: ws_pass<4>(ws_lds, e, t, hi, m, store); break;
+        case 5: ws_pass<5>(ws_lds, e, t, hi, m, store); break;
+        case 6: ws_pass<6>(ws_lds, e, t, hi, m, store); break;
+        case 7: ws_pass<7>(ws_lds, e, t, hi, m, store); break;
+        case 8: ws_pass<8>(ws_lds, e, t, hi, m, store); break;
+        case 9: ws_pass<9>(ws_lds, e, t, hi, m, store); break;
+        default: ws_pass<10>(ws_lds, e, t, hi, m, store); break;
+      }
+      __syncthreads();
+      hi = b - 1;
+    }
+  }
+  // the last pass had B = 0: the thread holds sorted slots 16 t .. 16 t + 15 of its window (n_pad is a multiple of 256: all of them or none)
+  if (w0 + 16 * t >= n_pad) return;
+  int4 *dst = reinterpret_cast<int4 *>(perm + w0 + 16 * t);
+  int32_t v[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) v[r] = (int32_t)(w0 + (int64_t)(__double_as_longlong(e[r]) & 0x3fff));
+#pragma unroll
+  for (int r = 0; r < 16; r += 4) dst[r >> 2] = make_int4(v[r], v[r + 1], v[r + 2], v[r + 3]);
+}
 __global__ void k_permute_map3(const int32_t *nbr_tmp, const uint32_t *pmask, const int32_t *perm, const int32_t *order,
                                int64_t n, int64_t n_pad, int32_t *nbr, int32_t *out_row, uint32_t *mask64) {
   int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // grid covers n_pad exactly
@@ -307,8 +518,8 @@ __global__ void k_permute_map3(const int32_t *nbr_tmp, const uint32_t *pmask, co
 // fine coordinate (in units of ts) and +-1 for an odd one: at most 2^3 of the 27 offsets, fixed by the row's parity class.  Only
 // those are probed, all (<= 8) in flight together as in k_build_map3; the other slots are -1.  Rows of one parity class share the
 // candidate set, so the window mask sort that follows groups them and a 64-row group's mask64 carries at most 8 bits.
-__global__ void k_build_map3_fine(const uint64_t *fkeys, int64_t n, int64_t n_pad, int log2ts, const uint64_t *hkeys,
-                                  const int32_t *hvals, uint64_t capm1, int32_t *nbr, uint32_t *pmask) {
+template <typename L>
+__global__ __launch_bounds__(256) void k_build_map3_fine(const uint64_t *fkeys, int64_t n, int64_t n_pad, int log2ts, L look, int32_t *nbr, uint32_t *pmask) {
   int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // blockDim multiple of 64; p < n_pad by grid
   const bool live = p < n;
   int b = 0, x = 0, y = 0, z = 0;
@@ -316,7 +527,7 @@ __global__ void k_build_map3_fine(const uint64_t *fkeys, int64_t n, int64_t n_pa
   const int ts = 1 << log2ts;
   // the bias 2^17 is a multiple of 2 ts, so the parity of the biased coordinate is the parity of the coordinate
   const int ox = (x >> log2ts) & 1, oy = (y >> log2ts) & 1, oz = (z >> log2ts) & 1;
-  uint64_t key[8], slot[8], hk[8];
+  uint64_t key[8];
   int kk[8];
   bool ok[8];
 #pragma unroll
@@ -328,29 +539,13 @@ __global__ void k_build_map3_fine(const uint64_t *fkeys, int64_t n, int64_t n_pa
     ok[j] = live && (ox || !jx) && (oy || !jy) && (oz || !jz) && (((unsigned)xx | (unsigned)yy | (unsigned)zz) < (1u << kCoordBits));
     kk[j] = (dx + 1) + 3 * (dy + 1) + 9 * (dz + 1);
     key[j] = ok[j] ? pack_key(b, xx, yy, zz) : 0ull;
-    slot[j] = hash64(key[j]) & capm1;
   }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) hk[j] = ok[j] ? hkeys[slot[j]] : kEmpty;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    if (ok[j]) {
-      uint64_t cur = hk[j], sl = slot[j];
-      while (cur != key[j] && cur != kEmpty) {
-        sl = (sl + 1) & capm1;
-        cur = hkeys[sl];
-      }
-      slot[j] = sl;
-      ok[j] = cur == key[j];
-    }
-  }
+  int32_t r[8];
+  look.template find<8>(key, ok, r);
   uint32_t m = 0;
 #pragma unroll
   for (int j = 0; j < 8; ++j)
     if (ok[j]) m |= 1u << kk[j];
-  int32_t r[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = ok[j] ? hvals[slot[j]] : -1;
   for (int k = 0; k < 27; ++k) {
     int32_t v = -1;
 #pragma unroll
@@ -440,6 +635,17 @@ __global__ void k_group_offsets(const int32_t *cnt, int32_t *goff /*[9] padded s
 __global__ void k_fill_i32(int32_t *p, int64_t n, int32_t v) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
+}
+// several small fills as ONE launch: segment j gets n[j] copies of v[j]
+constexpr int kFillSegs = 4;
+struct FillSegs { int32_t *p[kFillSegs]; int64_t n[kFillSegs]; int32_t v[kFillSegs]; };
+__global__ void k_fill_segs(FillSegs f) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < kFillSegs; ++j) {
+    if (i < f.n[j]) { f.p[j][i] = f.v[j]; return; }
+    i -= f.n[j];
+  }
 }
 __global__ void k_build_map2_fine(const uint32_t *kk_sorted, const int32_t *pp_sorted, int64_t n, const int32_t *goff,
                                   const int32_t *gsrc, const int32_t *fine_cidx, const int32_t *forder,
@@ -552,6 +758,8 @@ struct CoordMap {
   uint64_t *hkeys = nullptr;  // hash (lazy)
   int32_t *hvals = nullptr;
   int64_t hcap = 0;
+  DirEnt *dir = nullptr;      // block directory (lazy)
+  int64_t dcap = 0;
   int fine_key = -1, coarse_key = -1;
   bool origin = false;           // one row (b, 0, 0, 0) per batch index (lgs_manager_origin); tensor stride 0
   int32_t *cstart = nullptr;     // [n+1] first fine sorted position of each row (maps made by stride2)
@@ -766,6 +974,42 @@ int ensure_hash(lgs_manager *m, CoordMap &cm, hipStream_t s) {
   return 0;
 }
 
+// the block directory of a map (MAP_BLOCK_DIR), built where the per-voxel hash would be.  A block of the map at tensor stride 2^t
+// is a cell of the map two levels coarser, whose row count lgs_manager_insert already took (precount): the table is sized from
+// it without a host synchronisation, and from n (one block per row at the worst) where that count is not known.
+int ensure_dir(lgs_manager *m, CoordMap &cm, hipStream_t s) {
+  if (cm.dir) return 0;
+  int64_t blocks = cm.n;
+  const int lv = cm.log2ts + 2;
+  if (lv <= kPreLevels && m->precount[lv - 1] >= 0 && m->precount[lv - 1] < blocks) blocks = m->precount[lv - 1];
+  int64_t cap = 1024;
+  while (cap < 2 * blocks) cap <<= 1;
+  cm.dcap = cap;
+  if (dalloc(m, &cm.dir, cap, s)) return 1;
+  LGS_KLAUNCH(k_dir_fill, nblk(cap), 256, 0, s, cm.dir, cap);
+  if (cm.n > 0) LGS_KLAUNCH(k_dir_build, nblk(cm.n), 256, 0, s, cm.skeys, cm.n, 3 * cm.log2ts, cm.dir, (uint64_t)(cap - 1), m->d_err);
+  LGS_HIP(hipGetLastError());
+  return 0;
+}
+inline bool use_block_dir() { return tune(T_MAP_BLOCK_DIR) != 0; }
+// the table the probe kernels look a map's keys up in: only the one the knob names is built
+int ensure_lookup(lgs_manager *m, CoordMap &cm, hipStream_t s) { return use_block_dir() ? ensure_dir(m, cm, s) : ensure_hash(m, cm, s); }
+inline HashRef hash_ref(const CoordMap &cm) { return HashRef{cm.hkeys, cm.hvals, (uint64_t)(cm.hcap - 1)}; }
+inline DirRef dir_ref(const CoordMap &cm) { return DirRef{cm.dir, (uint64_t)(cm.dcap - 1), 3 * cm.log2ts, cm.order}; }
+
+// several small fills as one launch (k_fill_segs)
+int fill_segs(hipStream_t s, std::initializer_list<std::tuple<void *, int64_t, int32_t>> segs) {
+  FillSegs f = {};
+  int64_t total = 0;
+  int j = 0;
+  for (const auto &g : segs) {
+    f.p[j] = reinterpret_cast<int32_t *>(std::get<0>(g)); f.n[j] = std::get<1>(g); f.v[j] = std::get<2>(g);
+    total += f.n[j++];
+  }
+  LGS_KLAUNCH(k_fill_segs, nblk(total), 256, 0, s, f);
+  return 0;
+}
+
 int scan_incl(lgs_manager *m, const int32_t *in, int32_t *out, int64_t n, hipStream_t s) {
   size_t tb = 0;
   LGS_HIP(rocprim::inclusive_scan(nullptr, tb, in, out, (size_t)n, rocprim::plus<int32_t>(), s));
@@ -794,33 +1038,47 @@ int batch_heads(lgs_manager *m, const uint64_t *skeys, int64_t n, int32_t *head,
 }
 
 // the window mask sort of a 27-slot table built in sorted-position order (nbr_tmp, pmask) and its permutation into the view's arrays:
-// position q of the view is sorted position perm[q] and writes row order[perm[q]] (order == nullptr: the position itself)
-int sort_map3(lgs_manager *m, int64_t n, int64_t n_pad, const int32_t *nbr_tmp, const uint32_t *pmask, const int32_t *order, uint64_t *keys,
-              uint64_t *skeys2, int32_t *vals, int32_t *perm, int32_t *nbr, int32_t *orow, uint32_t *mask, hipStream_t s) {
-  const int window = (int)tune(T_MASK_WINDOW);   // tuning knob (default kMaskWindow)
-  LGS_KLAUNCH(k_mask_sort_keys, (unsigned)(n_pad / 256), 256, 0, s, pmask, n, n_pad, window, (int)tune(T_MASK_ORDER), keys, vals);
-  if (sort_pairs(m, keys, skeys2, vals, perm, n_pad, 0, mask_sort_bits(n_pad, window), s)) return 1;
-  LGS_KLAUNCH(k_permute_map3, (unsigned)(n_pad / 256), 256, 0, s, nbr_tmp, pmask, perm, order, n, n_pad, nbr, orow, mask);
-  LGS_HIP(hipGetLastError());
-  return 0;
+// position q of the view is sorted position perm[q] and writes row order[perm[q]] (order == nullptr: the position itself).
+// MAP_WINDOW_SORT: one k_window_sort launch where the window is a power of two that fits the LDS (window_sort_log2); else the radix
+// sort of (window, code) keys with its four n_pad-sized temporaries.
+int window_perm(lgs_manager *m, int64_t n, int64_t n_pad, const uint32_t *pmask, int32_t *perm, hipStream_t s) {
+  const int64_t window = tune(T_MASK_WINDOW);   // tuning knob (default kMaskWindow)
+  const int order = (int)tune(T_MASK_ORDER);
+  const int log2w = tune(T_MAP_WINDOW_SORT) != 0 ? window_sort_log2(window) : -1;
+  if (log2w >= 0) {
+    static bool attr_set = false;
+    if (!attr_set) {
+      LGS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_sort), hipFuncAttributeMaxDynamicSharedMemorySize, (int)window_sort_lds(kWsMaxLog2)));
+      attr_set = true;
+    }
+    // a map of one window sorts the smallest power of two that holds its positions (what lies beyond is padding, which sorts last)
+    int l = log2w;
+    while (l > kWsMinLog2 && n_pad <= (1ll << (l - 1))) --l;
+    LGS_KLAUNCH(k_window_sort, (unsigned)((n_pad + (1ll << l) - 1) >> l), 1u << (l - 4), window_sort_lds(l), s, pmask, n, n_pad, l, order, perm);
+    return 0;
+  }
+  uint64_t *keys, *skeys2; int32_t *vals;
+  if (dalloc(m, &keys, n_pad, s) || dalloc(m, &skeys2, n_pad, s) || dalloc(m, &vals, n_pad, s)) return 1;
+  LGS_KLAUNCH(k_mask_sort_keys, (unsigned)(n_pad / 256), 256, 0, s, pmask, n, n_pad, (int)window, order, keys, vals);
+  if (sort_pairs(m, keys, skeys2, vals, perm, n_pad, 0, mask_sort_bits(n_pad, (int)window), s)) return 1;
+  return dfree_now(m, keys, s) || dfree_now(m, skeys2, s) || dfree_now(m, vals, s);
 }
 
-// a 27-slot view over the rows of map `st` (the stationary side): table built by `build` into (nbr_tmp, pmask), then sort_map3
+// a 27-slot view over the rows of map `st` (the stationary side): table built by `build` into (nbr_tmp, pmask), then the window sort
 template <typename Build>
 int make_view27(lgs_manager *m, const CoordMap &st, int64_t n_in, hipStream_t s, View &v, Build &&build) {
   v = View();
   v.n_pad = st.n_pad; v.n_out = st.n; v.n_in = n_in; v.KS = 27; v.K = 27;
   if (st.n == 0) return 0;
-  int32_t *nbr, *orow, *nbr_tmp, *vals, *perm; uint32_t *mask, *pmask; uint64_t *keys, *skeys2;
+  int32_t *nbr, *orow, *nbr_tmp, *perm; uint32_t *mask, *pmask;
   if (dalloc(m, &nbr, 27 * st.n_pad, s) || dalloc(m, &mask, st.n_pad / kGroup, s) || dalloc(m, &orow, st.n_pad, s) ||
-      dalloc(m, &nbr_tmp, 27 * st.n_pad, s) || dalloc(m, &pmask, st.n_pad, s) || dalloc(m, &keys, st.n_pad, s) ||
-      dalloc(m, &skeys2, st.n_pad, s) || dalloc(m, &vals, st.n_pad, s) || dalloc(m, &perm, st.n_pad, s))
+      dalloc(m, &nbr_tmp, 27 * st.n_pad, s) || dalloc(m, &pmask, st.n_pad, s) || dalloc(m, &perm, st.n_pad, s))
     return 1;
   if (build(nbr_tmp, pmask)) return 1;
-  if (sort_map3(m, st.n, st.n_pad, nbr_tmp, pmask, st.order, keys, skeys2, vals, perm, nbr, orow, mask, s)) return 1;
-  if (dfree_now(m, nbr_tmp, s) || dfree_now(m, pmask, s) || dfree_now(m, keys, s) || dfree_now(m, skeys2, s) ||
-      dfree_now(m, vals, s) || dfree_now(m, perm, s))
-    return 1;
+  if (window_perm(m, st.n, st.n_pad, pmask, perm, s)) return 1;
+  LGS_KLAUNCH(k_permute_map3, (unsigned)(st.n_pad / 256), 256, 0, s, nbr_tmp, pmask, perm, st.order, st.n, st.n_pad, nbr, orow, mask);
+  LGS_HIP(hipGetLastError());
+  if (dfree_now(m, nbr_tmp, s) || dfree_now(m, pmask, s) || dfree_now(m, perm, s)) return 1;
   v.nbr = nbr; v.mask64 = mask; v.out_row = orow;
   return 0;
 }
@@ -834,18 +1092,21 @@ void build_identity(const CoordMap &ci, lgs_kmap *km) {
 }
 
 // a 27-slot view over the rows of `st` whose slot k holds the row of `probed` at c + off_k * scale: the 27 probes of k_build_map3
-// from st's sorted keys into probed's hash (st == probed: the stride-1 maps; st = the coarse map: the coarse-stationary strided view)
+// from st's sorted keys into probed's lookup table (st == probed: the stride-1 maps; st = the coarse map: the coarse-stationary strided
+// view).  A probed coordinate is always on the probed map's grid, so dilation needs no special case in either table.
 int probe_view27(lgs_manager *m, const CoordMap &st, const CoordMap &probed, int scale, hipStream_t s, View &v) {
   return make_view27(m, st, probed.n, s, v, [&](int32_t *nbr_tmp, uint32_t *pmask) {
-    LGS_KLAUNCH(k_build_map3, (unsigned)(st.n_pad / 256), 256, 0, s, st.skeys, st.n, st.n_pad, scale, probed.hkeys, probed.hvals,
-                (uint64_t)(probed.hcap - 1), nbr_tmp, pmask);
+    if (use_block_dir())
+      LGS_KLAUNCH(k_build_map3<DirRef>, (unsigned)(st.n_pad / 256), 256, 0, s, st.skeys, st.n, st.n_pad, scale, dir_ref(probed), nbr_tmp, pmask);
+    else
+      LGS_KLAUNCH(k_build_map3<HashRef>, (unsigned)(st.n_pad / 256), 256, 0, s, st.skeys, st.n, st.n_pad, scale, hash_ref(probed), nbr_tmp, pmask);
     return 0;
   });
 }
 
 // 3^3 stride 1, plain (dilation 1) or dilated: offsets scaled by dilation * ts; bwd = the same table read mirrored
 int build_conv3(lgs_manager *m, CoordMap &ci, int dilation, hipStream_t s, lgs_kmap *km) {
-  if (ci.n > 0 && ensure_hash(m, ci, s)) return 1;
+  if (ci.n > 0 && ensure_lookup(m, ci, s)) return 1;
   View v;
   if (probe_view27(m, ci, ci, dilation * ci.ts, s, v)) return 1;
   km->fwd = v;
@@ -872,13 +1133,10 @@ int build_conv2_s2(lgs_manager *m, const CoordMap &ci, const CoordMap &co, hipSt
         dalloc(m, &cnt, 8, s) || dalloc(m, &goff, 9, s) || dalloc(m, &gsrc, 9, s) || dalloc(m, &g_nbr, gp, s) ||
         dalloc(m, &g_out, gp, s) || dalloc(m, &tile_k, gp / kGroup, s))
       return 1;
-    LGS_HIP(hipMemsetAsync(cnt, 0, 8 * sizeof(int32_t), s));
+    if (fill_segs(s, {{cnt, 8, 0}, {g_nbr, gp, -1}, {g_out, gp, -1}, {tile_k, gp / kGroup, -1}})) return 1;
     LGS_KLAUNCH(k_child_keys, nblk(n), 256, 0, s, ci.skeys, n, shift, kk, pp, cnt);
     if (sort_pairs(m, kk, kks, pp, pps, n, 0, 3, s)) return 1;
     LGS_KLAUNCH(k_group_offsets, 1, 64, 0, s, cnt, goff, gsrc);
-    LGS_KLAUNCH(k_fill_i32, nblk(gp), 256, 0, s, g_nbr, gp, -1);
-    LGS_KLAUNCH(k_fill_i32, nblk(gp), 256, 0, s, g_out, gp, -1);
-    LGS_KLAUNCH(k_fill_i32, nblk(gp / kGroup), 256, 0, s, tile_k, gp / kGroup, -1);
     LGS_KLAUNCH(k_build_map2_fine, nblk(n), 256, 0, s, kks, pps, n, goff, gsrc, co.fine_cidx, ci.order, g_nbr,
                        g_out, tile_k);
     LGS_HIP(hipGetLastError());
@@ -894,12 +1152,14 @@ int build_conv2_s2(lgs_manager *m, const CoordMap &ci, const CoordMap &co, hipSt
 // 3^3 stride 2.  Both views carry offset k in slot k (no mirroring): the fine-stationary one lists, per fine row, the coarse row of
 // the pair (k, fine, coarse) under the k of the forward direction
 int build_conv3_s2(lgs_manager *m, CoordMap &ci, CoordMap &co, hipStream_t s, lgs_kmap *km) {
-  if (ci.n > 0 && (ensure_hash(m, ci, s) || ensure_hash(m, co, s))) return 1;
-  // coarse-stationary: from the coarse rows' keys into the FINE map's hash, offsets scaled by ts_in
+  if (ci.n > 0 && (ensure_lookup(m, ci, s) || ensure_lookup(m, co, s))) return 1;
+  // coarse-stationary: from the coarse rows' keys into the FINE map's table, offsets scaled by ts_in
   if (probe_view27(m, co, ci, ci.ts, s, km->fwd)) return 1;
   return make_view27(m, ci, co.n, s, km->bwd, [&](int32_t *nbr_tmp, uint32_t *pmask) {
-    LGS_KLAUNCH(k_build_map3_fine, (unsigned)(ci.n_pad / 256), 256, 0, s, ci.skeys, ci.n, ci.n_pad, ci.log2ts, co.hkeys, co.hvals,
-                (uint64_t)(co.hcap - 1), nbr_tmp, pmask);
+    if (use_block_dir())
+      LGS_KLAUNCH(k_build_map3_fine<DirRef>, (unsigned)(ci.n_pad / 256), 256, 0, s, ci.skeys, ci.n, ci.n_pad, ci.log2ts, dir_ref(co), nbr_tmp, pmask);
+    else
+      LGS_KLAUNCH(k_build_map3_fine<HashRef>, (unsigned)(ci.n_pad / 256), 256, 0, s, ci.skeys, ci.n, ci.n_pad, ci.log2ts, hash_ref(co), nbr_tmp, pmask);
     return 0;
   });
 }
@@ -1038,23 +1298,18 @@ int lgs_manager_insert(lgs_manager *m, const int32_t *coords, int64_t n, int64_t
     return 0;
   }
   if (!m->d_err) { if (dalloc(m, &m->d_err, 1, s)) return 1; }
-  LGS_HIP(hipMemsetAsync(m->d_err, 0, sizeof(int), s));
-  uint64_t *keys, *skeys; int32_t *vals, *svals, *head, *runid, *is_first, *urow;
-  if (dalloc(m, &keys, n, s) || dalloc(m, &skeys, n, s) || dalloc(m, &vals, n, s) || dalloc(m, &svals, n, s) ||
+  uint64_t *keys, *skeys; int32_t *vals, *svals, *head, *runid, *is_first, *urow, *lvl_counts;
+  if (dalloc(m, &lvl_counts, kPreLevels + 1, s) || dalloc(m, &keys, n, s) || dalloc(m, &skeys, n, s) || dalloc(m, &vals, n, s) || dalloc(m, &svals, n, s) ||
       dalloc(m, &head, n, s) || dalloc(m, &runid, n, s) || dalloc(m, &is_first, n, s) || dalloc(m, &urow, n + 1, s))
     return 1;
+  // d_err, the first slot of the exclusive scan and the level counters: one launch
+  if (fill_segs(s, {{m->d_err, 1, 0}, {urow, 1, 0}, {lvl_counts, kPreLevels + 1, 0}})) return 1;
   LGS_KLAUNCH(k_pack_keys, nblk(n), 256, 0, s, coords, n, keys, vals, m->d_err);
   if (sort_pairs(m, keys, skeys, vals, svals, n, 0, 64, s)) return 1;
   LGS_KLAUNCH(k_heads, nblk(n), 256, 0, s, skeys, n, ~0ull, head);
   LGS_KLAUNCH(k_mark_first, nblk(n), 256, 0, s, svals, head, n, is_first);
   if (scan_incl(m, head, runid, n, s)) return 1;
-  {  // exclusive scan of is_first = inclusive shifted: urow[0]=0, urow[i+1] = incl[i]
-    LGS_HIP(hipMemsetAsync(urow, 0, sizeof(int32_t), s));
-    if (scan_incl(m, is_first, urow + 1, n, s)) return 1;
-  }
-  int32_t *lvl_counts;
-  if (dalloc(m, &lvl_counts, kPreLevels + 1, s)) return 1;
-  LGS_HIP(hipMemsetAsync(lvl_counts, 0, sizeof(int32_t) * (kPreLevels + 1), s));
+  if (scan_incl(m, is_first, urow + 1, n, s)) return 1;   // exclusive scan of is_first = inclusive shifted: urow[0] = 0, urow[i+1] = incl[i]
   LGS_KLAUNCH(k_count_levels, (unsigned)((n + 256 * kCountPerThread - 1) / (256 * kCountPerThread)), 256, 0, s, skeys, n, lvl_counts);
   int32_t h_nu = 0; int h_err = 0; int32_t h_lvl[kPreLevels + 1];
   LGS_HIP(hipMemcpyAsync(&h_nu, urow + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -1193,6 +1448,24 @@ int lgs_debug_kmap_relation(const lgs_kmap_relation_query *q, lgs_kmap_relation_
   out->pairs_only[0] = t.wgrad_pairs_only(false); out->pairs_only[1] = t.wgrad_pairs_only(true);
   out->served_by_old_entry = t.old_entry;
   return 0;
+}
+
+// read-only: the tables of one view as they stand (exact-comparison tests of two build paths)
+int lgs_debug_kmap_tables(lgs_kmap *km, int bwd, int32_t *nbr, int32_t *out_row, uint32_t *mask64, void *stream, int64_t *n_pad, int *slots,
+                          int *present) {
+  LGS_REQUIRE(km && n_pad && slots && present, "lgs_debug_kmap_tables: null argument");
+  lgs_manager *m = km->mgr;
+  const View &v = bwd ? km->bwd : km->fwd;
+  *n_pad = v.n_pad; *slots = v.KS;
+  *present = (v.nbr ? 1 : 0) | (v.out_row ? 2 : 0) | (v.mask64 ? 4 : 0);
+  if (!nbr && !out_row && !mask64) return 0;
+  hipStream_t caller = (hipStream_t)stream, s = m->ms;
+  DeviceGuard guard(m->device);
+  if (begin_from_caller(m, caller)) return 1;   // the output buffers were allocated on the caller's stream
+  if (nbr && v.nbr && v.n_pad > 0) LGS_HIP(hipMemcpyAsync(nbr, v.nbr, sizeof(int32_t) * (size_t)(v.KS * v.n_pad), hipMemcpyDeviceToDevice, s));
+  if (out_row && v.out_row && v.n_pad > 0) LGS_HIP(hipMemcpyAsync(out_row, v.out_row, sizeof(int32_t) * (size_t)v.n_pad, hipMemcpyDeviceToDevice, s));
+  if (mask64 && v.mask64 && v.n_pad > 0) LGS_HIP(hipMemcpyAsync(mask64, v.mask64, sizeof(uint32_t) * (size_t)(v.n_pad / kGroup), hipMemcpyDeviceToDevice, s));
+  return publish(m, caller, true);
 }
 
 int lgs_manager_origin(lgs_manager *m, void *stream, int *out_key, int64_t *n_out) {

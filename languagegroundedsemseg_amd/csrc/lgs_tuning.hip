@@ -87,6 +87,13 @@ const Knob kKnobs[T_COUNT] = {
                               "passes instead of 8), and lgs_bn_forward_pair / lgs_bn_backward_pair run the two norms of a downsample block on shared "
                               "reads (5 instead of 7 passes forward, 10 instead of 13 backward, 3 launches instead of 6); 0 = the single calls, dy "
                               "masked in both launches.  Bit-identical either way"},
+    {T_MAP_WINDOW_SORT, "MAP_WINDOW_SORT", 1, "3^3 maps, the window mask sort (A/B): 1 = k_window_sort, one workgroup per MASK_WINDOW positions sorts (mask code, index in "
+                                              "window) in LDS with a bitonic network, one launch per view; 0 = 64-bit keys (window, code) through rocPRIM's radix "
+                                              "sort over the whole map (13 launches per view).  A window that is no power of two in 1024 .. 16384 takes the radix "
+                                              "sort either way.  The permutation is identical"},
+    {T_MAP_BLOCK_DIR, "MAP_BLOCK_DIR", 1, "3^3 maps, neighbour lookup (A/B): 1 = a directory with one entry per occupied 4 x 4 x 4 block of cells {block id, first "
+                                          "sorted position, 64-bit occupancy}; a probe is one entry and a popcount; 0 = the open-addressing hash with one slot "
+                                          "per voxel (>= 2 n slots of 12 bytes).  The tables are identical"},
 };
 std::atomic<int64_t> g_val[T_COUNT];
 std::once_flag g_once;

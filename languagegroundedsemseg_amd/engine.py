@@ -198,7 +198,7 @@ EXPORTS = [
     "lgs_debug_norm_plan", "lgs_debug_instnorm_plan", "lgs_debug_seg_plan", "lgs_debug_kmap_relation",
     "lgs_manager_create", "lgs_manager_destroy", "lgs_manager_insert", "lgs_manager_stride2", "lgs_manager_check",
     "lgs_manager_parent_of", "lgs_manager_map_size", "lgs_manager_get_coords", "lgs_manager_kernel_map", "lgs_manager_kernel_map_ex",
-    "lgs_kmap_export",
+    "lgs_kmap_export", "lgs_debug_kmap_tables",
     "lgs_manager_origin", "lgs_manager_segment_map", "lgs_segmap_size", "lgs_seg_workspace_bytes", "lgs_seg_reduce",
     "lgs_seg_broadcast", "lgs_seg_max_backward",
     "lgs_in_workspace_bytes", "lgs_in_forward", "lgs_in_backward",
@@ -261,6 +261,7 @@ def lib():
         "lgs_manager_kernel_map": [vp, ci, ci, ci, vp, pvp],
         "lgs_manager_kernel_map_ex": [vp, ci, ci, ci, ci, vp, pvp],
         "lgs_kmap_export": [vp, vp, vp, vp, vp, pi64],
+        "lgs_debug_kmap_tables": [vp, ci, vp, vp, vp, vp, pi64, pi, pi],
         "lgs_manager_origin": [vp, vp, pi, pi64],
         "lgs_manager_segment_map": [vp, ci, ci, vp, pvp],
         "lgs_segmap_size": [vp, pi64, pi64],

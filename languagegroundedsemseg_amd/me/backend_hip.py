@@ -297,6 +297,20 @@ class HipKernelMap:
                 engine.check(L.lgs_kmap_export(self.h, _ptr(k), _ptr(i), _ptr(o), _stream(), ctypes.byref(m)))
         return k, i, o
 
+    def tables(self, bwd=False):
+        """-> (nbr [slots, n_pad], out_row [n_pad], mask64 [n_pad / 64]) of one view as the kernels read them (int32 copies; None
+        where the view has no such table): lgs_debug_kmap_tables, for tests that compare two build paths exactly"""
+        L = engine.lib()
+        n_pad, slots, present = ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int(0)
+        with _dev(self.mgr.device):
+            engine.check(L.lgs_debug_kmap_tables(self.h, int(bwd), None, None, None, _stream(), ctypes.byref(n_pad), ctypes.byref(slots), ctypes.byref(present)))
+            n, has = n_pad.value, present.value
+            mk = lambda bit, *shape: torch.empty(*shape, dtype=torch.int32, device=self.mgr.device) if has & bit else None
+            nbr, orow, mask = mk(1, slots.value, n), mk(2, n), mk(4, n // 64)
+            engine.check(L.lgs_debug_kmap_tables(self.h, int(bwd), _ptr(nbr) if nbr is not None else None, _ptr(orow) if orow is not None else None,
+                                                 _ptr(mask) if mask is not None else None, _stream(), ctypes.byref(n_pad), ctypes.byref(slots), ctypes.byref(present)))
+        return nbr, orow, mask
+
     def _rows(self, transposed):
         n_in = self.mgr.map_size(self.in_key)
         n_out = self.mgr.map_size(self.out_key)
