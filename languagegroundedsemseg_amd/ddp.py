@@ -84,7 +84,7 @@ class BucketedDDP:
                   "flag_off": n, "grad_elems": n}
         flat[n:n + len(params)] = 1.0
         for p in params:
-            # the engine's backward kernels write gradients straight into this slot (me.modules.grad_slot_view);
+            # the engine's backward kernels write gradients straight into this slot (me.host.grad_slot_view);
             # any other producer falls back to autograd's own accumulation into the same memory
             p._lgs_grad_slot = (flat, off, tuple(p.shape))
             p._lgs_ddp = self
@@ -558,7 +558,7 @@ def sync_bn_forward(backend, x, weight, bias, residual, running_mean, running_va
             _SYNCBN_EVENTS.append(None)
         return backend.bn_forward_sync(comm, x, weight, bias, eps, momentum, running_mean, running_var, nbt, residual, relu, out_into)
     # [mean | M2 | count], 2 kernels; the partial sums come from the producing conv's epilogue when it made them
-    local = backend.bn_stats(x, conv_stats) if conv_stats is not None else backend.bn_stats(x)
+    local = backend.bn_stats(x, conv_stats=conv_stats)
     allst = torch.empty(world, 2 * c + 1, dtype=torch.float32, device=x.device)
     group = syncbn_collective_group(group)
     if dist.get_backend(group) == "nccl":
@@ -567,78 +567,35 @@ def sync_bn_forward(backend, x, weight, bias, residual, running_mean, running_va
         _timed_collective(lambda: dist.all_gather(list(allst.unbind(0)), local, group=group), x.is_cuda)
     # one kernel: Chan's combination, running statistics, num_batches_tracked, 1/N (device scalar)
     stats, inv_n = backend.bn_sync_combine(allst, c, eps, momentum, running_mean, running_var, nbt)
-    y = backend.bn_apply(x, weight, bias, stats, residual, relu, out_into) if out_into is not None else \
-        backend.bn_apply(x, weight, bias, stats, residual, relu)
-    return y, stats, inv_n
+    return backend.bn_apply(x, weight, bias, stats, residual, relu, out_into=out_into), stats, inv_n
 
 
-def sync_bn_backward(backend, x, y, dy, weight, bias, stats, inv_n, relu_mode, want_res, group, gparam, bparam):
-    """SyncBN backward: local [sum dy' | sum dy' xhat] -> ONE all_reduce of 2C floats -> apply.  Parameter gradients stay local
-    (DDP averages them): written by the reduce kernel, straight into the gradient-bucket slots when gparam / bparam own them.
-    -> dx, dres, dgamma, dbeta, slots (True: dgamma / dbeta ARE the slot views)"""
-    from .me.modules import grad_slot_view
-    c = x.shape[1]
-    gview = grad_slot_view(gparam) if gparam is not None else None
-    bview = grad_slot_view(bparam) if bparam is not None else None
-    if gview is None or bview is None:
-        gview = bview = None
-        dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
-        dbeta = torch.empty(c, dtype=torch.float32, device=x.device)
-    else:
-        dgamma, dbeta = gview, bview
+def sync_bn_backward(backend, x, y, dy, weight, bias, stats, inv_n, relu_mode, want_res, group, sink):
+    """SyncBN backward: local [sum dy' | sum dy' xhat] -> ONE all_reduce of 2C floats -> apply -> dx, dres.  Parameter gradients
+    stay local (DDP averages them): the reduce kernel writes them into sink's buffers (me.host.AffineSink: the gradient-bucket slots
+    when the parameters own them)."""
+    dgamma, dbeta = sink.bufs
     comm = EngineComm.get(group, x.device) if (x.is_cuda and hasattr(backend, "bn_backward_sync")) else None
     if comm is not None:        # ONE engine call: reduce -> ncclAllReduce -> apply
         if _TIMING["on"]:
             _SYNCBN_EVENTS.append(None)
-        dx, dres = backend.bn_backward_sync(comm, x, y, dy, weight, bias, stats, inv_n, relu_mode, want_res, dgamma, dbeta)
-        return dx, dres, dgamma, dbeta, gview is not None
+        return backend.bn_backward_sync(comm, x, y, dy, weight, bias, stats, inv_n, relu_mode, want_res, dgamma, dbeta)
     sums = backend.bn_backward_reduce(x, y, dy, weight, bias, stats, relu_mode, dgamma, dbeta)
     group = syncbn_collective_group(group)
     _timed_collective(lambda: dist.all_reduce(sums, group=group), x.is_cuda)
-    dx, dres = backend.bn_backward_apply(x, y, dy, weight, bias, stats, sums, inv_n, relu_mode, want_res)
-    return dx, dres, dgamma, dbeta, gview is not None
-
-
-class _SyncBNFused(torch.autograd.Function):
-    """SyncBN as one autograd node around sync_bn_forward / sync_bn_backward (the whole-block node of models.py calls the
-    same two functions)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, residual, running_mean, running_var, nbt, eps, momentum, relu, group, backend, conv_stats=None,
-                out_into=None):
-        # out_into (_CatSlot): y goes straight into a column slice of the concat buffer (zero-copy ME.cat; not a tensor input)
-        y, stats, inv_n = sync_bn_forward(backend, x, weight, bias, residual, running_mean, running_var, nbt, eps, momentum, relu,
-                                          group, conv_stats, (out_into.buf, out_into.off) if out_into is not None else None)
-        ctx.backend, ctx.group, ctx.has_res = backend, group, residual is not None
-        ctx.relu_mode = 0 if not relu else (1 if residual is not None else 2)
-        ctx.gparam = weight if isinstance(weight, torch.nn.Parameter) else None
-        ctx.bparam = bias if isinstance(bias, torch.nn.Parameter) else None
-        ctx.save_for_backward(x, weight, bias, stats, y if ctx.relu_mode == 1 else x.new_empty(0), inv_n)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight, bias, stats, y, inv_n = ctx.saved_tensors
-        yy = y if ctx.relu_mode == 1 else None      # (dy / y may be column slices of a concat buffer: the engine reads them in place)
-        dx, dres, dgamma, dbeta, slots = sync_bn_backward(ctx.backend, x, yy, dy, weight, bias, stats, inv_n, ctx.relu_mode,
-                                                          ctx.has_res and ctx.needs_input_grad[3], ctx.group, ctx.gparam, ctx.bparam)
-        if slots:
-            return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None, None, None, None
-        return dx, dgamma.to(weight.dtype), dbeta.to(weight.dtype), dres, None, None, None, None, None, None, None, None, None, None
+    return backend.bn_backward_apply(x, y, dy, weight, bias, stats, sums, inv_n, relu_mode, want_res)
 
 
 def sync_batch_norm(x, bn, group=None, residual=None, relu=False, conv_stats=None, out_into=None):
     """Batch statistics over the rows of all ranks.  Device tensors run on the engine's fused kernels; the pure
     torch formulation below is only reachable with CPU tensors (the gloo host-logic tests)."""
+    if x.is_cuda:           # me.modules.BatchNormFunction: the one training-mode node, around sync_bn_forward / sync_bn_backward
+        from .me.core import get_backend
+        from .me.modules import BatchNormFunction
+        return BatchNormFunction.apply(x, bn.weight, bn.bias, residual, bn, relu, get_backend(), (True, group), conv_stats, out_into)
     rm = bn.running_mean if bn.track_running_stats else None
     rv = bn.running_var if bn.track_running_stats else None
     nbt = bn.num_batches_tracked if bn.track_running_stats else None
-    if x.is_cuda:
-        from .me.core import get_backend
-        if conv_stats is not None and (conv_stats[1] is not None) != (rm is not None):
-            conv_stats = None
-        return _SyncBNFused.apply(x, bn.weight, bn.bias, residual, rm, rv, nbt, bn.eps, bn.momentum, relu, group, get_backend(), conv_stats,
-                                  out_into)
     if nbt is not None:
         nbt += 1
     y = _SyncBNFunction.apply(x, bn.weight, bn.bias, rm, rv, bn.eps, bn.momentum, syncbn_collective_group(group))

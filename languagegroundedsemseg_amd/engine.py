@@ -180,14 +180,19 @@ class BlockBwd(ctypes.Structure):
                 ("ev_w1", ctypes.c_void_p), ("ev_w2", ctypes.c_void_p), ("ev_wd", ctypes.c_void_p)]
 
 
-# struct-module formats of lgs_block_fwd / lgs_block_bwd (native alignment); checked against the ctypes layouts at import
-BLOCK_FWD_FMT = "@PPiiiiqP" + "PPP" + "PPP" + "iii" + "PPPPPff" * 3 + "PPPPPP" + "PPP" + "PP"
-BLOCK_BWD_FMT = "@PPiiiiiiqqP" + "PPPPPP" + "PPP" + "PPP" + "PPP" + "iii" + "PPPPPP" + "PPPPPP" + "PPP" + "PPPPPP" + "PP" + "PPPPPP"
+# struct-module packers of lgs_block_fwd / lgs_block_bwd (native alignment), derived from the ctypes layouts above
 import struct as _struct
-assert _struct.calcsize(BLOCK_FWD_FMT) == ctypes.sizeof(BlockFwd), (_struct.calcsize(BLOCK_FWD_FMT), ctypes.sizeof(BlockFwd))
-assert _struct.calcsize(BLOCK_BWD_FMT) == ctypes.sizeof(BlockBwd), (_struct.calcsize(BLOCK_BWD_FMT), ctypes.sizeof(BlockBwd))
-BLOCK_FWD_PACK = _struct.Struct(BLOCK_FWD_FMT)
-BLOCK_BWD_PACK = _struct.Struct(BLOCK_BWD_FMT)
+_FORMAT_OF = {ctypes.c_void_p: "P", ctypes.c_int: "i", ctypes.c_int64: "q", ctypes.c_float: "f"}
+
+
+def struct_format(cls):
+    """struct-module format characters of a ctypes.Structure, nested structures flattened member by member"""
+    return "".join(_FORMAT_OF[t] if t in _FORMAT_OF else struct_format(t) for _, t in cls._fields_)
+
+
+BLOCK_FWD_PACK = _struct.Struct("@" + struct_format(BlockFwd))
+BLOCK_BWD_PACK = _struct.Struct("@" + struct_format(BlockBwd))
+assert BLOCK_FWD_PACK.size == ctypes.sizeof(BlockFwd) and BLOCK_BWD_PACK.size == ctypes.sizeof(BlockBwd)
 
 _lib = None
 

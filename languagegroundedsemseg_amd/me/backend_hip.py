@@ -14,6 +14,8 @@ import torch
 from .. import engine
 from .kernel import ALL_CONV_RELATIONS
 from .. import tuning as _tuning
+from . import host as _host
+from .host import AffineSink, WeightSink, memo, param_event, row_stride, rows_in_place
 
 _vp = ctypes.c_void_p
 
@@ -73,44 +75,26 @@ def get_packed():
     return _PACKED
 
 
-def _row_strided(t, c):
-    """row stride (elements) if `t` [n, c] is a column slice of a wider row-major tensor the kernels can read in place
-    (16-byte aligned rows), else None"""
-    if t.dim() == 2 and t.shape[1] == c and t.stride(1) == 1 and t.stride(0) > c:
-        e = t.element_size()
-        if (t.stride(0) * e) % 16 == 0 and t.data_ptr() % 16 == 0:
-            return t.stride(0)
-    return None
-
-
 _WS = {}
-_BN_WSB = {}
+_QUERIES = {}     # host.memo of the engine queries that belong to no map
 
 
 def _bn_ws_bytes(L, n, c):
-    b = _BN_WSB.get((n, c))
-    if b is None:
-        if len(_BN_WSB) > 4096:
-            _BN_WSB.clear()
-        b = _BN_WSB[(n, c)] = L.lgs_bn_workspace_bytes(n, c)
-    return b
+    return memo(_QUERIES, ("bn_ws", n, c), L.lgs_bn_workspace_bytes, n, c)
 
 
-_BN_PAIR = {}
+def _ask_bn_pair_plan(L, direction, n, c, dt):
+    info = engine.NormPairPlanInfo()
+    engine.check(L.lgs_bn_pair_plan(direction, n, c, dt, ctypes.byref(info)))
+    return int(info.path), int(info.workspace_bytes)
 
 
 def _bn_pair_plan(L, direction, n, c, dt):
     """-> (path, workspace bytes) of lgs_bn_forward_pair (direction 0) / lgs_bn_backward_pair (1) for this call on the current device;
     path 0 = the engine issues the two single norms and needs their intermediate (res / dres) from the caller"""
-    key = (direction, n, c, dt, engine.TUNING_EPOCH)
-    v = _BN_PAIR.get(key)
-    if v is None:
-        if len(_BN_PAIR) > 4096:
-            _BN_PAIR.clear()
-        info = engine.NormPairPlanInfo()
-        engine.check(L.lgs_bn_pair_plan(direction, n, c, dt, ctypes.byref(info)))
-        v = _BN_PAIR[key] = (int(info.path), int(info.workspace_bytes))
-    return v
+    return memo(_QUERIES, ("bn_pair", direction, n, c, dt), _ask_bn_pair_plan, L, direction, n, c, dt)
+
+
 # input voxels per batch below which weight gradients are not moved to the side stream (LGS_WGRAD_INLINE_BELOW: tuning knob;
 # one 145 k-voxel scene per step: 11.2 -> 10.4 ms, the 1.2 M-voxel batch keeps the side stream: 29.9 vs 30.9 ms)
 _WGRAD_INLINE_BELOW = _tuning.host("WGRAD_INLINE_BELOW")
@@ -138,14 +122,6 @@ def _ws(nbytes, device, stream=None):
                 t = torch.empty(size, dtype=torch.uint8, device=device)
         _WS[key] = t
     return t
-
-
-def _param_event(param):
-    """the reusable event of a kernel parameter's weight gradient (me/modules.py conv_weight_grad; BucketedDDP waits on it)"""
-    ev = getattr(param, "_lgs_wgrad_event", None)
-    if ev is None:
-        ev = param._lgs_wgrad_event = torch.cuda.Event()
-    return ev
 
 
 def _raw_event(ev, stream):
@@ -201,15 +177,7 @@ class PackedWeights:
         """-> (packed buffer or None, pack_mode)"""
         if not self.enabled or cache is None:
             return None, 0
-        # the layout of a launch shape on this map: asked once per map (layers share maps) and per state of the tuning table -- the
-        # layout depends on knobs (FP32_SPLIT: 6 instead of 4 bytes per element), and a descriptor cached across engine.tuning(...)
-        # would hand a buffer of the old size / a "valid" image of the old layout to the new kernel (advisor, round 5)
-        ck = (op, transposed, cin, cout, dt, engine.TUNING_EPOCH)
-        d = km._pdesc.get(ck)
-        if d is None:
-            d = engine.PackDesc()
-            engine.check(engine.lib().lgs_conv_pack_desc(km.h, int(op), int(transposed), int(cin), int(cout), int(dt), ctypes.byref(d)))
-            km._pdesc[ck] = d
+        d = km.pack_desc(op, transposed, cin, cout, dt)
         if d.bytes == 0:
             return None, 0
         key = (op, int(transposed), dt, d.ncp, d.nbp, d.K, cin, cout, int(d.dtype), int(d.bytes))   # (d.dtype: the image's own layout code)
@@ -272,17 +240,30 @@ class HipKernelMap:
     def __init__(self, mgr, handle, in_key, out_key, ks):
         self.mgr, self.h, self.in_key, self.out_key, self.ks = mgr, handle, in_key, out_key, ks
         self.K = ks ** 3
-        # lgs_conv_workspace_bytes per (cin, cout, dtype, op, tuning epoch): several layers share a map, and the answer depends
-        # on knobs (tile configuration, weight-gradient plans), so a knob change must not reuse a size computed before it
-        self._wsb = {}
-        self._pdesc = {}          # lgs_conv_pack_desc per (op, transposed, cin, cout, dtype, tuning epoch)
+        # host.memo of what the engine answers about this map (several layers share a map; the answers depend on knobs: tile
+        # configuration, weight-gradient plans, FP32_SPLIT's 6 instead of 4 bytes per packed element)
+        self._memo = {}
 
     def _ws_bytes(self, L, cin, cout, dt, op):
-        key = (cin, cout, dt, op, engine.TUNING_EPOCH)
-        b = self._wsb.get(key)
-        if b is None:
-            b = self._wsb[key] = L.lgs_conv_workspace_bytes(self.h, cin, cout, dt, op)
-        return b
+        return memo(self._memo, ("conv_ws", cin, cout, dt, op), L.lgs_conv_workspace_bytes, self.h, cin, cout, dt, op)
+
+    def block_ws_bytes(self, L, kmap1, cin, planes, dt):
+        """lgs_block_workspace_bytes of a block on this 3^3 map (kmap1: the 1x1 map of its downsample branch, or None)"""
+        return memo(self._memo, ("block_ws", cin, planes, dt, kmap1 is not None),
+                    L.lgs_block_workspace_bytes, self.h, kmap1.h if kmap1 is not None else None, cin, planes, dt)
+
+    def can_accumulate(self, cin, cout, dt):
+        """does the forward-view dgrad of this launch shape have the accumulating epilogue (lgs_conv_dgrad_accumulate)?"""
+        return memo(self._memo, ("can_accumulate", cin, cout, dt), engine.lib().lgs_conv_dgrad_can_accumulate, self.h, 0, cin, cout, dt)
+
+    def _ask_pack_desc(self, op, transposed, cin, cout, dt):
+        d = engine.PackDesc()
+        engine.check(engine.lib().lgs_conv_pack_desc(self.h, int(op), int(transposed), int(cin), int(cout), int(dt), ctypes.byref(d)))
+        return d
+
+    def pack_desc(self, op, transposed, cin, cout, dt):
+        """the packed-image layout of a launch shape on this map (lgs_conv_pack_desc)"""
+        return memo(self._memo, ("pack_desc", op, transposed, cin, cout, dt), self._ask_pack_desc, op, transposed, cin, cout, dt)
 
     def export(self):
         L = engine.lib()
@@ -332,9 +313,8 @@ class HipKernelMap:
         L = engine.lib()
         w, cin, cout = self._w32(weight)
         # the skip half of a zero-copy ME.cat is a column slice of the concat buffer: gathered in place through a row stride
-        ld = _row_strided(x, cin) if (cin % (8 if x.dtype == torch.bfloat16 else 4) == 0 and cout % 4 == 0) else None
-        if ld is None:
-            x = x.contiguous()
+        vec_ok = cin % (8 if x.dtype == torch.bfloat16 else 4) == 0 and cout % 4 == 0
+        x, ld = rows_in_place(x, cin) if vec_ok else (x.contiguous(), 0)
         n_in, n_out = self._rows(transposed)
         assert x.shape[0] == n_in and x.shape[1] == cin, (x.shape, n_in, cin)
         dt = _dtype_code(x)
@@ -350,7 +330,7 @@ class HipKernelMap:
             piv = bn_pivot if part is not None else None
             pk, mode = get_packed().lookup(pack_cache, self, 0, transposed, weight, w, cin, cout, dt)
             engine.check(L.lgs_conv_forward(self.h, int(transposed), _ptr(x), cin, _ptr(w), cout, _ptr(b), _ptr(out), dt,
-                                            _ptr(ws), _ptr(part), _ptr(piv), _ptr(pk), int(mode), int(ld or 0), _stream()))
+                                            _ptr(ws), _ptr(part), _ptr(piv), _ptr(pk), int(mode), int(ld), _stream()))
         if want_bn_stats:
             return out, ((part, piv) if part is not None else None)
         return out
@@ -383,17 +363,17 @@ class HipKernelMap:
         stream: enqueue on this torch stream instead of the current one (the caller has ordered it after the producers of
         x / gout; no stream context switch on the host)"""
         L = engine.lib()
-        if stream is not None and (not gout.is_contiguous() or (not x.is_contiguous() and _row_strided(x, x.shape[1]) is None)):
+        if stream is not None and (not gout.is_contiguous() or (not x.is_contiguous() and not row_stride(x, x.shape[1]))):
             with torch.cuda.stream(stream):         # rare: a copy is needed, make it on the target stream
                 return self.conv_wgrad(x, gout, transposed, out=out)
         gout = gout.contiguous()
         cin, cout = x.shape[1], gout.shape[1]
         # strided input (see conv_forward): only the position-stationary bf16 kernel reads it in place
-        ld = _row_strided(x, cin) if (x.dtype == torch.bfloat16 and self.ks in (2, 3) and cin % 8 == 0 and cout % 8 == 0) else None
+        ld = row_stride(x, cin) if (x.dtype == torch.bfloat16 and self.ks in (2, 3) and cin % 8 == 0 and cout % 8 == 0) else 0
         dt = _dtype_code(x)
-        if ld is not None and not L.lgs_conv_wgrad_supports_stride(self.h, int(transposed), cin, cout, dt, int(ld)):
-            ld = None      # the position-stationary kernel declines this shape: hand the pair-list kernel a contiguous copy
-        if ld is None and not x.is_contiguous():
+        if ld and not L.lgs_conv_wgrad_supports_stride(self.h, int(transposed), cin, cout, dt, int(ld)):
+            ld = 0         # the position-stationary kernel declines this shape: hand the pair-list kernel a contiguous copy
+        if not ld and not x.is_contiguous():
             if stream is not None:
                 with torch.cuda.stream(stream):
                     return self.conv_wgrad(x, gout, transposed, out=out)
@@ -410,7 +390,7 @@ class HipKernelMap:
                 gw.record_stream(stream)
             ws = _ws(self._ws_bytes(L, cin, cout, dt, 2), x.device, stream)
             engine.check(L.lgs_conv_wgrad(self.h, int(transposed), _ptr(x), cin, _ptr(gout), cout, _ptr(gw), dt, _ptr(ws),
-                                          int(ld or 0), raw))
+                                          int(ld), raw))
         return gw
 
 
@@ -420,13 +400,10 @@ class HipSegmentMap:
     def __init__(self, mgr, handle, fine_key, coarse_key):
         self.mgr, self.h, self.fine_key, self.coarse_key = mgr, handle, fine_key, coarse_key
         self.n_fine, self.n_coarse = mgr.map_size(fine_key), mgr.map_size(coarse_key)
-        self._wsb = {}            # lgs_seg_workspace_bytes per c: a function of the map and c alone (no knob feeds it)
+        self._memo = {}
 
     def _ws_bytes(self, L, c):
-        b = self._wsb.get(c)
-        if b is None:
-            b = self._wsb[c] = L.lgs_seg_workspace_bytes(self.h, c)
-        return b
+        return memo(self._memo, ("seg_ws", c), L.lgs_seg_workspace_bytes, self.h, c)
 
 
 class HipManager:
@@ -737,9 +714,9 @@ class HipBackend:
         dt = _dtype_code(x)
         # a column slice of a wider row-major tensor (the gradient of one ME.cat input) is read in place; the engine is given
         # dy's row stride explicitly, also when it is c
-        dy, dy_ld = self._strided_in(dy, c) if dy.dtype == x.dtype else (dy.contiguous(), 0)
+        dy, dy_ld = rows_in_place(dy, c) if dy.dtype == x.dtype else (dy.contiguous(), 0)
         dy_ld = dy_ld or c
-        y, y_ld = self._strided_in(y, c)
+        y, y_ld = rows_in_place(y, c)
         with _dev(x.device):
             dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
             dres = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_residual else None
@@ -786,9 +763,9 @@ class HipBackend:
         L = engine.lib()
         n, c = xa.shape
         dt = _dtype_code(xa)
-        dy, dy_ld = self._strided_in(dy, c) if dy.dtype == xa.dtype else (dy.contiguous(), 0)
+        dy, dy_ld = rows_in_place(dy, c) if dy.dtype == xa.dtype else (dy.contiguous(), 0)
         dy_ld = dy_ld or c
-        ya, ya_ld = self._strided_in(ya, c)
+        ya, ya_ld = rows_in_place(ya, c)
         with _dev(xa.device):
             path, wsb = _bn_pair_plan(L, 1, n, c, dt)
             dx = torch.empty((2,) + tuple(xa.shape), dtype=xa.dtype, device=xa.device)
@@ -820,10 +797,7 @@ class HipBackend:
         return st
 
     def _block_ws(self, L, kmap3, kmap1, cin, planes, dt, n, device):
-        key = ("cblk_ws", cin, planes, dt, engine.TUNING_EPOCH)
-        b = kmap3._wsb.get(key)
-        if b is None:
-            b = kmap3._wsb[key] = L.lgs_block_workspace_bytes(kmap3.h, kmap1.h if kmap1 is not None else None, cin, planes, dt)
+        b = kmap3.block_ws_bytes(L, kmap1, cin, planes, dt)
         # conv scratch and BatchNorm scratch are never live at the same time inside the sequence (as in the call-by-call path,
         # where both are the stream's one grow-only buffer): one buffer, sized for the larger
         # (a block with a downsample branch runs two of its norms as a pair: lgs_bn_pair_workspace_bytes)
@@ -876,8 +850,6 @@ class HipBackend:
 
     def block_backward(self, dy, saved, extra, kmap3, kmap1, pcs, params, relu_final, want_gin):
         """BasicBlock backward through lgs_block_backward -> the gradient tuple of models._BasicBlockFunction"""
-        from . import modules as _modules
-        from .modules import grad_slot_view
         L = engine.lib()
         self.block_calls = getattr(self, "block_calls", 0) + 1
         x, w1, g1, b1, w2, g2, b2, o1, st1, y1, o2, st2, y2 = saved
@@ -888,12 +860,7 @@ class HipBackend:
         dt = _dtype_code(x)
         dev = x.device
         ds = wd is not None
-        esz = dy.element_size()
-        if (dy.dim() == 2 and dy.stride(1) == 1 and dy.stride(0) >= planes and (dy.stride(0) * esz) % 16 == 0
-                and dy.data_ptr() % 16 == 0 and dy.dtype == x.dtype):
-            dy_ld = dy.stride(0)
-        else:
-            dy, dy_ld = dy.contiguous(), planes
+        dy, dy_ld = rows_in_place(dy, planes) if dy.dtype == x.dtype else (dy.contiguous(), 0)
         pk = get_packed()
         with _dev(dev):
             p1, pm1 = pk.lookup(pcs[0], kmap3, 1, False, w1, w1, cin, planes, dt)
@@ -907,49 +874,36 @@ class HipBackend:
             row = n * planes * x.element_size()
             b_dres, b_dy1, b_dx1, b_dxd = (b0 + row, b0 + 2 * row, b0 + 3 * row, (b0 + 4 * row) if ds else 0) if want_dres else \
                 (0, b0 + row, b0 + 2 * row, b0 + 3 * row)
-
-            slots = [True]
-
-            def wgrad_out(param, ref):
-                v = grad_slot_view(param) if param is not None else None
-                if v is None:
-                    slots[0] = False
-                    return torch.empty(ref.shape, dtype=torch.float32, device=dev)
-                return v
-
-            def affine_out(pg, pb, c):
-                gv = grad_slot_view(pg) if pg is not None else None
-                bv = grad_slot_view(pb) if pb is not None else None
-                if gv is None or bv is None:
-                    t = torch.empty((2, c), dtype=torch.float32, device=dev)
-                    return t[0], t[1]
-                return gv, bv
-            gw1, gw2 = wgrad_out(pw1, w1), wgrad_out(pw2, w2)
-            dg1, db1 = affine_out(pg1, pb1, planes)
-            dg2, db2 = affine_out(pg2, pb2, planes)
+            sw1, sw2 = WeightSink(pw1, w1.shape, dev), WeightSink(pw2, w2.shape, dev)
+            (gw1,), (gw2,) = sw1.bufs, sw2.bufs
+            dg1, db1 = AffineSink(pg1, pb1, planes, dev).bufs
+            dg2, db2 = AffineSink(pg2, pb2, planes, dev).bufs
+            slots = sw1.adopted and sw2.adopted
             gwd = dgd = dbd = gind = None
             if ds:
-                gwd = wgrad_out(pwd, wd)
-                dgd, dbd = affine_out(pgd, pbd, planes)
+                swd = WeightSink(pwd, wd.shape, dev)
+                (gwd,), slots = swd.bufs, slots and swd.adopted
+                dgd, dbd = AffineSink(pgd, pbd, planes, dev).bufs
                 gind = torch.empty((n, cin), dtype=x.dtype, device=dev)
             cws = self._block_ws(L, kmap3, kmap1, cin, planes, dt, n, dev).data_ptr()
             # weight gradients beside the dgrad / BatchNorm chain (what modules.conv_weight_grad does call by call): every kernel
             # parameter owns a gradient-bucket slot and the batch is not one of the small ones that keep them on the compute stream
+            # (how this differs from the call-by-call rule: host.wgrad_placement)
             side = None
             s_raw = s_ws = s_fork = e1 = e2 = ed = 0
-            if not getattr(kmap3.mgr, "inline_wgrad", False) and slots[0] and _modules._DBG_WGRAD == "":
+            if not getattr(kmap3.mgr, "inline_wgrad", False) and slots and _host._DBG_WGRAD == "":
                 side = self.side_stream(dev)
                 s_raw = side.cuda_stream
                 need = max(kmap3._ws_bytes(L, cin, planes, dt, 2), kmap3._ws_bytes(L, planes, planes, dt, 2),
                            kmap1._ws_bytes(L, cin, planes, dt, 2) if ds else 0)
                 s_ws = _ws(need, dev, side).data_ptr()
                 s_fork = _raw_event(self.fork_event(dev), side)
-                e1, e2 = _raw_event(_param_event(pw1), side), _raw_event(_param_event(pw2), side)
-                ed = _raw_event(_param_event(pwd), side) if ds else 0
+                e1, e2 = _raw_event(param_event(pw1), side), _raw_event(param_event(pw2), side)
+                ed = _raw_event(param_event(pwd), side) if ds else 0
             args_b, addr_b = self._blk_stage("b")
             engine.BLOCK_BWD_PACK.pack_into(
                 args_b, 0, kmap3.h.value, kmap1.h.value if ds else 0, dt, int(relu_final), cin, planes, int(want_gin), 0,
-                n, 0 if dy_ld == planes else dy_ld, dy.data_ptr(),
+                n, dy_ld, dy.data_ptr(),
                 x.data_ptr(), o1.data_ptr(), y1.data_ptr(), o2.data_ptr(), y2.data_ptr() if relu_final else 0, od.data_ptr() if ds else 0,
                 st1.data_ptr(), st2.data_ptr(), std.data_ptr() if ds else 0,
                 w1.data_ptr(), w2.data_ptr(), wd.data_ptr() if ds else 0,
@@ -961,11 +915,8 @@ class HipBackend:
                 cws, cws, s_raw, s_ws, s_fork, e1, e2, ed)
             engine.check(L.lgs_block_backward(addr_b, _stream()))
             if side is not None:
-                # the side stream reads these after this call returns: their memory may only be reused in ITS order
-                for t in (x, y1, buf):
-                    t.record_stream(side)
-                for p in (pw2, pw1, pwd) if ds else (pw2, pw1):       # the order the engine issued them in
-                    _modules.note_side_wgrad(p)
+                # (parameters in the order the engine issued them; the side stream reads the operands after this call returns)
+                _host.side_wgrads_issued(side, (pw2, pw1, pwd) if ds else (pw2, pw1), (x, y1, buf))
         gin = (gind if ds else buf[1]) if want_gin else None
         # (all parameters of the fast path are fp32: the engine's fp32 gradients need no cast)
         out = (gin, None, None, None, gw1, dg1, db1, gw2, dg2, db2)
@@ -1021,18 +972,9 @@ class HipBackend:
         buf, off = out_into
         n, c = x.shape
         y = buf[:, off:off + c]
-        assert buf.dtype == x.dtype and buf.shape[0] == n and (buf.stride(0) * x.element_size()) % 16 == 0 and y.data_ptr() % 16 == 0
-        return y, buf.stride(0)
-
-    @staticmethod
-    def _strided_in(t, c):
-        """-> (tensor, row stride for the engine) of a [n, c] operand read in place when it is an aligned column slice, else a copy"""
-        if t is None:
-            return None, 0
-        ld = _row_strided(t, c)
-        if ld is not None:
-            return t, ld
-        return t.contiguous(), 0
+        ld = row_stride(y, c)
+        assert buf.dtype == x.dtype and buf.shape[0] == n and ld, (tuple(buf.shape), buf.dtype, off, c)
+        return y, ld
 
     def bn_forward_sync(self, comm, x, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, residual, relu,
                         out_into=None):
@@ -1055,8 +997,8 @@ class HipBackend:
         """-> dx, dres (dgamma_out / dbeta_out receive the LOCAL parameter gradients)"""
         L = engine.lib()
         n, c = x.shape
-        dy, dy_ld = self._strided_in(dy, c)
-        y, y_ld = self._strided_in(y, c)
+        dy, dy_ld = rows_in_place(dy, c)
+        y, y_ld = rows_in_place(y, c)
         with _dev(x.device):
             dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
             dres = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_residual else None
@@ -1070,8 +1012,8 @@ class HipBackend:
         """-> sums [2C] (local sum dy', sum dy' xhat); the same vectors are also written to dgamma_out / dbeta_out"""
         L = engine.lib()
         n, c = x.shape
-        dy, dy_ld = self._strided_in(dy, c)
-        y, y_ld = self._strided_in(y, c)
+        dy, dy_ld = rows_in_place(dy, c)
+        y, y_ld = rows_in_place(y, c)
         with _dev(x.device):
             if n == 0:                     # empty batch: zero sums (and zero parameter gradients)
                 for t in (dgamma_out, dbeta_out):
@@ -1089,8 +1031,8 @@ class HipBackend:
         L = engine.lib()
         n, c = x.shape
         dev_inv = inv_n_total if torch.is_tensor(inv_n_total) else None
-        dy, dy_ld = self._strided_in(dy, c)
-        y, y_ld = self._strided_in(y, c)
+        dy, dy_ld = rows_in_place(dy, c)
+        y, y_ld = rows_in_place(y, c)
         with _dev(x.device):
             dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
             dres = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_residual else None

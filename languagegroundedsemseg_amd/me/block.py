@@ -12,6 +12,8 @@ from .. import tuning as _tuning
 from .core import get_backend
 from . import modules as _mod
 from . import deferred as _d
+from .host import AffineSink, relu_mode_of
+from .modules import bn_bwd, bn_fwd, conv_weight_grad
 
 # ---------------------------------------------------------------------------------------------- whole-block autograd node
 # Op by op a BasicBlock is 4 (6 with a downsample branch) autograd nodes, as many module calls and SparseTensor wrappers each
@@ -81,43 +83,6 @@ def _sync_group(norm):
     return False, None
 
 
-def _bn_fwd(be, x, bn, g, b, residual, relu, conv_stats, sync=(False, None)):
-    """-> y, stats, inv_n (inv_n: device scalar 1 / global rows of a SyncBN layer, else None)"""
-    if conv_stats is not None and (conv_stats[1] is None):
-        conv_stats = None                                  # pivot convention of MinkowskiBatchNorm.forward
-    if sync[0]:
-        from ..ddp import sync_bn_forward
-        return sync_bn_forward(be, x, g, b, residual, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps, bn.momentum,
-                               relu, sync[1], conv_stats)
-    return _bn_fwd_local(be, x, bn, g, b, residual, relu, conv_stats) + (None,)
-
-
-def _bn_fwd_local(be, x, bn, g, b, residual, relu, conv_stats):
-    if conv_stats is not None:
-        return be.bn_forward(x, g, b, bn.eps, bn.momentum, bn.running_mean, bn.running_var, residual, relu, bn.num_batches_tracked,
-                             conv_stats=conv_stats)
-    return be.bn_forward(x, g, b, bn.eps, bn.momentum, bn.running_mean, bn.running_var, residual, relu, bn.num_batches_tracked)
-
-
-def _bn_bwd(be, x, y, dy, g, b, gp, bp, stats, relu_mode, want_res, need, sync=(False, None), inv_n=None):
-    """-> dx, dres, d gamma, d beta (the last two as bucket-slot views when the parameters gp / bp own slots)"""
-    from .modules import grad_slot_view
-    if sync[0]:
-        from ..ddp import sync_bn_backward
-        dx, dres, dg, db, slots = sync_bn_backward(be, x, y, dy.contiguous(), g, b, stats, inv_n, relu_mode, want_res, sync[1], gp, bp)
-        if slots:
-            return dx, dres, dg, db
-        return dx, dres, (dg.to(g.dtype) if need else None), (db.to(g.dtype) if need else None)
-    gv = grad_slot_view(gp) if gp is not None else None
-    bv = grad_slot_view(bp) if bp is not None else None
-    if gv is None or bv is None:
-        gv = bv = None
-    dx, dres, dg, db = be.bn_backward(x, y, dy, g, b, stats, relu_mode, want_res, gv, bv)
-    if gv is not None:
-        return dx, dres, gv, bv
-    return dx, dres, (dg.to(g.dtype) if need else None), (db.to(g.dtype) if need else None)
-
-
 _BLOCK_C = _tuning.host("BLOCK_C") != 0
 _BLOCK_C_VETO = None    # measurement hook (bench.py's per-launch instrumentation): callable(rows, cin, planes) -> True = enqueue this
 #                         block call by call (same launches, same results), so that its conv launches can be bracketed from Python
@@ -133,12 +98,7 @@ def _c_block_ok(x, kmap3, kmap1, cin, planes, be):
         return False
     if _BLOCK_C_VETO is not None and _BLOCK_C_VETO(x.shape[0], cin, planes):
         return False
-    key = ("cblk", cin, planes, x.dtype, engine.TUNING_EPOCH)     # the launch shape behind the answer depends on knobs
-    ok = kmap3._wsb.get(key)
-    if ok is None:
-        dt = engine.LGS_BF16 if x.dtype == torch.bfloat16 else engine.LGS_F32
-        ok = kmap3._wsb[key] = bool(engine.lib().lgs_conv_dgrad_can_accumulate(kmap3.h, 0, cin, planes, dt))
-    return ok
+    return kmap3.can_accumulate(cin, planes, engine.LGS_BF16 if x.dtype == torch.bfloat16 else engine.LGS_F32)
 
 
 class _BasicBlockFunction(torch.autograd.Function):
@@ -171,7 +131,7 @@ class _BasicBlockFunction(torch.autograd.Function):
         want = bool(getattr(be, "conv_bn_stats", False)) and be.want_conv_bn_stats(x.shape[0], w1.shape[-1], x.element_size())
         o1, s1 = kmap3.conv_forward(x, w1, None, False, bn_pivot=n1.running_mean, want_bn_stats=True, pack_cache=pc1) if want else \
             (kmap3.conv_forward(x, w1, None, False, pack_cache=pc1), None)
-        y1, st1, inv1 = _bn_fwd(be, o1, n1, g1, b1, None, True, s1, sync)
+        y1, st1, inv1 = bn_fwd(be, o1, n1, g1, b1, None, True, s1, sync)
         o2, s2 = kmap3.conv_forward(y1, w2, None, False, bn_pivot=n2.running_mean, want_bn_stats=True, pack_cache=pc2) if want else \
             (kmap3.conv_forward(y1, w2, None, False, pack_cache=pc2), None)
         ctx.has_ds = wd is not None
@@ -189,10 +149,10 @@ class _BasicBlockFunction(torch.autograd.Function):
             inv2 = invd = None
         else:
             if ctx.has_ds:
-                res, std, invd = _bn_fwd(be, od, nd, gd, bd, None, False, sd, sync)
+                res, std, invd = bn_fwd(be, od, nd, gd, bd, None, False, sd, sync)
             else:
                 res, invd = x, None
-            y2, st2, inv2 = _bn_fwd(be, o2, n2, g2, b2, res, relu, s2, sync)
+            y2, st2, inv2 = bn_fwd(be, o2, n2, g2, b2, res, relu, s2, sync)
         ctx.kmap3, ctx.kmap1, ctx.relu, ctx.pc = kmap3, kmap1, relu, (pc1, pc2, pcd if ctx.has_ds else None)
         ctx.params = tuple(t if isinstance(t, nn.Parameter) else None for t in (w1, g1, b1, w2, g2, b2, wd, gd, bd))
         inv = ((inv1, inv2, invd) if ctx.has_ds else (inv1, inv2)) if sync[0] else ()
@@ -204,7 +164,6 @@ class _BasicBlockFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from .modules import conv_weight_grad
         be = get_backend()
         sv = ctx.saved_tensors
         x, w1, g1, b1, w2, g2, b2, o1, st1, y1, o2, st2, y2 = sv[:13]
@@ -220,29 +179,26 @@ class _BasicBlockFunction(torch.autograd.Function):
         inv1, inv2, invd = (tuple(sv[n_base:]) + (None,))[:3] if sync[0] else (None, None, None)
         # norm2 (+ residual) (+ ReLU): mask from the saved output when there is a ReLU (a residual was added)
         pair = ctx.has_ds and getattr(ctx, "pair", False)
+        mode2, mode1, moded = relu_mode_of(ctx.relu, True), relu_mode_of(True, False), relu_mode_of(False, False)
         if pair:
-            from .modules import grad_slot_view
             wd, gd, bd, od, std = sv[13:18]
-            slots = [grad_slot_view(p_) if p_ is not None else None for p_ in (pg2, pb2, pgd, pbd)]
-            if any(v is None for v in slots):
-                slots = None
-            dx2, dxd, _, (dg2, db2, dgd, dbd) = be.bn_backward_pair(o2, y2 if ctx.relu else None, g2, b2, st2, 1 if ctx.relu else 0, od, gd, std, dy,
-                                                                    False, slots)
-            if slots is None:
-                dg2, db2 = ((dg2.to(g2.dtype), db2.to(g2.dtype)) if (need[8] or need[9]) else (None, None))
-                dgd, dbd = ((dgd.to(gd.dtype), dbd.to(gd.dtype)) if (need[11] or need[12]) else (None, None))
+            sink2, sinkd = AffineSink(pg2, pb2, g2.shape[0], dy.device), AffineSink(pgd, pbd, gd.shape[0], dy.device)
+            dx2, dxd = be.bn_backward_pair(o2, y2 if ctx.relu else None, g2, b2, st2, mode2, od, gd, std, dy, False,
+                                           sink2.bufs + sinkd.bufs)[:2]
+            dg2, db2 = sink2.returned(g2.dtype, need[8] or need[9])
+            dgd, dbd = sinkd.returned(gd.dtype, need[11] or need[12])
         else:
-            dx2, dres, dg2, db2 = _bn_bwd(be, o2, y2 if ctx.relu else None, dy, g2, b2, pg2, pb2, st2, 1 if ctx.relu else 0, True,
-                                          need[8] or need[9], sync, inv2)
+            dx2, dres, dg2, db2 = bn_bwd(be, o2, y2 if ctx.relu else None, dy, g2, b2, pg2, pb2, st2, mode2, True, need[8] or need[9],
+                                         sync, inv2)
         gw2 = conv_weight_grad(kmap3, y1, dx2, False, pw2, w2.shape, w2.dtype) if need[7] else None
         dy1 = kmap3.conv_dgrad(dx2, w2, False, pack_cache=pc2)
-        dx1, _, dg1, db1 = _bn_bwd(be, o1, None, dy1, g1, b1, pg1, pb1, st1, 2, False, need[5] or need[6], sync, inv1)
+        dx1, _, dg1, db1 = bn_bwd(be, o1, None, dy1, g1, b1, pg1, pb1, st1, mode1, False, need[5] or need[6], sync, inv1)
         gw1 = conv_weight_grad(kmap3, x, dx1, False, pw1, w1.shape, w1.dtype) if need[4] else None
         gin = None
         if ctx.has_ds:
             wd, gd, bd, od, std = sv[13:18]
             if not pair:
-                dxd, _, dgd, dbd = _bn_bwd(be, od, None, dres, gd, bd, pgd, pbd, std, 0, False, need[11] or need[12], sync, invd)
+                dxd, _, dgd, dbd = bn_bwd(be, od, None, dres, gd, bd, pgd, pbd, std, moded, False, need[11] or need[12], sync, invd)
             gwd = conv_weight_grad(ctx.kmap1, x, dxd, False, pwd, wd.shape, wd.dtype) if need[10] else None
             if need[0]:
                 gin = kmap3.conv_dgrad(dx1, w1, False, pack_cache=pc1,

@@ -14,18 +14,11 @@ import torch.nn as nn
 from . import deferred as _deferred
 from .core import SparseTensor, get_backend
 from .kernel import KernelGenerator, RegionType, conv_relation, convert_to_int_list, supported_convs_text
-
-
-from .. import tuning as _tuning
-_WIDE_WGRAD_INLINE = _tuning.host("WIDE_WGRAD_INLINE") != 0
-_DBG_WGRAD = _tuning.host("DBG_WGRAD")   # "", "skip", "inline": step-time attribution experiments only
+from .host import AffineSink, WeightSink, param_event, relu_mode_of, row_stride, side_wgrads_issued, wgrad_placement
 
 
 class MinkowskiModuleBase(nn.Module):
     pass
-
-
-_WGRAD_SEQ = [0]     # issue order of the side-stream weight gradients (the stream runs them in this order)
 
 
 def _invalidate_packed():
@@ -48,65 +41,30 @@ class MinkowskiNetwork(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------ convolution
-def grad_slot_view(param):
-    """Fresh view of the parameter's slot in a flat gradient bucket (languagegroundedsemseg_amd.ddp.BucketedDDP), or
-    None.  Returning such a view from backward() lets autograd adopt it as `.grad` without an accumulation kernel:
-    the engine has already written the gradient where the all-reduce and the optimiser will read it."""
-    slot = getattr(param, "_lgs_grad_slot", None)
-    if slot is None or param.grad is not None:
-        return None
-    flat, off, shape = slot
-    n = 1
-    for d in shape:
-        n *= d
-    return flat[off:off + n].view(shape)
-
-
-def note_side_wgrad(kparam):
-    """book-keeping of one weight gradient issued on the side stream (here, or by lgs_block_backward): its place in the stream's
-    order and the step it belongs to -- BucketedDDP picks the newest event of a bucket from these"""
-    _WGRAD_SEQ[0] += 1
-    kparam._lgs_wgrad_seq = _WGRAD_SEQ[0]
-    owner = getattr(kparam, "_lgs_ddp", None)
-    kparam._lgs_wgrad_step = owner._step if owner is not None else -1
-
-
 def conv_weight_grad(kmap, feats, gout, transposed, kparam, kshape, kdtype):
     """Weight gradient of one convolution.  When the kernel parameter owns a bucket slot the gradient is written straight
     into it ON A SIDE STREAM (off the backward critical path dgrad -> BN -> dgrad ...; both kernels are latency-bound, so
-    running them concurrently fills the machine) and the slot view is returned for autograd to adopt as `.grad`."""
-    view = grad_slot_view(kparam) if kparam is not None else None
+    running them concurrently fills the machine) and the slot view is returned for autograd to adopt as `.grad`;
+    host.wgrad_placement has the exceptions."""
+    sink = WeightSink(kparam)
     backend = get_backend()
-    if view is None or not gout.is_cuda or not hasattr(backend, "side_stream"):
+    where = wgrad_placement(sink.adopted and gout.is_cuda and hasattr(backend, "side_stream"), feats.shape[1], gout.shape[1],
+                            gout.shape[0], getattr(kmap.mgr, "inline_wgrad", False))
+    if where == "plain":
         return kmap.conv_wgrad(feats, gout, transposed).reshape(kshape).to(kdtype)
-    if _DBG_WGRAD == "skip":
-        return view                                      # profiling knob: no weight gradient at all
-    # >= 256 x 256-channel layers: both the weight gradient (k_wgrad_wide / wide k_wgrad_ps) and the dgrad running beside it on the
-    # compute stream (k_conv_wide) are MFMA-bound kernels that own their CUs -- concurrently they halve each other (round 3, CLIP
-    # step: dgrad 17.5 ms in-step vs 9.2 alone, weight gradient 15.9 vs 7.7, and the 1x1 512 -> 544 dgrad next to them 11.6 vs
-    # 1.3 ms), so there is nothing to overlap: they run back to back on the compute stream
-    # (big maps only: the 256-channel layers of the coarse levels are latency-bound launches that DO overlap)
-    wide = _WIDE_WGRAD_INLINE and feats.shape[1] >= 256 and gout.shape[1] >= 256 and gout.shape[0] >= 65536
-    if _DBG_WGRAD == "inline" or wide or getattr(kmap.mgr, "inline_wgrad", False):
-        # small (host-bound) batches, wide layers, or the profiling knob: weight gradient on the compute stream
+    view, = sink.bufs
+    if where == "inline":
         kmap.conv_wgrad(feats, gout, transposed, out=view.view(kmap.K, -1, kshape[-1]))
-        return view
-    dev = gout.device
-    side = backend.side_stream(dev)
-    fork = backend.fork_event(dev)
-    fork.record(backend.current_stream(dev))             # feats / gout are ready
-    side.wait_event(fork)
-    kmap.conv_wgrad(feats, gout, transposed, out=view.view(kmap.K, -1, kshape[-1]), stream=side)
-    # one reusable event per parameter: BucketedDDP waits for exactly the weight gradients of the bucket it is about to
-    # reduce (ddp._wait_bucket_wgrads), not for the whole side stream
-    ev = getattr(kparam, "_lgs_wgrad_event", None)
-    if ev is None:
-        ev = kparam._lgs_wgrad_event = torch.cuda.Event()
-    ev.record(side)
-    note_side_wgrad(kparam)
-    feats.record_stream(side)
-    gout.record_stream(side)
-    return view                                          # consumers wait for the side stream in BucketedDDP
+    elif where == "side":
+        dev = gout.device
+        side = backend.side_stream(dev)
+        fork = backend.fork_event(dev)
+        fork.record(backend.current_stream(dev))             # feats / gout are ready
+        side.wait_event(fork)
+        kmap.conv_wgrad(feats, gout, transposed, out=view.view(kmap.K, -1, kshape[-1]), stream=side)
+        param_event(kparam).record(side)
+        side_wgrads_issued(side, (kparam,), (feats, gout))
+    return view                                              # consumers wait for the side stream in BucketedDDP
 
 
 def _bias_grad(gout):
@@ -312,48 +270,57 @@ class MinkowskiConvolutionTranspose(MinkowskiConvolutionBase):
 
 
 # ------------------------------------------------------------------------------------------ normalisation
-class FusedBatchNormFunction(torch.autograd.Function):
-    """y = relu?(BN(x) (+ residual)) with batch statistics, one engine call each way."""
+def bn_fwd(be, x, bn, g, b, residual, relu, conv_stats=None, sync=(False, None), out_into=None):
+    """training-mode y = relu?(BN(x) (+ residual)) of the nn.BatchNorm1d `bn` with affine g, b -> y, stats, inv_n.  sync = (True,
+    process group): the statistics are exchanged across the group's ranks (ddp.sync_bn_forward) and inv_n is the device scalar
+    1 / global rows, else None.  conv_stats: (partials, pivot) from the producing conv's epilogue; out_into: the _CatSlot y goes to."""
+    if conv_stats is not None and (conv_stats[1] is not None) != (bn.running_mean is not None):
+        conv_stats = None                                  # pivot convention mismatch (cannot happen for the conv's own bn)
+    out = (out_into.buf, out_into.off) if out_into is not None else None
+    if sync[0]:
+        from ..ddp import sync_bn_forward
+        return sync_bn_forward(be, x, g, b, residual, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps, bn.momentum,
+                               relu, sync[1], conv_stats, out)
+    nbt = bn.num_batches_tracked if be.bn_counts_batches else None        # (else the caller has counted the batch)
+    return be.bn_forward(x, g, b, bn.eps, bn.momentum, bn.running_mean, bn.running_var, residual, relu, nbt, conv_stats=conv_stats,
+                         out_into=out) + (None,)
+
+
+def bn_bwd(be, x, y, dy, g, b, gp, bp, stats, relu_mode, want_res, need, sync=(False, None), inv_n=None):
+    """-> dx, dres, d gamma, d beta: the last two as bucket-slot views when the parameters gp / bp own slots, else cast to g's dtype
+    (None when not `need`ed).  dy / y may be column slices of a concat buffer: the engine reads them in place."""
+    sink = AffineSink(gp, bp, x.shape[1], x.device)
+    if sync[0]:
+        from ..ddp import sync_bn_backward
+        dx, dres = sync_bn_backward(be, x, y, dy, g, b, stats, inv_n, relu_mode, want_res, sync[1], sink)
+    else:
+        dx, dres = be.bn_backward(x, y, dy, g, b, stats, relu_mode, want_res, *sink.bufs)[:2]
+    return (dx, dres) + sink.returned(g.dtype, need)
+
+
+class BatchNormFunction(torch.autograd.Function):
+    """y = relu?(BN(x) (+ residual)) with batch statistics -- of this rank, or of every rank of sync's process group -- as one
+    node around bn_fwd / bn_bwd (the whole-block node of me/block.py calls the same two functions)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, residual, running_mean, running_var, eps, momentum, relu, backend, nbt=None, conv_stats=None,
-                out_into=None):
+    def forward(ctx, x, gamma, beta, residual, bn, relu, backend, sync=(False, None), conv_stats=None, out_into=None):
+        y, stats, inv_n = bn_fwd(backend, x, bn, gamma, beta, residual, relu, conv_stats, sync, out_into)
         ctx.gparam = gamma if isinstance(gamma, torch.nn.Parameter) else None
         ctx.bparam = beta if isinstance(beta, torch.nn.Parameter) else None
-        if out_into is not None:       # _CatSlot: y goes straight into a column slice of the concat buffer (not a tensor input)
-            y, stats = backend.bn_forward(x, gamma, beta, eps, momentum, running_mean, running_var, residual, relu, nbt,
-                                          conv_stats=conv_stats, out_into=(out_into.buf, out_into.off))
-        elif conv_stats is not None:
-            y, stats = backend.bn_forward(x, gamma, beta, eps, momentum, running_mean, running_var, residual, relu, nbt,
-                                          conv_stats=conv_stats)
-        elif nbt is not None:
-            y, stats = backend.bn_forward(x, gamma, beta, eps, momentum, running_mean, running_var, residual, relu, nbt)
-        else:
-            y, stats = backend.bn_forward(x, gamma, beta, eps, momentum, running_mean, running_var, residual, relu)
-        # ReLU mask in the backward: recomputed from x when there is no residual (mode 2, y is not kept alive),
-        # taken from the saved output otherwise (mode 1)
-        ctx.backend, ctx.has_res = backend, residual is not None
-        ctx.relu_mode = 0 if not relu else (1 if residual is not None else 2)
-        if ctx.relu_mode == 1:
-            ctx.save_for_backward(x, gamma, beta, stats, y)
-        else:
-            ctx.save_for_backward(x, gamma, beta, stats)
+        ctx.backend, ctx.sync, ctx.has_res = backend, sync, residual is not None
+        ctx.relu_mode = relu_mode_of(relu, ctx.has_res)
+        saved = (x, gamma, beta, stats) + ((y,) if ctx.relu_mode == 1 else ()) + ((inv_n,) if inv_n is not None else ())
+        ctx.save_for_backward(*saved)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         saved = ctx.saved_tensors
-        x, gamma, beta, stats = saved[0], saved[1], saved[2], saved[3]
-        y = saved[4] if ctx.relu_mode == 1 else None
-        gview = grad_slot_view(ctx.gparam) if ctx.gparam is not None else None
-        bview = grad_slot_view(ctx.bparam) if ctx.bparam is not None else None
-        if gview is None or bview is None or not hasattr(ctx.backend, "side_stream"):
-            gview = bview = None
-        dx, dres, dgamma, dbeta = ctx.backend.bn_backward(x, y, dy, gamma, beta, stats, ctx.relu_mode,
-                                                          ctx.has_res and ctx.needs_input_grad[3], gview, bview)
-        if gview is not None:
-            return dx, gview, bview, dres, None, None, None, None, None, None, None, None, None
-        return dx, dgamma.to(gamma.dtype), dbeta.to(gamma.dtype), dres, None, None, None, None, None, None, None, None, None
+        x, gamma, beta, stats = saved[:4]
+        dx, dres, dgamma, dbeta = bn_bwd(ctx.backend, x, saved[4] if ctx.relu_mode == 1 else None, dy, gamma, beta, ctx.gparam,
+                                         ctx.bparam, stats, ctx.relu_mode, ctx.has_res and ctx.needs_input_grad[3], True, ctx.sync,
+                                         saved[-1] if ctx.sync[0] else None)
+        return dx, dgamma, dbeta, dres, None, None, None, None, None, None
 
 
 class _CatSlot:
@@ -366,6 +333,13 @@ class _CatSlot:
         self.buf, self.off, self.width = buf, off, width
 
 
+def _cat_buffer(x, left, right):
+    """a fresh [N, left + right] concat buffer in x's dtype whose two column halves the engine can address in place
+    (host.row_stride), or None"""
+    buf = torch.empty((x.shape[0], left + right), dtype=x.dtype, device=x.device)
+    return buf if row_stride(buf[:, :left], left) and row_stride(buf[:, left:], right) else None
+
+
 class EvalBatchNormFunction(torch.autograd.Function):
     """eval-mode BatchNorm (running statistics) (+ residual) (+ ReLU) on the engine's apply kernels: forward =
     lgs_bn_apply with stats = [running_mean | 1/sqrt(running_var + eps)]; backward (frozen statistics: fine-tuning with
@@ -375,7 +349,7 @@ class EvalBatchNormFunction(torch.autograd.Function):
     def forward(ctx, x, gamma, beta, residual, stats, relu, backend):
         y = backend.bn_apply(x, gamma, beta, stats, residual, relu)
         ctx.backend, ctx.has_res = backend, residual is not None
-        ctx.relu_mode = 0 if not relu else (1 if residual is not None else 2)
+        ctx.relu_mode = relu_mode_of(relu, ctx.has_res)
         ctx.save_for_backward(x, gamma, beta, stats, y if ctx.relu_mode == 1 else x.new_empty(0))
         return y
 
@@ -436,17 +410,10 @@ class MinkowskiBatchNorm(nn.Module):
         res = residual.F if isinstance(residual, SparseTensor) else residual
         fused = hasattr(backend, "bn_forward") and bn.affine and (bn.training or not bn.track_running_stats)
         if fused:
-            rm = bn.running_mean if bn.track_running_stats else None
-            rv = bn.running_var if bn.track_running_stats else None
-            nbt = bn.num_batches_tracked if bn.track_running_stats else None
-            if nbt is not None and not getattr(backend, "bn_counts_batches", False):
-                nbt += 1
-                nbt = None                                 # (the HIP engine increments it inside the fold kernel)
-            cs = input._bn_stats
-            if cs is not None and (cs[1] is not None) != (rm is not None):
-                cs = None                                  # pivot convention mismatch (cannot happen for the conv's own bn)
+            if bn.track_running_stats and not getattr(backend, "bn_counts_batches", False):
+                bn.num_batches_tracked += 1                # (the HIP engine increments it inside the fold kernel)
             slot = self._cat_slot_for(x, cat_up, cat_into, backend) if type(self) is MinkowskiBatchNorm else None
-            y = FusedBatchNormFunction.apply(x, bn.weight, bn.bias, res, rm, rv, bn.eps, bn.momentum, relu, backend, nbt, cs, slot)
+            y = BatchNormFunction.apply(x, bn.weight, bn.bias, res, bn, relu, backend, (False, None), input._bn_stats, slot)
             return y, slot
         elif hasattr(backend, "bn_apply") and bn.affine and bn.track_running_stats and x.is_cuda:
             # eval mode on the engine too (inference / validation passes, BN frozen during fine-tuning)
@@ -474,10 +441,10 @@ class MinkowskiBatchNorm(nn.Module):
         if not (getattr(backend, "bn_out_into", False) and x.is_cuda):
             return None
         c = x.shape[1]
-        al = 8 if x.dtype == torch.bfloat16 else 4
-        if cat_up > 0 and cat_up % al == 0 and c % al == 0:
-            buf = torch.empty((x.shape[0], cat_up + c), dtype=x.dtype, device=x.device)
-            return _CatSlot(buf, cat_up, c)
+        if cat_up > 0:
+            buf = _cat_buffer(x, cat_up, c)
+            if buf is not None:
+                return _CatSlot(buf, cat_up, c)
         if cat_into is not None:
             other = cat_into._cat_slot
             if other is not None:
@@ -488,10 +455,11 @@ class MinkowskiBatchNorm(nn.Module):
                 return None
             # the skip tensor exists already as an ordinary tensor: this norm writes the left-hand columns of a fresh concat
             # buffer, the skip half is copied in once (me/deferred.py _cat_partner)
-            if cat_into._op is None and c % al == 0:
+            if cat_into._op is None:
                 sf = cat_into._F
-                if (sf.is_cuda and sf.dim() == 2 and sf.shape[0] == x.shape[0] and sf.dtype == x.dtype and sf.shape[1] % al == 0):
-                    buf = torch.empty((x.shape[0], c + sf.shape[1]), dtype=x.dtype, device=x.device)
+                buf = _cat_buffer(x, c, sf.shape[1]) if (sf.is_cuda and sf.dim() == 2 and sf.shape[0] == x.shape[0]
+                                                         and sf.dtype == x.dtype) else None
+                if buf is not None:
                     with torch.no_grad():
                         buf[:, c:].copy_(sf)
                     slot = _CatSlot(buf, 0, c)
@@ -506,8 +474,8 @@ class MinkowskiBatchNorm(nn.Module):
 
 
 class MinkowskiSyncBatchNorm(MinkowskiBatchNorm):
-    """Cross-rank batch statistics (main.py:122-123) on the engine's split BN kernels (ddp._SyncBNFused): every rank
-    contributes one [mean | M2 | count] record to ONE all-gather per layer, the records are combined with Chan's
+    """Cross-rank batch statistics (main.py:122-123) on the engine's split BN kernels (ddp.sync_bn_forward / sync_bn_backward): every
+    rank contributes one [mean | M2 | count] record to ONE all-gather per layer, the records are combined with Chan's
     parallel formula in one kernel; backward exchanges [sum dy | sum dy xhat] with ONE all-reduce of 2C floats.
     `force_sync` (class attribute, tests only) takes the collective path even in a world of one rank."""
     force_sync = False

@@ -3,6 +3,7 @@ include/lgs_engine.h declares (no compute calls without a GPU), and the product 
 import ctypes
 import os
 import re
+import struct
 
 import pytest
 import torch
@@ -89,6 +90,41 @@ def test_ctypes_signatures_match_the_header_prototypes():
         got = [_ctype_kind(t) for t in f.argtypes]
         assert got == params, "%s: engine.py argtypes %s != header %s" % (name, got, params)
         assert _ctype_kind(f.restype) == ret, "%s: restype %s != header %s" % (name, _ctype_kind(f.restype), ret)
+
+
+def declared_struct(name):
+    """-> [(member, kind)] of `typedef struct name {...} name;` in the header; kinds: ptr / int / i64 / f32, or the type name of a
+    nested struct"""
+    txt = open(os.path.join(ROOT, "include", "lgs_engine.h")).read()
+    txt = re.sub(r"/\*.*?\*/", " ", txt, flags=re.S)
+    body = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), txt, flags=re.S).group(1)
+    members = []
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        base, rest = re.match(r"((?:const\s+)?\w+)\s+(.*)", decl, flags=re.S).groups()
+        base = base.replace("const", "").strip()
+        for item in rest.split(","):
+            item = item.strip()
+            kind = "ptr" if item.startswith("*") else {"int": "int", "int64_t": "i64", "float": "f32"}.get(base, base)
+            members.append((item.lstrip("* "), kind))
+    return members
+
+
+def test_ctypes_structs_match_the_header_structs():
+    """member names, order and kinds of the structs the host packs by position (the block arguments, their nested norm
+    parameters, the pack descriptor) against the header, and the struct-module formats derived from the ctypes classes against
+    the ctypes layouts: a member added on one side only shifts every later value of a positional pack_into"""
+    from languagegroundedsemseg_amd import engine
+    classes = {"lgs_bn_params": engine.BnParams, "lgs_block_fwd": engine.BlockFwd, "lgs_block_bwd": engine.BlockBwd,
+               "lgs_pack_desc": engine.PackDesc}
+    nested = {cls: name for name, cls in classes.items()}
+    for name, cls in classes.items():
+        got = [(f, nested[t] if t in nested else _ctype_kind(t)) for f, t in cls._fields_]
+        assert got == declared_struct(name), name
+    assert [len(c._fields_) for c in classes.values()] == [7, 31, 58, 14]
+    for cls, packer in ((engine.BlockFwd, engine.BLOCK_FWD_PACK), (engine.BlockBwd, engine.BLOCK_BWD_PACK)):
+        assert packer.format == "@" + engine.struct_format(cls) and packer.size == ctypes.sizeof(cls)
+    for cls in classes.values():
+        assert struct.calcsize("@" + engine.struct_format(cls)) == ctypes.sizeof(cls), cls
 
 
 def test_integration_stub_signatures_match_the_header():

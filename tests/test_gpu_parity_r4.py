@@ -241,6 +241,61 @@ def test_c_side_block_equals_the_call_by_call_block(monkeypatch, dtype, with_ddp
                 assert torch.equal(ba[k], bb[k]), (name, k)
 
 
+def test_block_gradients_accumulate_through_declined_slots(monkeypatch):
+    """Gradient accumulation over two micro-batches: the first backward (inside no_sync) writes every parameter gradient into its
+    bucket slot, the second finds `.grad` set, so every sink declines the slot, the engine writes fp32 scratch and autograd adds.
+    The one-call block, the call-by-call block node and the op-by-op modules must agree bit for bit on every gradient and buffer,
+    and each accumulated gradient is g_A + g_B of the micro-batches alone (one fp32 add per leaf).  Res16UNet14A has blocks with
+    and without the 1x1 branch.  Reference: /root/reference/models/modules/resnet_block.py:41-57."""
+    from languagegroundedsemseg_amd import models
+    from languagegroundedsemseg_amd.ddp import BucketedDDP
+    from languagegroundedsemseg_amd.losses import fused_cross_entropy
+    from languagegroundedsemseg_amd.me import block as _block
+    from languagegroundedsemseg_amd.synthetic import make_batch
+    coords, feats, labels = make_batch([5], voxel=0.05, n_target=4000)
+    c = torch.from_numpy(coords).to(DEV)
+    fa = torch.from_numpy(feats).to(DEV).to(torch.bfloat16)
+    la = torch.from_numpy(labels % 20).to(DEV)
+    micro = {"A": (fa, la), "B": (fa.flip(0).contiguous(), la.roll(7))}
+    be = ME.get_backend()
+
+    def run(seq, block_c=True, block_fused=True):
+        """-> gradients, buffers, engine block calls per BasicBlock after zero_grad() and the micro-batches of `seq`, all but the
+        last inside no_sync()"""
+        monkeypatch.setattr(_block, "_BLOCK_C", block_c)
+        monkeypatch.setattr(_block, "_BLOCK_FUSED", block_fused)
+        m = deterministic_init(models.load_model("Res16UNet14A")(3, 20, Cfg()), 11).to(DEV).train()
+        ddp = BucketedDDP(m, bucket_mb=1.0)
+        calls0 = getattr(be, "block_calls", 0)
+        ddp.zero_grad()
+        for i, k in enumerate(seq):
+            f, l = micro[k]
+            if i + 1 < len(seq):
+                with ddp.no_sync():
+                    fused_cross_entropy(m(ME.SparseTensor(f, c))[0].F, l, ignore_index=-1).backward()
+            else:
+                fused_cross_entropy(m(ME.SparseTensor(f, c))[0].F, l, ignore_index=-1).backward()
+        ddp.finalize()
+        torch.cuda.synchronize()
+        n_blocks = sum(1 for mod in m.modules() if isinstance(mod, models.BasicBlock))
+        return ({k: p.grad.detach().clone() for k, p in m.named_parameters() if p.grad is not None},
+                {k: b.detach().clone() for k, b in m.named_buffers()}, (getattr(be, "block_calls", 0) - calls0) / n_blocks)
+
+    g, b, calls = run("AB")
+    assert calls == 4 and len(g) > 50                        # one engine call per block, direction and micro-batch
+    for kw in (dict(block_c=False), dict(block_fused=False)):
+        g2, b2, calls2 = run("AB", **kw)
+        assert calls2 == 0 and set(g2) == set(g) and set(b2) == set(b)
+        for k in g:
+            assert torch.equal(g[k], g2[k]), (kw, k)
+        for k in b:
+            assert torch.equal(b[k], b2[k]), (kw, k)
+    (ga, _, _), (gb, _, _) = run("A"), run("B")
+    assert set(ga) == set(gb) == set(g)
+    for k in g:
+        assert torch.equal(g[k], ga[k] + gb[k]), k
+
+
 @pytest.mark.gpu
 @pytest.mark.parity("plain torch restatement")
 @pytest.mark.parametrize("n,c,ignore", [(100003, 200, -1), (4097, 20, 255), (1, 13, -1), (70001, 200, 7)])

@@ -304,7 +304,7 @@ def test_live_map_knob_toggles_resize_the_workspace(scenes):
                     fresh = L.lgs_conv_workspace_bytes(km.h, case["cin"], case["cout"], dt, op)
                     assert cached == fresh, (label, knobs, op, cached, fresh)
                 ME.get_backend()._block_ws(L, km, None, case["cin"], case["cout"], dt, 16, torch.device(DEV))
-                assert km._wsb[("cblk_ws", case["cin"], case["cout"], dt, engine.TUNING_EPOCH)] == \
+                assert km.block_ws_bytes(L, None, case["cin"], case["cout"], dt) == \
                     L.lgs_block_workspace_bytes(km.h, None, case["cin"], case["cout"], dt), (label, knobs)
             for r in reps:
                 print(label, knobs, P.fmt(r))
