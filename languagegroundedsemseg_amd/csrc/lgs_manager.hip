@@ -512,6 +512,121 @@ __global__ void k_permute_map3(const int32_t *nbr_tmp, const uint32_t *pmask, co
   }
   if ((threadIdx.x & 63) == 0) mask64[q >> 6] = m;
 }
+// MAP_PERMUTE_LDS: the same tables with the gathers taken from LDS.  perm[q] stays inside q's window (the sort is per window), so the
+// rows a window gathers from nbr_tmp[k] are ONE contiguous segment of at most 4 x window bytes: workgroup (w, g) keeps the window's
+// slice of perm in registers (as indices into the segment), and for each of its offsets k in [g kg, g kg + kg) stages the segment
+// with 16-byte loads -- the next offset's loads are issued into registers before the current one is gathered -- reads LDS at the
+// permuted index and writes nbr[k] coalesced.  Group 0 also stages pmask and `order` the same way for mask64 and out_row.
+// A thread owns quads of four consecutive positions, so perm, the staged rows and the tables all move as 16-byte accesses and only
+// the LDS reads are single words.  window is a multiple of 256 (so is n_pad): a group of 64 positions lies in one window.
+constexpr int kPlThreads = 1024, kPlMaxWindow = 32768;
+__device__ __forceinline__ int pl_clamp(int l, int len) { return l < 0 ? 0 : (l >= len ? len - 1 : l); }
+typedef int pl_v4 __attribute__((ext_vector_type(4)));   // a plain 16-byte vector: arrays of it stay in registers
+template <int Q>   // the nq 16-byte pieces of a window's segment of one row: global memory -> registers -> LDS
+__device__ __forceinline__ void pl_load(pl_v4 (&pre)[Q], const int32_t *seg, int nq, int t) {
+  const pl_v4 *src = reinterpret_cast<const pl_v4 *>(seg);
+#pragma unroll
+  for (int j = 0; j < Q; ++j) pre[j] = src[j * kPlThreads + t < nq ? j * kPlThreads + t : t & 63];   // unconditional: nq >= 64
+}
+template <int Q>
+__device__ __forceinline__ void pl_store(const pl_v4 (&pre)[Q], int32_t *lds, int nq, int t) {
+  pl_v4 *lds4 = reinterpret_cast<pl_v4 *>(lds);
+#pragma unroll
+  for (int j = 0; j < Q; ++j)
+    if (j * kPlThreads + t < nq) lds4[j * kPlThreads + t] = pre[j];
+}
+__device__ __forceinline__ int4 pl_gather(const int32_t *lds, int4 l, int none) {
+  return make_int4(l.x >= 0 ? lds[l.x] : none, l.y >= 0 ? lds[l.y] : none, l.z >= 0 ? lds[l.z] : none, l.w >= 0 ? lds[l.w] : none);
+}
+template <int IPT>   // positions per thread: window <= IPT * kPlThreads
+__global__ __launch_bounds__(kPlThreads) void k_permute_map3_lds(const int32_t *__restrict__ nbr_tmp, const uint32_t *__restrict__ pmask,
+                                                                 const int32_t *__restrict__ perm, const int32_t *__restrict__ order, int64_t n,
+                                                                 int64_t n_pad, int window, int kg, int32_t *__restrict__ nbr,
+                                                                 int32_t *__restrict__ out_row, uint32_t *__restrict__ mask64) {
+  extern __shared__ int32_t pl_lds[];    // [min(window, n_pad)]
+  constexpr int Q = IPT / 4;             // a thread owns Q quads of four consecutive positions: quad j * kPlThreads + t of the window
+  const int t = threadIdx.x;
+  const int64_t w0 = (int64_t)blockIdx.x * window;
+  const int len = (int)(n_pad - w0 < (int64_t)window ? n_pad - w0 : (int64_t)window);   // positions of this window: a multiple of 256
+  const int nq = len >> 2;
+  const int live = (int)(n - w0 < (int64_t)len ? n - w0 : (int64_t)len);                // ... of which the first `live` are rows
+  int4 loc[Q];                           // perm[q] - w0, or -1 for a padding position
+  {
+    const int4 *src = reinterpret_cast<const int4 *>(perm + w0);   // perm has n_pad entries
+    const int w0i = (int)w0;
+#pragma unroll
+    for (int j = 0; j < Q; ++j) {
+      const int qd = j * kPlThreads + t;
+      int4 l = make_int4(-1, -1, -1, -1);
+      if (qd < nq) {
+        const int4 p = src[qd];
+        // a correct permutation is inside the window; nothing else may index the LDS
+        l.x = 4 * qd + 0 < live ? pl_clamp(p.x - w0i, len) : -1;
+        l.y = 4 * qd + 1 < live ? pl_clamp(p.y - w0i, len) : -1;
+        l.z = 4 * qd + 2 < live ? pl_clamp(p.z - w0i, len) : -1;
+        l.w = 4 * qd + 3 < live ? pl_clamp(p.w - w0i, len) : -1;
+      }
+      loc[j] = l;
+    }
+  }
+  pl_v4 pre[Q];
+  const int k0 = blockIdx.y * kg, k1 = k0 + kg < 27 ? k0 + kg : 27;
+  if (blockIdx.y == 0) {
+    pl_load<Q>(pre, reinterpret_cast<const int32_t *>(pmask) + w0, nq, t);   // pmask has n_pad entries
+    pl_store<Q>(pre, pl_lds, nq, t);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < Q; ++j) {
+      const int qd = j * kPlThreads + t;   // 64 consecutive quads per wave, nq a multiple of 64: a wave is inside or outside as a whole
+      const int4 pm = pl_gather(pl_lds, loc[j], 0);
+      uint32_t m = (uint32_t)(pm.x | pm.y | pm.z | pm.w);   // an offset is in the group's mask if any of its 64 positions has it: 16 lanes
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) m |= (uint32_t)__shfl_xor((int)m, o, 64);
+      if (qd < nq && (t & 15) == 0) mask64[(w0 + 4 * qd) >> 6] = m;
+    }
+    __syncthreads();
+    if (order) {                           // `order` has n entries, not n_pad
+#pragma unroll
+      for (int j = 0; j < Q; ++j) {
+        const int qd = j * kPlThreads + t;
+        if (qd >= nq) continue;
+        int4 v = make_int4(-1, -1, -1, -1);
+        if (4 * qd + 3 < live) v = reinterpret_cast<const int4 *>(order + w0)[qd];
+        else if (4 * qd < live) {
+          v.x = order[w0 + 4 * qd];
+          if (4 * qd + 1 < live) v.y = order[w0 + 4 * qd + 1];
+          if (4 * qd + 2 < live) v.z = order[w0 + 4 * qd + 2];
+        }
+        reinterpret_cast<int4 *>(pl_lds)[qd] = v;
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < Q; ++j) {
+      const int qd = j * kPlThreads + t;
+      if (qd >= nq) continue;
+      const int4 l = loc[j];
+      const int w0i = (int)w0;
+      const int4 v = order ? pl_gather(pl_lds, l, -1)
+                           : make_int4(l.x >= 0 ? w0i + l.x : -1, l.y >= 0 ? w0i + l.y : -1, l.z >= 0 ? w0i + l.z : -1, l.w >= 0 ? w0i + l.w : -1);
+      reinterpret_cast<int4 *>(out_row + w0)[qd] = v;
+    }
+    __syncthreads();
+  }
+  pl_load<Q>(pre, nbr_tmp + (int64_t)k0 * n_pad + w0, nq, t);
+  for (int k = k0; k < k1; ++k) {
+    pl_store<Q>(pre, pl_lds, nq, t);
+    __syncthreads();
+    if (k + 1 < k1) pl_load<Q>(pre, nbr_tmp + (int64_t)(k + 1) * n_pad + w0, nq, t);
+    int4 *dst = reinterpret_cast<int4 *>(nbr + (int64_t)k * n_pad + w0);
+#pragma unroll
+    for (int j = 0; j < Q; ++j) {
+      const int qd = j * kPlThreads + t;
+      if (qd < nq) dst[qd] = pl_gather(pl_lds, loc[j], -1);
+    }
+    __syncthreads();
+  }
+}
 
 // 3x3x3 stride-2, fine-stationary view (dgrad of the strided conv, forward of its transposed conv): slot k of fine position p holds
 // the coarse row at c_fine - off_k * ts.  That coordinate lies on the coarse grid only where, on every axis, off_k is 0 for an even
@@ -658,6 +773,102 @@ __global__ void k_build_map2_fine(const uint32_t *kk_sorted, const int32_t *pp_s
   g_nbr[slot] = fine_cidx[p];
   g_out[slot] = forder ? forder[p] : p;
   if (((s - gsrc[k]) & (kGroup - 1)) == 0) tile_k[slot >> 6] = k;
+}
+// MAP_OWN_SORTS: the same grouped view without the radix sort.  Sorting the positions by their 3-bit child index, stably, is an
+// 8-way partition: position p of child k lands at goff[k] + (the number of earlier positions with child k).  Three plain launches:
+// per-workgroup counts of the eight children over chunks of 256 x rounds positions; ONE workgroup that turns the counts of each child
+// into exclusive prefixes over the chunks (a wave per child) and writes the group starts k_group_offsets made; and a pass that
+// ranks the positions of its chunk (ballots inside a wave, counts of the waves before it through LDS) and writes g_nbr, g_out and
+// tile_k directly -- neither the (child, position) pairs nor their sorted copies exist.
+constexpr int kCpMaxRounds = 16;  // a workgroup walks its chunk in rounds of 256 positions (child_rounds)
+__global__ __launch_bounds__(256) void k_child_hist(const uint64_t *__restrict__ fkeys, int64_t n, int shift, int rounds, int32_t nwg,
+                                                    int32_t *__restrict__ wg_cnt /*[8][nwg]*/) {
+  __shared__ int32_t h[8];
+  if (threadIdx.x < 8) h[threadIdx.x] = 0;
+  __syncthreads();
+  int32_t c[8];
+#pragma unroll
+  for (int b = 0; b < 8; ++b) c[b] = 0;
+  const int64_t base = (int64_t)blockIdx.x * 256 * rounds;
+  for (int i = 0; i < rounds; ++i) {
+    const int64_t p = base + i * 256 + threadIdx.x;
+    if (p >= n) break;
+    const int k = (int)((fkeys[p] >> shift) & 7);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) c[b] += k == b ? 1 : 0;
+  }
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    int32_t v = c[b];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(&h[b], v);
+  }
+  __syncthreads();
+  if (threadIdx.x < 8) wg_cnt[(int64_t)threadIdx.x * nwg + blockIdx.x] = h[threadIdx.x];
+}
+__global__ __launch_bounds__(512) void k_child_prefix(int32_t *wg_cnt /*[8][nwg]: counts in, exclusive prefixes out*/, int32_t nwg,
+                                                      int32_t *goff /*[9] padded starts*/, int32_t *gsrc /*[9] plain starts*/) {
+  __shared__ int32_t tot[8];
+  const int b = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  int32_t *row = wg_cnt + (int64_t)b * nwg;
+  int32_t carry = 0;
+  for (int32_t w0 = 0; w0 < nwg; w0 += 64) {
+    const int32_t w = w0 + lane;
+    const int32_t v = w < nwg ? row[w] : 0;
+    int32_t inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int32_t u = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += u;
+    }
+    if (w < nwg) row[w] = carry + inc - v;
+    carry += __shfl(inc, 63, 64);
+  }
+  if (lane == 0) tot[b] = carry;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int32_t a = 0, s = 0;
+    for (int k = 0; k < 8; ++k) {
+      goff[k] = a; gsrc[k] = s;
+      a += (tot[k] + kPadRows - 1) / kPadRows * kPadRows;
+      s += tot[k];
+    }
+    goff[8] = a; gsrc[8] = s;
+  }
+}
+__global__ __launch_bounds__(256) void k_child_scatter(const uint64_t *__restrict__ fkeys, int64_t n, int shift, int rounds, int32_t nwg,
+                                                       const int32_t *__restrict__ wg_off, const int32_t *__restrict__ goff,
+                                                       const int32_t *__restrict__ fine_cidx, const int32_t *__restrict__ forder,
+                                                       int32_t *__restrict__ g_nbr, int32_t *__restrict__ g_out, int32_t *__restrict__ tile_k) {
+  __shared__ int32_t run[8], start[8];   // positions of each child before the current round (in this child's group); the group's first slot
+  __shared__ int32_t wcnt[2][4][8];      // [round & 1][wave][child]: the round after next reuses a buffer, two barriers later
+  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  if (t < 8) { run[t] = wg_off[(int64_t)t * nwg + blockIdx.x]; start[t] = goff[t]; }
+  const int64_t base = (int64_t)blockIdx.x * 256 * rounds;
+  for (int i = 0; i < rounds && base + i * 256 < n; ++i) {   // the bound is the same for the whole workgroup
+    const int64_t p = base + i * 256 + t;
+    const int k = p < n ? (int)((fkeys[p] >> shift) & 7) : 8;
+    int32_t before = 0, mine = 0;
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      const unsigned long long bal = __ballot(k == b);
+      if (k == b) before = __popcll(bal & ((1ull << lane) - 1ull));
+      if (lane == b) mine = __popcll(bal);
+    }
+    if (lane < 8) wcnt[i & 1][wave][lane] = mine;
+    __syncthreads();
+    if (k < 8) {
+      int32_t r = run[k] + before;
+      for (int w = 0; w < wave; ++w) r += wcnt[i & 1][w][k];
+      const int32_t slot = start[k] + r;
+      g_nbr[slot] = fine_cidx[p];
+      g_out[slot] = forder ? forder[p] : (int32_t)p;
+      if ((r & (kGroup - 1)) == 0) tile_k[slot >> 6] = k;
+    }
+    __syncthreads();
+    if (t < 8) run[t] += wcnt[i & 1][0][t] + wcnt[i & 1][1][t] + wcnt[i & 1][2][t] + wcnt[i & 1][3][t];
+  }
 }
 
 // export helpers (parity tests): count pairs of a view then write (k, in, out) triples
@@ -1064,6 +1275,42 @@ int window_perm(lgs_manager *m, int64_t n, int64_t n_pad, const uint32_t *pmask,
   return dfree_now(m, keys, s) || dfree_now(m, skeys2, s) || dfree_now(m, vals, s);
 }
 
+// the permutation of (nbr_tmp, pmask) into the view's arrays.  MAP_PERMUTE_LDS: through LDS (k_permute_map3_lds) where a window's
+// row segment fits it and windows are whole groups of 256 positions; else, and with the knob at 0, k_permute_map3
+// Offsets per workgroup (MAP_PERMUTE_GROUP): a workgroup walks its offsets one after the other and a CU holds two workgroups, so
+// a small map wants one offset per workgroup to fill the chip at all, and a large one as many as still leave the grid above
+// kPlWorkgroups -- every offset group reads the window's perm again
+constexpr int kPlWorkgroups = 640;
+inline int permute_group(int64_t windows) {
+  const int64_t g = tune(T_MAP_PERMUTE_GROUP);
+  if (g >= 1 && g <= 27) return (int)g;
+  const int64_t kg = 27 * windows / (g > 27 ? g : kPlWorkgroups);
+  return (int)(kg < 1 ? 1 : (kg > 27 ? 27 : kg));
+}
+int permute_rows(const CoordMap &st, const int32_t *nbr_tmp, const uint32_t *pmask, const int32_t *perm, hipStream_t s, int32_t *nbr,
+                 int32_t *orow, uint32_t *mask) {
+  const int64_t window = tune(T_MASK_WINDOW), knob = tune(T_MAP_PERMUTE_LDS);
+  if (knob <= 0 || window <= 0 || window > kPlMaxWindow || window % 256 != 0) {
+    LGS_KLAUNCH(k_permute_map3, (unsigned)(st.n_pad / 256), 256, 0, s, nbr_tmp, pmask, perm, st.order, st.n, st.n_pad, nbr, orow, mask);
+    return 0;
+  }
+  static bool attr_set = false;
+  if (!attr_set) {
+    LGS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_permute_map3_lds<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 16 * kPlThreads * 4));
+    LGS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_permute_map3_lds<32>), hipFuncAttributeMaxDynamicSharedMemorySize, kPlMaxWindow * 4));
+    attr_set = true;
+  }
+  const int64_t windows = (st.n_pad + window - 1) / window;
+  const int kg = permute_group(windows);
+  const dim3 grid((unsigned)windows, (unsigned)((27 + kg - 1) / kg));
+  const size_t lds = (size_t)(st.n_pad < window ? st.n_pad : window) * sizeof(int32_t);
+  if (window <= 16 * kPlThreads)
+    LGS_KLAUNCH(k_permute_map3_lds<16>, grid, kPlThreads, lds, s, nbr_tmp, pmask, perm, st.order, st.n, st.n_pad, (int)window, kg, nbr, orow, mask);
+  else
+    LGS_KLAUNCH(k_permute_map3_lds<32>, grid, kPlThreads, lds, s, nbr_tmp, pmask, perm, st.order, st.n, st.n_pad, (int)window, kg, nbr, orow, mask);
+  return 0;
+}
+
 // a 27-slot view over the rows of map `st` (the stationary side): table built by `build` into (nbr_tmp, pmask), then the window sort
 template <typename Build>
 int make_view27(lgs_manager *m, const CoordMap &st, int64_t n_in, hipStream_t s, View &v, Build &&build) {
@@ -1076,7 +1323,7 @@ int make_view27(lgs_manager *m, const CoordMap &st, int64_t n_in, hipStream_t s,
     return 1;
   if (build(nbr_tmp, pmask)) return 1;
   if (window_perm(m, st.n, st.n_pad, pmask, perm, s)) return 1;
-  LGS_KLAUNCH(k_permute_map3, (unsigned)(st.n_pad / 256), 256, 0, s, nbr_tmp, pmask, perm, st.order, st.n, st.n_pad, nbr, orow, mask);
+  if (permute_rows(st, nbr_tmp, pmask, perm, s, nbr, orow, mask)) return 1;
   LGS_HIP(hipGetLastError());
   if (dfree_now(m, nbr_tmp, s) || dfree_now(m, pmask, s) || dfree_now(m, perm, s)) return 1;
   v.nbr = nbr; v.mask64 = mask; v.out_row = orow;
@@ -1114,6 +1361,17 @@ int build_conv3(lgs_manager *m, CoordMap &ci, int dilation, hipStream_t s, lgs_k
   return 0;
 }
 
+// MAP_OWN_SORTS: rounds of 256 positions per workgroup of k_child_hist / k_child_scatter (MAP_CHILD_ROUNDS).  A round costs the
+// workgroup two barriers and a dependent load, so a small map takes one round per workgroup and a large one as many as still leave
+// kCpWorkgroups workgroups -- the prefix kernel is one workgroup and walks them all
+constexpr int kCpWorkgroups = 512;
+inline int child_rounds(int64_t n) {
+  const int64_t k = tune(T_MAP_CHILD_ROUNDS);
+  if (k >= 1) return (int)(k > kCpMaxRounds ? kCpMaxRounds : k);
+  const int64_t r = (n + 255) / 256 / kCpWorkgroups;
+  return (int)(r < 1 ? 1 : (r > kCpMaxRounds ? kCpMaxRounds : r));
+}
+
 // 2^3 stride 2: the children of a coarse row are one run of the fine Morton order
 int build_conv2_s2(lgs_manager *m, const CoordMap &ci, const CoordMap &co, hipStream_t s, lgs_kmap *km) {
   int shift = 3 * ci.log2ts;
@@ -1128,6 +1386,23 @@ int build_conv2_s2(lgs_manager *m, const CoordMap &ci, const CoordMap &co, hipSt
     vf.nbr = nbr8; vf.mask64 = mask;
     // grouped fine view
     int64_t n = ci.n, gp = pad_rows(n + 8 * kPadRows);
+    if (tune(T_MAP_OWN_SORTS) != 0) {   // the stable 8-way partition (k_child_hist)
+      const int rounds = child_rounds(n);
+      const int32_t nwg = (int32_t)((n + 256 * rounds - 1) / (256 * rounds));
+      int32_t *wg, *goff, *gsrc, *g_nbr, *g_out, *tile_k;
+      if (dalloc(m, &g_nbr, gp, s) || dalloc(m, &g_out, gp, s) || dalloc(m, &tile_k, gp / kGroup, s) || dalloc(m, &wg, 8 * (int64_t)nwg, s) ||
+          dalloc(m, &goff, 9, s) || dalloc(m, &gsrc, 9, s))
+        return 1;
+      if (fill_segs(s, {{g_nbr, gp, -1}, {g_out, gp, -1}, {tile_k, gp / kGroup, -1}})) return 1;
+      LGS_KLAUNCH(k_child_hist, (unsigned)nwg, 256, 0, s, ci.skeys, n, shift, rounds, nwg, wg);
+      LGS_KLAUNCH(k_child_prefix, 1, 512, 0, s, wg, nwg, goff, gsrc);
+      LGS_KLAUNCH(k_child_scatter, (unsigned)nwg, 256, 0, s, ci.skeys, n, shift, rounds, nwg, wg, goff, co.fine_cidx, ci.order, g_nbr, g_out, tile_k);
+      LGS_HIP(hipGetLastError());
+      vb.nbr = g_nbr; vb.out_row = g_out; vb.tile_k = tile_k; vb.n_pad = gp;
+      if (dfree_now(m, wg, s) || dfree_now(m, goff, s) || dfree_now(m, gsrc, s)) return 1;
+      km->fwd = vf; km->bwd = vb;
+      return 0;
+    }
     uint32_t *kk, *kks; int32_t *pp, *pps, *cnt, *goff, *gsrc, *g_nbr, *g_out, *tile_k;
     if (dalloc(m, &kk, n, s) || dalloc(m, &kks, n, s) || dalloc(m, &pp, n, s) || dalloc(m, &pps, n, s) ||
         dalloc(m, &cnt, 8, s) || dalloc(m, &goff, 9, s) || dalloc(m, &gsrc, 9, s) || dalloc(m, &g_nbr, gp, s) ||

@@ -94,6 +94,23 @@ const Knob kKnobs[T_COUNT] = {
     {T_MAP_BLOCK_DIR, "MAP_BLOCK_DIR", 1, "3^3 maps, neighbour lookup (A/B): 1 = a directory with one entry per occupied 4 x 4 x 4 block of cells {block id, first "
                                           "sorted position, 64-bit occupancy}; a probe is one entry and a popcount; 0 = the open-addressing hash with one slot "
                                           "per voxel (>= 2 n slots of 12 bytes).  The tables are identical"},
+    {T_MAP_PERMUTE_LDS, "MAP_PERMUTE_LDS", 1, "3^3 maps, the row permutation after the window sort (A/B): 1 = k_permute_map3_lds, one workgroup per (MASK_WINDOW "
+                                              "positions, group of offsets) stages the window's segment of every offset row in LDS with 16-byte loads and "
+                                              "gathers from there; 0 = k_permute_map3, 27 four-byte gathers per position from global memory.  A window "
+                                              "above 32768 positions or no multiple of 256 takes k_permute_map3 either way.  The tables are identical.  "
+                                              "Five maps of the 8-scene batch: 352 -> 90 us, all maps 1.86 -> 1.61 ms (profiles/map_stream.txt)"},
+    {T_MAP_PERMUTE_GROUP, "MAP_PERMUTE_GROUP", 0, "k_permute_map3_lds: offsets per workgroup (the grid against the re-reads of the permutation).  0 = as many as "
+                                                  "leave 640 workgroups (8-scene batch: 3 at level 0, 1 on the coarser maps); 1 .. 27 = that many on every "
+                                                  "map; above 27 = as 0 with that many workgroups as the aim.  All maps: 1.61 ms at 0, 1, 2, 3 and at 320 / "
+                                                  "1280 workgroups, 1.62 at 5, 1.65 at 9 -- flat wherever level 0 has at least ~600 workgroups"},
+    {T_MAP_OWN_SORTS, "MAP_OWN_SORTS", 1, "2^3 stride-2 maps, grouping the fine rows by child index (A/B): 1 = a stable 8-way partition in three launches "
+                                          "(k_child_hist per-workgroup counts, k_child_prefix one workgroup, k_child_scatter writes the grouped view "
+                                          "itself); 0 = k_child_keys, rocPRIM's radix sort on 3 key bits, k_group_offsets, k_build_map2_fine.  The "
+                                          "tables are identical.  Four maps of the 8-scene batch: 378 us in 57 launches -> 130 us in 12, all maps "
+                                          "1.86 -> 1.61 ms (profiles/map_stream.txt)"},
+    {T_MAP_CHILD_ROUNDS, "MAP_CHILD_ROUNDS", 0, "k_child_hist / k_child_scatter: rounds of 256 positions per workgroup (two barriers and a dependent load each).  "
+                                                "0 = as many as leave 512 workgroups, between 1 and 16 (8-scene batch: 9 at level 0, 2 at level 1, 1 below); "
+                                                "1 .. 16 = that many on every map (tests walk several rounds on small maps with it)"},
 };
 std::atomic<int64_t> g_val[T_COUNT];
 std::once_flag g_once;
