@@ -239,7 +239,9 @@ template <> __device__ inline float sq16<bf16_t>(const u32x4 &f, float s) {
 
 // ------------------------------------------------------------------------------------ forward / dgrad
 // Tile: WM x WN waves; each wave owns RB*32 positions x NCB*32 output channels.
-template <typename T, int RB, int NCB, int WM, int WN, int SC, int D, int EPI = 0>
+// SCL = chunks FETCHED AND STAGED per slab (see below); ROW1 = the gathered rows are one 16-byte piece wide (conv0's padded
+// colour rows): only the t = 0 gather is issued, the fragments of the pieces beyond the row are zero registers.
+template <typename T, int RB, int NCB, int WM, int WN, int SC, int D, int EPI = 0, int SCL = SC, bool ROW1 = false>
 __global__ __launch_bounds__(WM *WN * 64) void k_conv_gather(View v, const T *__restrict__ in, int cin_real, int nc,
                                                              const u32x4 *__restrict__ wp, int nb_total,
                                                              int ncp, int nbp,
@@ -254,14 +256,21 @@ __global__ __launch_bounds__(WM *WN * 64) void k_conv_gather(View v, const T *__
   // and one barrier separates slabs, while the gathered feature fragments stream chunk by chunk through a
   // D-deep register ring (loads issued D-1 chunks = several hundred MFMA cycles ahead of their use) that runs
   // across slab and offset boundaries.
+  // SC is the slab length of the packed IMAGE (plan_image() rounds the chunks of an offset up to whole SC-chunk slabs, zero
+  // filled); SCL is the slab length this instance WALKS it with.  The image is chunk-major -- chunk c of offset kw starts at
+  // (kw * ncp + c) * nbp * WLD * 64 -- so any SCL that divides nc reads exactly the real chunks and never the zero padding
+  // (launch_gather picks it; SCL = SC is the walk of the image's own slabs, padding included).
+  static_assert(SCL >= 1 && (EPI == 0 || SCL == SC), "the CLIP epilogue parks its similarity tile in the weight LDS of the image's own slabs");
+  static_assert(!ROW1 || EPI == 0, "the one-piece row is a convolution input");
   constexpr int EPL = Tr<T>::EPL, LD = Tr<T>::LD, WLD = Tr<T>::WLD;
   constexpr int NT = WM * WN * 64;
   constexpr int TM = WM * RB * 32;
   constexpr int WB = WN * NCB;                 // weight blocks per chunk
   constexpr int WCH = WB * WLD * 64;           // uint4 per chunk
-  constexpr int SLAB = SC * WCH;               // uint4 per slab
+  constexpr int SLAB = SCL * WCH;              // uint4 per slab
   constexpr int WR = (SLAB + NT - 1) / NT;     // staging registers per thread
   __shared__ u32x4 lds[2][SLAB];
+  static_assert(EPI != 0 || WM * 2 * WB * 32 * 4 <= 2 * SLAB * 16, "the statistics epilogue folds the waves through the weight LDS");
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
@@ -374,12 +383,13 @@ __global__ __launch_bounds__(WM *WN * 64) void k_conv_gather(View v, const T *__
       for (int t = 0; t < LD; ++t) {
         unsigned off = base + t * 16;
         if (ch_tail && (ichunk * 32 + h * 16 + t * EPL + EPL > cin_real)) off = kOOB;
-        F[rb][t] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, off, 0, 0);
+        if (ROW1 && t > 0) F[rb][t] = u32x4{0u, 0u, 0u, 0u};     // beyond the row in every lane: no instruction for it
+        else F[rb][t] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, off, 0, 0);
       }
     }
   };
   // ---- weight-side iterator: (slot, slab) in the same order
-  const int nslab = (nc + SC - 1) / SC, gs = (gc + SC - 1) / SC;   // slabs per channel group (gc is a multiple of SC or = nc)
+  const int nslab = (nc + SCL - 1) / SCL, gs = (gc + SCL - 1) / SCL;   // slabs per channel group (gc is a multiple of SCL or = nc)
   uint32_t wrem = smask;
   int wslot = -1, wgbase = 0, wgend = min(gs, nslab), wslab = wgend;
   auto wadvance = [&]() __attribute__((always_inline)) -> bool {
@@ -397,7 +407,7 @@ __global__ __launch_bounds__(WM *WN * 64) void k_conv_gather(View v, const T *__
   };
   // The packed weights are padded to whole slabs (ncp chunks) and whole cout tiles (nbp blocks), zero filled, so a
   // slab is fetched with unconditional, fully coalesced 16-byte buffer loads: per-thread offsets are loop invariant,
-  // the slab's base goes in the scalar offset.
+  // the slab's base goes in the scalar offset.  (With SCL < SC the last slab read ends at chunk nc - 1 <= ncp - 1.)
   unsigned woff[WR];
 #pragma unroll
   for (int i = 0; i < WR; ++i) {
@@ -407,7 +417,7 @@ __global__ __launch_bounds__(WM *WN * 64) void k_conv_gather(View v, const T *__
   }
   auto wissue = [&](u32x4 (&wreg)[WR]) __attribute__((always_inline)) {
     const int kw = v.KS > 1 ? wslot : kw_single;  // 3^3 dgrad mirroring (K-1-k) is folded into the weight packing
-    const unsigned sbase = (unsigned)((((int64_t)kw * ncp + wslab * SC) * nbp + nb_wg) * (WLD * 64) * 16);
+    const unsigned sbase = (unsigned)((((int64_t)kw * ncp + wslab * SCL) * nbp + nb_wg) * (WLD * 64) * 16);
 #pragma unroll
     for (int i = 0; i < WR; ++i) wreg[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, woff[i], sbase, 0);
   };
@@ -536,7 +546,7 @@ __global__ __launch_bounds__(WM *WN * 64) void k_conv_gather(View v, const T *__
   }
   if (whave) {
     wstage(0, wreg);
-    ncs = min(SC, nc - wslab * SC);
+    ncs = min(SCL, nc - wslab * SCL);
     wnext = wadvance();
     if (wnext) { pslab = wslab; wissue(wreg); }
   }
@@ -555,7 +565,7 @@ __global__ __launch_bounds__(WM *WN * 64) void k_conv_gather(View v, const T *__
     buf ^= 1;
     cc = 0;
     if (wnext) {
-      ncs = min(SC, nc - pslab * SC);
+      ncs = min(SCL, nc - pslab * SCL);
       wnext = wadvance();
       if (wnext) { pslab = wslab; wissue(wreg); }
     }
@@ -835,7 +845,7 @@ constexpr GatherCfg tile_of(int id, bool f32) {
     case 4: return {4, f32 ? 2 : 4, 1, 64};
     case 5: return {5, f32 ? 2 : 4, 2, 64};
     case 6: return {6, f32 ? 1 : 2, 7, 128};
-    case 7: return {7, 2, 4, 128};               // ids 7 .. 13, 16, 17: bf16 only.  128 positions x 128 channels (32 x 128 per wave)
+    case 7: return {7, 2, 4, 128};               // ids 7 .. 13, 16, 17: bf16 only.  128 positions x 128 channels (32 x 128 per wave), 2 workgroups / CU
     case 8: return {8, 4, 2, 128};
     case 9: return {9, 4, 4, 64};
     case 10: return {10, 4, 2, 64};
@@ -864,7 +874,7 @@ int gather_id(const View &v, int nb_total) {
     if (!kF32 && tune(T_CONV_WIDE) != 0 && (nb_total % 8 == 0 || nb_total >= 16) && !(v.KS == 1 && v.nbr == nullptr && nb_total < 16))
       return 17;
     if (!kF32 && nb_total % 8 == 0) return 16;
-    return kF32 ? 3 : 7;                // bf16: 128-position tiles, 4 column blocks per wave at 3 waves/SIMD
+    return kF32 ? 3 : 7;                // bf16: 128-position tiles, 4 column blocks per wave at 2 waves/SIMD (204 registers)
   }
   if (nb_total == 1) return 4;
   if (kF32) return 5;
@@ -977,6 +987,33 @@ ConvPlan conv_plan(const View &v, int K, int g_real, int o_real, ConvEpi epi, in
   return p;
 }
 
+// ---- instances that issue no load of a value that is zero by construction (CONV_SLAB_TRIM, CONV_ROW_TRIM)
+// The image's slab length sc comes from the tile (plan_image); the kernel may walk the chunk-major image with a shorter or
+// longer slab as long as it stops at chunk nc - 1.  -> chunks per slab of the instance to run, 0 = the tile's own instance.
+// Only a single reduction group of at most 8 chunks (gc == nc) is trimmed, and only on the big-map bf16 tiles 0, 1, 2 and 7,
+// whose step shapes fetch zero chunks today: 32 -> 32 and 3 -> 32 (nc 1 on sc 4), 64 -> 64 (2 on 4), 96 -> 96 (3 on 4) and
+// the 96 -> 128 dgrad (3 on sc 2: two slabs of 2).
+inline int trimmed_slab(int tile_id, int sc, int nc, int gc) {
+  const int64_t knob = tune(T_CONV_SLAB_TRIM);
+  if (knob == 0 || gc != nc || nc > 8 || !(tile_id <= 2 || tile_id == 7)) return 0;
+  if (nc < sc) return nc;
+  // tile 7 walks three chunks on 2-chunk slabs: ONE slab of three (62 KB of LDS at the tile's occupancy of 2: half the slab
+  // barriers), or with the knob at 2 three slabs of one
+  if (tile_id == 7 && nc == 3) return knob == 2 ? 1 : 3;
+  if (nc % sc == 0) return 0;              // whole slabs: nothing to trim
+  for (int d = sc - 1; d > 1; --d)         // the largest divisor of nc below sc; none (5, 7): the tile's own instance
+    if (nc % d == 0) return d;
+  return 0;
+}
+// launch-site text of a trimmed instance: "SlabWalk<SCL,ROW1>::k_conv_gather<T,...>", the tile's own text with the walk in front
+template <int SCL, bool ROW1>
+struct SlabWalk {
+  template <typename T, int RB, int NCB, int WM, int WN, int SC, int D>
+  static constexpr auto k_conv_gather = &lgs::k_conv_gather<T, RB, NCB, WM, WN, SC, D, 0, SCL, ROW1>;
+};
+constexpr int kLdsPerCu = 160 * 1024;
+constexpr int gather_lds_bytes(int tm, int wb, int wld, int scl) { return 2 * scl * wb * wld * 64 * 16 + 27 * tm * 4; }
+
 template <typename T>
 int launch_gather(const View &v, const ConvPlan &pl, const T *in, int cin_real, const uint4 *wp, int K, T *out, int cout_real,
                   const float *bias, hipStream_t s, float *out_f32 = nullptr, const float *row_scale = nullptr,
@@ -1010,6 +1047,40 @@ int launch_gather(const View &v, const ConvPlan &pl, const T *in, int cin_real, 
                        split ? zpartial : out_f32, row_scale, in_bytes, w_bytes, zstride, ClipEpi(), be, gc,              \
                        in_ld > 0 ? in_ld : cin_real);                                                                     \
   } while (0)
+  // the same tile walked with SCL-chunk slabs; OCC = workgroups per CU of the tile's own instance (registers, from the ISA):
+  // the walk may not take more LDS than leaves that many
+#define LGS_LAUNCH_WALK(ID, RB, NCB, WM, WN, SC, D, SCL, ROW1, OCC)                                                       \
+  do {                                                                                                                    \
+    constexpr GatherCfg t = tile_of(ID, false);                                                                           \
+    static_assert(t.sc == SC && t.wb == WN * NCB && t.tm == WM * RB * 32, "tile_of() and the launched instance disagree"); \
+    static_assert(gather_lds_bytes(t.tm, t.wb, Tr<bf16_t>::WLD, SCL) * OCC <= kLdsPerCu, "the slab walk costs the tile occupancy"); \
+    LGS_KLAUNCH((SlabWalk<SCL, ROW1>::k_conv_gather<T, RB, NCB, WM, WN, SC, D>), grid, dim3(WM *WN * 64), 0, s, v, in, cin_real, nc, \
+                       reinterpret_cast<const u32x4 *>(wp), nb_total, ncp, nbp, out, cout_real, split ? nullptr : bias,   \
+                       split ? zpartial : out_f32, row_scale, in_bytes, w_bytes, zstride, ClipEpi(), be, gc,              \
+                       in_ld > 0 ? in_ld : cin_real);                                                                     \
+  } while (0)
+  if constexpr (!kF32) {
+    const int scl = trimmed_slab(pl.tile_id, pl.sc, nc, gc);
+    // rows of one 16-byte piece (conv0: 3 colour channels padded to 8): the second gather of a chunk is out of range in every lane
+    const bool row1 = scl == 1 && pl.tile_id == 0 && cin_real <= Tr<T>::EPL && tune(T_CONV_ROW_TRIM) != 0;
+    bool done = true;
+    switch (scl * 100 + pl.tile_id * 2 + (row1 ? 1 : 0)) {
+      case 100: LGS_LAUNCH_WALK(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 1, false, 3); break;
+      case 101: LGS_LAUNCH_WALK(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 1, true, 3); break;
+      case 200: LGS_LAUNCH_WALK(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 2, false, 3); break;
+      case 300: LGS_LAUNCH_WALK(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 3, false, 3); break;
+      case 102: LGS_LAUNCH_WALK(1, 2, 2, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 1, false, 2); break;
+      case 202: LGS_LAUNCH_WALK(1, 2, 2, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 2, false, 2); break;
+      case 302: LGS_LAUNCH_WALK(1, 2, 2, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 3, false, 2); break;
+      case 104: LGS_LAUNCH_WALK(2, 2, 3, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 1, false, 2); break;
+      case 204: LGS_LAUNCH_WALK(2, 2, 3, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 2, false, 2); break;
+      case 304: LGS_LAUNCH_WALK(2, 2, 3, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 3, false, 2); break;
+      case 114: LGS_LAUNCH_WALK(7, 1, 4, 4, 1, 2, 4, 1, false, 2); break;
+      case 314: LGS_LAUNCH_WALK(7, 1, 4, 4, 1, 2, 4, 3, false, 2); break;
+      default: done = false; break;
+    }
+    if (done) goto launched;
+  }
   switch (pl.tile_id) {
     case 0: LGS_LAUNCH(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
     case 1: LGS_LAUNCH(1, 2, 2, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
@@ -1028,6 +1099,8 @@ int launch_gather(const View &v, const ConvPlan &pl, const T *in, int cin_real, 
     default: LGS_LAUNCH(5, 1, 1, 2, 2, (kF32 ? 2 : 4), (kF32 ? 4 : 8)); break;
   }
 #undef LGS_LAUNCH
+#undef LGS_LAUNCH_WALK
+launched:
   if (split) {
     const int64_t n4 = zstride / 4;
     if (n4 > 0) LGS_KLAUNCH((k_sum_partials<T>), (unsigned)((n4 + 255) / 256), 256, 0, s, zpartial, n4, zstride, bias, cout_real, out,

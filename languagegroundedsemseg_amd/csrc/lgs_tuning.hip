@@ -111,6 +111,14 @@ const Knob kKnobs[T_COUNT] = {
     {T_MAP_CHILD_ROUNDS, "MAP_CHILD_ROUNDS", 0, "k_child_hist / k_child_scatter: rounds of 256 positions per workgroup (two barriers and a dependent load each).  "
                                                 "0 = as many as leave 512 workgroups, between 1 and 16 (8-scene batch: 9 at level 0, 2 at level 1, 1 below); "
                                                 "1 .. 16 = that many on every map (tests walk several rounds on small maps with it)"},
+    {T_CONV_SLAB_TRIM, "CONV_SLAB_TRIM", 1, "k_conv_gather, bf16 tiles 0 / 1 / 2 / 7 with one reduction group of <= 8 chunks (A/B): 1 = the weight slabs the kernel fetches "
+                                            "and stages hold real chunks only (nc below the image's slab length sc: one slab of nc; otherwise the largest "
+                                            "divisor of nc below sc; tile 7 with 3 chunks: one slab of 3), the zero chunks the packed image pads an offset "
+                                            "with are never loaded; 2 = as 1 with tile 7's 3 chunks as three 1-chunk slabs; 0 = whole image slabs.  Same "
+                                            "chunks, same order, same MFMAs: bit-identical (profiles/conv_zero_loads.txt)"},
+    {T_CONV_ROW_TRIM, "CONV_ROW_TRIM", 1, "k_conv_gather tile 0 on rows of one 16-byte piece (conv0's 3 colour channels padded to 8; needs CONV_SLAB_TRIM): 1 = only "
+                                          "the first of a chunk's two gathers is issued, the fragment of the second piece is a zero register; 0 = both "
+                                          "(the second is out of range in every lane).  Bit-identical"},
 };
 std::atomic<int64_t> g_val[T_COUNT];
 std::once_flag g_once;
