@@ -72,6 +72,8 @@ struct View {
   int KS = 1;         // slots per position (27 / 8 / 1)
   int K = 1;          // weight matrices of the op (27 / 8 / 1)
   int mirror = 0;     // weight index = K-1-s (the 3^3 map read in the dgrad direction)
+  View() = default;
+  View(int KS_, int K_, int64_t n_pad_, int64_t n_out_, int64_t n_in_) : n_pad(n_pad_), n_out(n_out_), n_in(n_in_), KS(KS_), K(K_) {}   // by its shape
 };
 
 // A segment map between a fine map and a coarser one (a stride-2^k descendant or the origin map):

@@ -1,69 +1,26 @@
-// lgs_manager.hip -- coordinate manager + kernel-map construction for gfx950.
-//
-// Replaces (functionally) MinkowskiEngine's CoordinateManager as used by the reference:
-//   SparseTensor(feats, coords)            /root/reference/lib/train_test/pl_BaselineTrainer.py:300
-//   stride-2 output maps                    /root/reference/models/res16unet.py:49-107
-//   kernel maps for k in {1,2,3}            /root/reference/models/modules/common.py:179-236
+// lgs_manager.hip -- coordinate manager + kernel-map construction for gfx950 (functionally MinkowskiEngine's CoordinateManager).
 //
 // Design: every coordinate is packed into ONE 64-bit Morton key
 //   key = batch << 54 | interleave3(x + 2^17, y + 2^17, z + 2^17)
-// Level-0 rows keep the caller's order (logits stay row-aligned with the input), but every map also
-// carries its rows in Morton order (`order`: sorted position -> row).  Consequences:
-//   * coarsening by 2 is a bit-mask on the key and preserves the sort, so a strided map and its
-//     2x2x2 kernel map come from one flag+scan over the sorted keys -- no hashing;
-//   * 3x3x3 maps come from 27 probes per voxel into a directory of the occupied 4x4x4 blocks of the sorted keys (DirRef; the
-//     per-voxel open-addressing hash, HashRef, stays behind the knob MAP_BLOCK_DIR = 0);
-//   * conv tiles are runs of 64 Morton-consecutive voxels, so a wavefront ballot gives the per-tile
-//     bitmask of kernel offsets that have any neighbour at all (planar surfaces miss most
-//     out-of-plane offsets), which the conv kernels use to skip work.
+// Level-0 rows keep the caller's order, but every map also carries its rows in Morton order (`order`: sorted position -> row), so
+// coarsening by 2 is a bit-mask on the key that preserves the sort, 3x3x3 maps are 27 probes per voxel into a table of the sorted keys
+// (DirRef, or HashRef behind MAP_BLOCK_DIR = 0), and conv tiles are runs of 64 Morton-consecutive voxels with one offset mask each.
 #include "lgs_common.h"
 
-#include <cstring>
+#include <cstring>   // rocprim.hpp calls memset without including it
 #include <initializer_list>
 #include <memory>
 #include <tuple>
 #include <rocprim/rocprim.hpp>
 
+#include "lgs_arena.h"     // the arena's bump stack (host arithmetic, no HIP)
+#include "lgs_mapkeys.h"   // Morton keys, HashRef / DirRef and their table kernels
+#include "lgs_mapsort.h"   // window mask sort and row permutation kernels
+
 namespace lgs {
 
 static thread_local std::string g_err;
 void set_error(const std::string &msg) { g_err = msg; }
-
-constexpr int kBias = 1 << (kCoordBits - 1);  // 131072
-constexpr uint64_t kEmpty = ~0ull;
-
-__host__ __device__ inline uint64_t spread3(uint64_t x) {
-  x &= 0x1fffff;
-  x = (x | x << 32) & 0x1f00000000ffffull;
-  x = (x | x << 16) & 0x1f0000ff0000ffull;
-  x = (x | x << 8) & 0x100f00f00f00f00full;
-  x = (x | x << 4) & 0x10c30c30c30c30c3ull;
-  x = (x | x << 2) & 0x1249249249249249ull;
-  return x;
-}
-__host__ __device__ inline uint32_t compact3(uint64_t x) {
-  x &= 0x1249249249249249ull;
-  x = (x ^ (x >> 2)) & 0x10c30c30c30c30c3ull;
-  x = (x ^ (x >> 4)) & 0x100f00f00f00f00full;
-  x = (x ^ (x >> 8)) & 0x1f0000ff0000ffull;
-  x = (x ^ (x >> 16)) & 0x1f00000000ffffull;
-  x = (x ^ (x >> 32)) & 0x1fffff;
-  return (uint32_t)x;
-}
-__device__ inline uint64_t pack_key(int b, int xb, int yb, int zb) {  // biased coords
-  return ((uint64_t)b << 54) | spread3((uint64_t)xb) | (spread3((uint64_t)yb) << 1) | (spread3((uint64_t)zb) << 2);
-}
-__device__ inline void unpack_key(uint64_t key, int &b, int &xb, int &yb, int &zb) {
-  b = (int)(key >> 54);
-  uint64_t m = key & ((1ull << 54) - 1);
-  xb = (int)compact3(m);
-  yb = (int)compact3(m >> 1);
-  zb = (int)compact3(m >> 2);
-}
-__device__ inline uint64_t hash64(uint64_t k) {
-  k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-  return k;
-}
 
 // ------------------------------------------------------------------------------------------- kernels
 __global__ void k_pack_keys(const int32_t *coords, int64_t n, uint64_t *keys, int32_t *vals, int *err) {
@@ -140,24 +97,6 @@ __global__ void k_emit_coarse(const uint64_t *fkeys, const int32_t *head, const 
   if (p == n - 1) cstart[q + 1] = (int32_t)n;
 }
 
-__global__ void k_hash_fill(uint64_t *hkeys, int64_t cap) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < cap) hkeys[i] = kEmpty;
-}
-__global__ void k_hash_insert(const uint64_t *skeys, const int32_t *order, int64_t n, uint64_t *hkeys,
-                              int32_t *hvals, uint64_t capm1) {
-  int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n) return;
-  uint64_t key = skeys[p];
-  uint64_t s = hash64(key) & capm1;
-  for (;;) {
-    unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(hkeys + s), (unsigned long long)kEmpty,
-                                        (unsigned long long)key);
-    if (prev == kEmpty) { hvals[s] = order ? order[p] : (int32_t)p; return; }
-    s = (s + 1) & capm1;  // keys are unique here, no equality case
-  }
-}
-
 // Row counts of ALL coarser levels from the sorted stride-1 keys: coarsening by 2^L drops the 3 L low Morton bits and keeps the
 // order, so the level-L map has one row per run of equal masked keys.  Counting the run heads of every level in the pass that
 // already exists for the insert lets lgs_manager_insert return them with ITS host synchronisation: the four
@@ -198,110 +137,6 @@ __global__ __launch_bounds__(256) void k_count_levels(const uint64_t *__restrict
   if (threadIdx.x <= kPreLevels && l_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], l_cnt[threadIdx.x]);
 }
 
-// ---- neighbour lookup: "which row of the probed map has this key?" for NP keys at once, all NP loads of a step in flight together
-// (the probe kernels are bound by the latency of their random accesses, not by their number: profiles/r06_experiments.txt).
-// HashRef (MAP_BLOCK_DIR = 0): the open-addressing table with one slot per voxel.
-struct HashRef {
-  const uint64_t *hkeys;
-  const int32_t *hvals;
-  uint64_t capm1;
-  template <int NP>
-  __device__ inline void find(const uint64_t (&key)[NP], bool (&ok)[NP], int32_t (&r)[NP]) const {
-    uint64_t slot[NP], hk[NP];
-#pragma unroll
-    for (int j = 0; j < NP; ++j) slot[j] = hash64(key[j]) & capm1;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) hk[j] = ok[j] ? hkeys[slot[j]] : kEmpty;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-      if (ok[j]) {
-        uint64_t cur = hk[j], sl = slot[j];
-        while (cur != key[j] && cur != kEmpty) {
-          sl = (sl + 1) & capm1;
-          cur = hkeys[sl];
-        }
-        slot[j] = sl;
-        ok[j] = cur == key[j];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < NP; ++j) r[j] = ok[j] ? hvals[slot[j]] : -1;
-  }
-};
-// DirRef (MAP_BLOCK_DIR = 1): the block directory.  The rows are Morton-sorted, so the keys of one 4 x 4 x 4 block of cells (cells
-// of the map's own grid: the key above bit 3 log2ts + 6) are ONE run of the sorted order, and inside the run the order is the order
-// of the 6-bit cell index.  One entry per occupied block therefore answers the lookup exactly: present = the cell's occupancy bit,
-// sorted position = first + popcount(occupancy below that bit), row = order[position].  The table has one entry per ~16 rows
-// instead of two slots per row (level 0 of the 8-scene batch: 8 MB instead of 48 MB), and the 64 Morton-consecutive rows of a
-// wave ask for a few dozen entries between them instead of 1 728 unrelated slots.
-struct DirEnt { uint64_t id, occ; int32_t first, pad[3]; };   // 32 bytes: a probe reads one aligned half cache line
-static_assert(sizeof(DirEnt) == 32, "DirEnt is read as two 16-byte halves");
-struct DirRef {
-  const DirEnt *ent;
-  uint64_t capm1;
-  int sh;                 // 3 log2ts of the probed map: the cell index is key bits [sh, sh + 6), the block id the bits above
-  const int32_t *order;   // the probed map's sorted position -> row (nullptr: identity)
-  template <int NP>
-  __device__ inline void find(const uint64_t (&key)[NP], bool (&ok)[NP], int32_t (&r)[NP]) const {
-    uint32_t slot[NP];     // the table has at most 2^31 entries (n < 2^31)
-    ulonglong2 e[NP];      // (id, occ)
-    int32_t first[NP];
-#pragma unroll
-    for (int j = 0; j < NP; ++j) slot[j] = (uint32_t)(hash64(key[j] >> (sh + 6)) & capm1);
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-      e[j] = ok[j] ? *reinterpret_cast<const ulonglong2 *>(ent + slot[j]) : make_ulonglong2(kEmpty, 0ull);
-      first[j] = ok[j] ? ent[slot[j]].first : 0;
-    }
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-      if (ok[j]) {
-        const uint64_t id = key[j] >> (sh + 6);
-        uint32_t sl = slot[j];
-        while (e[j].x != id && e[j].x != kEmpty) {
-          sl = (sl + 1) & (uint32_t)capm1;
-          e[j] = *reinterpret_cast<const ulonglong2 *>(ent + sl);
-          first[j] = ent[sl].first;
-        }
-        const int cell = (int)((key[j] >> sh) & 63);
-        ok[j] = e[j].x == id && ((e[j].y >> cell) & 1ull);
-        first[j] += __popcll(e[j].y & ((1ull << cell) - 1ull));
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < NP; ++j) r[j] = ok[j] ? (order ? order[first[j]] : first[j]) : -1;
-  }
-};
-__global__ void k_dir_fill(DirEnt *dir, int64_t cap) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= cap) return;
-  ulonglong2 *q = reinterpret_cast<ulonglong2 *>(dir + i);
-  q[0] = make_ulonglong2(kEmpty, 0ull);
-  q[1] = make_ulonglong2(0ull, 0ull);
-}
-// one pass: the thread at a block head (the pattern of k_heads) walks its run of at most 64 keys, ORs the occupancy and inserts
-// the entry with k_hash_insert's atomicCAS idiom (block ids are unique among the heads).  The table holds at least twice the
-// block count, so the probe sequence ends; a full table (impossible by that sizing) sets d_err bit 3 instead of spinning.
-__global__ void k_dir_build(const uint64_t *skeys, int64_t n, int sh, DirEnt *dir, uint64_t capm1, int *d_err) {
-  int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n) return;
-  const uint64_t id = skeys[p] >> (sh + 6);
-  if (p > 0 && (skeys[p - 1] >> (sh + 6)) == id) return;
-  uint64_t occ = 0;
-  for (int64_t q = p; q < n && q < p + 64; ++q) {
-    const uint64_t k = skeys[q];
-    if ((k >> (sh + 6)) != id) break;
-    occ |= 1ull << ((k >> sh) & 63);
-  }
-  uint64_t s = hash64(id) & capm1;
-  for (uint64_t tries = 0; tries <= capm1; ++tries) {
-    unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&dir[s].id), (unsigned long long)kEmpty, (unsigned long long)id);
-    if (prev == kEmpty) { dir[s].occ = occ; dir[s].first = (int32_t)p; return; }
-    s = (s + 1) & capm1;
-  }
-  if (d_err) atomicOr(d_err, 8);
-}
-
 // 3x3x3 stride-1 map: one thread per sorted position, 27 probes; nbr is offset-major [27][n_pad].
 // Round 6: the probes of one z-plane (nine offsets) are issued TOGETHER -- nine slots computed, nine table loads in flight, then
 // the (rare) continued probes, then nine value loads in flight -- instead of 27 dependent load chains one after the other (level 0
@@ -335,297 +170,6 @@ __global__ __launch_bounds__(256) void k_build_map3(const uint64_t *skeys, int64
     }
   }
   pmask[p] = m;
-}
-
-// Rows whose neighbourhoods have the same shape are clustered: inside windows of kMaskWindow Morton-consecutive
-// positions (spatially compact -> the gathered rows stay L2-resident) the positions are re-ordered by their
-// 27-bit presence mask, so a 32-row MFMA block meets far fewer distinct (block, offset) combinations
-// (measured on the synthetic rooms: zero-padded MFMA work 1.83x -> 1.31x of the real pairs).
-constexpr int kMaskWindow = 16384;
-// Sort key of a neighbourhood mask inside its window (tuning knob MASK_ORDER; the row order is free, only speed depends on it):
-//   0  the mask itself (offset 26 most significant);
-//   1  offsets by CLASS, corners most significant, then edges, faces, centre -- the rare offsets split the window first, so a
-//      tile's rows agree on them and fewer (32-row block, offset) pairs are gathered for nothing;
-//   2  the reverse (faces most significant);  3  popcount-major, then the mask.
-__device__ inline uint32_t mask_sort_code(uint32_t m, int order) {
-  if (order == 0) return m;
-  if (order == 3) return ((uint32_t)__popc(m) << 27) | m;
-  // offset k = (dx+1) + 3 (dy+1) + 9 (dz+1): class = number of non-zero components
-  uint32_t corner = 0, edge = 0, face = 0, centre = (m >> 13) & 1u;
-  int nc = 0, ne = 0, nf = 0;
-#pragma unroll
-  for (int k = 0; k < 27; ++k) {
-    const int dx = k % 3 - 1, dy = (k / 3) % 3 - 1, dz = k / 9 - 1;
-    const int cls = (dx != 0) + (dy != 0) + (dz != 0);
-    const uint32_t b = (m >> k) & 1u;
-    if (cls == 3) corner |= b << nc++;
-    else if (cls == 2) edge |= b << ne++;
-    else if (cls == 1) face |= b << nf++;
-  }
-  if (order == 1) return (corner << 19) | (edge << 7) | (face << 1) | centre;
-  return (face << 21) | (edge << 9) | (corner << 1) | centre;
-}
-__global__ void k_mask_sort_keys(const uint32_t *pmask, int64_t n, int64_t n_pad, int window, int order, uint64_t *keys, int32_t *vals) {
-  int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n_pad) return;
-  keys[p] = p < n ? (((uint64_t)(p / window)) << 32) | mask_sort_code(pmask[p], order) : ~0ull;
-  vals[p] = (int32_t)p;
-}
-// key bits the window sort has to look at: 32 bits of mask code + the window index.  A padding key is all ones; its low
-// bits beat every real key as long as the largest real window index is not all ones too -- one more bit than it needs.
-inline unsigned mask_sort_bits(int64_t n_pad, int window) {
-  const uint64_t nw = (uint64_t)((n_pad + window - 1) / window);
-  unsigned wb = 1;
-  while ((1ull << wb) - 1 < nw) ++wb;
-  return 32u + wb > 64u ? 64u : 32u + wb;
-}
-// MAP_WINDOW_SORT: the same permutation without the global sort.  The window index is the high part of the radix key and p is
-// already ascending, so the result is an independent stable sort of every window by its 32-bit code -- and sorting the composite
-// (code, index in window), padding rows under the code 0xffffffff that no real code reaches (order 3 tops out at 0xdfffffff), by
-// ANY correct sort gives that stable order, because composites are unique.  One workgroup per window: 16 composites per thread,
-// a bitonic network whose stages are taken four at a time in registers (the 16 elements of a thread differ in four index bits
-// [B, B + 4), so the compare-exchanges at distances 2^(B+3) .. 2^B need no other thread); between such passes the window goes
-// through LDS once, and every thread writes back exactly the slots it read, so one workgroup barrier per pass suffices.  The
-// first four merge sizes and the last pass have B = 0: the codes come from global memory and the permutation goes to it straight
-// from registers.  29 passes for 16 384 positions.  Only workgroup barriers, no hand-off between workgroups.
-// One CU's vector ALU is the bound (a window is one workgroup), so the network is kept cheap per comparator: the 46-bit composite
-// sits in the mantissa of a double in [1, 2), where the order of the numbers is the order of the bit patterns, and a
-// compare-exchange is v_min_f64 + v_max_f64 (both return an operand unchanged); the direction of a merge is the same for all 16
-// elements of a thread once the merge is wider than a thread's span, so a descending thread complements the mantissas on the way
-// in and out instead of steering every comparator; B is a template parameter, so the LDS offsets are immediates.
-constexpr int kWsMinLog2 = 10, kWsMaxLog2 = 14;
-inline int window_sort_log2(int64_t window) {   // -> log2(window) where k_window_sort serves it, else -1 (the radix sort does)
-  for (int l = kWsMinLog2; l <= kWsMaxLog2; ++l)
-    if (window == (1ll << l)) return l;
-  return -1;
-}
-inline size_t window_sort_lds(int log2w) { return (((size_t)1 << log2w) + ((size_t)1 << (log2w - 4))) * sizeof(double); }
-static_assert((((size_t)1 << kWsMaxLog2) + ((size_t)1 << (kWsMaxLog2 - 4))) * 8 <= 160 * 1024, "k_window_sort: LDS budget of one CU");
-constexpr unsigned long long kWsOne = 0x3ff0000000000000ull, kWsMant = 0x000fffffffffffffull;
-// (the instructions by name: fmin / fmax would first quiet a possible signalling NaN of each operand, two more v_max_f64 per comparator)
-__device__ inline double ws_min(double x, double y) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y)); return r; }
-__device__ inline double ws_max(double x, double y) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y)); return r; }
-__device__ inline void ws_cmpx(double &lo, double &hi) {
-  double a;
-  asm("v_min_f64 %0, %1, %2\n\tv_max_f64 %1, %1, %2" : "=&v"(a), "+v"(hi) : "v"(lo));
-  lo = a;
-}
-// LDS slot of index i: i + i / 16 (one pad slot per 16: the B = 0 passes walk 16-element rows).  For a thread's elements
-// base | r << B the two terms split without a carry, so the slot is slot(base) + a compile-time offset
-template <int B>
-__device__ inline int ws_base(int t) { return ((t >> B) << (B + 4)) | (t & ((1 << B) - 1)); }
-template <int B>
-__device__ inline void ws_store(double *lds, const double (&e)[16], int t) {
-  const int base = ws_base<B>(t);
-  double *q = lds + base + (base >> 4);
-#pragma unroll
-  for (int r = 0; r < 16; ++r) q[(r << B) + ((r << B) >> 4)] = e[r];
-}
-// one pass: load the 16 elements at index bits [B, B + 4), the stages at distances 2^hi .. 2^B of the merge to runs of 2^m (m >= B + 4:
-// ascending where the thread's base has bit m clear), store unless it is the last pass of the sort
-template <int B>
-__device__ inline void ws_pass(double *lds, double (&e)[16], int t, int hi, int m, bool store) {
-  const int base = ws_base<B>(t);
-  const double *q = lds + base + (base >> 4);
-  const unsigned long long flip = ((base >> m) & 1) ? kWsMant : 0ull;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) e[r] = __longlong_as_double((long long)((unsigned long long)__double_as_longlong(q[(r << B) + ((r << B) >> 4)]) ^ flip));
-#pragma unroll
-  for (int s = 3; s >= 0; --s) {
-    if (B + s > hi) continue;
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      if (!(r & (1 << s))) ws_cmpx(e[r], e[r | (1 << s)]);
-  }
-#pragma unroll
-  for (int r = 0; r < 16; ++r) e[r] = __longlong_as_double((long long)((unsigned long long)__double_as_longlong(e[r]) ^ flip));
-  if (store) ws_store<B>(lds, e, t);
-}
-__global__ __launch_bounds__(1024) void k_window_sort(const uint32_t *__restrict__ pmask, int64_t n, int64_t n_pad, int log2w, int order,
-                                                      int32_t *__restrict__ perm) {
-  extern __shared__ double ws_lds[];     // [window + window / 16]
-  const int t = threadIdx.x;             // blockDim = window / 16
-  const int64_t w0 = (int64_t)blockIdx.x << log2w;
-  double e[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t p = w0 + 16 * t + r;
-    const uint32_t code = p < n ? mask_sort_code(pmask[p], order) : 0xffffffffu;
-    e[r] = __longlong_as_double((long long)(kWsOne | ((unsigned long long)code << 14) | (unsigned)(16 * t + r)));
-  }
-  // merges to runs of 2, 4, 8, 16 inside the thread: the direction bit m is a bit of r (or, for m = 4, of t)
-#pragma unroll
-  for (int m = 1; m <= 4; ++m) {
-#pragma unroll
-    for (int s = m - 1; s >= 0; --s) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if (r & (1 << s)) continue;
-        const bool up = (((16 * t) | r) & (1 << m)) == 0;
-        const double a = ws_min(e[r], e[r | (1 << s)]), b = ws_max(e[r], e[r | (1 << s)]);
-        e[r] = up ? a : b; e[r | (1 << s)] = up ? b : a;
-      }
-    }
-  }
-  ws_store<0>(ws_lds, e, t);
-  __syncthreads();
-  for (int m = 5; m <= log2w; ++m) {
-    for (int hi = m - 1; hi >= 0;) {
-      const int b = hi >= 3 ? hi - 3 : 0;
-      const bool store = !(m == log2w && b == 0);
-      switch (b) {
-        case 0: ws_pass<0>(ws_lds, e, t, hi, m, store); break;
-        case 1: ws_pass<1>(ws_lds, e, t, hi, m, store); break;
-        case 2: ws_pass<2>(ws_lds, e, t, hi, m, store); break;
-        case 3: ws_pass<3>(ws_lds, e, t, hi, m, store); break;
-        case 4: ws_pass<4>(ws_lds, e, t, hi, m, store); break;
-        case 5: ws_pass<5>(ws_lds, e, t, hi, m, store); break;
-        case 6: ws_pass<6>(ws_lds, e, t, hi, m, store); break;
-        case 7: ws_pass<7>(ws_lds, e, t, hi, m, store); break;
-        case 8: ws_pass<8>(ws_lds, e, t, hi, m, store); break;
-        case 9: ws_pass<9>(ws_lds, e, t, hi, m, store); break;
-        default: ws_pass<10>(ws_lds, e, t, hi, m, store); break;
-      }
-      __syncthreads();
-      hi = b - 1;
-    }
-  }
-  // the last pass had B = 0: the thread holds sorted slots 16 t .. 16 t + 15 of its window (n_pad is a multiple of 256: all of them or none)
-  if (w0 + 16 * t >= n_pad) return;
-  int4 *dst = reinterpret_cast<int4 *>(perm + w0 + 16 * t);
-  int32_t v[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) v[r] = (int32_t)(w0 + (int64_t)(__double_as_longlong(e[r]) & 0x3fff));
-#pragma unroll
-  for (int r = 0; r < 16; r += 4) dst[r >> 2] = make_int4(v[r], v[r + 1], v[r + 2], v[r + 3]);
-}
-__global__ void k_permute_map3(const int32_t *nbr_tmp, const uint32_t *pmask, const int32_t *perm, const int32_t *order,
-                               int64_t n, int64_t n_pad, int32_t *nbr, int32_t *out_row, uint32_t *mask64) {
-  int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // grid covers n_pad exactly
-  int32_t src = q < n ? perm[q] : -1;
-  uint32_t pm = src >= 0 ? pmask[src] : 0u;
-  out_row[q] = src >= 0 ? (order ? order[src] : src) : -1;
-  uint32_t m = 0;
-  for (int k = 0; k < 27; ++k) {
-    nbr[(int64_t)k * n_pad + q] = src >= 0 ? nbr_tmp[(int64_t)k * n_pad + src] : -1;
-    if (__ballot((pm >> k) & 1u)) m |= 1u << k;
-  }
-  if ((threadIdx.x & 63) == 0) mask64[q >> 6] = m;
-}
-// MAP_PERMUTE_LDS: the same tables with the gathers taken from LDS.  perm[q] stays inside q's window (the sort is per window), so the
-// rows a window gathers from nbr_tmp[k] are ONE contiguous segment of at most 4 x window bytes: workgroup (w, g) keeps the window's
-// slice of perm in registers (as indices into the segment), and for each of its offsets k in [g kg, g kg + kg) stages the segment
-// with 16-byte loads -- the next offset's loads are issued into registers before the current one is gathered -- reads LDS at the
-// permuted index and writes nbr[k] coalesced.  Group 0 also stages pmask and `order` the same way for mask64 and out_row.
-// A thread owns quads of four consecutive positions, so perm, the staged rows and the tables all move as 16-byte accesses and only
-// the LDS reads are single words.  window is a multiple of 256 (so is n_pad): a group of 64 positions lies in one window.
-constexpr int kPlThreads = 1024, kPlMaxWindow = 32768;
-__device__ __forceinline__ int pl_clamp(int l, int len) { return l < 0 ? 0 : (l >= len ? len - 1 : l); }
-typedef int pl_v4 __attribute__((ext_vector_type(4)));   // a plain 16-byte vector: arrays of it stay in registers
-template <int Q>   // the nq 16-byte pieces of a window's segment of one row: global memory -> registers -> LDS
-__device__ __forceinline__ void pl_load(pl_v4 (&pre)[Q], const int32_t *seg, int nq, int t) {
-  const pl_v4 *src = reinterpret_cast<const pl_v4 *>(seg);
-#pragma unroll
-  for (int j = 0; j < Q; ++j) pre[j] = src[j * kPlThreads + t < nq ? j * kPlThreads + t : t & 63];   // unconditional: nq >= 64
-}
-template <int Q>
-__device__ __forceinline__ void pl_store(const pl_v4 (&pre)[Q], int32_t *lds, int nq, int t) {
-  pl_v4 *lds4 = reinterpret_cast<pl_v4 *>(lds);
-#pragma unroll
-  for (int j = 0; j < Q; ++j)
-    if (j * kPlThreads + t < nq) lds4[j * kPlThreads + t] = pre[j];
-}
-__device__ __forceinline__ int4 pl_gather(const int32_t *lds, int4 l, int none) {
-  return make_int4(l.x >= 0 ? lds[l.x] : none, l.y >= 0 ? lds[l.y] : none, l.z >= 0 ? lds[l.z] : none, l.w >= 0 ? lds[l.w] : none);
-}
-template <int IPT>   // positions per thread: window <= IPT * kPlThreads
-__global__ __launch_bounds__(kPlThreads) void k_permute_map3_lds(const int32_t *__restrict__ nbr_tmp, const uint32_t *__restrict__ pmask,
-                                                                 const int32_t *__restrict__ perm, const int32_t *__restrict__ order, int64_t n,
-                                                                 int64_t n_pad, int window, int kg, int32_t *__restrict__ nbr,
-                                                                 int32_t *__restrict__ out_row, uint32_t *__restrict__ mask64) {
-  extern __shared__ int32_t pl_lds[];    // [min(window, n_pad)]
-  constexpr int Q = IPT / 4;             // a thread owns Q quads of four consecutive positions: quad j * kPlThreads + t of the window
-  const int t = threadIdx.x;
-  const int64_t w0 = (int64_t)blockIdx.x * window;
-  const int len = (int)(n_pad - w0 < (int64_t)window ? n_pad - w0 : (int64_t)window);   // positions of this window: a multiple of 256
-  const int nq = len >> 2;
-  const int live = (int)(n - w0 < (int64_t)len ? n - w0 : (int64_t)len);                // ... of which the first `live` are rows
-  int4 loc[Q];                           // perm[q] - w0, or -1 for a padding position
-  {
-    const int4 *src = reinterpret_cast<const int4 *>(perm + w0);   // perm has n_pad entries
-    const int w0i = (int)w0;
-#pragma unroll
-    for (int j = 0; j < Q; ++j) {
-      const int qd = j * kPlThreads + t;
-      int4 l = make_int4(-1, -1, -1, -1);
-      if (qd < nq) {
-        const int4 p = src[qd];
-        // a correct permutation is inside the window; nothing else may index the LDS
-        l.x = 4 * qd + 0 < live ? pl_clamp(p.x - w0i, len) : -1;
-        l.y = 4 * qd + 1 < live ? pl_clamp(p.y - w0i, len) : -1;
-        l.z = 4 * qd + 2 < live ? pl_clamp(p.z - w0i, len) : -1;
-        l.w = 4 * qd + 3 < live ? pl_clamp(p.w - w0i, len) : -1;
-      }
-      loc[j] = l;
-    }
-  }
-  pl_v4 pre[Q];
-  const int k0 = blockIdx.y * kg, k1 = k0 + kg < 27 ? k0 + kg : 27;
-  if (blockIdx.y == 0) {
-    pl_load<Q>(pre, reinterpret_cast<const int32_t *>(pmask) + w0, nq, t);   // pmask has n_pad entries
-    pl_store<Q>(pre, pl_lds, nq, t);
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < Q; ++j) {
-      const int qd = j * kPlThreads + t;   // 64 consecutive quads per wave, nq a multiple of 64: a wave is inside or outside as a whole
-      const int4 pm = pl_gather(pl_lds, loc[j], 0);
-      uint32_t m = (uint32_t)(pm.x | pm.y | pm.z | pm.w);   // an offset is in the group's mask if any of its 64 positions has it: 16 lanes
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) m |= (uint32_t)__shfl_xor((int)m, o, 64);
-      if (qd < nq && (t & 15) == 0) mask64[(w0 + 4 * qd) >> 6] = m;
-    }
-    __syncthreads();
-    if (order) {                           // `order` has n entries, not n_pad
-#pragma unroll
-      for (int j = 0; j < Q; ++j) {
-        const int qd = j * kPlThreads + t;
-        if (qd >= nq) continue;
-        int4 v = make_int4(-1, -1, -1, -1);
-        if (4 * qd + 3 < live) v = reinterpret_cast<const int4 *>(order + w0)[qd];
-        else if (4 * qd < live) {
-          v.x = order[w0 + 4 * qd];
-          if (4 * qd + 1 < live) v.y = order[w0 + 4 * qd + 1];
-          if (4 * qd + 2 < live) v.z = order[w0 + 4 * qd + 2];
-        }
-        reinterpret_cast<int4 *>(pl_lds)[qd] = v;
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int j = 0; j < Q; ++j) {
-      const int qd = j * kPlThreads + t;
-      if (qd >= nq) continue;
-      const int4 l = loc[j];
-      const int w0i = (int)w0;
-      const int4 v = order ? pl_gather(pl_lds, l, -1)
-                           : make_int4(l.x >= 0 ? w0i + l.x : -1, l.y >= 0 ? w0i + l.y : -1, l.z >= 0 ? w0i + l.z : -1, l.w >= 0 ? w0i + l.w : -1);
-      reinterpret_cast<int4 *>(out_row + w0)[qd] = v;
-    }
-    __syncthreads();
-  }
-  pl_load<Q>(pre, nbr_tmp + (int64_t)k0 * n_pad + w0, nq, t);
-  for (int k = k0; k < k1; ++k) {
-    pl_store<Q>(pre, pl_lds, nq, t);
-    __syncthreads();
-    if (k + 1 < k1) pl_load<Q>(pre, nbr_tmp + (int64_t)(k + 1) * n_pad + w0, nq, t);
-    int4 *dst = reinterpret_cast<int4 *>(nbr + (int64_t)k * n_pad + w0);
-#pragma unroll
-    for (int j = 0; j < Q; ++j) {
-      const int qd = j * kPlThreads + t;
-      if (qd < nq) dst[qd] = pl_gather(pl_lds, loc[j], -1);
-    }
-    __syncthreads();
-  }
 }
 
 // 3x3x3 stride-2, fine-stationary view (dgrad of the strided conv, forward of its transposed conv): slot k of fine position p holds
@@ -984,22 +528,15 @@ using namespace lgs;
 struct lgs_manager {
   int device = 0;
   hipMemPool_t pool = nullptr;
-  // All map construction runs on the manager's OWN stream: the host-side row-count syncs then wait for map work
-  // only (never for the compute backlog of the caller's stream), and the maps of step t+1 are built while step t's
-  // backward is still running.  Consumers order themselves after `ev_ready` (lgs::kmap_wait).
-  hipStream_t ms = nullptr;
+  hipStream_t ms = nullptr;        // the map stream: all construction runs on it; consumers order themselves after `ev_ready` (lgs::kmap_wait)
   hipEvent_t ev_ready = nullptr, ev_in = nullptr;
   std::vector<hipStream_t> users;  // caller streams that consumed this manager's arrays (joined before freeing)
-  hipStream_t last_stream = nullptr;
   std::vector<CoordMap> maps;
   std::vector<lgs_kmap *> kmaps;
   std::vector<void *> allocs;      // pool allocations (no arena yet, or the arena was too small)
   int *d_err = nullptr;
-  // arena: one device block per manager, bump-allocated (see "arena" below)
-  char *arena = nullptr;
-  size_t arena_cap = 0, arena_used = 0, arena_peak = 0;
-  struct Blk { size_t off, size; bool freed; };
-  std::vector<Blk> blks;           // live arena blocks in allocation order (a stack: freed blocks on top are popped)
+  char *arena = nullptr;           // one device block per manager, bump-allocated (see "arena" below)
+  ArenaStack stack;                // where in the block each allocation lies (lgs_arena.h)
   size_t pool_live = 0, pool_peak = 0;
   int64_t precount[8] = {-1, -1, -1, -1, -1, -1, -1, -1};   // rows of the maps at tensor stride 2^(i+1), counted by the insert (-1: unknown)
   int64_t precount_batches = -1;   // distinct batch indices of the insert = rows of the origin map
@@ -1021,13 +558,20 @@ struct DeviceGuard {
   }
 };
 
+// what the managers of one device share for the whole process
+struct ArenaBlock { char *base; size_t cap; std::vector<hipEvent_t> ready; };
+struct DeviceState {
+  hipMemPool_t pool = nullptr;      // the private stream-ordered pool (ensure_pool)
+  hipStream_t map_stream = nullptr; // the one map stream (lgs_manager_create)
+  std::vector<ArenaBlock> arenas;   // FIFO of released arena blocks
+  size_t arena_need = 0;            // largest (arena peak + pool peak) any manager of this device has needed
+} g_dev[64];
+
 // The maps of step t+1 reuse step t's memory: map arrays come from a PRIVATE stream-ordered pool per device whose
 // release threshold is unlimited (the process-wide default pool is left alone).
-hipMemPool_t g_pool[64] = {nullptr};
 int ensure_pool(int device) {
-  if (g_pool[device]) return 0;
-  hipMemPoolProps props;
-  memset(&props, 0, sizeof(props));
+  if (g_dev[device].pool) return 0;
+  hipMemPoolProps props = {};
   props.allocType = hipMemAllocationTypePinned;
   props.handleTypes = hipMemHandleTypeNone;
   props.location.type = hipMemLocationTypeDevice;
@@ -1040,56 +584,32 @@ int ensure_pool(int device) {
   // the allocator must not buy reuse with a stream dependency on the compute stream's tail
   int off = 0;
   (void)hipMemPoolSetAttribute(pool, hipMemPoolReuseAllowInternalDependencies, &off);
-  g_pool[device] = pool;
+  g_dev[device].pool = pool;
   return 0;
 }
-// ---- arena.  A manager makes ~150 device allocations per step; as stream-ordered pool calls each of them (and each
-// free when the manager dies) is a marker packet in a HIP stream, and freeing a manager cost ~3 ms of stream time per
-// step.  Instead every manager owns ONE block, bump-allocated on the host: allocation and release are pointer
-// arithmetic; temporaries are released as a stack (a freed block is reclaimed once everything above it is freed too --
-// all users of the arena run on the map stream, in order).  Blocks are recycled through a per-device FIFO: when a manager
-// dies its block is stamped with one event per user stream and queued; a new manager takes the OLDEST queued block (its
-// users finished a step ago, so the wait on its events is already satisfied) or, while fewer than two are queued,
-// allocates a new one sized to the largest need seen so far.  Steady state: three blocks in rotation, no allocator
-// call at all.  Whatever does not fit (first step, growing scenes) falls back to the private stream-ordered pool.
-struct ArenaBlock { char *base; size_t cap; std::vector<hipEvent_t> ready; };
-std::vector<ArenaBlock> g_arenas[64];   // FIFO of released blocks per device
-size_t g_arena_need[64] = {0};          // largest (arena peak + pool peak) any manager of this device has needed
-
-inline hipError_t pool_alloc(lgs_manager *m, void **q, size_t bytes, hipStream_t s) {
-  return hipMallocFromPoolAsync(q, bytes, m->pool, s);
-}
+// ---- arena ("Manager memory"): every manager owns ONE device block, bump-allocated on the host (ArenaStack); blocks are
+// recycled through the device's FIFO.  Whatever does not fit (first step, growing scenes) falls back to the private stream-ordered pool.
 int raw_alloc(lgs_manager *m, void **p, size_t bytes, hipStream_t s) {
-  bytes = (bytes + 255) / 256 * 256;
-  if (m->arena && m->arena_used + bytes <= m->arena_cap) {
-    *p = m->arena + m->arena_used;
-    m->blks.push_back({m->arena_used, bytes, false});
-    m->arena_used += bytes;
-    if (m->arena_used > m->arena_peak) m->arena_peak = m->arena_used;
+  bytes = ArenaStack::rounded(bytes);
+  size_t off = 0;
+  if (m->arena && m->stack.take(bytes, &off)) {
+    *p = m->arena + off;
     return 0;
   }
-  void *q = nullptr;
-  LGS_HIP(pool_alloc(m, &q, bytes, s));
-  m->allocs.push_back(q);
+  LGS_HIP(hipMallocFromPoolAsync(p, bytes, m->pool, s));
+  m->allocs.push_back(*p);
   m->pool_live += bytes;
   if (m->pool_live > m->pool_peak) m->pool_peak = m->pool_live;
-  *p = q;
   return 0;
 }
 template <typename T>
 int dalloc(lgs_manager *m, T **p, int64_t count, hipStream_t s) {
-  void *q = nullptr;
-  if (raw_alloc(m, &q, sizeof(T) * (size_t)(count > 0 ? count : 1), s)) return 1;
-  *p = reinterpret_cast<T *>(q);
-  return 0;
+  return raw_alloc(m, reinterpret_cast<void **>(p), sizeof(T) * (size_t)(count > 0 ? count : 1), s);
 }
 int dfree_now(lgs_manager *m, void *q, hipStream_t s) {  // temp buffer: release early
   char *c = reinterpret_cast<char *>(q);
-  if (m->arena && c >= m->arena && c < m->arena + m->arena_cap) {
-    const size_t off = (size_t)(c - m->arena);
-    for (size_t i = m->blks.size(); i-- > 0;)
-      if (m->blks[i].off == off) { m->blks[i].freed = true; break; }
-    while (!m->blks.empty() && m->blks.back().freed) { m->arena_used = m->blks.back().off; m->blks.pop_back(); }
+  if (m->arena && c >= m->arena && c < m->arena + m->stack.capacity()) {
+    m->stack.release((size_t)(c - m->arena));
     return 0;
   }
   for (size_t i = 0; i < m->allocs.size(); ++i)
@@ -1097,12 +617,38 @@ int dfree_now(lgs_manager *m, void *q, hipStream_t s) {  // temp buffer: release
   LGS_HIP(hipFreeAsync(q, s));
   return 0;
 }
+// The temporaries of one entry point or builder ("the scratch-scope rule"): what is still held when the scope ends goes
+// back, newest first, on every path out of it.  A fixed table, no heap: ~150 allocations per step pass through here on the host.
+struct Scratch {
+  lgs_manager *m;
+  hipStream_t s;
+  void *held[12];   // the largest scope, lgs_manager_insert, holds 9
+  int n = 0;
+  Scratch(lgs_manager *m_, hipStream_t s_) : m(m_), s(s_) {}
+  Scratch(const Scratch &) = delete;
+  ~Scratch() {      // (a failing hipFreeAsync of the pool fallback cannot be reported from here)
+    while (n > 0)
+      if (held[--n]) (void)dfree_now(m, held[n], s);
+  }
+  template <typename T>
+  int take(T **p, int64_t count) {
+    LGS_REQUIRE(n < 12, "Scratch: too many temporaries in one scope");
+    if (dalloc(m, p, count, s)) return 1;
+    held[n++] = *p;
+    return 0;
+  }
+  int drop(void *p) {   // release one temporary before the scope ends
+    for (int i = 0; i < n; ++i)
+      if (held[i] == p) { held[i] = nullptr; return dfree_now(m, p, s); }
+    return 0;
+  }
+};
 // take a recycled block (or a new one) for a fresh manager; the map stream waits for the block's previous users
-int arena_acquire(lgs_manager *m) {
+void arena_acquire(lgs_manager *m) {
   const int dev = m->device;
-  const size_t need = g_arena_need[dev];
-  if (need == 0) return 0;                       // first manager of the device: measure through the pool
-  std::vector<ArenaBlock> &q = g_arenas[dev];
+  const size_t need = g_dev[dev].arena_need;
+  if (need == 0) return;                         // first manager of the device: measure through the pool
+  std::vector<ArenaBlock> &q = g_dev[dev].arenas;
   // never the most recently released block (its users -- the previous step's backward -- are still running)
   for (size_t i = 0; q.size() >= 2 && i + 1 < q.size(); ++i) {
     if (q[i].cap >= need) {
@@ -1115,8 +661,8 @@ int arena_acquire(lgs_manager *m) {
                 need >> 20, pending, b.ready.size());
       }
       for (hipEvent_t e : b.ready) { (void)hipStreamWaitEvent(m->ms, e, 0); (void)hipEventDestroy(e); }
-      m->arena = b.base; m->arena_cap = b.cap;
-      return 0;
+      m->arena = b.base; m->stack.reset(b.cap);
+      return;
     }
     if (i == 0 && q.size() >= 4) {               // an undersized block at the head of a long queue: retire it
       for (hipEvent_t e : q[0].ready) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
@@ -1128,15 +674,15 @@ int arena_acquire(lgs_manager *m) {
   const size_t cap = (need + need / 4 + (2u << 20)) / (2u << 20) * (2u << 20);
   if (tune(T_ARENA_DBG)) fprintf(stderr, "[arena] hipMalloc %zu MB (need %zu MB, %zu queued)\n", cap >> 20, need >> 20, q.size());
   void *p = nullptr;
-  if (hipMalloc(&p, cap) != hipSuccess) { (void)hipGetLastError(); return 0; }   // no block: this manager uses the pool
-  m->arena = reinterpret_cast<char *>(p); m->arena_cap = cap;
-  return 0;
+  if (hipMalloc(&p, cap) != hipSuccess) { (void)hipGetLastError(); return; }   // no block: this manager uses the pool
+  m->arena = reinterpret_cast<char *>(p); m->stack.reset(cap);
 }
 void arena_release(lgs_manager *m) {
-  const size_t need = m->arena_peak + m->pool_peak;
-  if (need > g_arena_need[m->device]) g_arena_need[m->device] = need;
+  DeviceState &d = g_dev[m->device];
+  const size_t need = m->stack.peak() + m->pool_peak;
+  if (need > d.arena_need) d.arena_need = need;
   if (!m->arena) return;
-  ArenaBlock b{m->arena, m->arena_cap, {}};
+  ArenaBlock b{m->arena, m->stack.capacity(), {}};
   std::vector<hipStream_t> streams = m->users;
   streams.push_back(m->ms);
   for (hipStream_t u : streams) {
@@ -1145,7 +691,7 @@ void arena_release(lgs_manager *m) {
       if (hipEventRecord(e, u) == hipSuccess) b.ready.push_back(e); else (void)hipEventDestroy(e);
     }
   }
-  g_arenas[m->device].push_back(b);
+  d.arenas.push_back(b);
   m->arena = nullptr;
 }
 void add_user(lgs_manager *m, hipStream_t caller) {
@@ -1159,14 +705,16 @@ int begin_from_caller(lgs_manager *m, hipStream_t caller) {
   LGS_HIP(hipStreamWaitEvent(m->ms, m->ev_in, 0));
   return 0;
 }
+// order `stream` after the published map work; it becomes a user of the manager's arrays
+int wait_ready(lgs_manager *m, hipStream_t stream) {
+  LGS_HIP(hipStreamWaitEvent(stream, m->ev_ready, 0));
+  add_user(m, stream);
+  return 0;
+}
 // publish map work; if `caller` is given it is ordered after it (outputs written into caller-owned memory)
 int publish(lgs_manager *m, hipStream_t caller, bool caller_waits) {
   LGS_HIP(hipEventRecord(m->ev_ready, m->ms));
-  if (caller_waits) {
-    LGS_HIP(hipStreamWaitEvent(caller, m->ev_ready, 0));
-    add_user(m, caller);
-  }
-  return 0;
+  return caller_waits ? wait_ready(m, caller) : 0;
 }
 inline unsigned nblk(int64_t n, int t = 256) { return (unsigned)((n + t - 1) / t > 0 ? (n + t - 1) / t : 1); }
 
@@ -1185,9 +733,7 @@ int ensure_hash(lgs_manager *m, CoordMap &cm, hipStream_t s) {
   return 0;
 }
 
-// the block directory of a map (MAP_BLOCK_DIR), built where the per-voxel hash would be.  A block of the map at tensor stride 2^t
-// is a cell of the map two levels coarser, whose row count lgs_manager_insert already took (precount): the table is sized from
-// it without a host synchronisation, and from n (one block per row at the worst) where that count is not known.
+// the block directory of a map (MAP_BLOCK_DIR; DESIGN.md, "Neighbour lookup"): sized from the insert's count of the map two levels coarser, else from n
 int ensure_dir(lgs_manager *m, CoordMap &cm, hipStream_t s) {
   if (cm.dir) return 0;
   int64_t blocks = cm.n;
@@ -1224,62 +770,57 @@ int fill_segs(hipStream_t s, std::initializer_list<std::tuple<void *, int64_t, i
 int scan_incl(lgs_manager *m, const int32_t *in, int32_t *out, int64_t n, hipStream_t s) {
   size_t tb = 0;
   LGS_HIP(rocprim::inclusive_scan(nullptr, tb, in, out, (size_t)n, rocprim::plus<int32_t>(), s));
-  void *tmp = nullptr;
-  if (raw_alloc(m, &tmp, tb ? tb : 16, s)) return 1;
-  LGS_HIP(rocprim::inclusive_scan(tmp, tb, in, out, (size_t)n, rocprim::plus<int32_t>(), s));
-  if (dfree_now(m, tmp, s)) return 1;
+  Scratch tmp(m, s);   // rocPRIM's temporary: from and back to the arena's top
+  char *t;
+  if (tmp.take(&t, (int64_t)(tb ? tb : 16))) return 1;
+  LGS_HIP(rocprim::inclusive_scan(t, tb, in, out, (size_t)n, rocprim::plus<int32_t>(), s));
   return 0;
 }
 
-// radix sort of (key, value) pairs on key bits [begin_bit, end_bit); rocPRIM's temporary is taken from and returned to the arena's top
+// radix sort of (key, value) pairs on key bits [begin_bit, end_bit)
 template <typename K, typename V>
 int sort_pairs(lgs_manager *m, K *keys, K *keys_out, V *vals, V *vals_out, int64_t n, unsigned begin_bit, unsigned end_bit, hipStream_t s) {
   size_t tb = 0;
   LGS_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys, keys_out, vals, vals_out, (size_t)n, begin_bit, end_bit, s));
-  void *tmp = nullptr;
-  if (raw_alloc(m, &tmp, tb ? tb : 16, s)) return 1;
-  LGS_HIP(rocprim::radix_sort_pairs(tmp, tb, keys, keys_out, vals, vals_out, (size_t)n, begin_bit, end_bit, s));
-  return dfree_now(m, tmp, s);
+  Scratch tmp(m, s);
+  char *t;
+  if (tmp.take(&t, (int64_t)(tb ? tb : 16))) return 1;
+  LGS_HIP(rocprim::radix_sort_pairs(t, tb, keys, keys_out, vals, vals_out, (size_t)n, begin_bit, end_bit, s));
+  return 0;
 }
 
-// head[p] = 1 where sorted key p starts a new batch index; cincl = its inclusive scan (the origin map's row of every position, + 1)
-int batch_heads(lgs_manager *m, const uint64_t *skeys, int64_t n, int32_t *head, int32_t *cincl, hipStream_t s) {
-  LGS_KLAUNCH(k_heads, nblk(n), 256, 0, s, skeys, n, ~((1ull << kBatchShift) - 1), head);
-  return scan_incl(m, head, cincl, n, s);
+// head[p] = 1 where sorted key p starts a new run of (key & keep_mask); incl = its inclusive scan (the run of every position, + 1)
+constexpr uint64_t kBatchMask = ~((1ull << kBatchShift) - 1);   // runs of one batch index: the rows of the origin map
+int key_heads(lgs_manager *m, const uint64_t *skeys, int64_t n, uint64_t keep_mask, int32_t *head, int32_t *incl, hipStream_t s) {
+  LGS_KLAUNCH(k_heads, nblk(n), 256, 0, s, skeys, n, keep_mask, head);
+  return scan_incl(m, head, incl, n, s);
 }
 
-// the window mask sort of a 27-slot table built in sorted-position order (nbr_tmp, pmask) and its permutation into the view's arrays:
-// position q of the view is sorted position perm[q] and writes row order[perm[q]] (order == nullptr: the position itself).
-// MAP_WINDOW_SORT: one k_window_sort launch where the window is a power of two that fits the LDS (window_sort_log2); else the radix
-// sort of (window, code) keys with its four n_pad-sized temporaries.
+// the window mask sort of a 27-slot table (pmask) -> perm: position q of the view is sorted position perm[q].  MAP_WINDOW_SORT: one
+// k_window_sort launch where the window fits the LDS (window_sort_log2); else the radix sort of (window, code) keys and its temporaries
 int window_perm(lgs_manager *m, int64_t n, int64_t n_pad, const uint32_t *pmask, int32_t *perm, hipStream_t s) {
   const int64_t window = tune(T_MASK_WINDOW);   // tuning knob (default kMaskWindow)
   const int order = (int)tune(T_MASK_ORDER);
   const int log2w = tune(T_MAP_WINDOW_SORT) != 0 ? window_sort_log2(window) : -1;
   if (log2w >= 0) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      LGS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_sort), hipFuncAttributeMaxDynamicSharedMemorySize, (int)window_sort_lds(kWsMaxLog2)));
-      attr_set = true;
-    }
+    static const hipError_t lds_attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_sort), hipFuncAttributeMaxDynamicSharedMemorySize, (int)window_sort_lds(kWsMaxLog2));
+    LGS_HIP(lds_attr);   // once per process
     // a map of one window sorts the smallest power of two that holds its positions (what lies beyond is padding, which sorts last)
     int l = log2w;
     while (l > kWsMinLog2 && n_pad <= (1ll << (l - 1))) --l;
     LGS_KLAUNCH(k_window_sort, (unsigned)((n_pad + (1ll << l) - 1) >> l), 1u << (l - 4), window_sort_lds(l), s, pmask, n, n_pad, l, order, perm);
     return 0;
   }
+  Scratch tmp(m, s);
   uint64_t *keys, *skeys2; int32_t *vals;
-  if (dalloc(m, &keys, n_pad, s) || dalloc(m, &skeys2, n_pad, s) || dalloc(m, &vals, n_pad, s)) return 1;
+  if (tmp.take(&keys, n_pad) || tmp.take(&skeys2, n_pad) || tmp.take(&vals, n_pad)) return 1;
   LGS_KLAUNCH(k_mask_sort_keys, (unsigned)(n_pad / 256), 256, 0, s, pmask, n, n_pad, (int)window, order, keys, vals);
-  if (sort_pairs(m, keys, skeys2, vals, perm, n_pad, 0, mask_sort_bits(n_pad, (int)window), s)) return 1;
-  return dfree_now(m, keys, s) || dfree_now(m, skeys2, s) || dfree_now(m, vals, s);
+  return sort_pairs(m, keys, skeys2, vals, perm, n_pad, 0, mask_sort_bits(n_pad, (int)window), s);
 }
 
 // the permutation of (nbr_tmp, pmask) into the view's arrays.  MAP_PERMUTE_LDS: through LDS (k_permute_map3_lds) where a window's
 // row segment fits it and windows are whole groups of 256 positions; else, and with the knob at 0, k_permute_map3
-// Offsets per workgroup (MAP_PERMUTE_GROUP): a workgroup walks its offsets one after the other and a CU holds two workgroups, so
-// a small map wants one offset per workgroup to fill the chip at all, and a large one as many as still leave the grid above
-// kPlWorkgroups -- every offset group reads the window's perm again
+// Offsets per workgroup (MAP_PERMUTE_GROUP): as many as still leave the grid above kPlWorkgroups
 constexpr int kPlWorkgroups = 640;
 inline int permute_group(int64_t windows) {
   const int64_t g = tune(T_MAP_PERMUTE_GROUP);
@@ -1294,12 +835,9 @@ int permute_rows(const CoordMap &st, const int32_t *nbr_tmp, const uint32_t *pma
     LGS_KLAUNCH(k_permute_map3, (unsigned)(st.n_pad / 256), 256, 0, s, nbr_tmp, pmask, perm, st.order, st.n, st.n_pad, nbr, orow, mask);
     return 0;
   }
-  static bool attr_set = false;
-  if (!attr_set) {
-    LGS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_permute_map3_lds<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 16 * kPlThreads * 4));
-    LGS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_permute_map3_lds<32>), hipFuncAttributeMaxDynamicSharedMemorySize, kPlMaxWindow * 4));
-    attr_set = true;
-  }
+  static const hipError_t lds16 = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_permute_map3_lds<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 16 * kPlThreads * 4);
+  static const hipError_t lds32 = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_permute_map3_lds<32>), hipFuncAttributeMaxDynamicSharedMemorySize, kPlMaxWindow * 4);
+  LGS_HIP(lds16 != hipSuccess ? lds16 : lds32);   // once per process
   const int64_t windows = (st.n_pad + window - 1) / window;
   const int kg = permute_group(windows);
   const dim3 grid((unsigned)windows, (unsigned)((27 + kg - 1) / kg));
@@ -1314,29 +852,23 @@ int permute_rows(const CoordMap &st, const int32_t *nbr_tmp, const uint32_t *pma
 // a 27-slot view over the rows of map `st` (the stationary side): table built by `build` into (nbr_tmp, pmask), then the window sort
 template <typename Build>
 int make_view27(lgs_manager *m, const CoordMap &st, int64_t n_in, hipStream_t s, View &v, Build &&build) {
-  v = View();
-  v.n_pad = st.n_pad; v.n_out = st.n; v.n_in = n_in; v.KS = 27; v.K = 27;
+  v = View(27, 27, st.n_pad, st.n, n_in);
   if (st.n == 0) return 0;
   int32_t *nbr, *orow, *nbr_tmp, *perm; uint32_t *mask, *pmask;
-  if (dalloc(m, &nbr, 27 * st.n_pad, s) || dalloc(m, &mask, st.n_pad / kGroup, s) || dalloc(m, &orow, st.n_pad, s) ||
-      dalloc(m, &nbr_tmp, 27 * st.n_pad, s) || dalloc(m, &pmask, st.n_pad, s) || dalloc(m, &perm, st.n_pad, s))
-    return 1;
+  if (dalloc(m, &nbr, 27 * st.n_pad, s) || dalloc(m, &mask, st.n_pad / kGroup, s) || dalloc(m, &orow, st.n_pad, s)) return 1;
+  Scratch tmp(m, s);   // above the view's own arrays: they pop
+  if (tmp.take(&nbr_tmp, 27 * st.n_pad) || tmp.take(&pmask, st.n_pad) || tmp.take(&perm, st.n_pad)) return 1;
   if (build(nbr_tmp, pmask)) return 1;
   if (window_perm(m, st.n, st.n_pad, pmask, perm, s)) return 1;
   if (permute_rows(st, nbr_tmp, pmask, perm, s, nbr, orow, mask)) return 1;
   LGS_HIP(hipGetLastError());
-  if (dfree_now(m, nbr_tmp, s) || dfree_now(m, pmask, s) || dfree_now(m, perm, s)) return 1;
   v.nbr = nbr; v.mask64 = mask; v.out_row = orow;
   return 0;
 }
 
-
 // ---- kernel maps: one builder per relation (KmapRelation, lgs_common.h), all on the map stream
 // identity 1x1: no table
-void build_identity(const CoordMap &ci, lgs_kmap *km) {
-  View v; v.n_pad = ci.n_pad; v.n_out = ci.n; v.n_in = ci.n; v.KS = 1; v.K = 1;
-  km->fwd = v; km->bwd = v;
-}
+void build_identity(const CoordMap &ci, lgs_kmap *km) { km->fwd = km->bwd = View(1, 1, ci.n_pad, ci.n, ci.n); }
 
 // a 27-slot view over the rows of `st` whose slot k holds the row of `probed` at c + off_k * scale: the 27 probes of k_build_map3
 // from st's sorted keys into probed's lookup table (st == probed: the stride-1 maps; st = the coarse map: the coarse-stationary strided
@@ -1354,16 +886,13 @@ int probe_view27(lgs_manager *m, const CoordMap &st, const CoordMap &probed, int
 // 3^3 stride 1, plain (dilation 1) or dilated: offsets scaled by dilation * ts; bwd = the same table read mirrored
 int build_conv3(lgs_manager *m, CoordMap &ci, int dilation, hipStream_t s, lgs_kmap *km) {
   if (ci.n > 0 && ensure_lookup(m, ci, s)) return 1;
-  View v;
-  if (probe_view27(m, ci, ci, dilation * ci.ts, s, v)) return 1;
-  km->fwd = v;
-  km->bwd = v; km->bwd.mirror = 1;
+  if (probe_view27(m, ci, ci, dilation * ci.ts, s, km->fwd)) return 1;
+  km->bwd = km->fwd; km->bwd.mirror = 1;
   return 0;
 }
 
-// MAP_OWN_SORTS: rounds of 256 positions per workgroup of k_child_hist / k_child_scatter (MAP_CHILD_ROUNDS).  A round costs the
-// workgroup two barriers and a dependent load, so a small map takes one round per workgroup and a large one as many as still leave
-// kCpWorkgroups workgroups -- the prefix kernel is one workgroup and walks them all
+// MAP_OWN_SORTS: rounds of 256 positions per workgroup of k_child_hist / k_child_scatter (MAP_CHILD_ROUNDS): as many as
+// still leave kCpWorkgroups workgroups
 constexpr int kCpWorkgroups = 512;
 inline int child_rounds(int64_t n) {
   const int64_t k = tune(T_MAP_CHILD_ROUNDS);
@@ -1374,51 +903,40 @@ inline int child_rounds(int64_t n) {
 
 // 2^3 stride 2: the children of a coarse row are one run of the fine Morton order
 int build_conv2_s2(lgs_manager *m, const CoordMap &ci, const CoordMap &co, hipStream_t s, lgs_kmap *km) {
-  int shift = 3 * ci.log2ts;
-  View vf, vb;
-  vf.KS = 8; vf.K = 8; vf.n_pad = co.n_pad; vf.n_out = co.n; vf.n_in = ci.n;
-  vb.KS = 1; vb.K = 8; vb.n_out = ci.n; vb.n_in = co.n;
-  if (ci.n > 0) {
-    int32_t *nbr8; uint32_t *mask;
+  const int shift = 3 * ci.log2ts;
+  const int64_t n = ci.n, gp = n > 0 ? pad_rows(n + 8 * kPadRows) : 0;   // rows of the grouped fine view
+  View vf = View(8, 8, co.n_pad, co.n, n), vb = View(1, 8, gp, n, co.n);
+  if (n > 0) {
+    int32_t *nbr8, *g_nbr, *g_out, *tile_k; uint32_t *mask;
     if (dalloc(m, &nbr8, 8 * co.n_pad, s) || dalloc(m, &mask, co.n_pad / kGroup, s)) return 1;
-    LGS_KLAUNCH(k_build_map2_coarse, (unsigned)(co.n_pad / 256), 256, 0, s, ci.skeys, ci.order, co.cstart, co.n,
-                       co.n_pad, shift, nbr8, mask);
-    vf.nbr = nbr8; vf.mask64 = mask;
-    // grouped fine view
-    int64_t n = ci.n, gp = pad_rows(n + 8 * kPadRows);
-    if (tune(T_MAP_OWN_SORTS) != 0) {   // the stable 8-way partition (k_child_hist)
+    LGS_KLAUNCH(k_build_map2_coarse, (unsigned)(co.n_pad / 256), 256, 0, s, ci.skeys, ci.order, co.cstart, co.n, co.n_pad, shift, nbr8, mask);
+    // grouped fine view: the tables, all -1, and the radix path's child counters, zeroed by the same launch (MAP_OWN_SORTS = 1: cnt is
+    // nullptr and its segment has count 0, which IS the zero-initialised fourth slot of FillSegs: the launch is the three-segment one)
+    if (dalloc(m, &g_nbr, gp, s) || dalloc(m, &g_out, gp, s) || dalloc(m, &tile_k, gp / kGroup, s)) return 1;
+    const bool own = tune(T_MAP_OWN_SORTS) != 0;
+    Scratch tmp(m, s);
+    int32_t *cnt = nullptr, *goff, *gsrc;
+    if (!own && tmp.take(&cnt, 8)) return 1;
+    if (fill_segs(s, {{g_nbr, gp, -1}, {g_out, gp, -1}, {tile_k, gp / kGroup, -1}, {cnt, own ? 0 : 8, 0}})) return 1;
+    if (own) {   // the stable 8-way partition (k_child_hist)
       const int rounds = child_rounds(n);
       const int32_t nwg = (int32_t)((n + 256 * rounds - 1) / (256 * rounds));
-      int32_t *wg, *goff, *gsrc, *g_nbr, *g_out, *tile_k;
-      if (dalloc(m, &g_nbr, gp, s) || dalloc(m, &g_out, gp, s) || dalloc(m, &tile_k, gp / kGroup, s) || dalloc(m, &wg, 8 * (int64_t)nwg, s) ||
-          dalloc(m, &goff, 9, s) || dalloc(m, &gsrc, 9, s))
-        return 1;
-      if (fill_segs(s, {{g_nbr, gp, -1}, {g_out, gp, -1}, {tile_k, gp / kGroup, -1}})) return 1;
+      int32_t *wg;
+      if (tmp.take(&wg, 8 * (int64_t)nwg) || tmp.take(&goff, 9) || tmp.take(&gsrc, 9)) return 1;
       LGS_KLAUNCH(k_child_hist, (unsigned)nwg, 256, 0, s, ci.skeys, n, shift, rounds, nwg, wg);
       LGS_KLAUNCH(k_child_prefix, 1, 512, 0, s, wg, nwg, goff, gsrc);
       LGS_KLAUNCH(k_child_scatter, (unsigned)nwg, 256, 0, s, ci.skeys, n, shift, rounds, nwg, wg, goff, co.fine_cidx, ci.order, g_nbr, g_out, tile_k);
-      LGS_HIP(hipGetLastError());
-      vb.nbr = g_nbr; vb.out_row = g_out; vb.tile_k = tile_k; vb.n_pad = gp;
-      if (dfree_now(m, wg, s) || dfree_now(m, goff, s) || dfree_now(m, gsrc, s)) return 1;
-      km->fwd = vf; km->bwd = vb;
-      return 0;
+    } else {     // (child, position) pairs through the radix sort
+      uint32_t *kk, *kks; int32_t *pp, *pps;
+      if (tmp.take(&kk, n) || tmp.take(&kks, n) || tmp.take(&pp, n) || tmp.take(&pps, n) || tmp.take(&goff, 9) || tmp.take(&gsrc, 9)) return 1;
+      LGS_KLAUNCH(k_child_keys, nblk(n), 256, 0, s, ci.skeys, n, shift, kk, pp, cnt);
+      if (sort_pairs(m, kk, kks, pp, pps, n, 0, 3, s)) return 1;
+      LGS_KLAUNCH(k_group_offsets, 1, 64, 0, s, cnt, goff, gsrc);
+      LGS_KLAUNCH(k_build_map2_fine, nblk(n), 256, 0, s, kks, pps, n, goff, gsrc, co.fine_cidx, ci.order, g_nbr, g_out, tile_k);
     }
-    uint32_t *kk, *kks; int32_t *pp, *pps, *cnt, *goff, *gsrc, *g_nbr, *g_out, *tile_k;
-    if (dalloc(m, &kk, n, s) || dalloc(m, &kks, n, s) || dalloc(m, &pp, n, s) || dalloc(m, &pps, n, s) ||
-        dalloc(m, &cnt, 8, s) || dalloc(m, &goff, 9, s) || dalloc(m, &gsrc, 9, s) || dalloc(m, &g_nbr, gp, s) ||
-        dalloc(m, &g_out, gp, s) || dalloc(m, &tile_k, gp / kGroup, s))
-      return 1;
-    if (fill_segs(s, {{cnt, 8, 0}, {g_nbr, gp, -1}, {g_out, gp, -1}, {tile_k, gp / kGroup, -1}})) return 1;
-    LGS_KLAUNCH(k_child_keys, nblk(n), 256, 0, s, ci.skeys, n, shift, kk, pp, cnt);
-    if (sort_pairs(m, kk, kks, pp, pps, n, 0, 3, s)) return 1;
-    LGS_KLAUNCH(k_group_offsets, 1, 64, 0, s, cnt, goff, gsrc);
-    LGS_KLAUNCH(k_build_map2_fine, nblk(n), 256, 0, s, kks, pps, n, goff, gsrc, co.fine_cidx, ci.order, g_nbr,
-                       g_out, tile_k);
     LGS_HIP(hipGetLastError());
-    vb.nbr = g_nbr; vb.out_row = g_out; vb.tile_k = tile_k; vb.n_pad = gp;
-    if (dfree_now(m, kk, s) || dfree_now(m, kks, s) || dfree_now(m, pp, s) || dfree_now(m, pps, s) ||
-        dfree_now(m, cnt, s) || dfree_now(m, goff, s) || dfree_now(m, gsrc, s))
-      return 1;
+    vf.nbr = nbr8; vf.mask64 = mask;
+    vb.nbr = g_nbr; vb.out_row = g_out; vb.tile_k = tile_k;
   }
   km->fwd = vf; km->bwd = vb;
   return 0;
@@ -1441,9 +959,7 @@ int build_conv3_s2(lgs_manager *m, CoordMap &ci, CoordMap &co, hipStream_t s, lg
 
 // 1x1 stride 2: plain nbr (/ out_row) pairs on the KS = 1 path
 int build_conv1_s2(lgs_manager *m, const CoordMap &ci, const CoordMap &co, hipStream_t s, lgs_kmap *km) {
-  View vf, vb;
-  vf.KS = 1; vf.K = 1; vf.n_pad = co.n_pad; vf.n_out = co.n; vf.n_in = ci.n;
-  vb.KS = 1; vb.K = 1; vb.n_pad = ci.n_pad; vb.n_out = ci.n; vb.n_in = co.n;
+  View vf = View(1, 1, co.n_pad, co.n, ci.n), vb = View(1, 1, ci.n_pad, ci.n, co.n);
   if (ci.n > 0) {
     int32_t *nf, *nb, *ob;
     if (dalloc(m, &nf, co.n_pad, s) || dalloc(m, &nb, ci.n_pad, s) || dalloc(m, &ob, ci.n_pad, s)) return 1;
@@ -1488,21 +1004,59 @@ int kernel_map(bool ex, const char *who, lgs_manager *m, int in_key, int out_key
   *out = km.release();
   return publish(m, nullptr, false);
 }
+
+// ---- segment maps (lgs_manager_segment_map): one construction per kind of coarse map, then the chunk items; sm carries the row counts
+// the origin map over the fine map `cf`: one run of sorted positions per batch index
+int seg_origin(lgs_manager *m, const CoordMap &cf, hipStream_t s, SegMap &sm) {
+  const int64_t n = sm.n_fine, nc = sm.n_coarse;
+  Scratch tmp(m, s);
+  int32_t *head, *cincl, *seg_start, *coarse_of;
+  if (dalloc(m, &seg_start, nc + 1, s) || dalloc(m, &coarse_of, n, s) || tmp.take(&head, n) || tmp.take(&cincl, n)) return 1;
+  if (key_heads(m, cf.skeys, n, kBatchMask, head, cincl, s)) return 1;
+  LGS_KLAUNCH(k_origin_segments, nblk(n), 256, 0, s, head, cincl, n, nc, seg_start, coarse_of);
+  LGS_HIP(hipGetLastError());
+  if (tmp.drop(head) || tmp.drop(cincl)) return 1;   // row_seg takes their place
+  sm.seg_start = seg_start; sm.coarse_of = coarse_of; sm.row_seg = coarse_of;
+  if (cf.order) {   // level 0: rows are in the caller's order
+    int32_t *row_seg;
+    if (dalloc(m, &row_seg, n, s)) return 1;
+    LGS_KLAUNCH(k_row_seg, nblk(n), 256, 0, s, cf.order, coarse_of, n, row_seg);
+    LGS_HIP(hipGetLastError());
+    sm.row_seg = row_seg;
+  }
+  return 0;
+}
+// a stride-2^k descendant, k >= 2: the chain's steps composed
+int seg_composed(lgs_manager *m, const Chain &ch, hipStream_t s, SegMap &sm) {
+  const int64_t n = sm.n_fine, nc = sm.n_coarse;
+  int32_t *seg_start, *coarse_of;
+  if (dalloc(m, &seg_start, nc + 1, s) || dalloc(m, &coarse_of, n, s)) return 1;
+  LGS_KLAUNCH(k_compose_coarse_of, nblk(n), 256, 0, s, ch, n, coarse_of);
+  LGS_KLAUNCH(k_compose_seg_start, nblk(nc + 1), 256, 0, s, ch, nc, seg_start);
+  LGS_HIP(hipGetLastError());
+  sm.seg_start = seg_start; sm.coarse_of = coarse_of;
+  return 0;
+}
+// the chunk items of a two-pass map: at most n / kSegChunk + nc, the tables are sized by that bound (no host synchronisation), unused slots -1
+int seg_chunk_items(lgs_manager *m, hipStream_t s, SegMap &sm) {
+  const int64_t nc = sm.n_coarse, n_items = sm.n_fine / kSegChunk + nc + 1;
+  Scratch tmp(m, s);
+  int32_t *cnt, *item_start, *item_seg;
+  if (dalloc(m, &item_start, nc + 1, s) || dalloc(m, &item_seg, n_items, s) || tmp.take(&cnt, nc)) return 1;
+  LGS_KLAUNCH(k_item_counts, nblk(nc), 256, 0, s, sm.seg_start, nc, cnt);
+  LGS_HIP(hipMemsetAsync(item_start, 0, sizeof(int32_t), s));
+  if (scan_incl(m, cnt, item_start + 1, nc, s)) return 1;
+  LGS_KLAUNCH(k_fill_i32, nblk(n_items), 256, 0, s, item_seg, n_items, -1);
+  LGS_KLAUNCH(k_item_fill, nblk(nc), 256, 0, s, item_start, nc, n_items, item_seg);
+  LGS_HIP(hipGetLastError());
+  sm.item_start = item_start; sm.item_seg = item_seg; sm.n_items = n_items;
+  return 0;
+}
 }  // namespace
 
 namespace lgs {
-int kmap_wait(lgs_kmap *km, hipStream_t stream) {
-  lgs_manager *m = km->mgr;
-  LGS_HIP(hipStreamWaitEvent(stream, m->ev_ready, 0));
-  add_user(m, stream);
-  return 0;
-}
-int segmap_wait(lgs_segmap *sm, hipStream_t stream) {
-  lgs_manager *m = sm->mgr;
-  LGS_HIP(hipStreamWaitEvent(stream, m->ev_ready, 0));
-  add_user(m, stream);
-  return 0;
-}
+int kmap_wait(lgs_kmap *km, hipStream_t stream) { return wait_ready(km->mgr, stream); }
+int segmap_wait(lgs_segmap *sm, hipStream_t stream) { return wait_ready(sm->mgr, stream); }
 }  // namespace lgs
 
 extern "C" {
@@ -1517,12 +1071,11 @@ int lgs_manager_create(int device, lgs_manager **out) {
   if (ensure_pool(device)) return 1;
   lgs_manager *m = new lgs_manager();
   m->device = device;
-  m->pool = g_pool[device];
-  // one map stream per device for the whole process (creating / destroying a stream per batch costs host time and
-  // can block): managers of consecutive steps simply queue behind each other on it
-  static hipStream_t g_map_stream[64] = {nullptr};
-  if (!g_map_stream[device]) LGS_HIP(hipStreamCreateWithFlags(&g_map_stream[device], hipStreamNonBlocking));
-  m->ms = g_map_stream[device];
+  DeviceState &d = g_dev[device];
+  m->pool = d.pool;
+  // one map stream per device for the whole process: managers of consecutive steps simply queue behind each other on it
+  if (!d.map_stream) LGS_HIP(hipStreamCreateWithFlags(&d.map_stream, hipStreamNonBlocking));
+  m->ms = d.map_stream;
   LGS_HIP(hipEventCreateWithFlags(&m->ev_ready, hipEventDisableTiming));
   LGS_HIP(hipEventCreateWithFlags(&m->ev_in, hipEventDisableTiming));
   arena_acquire(m);
@@ -1560,22 +1113,20 @@ int lgs_manager_insert(lgs_manager *m, const int32_t *coords, int64_t n, int64_t
   LGS_REQUIRE(m && key && n_unique, "lgs_manager_insert: null argument");
   LGS_REQUIRE(m->maps.empty(), "lgs_manager_insert: manager already holds a stride-1 map");
   LGS_REQUIRE(n >= 0 && n < (1ll << 31) - 1024, "lgs_manager_insert: row count out of range");
-  hipStream_t caller = (hipStream_t)stream;
-  hipStream_t s = m->ms;
+  hipStream_t caller = (hipStream_t)stream, s = m->ms;
   DeviceGuard guard(m->device);
-  m->last_stream = caller;
   if (begin_from_caller(m, caller)) return 1;   // `coords` was produced on the caller's stream
   CoordMap cm;
   if (n == 0) {
-    cm.n = 0; cm.n_pad = 0;
     m->maps.push_back(cm);
     *key = 0; *n_unique = 0;
     return 0;
   }
   if (!m->d_err) { if (dalloc(m, &m->d_err, 1, s)) return 1; }
+  Scratch tmp(m, s);   // UNDER the map's own arrays, which are sized only after the host synchronisation: their room stays a hole
   uint64_t *keys, *skeys; int32_t *vals, *svals, *head, *runid, *is_first, *urow, *lvl_counts;
-  if (dalloc(m, &lvl_counts, kPreLevels + 1, s) || dalloc(m, &keys, n, s) || dalloc(m, &skeys, n, s) || dalloc(m, &vals, n, s) || dalloc(m, &svals, n, s) ||
-      dalloc(m, &head, n, s) || dalloc(m, &runid, n, s) || dalloc(m, &is_first, n, s) || dalloc(m, &urow, n + 1, s))
+  if (tmp.take(&lvl_counts, kPreLevels + 1) || tmp.take(&keys, n) || tmp.take(&skeys, n) || tmp.take(&vals, n) || tmp.take(&svals, n) ||
+      tmp.take(&head, n) || tmp.take(&runid, n) || tmp.take(&is_first, n) || tmp.take(&urow, n + 1))
     return 1;
   // d_err, the first slot of the exclusive scan and the level counters: one launch
   if (fill_segs(s, {{m->d_err, 1, 0}, {urow, 1, 0}, {lvl_counts, kPreLevels + 1, 0}})) return 1;
@@ -1602,20 +1153,16 @@ int lgs_manager_insert(lgs_manager *m, const int32_t *coords, int64_t n, int64_t
   LGS_KLAUNCH(k_emit_sorted, nblk(n), 256, 0, s, skeys, svals, head, runid, urow, n, cm.skeys, cm.order);
   if (inverse) LGS_KLAUNCH(k_emit_inverse, nblk(n), 256, 0, s, svals, runid, cm.order, n, inverse);
   LGS_HIP(hipGetLastError());
-  if (dfree_now(m, keys, s) || dfree_now(m, skeys, s) || dfree_now(m, vals, s) || dfree_now(m, svals, s) ||
-      dfree_now(m, head, s) || dfree_now(m, runid, s) || dfree_now(m, is_first, s) || dfree_now(m, urow, s) || dfree_now(m, lvl_counts, s))
-    return 1;
   m->maps.push_back(cm);
   *key = 0; *n_unique = nu;
   return publish(m, caller, true);   // unique_index / inverse live in caller memory; `coords` may be reused after this
 }
 
-int lgs_manager_stride2(lgs_manager *m, int in_key, void *stream, int *out_key, int64_t *n_out) {
+int lgs_manager_stride2(lgs_manager *m, int in_key, void *, int *out_key, int64_t *n_out) {
   LGS_REQUIRE(m && out_key && n_out, "lgs_manager_stride2: null argument");
   LGS_REQUIRE(in_key >= 0 && in_key < (int)m->maps.size(), "lgs_manager_stride2: bad key");
   LGS_REQUIRE(!m->maps[in_key].origin, "lgs_manager_stride2: the origin map has no coarser map");
   hipStream_t s = m->ms;
-  (void)stream;
   DeviceGuard guard(m->device);
   if (m->maps[in_key].coarse_key >= 0) {
     *out_key = m->maps[in_key].coarse_key; *n_out = m->maps[*out_key].n;
@@ -1625,18 +1172,18 @@ int lgs_manager_stride2(lgs_manager *m, int in_key, void *stream, int *out_key, 
   LGS_REQUIRE(f.log2ts < 12, "lgs_manager_stride2: tensor stride too large");
   CoordMap c;
   c.ts = f.ts * 2; c.log2ts = f.log2ts + 1; c.fine_key = in_key;
-  int64_t n = f.n;
-  if (n == 0) {
+  const int64_t n = f.n;
+  auto add = [&]() {   // c becomes in_key's coarse map
     m->maps.push_back(c);
-    m->maps[in_key].coarse_key = (int)m->maps.size() - 1;
-    *out_key = m->maps[in_key].coarse_key; *n_out = 0;
-    return 0;
-  }
+    *out_key = m->maps[in_key].coarse_key = (int)m->maps.size() - 1;
+    *n_out = c.n;
+  };
+  if (n == 0) { add(); return 0; }
   uint64_t keep = ~(7ull << (3 * f.log2ts));
+  Scratch tmp(m, s);   // under the coarse map's arrays, as in the insert
   int32_t *head, *cincl;
-  if (dalloc(m, &head, n, s) || dalloc(m, &cincl, n, s)) return 1;
-  LGS_KLAUNCH(k_heads, nblk(n), 256, 0, s, f.skeys, n, keep, head);
-  if (scan_incl(m, head, cincl, n, s)) return 1;
+  if (tmp.take(&head, n) || tmp.take(&cincl, n)) return 1;
+  if (key_heads(m, f.skeys, n, keep, head, cincl, s)) return 1;
   int64_t nc;
   if (c.log2ts >= 1 && c.log2ts <= kPreLevels && m->precount[c.log2ts - 1] >= 0) {
     nc = m->precount[c.log2ts - 1];                 // counted by lgs_manager_insert: no host synchronisation here
@@ -1653,11 +1200,7 @@ int lgs_manager_stride2(lgs_manager *m, int in_key, void *stream, int *out_key, 
   LGS_KLAUNCH(k_emit_coarse, nblk(n), 256, 0, s, f.skeys, head, cincl, n, keep, c.skeys, c.coords, c.cstart,
                      c.fine_cidx, nc, m->d_err);
   LGS_HIP(hipGetLastError());
-  if (dfree_now(m, head, s) || dfree_now(m, cincl, s)) return 1;
-  m->maps.push_back(c);
-  int ck = (int)m->maps.size() - 1;
-  m->maps[in_key].coarse_key = ck;
-  *out_key = ck; *n_out = nc;
+  add();
   return publish(m, nullptr, false);
 }
 
@@ -1666,10 +1209,8 @@ int lgs_manager_check(lgs_manager *m, int *flags) {
   *flags = 0;
   if (!m->d_err) return 0;
   DeviceGuard guard(m->device);
-  int h = 0;
-  LGS_HIP(hipMemcpyAsync(&h, m->d_err, sizeof(int), hipMemcpyDeviceToHost, m->ms));
+  LGS_HIP(hipMemcpyAsync(flags, m->d_err, sizeof(int), hipMemcpyDeviceToHost, m->ms));
   LGS_HIP(hipStreamSynchronize(m->ms));
-  *flags = h;
   return 0;
 }
 
@@ -1698,13 +1239,11 @@ int lgs_manager_get_coords(lgs_manager *m, int key, int32_t *dst, void *stream) 
   return publish(m, (hipStream_t)stream, true);
 }
 
-int lgs_manager_kernel_map(lgs_manager *m, int in_key, int out_key, int ks, void *stream, lgs_kmap **out) {
-  (void)stream;
+int lgs_manager_kernel_map(lgs_manager *m, int in_key, int out_key, int ks, void *, lgs_kmap **out) {
   return kernel_map(false, "lgs_manager_kernel_map", m, in_key, out_key, ks, 1, out);
 }
 
-int lgs_manager_kernel_map_ex(lgs_manager *m, int in_key, int out_key, int ks, int dilation, void *stream, lgs_kmap **out) {
-  (void)stream;
+int lgs_manager_kernel_map_ex(lgs_manager *m, int in_key, int out_key, int ks, int dilation, void *, lgs_kmap **out) {
   return kernel_map(true, "lgs_manager_kernel_map_ex", m, in_key, out_key, ks, dilation, out);
 }
 
@@ -1743,10 +1282,9 @@ int lgs_debug_kmap_tables(lgs_kmap *km, int bwd, int32_t *nbr, int32_t *out_row,
   return publish(m, caller, true);
 }
 
-int lgs_manager_origin(lgs_manager *m, void *stream, int *out_key, int64_t *n_out) {
+int lgs_manager_origin(lgs_manager *m, void *, int *out_key, int64_t *n_out) {
   LGS_REQUIRE(m && out_key && n_out, "lgs_manager_origin: null argument");
   LGS_REQUIRE(!m->maps.empty(), "lgs_manager_origin: the manager holds no map yet");
-  (void)stream;
   if (m->origin_key >= 0) {
     *out_key = m->origin_key; *n_out = m->maps[m->origin_key].n;
     return 0;
@@ -1761,12 +1299,12 @@ int lgs_manager_origin(lgs_manager *m, void *stream, int *out_key, int64_t *n_ou
   LGS_REQUIRE(nb >= 0, "lgs_manager_origin: batch count unknown");
   o.n = nb; o.n_pad = pad_rows(nb);
   if (n > 0) {
+    Scratch tmp(m, s);
     int32_t *head, *cincl;
-    if (dalloc(m, &o.coords, nb * 4, s) || dalloc(m, &head, n, s) || dalloc(m, &cincl, n, s)) return 1;
-    if (batch_heads(m, f.skeys, n, head, cincl, s)) return 1;
+    if (dalloc(m, &o.coords, nb * 4, s) || tmp.take(&head, n) || tmp.take(&cincl, n)) return 1;
+    if (key_heads(m, f.skeys, n, kBatchMask, head, cincl, s)) return 1;
     LGS_KLAUNCH(k_origin_coords, nblk(n), 256, 0, s, f.skeys, head, cincl, n, nb, o.coords, m->d_err);
     LGS_HIP(hipGetLastError());
-    if (dfree_now(m, head, s) || dfree_now(m, cincl, s)) return 1;
   }
   m->maps.push_back(o);
   m->origin_key = (int)m->maps.size() - 1;
@@ -1774,16 +1312,14 @@ int lgs_manager_origin(lgs_manager *m, void *stream, int *out_key, int64_t *n_ou
   return publish(m, nullptr, false);
 }
 
-int lgs_manager_segment_map(lgs_manager *m, int fine_key, int coarse_key, void *stream, lgs_segmap **out) {
+int lgs_manager_segment_map(lgs_manager *m, int fine_key, int coarse_key, void *, lgs_segmap **out) {
   LGS_REQUIRE(m && out, "lgs_manager_segment_map: null argument");
   const int nm = (int)m->maps.size();
   LGS_REQUIRE(fine_key >= 0 && fine_key < nm && coarse_key >= 0 && coarse_key < nm, "lgs_manager_segment_map: bad key");
   LGS_REQUIRE(!m->maps[fine_key].origin, "lgs_manager_segment_map: the fine map is the origin map");
   for (lgs_segmap *k : m->segmaps)
     if (k->fine_key == fine_key && k->coarse_key == coarse_key) { *out = k; return 0; }
-  (void)stream;
-  const CoordMap &cf = m->maps[fine_key];
-  const CoordMap &cc = m->maps[coarse_key];
+  const CoordMap &cf = m->maps[fine_key], &cc = m->maps[coarse_key];
   Chain ch;
   ch.k = 0;
   if (!cc.origin) {   // walk coarse -> fine through the maps stride2 made
@@ -1808,48 +1344,11 @@ int lgs_manager_segment_map(lgs_manager *m, int fine_key, int coarse_key, void *
   sm.n_fine = cf.n; sm.n_coarse = cc.n;
   sm.fine_row = cf.order;
   sm.max_len = cc.origin ? 0 : (int64_t)1 << (3 * ch.k);
-  const int64_t n = cf.n, nc = cc.n;
-  if (n > 0) {
-    if (cc.origin) {
-      int32_t *head, *cincl, *seg_start, *coarse_of;
-      if (dalloc(m, &seg_start, nc + 1, s) || dalloc(m, &coarse_of, n, s) || dalloc(m, &head, n, s) || dalloc(m, &cincl, n, s))
-        return 1;
-      if (batch_heads(m, cf.skeys, n, head, cincl, s)) return 1;
-      LGS_KLAUNCH(k_origin_segments, nblk(n), 256, 0, s, head, cincl, n, nc, seg_start, coarse_of);
-      LGS_HIP(hipGetLastError());
-      if (dfree_now(m, head, s) || dfree_now(m, cincl, s)) return 1;
-      sm.seg_start = seg_start; sm.coarse_of = coarse_of; sm.row_seg = coarse_of;
-      if (cf.order) {   // level 0: rows are in the caller's order
-        int32_t *row_seg;
-        if (dalloc(m, &row_seg, n, s)) return 1;
-        LGS_KLAUNCH(k_row_seg, nblk(n), 256, 0, s, cf.order, coarse_of, n, row_seg);
-        LGS_HIP(hipGetLastError());
-        sm.row_seg = row_seg;
-      }
-    } else if (ch.k == 1) {                    // one stride-2 step: its own arrays are the segment map
+  if (cf.n > 0) {
+    if (!cc.origin && ch.k == 1) {             // one stride-2 step: its own arrays are the segment map
       sm.seg_start = ch.cstart[0]; sm.coarse_of = ch.fine_cidx[0];
-    } else {
-      int32_t *seg_start, *coarse_of;
-      if (dalloc(m, &seg_start, nc + 1, s) || dalloc(m, &coarse_of, n, s)) return 1;
-      LGS_KLAUNCH(k_compose_coarse_of, nblk(n), 256, 0, s, ch, n, coarse_of);
-      LGS_KLAUNCH(k_compose_seg_start, nblk(nc + 1), 256, 0, s, ch, nc, seg_start);
-      LGS_HIP(hipGetLastError());
-      sm.seg_start = seg_start; sm.coarse_of = coarse_of;
-    }
-    if (!sm.single_pass()) {
-      // at most n / kSegChunk + nc items: the tables are sized by that bound (no host synchronisation), unused slots -1
-      const int64_t n_items = n / kSegChunk + nc + 1;
-      int32_t *cnt, *item_start, *item_seg;
-      if (dalloc(m, &item_start, nc + 1, s) || dalloc(m, &item_seg, n_items, s) || dalloc(m, &cnt, nc, s)) return 1;
-      LGS_KLAUNCH(k_item_counts, nblk(nc), 256, 0, s, sm.seg_start, nc, cnt);
-      LGS_HIP(hipMemsetAsync(item_start, 0, sizeof(int32_t), s));
-      if (scan_incl(m, cnt, item_start + 1, nc, s)) return 1;
-      LGS_KLAUNCH(k_fill_i32, nblk(n_items), 256, 0, s, item_seg, n_items, -1);
-      LGS_KLAUNCH(k_item_fill, nblk(nc), 256, 0, s, item_start, nc, n_items, item_seg);
-      LGS_HIP(hipGetLastError());
-      if (dfree_now(m, cnt, s)) return 1;
-      sm.item_start = item_start; sm.item_seg = item_seg; sm.n_items = n_items;
-    }
+    } else if (cc.origin ? seg_origin(m, cf, s, sm) : seg_composed(m, ch, s, sm)) return 1;
+    if (!sm.single_pass() && seg_chunk_items(m, s, sm)) return 1;
   }
   lgs_segmap *h = new lgs_segmap();
   h->mgr = m; h->fine_key = fine_key; h->coarse_key = coarse_key; h->sm = sm;
@@ -1861,13 +1360,13 @@ int lgs_manager_segment_map(lgs_manager *m, int fine_key, int coarse_key, void *
 int lgs_kmap_export(lgs_kmap *km, int32_t *ek, int32_t *ein, int32_t *eout, void *stream, int64_t *mcount) {
   LGS_REQUIRE(km && mcount, "lgs_kmap_export: null argument");
   lgs_manager *m = km->mgr;
-  hipStream_t caller = (hipStream_t)stream;
-  hipStream_t s = m->ms;
+  hipStream_t caller = (hipStream_t)stream, s = m->ms;
   DeviceGuard guard(m->device);
   if (begin_from_caller(m, caller)) return 1;   // the output buffers were allocated on the caller's stream
   const View &v = km->fwd;
+  Scratch tmp(m, s);
   int32_t *cnt;
-  if (raw_alloc(m, (void **)&cnt, sizeof(int32_t), s)) return 1;
+  if (tmp.take(&cnt, 1)) return 1;
   LGS_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t), s));
   if (v.n_pad > 0) {
     if (ek) LGS_KLAUNCH(k_view_export, nblk(v.n_pad), 256, 0, s, v, cnt, ek, ein, eout);
@@ -1876,7 +1375,6 @@ int lgs_kmap_export(lgs_kmap *km, int32_t *ek, int32_t *ein, int32_t *eout, void
   int32_t h = 0;
   LGS_HIP(hipMemcpyAsync(&h, cnt, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   LGS_HIP(hipStreamSynchronize(s));
-  if (dfree_now(m, cnt, s)) return 1;
   *mcount = h;
   return publish(m, caller, true);
 }
