@@ -106,6 +106,27 @@ int lgs_manager_map_size(lgs_manager *mgr, int key, int64_t *n, int *tensor_stri
 /* coords of map `key` into dst (device int32 [n,4]); replaces SparseTensor.C (pl_BaselineTrainer.py:384) */
 int lgs_manager_get_coords(lgs_manager *mgr, int key, int32_t *dst, void *stream);
 
+/* Nearest site of map `key` for every one of m points: rows[i] = the ROW of the map (at any tensor stride ts) whose site is nearest
+ * to point i, -1 where there is none.  A NEW SYMBOL ONLY: LGS_ABI_VERSION stays 18.
+ * The site frame: the sites are the integer lattice points c / ts.  Point q of scene s becomes p = (A_s (q, 1)) / ts - anchor, A_s the
+ * scene's 3x4 row-major affine evaluated in double as lgs_voxelize does (affines: HOST double [b, 12], read during the call; NULL =
+ * the identity).  anchor = 0.0 measures to the voxel corners coords * voxel_size (test_pointcloud's KD-tree), 0.5 to the voxel
+ * centres coords + 0.5 (get_original_pointcloud).  With h = rint(p) and f = p - h rounded to fp32 once, the distance to the site at
+ * integer offset k from h is d2 = ((f.x - k.x)^2 + (f.y - k.y)^2) + (f.z - k.z)^2 in fp32, each step rounded, in this order; the
+ * smallest (d2, row) wins, so among equal d2 the smallest row index.  d2 (device float [m], or NULL) receives it, in site-frame
+ * units squared.  Nearest in the site frame is nearest in world space only where A_s is a similarity.
+ * scene_offsets: DEVICE int64 [b + 1] as in lgs_voxelize_batched, 1 <= b <= LGS_AUG_MAX_SCENES; points of scene s are matched only
+ * against sites with batch index batch_base + s.  A non-finite point, and a point of a scene without sites, gets row -1 and
+ * d2 = +inf; a map without rows gives that to every point; m == 0 launches nothing.
+ * How: a ring search through the map's lookup table (block directory or hash, MAP_BLOCK_DIR) up to ring NEAREST_MAX_RING, then an
+ * exact scan of the scene's sorted keys for what is left -- same arithmetic, same answer at every knob value.  No host
+ * synchronisation: the work runs on the map stream, after the caller's pending work and before its later work.
+ * Null arguments, unknown keys and the origin map are refused.
+ * replaces: spatial.KDTree(pred[:, :3]).query(query_xyz)          /root/reference/lib/datasets/scannet.py:420-421
+ *           the pykeops argKmin of get_original_pointcloud         /root/reference/downstream/insseg/datasets/scannet.py:161-169 */
+int lgs_manager_nearest(lgs_manager *mgr, int key, const float *points, int64_t m, const int64_t *scene_offsets, int b,
+                        int batch_base, const double *affines, double anchor, int64_t *rows, float *d2, void *stream);
+
 /* Kernel map between two maps of this manager (cached per (in_key,out_key,kernel_size)).
  *   kernel_size 3, in_key == out_key            : 3x3x3 stride-1 (a4)
  *   kernel_size 2, out_key == stride2(in_key)   : 2x2x2 stride-2 (a5); the transposed conv (a6)

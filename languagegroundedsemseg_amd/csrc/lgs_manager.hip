@@ -16,6 +16,7 @@
 #include "lgs_arena.h"     // the arena's bump stack (host arithmetic, no HIP)
 #include "lgs_mapkeys.h"   // Morton keys, HashRef / DirRef and their table kernels
 #include "lgs_mapsort.h"   // window mask sort and row permutation kernels
+#include "lgs_nearest.h"   // nearest-site query: ring search through the lookup table, exact scan for the rest
 
 namespace lgs {
 
@@ -1237,6 +1238,49 @@ int lgs_manager_get_coords(lgs_manager *m, int key, int32_t *dst, void *stream) 
   if (cm.n > 0)
     LGS_HIP(hipMemcpyAsync(dst, cm.coords, sizeof(int32_t) * 4 * (size_t)cm.n, hipMemcpyDeviceToDevice, m->ms));
   return publish(m, (hipStream_t)stream, true);
+}
+
+// Nearest site of map `key` for m points (lgs_nearest.h).  Runs on the map stream, between the caller's pending work and its later
+// work, like lgs_manager_get_coords: the lookup table may have to be built there, and the leftover list is scoped scratch of the arena,
+// whose reuse is ordered by that stream alone.  No host synchronisation: the exact scan is launched with a fixed grid and reads the
+// list's length on the device.
+int lgs_manager_nearest(lgs_manager *m, int key, const float *points, int64_t mq, const int64_t *scene_offsets, int b, int batch_base,
+                        const double *affines, double anchor, int64_t *rows, float *d2, void *stream) {
+  LGS_REQUIRE(m != nullptr, "lgs_manager_nearest: null argument");
+  LGS_REQUIRE(key >= 0 && key < (int)m->maps.size(), "lgs_manager_nearest: bad key");
+  LGS_REQUIRE(!m->maps[key].origin, "lgs_manager_nearest: the origin map has no sites to search");
+  LGS_REQUIRE(mq >= 0 && mq < (1ll << 31) - 1024, "lgs_manager_nearest: point count out of range");
+  LGS_REQUIRE(mq == 0 || (points && scene_offsets && rows), "lgs_manager_nearest: null argument");   // no points: nothing is read or written
+  LGS_REQUIRE(b >= 1 && b <= kNearestScenes, "lgs_manager_nearest: 1 <= b <= LGS_AUG_MAX_SCENES");
+  LGS_REQUIRE(batch_base >= 0 && batch_base + b <= 1024, "lgs_manager_nearest: batch index out of range");
+  LGS_REQUIRE(anchor == anchor && anchor - anchor == 0.0, "lgs_manager_nearest: anchor must be finite");
+  if (mq == 0) return 0;
+  hipStream_t caller = (hipStream_t)stream, s = m->ms;
+  DeviceGuard guard(m->device);
+  if (begin_from_caller(m, caller)) return 1;   // points, scene_offsets and the outputs belong to the caller's stream
+  CoordMap &cm = m->maps[key];
+  if (cm.n == 0) {
+    LGS_KLAUNCH(k_nearest_none, nblk(mq), 256, 0, s, mq, rows, d2);
+    LGS_HIP(hipGetLastError());
+    return publish(m, caller, true);
+  }
+  if (ensure_lookup(m, cm, s)) return 1;
+  NearestArgs q = {points, scene_offsets, mq, b, affines ? 1 : 0, batch_base, cm.log2ts, 1.0 / (double)cm.ts, anchor};
+  NearestAffines A = {};
+  if (affines) std::memcpy(&A, affines, sizeof(double) * 12 * (size_t)b);
+  int64_t ring = tune(T_NEAREST_MAX_RING);
+  ring = ring < 0 ? 0 : (ring > 64 ? 64 : ring);
+  Scratch tmp(m, s);
+  int32_t *left, *n_left;
+  if (tmp.take(&n_left, 1) || tmp.take(&left, mq)) return 1;
+  LGS_HIP(hipMemsetAsync(n_left, 0, sizeof(int32_t), s));
+  if (use_block_dir())
+    LGS_KLAUNCH(k_nearest_ring<DirRef>, nblk(mq), 256, 0, s, q, A, dir_ref(cm), (int)ring, rows, d2, left, n_left);
+  else
+    LGS_KLAUNCH(k_nearest_ring<HashRef>, nblk(mq), 256, 0, s, q, A, hash_ref(cm), (int)ring, rows, d2, left, n_left);
+  LGS_KLAUNCH(k_nearest_scan, kNearestScanGrid, 256, 0, s, q, A, cm.skeys, cm.order, cm.n, left, n_left, rows, d2);
+  LGS_HIP(hipGetLastError());
+  return publish(m, caller, true);
 }
 
 int lgs_manager_kernel_map(lgs_manager *m, int in_key, int out_key, int ks, void *, lgs_kmap **out) {

@@ -119,6 +119,11 @@ const Knob kKnobs[T_COUNT] = {
     {T_CONV_ROW_TRIM, "CONV_ROW_TRIM", 1, "k_conv_gather tile 0 on rows of one 16-byte piece (conv0's 3 colour channels padded to 8; needs CONV_SLAB_TRIM): 1 = only "
                                           "the first of a chunk's two gathers is issued, the fragment of the second piece is a zero register; 0 = both "
                                           "(the second is out of range in every lane).  Bit-identical"},
+    {T_NEAREST_MAX_RING, "NEAREST_MAX_RING", 2, "lgs_manager_nearest: the last ring of cells (Chebyshev distance from the query's home cell) that k_nearest_ring searches "
+                                                "through the map's lookup table before a query goes to the exact scan of its scene's keys (k_nearest_scan).  The "
+                                                "answer is the same at every value (tests/test_gpu_nearest.py).  3.6 M points inside the occupied cells of the 8-scene, "
+                                                "1.2 M-voxel batch, block directory, voxel corners / centres as sites: 1 = 1.056 / 0.514 ms with 0.025 % / 0 of the "
+                                                "queries left to the scan, 2 = 0.611 / 0.514 ms with none, 4 = the same as 2 (tools/microbench.py nearest)"},
 };
 std::atomic<int64_t> g_val[T_COUNT];
 std::once_flag g_once;

@@ -202,7 +202,8 @@ EXPORTS = [
     "lgs_tuning_set", "lgs_tuning_get", "lgs_tuning_describe", "lgs_debug_dispatch_counts", "lgs_debug_conv_plan", "lgs_debug_wgrad_plan",
     "lgs_debug_norm_plan", "lgs_debug_instnorm_plan", "lgs_debug_seg_plan", "lgs_debug_kmap_relation",
     "lgs_manager_create", "lgs_manager_destroy", "lgs_manager_insert", "lgs_manager_stride2", "lgs_manager_check",
-    "lgs_manager_parent_of", "lgs_manager_map_size", "lgs_manager_get_coords", "lgs_manager_kernel_map", "lgs_manager_kernel_map_ex",
+    "lgs_manager_parent_of", "lgs_manager_map_size", "lgs_manager_get_coords", "lgs_manager_nearest", "lgs_manager_kernel_map",
+    "lgs_manager_kernel_map_ex",
     "lgs_kmap_export", "lgs_debug_kmap_tables",
     "lgs_manager_origin", "lgs_manager_segment_map", "lgs_segmap_size", "lgs_seg_workspace_bytes", "lgs_seg_reduce",
     "lgs_seg_broadcast", "lgs_seg_max_backward",
@@ -263,6 +264,7 @@ def lib():
         "lgs_manager_parent_of": [vp, ci, pi],
         "lgs_manager_map_size": [vp, ci, pi64, pi],
         "lgs_manager_get_coords": [vp, ci, vp, vp],
+        "lgs_manager_nearest": [vp, ci, vp, i64, vp, ci, ci, ctypes.POINTER(ctypes.c_double), ctypes.c_double, vp, vp, vp],
         "lgs_manager_kernel_map": [vp, ci, ci, ci, vp, pvp],
         "lgs_manager_kernel_map_ex": [vp, ci, ci, ci, ci, vp, pvp],
         "lgs_kmap_export": [vp, vp, vp, vp, vp, pi64],

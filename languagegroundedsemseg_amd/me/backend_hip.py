@@ -487,6 +487,25 @@ class HipManager:
             self._coords[key] = c
         return self._coords[key]
 
+    def nearest(self, key, points, scene_offsets, b, batch_base=0, affines=None, anchor=0.5, want_d2=False):
+        """rows int64 [M] (and d2 float32 [M], site-frame units squared) of the sites of map `key` nearest to points [M, 3] float32
+        (lgs_manager_nearest; no synchronisation).  scene_offsets: device int64 [b + 1]; affines: None or b x 12 host doubles."""
+        _require_dev(points, "points")
+        _require_dev(scene_offsets, "scene_offsets")
+        m = points.shape[0]
+        a12 = None
+        if affines is not None:
+            flat = [float(v) for v in affines]
+            if len(flat) != 12 * b:
+                raise ValueError("nearest: %d affine values for %d scenes" % (len(flat), b))
+            a12 = (ctypes.c_double * len(flat))(*flat)
+        with _dev(self.device):
+            rows = torch.empty(m, dtype=torch.int64, device=self.device)
+            d2 = torch.empty(m, dtype=torch.float32, device=self.device) if want_d2 else None
+            engine.check(engine.lib().lgs_manager_nearest(self.h, key, _ptr(points), m, _ptr(scene_offsets), b, int(batch_base), a12,
+                                                          float(anchor), _ptr(rows), _ptr(d2), _stream()))
+        return rows, d2
+
     def origin(self):
         """key of the origin map: one row (b, 0, 0, 0) per batch index, ascending (lgs_manager_origin; no synchronisation)"""
         ok, n = ctypes.c_int(0), ctypes.c_int64(0)

@@ -1,5 +1,5 @@
 """Per-op timings on the GPU (HIP events on torch's current stream) for the hot layer shapes.
-usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal | supcon | augment]"""
+usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal | supcon | augment | nearest]"""
 import os
 import sys
 import time
@@ -666,7 +666,64 @@ def augment():
           % (sum(t_cpu.values()) * 1e3, 8 * sum(t_cpu.values()) * 1e3, t_chain))
 
 
+def nearest():
+    """lgs_manager_nearest at the evaluation shape -- 8 scenes x ~150 k voxels, three points inside every occupied cell -- at
+    NEAREST_MAX_RING 1, 2 and 4, anchors 0.0 and 0.5, with both lookup tables, and the share of queries that the ring search leaves to
+    the exact scan (read off the returned d2: a query is unfinished after ring r exactly when d2 >= (r + 1/2)^2).  Beside it, on ONE
+    scene (the insseg validation is one scene per iteration): a chunked torch.cdist arg-min on the device, the brute force
+    get_original_pointcloud does today, and scipy's cKDTree on one host core, the search of test_pointcloud."""
+    from scipy.spatial import cKDTree
+    from languagegroundedsemseg_amd import engine
+    from languagegroundedsemseg_amd.pointcloud import nearest_voxel
+    scenes = int(sys.argv[2]) if len(sys.argv) > 2 else 8
+    coords, _, _ = make_batch(list(range(scenes)))
+    rng = np.random.default_rng(0)
+    pts, off = [], [0]
+    for s in range(scenes):
+        c = coords[coords[:, 0] == s][:, 1:].astype(np.float64)
+        pts.append((np.repeat(c, 3, 0) + rng.random((3 * len(c), 3))).astype(np.float32))
+        off.append(off[-1] + len(pts[-1]))
+    q = torch.from_numpy(np.concatenate(pts)).to(DEV)
+    off_dev = torch.tensor(off, dtype=torch.int64, device=DEV)
+    c_dev = torch.from_numpy(coords).to(DEV)
+    x = ME.SparseTensor(torch.zeros(len(coords), 1, device=DEV), c_dev)
+    print("%d scenes, %d voxels, %d queries" % (scenes, len(coords), q.shape[0]))
+    for table in (1, 0):
+        for anchor in (0.0, 0.5):
+            for ring in (1, 2, 4):
+                with engine.tuning(MAP_BLOCK_DIR=table, NEAREST_MAX_RING=ring):
+                    ts = [timeit(lambda: nearest_voxel(x, q, off_dev, None, anchor, return_distance=True), 200, 5) for _ in range(3)]
+                    _, d2 = nearest_voxel(x, q, off_dev, None, anchor, return_distance=True)
+                    left = float((d2 >= (ring + 0.5) ** 2).float().mean())
+                print("lgs_manager_nearest  MAP_BLOCK_DIR=%d anchor %.1f NEAREST_MAX_RING=%d  %8.3f ms (median %8.3f)  to the exact scan: %.5f %%"
+                      % (table, anchor, ring, min(ts), sorted(ts)[1], 100.0 * left))
+    # one scene: the engine, the device brute force, the host KD-tree
+    s0 = slice(off[0], off[1])
+    q0, sites0 = q[s0], c_dev[c_dev[:, 0] == 0][:, 1:].float() + 0.5
+    one = ME.SparseTensor(torch.zeros(sites0.shape[0], 1, device=DEV), c_dev[c_dev[:, 0] == 0].contiguous())
+    t_one = min(timeit(lambda: nearest_voxel(one, q0, None, None, 0.5), 500, 5) for _ in range(3))
+    rows = nearest_voxel(one, q0, None, None, 0.5)
+
+    def brute(chunk=2048):
+        out = torch.empty(q0.shape[0], dtype=torch.int64, device=DEV)
+        for i in range(0, q0.shape[0], chunk):
+            out[i:i + chunk] = torch.cdist(q0[i:i + chunk], sites0).argmin(1)
+        return out
+    t_brute = timeit(brute, 1, 1)
+    agree = float((brute() == rows).float().mean())
+    t0 = time.perf_counter()
+    tree = cKDTree(sites0.double().cpu().numpy())
+    _, idx = tree.query(q0.double().cpu().numpy(), workers=1)
+    t_tree = (time.perf_counter() - t0) * 1e3
+    agree_tree = float((torch.from_numpy(idx).to(DEV) == rows).float().mean())
+    print("scene 0 (%d voxels, %d queries), anchor 0.5: lgs_manager_nearest %.3f ms | chunked torch.cdist arg-min %.1f ms (same rows: %.5f) | "
+          "cKDTree build + query, one core %.1f ms (same rows: %.5f)" % (sites0.shape[0], q0.shape[0], t_one, t_brute, agree, t_tree, agree_tree))
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "nearest":
+        nearest()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "augment":
         augment()
         sys.exit(0)
