@@ -772,6 +772,28 @@ int lgs_ce_weight_sum(const int64_t *labels, int64_t n, int c, int64_t ignore_in
 int lgs_seg_metrics(const void *scores, int64_t n, int c, const int64_t *labels, int64_t ignore_index, int64_t *pred, float *prob,
                     int64_t *confmat, int dtype, void *stream);
 
+/* ---- per-class average precision (csrc/lgs_ap.hip) -----------------------------------------------
+ * replaces: AveragePrecision(num_classes, average=None)(prob, target) of every validation step
+ *   (lib/train_test/pl_BaselineTrainer.py:380, downstream/insseg/lib/pl_Trainer.py:316) and sklearn's average_precision_score per class
+ *   (downstream/insseg/lib/test.py:58-62, :215): C sorts of N scores, driven from the host
+ * NEW SYMBOLS ONLY: LGS_ABI_VERSION stays 18; a library that lacks them lacks the capability.
+ * ap_out[c] (DEVICE double, overwritten): sklearn's step-wise AP of every class, as
+ *   AP_c = (1 / P_c) sum over the rows i with labels[i] == c of TP_c(s_i) / Rank_c(s_i),   s_i = prob[i, c],
+ *   TP_c(s) = #{ j : labels[j] == c, prob[j, c] >= s },  Rank_c(s) = #{ j : prob[j, c] >= s } over ALL n rows
+ * A row is a positive of its label's class iff labels[i] != ignore_index and 0 <= labels[i] < c; every other row is a negative of every
+ * class.  A class without a positive gives NaN.  -0 ties with +0.  n == 0 is legal (all NaN, no workspace needed).
+ * scores[n, c]: float32 / bf16, contiguous rows, class counts as lgs_seg_metrics (<= 512 fp32, <= 1024 bf16).  from_logits == 0: they
+ * are the probabilities (any finite values rank).  from_logits != 0: prob is the fp32 softmax of the values as stored, with the very
+ * expressions of lgs_seg_metrics' prob: the result equals, bit for bit, the call on that prob with from_logits == 0.
+ * The positives are sorted (one radix sort of n 64-bit keys), every element of the matrix is counted against the sorted positives of
+ * its column in one more pass, and the terms are added in fp64 in a fixed order: integer counts and one summation order, so two calls
+ * give the same bits.  Enqueues on `stream`, never synchronises.  NaN scores are not supported: the result of a class they touch is
+ * unspecified (nothing is read or written out of bounds).
+ * workspace: lgs_ap_workspace_bytes(n, c) bytes (-1: c outside 1 .. 1024, n < 0, or the size query failed). */
+int64_t lgs_ap_workspace_bytes(int64_t n, int c);
+int lgs_average_precision(const void *scores, int64_t n, int c, const int64_t *labels, int64_t ignore_index, int from_logits,
+                          double *ap_out /* [c] */, int dtype, void *workspace, void *stream);
+
 /* ---- supervised point-contrastive loss (csrc/lgs_supcon.hip) -------------------------------------
  * replaces: PointSupConLoss.forward (lib/losses/PointSupConLoss.py:74-154), the third embedding criterion of
  *   BaselineTrainerModule.init_criterions (lib/train_test/pl_BaselineTrainer.py:92-108): per class of the batch three device -> host

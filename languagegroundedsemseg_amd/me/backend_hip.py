@@ -1284,6 +1284,36 @@ class HipBackend:
                                            _dtype_code(scores), _stream()))
         return pred, prob
 
+    # ---- per-class average precision: lgs_average_precision
+    @staticmethod
+    def average_precision_supports(scores):
+        """fp32 or bf16 scores of at most class_limit classes"""
+        return scores.dtype in (torch.float32, torch.bfloat16) and 1 <= scores.shape[1] <= HipBackend.class_limit(scores.dtype)
+
+    def average_precision(self, scores, labels, ignore_index, from_logits=False):
+        """scores [N, C] -> float64 [C]: sklearn's step-wise AP of every class, NaN for a class without a positive row (the rows with
+        a label in [0, C) other than ignore_index are the positives of their class; every other row is a negative of all).
+        from_logits: rank the fp32 softmax of the scores -- the very bits seg_metrics' prob holds -- without materialising it.
+        Sorted positives, one counting pass over the scores; no host sync."""
+        _require_dev(scores, "scores")
+        L = engine.lib()
+        scores = scores.detach().contiguous()
+        labels = labels.contiguous().to(torch.int64)
+        n, c = scores.shape
+        if labels.shape[0] != n:
+            raise RuntimeError("average_precision: %d labels for %d rows" % (labels.shape[0], n))
+        with _dev(scores.device):
+            ap = torch.empty(c, dtype=torch.float64, device=scores.device)
+            ws = None
+            if n > 0:
+                nbytes = memo(_QUERIES, ("ap_ws", n, c), L.lgs_ap_workspace_bytes, n, c)
+                if nbytes < 0:
+                    raise RuntimeError("average_precision: lgs_ap_workspace_bytes(%d, %d) failed" % (n, c))
+                ws = _ws(nbytes, scores.device)
+            engine.check(L.lgs_average_precision(_ptr(scores), n, c, _ptr(labels), int(ignore_index), 1 if from_logits else 0, _ptr(ap),
+                                                 _dtype_code(scores), _ptr(ws), _stream()))
+        return ap
+
     # ---- supervised point-contrastive loss: lgs_supcon_sample / lgs_supcon_forward / lgs_supcon_backward
     SUPCON_MAX_SAMPLES = 8
     _SUPCON_DISTANCE = {"cos": engine.LGS_SUPCON_COS, "l2": engine.LGS_SUPCON_L2}

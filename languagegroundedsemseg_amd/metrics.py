@@ -2,11 +2,16 @@
 
 The reference measures itself in EVERY step: `BaselineTrainerModule.eval_step` (lib/train_test/pl_BaselineTrainer.py:357-378) takes
 `pred = soutput.F.max(1)[1]`, `prob = softmax(soutput.F, 1)` and feeds torchmetrics' Precision / Recall / JaccardIndex, once over all
-valid rows and once over each of the head / common / tail row subsets.  Everything it logs from them (except the per-class average
-precision, which stays on torch and takes `prob` from here) is a function of ONE integer matrix: the confusion matrix of the valid
+valid rows and once over each of the head / common / tail row subsets.  Everything it logs from them except the per-class average
+precision is a function of ONE integer matrix: the confusion matrix of the valid
 rows, and -- because `split_items[:, g]` is `valid & group_of_class[target] == g` -- the three subsets are row subsets of the same
 matrix.  `SegmentationMeter.update` is one pass over the scores (lgs_seg_metrics on HIP tensors); `compute` derives the numbers on
 the device.
+
+The per-class average precision (pl_BaselineTrainer.py:380: `AveragePrecision(num_classes, average=None)(prob, target)`, stacked per
+step and nanmean-ed per class) is `average_precision` / `AveragePrecisionMeter`: sklearn's step-wise AP, computed from the sorted
+positives and one counting pass over the scores (lgs_average_precision on HIP tensors), also straight from the logits, so that a
+validation step needs no fp32 [N, C] `prob` at all.
 
 The definitions below are THIS PROJECT'S (the reference's torchmetrics version is not a dependency here and its exact averaging
 conventions were not reproduced); they are not a parity claim.  Only `fast_hist` / `per_class_iu` restate reference code
@@ -133,6 +138,97 @@ class SegmentationMeter(nn.Module):
             cm = cm.clone()
             dist.all_reduce(cm, op=dist.ReduceOp.SUM, group=process_group)
         return confusion_metrics(cm, groups)
+
+
+def _torch_average_precision(scores, target, ignore_label, from_logits):
+    """lgs_average_precision's semantics in torch lines (sort, searchsorted): CPU tensors and heads wider than one half-wave holds.
+    AP_c = (1 / P_c) sum over the positives i of c of TP_c(s_i) / Rank_c(s_i): TP_c(s) = #{positives j of c: prob[j, c] >= s},
+    Rank_c(s) = #{all rows j: prob[j, c] >= s}."""
+    x = scores.float()
+    prob = (torch.softmax(x, 1) if from_logits else x).to(torch.float64)
+    n, c = prob.shape
+    t = target.long()
+    cols = prob.t().contiguous()                                                        # [C, N]
+    is_pos = ((t != ignore_label) & (t >= 0) & (t < c))[None, :] & (t[None, :] == torch.arange(c, device=t.device)[:, None])
+    p = is_pos.sum(1)
+    rank = n - torch.searchsorted(cols.sort(1).values, cols, right=False)               # rows with a score >= this one, per column
+    inf = torch.full_like(cols, float("inf"))
+    pos_sorted = torch.where(is_pos, cols, inf).sort(1).values                          # the positives first, then the padding
+    tp = p[:, None] - torch.searchsorted(pos_sorted, cols, right=False)                 # positives with a score >= this one
+    terms = torch.where(is_pos, tp.to(torch.float64) / rank.clamp_min(1).to(torch.float64), torch.zeros_like(cols))
+    nan = torch.full((c,), float("nan"), dtype=torch.float64, device=prob.device)
+    return torch.where(p > 0, terms.sum(1) / p.clamp_min(1).to(torch.float64), nan)
+
+
+@torch.no_grad()
+def average_precision(scores, target, ignore_label=-1, from_logits=False):
+    """scores [N, C] (tensor or SparseTensor), target [N] -> float64 [C] on the scores' device: per class, sklearn's
+    average_precision_score of the column against `target == c` (torchmetrics' AveragePrecision(num_classes, average=None)).
+    A class without a positive row gives NaN (what a nanmean over steps expects).  Rows whose target is ignore_label or outside
+    [0, C) are negatives of every class (label_binarize).  Equal scores share one threshold; -0.0 ties with +0.0.
+    from_logits: rank the fp32 softmax of `scores` instead -- bit for bit the result on SegmentationMeter.update(...,
+    want_prob=True)'s prob, without the [N, C] fp32 tensor.  HIP tensors of at most 512 (fp32) / 1024 (bf16) classes go to the
+    engine (lgs_average_precision: no host sync, two calls give the same bits), everything else takes the same formula in torch.
+    NaN scores are not supported: the result of a class they touch is unspecified (nothing is read out of bounds)."""
+    scores = _features(scores).detach()
+    if scores.dim() != 2:
+        raise ValueError("scores must be [N, C], got %s" % (tuple(scores.shape),))
+    if target.shape[0] != scores.shape[0]:
+        raise ValueError("%d targets for %d rows" % (target.shape[0], scores.shape[0]))
+    target = target.to(scores.device)
+    be = get_backend()
+    if scores.is_cuda and hasattr(be, "average_precision") and be.average_precision_supports(scores):
+        return be.average_precision(scores, target, ignore_label, from_logits)
+    return _torch_average_precision(scores, target, ignore_label, from_logits)
+
+
+class AveragePrecisionMeter(nn.Module):
+    """Per-class average precision over a run of steps, kept on the device: the reference stacks the [C] result of every validation
+    step and takes the nanmean per class (pl_BaselineTrainer.py:380).
+
+        meter = AveragePrecisionMeter(num_labels, ignore_label=config.ignore_label).to(device)
+        ap_step = meter.update(soutput.F, target, from_logits=True)          # or: meter.update(prob, target)
+        stats = meter.compute()                                              # {"ap": [C], "map": scalar, "steps": [C]}
+
+    Two registered buffers: `ap_sum` (float64 [C], the sum over the steps in which the class had a positive) and `steps` (int64 [C],
+    how many those were).  No host sync in update or compute."""
+
+    def __init__(self, num_classes, ignore_label=-1):
+        super().__init__()
+        self.num_classes = int(num_classes)
+        self.ignore_label = int(ignore_label)
+        self.register_buffer("ap_sum", torch.zeros(self.num_classes, dtype=torch.float64))
+        self.register_buffer("steps", torch.zeros(self.num_classes, dtype=torch.int64))
+
+    @torch.no_grad()
+    def update(self, scores, target, from_logits=False):
+        """-> this step's average_precision(scores, target) [C]; its classes that are not NaN are added to the buffers"""
+        scores = _features(scores)
+        if scores.dim() != 2 or scores.shape[1] != self.num_classes:
+            raise ValueError("scores must be [N, %d], got %s" % (self.num_classes, tuple(scores.shape)))
+        ap = average_precision(scores, target, self.ignore_label, from_logits).to(self.ap_sum.device)
+        seen = ~torch.isnan(ap)
+        self.ap_sum += torch.where(seen, ap, torch.zeros_like(ap))
+        self.steps += seen.to(torch.int64)
+        return ap
+
+    def reset(self):
+        self.ap_sum.zero_()
+        self.steps.zero_()
+
+    @torch.no_grad()
+    def compute(self, process_group=None):
+        """-> {"ap": [C] mean over the steps that saw the class (NaN: none did), "map": its nanmean over the classes, "steps": [C]}.
+        When torch.distributed is initialised the two buffers are sum-reduced over the ranks first; the local ones stay."""
+        ap_sum, steps = self.ap_sum, self.steps
+        dist = torch.distributed
+        if dist.is_available() and dist.is_initialized():
+            ap_sum, steps = ap_sum.clone(), steps.clone()
+            dist.all_reduce(ap_sum, op=dist.ReduceOp.SUM, group=process_group)
+            dist.all_reduce(steps, op=dist.ReduceOp.SUM, group=process_group)
+        nan = torch.full_like(ap_sum, float("nan"))
+        ap = torch.where(steps > 0, ap_sum / steps.clamp_min(1).to(torch.float64), nan)
+        return {"ap": ap, "map": torch.nanmean(ap), "steps": steps}
 
 
 def fast_hist(pred, label, n):

@@ -1,5 +1,5 @@
 """Per-op timings on the GPU (HIP events on torch's current stream) for the hot layer shapes.
-usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal | supcon | augment | nearest]"""
+usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal | supcon | augment | nearest | ap]"""
 import os
 import sys
 import time
@@ -504,6 +504,106 @@ def metrics():
         report("METRICS_BLOCKS=%d bfloat16 %s labels no prob" % (blocks, dist_name), ts, n * c * 2 + 16 * n)
 
 
+def ap():
+    """lgs_average_precision behind metrics.average_precision: the whole call (HIP events) and its four stages (kernel times from
+    torch.profiler, by kernel name: 1 keys, 2 sort + segment starts, 3 rank pass, 4 scan + terms + finish) on
+      scene      [151 k, 200], "trained" scores (the row's own class lifted), 90 % of the rows on two classes
+      batch      [1.2 M, 200], the same
+      untrained  [1.2 M, 200], near-uniform probabilities, uniform labels: the skip test of stage 3 ends almost nothing
+    each from bf16 logits (from_logits=True) and from fp32 prob; beside a per-column torch.sort AP on the same device (cumulative
+    precision at each positive; ties are not grouped: a timing baseline) and, on the scene shape (every shape with `ap full`),
+    sklearn's average_precision_score per class on the host, the copy included."""
+    from languagegroundedsemseg_amd.metrics import average_precision
+    c, rounds = 200, 3
+    full = len(sys.argv) > 2 and sys.argv[2] == "full"
+    g = torch.Generator(device=DEV).manual_seed(0)
+
+    def make(n, trained):
+        lab = torch.randint(0, c, (n,), device=DEV, generator=g)
+        if trained:
+            r = torch.rand(n, device=DEV, generator=g)
+            lab = torch.where(r < 0.45, torch.full_like(lab, 3), torch.where(r < 0.9, torch.full_like(lab, 7), lab))
+            x = torch.randn(n, c, device=DEV, generator=g) * 2.0
+            hit = torch.rand(n, device=DEV, generator=g) < 0.8          # 80 % of the rows score their own class highest
+            x[torch.arange(n, device=DEV)[hit], lab[hit]] += 8.0
+        else:
+            x = torch.randn(n, c, device=DEV, generator=g) * 0.01
+        lab[torch.rand(n, device=DEV, generator=g) < 0.1] = -1
+        return x.to(torch.bfloat16), lab
+
+    def sort_ap(prob, lab):
+        cols = prob.t().contiguous()
+        ar = torch.arange(1, prob.shape[0] + 1, device=prob.device, dtype=torch.float64)
+        out = []
+        for k in range(c):
+            s, idx = torch.sort(cols[k], descending=True)
+            y = (lab[idx] == k).to(torch.float64)
+            out.append((torch.cumsum(y, 0) / ar * y).sum() / y.sum())
+        return torch.stack(out)
+
+    def sklearn_ap(prob, lab):
+        from sklearn.metrics import average_precision_score
+        p, t = prob.cpu().numpy(), lab.cpu().numpy()
+        return [average_precision_score(t == k, p[:, k]) for k in range(c) if (t == k).any()]
+
+    def stage_of(name):
+        if "k_ap_softmax_keys" in name or "k_ap_keys" in name:
+            return 1
+        if "k_ap_rank" in name:
+            return 3
+        if "k_ap_terms" in name or "k_ap_finish" in name:
+            return 4
+        if "k_ap_offsets" in name or "onesweep" in name or "radix" in name or "sort" in name:
+            return 2
+        if "scan" in name:
+            return 4
+        return 0
+
+    def stages(fn, iters=5):
+        """-> us per call of the stages 1 .. 4 and of the device work that belongs to none (memset), or None without a profiler"""
+        try:
+            from torch.profiler import profile, ProfilerActivity
+            fn()
+            torch.cuda.synchronize()
+            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                for _ in range(iters):
+                    fn()
+                torch.cuda.synchronize()
+            out = [0.0] * 5
+            for ev in prof.key_averages():
+                t = getattr(ev, "self_device_time_total", None)
+                if t is None:
+                    t = ev.self_cuda_time_total
+                out[stage_of(ev.key)] += t / iters
+            return out if sum(out) > 0 else None
+        except Exception as exc:          # a build without the tracer: the whole-call times stand
+            print("  (no stage times: %s)" % exc)
+            return None
+
+    print("%-44s %10s | %8s %8s %8s %8s %8s | %12s %12s" % ("case", "call us", "1 keys", "2 sort", "3 rank", "4 finish", "other",
+                                                             "torch.sort us", "sklearn ms"))
+    for name, n, trained in (("scene [151k,200]", 151000, True), ("batch [1.2M,200]", 1200000, True), ("untrained [1.2M,200]", 1200000, False)):
+        x, lab = make(n, trained)
+        prob = torch.softmax(x.float(), 1)
+        t_sort = min(timeit(lambda: sort_ap(prob, lab), 1, 1) for _ in range(2))
+        t_sk = None
+        if n < 200000 or full:
+            try:
+                t0 = time.perf_counter()
+                sklearn_ap(prob, lab)
+                t_sk = (time.perf_counter() - t0) * 1e3
+            except ImportError:
+                pass
+        for kind, src, kw in (("bf16 logits", x, {"from_logits": True}), ("fp32 prob", prob, {})):
+            call = lambda: average_precision(src, lab, **kw)
+            ts = [timeit(call, 10, 2) for _ in range(rounds)]
+            st = stages(call)
+            cells = " ".join("%8.1f" % v for v in (st[1:] + st[:1])) if st else " ".join(["%8s" % "-"] * 5)
+            print("%-44s %10.1f | %s | %12.1f %12s" % ("%s %s (median %.1f)" % (name, kind, sorted(ts)[len(ts) // 2] * 1e3), min(ts) * 1e3,
+                                                        cells, t_sort * 1e3, "%.0f" % t_sk if t_sk is not None else "-"))
+        del x, prob
+
+
 def focal():
     """k_focal_fwd_bwd (gamma 0 / 2 / 2.5, with and without alpha) beside k_ce_fwd_bwd on the same [1.2 M, 200] scores, bf16 and fp32,
     forward (loss rows) and backward (d logits) calls, all variants alternating inside this process; min / median over the rounds.
@@ -721,6 +821,9 @@ def nearest():
 
 
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "ap":
+        ap()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "nearest":
         nearest()
         sys.exit(0)
