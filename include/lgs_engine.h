@@ -794,6 +794,35 @@ int64_t lgs_ap_workspace_bytes(int64_t n, int c);
 int lgs_average_precision(const void *scores, int64_t n, int c, const int64_t *labels, int64_t ignore_index, int from_logits,
                           double *ap_out /* [c] */, int dtype, void *workspace, void *stream);
 
+/* ---- instance evaluation: proposal / ground-truth overlap tables (csrc/lgs_insteval.hip) ---------
+ * replaces: the per-proposal host loop of Clustering.get_instances (downstream/insseg/lib/bfs/bfs.py:127-157: a dense [P, N] mask, one
+ *   score_func over a boolean gather and three device -> host copies per proposal) and assign_instances_for_scan
+ *   (downstream/insseg/datasets/evaluation/evaluate_semantic_instance.py:251-306: one [N] pass per (proposal, ground-truth instance))
+ * NEW SYMBOLS ONLY: LGS_ABI_VERSION stays 18; a library that lacks them lacks the capability.
+ * All pointers are DEVICE pointers.  Enqueues on `stream`, never synchronises.
+ * Proposals in CSR form: member[offsets[q] .. offsets[q + 1]) are the point indices of proposal q (offsets[0] == 0, offsets[p] == m,
+ *   ascending).  The members of one proposal are distinct (not checked); a point may belong to several proposals.
+ * Ground truth: g = gt_ids[i] names an instance iff g != 0 and floor(g / 1000) is one of valid_class_ids[v] (ascending, all >= 1: a
+ *   smaller one sets status bit 8).  Every other point is void; gt_ids == NULL: all of them are (the call then serves conf alone).
+ * gt_id / gt_count [g_cap]: the distinct instance ids of the scene and their point counts; unused slots have gt_count == 0.  WHICH slot an
+ *   id takes is unspecified (the compaction runs on the device); the map id -> (count, column of inter) is exact.  1 <= g_cap <= 4096.
+ *   More than g_cap distinct ids set status bit 1: nothing is written out of bounds, the other outputs are unspecified.
+ * inter[q, slot] ([p, g_cap]): members of q whose id is that slot's.  prop_void[q]: members of q that are void.
+ *   prop_void[q] + sum(inter[q, :]) == offsets[q + 1] - offsets[q] whenever status == 0.
+ * conf[q]: score_mode 1 = the maximum of scores[i, score_col[q]] over the members (bf16 widened exactly; the bits torch.max gives, NaN
+ *   once a member is NaN); 2 = their mean, summed in fp64 per piece of at most 1024 members in a fixed tree, the pieces in order, rounded
+ *   to fp32 once: two calls give the same bits.  An empty proposal, or a score_col outside [0, c) (status bit 4), gives NaN.
+ *   score_mode 0 writes nothing to conf (scores, score_col, conf may be NULL).  scores[n, c]: float32 / bf16, contiguous rows.
+ * A member outside [0, n) sets status bit 2 and is skipped.  p == 0, m == 0 and n == 0 are legal.  status is one int32, overwritten.
+ * Integer sums only (LDS adds per workgroup, 32-bit global adds where a proposal spans several): the result does not depend on order.
+ * workspace: lgs_inst_overlap_workspace_bytes(n, m, p, g_cap) bytes (-1: a negative size or g_cap outside 1 .. 4096). */
+int64_t lgs_inst_overlap_workspace_bytes(int64_t n, int64_t m, int p, int g_cap);
+int lgs_inst_overlap(const int32_t *member /* [m] */, const int32_t *offsets /* [p + 1] */, const int32_t *score_col /* [p] */, int p, int64_t m,
+                     const int64_t *gt_ids /* [n] */, int64_t n, const int64_t *valid_class_ids /* [v] */, int v,
+                     const void *scores /* [n, c] or NULL */, int c, int dtype, int score_mode, int g_cap, int64_t *gt_id /* [g_cap] */,
+                     int32_t *gt_count /* [g_cap] */, int32_t *inter /* [p, g_cap] */, int32_t *prop_void /* [p] */, float *conf /* [p] */,
+                     int32_t *status, void *workspace, void *stream);
+
 /* ---- supervised point-contrastive loss (csrc/lgs_supcon.hip) -------------------------------------
  * replaces: PointSupConLoss.forward (lib/losses/PointSupConLoss.py:74-154), the third embedding criterion of
  *   BaselineTrainerModule.init_criterions (lib/train_test/pl_BaselineTrainer.py:92-108): per class of the batch three device -> host

@@ -40,7 +40,7 @@ enum Tune {
   T_BN_FOLD, T_BN_FOLD_MAX_MB, T_BN_FOLD_PARTS, T_BN_FOLD_GRID, T_FP32_SPLIT, T_BLOCK_WGRAD_LATE, T_WGRAD_F32_LDS, T_WIDE_SCHED, T_HEAD_TILE, T_POINTWISE,
   T_INSTANCE_NORM, T_METRICS_BLOCKS, T_SUPCON_FUSED, T_BN_PAIR, T_MAP_WINDOW_SORT, T_MAP_BLOCK_DIR,
   T_MAP_PERMUTE_LDS, T_MAP_PERMUTE_GROUP, T_MAP_OWN_SORTS, T_MAP_CHILD_ROUNDS, T_CONV_SLAB_TRIM, T_CONV_ROW_TRIM,
-  T_NEAREST_MAX_RING,
+  T_NEAREST_MAX_RING, T_INST_EVAL_FUSED,
   T_COUNT
 };
 int64_t tune(Tune t);                                                   // current value (environment LGS_<NAME> at start, lgs_tuning_set later)

@@ -124,6 +124,10 @@ const Knob kKnobs[T_COUNT] = {
                                                 "answer is the same at every value (tests/test_gpu_nearest.py).  3.6 M points inside the occupied cells of the 8-scene, "
                                                 "1.2 M-voxel batch, block directory, voxel corners / centres as sites: 1 = 1.056 / 0.514 ms with 0.025 % / 0 of the "
                                                 "queries left to the scan, 2 = 0.611 / 0.514 ms with none, 4 = the same as 2 (tools/microbench.py nearest)"},
+    {T_INST_EVAL_FUSED, "INST_EVAL_FUSED", 1, "insteval.instance_overlaps and Clustering.get_proposals on HIP tensors: 1 = the kernels of lgs_insteval.hip (one gather "
+                                              "and one table probe per proposal member, an LDS histogram per piece of a proposal); 0 = the torch lines CPU tensors "
+                                              "take (torch.unique over the ids, one bincount over (proposal, id) pairs, torch.max / mean per proposal) -- read at call "
+                                              "time.  The integer tables and the max confidences are equal (tests/test_gpu_insteval.py)"},
 };
 std::atomic<int64_t> g_val[T_COUNT];
 std::once_flag g_once;

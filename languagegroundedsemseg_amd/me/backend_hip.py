@@ -1314,6 +1314,59 @@ class HipBackend:
                                                  _dtype_code(scores), _ptr(ws), _stream()))
         return ap
 
+    # ---- instance evaluation: lgs_inst_overlap
+    INST_MAX_GT = 4096
+    _INST_SCORE_MODE = {None: 0, "max": 1, "mean": 2}
+
+    @staticmethod
+    def inst_eval_fused():
+        """tuning knob INST_EVAL_FUSED, read at call time (0 = the torch lines CPU tensors take, also on HIP tensors)"""
+        return engine.tuning_get("INST_EVAL_FUSED") != 0
+
+    def inst_overlap(self, member, offsets, n, gt_ids=None, valid_class_ids=None, g_cap=1024, scores=None, score_col=None, score_mode=None):
+        """Proposals in CSR form (member [M] int32 point indices grouped by proposal, offsets [P + 1] int32) against the ground-truth
+        ids [n] int64 of one scene -> (gt_id [g_cap] int64, gt_count [g_cap] int32, inter [P, g_cap] int32, prop_void [P] int32,
+        conf [P] float32 or None, status [1] int32), all on the device, by the contract of lgs_inst_overlap in include/lgs_engine.h.
+        score_mode "max" / "mean": conf[q] over scores[member of q, score_col[q]].  gt_ids None: conf alone.  No host sync."""
+        _require_dev(member, "member")
+        L = engine.lib()
+        dev = member.device
+        mode = self._INST_SCORE_MODE[score_mode]
+        member = member.contiguous()
+        offsets = offsets.contiguous()
+        if member.dtype != torch.int32 or offsets.dtype != torch.int32:
+            raise RuntimeError("inst_overlap: member and offsets must be int32")
+        p, m = offsets.shape[0] - 1, member.shape[0]
+        if gt_ids is not None:
+            gt_ids = gt_ids.contiguous()
+            valid_class_ids = valid_class_ids.contiguous()
+            if gt_ids.dtype != torch.int64 or valid_class_ids.dtype != torch.int64 or gt_ids.shape[0] != n:
+                raise RuntimeError("inst_overlap: gt_ids [n] and valid_class_ids must be int64")
+        c = dt = 0
+        if mode:
+            scores = scores.detach().contiguous()
+            score_col = score_col.contiguous()
+            if scores.shape[0] != n or score_col.dtype != torch.int32 or score_col.shape[0] != p:
+                raise RuntimeError("inst_overlap: scores must be [n, c] and score_col [P] int32")
+            c, dt = scores.shape[1], _dtype_code(scores)
+        with _dev(dev):
+            gt_id = torch.empty(g_cap, dtype=torch.int64, device=dev)
+            gt_count = torch.empty(g_cap, dtype=torch.int32, device=dev)
+            inter = torch.empty((p, g_cap), dtype=torch.int32, device=dev)
+            prop_void = torch.empty(p, dtype=torch.int32, device=dev)
+            conf = torch.empty(p, dtype=torch.float32, device=dev) if mode else None
+            status = torch.empty(1, dtype=torch.int32, device=dev)
+            nbytes = memo(_QUERIES, ("inst_ws", n, m, p, g_cap), L.lgs_inst_overlap_workspace_bytes, n, m, p, g_cap)
+            if nbytes < 0:
+                raise RuntimeError("inst_overlap: lgs_inst_overlap_workspace_bytes(%d, %d, %d, %d) failed" % (n, m, p, g_cap))
+            ws = _ws(nbytes, dev)
+            engine.check(L.lgs_inst_overlap(_ptr(member), _ptr(offsets), _ptr(score_col) if mode else None, p, m, _ptr(gt_ids), n,
+                                            _ptr(valid_class_ids) if gt_ids is not None else None,
+                                            valid_class_ids.shape[0] if gt_ids is not None else 0, _ptr(scores) if mode else None, c, dt,
+                                            mode, g_cap, _ptr(gt_id), _ptr(gt_count), _ptr(inter), _ptr(prop_void), _ptr(conf), _ptr(status),
+                                            _ptr(ws), _stream()))
+        return gt_id, gt_count, inter, prop_void, conf, status
+
     # ---- supervised point-contrastive loss: lgs_supcon_sample / lgs_supcon_forward / lgs_supcon_backward
     SUPCON_MAX_SAMPLES = 8
     _SUPCON_DISTANCE = {"cos": engine.LGS_SUPCON_COS, "l2": engine.LGS_SUPCON_L2}

@@ -89,3 +89,28 @@ class Clustering:
             sc = self.score_func(scores[pred[i].bool(), labels[i]])
             out[i] = {"conf": sc.cpu().numpy(), "label_id": self.class_mapping.cpu()[labels[i]], "pred_mask": pred[i].cpu().numpy()}
         return out
+
+    def get_proposals(self, vertices, scores):
+        """get_instances without the dense [P, N] mask and without the per-proposal host loop: the same clusters, the same
+        `> propose_points` filter, label and order, as an insteval.Proposals of device tensors.  conf is score_func over
+        scores[members, label] for score_func torch.max / torch.mean (lgs_inst_overlap; max: torch.max's bits, mean: summed in fp64,
+        rounded once)."""
+        from . import insteval
+        mode = {torch.max: "max", torch.mean: "mean"}.get(self.score_func)
+        if mode is None:
+            raise NotImplementedError("Clustering.get_proposals: score_func %s is not supported (torch.max and torch.mean are); "
+                                      "use get_instances" % getattr(self.score_func, "__name__", repr(self.score_func)))
+        scores = scores.to(self.device)
+        labels = torch.max(scores, 1)[1]
+        idx, off = self.cluster_(vertices, labels)
+        idx, off = idx.to(self.device), off.to(self.device)
+        sizes = (off[1:] - off[:-1]).long()
+        lab = labels[idx[:, 1][off[:-1].long()].long()]
+        keep = sizes > self.propose_points
+        member = idx[:, 1][torch.repeat_interleave(keep, sizes)].contiguous()
+        offsets = torch.cat([sizes.new_zeros(1), torch.cumsum(sizes[keep], 0)]).int()
+        lab = lab[keep]
+        if scores.dtype not in (torch.float32, torch.bfloat16):
+            scores = scores.float()
+        conf = insteval.proposal_conf(member, offsets, lab.int(), scores, mode)
+        return insteval.Proposals(member, offsets, lab, self.class_mapping[lab].long(), conf, scores.shape[0])

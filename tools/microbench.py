@@ -820,7 +820,152 @@ def nearest():
           "cKDTree build + query, one core %.1f ms (same rows: %.5f)" % (sites0.shape[0], q0.shape[0], t_one, t_brute, agree, t_tree, agree_tree))
 
 
+def _insteval_runs(n, n_inst, n_cls, seed):
+    """one synthetic scene for the host-side timing: instances are runs of the point index, predictions jittered runs (the shape of
+    tests/golden/make_insteval_fixtures.py at any size) -> (gt_ids, the reference's prediction dict)"""
+    rng = np.random.default_rng(seed)
+    cuts = np.sort(rng.choice(np.arange(1, n), n_inst - 1, replace=False))
+    seg = np.searchsorted(cuts, np.arange(n), side="right")
+    cls = rng.integers(0, n_cls + 2, n_inst)                       # 1 .. n_cls are valid
+    gt = (cls[seg] * 1000 + seg + 1).astype(np.int64)
+    gt[rng.random(n) < 0.05] = 0
+    bounds = np.concatenate([[0], cuts, [n]])
+    preds = {}
+    for s in range(n_inst):
+        for _ in range(rng.integers(0, 3)):
+            a, b = max(0, bounds[s] + rng.integers(-40, 40)), min(n, bounds[s + 1] + rng.integers(-40, 40))
+            if b - a < 5:
+                continue
+            mask = np.zeros(n, np.int32)
+            mask[a:b] = 1
+            mask[rng.random(n) < 0.02] = 0
+            label = cls[s] if rng.random() < 0.8 else rng.integers(0, n_cls + 2)
+            preds[len(preds)] = {"conf": np.float32(rng.integers(0, 8) / 8.0), "label_id": torch.tensor(int(label)), "pred_mask": mask}
+    return gt, preds
+
+
+def insteval_host():
+    """CPU only: InstanceEvaluator.evaluate() against the reference's own Evaluator.evaluate() on identical inputs (the reference's
+    checkout is argv[2]): one 18-class 150 k-point scene, and a set of 50 scenes of 20 k points.  Both sides get the dict with dense masks;
+    the evaluator's side is timed once from the dict (np.nonzero per mask included) and once from Proposals."""
+    import importlib.util
+    import io
+    from contextlib import redirect_stdout
+    from languagegroundedsemseg_amd.insteval import InstanceEvaluator, Proposals
+    spec = importlib.util.spec_from_file_location("make_insteval_fixtures", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                                                                       "tests", "golden", "make_insteval_fixtures.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    ref = gen.load_reference(sys.argv[2])
+    labels, valid = ["c%d" % i for i in range(1, 19)], np.arange(1, 19)
+    warm = InstanceEvaluator(labels, valid)                        # first use of the torch operators at this size (their thread pool: ~1 s, once)
+    gt, preds = _insteval_runs(150000, 10, 18, 0)
+    warm.add_gt(gt, 0)
+    warm.add_prediction(preds, 0)
+    warm.evaluate()
+    for name, scenes in (("1 scene, 150 k points, 120 instances", [_insteval_runs(150000, 120, 18, 7)]),
+                         ("50 scenes, 20 k points, 60 instances each", [_insteval_runs(20000, 60, 18, 100 + k) for k in range(50)])):
+        t0 = time.perf_counter()
+        rev = ref.Evaluator(labels, valid)
+        for k, (gt, preds) in enumerate(scenes):
+            rev.add_gt(gt, k)
+            rev.add_prediction(preds, k)
+        with redirect_stdout(io.StringIO()):
+            want = rev.evaluate()
+        t_ref = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        ev = InstanceEvaluator(labels, valid)
+        for k, (gt, preds) in enumerate(scenes):
+            ev.add_gt(gt, k)
+            ev.add_prediction(preds, k)
+        got = ev.evaluate()
+        t_dict = time.perf_counter() - t0
+        props = [Proposals.from_instances(preds) for _, preds in scenes]
+        t0 = time.perf_counter()
+        ev = InstanceEvaluator(labels, valid)
+        for k, (gt, _) in enumerate(scenes):
+            ev.add_gt(torch.from_numpy(gt), k)
+            ev.add_prediction(props[k], k)
+        t_tab = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        got2 = ev.evaluate()
+        t_eval = time.perf_counter() - t0
+        assert got == got2 and np.allclose(got, want, rtol=0, atol=1e-14), (got, got2, want)
+        print("%-44s %4d predictions | reference add + evaluate %8.3f s | InstanceEvaluator from the dict %8.3f s | from Proposals: tables (CPU "
+              "torch lines) %8.3f s, evaluate() %8.3f s | mAP %.6f / %.6f / %.6f equal" % (name, sum(len(p) for _, p in scenes), t_ref, t_dict, t_tab, t_eval, *got))
+
+
+def insteval():
+    """from "clusters exist" to the overlap tables on the host, on one synthetic scene of ~150 k voxels with its point cloud
+    (three points per occupied cell, the shape `nearest` builds): Clustering.get_proposals + InstanceEvaluator.add_prediction up to the
+    tables' arrival on the host, against Clustering.get_instances alone (the dense [P, N] mask and the per-proposal host loop), the
+    clustering both share, and the kernels alone."""
+    from languagegroundedsemseg_amd.insteval import InstanceEvaluator, instance_overlaps, proposal_conf
+    from languagegroundedsemseg_amd.pointgroup import Clustering
+    coords, _, _ = make_batch([1000], n_target=150000)
+    rng = np.random.default_rng(0)
+    cells = np.repeat(coords[:, 1:].astype(np.float64), 3, 0)
+    xyz = ((cells + rng.random(cells.shape)) * 0.02).astype(np.float32)
+    n, n_cls = xyz.shape[0], 20
+    blk = np.floor(xyz / np.float32(0.6)).astype(np.int64)
+    blk_id = (blk[:, 0] * 31 + blk[:, 1]) * 31 + blk[:, 2]
+    blk_id -= blk_id.min()
+    sem = (blk_id * 7 % n_cls).astype(np.int64)
+    valid = np.arange(2, n_cls)                                     # columns 0 and 1 are wall and floor: ignored, as in the reference
+    gt = np.where(sem >= 2, sem * 1000 + blk_id % 1000, 0).astype(np.int64)      # one instance per 0.6 m block; the predictions see 2 % label noise
+    noise = rng.random(n) < 0.02
+    sem[noise] = rng.integers(0, n_cls, int(noise.sum()))
+    g = torch.Generator().manual_seed(0)
+    scores = (torch.nn.functional.one_hot(torch.from_numpy(sem), n_cls).float() * 6 + torch.randn(n, n_cls, generator=g)).to(DEV)
+    xyz_d, gt_d = torch.from_numpy(xyz).to(DEV), torch.from_numpy(gt).to(DEV)
+    cl = Clustering(ignored_labels=[0, 1], class_mapping=torch.arange(n_cls), thresh=0.03, min_points=50, propose_points=100, score_func=torch.max)
+
+    def wall(fn, reps=3):
+        ts = []
+        for _ in range(reps + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return min(ts[1:])
+
+    def new_route():
+        ev = InstanceEvaluator(["c%d" % c for c in valid], valid)
+        ev.add_gt(gt_d, 0)
+        ev.add_prediction(cl.get_proposals(xyz_d, scores), 0)
+        return ev
+    prop = cl.get_proposals(xyz_d, scores)
+    p, m = len(prop), prop.member.shape[0]
+    n_gt = len(np.unique(gt[gt != 0]))
+    assert n_gt <= 1024, n_gt
+    print("%d points, %d classes, %d proposals with %d members, %d ground-truth instances" % (n, n_cls, p, m, n_gt))
+    t_cluster = wall(lambda: cl.cluster_(xyz_d, torch.max(scores, 1)[1]))
+    t_new = wall(new_route)
+    t_old = wall(lambda: cl.get_instances(xyz_d, scores))
+    t_tab = timeit(lambda: instance_overlaps(prop, gt_d, valid), 200, 5)
+    t_conf = timeit(lambda: proposal_conf(prop.member, prop.offsets, prop.label.int(), scores, "max"), 200, 5)
+    ev = new_route()
+    t0 = time.perf_counter()
+    res = ev.evaluate()
+    t_eval = (time.perf_counter() - t0) * 1e3
+    print("clustering alone (cluster_, shared by both routes)               %9.2f ms" % t_cluster)
+    print("get_proposals + add_gt + add_prediction, tables on the host       %9.2f ms   (%.2f MB to the host: [P, 1024] int32 + ids)"
+          % (t_new, (p * 1024 * 4 + 1024 * 12 + p * 20) / 1e6))
+    print("get_instances alone (dense [P, N] mask, per-proposal host loop)   %9.2f ms   (%.1f MB to the host: P masks of N int32)" % (t_old, p * n * 4 / 1e6))
+    print("lgs_inst_overlap, tables (ids + overlap + zeroing [P, 1024])      %9.3f ms   reads %.2f MB: gt_ids once, 4 + 8 B per member" % (t_tab, (8 * n + 12 * m) / 1e6))
+    print("lgs_inst_overlap, conf (max over one score column per proposal)   %9.3f ms   reads %.2f MB: 4 B + one 32 B sector per member" % (t_conf, 36 * m / 1e6))
+    print("InstanceEvaluator.evaluate() on the host, this scene              %9.2f ms   mAP %.4f mAP50 %.4f mAP25 %.4f" % (t_eval, *res))
+    print("new route / get_instances: x %.1f" % (t_old / t_new))
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "insteval":
+        insteval()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "insteval_host":
+        insteval_host()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "ap":
         ap()
         sys.exit(0)
