@@ -909,6 +909,10 @@ int lgs_supcon_backward(const void *feat, int64_t n, int c, const int64_t *label
 #define LGS_AUG_F32X3 0
 #define LGS_AUG_I32X4 1
 #define LGS_AUG_STAGE_COLOR 16
+#define LGS_AUG_STAGE_PASTE 17          /* the tail-instance paste's trial draws (below) */
+#define LGS_PASTE_MAX_SLOTS 1024
+#define LGS_PASTE_SLOT_COLS 6
+#define LGS_PASTE_SCENE_COLS 4
 #define LGS_COLOR_AUTOCONTRAST 1
 #define LGS_COLOR_TRANSLATION 2
 #define LGS_COLOR_JITTER 4
@@ -933,6 +937,50 @@ int lgs_color_augment(float *colors, int64_t n, const int64_t *scene_offsets, in
                       const lgs_color_scene *scenes, float scale, int normalize, int64_t seed, const float *noise, void *stream);
 int lgs_aug_status(const int32_t *status, int *flags, void *stream);
 int lgs_debug_philox(const int32_t *counters, int64_t n, int64_t key, int32_t *out, void *stream);
+
+/* ---- class-balanced tail-instance paste (csrc/lgs_paste.hip) -------------------------------------
+ * replaces: ScannetVoxelizationDataset.add_instances_to_cloud (lib/datasets/scannet.py:143-241), the reference's
+ *   --sample_tail_instances: per scene a height map with a 5 x 5 maximum filter, per pasted instance up to `trials` placement
+ *   trials against the scene's instance boxes, then the rotation M_r of every row.  The dedup that follows is the caller's.
+ * NEW SYMBOLS ONLY: LGS_ABI_VERSION stays 18; a library that lacks them lacks the capability.
+ * A batch is b <= LGS_AUG_MAX_SCENES scenes, coords int32 [n, 4] with the scene index 0 .. b - 1 in column 0 (ascending) and
+ * floor(M_v p) in columns 1..3, feats float32 [n, 3], labels int64 [n].  A SLOT is one (scene, instance) pair, at most
+ * LGS_PASTE_MAX_SLOTS per call, slots of a scene adjacent and in paste order; the instances' rows, slot after slot, are the
+ * inst_rows INSTANCE ROWS.  The bank is bank_points / bank_colors float32 [bank_rows, 3] and bank_labels int64 [bank_rows], world
+ * units.  Every table is DEVICE memory, filled by the host (one upload serves them all):
+ *   slot_table    int64 [slots + 1, LGS_PASTE_SLOT_COLS] = (first bank row, first instance row, first output row, scene, index of
+ *                 the instance within its scene, rows); every slot has at least one row; record `slots` holds inst_rows in column 1.
+ *   slot_affines  double [slots, 12]: the instance's own M_r M_v (the reference voxelises each instance with augmentation on).
+ *   scene_table   int64 [b + 1, LGS_PASTE_SCENE_COLS] = (first output row of the scene's own rows, first box, the scene's Philox
+ *                 key word, first input row); record b holds n_boxes in column 1 and n in column 3.  An empty scene has no slots.
+ *   scene_xforms  double [b, 13] = (the scalar of M_v, then M_r as [3, 4]).
+ *   boxes         double [n_boxes, 6] = world-space (min corner, max corner); a trial compares against round(corner * scalar).
+ * Steps (float64 wherever the reference computes in float64; integer atomics only, so two calls give the same bits):
+ *   instance voxels  floor(M p) with lgs_voxelize_batched's arithmetic.  A row is FIRST if it is the lowest row of its (slot, voxel),
+ *                    found through an open-addressing table of packed keys (18 bits per coordinate).
+ *   statistics       over first rows per slot: min, max, int64 sum, count -> dims = max - min + 1, mean = trunc(sum / count).
+ *   height map       per scene int32 [dim_x, dim_y] over the bounds of its rows (lgs_aug_bounds), z_min where no row lies.
+ *   placement        trial t: (x, y) = trial_draws[slot, t] (DEVICE int32 [slots, trials, 2], clamped into the scene's bounds) if
+ *                    not NULL, else x = x_min + (w0 dim_x >> 32), y likewise with w1, (w0, w1) from Philox-4x32-10 with counter =
+ *                    (t, index within the scene, LGS_AUG_STAGE_PASTE, seed >> 32) and key = (seed & 2^32-1, scene key word).
+ *                    h = max of the map over the 5 x 5 window clamped to the map (= scipy's maximum_filter(size=5), reflect);
+ *                    centroid = (x, y, trunc(h + dims_z / 2.0)); the trial fails if any box of the scene intersects
+ *                    centroid -+ dims / 2.0 (inclusive on all six comparisons).  The first trial that does not fail wins; if all
+ *                    fail the last trial's centroid is used.  placement int32 [slots, 4] = (winning trial, `trials` if all failed,
+ *                    -1 if the scene was not pasted; centroid).
+ *   output           per scene its own rows, then its instances in slot order, n + inst_rows rows: coords_out = (scene,
+ *                    floor(M_r c)), c = the scene row, or voxel - mean + centroid; feats_out / labels_out copied alongside.
+ * A scene whose map has more than max_map_cells (1 .. 2^26) cells, or with an instance voxel outside [-2^17, 2^17), is NOT pasted:
+ *   bit `scene` of *status (DEVICE int32, OR-ed, never cleared here; read with lgs_aug_status) is set and its instance rows are
+ *   written as copies of the scene's first row, which the dedup drops.
+ * workspace: lgs_paste_workspace_bytes(b, slots, inst_rows, max_map_cells) bytes (0 = bad shape).  Nothing is read back. */
+int64_t lgs_paste_workspace_bytes(int b, int slots, int64_t inst_rows, int64_t max_map_cells);
+int lgs_paste_instances(const int32_t *coords, const float *feats, const int64_t *labels, int64_t n, int b, const float *bank_points,
+                        const float *bank_colors, const int64_t *bank_labels, int64_t bank_rows, const int64_t *slot_table,
+                        const double *slot_affines, int slots, int64_t inst_rows, const int64_t *scene_table,
+                        const double *scene_xforms, const double *boxes, int64_t n_boxes, const int32_t *trial_draws, int trials,
+                        int64_t seed, int64_t max_map_cells, void *workspace, int32_t *coords_out, float *feats_out,
+                        int64_t *labels_out, int32_t *placement, int32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -12,8 +12,12 @@ Scalar decisions (apply or not, blend factor, translation vector, rigid matrix, 
 per point, per voxel and per noise cell runs in HIP kernels, and nothing before the dedup's own row count synchronises.
 Host tensors raise RuntimeError: there is no CPU path.
 
-Out of scope, refused by name: RandomDropout, HueSaturationTranslation, the clip bound, instance augmentation,
-the paired voxeliser."""
+With `tail_instances=TailInstancePaste(bank, ...)` the chain also runs the reference's class-balanced instance sampling
+(--sample_tail_instances, lib/datasets/scannet.py:143-241; csrc/lgs_paste.hip): the voxeliser applies M_v only, `paste_instances`
+places the drawn bank instances on the scene's height map and rotates every row by M_r, and the chain's one dedup follows.
+
+Out of scope, refused by name: RandomDropout, HueSaturationTranslation, the clip bound, instance augmentation
+(the raw / latent colour and scale shifts of augment_instances), the paired voxeliser."""
 import ctypes
 import dataclasses
 
@@ -90,8 +94,11 @@ def aug_bounds(table, scene_offsets=None, batch_size=None):
 
 
 def aug_status(status):
-    """Reads the device status words of an elastic call (this SYNCHRONISES) -> scenes whose noise grid exceeded max_cells"""
+    """Reads the device status words of an elastic or paste call (this SYNCHRONISES) -> scenes whose noise grid exceeded max_cells
+    (elastic) / that were left unpasted (paste)"""
     out = []
+    if isinstance(status, torch.Tensor):          # one word: what paste_instances returns
+        status = [status]
     for chunk, word in enumerate(status):
         f = ctypes.c_int(0)
         with torch.cuda.device(word.device):
@@ -304,6 +311,8 @@ class AugmentPlan:
     scene_seeds: np.ndarray           # [B] uint32     per-scene Philox key word
     seed: int                         # the batch's 64-bit Philox seed
     shift: np.ndarray                 # [3] int        the trainer's per-batch coordinate shift (zeros unless coordinate_shift)
+    rotations: np.ndarray = None      # [B, 4, 4]      M_r alone (the paste rotates after it has placed the instances)
+    paste: "PastePlan" = None         # the tail-instance decisions, when the chain has tail_instances
 
 
 def axis_rotation(axis, theta):
@@ -315,18 +324,204 @@ def axis_rotation(axis, theta):
     return r
 
 
+def draw_rigid(r, n, voxel_size, rotation_bound=None, scale_bound=None):
+    """Voxelizer.get_transformation_matrix with augmentation on, n times from the generator r
+    -> (angles [n, 3], order [n, 3], scale [n], M_r [n, 4, 4], M_r @ M_v [n, 4, 4])"""
+    angles = np.zeros((n, 3))
+    if rotation_bound is not None:
+        for a, bound in enumerate(rotation_bound):
+            if bound is not None:
+                angles[:, a] = r.uniform(bound[0], bound[1], n)
+    order = np.stack([r.permutation(3) for _ in range(n)]) if n else np.zeros((0, 3), np.int64)
+    scale = np.full(n, 1.0 / voxel_size)
+    if scale_bound is not None:
+        scale = scale * r.uniform(scale_bound[0], scale_bound[1], n)
+    rotations, matrices = np.zeros((n, 4, 4)), np.zeros((n, 4, 4))
+    for s in range(n):
+        rots = [axis_rotation(a, angles[s, a]) for a in range(3)]
+        m_r, m_v = np.eye(4), np.eye(4)
+        m_r[:3, :3] = rots[order[s, 0]] @ rots[order[s, 1]] @ rots[order[s, 2]]
+        np.fill_diagonal(m_v[:3, :3], scale[s])
+        rotations[s], matrices[s] = m_r, m_r @ m_v
+    return angles, order, scale, rotations, matrices
+
+
+# ---- class-balanced tail-instance paste
+class InstanceBank:
+    """The cropped instances of the training set, concatenated on the device.  points float32 [M, 3] in world units, colors [M, 3],
+    labels [M] (HIP tensors); offsets: host CSR, I + 1 integers; categories: one host category id per instance."""
+
+    def __init__(self, points, colors, labels, offsets, categories):
+        for t, what in ((points, "bank points"), (colors, "bank colors"), (labels, "bank labels")):
+            _require_hip(t, what)
+        self.points = points.detach().to(torch.float32).contiguous()
+        self.colors = colors.detach().to(torch.float32).contiguous()
+        self.labels = labels.detach().to(torch.int64).contiguous()
+        m = self.points.shape[0]
+        assert self.points.shape == (m, 3) and self.colors.shape == (m, 3) and self.labels.shape == (m,)
+        self.offsets = np.asarray(offsets, np.int64).reshape(-1)
+        self.categories = np.asarray(categories, np.int64).reshape(-1)
+        if (len(self.offsets) != len(self.categories) + 1 or self.offsets[0] != 0 or self.offsets[-1] != m
+                or (np.diff(self.offsets) < 1).any()):
+            raise ValueError("InstanceBank: offsets must be I + 1 increasing integers from 0 to the number of rows, one more than categories")
+
+
+@dataclasses.dataclass
+class PastePlan:
+    """every host decision of one batch's paste; see TailInstancePaste.draw"""
+    bank: object                      # the InstanceBank the instance indices refer to
+    instances: np.ndarray             # [B, K] int     bank instance per (scene, paste), -1 = none
+    categories: np.ndarray            # [B, K] int     the category that was drawn for it
+    matrices: np.ndarray              # [B, K, 4, 4]   the instance's own M_r @ M_v (it is voxelised with augmentation on)
+    scene_seeds: np.ndarray           # [B] uint32     per-scene Philox key word
+    seed: int                         # the batch's 64-bit Philox seed
+    max_iterations: int               # placement trials per instance
+    max_map_cells: int                # a scene whose height map is larger is left unpasted
+
+
+class TailInstancePaste:
+    """The host side of --sample_tail_instances: per scene num_instances categories from class_ids with probability weights
+    (np.random.choice(VALID_CLASS_IDS, n, p=instance_sampling_weights)), one instance of that category uniformly
+    (random.choice(os.listdir(cat_path))), and the instance's own voxeliser matrix.  `bank` needs host `offsets` and `categories`."""
+
+    def __init__(self, bank, class_ids, weights, num_instances=5, max_iterations=50, max_map_cells=1 << 18, seed=0, rigid=None):
+        self.bank = bank
+        self.class_ids = np.asarray(class_ids, np.int64).reshape(-1)
+        w = np.asarray(weights, np.float64).reshape(-1)
+        if w.shape != self.class_ids.shape or (w < 0).any() or not w.sum() > 0:
+            raise ValueError("TailInstancePaste: weights must be one non-negative number per class id, not all zero")
+        self.weights = w / w.sum()
+        self.num_instances, self.max_iterations, self.max_map_cells = int(num_instances), int(max_iterations), int(max_map_cells)
+        if self.num_instances < 0 or self.max_iterations < 1 or not 1 <= self.max_map_cells <= 1 << 26:
+            raise ValueError("TailInstancePaste: num_instances >= 0, max_iterations >= 1, 1 <= max_map_cells <= 2^26")
+        cats = np.asarray(bank.categories, np.int64)
+        self.by_category = {int(c): np.flatnonzero(cats == c) for c in self.class_ids}
+        missing = [int(c) for c, p in zip(self.class_ids, self.weights) if p > 0 and len(self.by_category[int(c)]) == 0]
+        if missing:
+            raise ValueError("TailInstancePaste: the bank has no instance of categories %r, which have a sampling weight" % missing[:8])
+        self.rigid = rigid            # callable(generator, n) -> [n, 4, 4]; DeviceAugmentation binds its own voxeliser's
+        self.rng = np.random.default_rng(seed)
+
+    def draw(self, batch_size, rigid=None):
+        B, K, r = int(batch_size), self.num_instances, self.rng
+        if B * K > engine.LGS_PASTE_MAX_SLOTS:
+            raise ValueError("TailInstancePaste: B * K = %d (scene, instance) slots, more than LGS_PASTE_MAX_SLOTS = %d"
+                             % (B * K, engine.LGS_PASTE_MAX_SLOTS))
+        rigid = rigid if rigid is not None else self.rigid
+        categories = r.choice(self.class_ids, size=(B, K), p=self.weights).astype(np.int64)
+        instances = np.zeros((B, K), np.int64)
+        for s in range(B):
+            for k in range(K):
+                pool = self.by_category[int(categories[s, k])]
+                instances[s, k] = pool[r.integers(0, len(pool))]
+        matrices = np.tile(np.eye(4), (B, K, 1, 1)) if rigid is None else np.asarray(rigid(r, B * K), np.float64).reshape(B, K, 4, 4)
+        scene_seeds = r.integers(0, 1 << 32, B, dtype=np.uint64).astype(np.uint32)
+        return PastePlan(self.bank, instances, categories, matrices, scene_seeds, int(r.integers(0, 1 << 63)), self.max_iterations,
+                         self.max_map_cells)
+
+
+def paste_instances(coords, feats, labels, scene_offsets, scene_boxes, plan, scale, rotations, trial_draws=None, return_state=False):
+    """add_instances_to_cloud on every scene of a batch (csrc/lgs_paste.hip), without a host synchronisation.
+    coords int32 [N, 4]: scene rows at floor(M_v p), scene index in column 0; feats [N, 3]; labels [N]; scene_offsets: B + 1 host
+    integers.  scene_boxes: per scene a host float64 [m_s, 2, 3] array of world-space (min, max) corners, or None.  plan: a PastePlan.
+    scale [B]: the scalar of each scene's M_v; rotations [B, 4, 4] or [B, 3, 4]: each scene's M_r.
+    trial_draws: None (Philox) or int [B, K, T, 2], the (x, y) of every trial (teacher-forced).
+    -> (coords_out [n, 4] int32, feats_out [n, 3] float32, labels_out [n] int64, offsets_out (B + 1 host integers), status): per scene
+    its own rows, then instance 0 .. K - 1, every row rotated by M_r.  A scene without rows gets no instances.  aug_status(status)
+    names the scenes that were left unpasted (height map larger than plan.max_map_cells, instance voxel outside 18 bits); their
+    instance rows are copies of the scene's first row, which the dedup drops.
+    return_state: also {"placement": device int32 [S, 4] = (winning trial, centroid), "slots": [(scene, k)]}."""
+    for t, what in ((coords, "coords"), (feats, "feats"), (labels, "labels")):
+        _require_hip(t, what)
+    assert coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 4
+    dev = coords.device
+    c = coords.contiguous()
+    f = feats.detach().to(torch.float32).contiguous()
+    lab = labels.detach().to(torch.int64).contiguous()
+    n = c.shape[0]
+    assert f.shape == (n, 3) and lab.shape == (n,)
+    off = _host_offsets(scene_offsets, n)
+    B = len(off) - 1
+    if not 1 <= B <= MAX_SCENES:
+        raise ValueError("paste_instances takes 1 .. %d scenes per call" % MAX_SCENES)
+    bank = plan.bank
+    _require_hip(bank.points, "the bank")
+    inst = np.asarray(plan.instances, np.int64).reshape(B, -1)
+    K, T = inst.shape[1], int(plan.max_iterations)
+    if ((inst >= len(bank.categories)) | (inst < -1)).any():
+        raise ValueError("paste_instances: the plan names an instance the bank does not have")
+    slots = [(s, k) for s in range(B) if off[s + 1] > off[s] for k in range(K) if inst[s, k] >= 0]
+    S = len(slots)
+    if S > engine.LGS_PASTE_MAX_SLOTS:
+        raise ValueError("paste_instances: %d (scene, instance) slots, more than LGS_PASTE_MAX_SLOTS = %d (B * K)"
+                         % (S, engine.LGS_PASTE_MAX_SLOTS))
+    boxes = [np.zeros((0, 6)) if bx is None else np.asarray(bx, np.float64).reshape(-1, 6) for bx in (scene_boxes or [None] * B)]
+    assert len(boxes) == B
+    # the tables, front to back in one buffer of 8-byte words: one pinned upload
+    SC, CC = engine.LGS_PASTE_SLOT_COLS, engine.LGS_PASTE_SCENE_COLS
+    slot_table, scene_table = np.zeros((S + 1, SC), np.int64), np.zeros((B + 1, CC), np.int64)
+    slot_aff = np.zeros((S, 12))
+    mats = np.asarray(plan.matrices, np.float64).reshape(B, K, 4, 4)
+    rows = np.diff(bank.offsets)
+    offsets_out, pos, inst_rows, at = [0], 0, 0, 0
+    for s in range(B):
+        scene_table[s] = (pos, sum(len(b_) for b_ in boxes[:s]), int(np.asarray(plan.scene_seeds)[s]), off[s])
+        pos += off[s + 1] - off[s]
+        while at < S and slots[at][0] == s:
+            k = slots[at][1]
+            i = int(inst[s, k])
+            slot_table[at] = (bank.offsets[i], inst_rows, pos, s, k, rows[i])
+            slot_aff[at] = mats[s, k, :3, :4].reshape(-1)
+            pos, inst_rows, at = pos + int(rows[i]), inst_rows + int(rows[i]), at + 1
+        offsets_out.append(pos)
+    n_boxes = sum(len(b_) for b_ in boxes)
+    slot_table[S, 1] = inst_rows
+    scene_table[B] = (pos, n_boxes, 0, n)
+    xf = np.zeros((B, 13))
+    xf[:, 0] = np.asarray(scale, np.float64).reshape(B)
+    xf[:, 1:] = np.asarray(rotations, np.float64)[:, :3, :4].reshape(B, 12)
+    parts = [slot_table.reshape(-1), slot_aff.reshape(-1).view(np.int64), scene_table.reshape(-1), xf.reshape(-1).view(np.int64),
+             np.concatenate(boxes).reshape(-1).view(np.int64)]
+    starts = np.concatenate([[0], np.cumsum([p.size for p in parts])])
+    draws = None
+    if trial_draws is not None and S:
+        td = np.asarray(trial_draws).reshape(B, K, T, 2)
+        draws = np.stack([td[s, k] for s, k in slots]).astype(np.int32)
+    L = engine.lib()
+    with torch.cuda.device(dev):
+        tables = _upload(np.concatenate(parts), dev)
+        ptr = [ctypes.c_void_p(tables.data_ptr() + 8 * int(a)) for a in starts[:5]]
+        draws_dev = None if draws is None else _upload(draws, dev)
+        nbytes = int(L.lgs_paste_workspace_bytes(B, S, inst_rows, int(plan.max_map_cells)))
+        if nbytes <= 0:
+            raise ValueError("paste_instances: bad shape (max_map_cells must be 1 .. 2^26)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        coords_out = torch.empty((n + inst_rows, 4), dtype=torch.int32, device=dev)
+        feats_out = torch.empty((n + inst_rows, 3), dtype=torch.float32, device=dev)
+        labels_out = torch.empty(n + inst_rows, dtype=torch.int64, device=dev)
+        placement = torch.empty((S, 4), dtype=torch.int32, device=dev)
+        engine.check(L.lgs_paste_instances(_vp(c), _vp(f), _vp(lab), n, B, _vp(bank.points), _vp(bank.colors), _vp(bank.labels),
+                                           bank.points.shape[0], ptr[0], ptr[1], S, inst_rows, ptr[2], ptr[3], ptr[4], n_boxes,
+                                           _vp(draws_dev), T, _i64(plan.seed), int(plan.max_map_cells), _vp(ws), _vp(coords_out),
+                                           _vp(feats_out), _vp(labels_out), _vp(placement), _vp(status), _stream(dev)))
+    out = (coords_out, feats_out, labels_out, offsets_out, status)
+    return out + ({"placement": placement, "slots": slots},) if return_state else out
+
+
 _REFUSED = ("random_dropout", "hue_saturation", "clip_bound", "instance_augmentation")
 
 
 class DeviceAugmentation:
     """The reference's default train-time chain for one batch: elastic stages -> per-scene rigid matrix + floor -> dedup (first
     occurrence wins) -> flip on the voxel rows -> colour on the voxel rows.  `draw` makes the host decisions, `__call__` runs the
-    kernels.  At most 32 scenes per batch."""
+    kernels.  At most 32 scenes per batch.  With tail_instances (a TailInstancePaste) the second step becomes: M_v + floor -> paste
+    the drawn instances -> M_r + floor of every row (paste_instances); the dedup after it is still the chain's only one."""
 
     def __init__(self, voxel_size, elastic_params=((0.2, 0.4), (0.8, 1.6)), rotation_bound=None, scale_bound=None, rotation_axis="z",
                  color_trans_ratio=0.1, color_jitter_std=0.05, color_scale=1.0, normalize_color=False, coordinate_shift=False,
                  max_cells=DEFAULT_MAX_CELLS, seed=0, random_dropout=None, hue_saturation=None, clip_bound=None,
-                 instance_augmentation=None, num_pairs=1):
+                 instance_augmentation=None, num_pairs=1, tail_instances=None):
         given = dict(random_dropout=random_dropout, hue_saturation=hue_saturation, clip_bound=clip_bound,
                      instance_augmentation=instance_augmentation)
         for name in _REFUSED:
@@ -346,6 +541,9 @@ class DeviceAugmentation:
         self.coordinate_shift = bool(coordinate_shift)
         self.max_cells = int(max_cells)
         self.rng = np.random.default_rng(seed)
+        self.tail = tail_instances
+        if self.tail is not None and self.tail.rigid is None:          # an instance is voxelised by the scene's voxeliser, augmentation on
+            self.tail.rigid = lambda r, n: draw_rigid(r, n, self.voxel_size, self.rotation_bound, self.scale_bound)[4]
 
     @classmethod
     def from_dataset(cls, DatasetClass, config, **kw):
@@ -355,6 +553,15 @@ class DeviceAugmentation:
         if float(getattr(config, "data_aug_patch_dropout_ratio", 0.35)) == 0.0:
             kw.setdefault("random_dropout", 0.2)          # lib/dataset.py:385 adds RandomDropout in that case only
         elastic = DatasetClass.ELASTIC_DISTORT_PARAMS if getattr(config, "elastic_distortion", True) else None
+        bank, weights = kw.pop("instance_bank", None), kw.pop("instance_sampling_weights", None)
+        if getattr(config, "sample_tail_instances", False) and kw.get("tail_instances") is None:
+            if bank is None:
+                raise NotImplementedError("DeviceAugmentation: config.sample_tail_instances needs instance_bank= (the cropped training "
+                                          "instances as an InstanceBank); without one the recipe would train without its tail instances")
+            ids = np.asarray(DatasetClass.VALID_CLASS_IDS)
+            kw["tail_instances"] = TailInstancePaste(bank, ids, np.ones(len(ids)) if weights is None else weights,
+                                                     num_instances=config.num_instances_to_add,
+                                                     max_iterations=config.max_instance_placing_iterations, seed=kw.get("seed", 0))
         return cls(voxel_size=DatasetClass.VOXEL_SIZE, elastic_params=elastic,
                    rotation_bound=DatasetClass.ROTATION_AUGMENTATION_BOUND, scale_bound=DatasetClass.SCALE_AUGMENTATION_BOUND,
                    rotation_axis=DatasetClass.ROTATION_AXIS, color_trans_ratio=config.data_aug_color_trans_ratio,
@@ -374,27 +581,13 @@ class DeviceAugmentation:
         translate = r.random(B) < 0.95
         translation = (r.random((B, 3)) - 0.5) * 255 * 2 * self.color_trans_ratio
         jitter = r.random(B) < 0.95
-        angles = np.zeros((B, 3))
-        if self.rotation_bound is not None:
-            for a, bound in enumerate(self.rotation_bound):
-                if bound is not None:
-                    angles[:, a] = r.uniform(bound[0], bound[1], B)
-        order = np.stack([r.permutation(3) for _ in range(B)]) if B else np.zeros((0, 3), np.int64)
-        scale = np.full(B, 1.0 / self.voxel_size)
-        if self.scale_bound is not None:
-            scale = scale * r.uniform(self.scale_bound[0], self.scale_bound[1], B)
-        matrices = np.zeros((B, 4, 4))
-        for s in range(B):
-            rots = [axis_rotation(a, angles[s, a]) for a in range(3)]
-            m_r, m_v = np.eye(4), np.eye(4)
-            m_r[:3, :3] = rots[order[s, 0]] @ rots[order[s, 1]] @ rots[order[s, 2]]
-            np.fill_diagonal(m_v[:3, :3], scale[s])
-            matrices[s] = m_r @ m_v
+        angles, order, scale, rotations, matrices = draw_rigid(r, B, self.voxel_size, self.rotation_bound, self.scale_bound)
         scene_seeds = r.integers(0, 1 << 32, B, dtype=np.uint64).astype(np.uint32)
         seed = int(r.integers(0, 1 << 63))
         shift = np.floor(r.random(3) * 100).astype(np.int64) if self.coordinate_shift else np.zeros(3, np.int64)
+        paste = self.tail.draw(B) if self.tail is not None else None          # from the paste's own generator
         return AugmentPlan(elastic, flip_axes, autocontrast, blend, translate, translation, jitter, angles, order, scale, matrices,
-                           scene_seeds, seed, shift)
+                           scene_seeds, seed, shift, rotations=rotations, paste=paste)
 
     def color_params(self, plan):
         return [ColorParams(blend=float(plan.blend[s]) if plan.autocontrast[s] else None,
@@ -402,10 +595,13 @@ class DeviceAugmentation:
                             jitter_std=self.color_jitter_std if plan.jitter[s] else None, seed=int(plan.scene_seeds[s]))
                 for s in range(len(plan.elastic))]
 
-    def __call__(self, points, colors, labels, scene_offsets, plan=None, elastic_noise=None, jitter_noise=None, return_state=False):
+    def __call__(self, points, colors, labels, scene_offsets, plan=None, elastic_noise=None, jitter_noise=None, return_state=False,
+                 scene_boxes=None, trial_draws=None):
         """points [N, 3], colors [N, 3], labels [N] (HIP tensors), scene_offsets (B + 1 host integers)
         -> (coords [n, 4] int32, feats [n, 3] float32, labels [n]) of the surviving voxel rows.
-        elastic_noise: per stage a list of per-scene noise arrays; jitter_noise: callable(n) or device [n, 3] normals (teacher-forced)."""
+        elastic_noise: per stage a list of per-scene noise arrays; jitter_noise: callable(n) or device [n, 3] normals (teacher-forced).
+        With tail_instances: scene_boxes (per scene a host [m_s, 2, 3] array of the scene's instance boxes, world units) and
+        optionally trial_draws, as paste_instances takes them; the voxeliser then applies M_v only and the paste rotates."""
         for t, what in ((points, "points"), (colors, "colors"), (labels, "labels")):
             _require_hip(t, what)
         dev = points.device
@@ -414,7 +610,10 @@ class DeviceAugmentation:
         if B > MAX_SCENES:
             raise ValueError("DeviceAugmentation takes at most %d scenes per batch" % MAX_SCENES)
         plan = self.draw(B) if plan is None else plan
+        if self.tail is not None and (plan.paste is None or plan.rotations is None):
+            raise ValueError("DeviceAugmentation: the plan has no paste decisions (draw it from this chain)")
         state = {"status": [], "stages": []}
+        feats_in, labels_in = None, labels
         previous = torch.cuda.get_sync_debug_mode()
         torch.cuda.set_sync_debug_mode("error")        # nothing before the dedup's own row count may synchronise
         try:
@@ -432,18 +631,29 @@ class DeviceAugmentation:
                         if return_state:
                             state["stages"].append(pts.clone())
                     state["status"].append(status)
-                coords = voxelize_batched(pts, off, plan.matrices, offsets_dev=off_dev)
+                if self.tail is None:
+                    coords = voxelize_batched(pts, off, plan.matrices, offsets_dev=off_dev)
+                else:                 # lib/datasets/scannet.py:344-347: voxelise without augmentation, paste, then rotate
+                    m_v = np.tile(np.eye(4), (B, 1, 1)) * np.asarray(plan.scale).reshape(B, 1, 1)
+                    m_v[:, 3, 3] = 1.0
+                    vox = voxelize_batched(pts, off, m_v, offsets_dev=off_dev)
+                    coords, feats_in, labels_in, off_p, pstatus, pstate = paste_instances(
+                        vox, colors, labels, off, scene_boxes, plan.paste, plan.scale, plan.rotations, trial_draws=trial_draws,
+                        return_state=True)
+                    state.update(paste_status=pstatus, paste=pstate, paste_offsets=off_p)
+                    if return_state:
+                        state.update(voxels=vox, pasted=(coords, feats_in, labels_in))
         finally:
             torch.cuda.set_sync_debug_mode(previous)
         from .me.utils import sparse_quantize
         keep = sparse_quantize(coords, return_maps_only=True)          # first occurrence wins, indices ascending (one host sync)
         coords, off_vox = horizontal_flip(coords.index_select(0, keep), plan.flip_axes, shift=plan.shift, batch_size=B, return_offsets=True)
-        feats = colors.detach().to(torch.float32).index_select(0, keep)
+        feats = (colors.detach().to(torch.float32) if feats_in is None else feats_in).index_select(0, keep)
         if callable(jitter_noise):
             jitter_noise = jitter_noise(feats.shape[0])
         feats = chromatic_augment(feats, off_vox, self.color_params(plan), scale=self.color_scale, normalize=self.normalize_color,
                                   seed=plan.seed, noise=jitter_noise)
-        out = (coords, feats, labels.index_select(0, keep))
+        out = (coords, feats, labels_in.index_select(0, keep).to(labels.dtype))
         if return_state:
             state["points"], state["keep"] = pts, keep
             return out + (state,)

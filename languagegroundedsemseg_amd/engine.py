@@ -13,6 +13,8 @@ LGS_F32, LGS_BF16 = 0, 1
 LGS_SUPCON_COS, LGS_SUPCON_L2 = 0, 1     # `distance` of lgs_supcon_forward / lgs_supcon_backward
 LGS_AUG_MAX_SCENES = 32                  # scenes per call of the lgs_aug_* / lgs_elastic_* / lgs_color_* entry points
 LGS_AUG_F32X3, LGS_AUG_I32X4 = 0, 1      # `form` of lgs_aug_bounds
+LGS_PASTE_MAX_SLOTS = 1024               # (scene, instance) slots per call of lgs_paste_instances
+LGS_PASTE_SLOT_COLS, LGS_PASTE_SCENE_COLS = 6, 4
 LGS_COLOR_AUTOCONTRAST, LGS_COLOR_TRANSLATION, LGS_COLOR_JITTER = 1, 2, 4     # lgs_color_scene.flags
 ABI_VERSION = 18     # LGS_ABI_VERSION of include/lgs_engine.h
 
@@ -228,6 +230,7 @@ EXPORTS = [
     "lgs_voxelize", "lgs_label_vote", "lgs_cluster_workspace_bytes", "lgs_cluster", "lgs_sgd_step",
     "lgs_aug_bounds", "lgs_elastic_workspace_bytes", "lgs_elastic_distort", "lgs_voxelize_batched", "lgs_coords_flip_shift",
     "lgs_color_augment", "lgs_aug_status", "lgs_debug_philox",
+    "lgs_paste_workspace_bytes", "lgs_paste_instances",
 ]
 
 
@@ -329,6 +332,8 @@ def lib():
         "lgs_color_augment": [vp, i64, vp, ci, vp, ctypes.POINTER(ColorScene), cf, ci, i64, vp, vp],
         "lgs_aug_status": [vp, pi, vp],
         "lgs_debug_philox": [vp, i64, i64, vp, vp],
+        "lgs_paste_instances": [vp, vp, vp, i64, ci, vp, vp, vp, i64, vp, vp, ci, i64, vp, vp, vp, i64, vp, ci, i64, i64, vp, vp, vp, vp,
+                                vp, vp, vp],
         "lgs_comm_unique_id": [vp],
         "lgs_comm_create": [vp, ci, ci, ci, ctypes.POINTER(vp)],
         "lgs_comm_create_ipc": [ci, ci, ci, ctypes.POINTER(vp), vp],
@@ -357,6 +362,8 @@ def lib():
     L.lgs_in_workspace_bytes.argtypes = [vp, ci]
     L.lgs_elastic_workspace_bytes.restype = i64
     L.lgs_elastic_workspace_bytes.argtypes = [ci, i64]
+    L.lgs_paste_workspace_bytes.restype = i64
+    L.lgs_paste_workspace_bytes.argtypes = [ci, ci, i64, i64]
     L.lgs_cluster_workspace_bytes.restype = i64
     L.lgs_cluster_workspace_bytes.argtypes = [i64]
     L.lgs_conv_workspace_bytes.restype = i64

@@ -93,6 +93,38 @@ def make_batch(seeds, voxel=0.02, n_target=150000, shift_seed=None, **kw):
     return coords, np.concatenate(fs, 0).astype(np.float32), np.concatenate(ls, 0)
 
 
+def make_instance_bank(n_instances=64, num_labels=200, seed=0, rows=(300, 6000)):
+    """stand-in for the cropped training instances of --sample_tail_instances (train/train_instances/<category>/*.ply): boxes of
+    0.2 .. 1.2 m with points on their surfaces, anywhere within a few metres of the origin (world units, as the crops are stored)
+    -> (points [M, 3] float32, colors [M, 3] float32, labels [M] int64, offsets [I + 1] int64, categories [I] int64)"""
+    rng = np.random.default_rng(seed)
+    pts, cats, off = [], [], [0]
+    for i in range(n_instances):
+        n = int(rng.integers(rows[0], rows[1]))
+        size, origin = 0.2 + rng.random(3), rng.random(3) * 6 - 3
+        p = rng.random((n, 3))
+        face = rng.integers(0, 6, n)
+        p[np.arange(n), face % 3] = face // 3                  # every point on one of the six faces
+        pts.append((origin + p * size).astype(np.float32))
+        cats.append(int(rng.integers(0, num_labels)))
+        off.append(off[-1] + n)
+    points = np.concatenate(pts)
+    colors = np.floor(rng.random(points.shape) * 256).astype(np.float32)
+    labels = np.repeat(np.asarray(cats, np.int64), np.diff(off))
+    return points, colors, labels, np.asarray(off, np.int64), np.asarray(cats, np.int64)
+
+
+def make_scene_boxes(points, n_boxes=25, seed=0):
+    """stand-in for one scene's entry of the bounding-box pickle: n_boxes instance boxes of 0.3 .. 1.5 m standing on the floor inside
+    the scene's footprint -> float64 [n_boxes, 2, 3] (min corner, max corner), world units"""
+    rng = np.random.default_rng(seed)
+    lo, hi = points.min(0).astype(np.float64), points.max(0).astype(np.float64)
+    size = 0.3 + rng.random((n_boxes, 3)) * 1.2
+    corner = lo + rng.random((n_boxes, 3)) * np.maximum(hi - lo - size, 0.0)
+    corner[:, 2] = lo[2]
+    return np.stack([corner, corner + size], 1)
+
+
 def text_anchors(num_labels=200, dim=512, seed=1234):
     """stand-in for clip_feats_scannet_200.pkl (lib/datasets/prior_info.py:25-28): T ~ N(0,1)^{200 x 512}"""
     return np.random.default_rng(seed).standard_normal((num_labels, dim)).astype(np.float32)

@@ -1,6 +1,7 @@
 """Per-op timings on the GPU (HIP events on torch's current stream) for the hot layer shapes.
-usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal | supcon | augment | nearest | ap]"""
+usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal | supcon | augment | paste | nearest | ap]"""
 import os
+import re
 import sys
 import time
 
@@ -766,6 +767,81 @@ def augment():
           % (sum(t_cpu.values()) * 1e3, 8 * sum(t_cpu.values()) * 1e3, t_chain))
 
 
+def paste():
+    """The class-balanced tail-instance paste (csrc/lgs_paste.hip) on the benchmark's 8-scene batch with a synthetic bank and boxes:
+    the call, its kernels one by one (the profiler's device times), what it adds to the augmentation chain, and the numpy
+    restatement of the reference's host method (tests/paste_reference.py, scene 0, one thread) beside it"""
+    from languagegroundedsemseg_amd import augment as A
+    from languagegroundedsemseg_amd.synthetic import make_instance_bank, make_scene_boxes
+    coords, feats, labels = make_batch(list(range(8)), n_target=150000, shift_seed=0)
+    rng = np.random.default_rng(0)
+    order = np.argsort(coords[:, 0], kind="stable")
+    coords, labels = coords[order], labels[order]
+    rep = np.repeat(coords, 2, 0)
+    pts = ((rep[:, 1:].astype(np.float64) + rng.uniform(0.05, 0.95, (rep.shape[0], 3))) * 0.02).astype(np.float32)
+    off = np.concatenate([[0], np.cumsum(np.bincount(rep[:, 0], minlength=8))]).tolist()
+    for s in range(8):
+        pts[off[s]:off[s + 1]] -= pts[off[s]:off[s + 1]].min(0)
+    cols = np.floor(rng.random(pts.shape) * 256).astype(np.float32)
+    lab_h = np.repeat(labels, 2)
+    p, c, lab = torch.from_numpy(pts).to(DEV), torch.from_numpy(cols).to(DEV), torch.from_numpy(lab_h).to(DEV)
+    n = p.shape[0]
+    bp, bc, bl, boff, bcat = make_instance_bank()
+    bank = A.InstanceBank(torch.from_numpy(bp).to(DEV), torch.from_numpy(bc).to(DEV), torch.from_numpy(bl).to(DEV), boff, bcat)
+    ids = np.unique(bcat)
+    kw = dict(voxel_size=0.02, rotation_bound=((-np.pi / 64, np.pi / 64), (-np.pi / 64, np.pi / 64), (-np.pi, np.pi)), scale_bound=(0.9, 1.1),
+              normalize_color=True, seed=1)
+    aug = A.DeviceAugmentation(tail_instances=A.TailInstancePaste(bank, ids, np.ones(len(ids)), num_instances=5, max_iterations=50, seed=2), **kw)
+    plain = A.DeviceAugmentation(**kw)
+    plan = aug.draw(8)
+    plan.elastic[:], plan.autocontrast[:], plan.translate[:], plan.jitter[:] = True, True, True, True
+    plan.flip_axes[:] = 3
+    boxes = [make_scene_boxes(pts[off[s]:off[s + 1]], seed=s) for s in range(8)]
+    m_v = np.stack([np.diag([v, v, v, 1.0]) for v in plan.scale])
+    vox = A.voxelize_batched(p, off, m_v)
+    inst_rows = int(np.diff(boff)[plan.paste.instances].sum())
+    print("%d points in 8 scenes, 40 instances of %d rows, %d boxes per scene" % (n, inst_rows, len(boxes[0])))
+
+    def call():
+        return A.paste_instances(vox, c, lab, off, boxes, plan.paste, plan.scale, plan.rotations, return_state=True)
+    out = call()
+    assert A.aug_status(out[4]) == []
+    trials = out[5]["placement"][:, 0].cpu().numpy()
+    print("winning trials: %d at trial 0, %d later, %d exhausted" % ((trials == 0).sum(), ((trials > 0) & (trials < 50)).sum(), (trials == 50).sum()))
+    t_call = timeit(call, iters=20)
+    print("%-52s %8.3f ms per batch" % ("paste_instances (tables, upload, 8 launches)", t_call))
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            for _ in range(10):
+                call()
+            torch.cuda.synchronize()
+        for ev in sorted(prof.key_averages(), key=lambda e: e.key):
+            if "k_paste" in ev.key or "k_aug_bounds" in ev.key or "k_aug_scene" in ev.key:
+                us = getattr(ev, "device_time_total", None) or getattr(ev, "cuda_time_total", 0.0)
+                name = re.search(r"k_[a-z_]+(<[^>]*>)?", ev.key).group(0)
+                print("  %-50s %8.1f us per call (%d launches)" % (name, us / 10.0, ev.count // 10))
+    except Exception as e:      # the profiler is a convenience: the call's own time above stands without it
+        print("  (no per-kernel times: %s)" % e)
+    t_plain = timeit(lambda: plain(p, c, lab, off, plan=plan), iters=10)
+    t_tail = timeit(lambda: aug(p, c, lab, off, plan=plan, scene_boxes=boxes), iters=10)
+    print("%-52s %8.3f ms per batch" % ("chain without the paste", t_plain))
+    print("%-52s %8.3f ms per batch  (+ %.3f ms)" % ("chain with the paste", t_tail, t_tail - t_plain))
+    # the numpy restatement of the reference's host method on scene 0, one thread: three dedups, filter over the whole map, sequential trials
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import paste_reference as pr
+    torch.set_num_threads(1)
+    v0 = vox[off[0]:off[1], 1:].cpu().numpy()
+    inst = [(bp[boff[i]:boff[i + 1]], bc[boff[i]:boff[i + 1]], bl[boff[i]:boff[i + 1]], plan.paste.matrices[0, k])
+            for k, i in enumerate(plan.paste.instances[0])]
+    t0 = time.perf_counter()
+    pr.paste_scene(v0, cols[off[0]:off[1]], lab_h[off[0]:off[1]], boxes[0], plan.scale[0], plan.rotations[0], inst, None, 50,
+                   seeds=(plan.paste.seed, plan.paste.scene_seeds[0]))
+    t_cpu = time.perf_counter() - t0
+    print("numpy restatement, scene 0 (%d points), 1 thread: %.1f ms (x 8 scenes = %.0f ms per batch; device call %.3f ms)"
+          % (len(v0), t_cpu * 1e3, 8 * t_cpu * 1e3, t_call))
+
+
 def nearest():
     """lgs_manager_nearest at the evaluation shape -- 8 scenes x ~150 k voxels, three points inside every occupied cell -- at
     NEAREST_MAX_RING 1, 2 and 4, anchors 0.0 and 0.5, with both lookup tables, and the share of queries that the ring search leaves to
@@ -974,6 +1050,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "augment":
         augment()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "paste":
+        paste()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "supcon":
         supcon()
