@@ -93,8 +93,8 @@ int lgs_manager_stride2(lgs_manager *mgr, int in_key, void *stream, int *out_key
  * (test / debug infrastructure: the map builders size coarse maps from counts taken at insert time and never synchronise;
  * a builder that finds its own count disagreeing raises the flag instead of writing past its arrays).  *flags: 0 = consistent,
  * bit 0 = coordinate out of the key range at insert, bit 1 = a coarse map's row count differs from the insert-time count,
- * bit 2 = the origin map's row count differs from the insert-time batch count, bit 3 = a map's block directory (3^3 neighbour lookup)
- * found its table full, which its sizing from the insert-time counts rules out.
+ * bit 2 = the origin map's row count differs from the insert-time batch count, bit 3 = a map's lookup table (3^3 neighbour lookup: the block
+ * directory, or the hash table of MAP_BLOCK_DIR = 0) was found full while it was filled, which its sizing at twice the entries rules out.
  * Same call sites as lgs_manager_stride2.                                                                             */
 int lgs_manager_check(lgs_manager *mgr, int *flags);
 

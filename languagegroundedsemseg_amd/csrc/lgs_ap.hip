@@ -47,11 +47,9 @@ constexpr int kColSplit = 4096;                        //   16 KiB of splitters:
 constexpr int64_t kColRows = 60 * kColThreads;         //   at most 61 440 (< 2^16) rows per slab
 constexpr int64_t kColMinElems = 1 << 19;              // n c from which the rank pass keeps its counters in LDS
 
-// order-preserving float -> uint32 (-0 counts as +0)
-__device__ inline uint32_t ord_of(float f) {
-  const uint32_t u = f == 0.f ? 0u : __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// ord_key with -0 counted as +0: sklearn compares scores as numbers, and the plain map would rank a -0.0 below a +0.0
+// (the zero is chosen on the bit pattern, as it always was: that keeps the instruction streams of the class-row kernels)
+__device__ inline uint32_t ord_of(float f) { return ord_key_of_bits(f == 0.f ? 0u : __float_as_uint(f)); }
 __device__ inline bool counted(int64_t lab, int64_t ignore_index, int c) { return lab != ignore_index && lab >= 0 && lab < c; }
 __device__ inline uint32_t key_lo(const uint64_t *__restrict__ k, int64_t i) { return (uint32_t)k[i]; }
 
@@ -156,7 +154,7 @@ __global__ void k_ap_offsets(const uint64_t *__restrict__ skeys, int64_t n, int 
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t > c) return;
   const uint64_t k = (uint64_t)t << 32;
-  int64_t lo = 0, hi = n;
+  int64_t lo = 0, hi = n;      // lower_bound, spelled out here and in k_ap_terms: a case measured outside the parent's spread with the helper
   while (lo < hi) {
     const int64_t mid = (lo + hi) >> 1;
     if (skeys[mid] < k) lo = mid + 1; else hi = mid;
@@ -461,8 +459,7 @@ extern "C" int64_t lgs_ap_workspace_bytes(int64_t n, int c) {
   if (n < 0 || c < 1 || c > kMaxClasses) return -1;
   size_t sort_b = 0, scan_b = 0;
   if (rocprim_bytes(n, c, (hipStream_t)0, &sort_b, &scan_b)) return -1;
-  // rocprim's temporary, keys (later the terms), sorted keys, counters, their scan, (max, se) per row, off[c + 1], mn[c]
-  return align256((int64_t)std::max(sort_b, scan_b)) + 3 * align256(8 * (n + 1)) + 2 * align256(4 * (n + 1)) + 2 * align256(4 * (c + 1)) + 256;
+  return ap_layout(n, c, (int64_t)std::max(sort_b, scan_b)).total;
 }
 
 extern "C" int lgs_average_precision(const void *scores, int64_t n, int c, const int64_t *labels, int64_t ignore_index, int from_logits,
@@ -480,16 +477,13 @@ extern "C" int lgs_average_precision(const void *scores, int64_t n, int c, const
   }
   size_t sort_b = 0, scan_b = 0;
   if (int rc = rocprim_bytes(n, c, s, &sort_b, &scan_b)) return rc;
-  char *ws = reinterpret_cast<char *>(workspace);
-  void *tmp = ws; ws += align256((int64_t)std::max(sort_b, scan_b));
-  uint64_t *keys = reinterpret_cast<uint64_t *>(ws); ws += align256(8 * (n + 1));
-  uint64_t *skeys = reinterpret_cast<uint64_t *>(ws); ws += align256(8 * (n + 1));
-  float2 *rowstat = reinterpret_cast<float2 *>(ws); ws += align256(8 * (n + 1));
-  uint32_t *cnt = reinterpret_cast<uint32_t *>(ws); ws += align256(4 * (n + 1));
-  uint32_t *pfx = reinterpret_cast<uint32_t *>(ws); ws += align256(4 * (n + 1));
-  uint32_t *off = reinterpret_cast<uint32_t *>(ws); ws += align256(4 * (c + 1));
-  uint32_t *mn = reinterpret_cast<uint32_t *>(ws);
-  double *terms = reinterpret_cast<double *>(keys);      // the unsorted keys are dead after the sort
+  const ApWs w = ap_layout(n, c, (int64_t)std::max(sort_b, scan_b));
+  void *tmp = Layout::at<char>(workspace, w.tmp);
+  uint64_t *keys = Layout::at<uint64_t>(workspace, w.keys), *skeys = Layout::at<uint64_t>(workspace, w.skeys);
+  double *terms = Layout::at<double>(workspace, w.terms);
+  float2 *rowstat = Layout::at<float2>(workspace, w.rowstat);
+  uint32_t *cnt = Layout::at<uint32_t>(workspace, w.cnt), *pfx = Layout::at<uint32_t>(workspace, w.pfx);
+  uint32_t *off = Layout::at<uint32_t>(workspace, w.off), *mn = Layout::at<uint32_t>(workspace, w.mn);
   const unsigned row_blocks = (unsigned)((n + 255) / 256);
   LGS_HIP(hipMemsetAsync(cnt, 0, sizeof(uint32_t) * n, s));
   // 1. keys

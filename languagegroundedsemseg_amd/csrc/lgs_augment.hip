@@ -33,27 +33,10 @@ constexpr int kAugScenes = LGS_AUG_MAX_SCENES;
 constexpr int kAugBlock = 256;
 constexpr int kAugWaves = kAugBlock / 64;
 constexpr int kFieldBlocks = 64;              // grid.x of the per-scene grid kernels (they loop over the scene's cells)
-constexpr uint32_t kKeyPosInf = 0xFF800000u;  // fkey(+inf)
-constexpr uint32_t kKeyNegInf = 0x007FFFFFu;  // fkey(-inf)
+constexpr uint32_t kKeyPosInf = 0xFF800000u;  // ord_key(+inf)
+constexpr uint32_t kKeyNegInf = 0x007FFFFFu;  // ord_key(-inf)
 
-// order-preserving key of a float: a < b (as numbers, and -0.0 < +0.0) <=> fkey(a) < fkey(b)
-__device__ inline uint32_t fkey(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float fkey_inv(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-__device__ inline uint32_t ikey(int32_t v) { return (uint32_t)v ^ 0x80000000u; }
-__device__ inline int32_t ikey_inv(uint32_t k) { return (int32_t)(k ^ 0x80000000u); }
-
-// the last scene s in [0, b) with off[s] <= i: the scene of row i (empty scenes share their offset with the next one and lose)
-__device__ inline int scene_of(const int64_t *__restrict__ off, int b, int64_t i) {
-  int lo = 0, hi = b - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
+__device__ inline int scene_of(const int64_t *__restrict__ off, int b, int64_t i) { return last_not_above(off, 1, b, i); }   // of row i
 
 struct SceneSeeds { uint32_t v[kAugScenes]; };
 struct AffineTable { double a[kAugScenes][12]; };
@@ -71,7 +54,7 @@ __global__ void k_aug_bounds_decode(uint32_t *__restrict__ kb, int b, int is_flo
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= b * 6) return;
   const uint32_t k = kb[t];
-  kb[t] = is_float ? __float_as_uint(fkey_inv(k)) : (uint32_t)ikey_inv(k);
+  kb[t] = is_float ? __float_as_uint(ord_key_inv(k)) : (uint32_t)ikey_inv(k);
 }
 
 // scene_offsets[b + 1] from the ascending scene ids in column 0 of coords[n, 4]; ids are clamped to [0, b)
@@ -96,16 +79,8 @@ __device__ inline void block_bounds_commit(const uint32_t (&lo)[3], const uint32
     uint32_t v[6];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      v[c] = mine ? lo[c] : 0xFFFFFFFFu;
-      v[3 + c] = mine ? hi[c] : 0u;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        v[c] = std::min(v[c], (uint32_t)__shfl_xor((int)v[c], o, 64));
-        v[3 + c] = std::max(v[3 + c], (uint32_t)__shfl_xor((int)v[3 + c], o, 64));
-      }
+      v[c] = wave_min(mine ? lo[c] : 0xFFFFFFFFu);
+      v[3 + c] = wave_max(mine ? hi[c] : 0u);
     }
     if (lane == 0) {
 #pragma unroll
@@ -138,7 +113,7 @@ __global__ void __launch_bounds__(kAugBlock) k_aug_bounds(const void *__restrict
     my_scene = scene_of(off, b, i);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      lo[c] = F32 ? fkey(static_cast<const float *>(table)[3 * i + c]) : ikey(static_cast<const int32_t *>(table)[4 * i + 1 + c]);
+      lo[c] = F32 ? ord_key(static_cast<const float *>(table)[3 * i + c]) : ikey(static_cast<const int32_t *>(table)[4 * i + 1 + c]);
       hi[c] = lo[c];
     }
   }
@@ -271,7 +246,7 @@ __global__ void __launch_bounds__(kAugBlock) k_elastic_apply(float *__restrict__
       }
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) lo[c] = hi[c] = fkey(p[c]);
+    for (int c = 0; c < 3; ++c) lo[c] = hi[c] = ord_key(p[c]);
   }
   block_bounds_commit(lo, hi, valid, s, s_first, s_last, kb_out);
 }
@@ -286,9 +261,7 @@ __global__ void __launch_bounds__(kAugBlock) k_voxelize_batched(const float *__r
   int32_t o[3];
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    const double *a = A.a[s] + 4 * r;
-    const double v = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(x, a[0]), __dmul_rn(y, a[1])), __dmul_rn(z, a[2])), a[3]);
-    o[r] = (int32_t)floor(v);
+    o[r] = (int32_t)floor(affine_row(A.a[s] + 4 * r, x, y, z));
   }
   reinterpret_cast<int4 *>(coords)[i] = make_int4(batch_base + s, o[0], o[1], o[2]);
 }
@@ -385,7 +358,7 @@ int lgs_aug_bounds(const void *table, int64_t n, int form, int64_t *scene_offset
 
 int64_t lgs_elastic_workspace_bytes(int b, int64_t max_cells) {
   if (b < 1 || b > kAugScenes || max_cells < 27 || max_cells > (1ll << 26)) return 0;
-  return 2 * align256((int64_t)b * max_cells * 3 * (int64_t)sizeof(float));      // noise slots, field slots
+  return elastic_layout(b, max_cells).total;
 }
 
 int lgs_elastic_distort(float *points, int64_t n, const int64_t *scene_offsets, int b, const float *bounds_in, double granularity,
@@ -404,8 +377,8 @@ int lgs_elastic_distort(float *points, int64_t n, const int64_t *scene_offsets, 
   if (n > 0) {
     const float g32 = (float)granularity;
     const uint32_t mask = (uint32_t)apply_mask;
-    float *ws_noise = static_cast<float *>(workspace);
-    float *ws_field = reinterpret_cast<float *>(static_cast<char *>(workspace) + align256((int64_t)b * max_cells * 3 * (int64_t)sizeof(float)));
+    const ElasticWs w = elastic_layout(b, max_cells);
+    float *ws_noise = Layout::at<float>(workspace, w.noise), *ws_field = Layout::at<float>(workspace, w.field);
     if (mask) {
       if (!noise) {
         SceneSeeds seeds;

@@ -51,15 +51,6 @@ __global__ void k_cell_keys(const float *__restrict__ xyz, const int32_t *__rest
   vals[i] = (int32_t)i;
 }
 
-__device__ inline int64_t lower_bound_key(const uint64_t *__restrict__ skeys, int64_t n, uint64_t k) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (skeys[mid] < k) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 __device__ inline int32_t uf_find(int32_t *parent_, int32_t i) {
   volatile int32_t *parent = parent_;   // other threads shorten paths concurrently; pointers only ever move towards the root
   while (true) {
@@ -99,7 +90,7 @@ __global__ void k_union_neighbours(const float *__restrict__ xyz, const int32_t 
     for (int dy = -1; dy <= 1; ++dy) {
       // the three z-cells of a (dx, dy) column are consecutive keys: one search, one contiguous scan
       const uint64_t k0 = cell_key(b, cx + dx, cy + dy, cz - 1), k1 = cell_key(b, cx + dx, cy + dy, cz + 1);
-      for (int64_t p = lower_bound_key(skeys, n, k0); p < n && skeys[p] <= k1; ++p) {
+      for (int64_t p = lower_bound(skeys, (int64_t)0, n, k0); p < n && skeys[p] <= k1; ++p) {
         const int32_t j = svals[p];
         if (j >= i || sem[j] != li) continue;               // every edge once, from its larger endpoint
         const float ddx = __fsub_rn(ox, xyz[3 * (int64_t)j]), ddy = __fsub_rn(oy, xyz[3 * (int64_t)j + 1]),
@@ -141,7 +132,7 @@ int64_t lgs_cluster_workspace_bytes(int64_t n) {
   size_t tb = 0;
   (void)rocprim::radix_sort_pairs(nullptr, tb, (uint64_t *)nullptr, (uint64_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr,
                                   (size_t)(n > 0 ? n : 1), 0, 64, (hipStream_t)0);
-  return align256((int64_t)tb) + 2 * align256(8 * (n + 1)) + 4 * align256(4 * (n + 1)) + 512;
+  return cluster_layout(n, (int64_t)tb).total;
 }
 
 int lgs_cluster(const float *xyz, const int32_t *batch_idx, const int32_t *semantic_label, int64_t n, float radius, int threshold,
@@ -151,18 +142,15 @@ int lgs_cluster(const float *xyz, const int32_t *batch_idx, const int32_t *seman
   if (n == 0) return 0;
   LGS_REQUIRE(xyz && semantic_label && component && workspace, "lgs_cluster: null argument");
   hipStream_t s = (hipStream_t)stream;
-  char *ws = reinterpret_cast<char *>(workspace);
   size_t tb = 0;
   LGS_HIP(rocprim::radix_sort_pairs(nullptr, tb, (uint64_t *)nullptr, (uint64_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr,
                                     (size_t)n, 0, 64, s));
-  void *tmp = ws; ws += align256((int64_t)tb);
-  uint64_t *keys = reinterpret_cast<uint64_t *>(ws); ws += align256(8 * (n + 1));
-  uint64_t *skeys = reinterpret_cast<uint64_t *>(ws); ws += align256(8 * (n + 1));
-  int32_t *vals = reinterpret_cast<int32_t *>(ws); ws += align256(4 * (n + 1));
-  int32_t *svals = reinterpret_cast<int32_t *>(ws); ws += align256(4 * (n + 1));
-  int32_t *parent = reinterpret_cast<int32_t *>(ws); ws += align256(4 * (n + 1));
-  int32_t *size = reinterpret_cast<int32_t *>(ws); ws += align256(4 * (n + 1));
-  int32_t *scal = reinterpret_cast<int32_t *>(ws);   // [0] error flag, [1] cluster count
+  const ClusterWs w = cluster_layout(n, (int64_t)tb);
+  void *tmp = Layout::at<char>(workspace, w.tmp);
+  uint64_t *keys = Layout::at<uint64_t>(workspace, w.keys), *skeys = Layout::at<uint64_t>(workspace, w.skeys);
+  int32_t *vals = Layout::at<int32_t>(workspace, w.vals), *svals = Layout::at<int32_t>(workspace, w.svals);
+  int32_t *parent = Layout::at<int32_t>(workspace, w.parent), *size = Layout::at<int32_t>(workspace, w.size);
+  int32_t *scal = Layout::at<int32_t>(workspace, w.scal);   // [0] error flag, [1] cluster count
   const unsigned nb = (unsigned)((n + 255) / 256);
   // cells a hair larger than the radius: two points closer than `radius` then provably sit in adjacent cells even after
   // the rounding of x * inv_r

@@ -69,8 +69,6 @@ Rccl &rccl() {
     }                                                                                                          \
   } while (0)
 
-inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace
 
 // ---- device-side mailbox exchange (knob SYNCBN_IPC; round 5).  Every rank owns ONE mailbox in its HBM
@@ -179,9 +177,12 @@ inline int mbox_next(lgs_comm *c) {
 struct SyncBnLayout {
   int64_t records, sums, total;
   SyncBnLayout(int64_t n, int c, int world) {
-    records = align256(lgs_bn_workspace_bytes(n, c));
-    sums = records + align256((int64_t)(world + 1) * (2 * c + 1) * 4);
-    total = sums + align256(2 * c * 4) + 256;
+    lgs::Layout l;
+    l.take(lgs_bn_workspace_bytes(n, c));
+    records = l.take((int64_t)(world + 1) * (2 * c + 1) * 4);
+    sums = l.take(2 * c * 4);
+    l.take(256);   // slack
+    total = l.total();
   }
 };
 }  // namespace

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/lgs_engine.h"
+#include "lgs_idioms.h"
 
 struct lgs_kmap;
 struct lgs_segmap;
@@ -97,7 +98,6 @@ struct SegMap {
 inline int pad32(int c) { return (c + 31) / 32 * 32; }
 inline int esize(int dtype) { return dtype == LGS_BF16 ? 2 : 4; }
 inline int epl(int dtype) { return dtype == LGS_BF16 ? 8 : 4; }
-inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
 
 #if defined(__HIPCC__)
 using f32x16 = __attribute__((ext_vector_type(16))) float;
@@ -131,9 +131,10 @@ enum WgradPath { kWgEmpty = 0, kWgWide = 1, kWgPs = 2, kWgPairs = 3, kWgF32 = 4 
 int64_t wgrad_workspace_bytes(const lgs_kmap *km, int cin, int cout, int dtype);
 // the next region of a workspace that is laid out front to back
 inline lgs_conv_plan_region take_region(int64_t &used, int64_t bytes) {
-  const lgs_conv_plan_region r = {used, align256(bytes)};
-  used += r.bytes;
-  return r;
+  Layout l{used};
+  const int64_t at = l.take(bytes);
+  used = l.total();
+  return {at, used - at};
 }
 // 1x1 stride-1 convolutions of the big maps as a streaming GEMM (lgs_pointwise.hip)
 bool pointwise_supported(const View &v, int K, int g_real, int o_real, int64_t in_ld);

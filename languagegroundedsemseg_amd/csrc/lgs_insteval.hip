@@ -29,7 +29,7 @@ namespace lgs {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kChunk = 1024;              // members per workgroup of the overlap pass
+constexpr int kChunk = kInstChunk;        // members per workgroup of the overlap pass (1024; the layout counts pieces by it)
 constexpr int kIdPoints = 2048;           // points per workgroup of the id pass
 constexpr int kIdLds = 1024;              // entries of its LDS table
 constexpr int kIdProbes = 8;
@@ -44,39 +44,21 @@ __device__ inline uint32_t hash_id(int64_t g) {
   h ^= h >> 33;
   return (uint32_t)h;
 }
-// order-preserving float -> uint32; any NaN is the top key (torch.max returns NaN once it meets one)
-__device__ inline uint32_t ord_of(float f) {
-  if (f != f) return kNanKey;
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float of_ord(uint32_t o) {
-  if (o == kNanKey) return __uint_as_float(0x7fc00000u);
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
+// ord_key with any NaN as the top key, whatever its sign: torch.max returns NaN once it meets one, so a NaN must win every maximum
+__device__ inline uint32_t ord_of(float f) { return f != f ? kNanKey : ord_key(f); }
+__device__ inline float of_ord(uint32_t o) { return o == kNanKey ? __uint_as_float(0x7fc00000u) : ord_key_inv(o); }
 // g names an instance: g > 0 (a negative id floors to a negative class, and every valid class is >= 1) and g / 1000 is valid
 __device__ inline bool is_instance(int64_t g, const int64_t *__restrict__ valid, int v) {
   if (g <= 0) return false;
   const int64_t cls = g / 1000;
-  int lo = 0, hi = v;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (valid[mid] < cls) lo = mid + 1; else hi = mid;
-  }
+  const int lo = lower_bound(valid, 0, v, cls);
   return lo < v && valid[lo] == cls;
 }
-// add `add` to g's entry of the global table; false = no entry left in T probes
+// add `add` to g's entry of the global table (the key 0 = empty); false = no entry left in T probes
 __device__ inline bool table_add(unsigned long long *__restrict__ t_key, int32_t *__restrict__ t_cnt, uint32_t tmask, int64_t g, int add) {
-  uint32_t h = hash_id(g) & tmask;
-  for (uint32_t probe = 0; probe <= tmask; ++probe) {
-    const unsigned long long prev = atomicCAS(&t_key[h], 0ull, (unsigned long long)g);
-    if (prev == 0ull || prev == (unsigned long long)g) {
-      atomicAdd(&t_cnt[h], add);
-      return true;
-    }
-    h = (h + 1) & tmask;
-  }
-  return false;
+  const int64_t h = table_claim(t_key, hash_id(g) & tmask, tmask, (unsigned long long)g, 0ull, (uint64_t)tmask + 1);
+  if (h >= 0) atomicAdd(&t_cnt[h], add);
+  return h >= 0;
 }
 
 // stage 1
@@ -92,6 +74,7 @@ __global__ __launch_bounds__(kThreads) void k_ie_ids(const int64_t *__restrict__
   for (int64_t i = i0 + threadIdx.x; i < i1; i += kThreads) {
     const int64_t g = gt_ids[i];
     if (!is_instance(g, valid, v)) continue;
+    // table_claim's probe sequence on the LDS table, spelled out: through the helper the kernel measured slower (profiles/device_idioms.md)
     uint32_t h = hash_id(g) & (kIdLds - 1);
     bool placed = false;
 #pragma unroll 1
@@ -148,6 +131,7 @@ __global__ __launch_bounds__(kThreads) void k_ie_overlap(const int32_t *__restri
   if (threadIdx.x == 0) { l_ntouched = 0; l_void = 0; }
   const int64_t j0 = (int64_t)blockIdx.x * kChunk, j1 = j0 + kChunk < m ? j0 + kChunk : m;
   // the proposal of member j0: the first q with offsets[q + 1] > j0 (proposals in front of it that are empty are skipped)
+  // (upper_bound over offsets + 1 and the wave folds below, spelled out: through the helpers the kernel measured slower)
   int q;
   {
     int lo = 0, hi = p;
@@ -265,13 +249,6 @@ __global__ __launch_bounds__(kThreads) void k_ie_conf(const int32_t *__restrict_
   }
 }
 
-uint32_t table_size(int g_cap) {
-  uint32_t t = 2;
-  while (t < 2u * (uint32_t)g_cap) t <<= 1;
-  return t;
-}
-int64_t pieces(int64_t m, int p) { return (m + kChunk - 1) / kChunk + p + 1; }
-
 }  // namespace
 
 }  // namespace lgs
@@ -280,9 +257,7 @@ using namespace lgs;
 
 extern "C" int64_t lgs_inst_overlap_workspace_bytes(int64_t n, int64_t m, int p, int g_cap) {
   if (n < 0 || m < 0 || p < 0 || g_cap < 1 || g_cap > kMaxCap) return -1;
-  const int64_t t = table_size(g_cap);
-  // table keys, table counts / slots, the slot counter, one partial maximum and one partial sum per piece
-  return align256(8 * t) + align256(4 * t) + 256 + align256(4 * pieces(m, p)) + align256(8 * pieces(m, p));
+  return inst_overlap_layout(m, p, g_cap).total;
 }
 
 extern "C" int lgs_inst_overlap(const int32_t *member, const int32_t *offsets, const int32_t *score_col, int p, int64_t m,
@@ -303,14 +278,13 @@ extern "C" int lgs_inst_overlap(const int32_t *member, const int32_t *offsets, c
     LGS_REQUIRE(m == 0 || (scores && c >= 1), "lgs_inst_overlap: score_mode without scores");
   }
   hipStream_t s = (hipStream_t)stream;
-  const uint32_t tsize = table_size(g_cap);
-  char *ws = reinterpret_cast<char *>(workspace);
-  unsigned long long *t_key = reinterpret_cast<unsigned long long *>(ws); ws += align256(8 * (int64_t)tsize);
-  int32_t *t_cnt = reinterpret_cast<int32_t *>(ws); ws += align256(4 * (int64_t)tsize);
-  int32_t *n_slots = reinterpret_cast<int32_t *>(ws); ws += 256;
-  uint32_t *part_max = reinterpret_cast<uint32_t *>(ws); ws += align256(4 * pieces(m, p));
-  double *part_sum = reinterpret_cast<double *>(ws);
-  LGS_HIP(hipMemsetAsync(workspace, 0, (size_t)(align256(8 * (int64_t)tsize) + align256(4 * (int64_t)tsize) + 256), s));
+  const uint32_t tsize = inst_table_size(g_cap);
+  const InstOverlapWs w = inst_overlap_layout(m, p, g_cap);
+  unsigned long long *t_key = Layout::at<unsigned long long>(workspace, w.t_key);
+  int32_t *t_cnt = Layout::at<int32_t>(workspace, w.t_cnt), *n_slots = Layout::at<int32_t>(workspace, w.n_slots);
+  uint32_t *part_max = Layout::at<uint32_t>(workspace, w.part_max);
+  double *part_sum = Layout::at<double>(workspace, w.part_sum);
+  LGS_HIP(hipMemsetAsync(workspace, 0, (size_t)w.zeroed, s));
   LGS_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
   LGS_HIP(hipMemsetAsync(gt_id, 0, sizeof(int64_t) * g_cap, s));
   LGS_HIP(hipMemsetAsync(gt_count, 0, sizeof(int32_t) * g_cap, s));

@@ -1,6 +1,6 @@
 // lgs_keypack.h -- the engine's packed voxel key: a 10-bit batch field above three 18-bit coordinates in Morton order, and the hash
-// of the open-addressing tables keyed by it.  Functions only, no kernels: lgs_mapkeys.h (the coordinate manager) and lgs_paste.hip
-// (the per-instance voxel table of the tail-instance paste) include it.
+// of the open-addressing tables keyed by it (a slot is claimed by table_claim's probe sequence, lgs_idioms.h, from hash64(key) & (cap - 1)).
+// Functions only, no kernels: lgs_mapkeys.h (the coordinate manager) and lgs_paste.hip (the per-instance voxel table) include it.
 #pragma once
 #include "lgs_common.h"
 

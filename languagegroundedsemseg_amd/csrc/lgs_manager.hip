@@ -721,15 +721,13 @@ inline unsigned nblk(int64_t n, int t = 256) { return (unsigned)((n + t - 1) / t
 
 int ensure_hash(lgs_manager *m, CoordMap &cm, hipStream_t s) {
   if (cm.hkeys) return 0;
-  int64_t cap = 1024;
-  while (cap < 2 * cm.n) cap <<= 1;
+  const int64_t cap = table_pow2(1024, 2 * cm.n);
   cm.hcap = cap;
   if (dalloc(m, &cm.hkeys, cap, s)) return 1;
   if (dalloc(m, &cm.hvals, cap, s)) return 1;
   LGS_KLAUNCH(k_hash_fill, nblk(cap), 256, 0, s, cm.hkeys, cap);
   if (cm.n > 0)
-    LGS_KLAUNCH(k_hash_insert, nblk(cm.n), 256, 0, s, cm.skeys, cm.order, cm.n, cm.hkeys, cm.hvals,
-                       (uint64_t)(cap - 1));
+    LGS_KLAUNCH(k_hash_insert, nblk(cm.n), 256, 0, s, cm.skeys, cm.order, cm.n, cm.hkeys, cm.hvals, (uint64_t)(cap - 1), m->d_err);
   LGS_HIP(hipGetLastError());
   return 0;
 }
@@ -740,8 +738,7 @@ int ensure_dir(lgs_manager *m, CoordMap &cm, hipStream_t s) {
   int64_t blocks = cm.n;
   const int lv = cm.log2ts + 2;
   if (lv <= kPreLevels && m->precount[lv - 1] >= 0 && m->precount[lv - 1] < blocks) blocks = m->precount[lv - 1];
-  int64_t cap = 1024;
-  while (cap < 2 * blocks) cap <<= 1;
+  const int64_t cap = table_pow2(1024, 2 * blocks);
   cm.dcap = cap;
   if (dalloc(m, &cm.dir, cap, s)) return 1;
   LGS_KLAUNCH(k_dir_fill, nblk(cap), 256, 0, s, cm.dir, cap);

@@ -1,4 +1,7 @@
-// lgs_mapkeys.h -- the lookup tables over Morton keys (lgs_keypack.h), HashRef / DirRef and the kernels that fill them.  Included by lgs_manager.hip only.
+// lgs_mapkeys.h -- the lookup tables over Morton keys (lgs_keypack.h), HashRef / DirRef and the kernels that fill them: k_hash_insert
+// claims its slots through table_claim (lgs_idioms.h), k_dir_build walks the same bounded probe sequence spelled out; the find() loops
+// are tuned for loads in flight and stay their own.
+// Included by lgs_manager.hip only.
 #pragma once
 #include "lgs_common.h"
 #include "lgs_keypack.h"
@@ -9,18 +12,16 @@ __global__ void k_hash_fill(uint64_t *hkeys, int64_t cap) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < cap) hkeys[i] = kEmpty;
 }
+// one slot per key by table_claim (lgs_idioms.h; the keys are unique, so no slot is found already held).  The table holds at least
+// twice the keys, so the probe sequence ends; a full table (impossible by that sizing) sets d_err bit 3 instead of spinning.
 __global__ void k_hash_insert(const uint64_t *skeys, const int32_t *order, int64_t n, uint64_t *hkeys,
-                              int32_t *hvals, uint64_t capm1) {
+                              int32_t *hvals, uint64_t capm1, int *d_err) {
   int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n) return;
   uint64_t key = skeys[p];
-  uint64_t s = hash64(key) & capm1;
-  for (;;) {
-    unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(hkeys + s), (unsigned long long)kEmpty,
-                                        (unsigned long long)key);
-    if (prev == kEmpty) { hvals[s] = order ? order[p] : (int32_t)p; return; }
-    s = (s + 1) & capm1;  // keys are unique here, no equality case
-  }
+  const int64_t s = table_claim(hkeys, hash64(key) & capm1, capm1, key, kEmpty, capm1 + 1);
+  if (s >= 0) hvals[s] = order ? order[p] : (int32_t)p;
+  else if (d_err) atomicOr(d_err, 8);
 }
 
 // ---- neighbour lookup: "which row of the probed map has this key?" for NP keys at once, all NP loads of a step in flight together
@@ -105,8 +106,9 @@ __global__ void k_dir_fill(DirEnt *dir, int64_t cap) {
   q[1] = make_ulonglong2(0ull, 0ull);
 }
 // one pass: the thread at a block head (the pattern of k_heads) walks its run of at most 64 keys, ORs the occupancy and inserts
-// the entry with k_hash_insert's atomicCAS idiom (block ids are unique among the heads).  The table holds at least twice the
-// block count, so the probe sequence ends; a full table (impossible by that sizing) sets d_err bit 3 instead of spinning.
+// the entry with table_claim's probe sequence, spelled out: the kernel is on the training step's map-build stream, and through the
+// helper (a stride of four words, an equality case that unique block ids never meet) it came out three instructions longer
+// (profiles/device_idioms.md).  The table holds at least twice the block count; a full one sets d_err bit 3 instead of spinning.
 __global__ void k_dir_build(const uint64_t *skeys, int64_t n, int sh, DirEnt *dir, uint64_t capm1, int *d_err) {
   int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n) return;

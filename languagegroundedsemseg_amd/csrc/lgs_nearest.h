@@ -18,7 +18,7 @@
 // Stage B (k_nearest_scan), one workgroup per listed query: the exact scan of the scene's run of sorted keys (the batch index is the
 // top key field, so the run is contiguous), same d2, same tie rule, minimum over the wave and then the workgroup.
 // Every loop is bounded before it starts: rings by the knob, blocks and cells of a ring by its size, bits of an occupancy word by 64,
-// probe sequences as in DirRef::find / HashRef::find (tables at most half full), binary searches by 32 steps, the scan by the run length.
+// probe sequences as in DirRef::find / HashRef::find (tables at most half full), binary searches by their halving, the scan by the run length.
 #pragma once
 #include "lgs_mapkeys.h"
 
@@ -44,14 +44,7 @@ struct SiteQuery {
 };
 struct Best { float d2; int32_t row; };
 
-__device__ inline int nearest_scene_of(const int64_t *__restrict__ off, int b, int64_t i) {
-  int lo = 0, hi = b - 1;
-  for (int it = 0; it < 6 && lo < hi; ++it) {   // b <= 32
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
+__device__ inline int nearest_scene_of(const int64_t *__restrict__ off, int b, int64_t i) { return last_not_above(off, 1, b, i); }
 __device__ inline SiteQuery site_query(const NearestArgs &q, const NearestAffines &A, int64_t i) {
   SiteQuery o;
   o.scene = nearest_scene_of(q.off, q.b, i);
@@ -60,10 +53,7 @@ __device__ inline SiteQuery site_query(const NearestArgs &q, const NearestAffine
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
     double v = r == 0 ? x : (r == 1 ? y : z);
-    if (q.has_affine) {
-      const double *a = A.a[o.scene] + 4 * r;
-      v = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(x, a[0]), __dmul_rn(y, a[1])), __dmul_rn(z, a[2])), a[3]);
-    }
+    if (q.has_affine) v = affine_row(A.a[o.scene] + 4 * r, x, y, z);
     const double p = __dsub_rn(__dmul_rn(v, q.inv_ts), q.anchor);
     o.finite = o.finite && isfinite(p);
     o.h[r] = rint(p);
@@ -234,15 +224,6 @@ __global__ __launch_bounds__(256) void k_nearest_ring(NearestArgs q, NearestAffi
   if (d2) d2[i] = best.d2;
 }
 
-// first position of the sorted keys that is >= key
-__device__ inline int64_t key_lower_bound(const uint64_t *__restrict__ skeys, int64_t n, uint64_t key) {
-  int64_t lo = 0, hi = n;
-  for (int it = 0; it < 32 && lo < hi; ++it) {   // n < 2^31
-    const int64_t mid = (lo + hi) >> 1;
-    if (skeys[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 __global__ __launch_bounds__(256) void k_nearest_scan(NearestArgs q, NearestAffines A, const uint64_t *__restrict__ skeys, const int32_t *__restrict__ order,
                                                       int64_t n, const int32_t *__restrict__ left, const int32_t *__restrict__ n_left,
                                                       int64_t *__restrict__ rows, float *__restrict__ d2) {
@@ -254,8 +235,8 @@ __global__ __launch_bounds__(256) void k_nearest_scan(NearestArgs q, NearestAffi
     const int64_t i = left[it];
     const SiteQuery sq = site_query(q, A, i);
     const int batch = q.batch_base + sq.scene;
-    const int64_t lo = key_lower_bound(skeys, n, (uint64_t)batch << kSceneShift);
-    const int64_t hi = batch + 1 >= 1024 ? n : key_lower_bound(skeys, n, (uint64_t)(batch + 1) << kSceneShift);
+    const int64_t lo = lower_bound(skeys, (int64_t)0, n, (uint64_t)batch << kSceneShift);
+    const int64_t hi = batch + 1 >= 1024 ? n : lower_bound(skeys, (int64_t)0, n, (uint64_t)(batch + 1) << kSceneShift);
     Best best{__builtin_inff(), -1};
     for (int64_t p = lo + threadIdx.x; p < hi; p += 256) {
       int bb, xb, yb, zb;

@@ -40,65 +40,18 @@ struct SlotStats {                              // 64 bytes
   int32_t mx[3], pad;
   unsigned long long sum[3], pad64;             // two's-complement sums of signed coordinates
 };
-static_assert(sizeof(SlotStats) == 64, "one slot's statistics are 64 bytes");
-
-// the regions of the workspace, front to back
-struct PasteWs {
-  int64_t off, bounds, flags, stats, place, hkeys, hmin, hslot, ivox, maps, total;
-  int64_t cap;
-};
-inline int64_t table_cap(int64_t inst_rows) {
-  int64_t cap = 64;
-  while (cap < 2 * inst_rows) cap <<= 1;
-  return cap;
-}
-inline PasteWs paste_layout(int b, int slots, int64_t inst_rows, int64_t max_map_cells) {
-  PasteWs w;
-  int64_t used = 0;
-  auto take = [&](int64_t bytes) { const int64_t at = used; used += align256(bytes); return at; };
-  w.cap = table_cap(inst_rows);
-  w.off = take((int64_t)sizeof(int64_t) * (b + 1));
-  w.bounds = take((int64_t)sizeof(int32_t) * 6 * b);
-  w.flags = take((int64_t)sizeof(int32_t) * kPasteScenes);
-  w.stats = take((int64_t)sizeof(SlotStats) * std::max(slots, 1));
-  w.place = take((int64_t)sizeof(int32_t) * 4 * std::max(slots, 1));
-  w.hkeys = take((int64_t)sizeof(uint64_t) * w.cap);
-  w.hmin = take((int64_t)sizeof(int32_t) * w.cap);
-  w.hslot = take((int64_t)sizeof(int32_t) * std::max<int64_t>(inst_rows, 1));
-  w.ivox = take((int64_t)sizeof(int32_t) * 4 * std::max<int64_t>(inst_rows, 1));
-  w.maps = take((int64_t)sizeof(int32_t) * b * max_map_cells);
-  w.total = used;
-  return w;
-}
+static_assert(sizeof(SlotStats) == kPasteStatsBytes, "paste_layout (lgs_idioms.h) sizes the statistics at 64 bytes per slot");
 
 constexpr int kSlotCols = LGS_PASTE_SLOT_COLS, kSceneCols = LGS_PASTE_SCENE_COLS;
 enum { kSlotBank = 0, kSlotFirst = 1, kSlotOut = 2, kSlotScene = 3, kSlotIndex = 4, kSlotRows = 5 };      // columns of slot_table
 enum { kSceneOut = 0, kSceneBox = 1, kSceneSeed = 2, kSceneFirst = 3 };                                   // columns of scene_table
 
-// the last record t in [0, count) with table[t, col] <= i (records of `cols` int64 each, that column non-decreasing): the slot of an
-// instance row (every slot has at least one row), the scene of a scene row (empty scenes share their start with the next and lose)
-__device__ inline int record_of(const int64_t *__restrict__ table, int cols, int col, int count, int64_t i) {
-  int lo = 0, hi = count - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (table[cols * mid + col] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-__device__ inline int slot_of(const int64_t *__restrict__ slot_table, int slots, int64_t r) {
-  return record_of(slot_table, kSlotCols, kSlotFirst, slots, r);
-}
-__device__ inline int scene_of_row(const int64_t *__restrict__ scene_table, int b, int64_t i) {
-  return record_of(scene_table, kSceneCols, kSceneFirst, b, i);
-}
+// the slot of an instance row (every slot has at least one row), the scene of a scene row
+__device__ inline int slot_of(const int64_t *__restrict__ slot_table, int slots, int64_t r) { return last_not_above(slot_table + kSlotFirst, kSlotCols, slots, r); }
+__device__ inline int scene_of_row(const int64_t *__restrict__ scene_table, int b, int64_t i) { return last_not_above(scene_table + kSceneFirst, kSceneCols, b, i); }
 // the tables are the caller's: a scene id is clamped before it indexes anything
 __device__ inline int slot_scene(const int64_t *__restrict__ slot_table, int slot, int b) {
   return (int)std::min<int64_t>(std::max<int64_t>(slot_table[kSlotCols * slot + kSlotScene], 0), b - 1);
-}
-
-// one row of an affine [3, 4] applied to (x, y, z, 1): ((x a0 + y a1) + z a2) + a3, every operation rounded (k_voxelize_batched)
-__device__ inline int32_t affine_floor(const double *__restrict__ a, double x, double y, double z) {
-  return (int32_t)floor(__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(x, a[0]), __dmul_rn(y, a[1])), __dmul_rn(z, a[2])), a[3]));
 }
 
 // a scene's map: its dimensions from the bounds; false for an empty scene
@@ -189,8 +142,7 @@ __global__ void __launch_bounds__(kPasteBlock) k_paste_voxelize(const float *__r
     const double *a = slot_affines + 12 * slot;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      const double *q = a + 4 * k;
-      const double f = floor(__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(x, q[0]), __dmul_rn(y, q[1])), __dmul_rn(z, q[2])), q[3]));
+      const double f = floor(affine_row(a + 4 * k, x, y, z));
       in_range = in_range && f >= (double)-kBias && f < (double)kBias;      // also NaN
       v[k] = in_range ? (int32_t)f : 0;
     }
@@ -204,19 +156,9 @@ __global__ void __launch_bounds__(kPasteBlock) k_paste_voxelize(const float *__r
     return;
   }
   const uint64_t key = pack_key(slot, v[0] + kBias, v[1] + kBias, v[2] + kBias);
-  uint64_t s = hash64(key) & capm1;
-  int32_t at = -1;
-  for (uint64_t tries = 0; tries <= capm1; ++tries) {        // the table holds at least twice the rows: the probe ends
-    const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(hkeys + s), (unsigned long long)kEmpty,
-                                              (unsigned long long)key);
-    if (prev == kEmpty || prev == key) {
-      atomicMin(hmin + s, (int32_t)r);
-      at = (int32_t)s;
-      break;
-    }
-    s = (s + 1) & capm1;
-  }
-  hslot[r] = at;
+  const int64_t at = table_claim(hkeys, hash64(key) & capm1, capm1, key, kEmpty, capm1 + 1);      // the table holds at least twice the rows
+  if (at >= 0) atomicMin(hmin + at, (int32_t)r);
+  hslot[r] = (int32_t)at;
 }
 
 __global__ void __launch_bounds__(kPasteBlock) k_paste_stats(const int64_t *__restrict__ slot_table, int slots, int64_t inst_rows,
@@ -242,23 +184,13 @@ __global__ void __launch_bounds__(kPasteBlock) k_paste_stats(const int64_t *__re
     const bool mine = first && my_slot == s;
     int32_t mn[3], mx[3];
     long long sm[3];
-    int32_t cnt = mine ? 1 : 0;
+    const int32_t cnt = wave_sum(mine ? 1 : 0);
     const int32_t c[3] = {v.y, v.z, v.w};
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      mn[a] = mine ? c[a] : INT_MAX;
-      mx[a] = mine ? c[a] : INT_MIN;
-      sm[a] = mine ? (long long)c[a] : 0ll;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        mn[a] = std::min(mn[a], __shfl_xor(mn[a], o, 64));
-        mx[a] = std::max(mx[a], __shfl_xor(mx[a], o, 64));
-        sm[a] += __shfl_xor(sm[a], o, 64);
-      }
-      cnt += __shfl_xor(cnt, o, 64);
+      mn[a] = wave_min(mine ? c[a] : INT_MAX);
+      mx[a] = wave_max(mine ? c[a] : INT_MIN);
+      sm[a] = wave_sum(mine ? (long long)c[a] : 0ll);
     }
     if (lane == 0 && cnt > 0) {
       SlotStats *q = stats + s;
@@ -405,7 +337,8 @@ __global__ void __launch_bounds__(kPasteBlock) k_paste_write(const int32_t *__re
   }
   const double *m = scene_xforms + 13 * s + 1;
   const double x = (double)c[0], y = (double)c[1], z = (double)c[2];
-  reinterpret_cast<int4 *>(coords_out)[dst] = make_int4(s, affine_floor(m, x, y, z), affine_floor(m + 4, x, y, z), affine_floor(m + 8, x, y, z));
+  reinterpret_cast<int4 *>(coords_out)[dst] = make_int4(s, (int32_t)floor(affine_row(m, x, y, z)), (int32_t)floor(affine_row(m + 4, x, y, z)),
+                                                        (int32_t)floor(affine_row(m + 8, x, y, z)));
   const float *f = src_scene >= 0 ? feats + 3 * src_scene : bank_colors + 3 * src_bank;
 #pragma unroll
   for (int k = 0; k < 3; ++k) feats_out[3 * dst + k] = f[k];
@@ -452,14 +385,13 @@ int lgs_paste_instances(const int32_t *coords, const float *feats, const int64_t
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   const PasteWs w = paste_layout(b, slots, inst_rows, max_map_cells);
-  char *ws = static_cast<char *>(workspace);
-  int64_t *off = reinterpret_cast<int64_t *>(ws + w.off);
-  int32_t *bounds = reinterpret_cast<int32_t *>(ws + w.bounds), *flags = reinterpret_cast<int32_t *>(ws + w.flags);
-  SlotStats *stats = reinterpret_cast<SlotStats *>(ws + w.stats);
-  int32_t *place = reinterpret_cast<int32_t *>(ws + w.place);
-  uint64_t *hkeys = reinterpret_cast<uint64_t *>(ws + w.hkeys);
-  int32_t *hmin = reinterpret_cast<int32_t *>(ws + w.hmin), *hslot = reinterpret_cast<int32_t *>(ws + w.hslot);
-  int32_t *ivox = reinterpret_cast<int32_t *>(ws + w.ivox), *maps = reinterpret_cast<int32_t *>(ws + w.maps);
+  int64_t *off = Layout::at<int64_t>(workspace, w.off);
+  int32_t *bounds = Layout::at<int32_t>(workspace, w.bounds), *flags = Layout::at<int32_t>(workspace, w.flags);
+  SlotStats *stats = Layout::at<SlotStats>(workspace, w.stats);
+  int32_t *place = Layout::at<int32_t>(workspace, w.place);
+  uint64_t *hkeys = Layout::at<uint64_t>(workspace, w.hkeys);
+  int32_t *hmin = Layout::at<int32_t>(workspace, w.hmin), *hslot = Layout::at<int32_t>(workspace, w.hslot);
+  int32_t *ivox = Layout::at<int32_t>(workspace, w.ivox), *maps = Layout::at<int32_t>(workspace, w.maps);
   const int64_t init_n = slots ? std::max<int64_t>(w.cap, kPasteScenes) : kPasteScenes;
   LGS_KLAUNCH(k_paste_init, paste_blocks(init_n), kPasteBlock, 0, s, hkeys, hmin, slots ? w.cap : 0, stats, slots, flags);
   if (slots) {

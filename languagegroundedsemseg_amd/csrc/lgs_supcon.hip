@@ -62,12 +62,7 @@ __global__ void __launch_bounds__(256) k_supcon_sample(const int64_t *__restrict
       return;
     }
     const int64_t x = below(r0, total);
-    int lo = 0, hi = n_labels - 1;     // the first class whose cumulative weight exceeds x; cum[hi] = total > x
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (row_cum[mid] > x) hi = mid; else lo = mid + 1;
-    }
-    cls = lo;
+    cls = upper_bound(row_cum, 0, n_labels - 1, x);     // the first class whose cumulative weight exceeds x; cum[n_labels - 1] = total > x
     members = elig_count[cls];
   }
   if (members <= 0) {       // (cannot happen with tables built from these labels)
@@ -110,12 +105,6 @@ template <> struct SupRow<bf16_t, false> {
   __device__ static void load(const bf16_t *p, float (&v)[1]) { v[0] = bf16_to_f32(*p); }
   __device__ static void store(bf16_t *p, const float (&v)[1]) { *p = f32_to_bf16(v[0]); }
 };
-
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // sample index of slot j of `row` (positives first), -1 for "no sample"; anything outside [0, n) is no sample
 __device__ inline int64_t slot_index(const int64_t *pos_idx, int p, const int64_t *neg_idx, int k, int64_t row, int j, int64_t n) {

@@ -32,9 +32,7 @@ __global__ void k_voxelize(const float *__restrict__ pts, int64_t n, Affine A, i
   int32_t o[3];
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    const double *a = A.a + 4 * r;
-    const double v = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(x, a[0]), __dmul_rn(y, a[1])), __dmul_rn(z, a[2])), a[3]);
-    o[r] = (int32_t)floor(v);
+    o[r] = (int32_t)floor(affine_row(A.a + 4 * r, x, y, z));
   }
   reinterpret_cast<int4 *>(coords)[i] = make_int4(batch, o[0], o[1], o[2]);
 }
