@@ -25,45 +25,15 @@ import numpy as np
 import torch
 
 from . import engine
+from .hipcall import host_offsets, i32, i64, on_device, ptr, raw_stream, require_hip, scratch
 
 MAX_SCENES = engine.LGS_AUG_MAX_SCENES
 DEFAULT_MAX_CELLS = 1 << 16           # 43 x 40 x 16 = 27 520 cells for an 8 m room at granularity 0.2
 
 
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else None)
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _i32(v):
-    """the low 32 bits of an integer as a C int32"""
-    v = int(v) & 0xffffffff
-    return v - (1 << 32) if v >= (1 << 31) else v
-
-
-def _i64(v):
-    v = int(v) & 0xffffffffffffffff
-    return v - (1 << 64) if v >= (1 << 63) else v
-
-
-def _require_hip(t, what):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda):
-        raise RuntimeError("languagegroundedsemseg_amd.augment runs on the MI355X engine: %s must be a HIP tensor" % what)
-
-
 def _upload(array, device):
     """host array -> device without a synchronising copy (pinned staging buffer, asynchronous copy)"""
     return torch.from_numpy(np.ascontiguousarray(array)).pin_memory().to(device, non_blocking=True)
-
-
-def _host_offsets(scene_offsets, n):
-    off = [int(v) for v in (scene_offsets.tolist() if hasattr(scene_offsets, "tolist") else scene_offsets)]
-    if len(off) < 2 or off[0] != 0 or off[-1] != n or any(a > b for a, b in zip(off, off[1:])):
-        raise ValueError("scene_offsets must be B + 1 non-decreasing integers from 0 to the number of rows (%d): %r" % (n, off[:8]))
-    return off
 
 
 def _chunks(off):
@@ -76,12 +46,12 @@ def aug_bounds(table, scene_offsets=None, batch_size=None):
     """Per-scene min / max of three columns -> (bounds [B, 6] on the device, device scene offsets [B + 1]).
     float32 [N, 3] with `scene_offsets` (a device int64 tensor, B <= 32), or int32 [N, 4] coordinates with `batch_size`: the scene
     id is column 0 and the offsets are derived from it on the device."""
-    _require_hip(table, "table")
+    require_hip(table, "table")
     t = table.contiguous()
     dev = t.device
-    with torch.cuda.device(dev):
+    with on_device(dev):
         if t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 3:
-            _require_hip(scene_offsets, "scene_offsets (device form)")
+            require_hip(scene_offsets, "scene_offsets (device form)")
             b, form, off = scene_offsets.shape[0] - 1, engine.LGS_AUG_F32X3, scene_offsets
         elif t.dtype == torch.int32 and t.dim() == 2 and t.shape[1] == 4:
             b, form = int(batch_size), engine.LGS_AUG_I32X4
@@ -89,7 +59,7 @@ def aug_bounds(table, scene_offsets=None, batch_size=None):
         else:
             raise ValueError("aug_bounds takes float32 [N, 3] or int32 [N, 4]")
         bounds = torch.empty((b, 6), dtype=t.dtype, device=dev)
-        engine.check(engine.lib().lgs_aug_bounds(_vp(t), t.shape[0], form, _vp(off), b, _vp(bounds), _stream(dev)))
+        engine.check(engine.lib().lgs_aug_bounds(ptr(t), t.shape[0], form, ptr(off), b, ptr(bounds), raw_stream()))
     return bounds, off
 
 
@@ -101,8 +71,8 @@ def aug_status(status):
         status = [status]
     for chunk, word in enumerate(status):
         f = ctypes.c_int(0)
-        with torch.cuda.device(word.device):
-            engine.check(engine.lib().lgs_aug_status(_vp(word), ctypes.byref(f), _stream(word.device)))
+        with on_device(word.device):
+            engine.check(engine.lib().lgs_aug_status(ptr(word), ctypes.byref(f), raw_stream()))
         out += [chunk * MAX_SCENES + s for s in range(MAX_SCENES) if (f.value >> s) & 1]
     return out
 
@@ -125,12 +95,11 @@ def _elastic_stage(points, off_dev, b, bounds_in, granularity, magnitude, seed, 
     dev = points.device
     L = engine.lib()
     bounds_out = torch.empty((b, 6), dtype=torch.float32, device=dev)
-    seeds = (ctypes.c_int32 * b)(*[_i32(v) for v in scene_seeds])
-    mask = sum(1 << s for s in range(b) if apply[s])
-    mask = mask - (1 << 32) if mask >= (1 << 31) else mask
-    engine.check(L.lgs_elastic_distort(_vp(points), points.shape[0], _vp(off_dev), b, _vp(bounds_in), float(granularity), float(magnitude),
-                                       _i64(seed), seeds, mask, int(stage), _vp(noise_dev),
-                                       int(max_cells), _vp(workspace), _vp(bounds_out), _vp(status), _stream(dev)))
+    seeds = (ctypes.c_int32 * b)(*[i32(v) for v in scene_seeds])
+    mask = i32(sum(1 << s for s in range(b) if apply[s]))
+    engine.check(L.lgs_elastic_distort(ptr(points), points.shape[0], ptr(off_dev), b, ptr(bounds_in), float(granularity), float(magnitude),
+                                       i64(seed), seeds, mask, int(stage), ptr(noise_dev), int(max_cells), ptr(workspace), ptr(bounds_out),
+                                       ptr(status), raw_stream()))
     return bounds_out
 
 
@@ -147,16 +116,16 @@ def elastic_distortion(points, scene_offsets, granularity, magnitude, seed, nois
     noise: None (Philox, keyed by seed / scene_seeds / stage) or one array per scene, [dx, dy, dz, 3] in C order (teacher-forced).
     A scene whose noise grid has more than max_cells cells is left as it is; aug_status(state["status"]) names such scenes.
     return_state: also return {"status", "bounds", "noise", "field"} (device tensors, per chunk of 32 scenes)."""
-    _require_hip(points, "points")
+    require_hip(points, "points")
     pts = points.detach().to(torch.float32).contiguous().clone()
     assert pts.dim() == 2 and pts.shape[1] == 3
-    off = _host_offsets(scene_offsets, pts.shape[0])
+    off = host_offsets(scene_offsets, pts.shape[0])
     B = len(off) - 1
     scene_seeds = [0] * B if scene_seeds is None else list(scene_seeds)
     apply = [True] * B if apply is None else list(apply)
     dev = pts.device
     state = {"status": [], "bounds": [], "noise": [], "field": []}
-    with torch.cuda.device(dev):
+    with on_device(dev):
         for s0, s1 in _chunks(off):
             b = s1 - s0
             rows = pts[off[s0]:off[s1]]
@@ -178,16 +147,16 @@ def elastic_distortion(points, scene_offsets, granularity, magnitude, seed, nois
 def voxelize_batched(points, scene_offsets, matrices, batch_base=0, offsets_dev=None):
     """ME.utils.voxelize with one rigid matrix per scene: points [N, 3] -> int32 [N, 4] = (scene, floor(M_s (x, y, z, 1))).
     matrices: [B, 4, 4] or [B, 3, 4] (host).  More than 32 scenes are split into several launches."""
-    _require_hip(points, "points")
+    require_hip(points, "points")
     pts = points.detach().to(torch.float32).contiguous()
     assert pts.dim() == 2 and pts.shape[1] == 3
-    off = _host_offsets(scene_offsets, pts.shape[0])
+    off = host_offsets(scene_offsets, pts.shape[0])
     B = len(off) - 1
     m = np.asarray(matrices, dtype=np.float64)
     assert m.shape[0] == B and m.shape[1] in (3, 4) and m.shape[2] == 4
     dev = pts.device
     out = torch.empty((pts.shape[0], 4), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
+    with on_device(dev):
         for s0, s1 in _chunks(off):
             b = s1 - s0
             rows, dst = pts[off[s0]:off[s1]], out[off[s0]:off[s1]]
@@ -197,8 +166,7 @@ def voxelize_batched(points, scene_offsets, matrices, batch_base=0, offsets_dev=
                 off_dev = _upload(np.asarray(off[s0:s1 + 1], np.int64) - off[s0], dev)
             a = np.ascontiguousarray(m[s0:s1, :3, :4]).reshape(-1)
             a12 = (ctypes.c_double * (12 * b))(*a.tolist())
-            engine.check(engine.lib().lgs_voxelize_batched(_vp(rows), rows.shape[0], _vp(off_dev), b, a12, int(batch_base) + s0, _vp(dst),
-                                                           _stream(dev)))
+            engine.check(engine.lib().lgs_voxelize_batched(ptr(rows), rows.shape[0], ptr(off_dev), b, a12, int(batch_base) + s0, ptr(dst), raw_stream()))
     return out
 
 
@@ -215,17 +183,16 @@ def horizontal_flip(coords, flip_axes, shift=None, batch_size=None, return_offse
     """RandomHorizontalFlip's coordinate step on int32 [n, 4] batch-tagged coordinates -> new coordinates.
     flip_axes: per scene a bit mask (bit a = axis a) or [B, 3] booleans; a flipped axis becomes max - c, the max over the scene's
     rows.  shift: three integers added to every scene afterwards (the trainer's per-batch coordinate shift)."""
-    _require_hip(coords, "coords")
+    require_hip(coords, "coords")
     assert coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 4
     c = coords.contiguous().clone()
     b = int(batch_size) if batch_size is not None else len(np.asarray(flip_axes))
     if b > MAX_SCENES:
         raise ValueError("horizontal_flip takes at most %d scenes per call" % MAX_SCENES)
-    with torch.cuda.device(c.device):
+    with on_device(c.device):
         bounds, off = aug_bounds(c, batch_size=b)
         sh = None if shift is None else (ctypes.c_int32 * 3)(*[int(v) for v in shift])
-        engine.check(engine.lib().lgs_coords_flip_shift(_vp(c), c.shape[0], _vp(off), b, _vp(bounds), _flip_words(flip_axes, b), sh,
-                                                        _stream(c.device)))
+        engine.check(engine.lib().lgs_coords_flip_shift(ptr(c), c.shape[0], ptr(off), b, ptr(bounds), _flip_words(flip_axes, b), sh, raw_stream()))
     return (c, off) if return_offsets else c       # off: the voxel rows' scene offsets, derived on the device from column 0
 
 
@@ -243,7 +210,7 @@ def chromatic_augment(colors, scene_offsets, scenes, scale=1.0, normalize=False,
     -> new colours.  scene_offsets: B + 1 host integers, or a device int64 tensor (e.g. the one aug_bounds derives from coordinates).
     scenes: one ColorParams per scene.  noise: device float32 [n, 3] standard normals for the jitter (teacher-forced) or None (Philox).
     A channel whose min equals its max over the scene is left unblended by the autocontrast (the reference yields inf / NaN)."""
-    _require_hip(colors, "colors")
+    require_hip(colors, "colors")
     f = colors.detach().to(torch.float32).contiguous().clone()
     assert f.dim() == 2 and f.shape[1] == 3
     dev = f.device
@@ -264,32 +231,31 @@ def chromatic_augment(colors, scene_offsets, scenes, scale=1.0, normalize=False,
             flags |= engine.LGS_COLOR_JITTER
             rec[s].jitter_std = float(p.jitter_std)
         rec[s].flags = flags
-        rec[s].seed = _i32(p.seed)
-    with torch.cuda.device(dev):
+        rec[s].seed = i32(p.seed)
+    with on_device(dev):
         if isinstance(scene_offsets, torch.Tensor) and scene_offsets.is_cuda:
             off_dev = scene_offsets
         else:
-            off_dev = _upload(np.asarray(_host_offsets(scene_offsets, f.shape[0]), np.int64), dev)
+            off_dev = _upload(np.asarray(host_offsets(scene_offsets, f.shape[0]), np.int64), dev)
         assert off_dev.shape[0] == b + 1
         bounds, _ = aug_bounds(f, off_dev)
         nz = None
         if noise is not None:
-            _require_hip(noise, "noise")
+            require_hip(noise, "noise")
             nz = noise.to(torch.float32).contiguous()
             assert nz.shape == f.shape
-        engine.check(engine.lib().lgs_color_augment(_vp(f), f.shape[0], _vp(off_dev), b, _vp(bounds), rec, float(scale), int(bool(normalize)),
-                                                    _i64(seed), _vp(nz), _stream(dev)))
+        engine.check(engine.lib().lgs_color_augment(ptr(f), f.shape[0], ptr(off_dev), b, ptr(bounds), rec, float(scale), int(bool(normalize)),
+                                                    i64(seed), ptr(nz), raw_stream()))
     return f
 
 
 def philox_words(counters, key):
     """Philox-4x32-10 blocks of the device generator: counters uint32-valued [n, 4] (device int32) -> int32 [n, 4] words (tests)"""
-    _require_hip(counters, "counters")
+    require_hip(counters, "counters")
     c = counters.to(torch.int32).contiguous()
     out = torch.empty_like(c)
-    with torch.cuda.device(c.device):
-        engine.check(engine.lib().lgs_debug_philox(_vp(c), c.shape[0], _i64(key), _vp(out),
-                                                   _stream(c.device)))
+    with on_device(c.device):
+        engine.check(engine.lib().lgs_debug_philox(ptr(c), c.shape[0], i64(key), ptr(out), raw_stream()))
     return out
 
 
@@ -353,7 +319,7 @@ class InstanceBank:
 
     def __init__(self, points, colors, labels, offsets, categories):
         for t, what in ((points, "bank points"), (colors, "bank colors"), (labels, "bank labels")):
-            _require_hip(t, what)
+            require_hip(t, what)
         self.points = points.detach().to(torch.float32).contiguous()
         self.colors = colors.detach().to(torch.float32).contiguous()
         self.labels = labels.detach().to(torch.int64).contiguous()
@@ -432,7 +398,7 @@ def paste_instances(coords, feats, labels, scene_offsets, scene_boxes, plan, sca
     instance rows are copies of the scene's first row, which the dedup drops.
     return_state: also {"placement": device int32 [S, 4] = (winning trial, centroid), "slots": [(scene, k)]}."""
     for t, what in ((coords, "coords"), (feats, "feats"), (labels, "labels")):
-        _require_hip(t, what)
+        require_hip(t, what)
     assert coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 4
     dev = coords.device
     c = coords.contiguous()
@@ -440,12 +406,12 @@ def paste_instances(coords, feats, labels, scene_offsets, scene_boxes, plan, sca
     lab = labels.detach().to(torch.int64).contiguous()
     n = c.shape[0]
     assert f.shape == (n, 3) and lab.shape == (n,)
-    off = _host_offsets(scene_offsets, n)
+    off = host_offsets(scene_offsets, n)
     B = len(off) - 1
     if not 1 <= B <= MAX_SCENES:
         raise ValueError("paste_instances takes 1 .. %d scenes per call" % MAX_SCENES)
     bank = plan.bank
-    _require_hip(bank.points, "the bank")
+    require_hip(bank.points, "the bank")
     inst = np.asarray(plan.instances, np.int64).reshape(B, -1)
     K, T = inst.shape[1], int(plan.max_iterations)
     if ((inst >= len(bank.categories)) | (inst < -1)).any():
@@ -488,23 +454,23 @@ def paste_instances(coords, feats, labels, scene_offsets, scene_boxes, plan, sca
         td = np.asarray(trial_draws).reshape(B, K, T, 2)
         draws = np.stack([td[s, k] for s, k in slots]).astype(np.int32)
     L = engine.lib()
-    with torch.cuda.device(dev):
+    with on_device(dev):
         tables = _upload(np.concatenate(parts), dev)
-        ptr = [ctypes.c_void_p(tables.data_ptr() + 8 * int(a)) for a in starts[:5]]
+        tab = [tables.data_ptr() + 8 * int(a) for a in starts[:5]]
         draws_dev = None if draws is None else _upload(draws, dev)
         nbytes = int(L.lgs_paste_workspace_bytes(B, S, inst_rows, int(plan.max_map_cells)))
         if nbytes <= 0:
             raise ValueError("paste_instances: bad shape (max_map_cells must be 1 .. 2^26)")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = scratch(nbytes, dev)          # (lgs_paste_instances initialises what it reads of it and is done with it at the next call)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
         coords_out = torch.empty((n + inst_rows, 4), dtype=torch.int32, device=dev)
         feats_out = torch.empty((n + inst_rows, 3), dtype=torch.float32, device=dev)
         labels_out = torch.empty(n + inst_rows, dtype=torch.int64, device=dev)
         placement = torch.empty((S, 4), dtype=torch.int32, device=dev)
-        engine.check(L.lgs_paste_instances(_vp(c), _vp(f), _vp(lab), n, B, _vp(bank.points), _vp(bank.colors), _vp(bank.labels),
-                                           bank.points.shape[0], ptr[0], ptr[1], S, inst_rows, ptr[2], ptr[3], ptr[4], n_boxes,
-                                           _vp(draws_dev), T, _i64(plan.seed), int(plan.max_map_cells), _vp(ws), _vp(coords_out),
-                                           _vp(feats_out), _vp(labels_out), _vp(placement), _vp(status), _stream(dev)))
+        engine.check(L.lgs_paste_instances(ptr(c), ptr(f), ptr(lab), n, B, ptr(bank.points), ptr(bank.colors), ptr(bank.labels), bank.points.shape[0],
+                                           tab[0], tab[1], S, inst_rows, tab[2], tab[3], tab[4], n_boxes, ptr(draws_dev), T, i64(plan.seed),
+                                           int(plan.max_map_cells), ptr(ws), ptr(coords_out), ptr(feats_out), ptr(labels_out), ptr(placement),
+                                           ptr(status), raw_stream()))
     out = (coords_out, feats_out, labels_out, offsets_out, status)
     return out + ({"placement": placement, "slots": slots},) if return_state else out
 
@@ -603,9 +569,9 @@ class DeviceAugmentation:
         With tail_instances: scene_boxes (per scene a host [m_s, 2, 3] array of the scene's instance boxes, world units) and
         optionally trial_draws, as paste_instances takes them; the voxeliser then applies M_v only and the paste rotates."""
         for t, what in ((points, "points"), (colors, "colors"), (labels, "labels")):
-            _require_hip(t, what)
+            require_hip(t, what)
         dev = points.device
-        off = _host_offsets(scene_offsets, points.shape[0])
+        off = host_offsets(scene_offsets, points.shape[0])
         B = len(off) - 1
         if B > MAX_SCENES:
             raise ValueError("DeviceAugmentation takes at most %d scenes per batch" % MAX_SCENES)
@@ -617,7 +583,7 @@ class DeviceAugmentation:
         previous = torch.cuda.get_sync_debug_mode()
         torch.cuda.set_sync_debug_mode("error")        # nothing before the dedup's own row count may synchronise
         try:
-            with torch.cuda.device(dev):
+            with on_device(dev):
                 pts = points.detach().to(torch.float32).contiguous().clone()
                 off_dev = _upload(np.asarray(off, np.int64), dev)
                 if self.elastic_params and plan.elastic.any():

@@ -11,8 +11,13 @@ large flat fp32 buckets (param.grad are views into them, so there is no copy-in/
 all-reduced asynchronously on RCCL's stream the moment its last gradient has been accumulated, i.e.
 overlapped with the rest of backward; finalize() waits once before the optimiser step.
 """
+import ctypes
+
 import torch
 import torch.distributed as dist
+
+from . import engine, tuning as _tuning
+from .hipcall import device_index, on_device, ptr, raw_stream
 
 _TIMING = {"on": False}
 _SYNCBN_EVENTS = []      # (start, end) HIP events around SyncBN collectives while BucketedDDP.enable_timing() is active
@@ -329,17 +334,13 @@ class FlatSGD:
                         st["mask"][off:off + p.numel()] = 0.0
             ne = b["grad_elems"]          # the "used" flags and the padding behind the gradients are not parameters
             if fused:   # one kernel per bucket (lgs_sgd_step) instead of four elementwise passes
-                import ctypes
-                from . import engine
                 first = st["buf"] is None
                 if first and self.momentum != 0:
                     st["buf"] = torch.zeros_like(g)
-                vp = ctypes.c_void_p
-                with torch.cuda.device(g.device):
+                with on_device(g.device):
                     engine.check(engine.lib().lgs_sgd_step(
-                        vp(st["p"].data_ptr()), vp(g.data_ptr()), vp(st["buf"].data_ptr()) if st["buf"] is not None else vp(None),
-                        vp(st["mask"].data_ptr()) if unused else vp(None), int(ne), float(self.lr), float(self.momentum),
-                        float(self.dampening), float(self.weight_decay), int(first), vp(torch.cuda.current_stream(g.device).cuda_stream)))
+                        ptr(st["p"]), ptr(g), ptr(st["buf"]), ptr(st["mask"]) if unused else None, int(ne), float(self.lr),
+                        float(self.momentum), float(self.dampening), float(self.weight_decay), int(first), raw_stream()))
                 continue
             d = g.add(st["p"], alpha=self.weight_decay) if self.weight_decay != 0 else g.clone()
             d[ne:] = 0.0
@@ -418,8 +419,6 @@ class EngineComm:
     _by_group = {}
 
     def __init__(self, group, device, ipc=False):
-        import ctypes
-        from . import engine
         world, rank = dist.get_world_size(group), dist.get_rank(group)
         self.h, self.world, self.rank, self._L = None, world, rank, None
         self.ipc = ipc
@@ -439,8 +438,7 @@ class EngineComm:
         if err is None and len(box[0]) == 128:
             try:
                 h = ctypes.c_void_p(None)
-                idx = device.index if device.index is not None else torch.cuda.current_device()
-                engine.check(L.lgs_comm_create(ctypes.create_string_buffer(box[0], 128), world, rank, idx, ctypes.byref(h)))
+                engine.check(L.lgs_comm_create(ctypes.create_string_buffer(box[0], 128), world, rank, device_index(device), ctypes.byref(h)))
                 self.h = h
             except Exception as e:
                 err = e
@@ -457,14 +455,11 @@ class EngineComm:
         """mailbox mode (knob SYNCBN_IPC, csrc/lgs_comm.hip): every rank allocates its mailbox, the 64-byte IPC handles go round in
         ONE all-gather over the torch group (any backend), every rank maps the others'.  Failure anywhere is agreed on collectively,
         as for the RCCL communicator."""
-        import ctypes
-        from . import engine
         err, mine = None, bytes(64)
         try:
             L = self._L = engine.lib()
             h, buf = ctypes.c_void_p(None), ctypes.create_string_buffer(64)
-            idx = device.index if device.index is not None else torch.cuda.current_device()
-            engine.check(L.lgs_comm_create_ipc(world, rank, idx, ctypes.byref(h), buf))
+            engine.check(L.lgs_comm_create_ipc(world, rank, device_index(device), ctypes.byref(h), buf))
             self.h, mine = h, bytes(buf.raw)
         except Exception as e:
             err = e
@@ -492,7 +487,6 @@ class EngineComm:
     @classmethod
     def get(cls, group, device):
         """-> EngineComm of this group, or None (off by knob, not an RCCL group, or some rank could not create it: said once)"""
-        from . import tuning as _tuning
         g = group if group is not None else dist.group.WORLD
         key = (g, device.index)                    # the group OBJECT (kept alive by the key): id() of a freed group can be reused
         if key in cls._by_group:
@@ -532,7 +526,6 @@ def syncbn_collective_group(group):
     stream.  A caller-supplied subgroup is used as it is (dist.new_group would need the ranks outside it to take part)."""
     if group is not None:
         return group
-    from . import tuning as _tuning
     knob = _tuning.host("SYNCBN_OWN_GROUP")
     if knob == 0:
         return group

@@ -12,59 +12,14 @@ import weakref
 import torch
 
 from .. import engine
+from ..hipcall import (device_index, dtype_code as _dtype_code, on_device as _dev, ptr as _ptr, raw_stream as _stream,
+                       require_hip as _require_dev, scratch as _ws)
 from .kernel import ALL_CONV_RELATIONS
 from .. import tuning as _tuning
 from . import host as _host
 from .host import AffineSink, WeightSink, memo, param_event, row_stride, rows_in_place
 
 _vp = ctypes.c_void_p
-
-
-def _stream():
-    """raw handle of torch's current HIP stream on the current device (one C call: torch.cuda.current_stream() builds a
-    Stream object and resolves the device twice, ~14 us of host time per engine call)"""
-    return torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice())
-
-
-class _NoGuard:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
-_NOGUARD = _NoGuard()
-
-
-def _dev(device):
-    """device guard that only switches when the tensor's device is not the current one (the usual case: one process per GPU)"""
-    if device.index is None or device.index == torch._C._cuda_getDevice():
-        return _NOGUARD
-    return torch.cuda.device(device)
-
-
-def _ptr(t):
-    """device address as a plain int (None = NULL): every engine entry point has its argtypes declared (engine.py, checked against
-    the header by tests/test_abi.py), so ctypes converts -- building a c_void_p object per argument cost ~1 ms of host time per
-    step (2500 pointer arguments)"""
-    return t.data_ptr() if t is not None else None
-
-
-def _dtype_code(t):
-    if t.dtype == torch.float32:
-        return engine.LGS_F32
-    if t.dtype == torch.bfloat16:
-        return engine.LGS_BF16
-    raise RuntimeError("lgs_engine supports float32 and bfloat16 features, got %s" % t.dtype)
-
-
-def _require_dev(t, what):
-    if not t.is_cuda:
-        raise RuntimeError("%s must live on a HIP device (got %s): the MI355X engine has no CPU fallback"
-                           % (what, t.device))
-
-
 _PACKED = None
 
 
@@ -75,7 +30,6 @@ def get_packed():
     return _PACKED
 
 
-_WS = {}
 _QUERIES = {}     # host.memo of the engine queries that belong to no map
 
 
@@ -100,30 +54,6 @@ def _bn_pair_plan(L, direction, n, c, dt):
 _WGRAD_INLINE_BELOW = _tuning.host("WGRAD_INLINE_BELOW")
 
 
-def _ws(nbytes, device, stream=None):
-    """Scratch of one engine call: ONE grow-only buffer per (device, current stream).  Every use is confined to the launches
-    of a single call, and calls on one stream run in order, so the next call may overwrite it; weight gradients on the side
-    stream get their own.  (A fresh torch.empty per call cost ~7 us of allocator time, ~250 times per step.)"""
-    if stream is None:
-        raw_stream = torch._C._cuda_getCurrentRawStream(device.index if device.index is not None else torch._C._cuda_getDevice())
-    else:
-        raw_stream = stream.cuda_stream
-    key = (device.index, raw_stream)
-    t = _WS.get(key)
-    nbytes = int(nbytes)
-    if t is None or t.numel() < nbytes:
-        size = max(nbytes + nbytes // 4, 1 << 20)
-        if stream is None:
-            t = torch.empty(size, dtype=torch.uint8, device=device)
-        else:
-            # the buffer must belong to the allocator pool of the stream that uses it: when it is replaced by a larger one, the
-            # old block may only be handed out again in that stream's order
-            with torch.cuda.stream(stream):
-                t = torch.empty(size, dtype=torch.uint8, device=device)
-        _WS[key] = t
-    return t
-
-
 def _raw_event(ev, stream):
     """hipEvent_t of a torch event for the engine to record; torch creates the handle at the first record"""
     h = ev.cuda_event
@@ -131,6 +61,43 @@ def _raw_event(ev, stream):
         ev.record(stream)
         h = ev.cuda_event
     return int(h.value if hasattr(h, "value") else h)
+
+
+# ---- operands the wrappers below prepare the same way
+def _int64(t):          # an index operand (labels, sample indices, tables) as the kernels read it
+    return t.contiguous().to(torch.int64)
+
+
+def _grad32(g):         # an optional upstream gradient as the kernels read it; None stays None
+    return g.contiguous().float() if g is not None else None
+
+
+def _contiguous(t):     # an optional operand (a norm's residual); None stays None
+    return t.contiguous() if t is not None else None
+
+
+def _dy_rows(dy, dtype, c):
+    """-> (dy, row stride or 0) of a norm backward's gradient: a column slice of a wider row-major tensor (the gradient of one ME.cat
+    input) is read in place when it has the features' dtype, anything else is copied.  0 means c; a caller says so itself where it has to."""
+    return rows_in_place(dy, c) if dy.dtype == dtype else (dy.contiguous(), 0)
+
+
+def _partial_rows(n):   # per-workgroup partial rows of lgs_ce_weight_sum / lgs_split_stats: one per 2048 rows, 1 .. 1024
+    return max(1, min(1024, (n + 2047) // 2048))
+
+
+def _empty_batch(x):    # what nn.BatchNorm1d (= MinkowskiBatchNorm's `.bn`) says about batch statistics of nothing
+    return ValueError("Expected more than 1 value per channel when training, got input size %s" % (list(x.shape),))
+
+
+def _sized_then_filled(call, allocate):
+    """the engine's two-phase exports: call(None, None, None) answers the sizes into the caller's out-parameters, allocate() makes the
+    buffers from them -> (buffers, whether there is anything to fill), call(addresses) fills them -> the buffers"""
+    call(None, None, None)
+    bufs, fill = allocate()
+    if fill:
+        call(*[_ptr(b) for b in bufs])
+    return bufs
 
 
 _DESC_FIELDS = [f for f, _ in engine.PackDesc._fields_]
@@ -268,29 +235,28 @@ class HipKernelMap:
     def export(self):
         L = engine.lib()
         m = ctypes.c_int64(0)
+
+        def allocate():
+            k = torch.empty(m.value, dtype=torch.int32, device=self.mgr.device)
+            return (k, torch.empty_like(k), torch.empty_like(k)), m.value
+
         with _dev(self.mgr.device):
-            engine.check(L.lgs_kmap_export(self.h, None, None, None, _stream(), ctypes.byref(m)))
-            n = m.value
-            k = torch.empty(n, dtype=torch.int32, device=self.mgr.device)
-            i = torch.empty_like(k)
-            o = torch.empty_like(k)
-            if n:
-                engine.check(L.lgs_kmap_export(self.h, _ptr(k), _ptr(i), _ptr(o), _stream(), ctypes.byref(m)))
-        return k, i, o
+            return _sized_then_filled(lambda k, i, o: engine.check(L.lgs_kmap_export(self.h, k, i, o, _stream(), ctypes.byref(m))), allocate)
 
     def tables(self, bwd=False):
         """-> (nbr [slots, n_pad], out_row [n_pad], mask64 [n_pad / 64]) of one view as the kernels read them (int32 copies; None
         where the view has no such table): lgs_debug_kmap_tables, for tests that compare two build paths exactly"""
         L = engine.lib()
         n_pad, slots, present = ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int(0)
-        with _dev(self.mgr.device):
-            engine.check(L.lgs_debug_kmap_tables(self.h, int(bwd), None, None, None, _stream(), ctypes.byref(n_pad), ctypes.byref(slots), ctypes.byref(present)))
+
+        def allocate():
             n, has = n_pad.value, present.value
             mk = lambda bit, *shape: torch.empty(*shape, dtype=torch.int32, device=self.mgr.device) if has & bit else None
-            nbr, orow, mask = mk(1, slots.value, n), mk(2, n), mk(4, n // 64)
-            engine.check(L.lgs_debug_kmap_tables(self.h, int(bwd), _ptr(nbr) if nbr is not None else None, _ptr(orow) if orow is not None else None,
-                                                 _ptr(mask) if mask is not None else None, _stream(), ctypes.byref(n_pad), ctypes.byref(slots), ctypes.byref(present)))
-        return nbr, orow, mask
+            return (mk(1, slots.value, n), mk(2, n), mk(4, n // 64)), True
+
+        with _dev(self.mgr.device):
+            return _sized_then_filled(lambda nbr, orow, mask: engine.check(L.lgs_debug_kmap_tables(
+                self.h, int(bwd), nbr, orow, mask, _stream(), ctypes.byref(n_pad), ctypes.byref(slots), ctypes.byref(present))), allocate)
 
     def _rows(self, transposed):
         n_in = self.mgr.map_size(self.in_key)
@@ -413,7 +379,7 @@ class HipManager:
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("the MI355X engine needs a HIP device, got %s (no CPU fallback)" % device)
-        self.device = device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        self.device = torch.device("cuda", device_index(device))
         h = _vp(None)
         engine.check(engine.lib().lgs_manager_create(self.device.index, ctypes.byref(h)))
         self.h = h
@@ -579,7 +545,7 @@ class HipBackend:
 
     def current_stream(self, device):
         """torch.cuda.current_stream(device) without its per-call Python cost: Stream objects are cached per raw handle"""
-        idx = device.index if device.index is not None else torch._C._cuda_getDevice()
+        idx = device_index(device)
         raw = torch._C._cuda_getCurrentRawStream(idx)
         s = self._cur.get((idx, raw))
         if s is None:
@@ -588,7 +554,7 @@ class HipBackend:
 
     def fork_event(self, device):
         """one reusable event per device for ordering the side stream after the compute stream (record, then wait_event)"""
-        idx = device.index if device.index is not None else torch._C._cuda_getDevice()
+        idx = device_index(device)
         ev = self._fork.get(idx)
         if ev is None:
             ev = self._fork[idx] = torch.cuda.Event()
@@ -615,7 +581,7 @@ class HipBackend:
         assert x.dim() == 2 and x.shape[0] == sm.n_fine, (tuple(x.shape), sm.n_fine)
         if x.stride(1) != 1 or x.stride(0) < c or (x2 is not None and x2.stride() != x.stride()):
             x = x.contiguous()
-            x2 = x2.contiguous() if x2 is not None else None
+            x2 = _contiguous(x2)
         if x2 is not None:
             assert x2.shape == x.shape and x2.dtype == x.dtype
         dt = _dtype_code(x)
@@ -710,14 +676,14 @@ class HipBackend:
         L = engine.lib()
         x = x.contiguous()
         n, c = x.shape
-        if n == 0:      # what nn.BatchNorm1d (= MinkowskiBatchNorm's `.bn`) says about batch statistics of nothing
-            raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (list(x.shape),))
+        if n == 0:
+            raise _empty_batch(x)
         dt = _dtype_code(x)
         part, piv = conv_stats if conv_stats is not None else (None, None)
         with _dev(x.device):
             y, y_ld = self._y_out(x, out_into)
             stats = torch.empty(2 * c, dtype=torch.float32, device=x.device)
-            res = residual.contiguous() if residual is not None else None
+            res = _contiguous(residual)
             ws = _ws(_bn_ws_bytes(L, n, c), x.device)
             engine.check(L.lgs_bn_forward(_ptr(x), n, c, _ptr(gamma), _ptr(beta), float(eps), float(momentum),
                                           _ptr(running_mean), _ptr(running_var), _ptr(num_batches_tracked), _ptr(res), int(relu), _ptr(y),
@@ -733,7 +699,7 @@ class HipBackend:
         dt = _dtype_code(x)
         # a column slice of a wider row-major tensor (the gradient of one ME.cat input) is read in place; the engine is given
         # dy's row stride explicitly, also when it is c
-        dy, dy_ld = rows_in_place(dy, c) if dy.dtype == x.dtype else (dy.contiguous(), 0)
+        dy, dy_ld = _dy_rows(dy, x.dtype, c)
         dy_ld = dy_ld or c
         y, y_ld = rows_in_place(y, c)
         with _dev(x.device):
@@ -761,7 +727,7 @@ class HipBackend:
         xa, xb = xa.contiguous(), xb.contiguous()
         n, c = xa.shape
         if n == 0:
-            raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (list(xa.shape),))
+            raise _empty_batch(xa)
         dt = _dtype_code(xa)
         with _dev(xa.device):
             path, wsb = _bn_pair_plan(L, 0, n, c, dt)
@@ -782,7 +748,7 @@ class HipBackend:
         L = engine.lib()
         n, c = xa.shape
         dt = _dtype_code(xa)
-        dy, dy_ld = rows_in_place(dy, c) if dy.dtype == xa.dtype else (dy.contiguous(), 0)
+        dy, dy_ld = _dy_rows(dy, xa.dtype, c)
         dy_ld = dy_ld or c
         ya, ya_ld = rows_in_place(ya, c)
         with _dev(xa.device):
@@ -879,7 +845,7 @@ class HipBackend:
         dt = _dtype_code(x)
         dev = x.device
         ds = wd is not None
-        dy, dy_ld = rows_in_place(dy, planes) if dy.dtype == x.dtype else (dy.contiguous(), 0)
+        dy, dy_ld = _dy_rows(dy, x.dtype, planes)      # (no `or planes` here: lgs_block_bwd.dy_row_stride is handed the 0, which means planes)
         pk = get_packed()
         with _dev(dev):
             p1, pm1 = pk.lookup(pcs[0], kmap3, 1, False, w1, w1, cin, planes, dt)
@@ -977,7 +943,7 @@ class HipBackend:
             y, y_ld = self._y_out(x, out_into)
             if n == 0:                     # an empty batch (a zero-row tensor has no storage to point at): nothing to normalise
                 return y
-            res = residual.contiguous() if residual is not None else None
+            res = _contiguous(residual)
             engine.check(L.lgs_bn_apply(_ptr(x), n, c, _ptr(gamma), _ptr(beta), _ptr(stats), _ptr(res), int(relu), _ptr(y),
                                         _dtype_code(x), int(y_ld), _stream()))
         return y
@@ -1004,7 +970,7 @@ class HipBackend:
         with _dev(x.device):
             y, y_ld = self._y_out(x, out_into)
             stats = torch.empty(2 * c + 1, dtype=torch.float32, device=x.device)      # [mean | invstd | 1 / global rows]
-            res = residual.contiguous() if residual is not None else None
+            res = _contiguous(residual)
             ws = _ws(L.lgs_bn_sync_workspace_bytes(n, c, comm.world), x.device)
             engine.check(L.lgs_bn_forward_sync(comm.h, _ptr(x), n, c, _ptr(gamma), _ptr(beta), float(eps), float(momentum),
                                                _ptr(running_mean), _ptr(running_var), _ptr(num_batches_tracked), _ptr(res), int(relu),
@@ -1088,8 +1054,8 @@ class HipBackend:
         L = engine.lib()
         feats = feats.contiguous()
         anchors = anchors.detach().contiguous().float()
-        labels = labels.contiguous().to(torch.int64)
-        neg = neg.contiguous().to(torch.int64)
+        labels = _int64(labels)
+        neg = _int64(neg)
         n, c = feats.shape
         na, k = anchors.shape[0], neg.shape[1]
         dt = _dtype_code(feats)
@@ -1113,8 +1079,8 @@ class HipBackend:
         n, c = feats.shape
         with _dev(feats.device):
             gf = torch.empty_like(feats)
-            gp = g_dpos.contiguous().float() if g_dpos is not None else None
-            gn = g_dneg.contiguous().float() if g_dneg is not None else None
+            gp = _grad32(g_dpos)
+            gn = _grad32(g_dneg)
             engine.check(L.lgs_clip_loss_backward(_ptr(feats), n, c, _ptr(tn), tn.shape[0], _ptr(labels), _ptr(neg), int(neg.shape[1]),
                                                   int(ignore_label), _ptr(inv), _ptr(d_pos), _ptr(d_neg), _ptr(gp), _ptr(gn), _ptr(gf),
                                                   _dtype_code(feats), _stream()))
@@ -1130,8 +1096,8 @@ class HipBackend:
         dt = _dtype_code(feats)
         with _dev(feats.device):
             gt = torch.empty((c, a8), dtype=torch.float32, device=feats.device)
-            gp = g_dpos.contiguous().float() if g_dpos is not None else None
-            gn = g_dneg.contiguous().float() if g_dneg is not None else None
+            gp = _grad32(g_dpos)
+            gn = _grad32(g_dneg)
             ws = _ws(L.lgs_clip_anchor_grad_workspace_bytes(n, c, na, dt), feats.device)
             engine.check(L.lgs_clip_loss_backward_anchors(_ptr(feats), n, c, na, _ptr(labels), _ptr(neg), int(neg.shape[1]),
                                                           int(ignore_label), _ptr(inv), _ptr(gp), _ptr(gn), _ptr(gt), dt, _ptr(ws),
@@ -1153,7 +1119,7 @@ class HipBackend:
         _require_dev(logits, "logits")
         L = engine.lib()
         logits = logits.contiguous()
-        labels = labels.contiguous().to(torch.int64)
+        labels = _int64(labels)
         n, c = logits.shape
         dev = logits.device
         with _dev(dev):
@@ -1161,8 +1127,7 @@ class HipBackend:
             dlogits = torch.empty_like(logits) if want_grad else None
             if n == 0:
                 return loss_rows, dlogits
-            if row_grad is not None:
-                row_grad = row_grad.contiguous().to(torch.float32)
+            row_grad = _grad32(row_grad)
             args = (_ptr(scale if scale is not None else self._one(dev)), _ptr(row_grad), _ptr(loss_rows), _ptr(dlogits),
                     _dtype_code(logits), _stream())
             if focal is None:
@@ -1178,7 +1143,7 @@ class HipBackend:
         denom: 'valid' = the counted rows (lgs_ce_count_valid: the kernel's predicate, a label outside [0, C) is an ignored row),
         'weight' = the sum of alpha[label] (ce_weight_sum; a zero sum counts as 1), 'sum' = 1.  An empty batch: loss 0, 1."""
         _require_dev(logits, "logits")
-        labels = labels.contiguous().to(torch.int64)
+        labels = _int64(labels)
         n, c = logits.shape
         one = self._one(logits.device)
         if inv_denom is None:
@@ -1218,11 +1183,11 @@ class HipBackend:
         order), the denominator of nn.CrossEntropyLoss(weight=alpha) 'mean'.  No host sync."""
         _require_dev(alpha, "alpha")
         L = engine.lib()
-        labels = labels.contiguous().to(torch.int64)
+        labels = _int64(labels)
         n = labels.shape[0]
         if n == 0:
             return self._one(alpha.device) * 0.0
-        rows = max(1, min(1024, (n + 2047) // 2048))
+        rows = _partial_rows(n)
         with _dev(alpha.device):
             partial = torch.empty(rows, dtype=torch.float32, device=alpha.device)
             engine.check(L.lgs_ce_weight_sum(_ptr(labels), n, int(n_classes), int(ignore_index), _ptr(alpha), _ptr(partial), rows, _stream()))
@@ -1248,10 +1213,10 @@ class HipBackend:
         _require_dev(loss_rows, "loss_rows")
         L = engine.lib()
         loss_rows = loss_rows.detach().contiguous().to(torch.float32)
-        labels = labels.contiguous().to(torch.int64)
+        labels = _int64(labels)
         group_of_class = group_of_class.contiguous().to(torch.int32)
         n = loss_rows.shape[0]
-        rows = max(1, min(1024, (n + 2047) // 2048))
+        rows = _partial_rows(n)
         with _dev(loss_rows.device):
             partial = torch.empty(rows, 6, dtype=torch.float32, device=loss_rows.device)
             engine.check(L.lgs_split_stats(_ptr(loss_rows), _ptr(labels), n, _ptr(group_of_class), int(group_of_class.shape[0]),
@@ -1271,7 +1236,7 @@ class HipBackend:
         _require_dev(confmat, "confmat")
         L = engine.lib()
         scores = scores.detach().contiguous()
-        labels = labels.contiguous().to(torch.int64)
+        labels = _int64(labels)
         n, c = scores.shape
         if confmat.dtype != torch.int64 or tuple(confmat.shape) != (c, c) or not confmat.is_contiguous():
             raise RuntimeError("seg_metrics: confmat must be a contiguous int64 [%d, %d] tensor" % (c, c))
@@ -1298,7 +1263,7 @@ class HipBackend:
         _require_dev(scores, "scores")
         L = engine.lib()
         scores = scores.detach().contiguous()
-        labels = labels.contiguous().to(torch.int64)
+        labels = _int64(labels)
         n, c = scores.shape
         if labels.shape[0] != n:
             raise RuntimeError("average_precision: %d labels for %d rows" % (labels.shape[0], n))
@@ -1381,8 +1346,8 @@ class HipBackend:
         seg_start [L], cls_count [L], elig_count [L]), device int64; seed: a host integer.  No host sync."""
         _require_dev(labels, "labels")
         L = engine.lib()
-        labels = labels.contiguous().to(torch.int64)
-        cum, order, seg_start, cls_count, elig_count = (t.contiguous().to(torch.int64) for t in tables)
+        labels = _int64(labels)
+        cum, order, seg_start, cls_count, elig_count = (_int64(t) for t in tables)
         n = labels.shape[0]
         if tuple(cum.shape) != (n_labels, n_labels) or order.shape[0] != n or any(t.shape[0] != n_labels for t in (seg_start, cls_count, elig_count)):
             raise RuntimeError("supcon_sample: tables do not match %d rows and %d labels" % (n, n_labels))
@@ -1399,8 +1364,8 @@ class HipBackend:
         _require_dev(feats, "features")
         L = engine.lib()
         feats = feats.contiguous()
-        labels = labels.contiguous().to(torch.int64)
-        pos_idx, neg_idx = pos_idx.contiguous().to(torch.int64), neg_idx.contiguous().to(torch.int64)
+        labels = _int64(labels)
+        pos_idx, neg_idx = _int64(pos_idx), _int64(neg_idx)
         n, c = feats.shape
         p, k = pos_idx.shape[1], neg_idx.shape[1]
         if labels.shape[0] != n or pos_idx.shape[0] != n or neg_idx.shape[0] != n:
@@ -1423,8 +1388,8 @@ class HipBackend:
         n, c = feats.shape
         with _dev(feats.device):
             gf = torch.empty_like(feats)
-            gp = g_dpos.contiguous().float() if g_dpos is not None else None
-            gn = g_dneg.contiguous().float() if g_dneg is not None else None
+            gp = _grad32(g_dpos)
+            gn = _grad32(g_dneg)
             engine.check(L.lgs_supcon_backward(_ptr(feats), n, c, _ptr(labels), _ptr(pos_idx), pos_idx.shape[1], _ptr(neg_idx),
                                                neg_idx.shape[1], int(ignore_label), int(n_labels), self._SUPCON_DISTANCE[distance],
                                                _ptr(sim), _ptr(inv), _ptr(gp), _ptr(gn), _ptr(gf), _dtype_code(feats), _stream()))

@@ -4,7 +4,8 @@
   GradSink         where a parameter gradient goes: the bucket slot or fp32 scratch (AffineSink / WeightSink build one)
   wgrad_placement  which stream a weight gradient runs on (+ the side-stream book-keeping BucketedDDP reads)
   memo             the one cache of engine size / plan queries
-Imports torch, engine and tuning only: backend_hip, modules, block and ddp all import it."""
+Imports torch, engine and tuning only: backend_hip, modules, block and ddp all import it.  How a caller hands addresses, streams and
+scratch to the C-ABI is the call layer's business: ../hipcall.py, under the same import rule."""
 import torch
 
 from .. import engine

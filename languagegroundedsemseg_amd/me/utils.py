@@ -5,9 +5,14 @@ Host inputs (numpy / CPU tensors) take the numpy path below, as in ME.  DEVICE t
 (SURVEY 8f-1): `voxelize` = the reference's rigid transform + floor (lib/voxelizer.py:136-139) as one kernel,
 dedup = the engine's coordinate insert (first occurrence wins, indices ascending), label collisions = lgs_label_vote."""
 import collections.abc
+import ctypes
 
 import numpy as np
 import torch
+
+from .. import engine
+from ..hipcall import on_device, ptr, raw_stream, require_hip
+from .core import get_backend
 
 
 def _floor_int(coords):
@@ -21,10 +26,7 @@ def voxelize(points, affine=None, batch_index=0, quantization_size=None):
     """Device voxelisation: points [N,3] float (HIP tensor) -> int32 [N,4] = (batch, floor(A (x,y,z,1))).
     `affine`: 3x4 / 4x4 array-like (the reference's `rigid_transformation`, lib/voxelizer.py:129-139); default =
     identity scaled by 1/quantization_size."""
-    import ctypes
-    from .. import engine
-    if not (isinstance(points, torch.Tensor) and points.is_cuda):
-        raise RuntimeError("ME.utils.voxelize runs on the MI355X engine: points must be a HIP tensor")
+    require_hip(points, "ME.utils.voxelize: points")
     a = np.eye(4, dtype=np.float64)
     if affine is not None:
         m = np.asarray(affine.cpu() if isinstance(affine, torch.Tensor) else affine, dtype=np.float64)
@@ -35,20 +37,15 @@ def voxelize(points, affine=None, batch_index=0, quantization_size=None):
     pts = points.detach().to(torch.float32).contiguous()
     n = pts.shape[0]
     assert pts.dim() == 2 and pts.shape[1] == 3
-    with torch.cuda.device(pts.device):
+    with on_device(pts.device):
         out = torch.empty((n, 4), dtype=torch.int32, device=pts.device)
-        engine.check(engine.lib().lgs_voxelize(ctypes.c_void_p(pts.data_ptr()), n, a12, int(batch_index),
-                                               ctypes.c_void_p(out.data_ptr()),
-                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        engine.check(engine.lib().lgs_voxelize(ptr(pts), n, a12, int(batch_index), ptr(out), raw_stream()))
     return out
 
 
 def _sparse_quantize_device(coordinates, features, labels, ignore_label, return_index, return_inverse, return_maps_only,
                             quantization_size):
     """sparse_quantize on HIP tensors: floor (+ 1/quantization_size) -> engine insert -> label vote, all on the device"""
-    import ctypes
-    from .. import engine
-    from .core import get_backend
     c = coordinates
     if c.is_floating_point():
         if c.shape[1] == 3:
@@ -68,10 +65,8 @@ def _sparse_quantize_device(coordinates, features, labels, ignore_label, return_
     if labels is not None:
         ln = labels.to(q.device).to(torch.int64).contiguous()
         lab = torch.empty(nu, dtype=torch.int64, device=q.device)
-        sp = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-        engine.check(engine.lib().lgs_label_vote(ctypes.c_void_p(ln.data_ptr()), int(ln.shape[0]), ctypes.c_void_p(unique_map.data_ptr()),
-                                                 ctypes.c_void_p(inverse_map.data_ptr()), int(nu), int(ignore_label),
-                                                 ctypes.c_void_p(lab.data_ptr()), sp))
+        engine.check(engine.lib().lgs_label_vote(ptr(ln), int(ln.shape[0]), ptr(unique_map), ptr(inverse_map), int(nu), int(ignore_label),
+                                                 ptr(lab), raw_stream(q.device)))
         lab = lab.to(labels.dtype)
     if return_maps_only:
         return (unique_map, inverse_map) if return_inverse else unique_map

@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import metrics as _metrics
+from .hipcall import host_offsets, require_hip
 
 SIMILARITY_RTOL = 1e-6
 
@@ -74,8 +75,7 @@ def _check_points(points):
         raise ValueError("points must be a tensor [M, 3], got %s" % (tuple(points.shape) if torch.is_tensor(points) else type(points),))
     if points.dtype != torch.float32:
         raise ValueError("points must be float32, got %s" % points.dtype)
-    if not points.is_cuda:
-        raise RuntimeError("nearest_voxel runs on the MI355X engine: points must be a HIP tensor (no CPU fallback)")
+    require_hip(points, "nearest_voxel: points")
 
 
 def _scene_offsets(scene_offsets, m, device):
@@ -86,9 +86,7 @@ def _scene_offsets(scene_offsets, m, device):
         if scene_offsets.dim() != 1 or scene_offsets.shape[0] < 2:
             raise ValueError("scene_offsets must be [b + 1]")
         return scene_offsets.to(device=device, dtype=torch.int64).contiguous(), scene_offsets.shape[0] - 1
-    off = [int(v) for v in scene_offsets]
-    if len(off) < 2 or off[0] != 0 or off[-1] != m or any(x > y for x, y in zip(off, off[1:])):
-        raise ValueError("scene_offsets must ascend from 0 to the point count %d, got %s" % (m, off))
+    off = host_offsets(scene_offsets, m)
     return torch.tensor(off, dtype=torch.int64, device=device), len(off) - 1
 
 

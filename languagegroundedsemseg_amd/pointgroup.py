@@ -11,27 +11,25 @@ import numpy as np
 import torch
 
 from . import engine
+from .hipcall import on_device, ptr, raw_stream, require_hip, scratch
 
 
 def cluster_points(coords, semantic_label, radius, threshold, batch_idxs=None):
     """coords [N,3] float (HIP tensor), semantic_label [N] int -> (cluster_idxs int32 [M,2] = (cluster id, point index),
     cluster_offsets int32 [nCluster+1]), the output format of PG_OP.bfs_cluster (bfs_cluster.cpp:104-125)."""
-    if not (isinstance(coords, torch.Tensor) and coords.is_cuda):
-        raise RuntimeError("cluster_points runs on the MI355X engine: coords must be a HIP tensor (no CPU fallback)")
+    require_hip(coords, "cluster_points: coords")
     L = engine.lib()
     dev = coords.device
     xyz = coords.detach().to(torch.float32).contiguous()
     sem = semantic_label.to(dev).to(torch.int32).contiguous()
     n = xyz.shape[0]
     bi = batch_idxs.to(dev).to(torch.int32).contiguous() if batch_idxs is not None else None
-    vp = ctypes.c_void_p
-    with torch.cuda.device(dev):
+    with on_device(dev):
         comp = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        ws = torch.empty(max(int(L.lgs_cluster_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
+        ws = scratch(L.lgs_cluster_workspace_bytes(n), dev)          # (lgs_cluster initialises what it reads of it, and returns done with it)
         nc = ctypes.c_int32(0)
-        engine.check(L.lgs_cluster(vp(xyz.data_ptr()), vp(bi.data_ptr()) if bi is not None else vp(None), vp(sem.data_ptr()), n,
-                                   float(radius), int(threshold), vp(comp.data_ptr()), ctypes.byref(nc), vp(ws.data_ptr()),
-                                   vp(torch.cuda.current_stream(dev).cuda_stream)))
+        engine.check(L.lgs_cluster(ptr(xyz), ptr(bi), ptr(sem), n, float(radius), int(threshold), ptr(comp), ctypes.byref(nc), ptr(ws),
+                                   raw_stream()))
     comp = comp[:n]
     keep = torch.nonzero(comp >= 0).flatten()
     if keep.numel() == 0:

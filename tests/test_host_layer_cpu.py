@@ -1,10 +1,12 @@
-"""me/host.py: the decisions the engine's Python wrappers share, checked on CPU tensors (no library, no device)."""
+"""me/host.py and hipcall.py: the decisions the engine's Python wrappers share, checked on CPU tensors (no library, no device)."""
+import ctypes
 import itertools
 
+import numpy as np
 import pytest
 import torch
 
-from languagegroundedsemseg_amd import engine
+from languagegroundedsemseg_amd import engine, hipcall
 from languagegroundedsemseg_amd.me import host
 
 
@@ -114,3 +116,60 @@ def test_wgrad_placement_truth_table(monkeypatch, dbg, wide_rule):
         want = "skip" if dbg == "skip" else \
             "inline" if (dbg == "inline" or inline or (wide_rule and (cin, cout, rows) == wide)) else "side"
         assert host.wgrad_placement(True, cin, cout, rows, inline) == want, (dbg, wide_rule, cin, cout, rows, inline)
+
+
+# ------------------------------------------------------------------------------------------ the call layer (hipcall.py)
+def test_ptr_is_a_plain_int_and_none_is_null():
+    t = torch.zeros(4)
+    assert hipcall.ptr(None) is None
+    assert type(hipcall.ptr(t)) is int and hipcall.ptr(t) == t.data_ptr()
+
+
+def test_dtype_code():
+    assert hipcall.dtype_code(torch.zeros(1)) == engine.LGS_F32
+    assert hipcall.dtype_code(torch.zeros(1, dtype=torch.bfloat16)) == engine.LGS_BF16
+    for dt in (torch.float16, torch.int32):
+        with pytest.raises(RuntimeError, match="float32 and bfloat16"):
+            hipcall.dtype_code(torch.zeros(1, dtype=dt))
+
+
+@pytest.mark.parametrize("value", [torch.zeros(3), [1.0, 2.0], None])
+def test_require_hip_refuses_host_tensors_and_non_tensors(value):
+    with pytest.raises(RuntimeError) as e:
+        hipcall.require_hip(value, "the bank points")
+    assert all(s in str(e.value) for s in ("HIP tensor", "no CPU fallback", "the bank points"))
+
+
+@pytest.mark.parametrize("v", [0, 2 ** 31 - 1, 2 ** 31, 2 ** 32 - 1, -1, 2 ** 63 - 1, 2 ** 63, 2 ** 64 - 1])
+def test_i32_i64_wrap_like_c(v):
+    assert hipcall.i32(v) == ctypes.c_int32(v).value
+    assert hipcall.i64(v) == ctypes.c_int64(v).value
+
+
+def test_host_offsets():
+    n = 7
+    assert hipcall.host_offsets([0, n], n) == [0, n]
+    for form in ([0, 0, n], np.array([0, 0, n]), torch.tensor([0, 0, n])):
+        off = hipcall.host_offsets(form, n)
+        assert off == [0, 0, n] and type(off) is list and all(type(v) is int for v in off)
+    for bad in ([0], [1, n], [0, n - 1], [0, 5, 3, n]):          # too short, first != 0, last != n, a descending pair
+        with pytest.raises(ValueError, match="scene_offsets"):
+            hipcall.host_offsets(bad, n)
+
+
+def _voxelize_batched(points, offsets):
+    from languagegroundedsemseg_amd import augment
+    return augment.voxelize_batched(points, offsets, np.tile(np.eye(4), (len(offsets) - 1, 1, 1)))
+
+
+def _nearest_voxel(points, offsets):
+    from languagegroundedsemseg_amd import pointcloud
+    return pointcloud.nearest_voxel(None, points, offsets)
+
+
+@pytest.mark.parametrize("call", [_voxelize_batched, _nearest_voxel])
+def test_the_device_refusal_comes_before_the_offset_refusal(call):
+    """host points AND a bad offset list: both operators refuse the host tensor first (RuntimeError), before they look at the offsets
+    (whose ValueError a HIP tensor would get) -- and neither reaches an engine call"""
+    with pytest.raises(RuntimeError, match="HIP tensor"):
+        call(torch.zeros(5, 3), [0, 4, 2, 5])
