@@ -823,6 +823,53 @@ int lgs_inst_overlap(const int32_t *member /* [m] */, const int32_t *offsets /* 
                      int32_t *gt_count /* [g_cap] */, int32_t *inter /* [p, g_cap] */, int32_t *prop_void /* [p] */, float *conf /* [p] */,
                      int32_t *status, void *workspace, void *stream);
 
+/* ---- instance targets: per-instance table of a batch and the offset losses (csrc/lgs_insttarget.hip) ----
+ * replaces: VoxelizationDataset.get_instance_info (downstream/insseg/datasets/dataset.py:280-304: per scene, on the host, one boolean
+ *   mask over all points per instance id) with the masking of :336-341, the per-step concatenation and upload of centers and ids
+ *   (downstream/insseg/lib/pl_Trainer.py:280-284) and the offset losses of :286-298 (about fifteen torch launches over [N, 3] per direction)
+ * NEW SYMBOLS ONLY: LGS_ABI_VERSION stays 18; a library that lacks them lacks the capability.
+ * All pointers are DEVICE pointers except masked_labels (HOST, read during the call).  Enqueues on `stream`, never synchronises.
+ *
+ * lgs_instance_info: coords[n, 4] int32 with the batch index in column 0, instance_ids[n] int64.  An instance is the pair (batch index,
+ *   id): the same id in two scenes names two instances.  id == -1 names none; so does a point whose labels[i] equals one of the
+ *   n_masked <= 32 masked_labels (n_masked == 0: labels may be NULL).  Any other id outside [0, 2^31) sets status bit 2, a negative
+ *   batch index status bit 4; such a point is treated as -1.
+ *   ids_out[n]: the ids after masking (-1 or the id).  slot[n]: the point's row of the table, -1 for none.
+ *   key / count / bbox / center [inst_cap] / [inst_cap] / [inst_cap, 6] / [inst_cap, 3]: per instance (batch << 32) | id, its points, min
+ *   xyz then max xyz, and its centre.  Unused rows hold key -1, count 0, zeros.  WHICH row an instance takes is unspecified, but it
+ *   depends on the set of instances alone: two calls on the same points give the same rows.  The map instance -> (count, box, centre)
+ *   is exact: the three coordinate sums are signed 64-bit integers, count and box are integers, and
+ *   center = (float)((double)sum / (double)count) -- what numpy's xyz.mean(0) stored into a float32 row gives.
+ *   centers[n, 3] (may be NULL): center[slot] per point, -1 on the rows without an instance: the reference's array.
+ *   status: one int32, overwritten.  Bit 1: more than inst_cap distinct instances -- nothing is written out of bounds, the instances
+ *   beyond the capacity get slot -1, the other outputs are unspecified.  1 <= inst_cap <= 65536.  n == 0 is legal.
+ *   Integer atomics only, folded per workgroup in LDS before they reach global memory; the result does not depend on order.
+ *   workspace: lgs_instance_info_workspace_bytes(n, inst_cap) bytes (-1: n outside 0 .. 2^31 - 1 or inst_cap outside 1 .. 65536); it
+ *   depends on inst_cap alone.
+ *
+ * lgs_offset_loss_forward: pt_offsets[n, 3] float32 / bf16 (widened exactly), coords and slot as above, center = the table.  Per row with
+ *   slot >= 0, in fp32 and the reference's order: gt = (center[slot] - xyz) * voxel_size; dist = sum |po - gt|;
+ *   dir = -sum (gt / (|gt| + 1e-8)) * (po / (|po| + 1e-8)).  partial[partial_rows, 3] (fp64, 1 <= partial_rows <= 1024 = the grid):
+ *   per workgroup the sums of dist, of dir and the number of such rows, folded in a fixed tree; one more launch adds the rows in
+ *   a fixed tree and writes *norm_loss = sum dist / (valid + 1e-6), *dir_loss = sum dir / (valid + 1e-6), *valid = the count, each
+ *   rounded to fp32 once.  No float atomics: two calls give the same bits.  n == 0 gives 0, 0, 0.
+ * lgs_offset_loss_backward: d_pt_offsets[n, 3] in `dtype` =
+ *     (*g_norm / den) * sign(po - gt) + (*g_dir / den) * d dir / d po,   den = *valid + 1e-6,   sign(0) = 0,
+ *   d dir / d po = -u / D + (u . po / D) po / (D |po|) with u = gt / (|gt| + 1e-8), D = |po| + 1e-8 and the second term absent at
+ *   po == 0 (torch's zero subgradient of the norm); zero on the rows without an instance.  valid, g_norm, g_dir: one DEVICE float
+ *   each (valid: what the forward wrote).  Neither direction reads or writes an [n, 3] array but pt_offsets and d_pt_offsets. */
+int64_t lgs_instance_info_workspace_bytes(int64_t n, int inst_cap);
+int lgs_instance_info(const int32_t *coords /* [n, 4] */, const int64_t *instance_ids /* [n] */, const int64_t *labels /* [n] or NULL */,
+                      int64_t n, const int64_t *masked_labels /* HOST [n_masked] */, int n_masked, int inst_cap, int64_t *ids_out /* [n] */,
+                      int32_t *slot /* [n] */, int64_t *key /* [inst_cap] */, int32_t *count /* [inst_cap] */, int32_t *bbox /* [inst_cap, 6] */,
+                      float *center /* [inst_cap, 3] */, float *centers /* [n, 3] or NULL */, int32_t *status, void *workspace, void *stream);
+int lgs_offset_loss_forward(const void *pt_offsets /* [n, 3] */, const int32_t *coords /* [n, 4] */, const int32_t *slot /* [n] */,
+                            const float *center /* [inst_cap, 3] */, int64_t n, float voxel_size, int dtype, double *partial /* [partial_rows, 3] */,
+                            int partial_rows, float *norm_loss, float *dir_loss, float *valid, void *stream);
+int lgs_offset_loss_backward(const void *pt_offsets /* [n, 3] */, const int32_t *coords /* [n, 4] */, const int32_t *slot /* [n] */,
+                             const float *center /* [inst_cap, 3] */, int64_t n, float voxel_size, int dtype, const float *valid,
+                             const float *g_norm, const float *g_dir, void *d_pt_offsets /* [n, 3] */, void *stream);
+
 /* ---- supervised point-contrastive loss (csrc/lgs_supcon.hip) -------------------------------------
  * replaces: PointSupConLoss.forward (lib/losses/PointSupConLoss.py:74-154), the third embedding criterion of
  *   BaselineTrainerModule.init_criterions (lib/train_test/pl_BaselineTrainer.py:92-108): per class of the batch three device -> host

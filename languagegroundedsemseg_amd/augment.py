@@ -562,14 +562,24 @@ class DeviceAugmentation:
                 for s in range(len(plan.elastic))]
 
     def __call__(self, points, colors, labels, scene_offsets, plan=None, elastic_noise=None, jitter_noise=None, return_state=False,
-                 scene_boxes=None, trial_draws=None):
+                 scene_boxes=None, trial_draws=None, instances=None):
         """points [N, 3], colors [N, 3], labels [N] (HIP tensors), scene_offsets (B + 1 host integers)
         -> (coords [n, 4] int32, feats [n, 3] float32, labels [n]) of the surviving voxel rows.
+        instances: [N] per-point instance ids (a HIP tensor); they ride through the chain like the labels (the dedup's first
+        occurrence wins) and come back as a fourth value, ready for instances.instance_info.  Refused together with tail_instances:
+        pasted rows have no scene instance id.
         elastic_noise: per stage a list of per-scene noise arrays; jitter_noise: callable(n) or device [n, 3] normals (teacher-forced).
         With tail_instances: scene_boxes (per scene a host [m_s, 2, 3] array of the scene's instance boxes, world units) and
         optionally trial_draws, as paste_instances takes them; the voxeliser then applies M_v only and the paste rotates."""
+        if instances is not None and self.tail is not None:
+            raise NotImplementedError("DeviceAugmentation: instances= together with tail_instances is not part of the device chain "
+                                      "(pasted rows have no scene instance id; DESIGN.md section 8)")
         for t, what in ((points, "points"), (colors, "colors"), (labels, "labels")):
             require_hip(t, what)
+        if instances is not None:
+            require_hip(instances, "instances")
+            if instances.dim() != 1 or instances.shape[0] != points.shape[0]:
+                raise ValueError("DeviceAugmentation: instances must be [N], one id per point")
         dev = points.device
         off = host_offsets(scene_offsets, points.shape[0])
         B = len(off) - 1
@@ -620,6 +630,8 @@ class DeviceAugmentation:
         feats = chromatic_augment(feats, off_vox, self.color_params(plan), scale=self.color_scale, normalize=self.normalize_color,
                                   seed=plan.seed, noise=jitter_noise)
         out = (coords, feats, labels_in.index_select(0, keep).to(labels.dtype))
+        if instances is not None:
+            out += (instances.index_select(0, keep),)
         if return_state:
             state["points"], state["keep"] = pts, keep
             return out + (state,)

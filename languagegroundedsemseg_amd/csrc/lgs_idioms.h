@@ -81,6 +81,17 @@ inline InstOverlapWs inst_overlap_layout(int64_t m, int p, int g_cap) {
   return w;
 }
 
+// lgs_insttarget.hip: the instance table of 2^k >= 2 inst_cap entries (key, point count, three coordinate sums, min, max: filled per
+// entry, moved to the entry's output row once the rows are known) and the row of every entry
+constexpr int kInstTargetMaxCap = 65536;
+inline uint32_t inst_target_table_size(int inst_cap) { return (uint32_t)table_pow2(64, 2 * (int64_t)inst_cap); }
+struct InstTargetWs { int64_t t_key, t_cnt, t_sum, t_min, t_max, t_row, total; };
+inline InstTargetWs inst_target_layout(int inst_cap) {
+  Layout l;
+  const int64_t t = inst_target_table_size(inst_cap);
+  return {l.take(8 * t), l.take(4 * t), l.take(24 * t), l.take(12 * t), l.take(12 * t), l.take(4 * t), l.total()};
+}
+
 // lgs_augment.hip, elastic distortion: one slot of max_cells x 3 floats per scene, noise then field
 struct ElasticWs { int64_t noise, field, total; };
 inline ElasticWs elastic_layout(int b, int64_t max_cells) {

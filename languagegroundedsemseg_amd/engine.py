@@ -224,6 +224,7 @@ EXPORTS = [
     "lgs_ce_count_valid", "lgs_focal_forward_backward", "lgs_ce_weight_sum", "lgs_seg_metrics",
     "lgs_ap_workspace_bytes", "lgs_average_precision",
     "lgs_inst_overlap_workspace_bytes", "lgs_inst_overlap",
+    "lgs_instance_info_workspace_bytes", "lgs_instance_info", "lgs_offset_loss_forward", "lgs_offset_loss_backward",
     "lgs_supcon_sample", "lgs_supcon_forward", "lgs_supcon_backward",
     "lgs_comm_unique_id", "lgs_comm_create", "lgs_comm_create_ipc", "lgs_comm_ipc_open", "lgs_comm_destroy", "lgs_comm_world", "lgs_bn_sync_workspace_bytes",
     "lgs_bn_forward_sync", "lgs_bn_backward_sync",
@@ -322,6 +323,9 @@ def lib():
         "lgs_seg_metrics": [vp, i64, ci, vp, i64, vp, vp, vp, ci, vp],
         "lgs_average_precision": [vp, i64, ci, vp, i64, ci, vp, ci, vp, vp],
         "lgs_inst_overlap": [vp, vp, vp, ci, i64, vp, i64, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp],
+        "lgs_instance_info": [vp, vp, vp, i64, pi64, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "lgs_offset_loss_forward": [vp, vp, vp, vp, i64, cf, ci, vp, ci, vp, vp, vp, vp],
+        "lgs_offset_loss_backward": [vp, vp, vp, vp, i64, cf, ci, vp, vp, vp, vp, vp],
         "lgs_supcon_sample": [vp, i64, ci, i64, vp, vp, vp, vp, vp, ci, ci, i64, vp, vp, vp],
         "lgs_supcon_forward": [vp, i64, ci, vp, vp, ci, vp, ci, i64, ci, ci, vp, vp, vp, vp, ci, vp],
         "lgs_supcon_backward": [vp, i64, ci, vp, vp, ci, vp, ci, i64, ci, ci, vp, vp, vp, vp, vp, ci, vp],
@@ -378,6 +382,8 @@ def lib():
     L.lgs_ap_workspace_bytes.argtypes = [i64, ci]
     L.lgs_inst_overlap_workspace_bytes.restype = i64
     L.lgs_inst_overlap_workspace_bytes.argtypes = [i64, i64, ci, ci]
+    L.lgs_instance_info_workspace_bytes.restype = i64
+    L.lgs_instance_info_workspace_bytes.argtypes = [i64, ci]
     L.lgs_clip_workspace_bytes.restype = i64
     L.lgs_clip_workspace_bytes.argtypes = [ci, ci, ci]
     L.lgs_clip_loss_workspace_bytes.restype = i64

@@ -10,12 +10,15 @@
                           (/root/reference/lib/losses/ContrastiveLanguageLoss.py:97-194, feat_dist :73-95) written
                           on the dense MFMA contraction S = normalize(F) . normalize(T)^T plus index gathers, which
                           is mathematically the reference's [N,1+K,C] gather + bmm.
+* fused_instance_offset_losses -- the two PointGroup offset losses of downstream/insseg/lib/pl_Trainer.py:286-298 from the instance
+                          table of the batch (instances.instance_info): one streaming kernel per direction (lgs_insttarget.hip).
 * PointSupConLoss         -- the supervised point-contrastive baseline (lib/losses/PointSupConLoss.py): samples drawn on the device
                           (k_supcon_sample), distances and their gradient from (1 + P + K) row reads per point (lgs_supcon.hip).
 """
 import torch
 import torch.nn as nn
 
+from . import instances, tuning
 from .me.core import get_backend
 
 
@@ -971,6 +974,50 @@ def instance_offset_losses(pt_offsets, coords_xyz, centers, instance_ids, voxel_
     po_n = po / (po.norm(p=2, dim=1, keepdim=True) + 1e-8)
     dir_loss = (-(gt_n * po_n).sum(-1) * valid).sum() / denom
     return norm_loss, dir_loss
+
+
+class _OffsetLossFused(torch.autograd.Function):
+    """(norm_loss, dir_loss) of the offset head from one streaming kernel per direction (lgs_offset_loss_forward / _backward): the
+    centre of a row is read from the instance table through its slot, nothing [N, 3] is allocated but the gradient, and the backward
+    takes the upstream gradients and the valid count from device memory."""
+
+    @staticmethod
+    def forward(ctx, pt_offsets, coords, slot, center_table, voxel_size):
+        po = pt_offsets.detach().contiguous()
+        norm_loss, dir_loss, valid = instances.offset_loss_forward(po, coords, slot, center_table, voxel_size)
+        ctx.save_for_backward(po, coords, slot, center_table, valid)
+        ctx.voxel_size = voxel_size
+        return norm_loss, dir_loss
+
+    @staticmethod
+    def backward(ctx, g_norm, g_dir):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        po, coords, slot, center_table, valid = ctx.saved_tensors
+        g_norm, g_dir = (g.detach().to(torch.float32).reshape(()).contiguous() for g in (g_norm, g_dir))
+        return instances.offset_loss_backward(po, coords, slot, center_table, ctx.voxel_size, valid, g_norm, g_dir), None, None, None, None
+
+
+def fused_instance_offset_losses(pt_offsets, coords, info, voxel_size):
+    """The offset losses of downstream/insseg/lib/pl_Trainer.py:286-298 from the instance table of the batch, without the [N, 3]
+    `centers` upload of :280-284: pt_offsets [N, 3] (fp32 or bf16), coords int32 [N, 4] (batch index in column 0), info = what
+    instances.instance_info(coords, instance_ids, ...) returned.  -> (offset_norm_loss, offset_dir_loss), differentiable in pt_offsets.
+    HIP tensors: one kernel per direction, no host synchronisation, sums in fp64 in a fixed order (two calls give the same bits).
+    Tuning knob LGS_INST_TARGETS_FUSED=0: the torch lines of instance_offset_losses on info.center instead.  CPU tensors always take
+    those lines; there `info` is the [N] tensor of instance ids after masking (-1: none) and the centres are computed with torch
+    (instances.centers_torch)."""
+    if pt_offsets.dim() != 2 or pt_offsets.shape[1] != 3 or coords.dim() != 2 or coords.shape[1] != 4 or coords.shape[0] != pt_offsets.shape[0]:
+        raise ValueError("pt_offsets must be [N, 3] and coords [N, 4], got %s and %s" % (tuple(pt_offsets.shape), tuple(coords.shape)))
+    is_info = isinstance(info, instances.InstanceInfo)
+    rows = (info.ids if is_info else info).shape[0]
+    if rows != pt_offsets.shape[0]:
+        raise ValueError("instance targets of %d rows for %d offsets" % (rows, pt_offsets.shape[0]))
+    if (pt_offsets.is_cuda and is_info and pt_offsets.dtype in (torch.float32, torch.bfloat16) and coords.dtype == torch.int32
+            and tuning.host("INST_TARGETS_FUSED")):
+        return _OffsetLossFused.apply(pt_offsets, coords.contiguous(), info.slot, info.center_table, float(voxel_size))
+    ids = info.ids if is_info else info
+    centers = info.center if is_info and info.center is not None else instances.centers_torch(coords, ids)
+    return instance_offset_losses(pt_offsets, coords[:, 1:], centers, ids, voxel_size)
 
 
 def feature_sim_argmax(sim):

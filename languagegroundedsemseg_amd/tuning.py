@@ -44,6 +44,9 @@ HOST_KNOBS = {
                                  "gradient-bucket all-reduces: behind one of those a 800-byte statistics exchange on the backward pass's critical path "
                                  "waits ~0.2 - 0.3 ms, up to six times per step.  1 = for the default group of an `nccl` world of >= 2 ranks, "
                                  "2 = for any backend and world size (tests), 0 = off"),
+    "INST_TARGETS_FUSED": (1, int, "0 = losses.fused_instance_offset_losses takes the torch lines of instance_offset_losses on the per-point "
+                                   "centres (what CPU tensors always take) instead of lgs_offset_loss_forward / lgs_offset_loss_backward; read at "
+                                   "every call (same losses within fp32 rounding: tests/test_gpu_insttarget.py)"),
     "SET_HW_QUEUES": (0, int, "1 = importing the package sets GPU_MAX_HW_QUEUES=8 before the HIP runtime starts (see configure_hw_queues)"),
 }
 

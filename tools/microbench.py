@@ -171,6 +171,53 @@ def insseg():
     t = timeit(step)
     print("InsSegRes16UNet34C fwd+bwd (CE + offset losses, incl. map build) %d voxels: %.2f ms = %.1f M voxels/s" % (
         coords.shape[0], t, coords.shape[0] / t / 1e3))
+    insseg_targets(coords, c, inst, centers)
+
+
+def insseg_targets(coords, c, inst, centers):
+    """the instance targets of that batch: the torch lines the trainer runs on uploaded centres (forward + backward) against
+    instance_info + fused_instance_offset_losses + backward, and the host time of get_instance_info's numpy restatement for one scene"""
+    import time
+    from languagegroundedsemseg_amd import instances
+    from languagegroundedsemseg_amd.losses import fused_instance_offset_losses, instance_offset_losses
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    n = coords.shape[0]
+    po = (torch.randn(n, 3, device=DEV) * 0.3).bfloat16().requires_grad_(True)
+    xyz = c[:, 1:].contiguous()
+
+    def torch_lines():
+        po.grad = None
+        nl, dl = instance_offset_losses(po, xyz, centers, inst, 0.02)
+        (nl + dl).backward()
+
+    def fused(targets=True, info=[None]):
+        po.grad = None
+        if targets or info[0] is None:
+            info[0] = instances.instance_info(c, inst, return_centers=False)
+        nl, dl = fused_instance_offset_losses(po, c, info[0], 0.02)
+        (nl + dl).backward()
+    # 200 calls per window, three windows each, the variants alternating: medians, and the spread of the three in brackets
+    variants = [("offset losses, torch lines on given centres, fwd + bwd", torch_lines),
+                ("instance_info + fused offset losses, fwd + bwd", fused),
+                ("  fused offset losses alone, fwd + bwd", lambda: fused(False)),
+                ("  instance_info alone (table, ids, slots)", lambda: instances.instance_info(c, inst, return_centers=False)),
+                ("  instance_info with the [n, 3] centres", lambda: instances.instance_info(c, inst))]
+    times = [[] for _ in variants]
+    for _ in range(3):
+        for k, (_, fn) in enumerate(variants):
+            times[k].append(timeit(fn, 200, 5))
+    print("instance targets, %d voxels, bf16 offsets:" % n)
+    for (name, _), t in zip(variants, times):
+        print("%-66s %9.3f ms   [%.3f .. %.3f]" % (name, sorted(t)[1], min(t), max(t)))
+    import insttarget_reference as ir          # the tests' numpy restatement of get_instance_info (one sort + segment reductions)
+    rows = coords[:, 0] == 0
+    xyz0, ids0 = coords[rows, 1:], inst.cpu().numpy()[rows]
+    ir.get_instance_info(xyz0, ids0)
+    t0 = time.perf_counter()
+    for _ in range(5):
+        ir.get_instance_info(xyz0, ids0)
+    t_host = (time.perf_counter() - t0) * 1e3 / 5
+    print("host: numpy restatement of get_instance_info, ONE scene (%d voxels, %d ids) %9.3f ms" % (xyz0.shape[0], len(np.unique(ids0)), t_host))
 
 
 def cluster():
