@@ -15,10 +15,14 @@
 // (x, dy twice, dx written), 7 with a ReLU mask from y and a residual gradient out -- the reduce launch writes the masked
 // gradient and the apply reads it back, so y is read and dy masked once.  The two norms that meet at the residual add of a
 // downsample block share their passes (lgs_bn_forward_pair / lgs_bn_backward_pair, below): 5 forward and 10 backward for both.
+// Every floating-point expression of these kernels is a function of lgs_normmath.h; contraction is off here as it is there.
+#include "lgs_normmath.h"
 #include "lgs_rows.h"
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+
+#pragma clang fp contract(off)
 
 namespace lgs {
 
@@ -29,7 +33,21 @@ template <typename T> __device__ inline float stored_value(float x);
 template <> __device__ inline float stored_value<float>(float x) { return x; }
 template <> __device__ inline float stored_value<bf16_t>(float x) { return bf16_to_f32(f32_to_bf16(x)); }
 
-// Column reduction of up to two per-element quantities.  MODE 0: (x, x*x)  [forward statistics]
+// How a float that crosses workgroups is moved.  Between launches: plainly.  Inside a fused kernel (scratch rows, statistics):
+// with agent-scope accesses (sc1: coherent across the eight XCDs' L2s) instead of fencing -- a release / acquire fence at agent
+// scope writes back and invalidates the whole L2 of the XCD, and 512 workgroups doing that twice cost 0.24 ms per launch.
+__device__ inline void st_coh(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ inline float ld_coh(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <bool COH> struct Mem {
+  __device__ static float ld(const float *p) { if constexpr (COH) return ld_coh(p); else return *p; }
+  __device__ static void st(float *p, float v) { if constexpr (COH) st_coh(p, v); else *p = v; }
+};
+// the 16-byte row store, non-temporal or not
+template <bool NT, int W, typename T> __device__ inline void store_row(T *p, const float *v) {
+  if constexpr (NT) stv_nt<W>(p, v); else stv<W>(p, v);
+}
+
+// Column reduction of up to two per-element quantities.  MODE 0: (x - pivot, (x - pivot)^2)  [forward statistics]
 // MODE 1: (dy', dy' * xhat) where dy' = dy masked by (y > 0) when relu  [backward reductions]
 // Each block handles a contiguous slab of rows; thread layout: cg = tid % G channel groups, rl = tid / G.
 // out: scratch[blocks][2][C]
@@ -52,22 +70,18 @@ __device__ inline void colreduce_rows(const T *__restrict__ x, const T *__restri
   const int RL = kNT / G;           // rows in flight per block iteration (G <= 256)
   const int cg = threadIdx.x % G, rl = threadIdx.x / G;
   const bool active = rl < RL;
-  float s0[W], s1[W];
+  float s0[W], s1[W], q0[W], q1[W];          // q: the second norm's sums
 #pragma unroll
-  for (int i = 0; i < W; ++i) s0[i] = s1[i] = 0.f;
-  float mean[W], istd[W], gm[W], bt[W];
-  float q0[PAIR ? W : 1], q1[PAIR ? W : 1], mean_b[PAIR ? W : 1], istd_b[PAIR ? W : 1];   // the second norm's sums and statistics
+  for (int i = 0; i < W; ++i) s0[i] = s1[i] = q0[i] = q1[i] = 0.f;
+  float pivot[W];
+  BnBwdConsts<W> k, kb;
   if (MODE == 1) {
-#pragma unroll
-    for (int i = 0; i < W; ++i) {
-      mean[i] = stats[cg * W + i]; istd[i] = stats[c + cg * W + i];
-      gm[i] = relu == 2 ? gamma[cg * W + i] : 0.f; bt[i] = relu == 2 ? beta[cg * W + i] : 0.f;
-      if constexpr (PAIR) { q0[i] = q1[i] = 0.f; mean_b[i] = stats_b[cg * W + i]; istd_b[i] = stats_b[c + cg * W + i]; }
-    }
+    k.load_norm(stats, gamma, beta, c, cg * W, relu);
+    if constexpr (PAIR) kb.load_norm(stats_b, nullptr, nullptr, c, cg * W, 0);
   } else {
     // forward statistics are accumulated about a per-channel pivot (row 0, the same for every block) so that
     // var = E[(x-k)^2] - E[x-k]^2 does not cancel catastrophically when |mean| >> std
-    if (n > 0) ldv<W>(x + cg * W, mean);
+    if (n > 0) ldv<W>(x + cg * W, pivot);
   }
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
   const int64_t r1 = min(r0 + rows_per_block, n);
@@ -79,20 +93,20 @@ __device__ inline void colreduce_rows(const T *__restrict__ x, const T *__restri
     auto accumulate = [&](const float (&xv)[W], float (&gv)[W], const float (&yv)[W], const float (&xbv)[W], int64_t row) __attribute__((always_inline)) {
       if (MODE == 0) {
 #pragma unroll
-        for (int i = 0; i < W; ++i) { const float d = xv[i] - mean[i]; s0[i] += d; s1[i] += d * d; }
+        for (int i = 0; i < W; ++i) bn_acc_fwd(xv[i], pivot[i], s0[i], s1[i]);
       } else {
         if (relu == 1) {
 #pragma unroll
           for (int i = 0; i < W; ++i) gv[i] = yv[i] > 0.f ? gv[i] : 0.f;
         } else if (relu == 2) {
 #pragma unroll
-          for (int i = 0; i < W; ++i) gv[i] = ((xv[i] - mean[i]) * (istd[i] * gm[i]) + bt[i]) > 0.f ? gv[i] : 0.f;  // same expression as k_bn_apply
+          for (int i = 0; i < W; ++i) gv[i] = k.out(i, xv[i]) > 0.f ? gv[i] : 0.f;
         }
 #pragma unroll
-        for (int i = 0; i < W; ++i) { s0[i] += gv[i]; s1[i] += gv[i] * (xv[i] - mean[i]) * istd[i]; }
+        for (int i = 0; i < W; ++i) bn_acc_bwd(gv[i], xv[i], k.mean[i], k.istd[i], s0[i], s1[i]);
         if constexpr (PAIR) {
 #pragma unroll
-          for (int i = 0; i < W; ++i) { q0[i] += gv[i]; q1[i] += gv[i] * (xbv[i] - mean_b[i]) * istd_b[i]; }
+          for (int i = 0; i < W; ++i) bn_acc_bwd(gv[i], xbv[i], kb.mean[i], kb.istd[i], q0[i], q1[i]);
         }
         if (gout) stv<W>(gout + row * c + cg * W, gv);
       }
@@ -182,13 +196,14 @@ __global__ __launch_bounds__(kNT) void k_colreduce_pair(const T *__restrict__ xa
 // backward -> dbeta = sum dy', dgamma = sum dy' xhat.  Block = 16 channels x 16 partial-slices: a thread sums every
 // 16th partial with eight independent loads in flight (the fold is a pure latency chain: 4 slices of 128 dependent
 // steps took 13 us per BatchNorm, twice per layer), slices are combined through LDS in slice order.
+// COH (here and below): the step runs inside a fused kernel, on rows other workgroups of the same launch wrote and for them to read.
 constexpr int kFoldCh = 16, kFoldSl = 16;
-__device__ inline void fold_sums(const float *__restrict__ scratch, int nblocks, int c, int ch, int part, double &s, double &ss,
-                                 double (*red)[2][kFoldCh]) {
+template <bool COH>
+__device__ inline void fold_sums(const float *scratch, int nblocks, int c, int ch, int part, double &s, double &ss, double (*red)[2][kFoldCh]) {
   s = 0.0; ss = 0.0;
   if (ch < c) {
 #pragma unroll 8
-    for (int b = part; b < nblocks; b += kFoldSl) { s += scratch[(int64_t)b * 2 * c + ch]; ss += scratch[(int64_t)b * 2 * c + c + ch]; }
+    for (int b = part; b < nblocks; b += kFoldSl) { s += Mem<COH>::ld(scratch + (int64_t)b * 2 * c + ch); ss += Mem<COH>::ld(scratch + (int64_t)b * 2 * c + c + ch); }
   }
   red[part][0][threadIdx.x % kFoldCh] = s;
   red[part][1][threadIdx.x % kFoldCh] = ss;
@@ -198,11 +213,10 @@ __device__ inline void fold_sums(const float *__restrict__ scratch, int nblocks,
   }
 }
 // statistics that arrive as per-tile partial rows from the conv epilogue (BnEpi): fold groups of rows into <= 128 rows
-// of the same [row][2][C] layout, fixed order (deterministic)
+// of the same [row][2][C] layout, fixed order (deterministic).  Rows [r0, r1) of `part` -> out_row
 constexpr int kPartialFoldRows = 128;
-__global__ __launch_bounds__(256) void k_partial_reduce(const float *__restrict__ part, int rows, int c2, int rows_per_block,
-                                                        float *__restrict__ out) {
-  const int r0 = blockIdx.x * rows_per_block, r1 = min(r0 + rows_per_block, rows);
+template <bool COH>
+__device__ inline void partial_reduce_rows(const float *part, int r0, int r1, int c2, float *out_row) {
   for (int col = threadIdx.x; col < c2; col += blockDim.x) {
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     int r = r0;
@@ -211,41 +225,43 @@ __global__ __launch_bounds__(256) void k_partial_reduce(const float *__restrict_
       a2 += part[(int64_t)(r + 2) * c2 + col]; a3 += part[(int64_t)(r + 3) * c2 + col];
     }
     for (; r < r1; ++r) a0 += part[(int64_t)r * c2 + col];
-    out[(int64_t)blockIdx.x * c2 + col] = (a0 + a1) + (a2 + a3);
+    Mem<COH>::st(out_row + col, (a0 + a1) + (a2 + a3));
   }
 }
+__global__ __launch_bounds__(256) void k_partial_reduce(const float *__restrict__ part, int rows, int c2, int rows_per_block,
+                                                        float *__restrict__ out) {
+  const int r0 = blockIdx.x * rows_per_block;
+  partial_reduce_rows<false>(part, r0, min(r0 + rows_per_block, rows), c2, out + (int64_t)blockIdx.x * c2);
+}
 
-// pivot_mode 0: the per-channel pivot is row 0 of x (k_colreduce<0>); 1: pivot_ptr[ch] (or 0 if NULL) -- conv-epilogue partials
-template <typename T>
-__device__ inline void fold_fwd_body(const float *__restrict__ scratch, const T *__restrict__ x, int nblocks, int c,
-                                     int64_t n, float eps, float momentum, float *__restrict__ running_mean,
-                                     float *__restrict__ running_var, long long *__restrict__ nbt,
-                                     float *__restrict__ stats, int pivot_mode, const float *__restrict__ pivot_ptr) {
+// the per-channel pivot of forward sums.  pivot_mode 0: row 0 of x (k_colreduce<0>); 1: pivot_ptr[ch] (or 0 if NULL) -- conv-epilogue partials
+template <typename T> __device__ inline double fold_pivot(const T *x, int64_t n, int ch, int pivot_mode, const float *pivot_ptr) {
+  return pivot_mode ? (pivot_ptr ? (double)pivot_ptr[ch] : 0.0) : (n > 0 ? (double)ld_elem(x + ch) : 0.0);
+}
+// channels [fb * kFoldCh, +kFoldCh): fold, finish, save the statistics, update the running statistics
+template <typename T, bool COH>
+__device__ inline void fold_fwd_body(const float *scratch, const T *x, int fb, int nblocks, int c, int64_t n, float eps, float momentum,
+                                     float *running_mean, float *running_var, float *stats, int pivot_mode, const float *pivot_ptr) {
   __shared__ double red[kFoldSl][2][kFoldCh];
-  const int ch = blockIdx.x * kFoldCh + (threadIdx.x % kFoldCh), part = threadIdx.x / kFoldCh;
+  const int ch = fb * kFoldCh + (threadIdx.x % kFoldCh), part = threadIdx.x / kFoldCh;
   double s, ss;
-  fold_sums(scratch, nblocks, c, ch, part, s, ss, red);
-  if (nbt && blockIdx.x == 0 && threadIdx.x == 0) *nbt += 1;   // nn.BatchNorm1d.num_batches_tracked
+  fold_sums<COH>(scratch, nblocks, c, ch, part, s, ss, red);
   if (part != 0 || ch >= c) return;
-  const double pivot = pivot_mode ? (pivot_ptr ? (double)pivot_ptr[ch] : 0.0) : (n > 0 ? (double)ld_elem(x + ch) : 0.0);
-  double dm = n > 0 ? s / (double)n : 0.0;
-  double var = n > 0 ? ss / (double)n - dm * dm : 0.0;
-  if (var < 0.0) var = 0.0;
-  const double mean = pivot + dm;
-  stats[ch] = (float)mean;
-  stats[c + ch] = (float)(1.0 / sqrt(var + (double)eps));
-  if (running_mean) {
-    double unb = n > 1 ? var * (double)n / (double)(n - 1) : var;
-    running_mean[ch] = (float)((1.0 - momentum) * running_mean[ch] + momentum * mean);
-    running_var[ch] = (float)((1.0 - momentum) * running_var[ch] + momentum * unb);
-  }
+  const BnMoments m = bn_finish(s, ss, n, fold_pivot(x, n, ch, pivot_mode, pivot_ptr), eps);
+  Mem<COH>::st(stats + ch, (float)m.mean);
+  Mem<COH>::st(stats + c + ch, m.istd);
+  if (running_mean) bn_update_running(running_mean[ch], running_var[ch], momentum, m, n);
+}
+__device__ inline void count_batch(long long *nbt) {          // nn.BatchNorm1d.num_batches_tracked
+  if (nbt && blockIdx.x == 0 && threadIdx.x == 0) *nbt += 1;
 }
 template <typename T>
 __global__ __launch_bounds__(256) void k_fold_fwd(const float *__restrict__ scratch, const T *__restrict__ x, int nblocks, int c,
                                                   int64_t n, float eps, float momentum, float *__restrict__ running_mean,
                                                   float *__restrict__ running_var, long long *__restrict__ nbt,
                                                   float *__restrict__ stats, int pivot_mode, const float *__restrict__ pivot_ptr) {
-  fold_fwd_body<T>(scratch, x, nblocks, c, n, eps, momentum, running_mean, running_var, nbt, stats, pivot_mode, pivot_ptr);
+  count_batch(nbt);
+  fold_fwd_body<T, false>(scratch, x, blockIdx.x, nblocks, c, n, eps, momentum, running_mean, running_var, stats, pivot_mode, pivot_ptr);
 }
 // one norm of a forward pair as the kernels see it: input, parameters, buffers, and where its partial rows / statistics lie
 template <typename T> struct PairFwdNorm {
@@ -261,7 +277,8 @@ template <typename T> struct PairFwdNorm {
 template <typename T>
 __global__ __launch_bounds__(256) void k_fold_fwd_pair(PairFwdNorm<T> a, PairFwdNorm<T> b, int nblocks, int c, int64_t n) {
   const PairFwdNorm<T> &p = blockIdx.y ? b : a;
-  fold_fwd_body<T>(p.scratch, p.x, nblocks, c, n, p.eps, p.momentum, p.running_mean, p.running_var, p.nbt, p.stats, 0, nullptr);
+  count_batch(p.nbt);
+  fold_fwd_body<T, false>(p.scratch, p.x, blockIdx.x, nblocks, c, n, p.eps, p.momentum, p.running_mean, p.running_var, p.stats, 0, nullptr);
 }
 // split API (SyncBN): local mean and M2 = sum (x - mean)^2, to be combined across ranks with Chan's formula
 template <typename T>
@@ -271,40 +288,40 @@ __global__ __launch_bounds__(256) void k_fold_stats(const float *__restrict__ sc
   __shared__ double red[kFoldSl][2][kFoldCh];
   const int ch = blockIdx.x * kFoldCh + (threadIdx.x % kFoldCh), part = threadIdx.x / kFoldCh;
   double s, ss;
-  fold_sums(scratch, nblocks, c, ch, part, s, ss, red);
+  fold_sums<false>(scratch, nblocks, c, ch, part, s, ss, red);
   if (part != 0 || ch >= c) return;
-  const double pivot = pivot_mode ? (pivot_ptr ? (double)pivot_ptr[ch] : 0.0) : (n > 0 ? (double)ld_elem(x + ch) : 0.0);
-  const double dm = n > 0 ? s / (double)n : 0.0;
-  double m2 = ss - (double)n * dm * dm;
+  const double dm = bn_shift(s, n);
+  double m2 = __builtin_fma(-dm, (double)n * dm, ss);
   if (m2 < 0.0) m2 = 0.0;
-  mean_m2[ch] = (float)(pivot + dm);
+  mean_m2[ch] = (float)(fold_pivot(x, n, ch, pivot_mode, pivot_ptr) + dm);
   mean_m2[c + ch] = (float)m2;
   if (ch == 0) mean_m2[2 * c] = (float)n;   // [mean | M2 | count]: one packed all-gather per layer
 }
 
-__device__ inline void fold_bwd_body(const float *__restrict__ scratch, int nblocks, int c, float *__restrict__ dgamma,
-                                     float *__restrict__ dbeta, float *__restrict__ sums) {
+// channels [fb * kFoldCh, +kFoldCh): dbeta = sum dy', dgamma = sum dy' xhat, and both again as the `sums` row of the apply
+template <bool COH>
+__device__ inline void fold_bwd_body(const float *scratch, int fb, int nblocks, int c, float *dgamma, float *dbeta, float *sums) {
   __shared__ double red[kFoldSl][2][kFoldCh];
-  const int ch = blockIdx.x * kFoldCh + (threadIdx.x % kFoldCh), part = threadIdx.x / kFoldCh;
+  const int ch = fb * kFoldCh + (threadIdx.x % kFoldCh), part = threadIdx.x / kFoldCh;
   double s, ss;
-  fold_sums(scratch, nblocks, c, ch, part, s, ss, red);
+  fold_sums<COH>(scratch, nblocks, c, ch, part, s, ss, red);
   if (part != 0 || ch >= c) return;
   dbeta[ch] = (float)s;
   dgamma[ch] = (float)ss;
-  sums[ch] = (float)s;
-  sums[c + ch] = (float)ss;
+  Mem<COH>::st(sums + ch, (float)s);
+  Mem<COH>::st(sums + c + ch, (float)ss);
 }
 __global__ __launch_bounds__(256) void k_fold_bwd(const float *__restrict__ scratch, int nblocks, int c, float *__restrict__ dgamma,
                                                   float *__restrict__ dbeta, float *__restrict__ sums) {
-  fold_bwd_body(scratch, nblocks, c, dgamma, dbeta, sums);
+  fold_bwd_body<false>(scratch, blockIdx.x, nblocks, c, dgamma, dbeta, sums);
 }
 // k_fold_bwd for the two norms of a pair: blockIdx.y picks the norm
 __global__ __launch_bounds__(256) void k_fold_bwd_pair(const float *__restrict__ scratch_a, const float *__restrict__ scratch_b, int nblocks,
                                                        int c, float *__restrict__ dgamma_a, float *__restrict__ dbeta_a,
                                                        float *__restrict__ sums_a, float *__restrict__ dgamma_b,
                                                        float *__restrict__ dbeta_b, float *__restrict__ sums_b) {
-  if (blockIdx.y) fold_bwd_body(scratch_b, nblocks, c, dgamma_b, dbeta_b, sums_b);
-  else fold_bwd_body(scratch_a, nblocks, c, dgamma_a, dbeta_a, sums_a);
+  if (blockIdx.y) fold_bwd_body<false>(scratch_b, blockIdx.x, nblocks, c, dgamma_b, dbeta_b, sums_b);
+  else fold_bwd_body<false>(scratch_a, blockIdx.x, nblocks, c, dgamma_a, dbeta_a, sums_a);
 }
 
 // SyncBN: combine the per-rank [mean | M2 | count] records (Chan's parallel formula, double) into the global
@@ -322,44 +339,38 @@ __global__ void k_sync_combine(const float *__restrict__ all_stats, int world, i
   }
   if (ch >= c) return;
   double mean = 0.0;
-  for (int r = 0; r < world; ++r) mean += (double)all_stats[(int64_t)r * rec + 2 * c] * (double)all_stats[(int64_t)r * rec + ch];
+  for (int r = 0; r < world; ++r) mean = __builtin_fma((double)all_stats[(int64_t)r * rec + 2 * c], (double)all_stats[(int64_t)r * rec + ch], mean);
   mean = n > 0.0 ? mean / n : 0.0;
   double m2 = 0.0;
   for (int r = 0; r < world; ++r) {
     const double d = (double)all_stats[(int64_t)r * rec + ch] - mean;
-    m2 += (double)all_stats[(int64_t)r * rec + c + ch] + (double)all_stats[(int64_t)r * rec + 2 * c] * d * d;
+    m2 += __builtin_fma(d, (double)all_stats[(int64_t)r * rec + 2 * c] * d, (double)all_stats[(int64_t)r * rec + c + ch]);
   }
   const double var = n > 0.0 ? m2 / n : 0.0;
   stats[ch] = (float)mean;
   stats[c + ch] = (float)(1.0 / sqrt(var + (double)eps));
-  if (running_mean) {
-    const double unb = n > 1.0 ? m2 / (n - 1.0) : var;
-    running_mean[ch] = (float)((1.0 - momentum) * running_mean[ch] + momentum * mean);
-    running_var[ch] = (float)((1.0 - momentum) * running_var[ch] + momentum * unb);
-  }
+  if (running_mean) bn_update_running(running_mean[ch], running_var[ch], momentum, mean, n > 1.0 ? m2 / (n - 1.0) : var);
 }
 
 // y = relu?( (x - mean) * invstd * gamma + beta (+ residual) )
 // A thread owns ONE channel group (its per-channel constants live in registers) and walks rows: with
 // G = C / W groups, thread t handles group t % G of rows t / G, t / G + R, ...  (R = rows per sweep of the grid).
-// Two independent 16-byte loads are in flight per operand per thread.
-template <typename T>
-__global__ __launch_bounds__(kNT) void k_bn_apply(const T *__restrict__ x, const T *__restrict__ res, int64_t n, int c,
-                                                  const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                  const float *__restrict__ stats, int relu, T *__restrict__ y, int64_t y_ld) {
-  // y_ld = row stride of the output (elements): > c when y is a column slice of a wider buffer (zero-copy ME.cat)
+// Two independent 16-byte loads are in flight per operand per thread.  NT: the output is not read again soon.
+// y_ld = row stride of the output (elements): > c when y is a column slice of a wider buffer (zero-copy ME.cat)
+// (this loop, bwd_apply_rows and the two constant loaders below are __forceinline__: inlined by the ordinary inliner the bf16
+// kernels took up to 24 VGPRs more and lost a wave or two per SIMD -- profiles/norm_arith.txt, section 3)
+template <typename T, bool NT>
+__device__ __forceinline__ void apply_rows(const T *__restrict__ x, const T *__restrict__ res, int64_t n, int c, const BnFwdConsts<Width<T>::V> &k,
+                                  int relu, T *__restrict__ y, int64_t y_ld, int cg, int rl, int RL) {
   constexpr int W = Width<T>::V;
-  const int G = c / W, RL = kNT / G;
-  const int cg = threadIdx.x % G, rl = threadIdx.x / G;
-  if (rl >= RL) return;
-  float sc[W], mean[W], bt[W];
+  auto finish = [&](float (&xv)[W], const float (&rv)[W]) __attribute__((always_inline)) {
 #pragma unroll
-  for (int k = 0; k < W; ++k) {
-    const int ch = cg * W + k;
-    sc[k] = stats[c + ch] * gamma[ch];
-    mean[k] = stats[ch];
-    bt[k] = beta[ch];
-  }
+    for (int i = 0; i < W; ++i) {
+      float o = k.out(i, xv[i]);
+      if (res) o += rv[i];
+      xv[i] = (relu && o < 0.f) ? 0.f : o;
+    }
+  };
   const int64_t stride = (int64_t)gridDim.x * RL;
   for (int64_t r = (int64_t)blockIdx.x * RL + rl; r < n; r += 2 * stride) {
     const int64_t r2 = r + stride;
@@ -368,26 +379,54 @@ __global__ __launch_bounds__(kNT) void k_bn_apply(const T *__restrict__ x, const
     ldv<W>(x + r * c + cg * W, xa);
     if (two) ldv<W>(x + r2 * c + cg * W, xb);
     if (res) { ldv<W>(res + r * c + cg * W, ra); if (two) ldv<W>(res + r2 * c + cg * W, rb); }
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-      float o = (xa[k] - mean[k]) * sc[k] + bt[k];   // keep this exact expression: the backward recomputes the ReLU mask from it
-      if (res) o += ra[k];
-      xa[k] = (relu && o < 0.f) ? 0.f : o;
-    }
-    stv_nt<W>(y + r * y_ld + cg * W, xa);
+    finish(xa, ra);
+    store_row<NT, W>(y + r * y_ld + cg * W, xa);
     if (two) {
-#pragma unroll
-      for (int k = 0; k < W; ++k) {
-        float o = (xb[k] - mean[k]) * sc[k] + bt[k];
-        if (res) o += rb[k];
-        xb[k] = (relu && o < 0.f) ? 0.f : o;
-      }
-      stv_nt<W>(y + r2 * y_ld + cg * W, xb);
+      finish(xb, rb);
+      store_row<NT, W>(y + r2 * y_ld + cg * W, xb);
     }
   }
 }
+template <typename T>
+__global__ __launch_bounds__(kNT) void k_bn_apply(const T *__restrict__ x, const T *__restrict__ res, int64_t n, int c,
+                                                  const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                  const float *__restrict__ stats, int relu, T *__restrict__ y, int64_t y_ld) {
+  constexpr int W = Width<T>::V;
+  const int G = c / W, RL = kNT / G;
+  const int cg = threadIdx.x % G, rl = threadIdx.x / G;
+  if (rl >= RL) return;
+  BnFwdConsts<W> k;
+  k.template load<Mem<false>>(stats, gamma, beta, c, cg * W);
+  apply_rows<T, true>(x, res, n, c, k, relu, y, y_ld, cg, rl, RL);
+}
 
 // dx = gamma*invstd * (dy' - mean(dy') - xhat * mean(dy' xhat));  dres = dy'
+template <typename T, bool NT, bool FMA>
+__device__ __forceinline__ void bwd_apply_rows(const T *__restrict__ x, const T *__restrict__ y, const T *__restrict__ dy, int64_t n, int c,
+                                      const BnBwdConsts<Width<T>::V> &k, int relu, T *__restrict__ dx, T *__restrict__ dres,
+                                      int64_t dy_ld, int64_t y_ld, int cg, int rl, int RL) {
+  constexpr int W = Width<T>::V;
+  const int64_t stride = (int64_t)gridDim.x * RL;
+  for (int64_t r = (int64_t)blockIdx.x * RL + rl; r < n; r += stride) {
+    const int64_t o = r * c + cg * W;
+    float xv[W], gv[W];
+    ldv<W>(x + o, xv);
+    ldv<W>(dy + r * dy_ld + cg * W, gv);
+    if (relu == 1) {
+      float yv[W];
+      ldv<W>(y + r * y_ld + cg * W, yv);
+#pragma unroll
+      for (int i = 0; i < W; ++i) gv[i] = yv[i] > 0.f ? gv[i] : 0.f;
+    } else if (relu == 2) {
+#pragma unroll
+      for (int i = 0; i < W; ++i) gv[i] = k.out(i, xv[i]) > 0.f ? gv[i] : 0.f;
+    }
+    if (dres) store_row<NT, W>(dres + o, gv);
+#pragma unroll
+    for (int i = 0; i < W; ++i) xv[i] = k.template dx<FMA>(i, xv[i], gv[i]);
+    store_row<NT, W>(dx + o, xv);
+  }
+}
 template <typename T>
 __global__ __launch_bounds__(kNT) void k_bn_bwd_apply(const T *__restrict__ x, const T *__restrict__ y, const T *__restrict__ dy,
                                                       int64_t n, int c, const float *__restrict__ gamma,
@@ -399,40 +438,13 @@ __global__ __launch_bounds__(kNT) void k_bn_bwd_apply(const T *__restrict__ x, c
   const int G = c / W, RL = kNT / G;
   const int cg = threadIdx.x % G, rl = threadIdx.x / G;
   if (rl >= RL) return;
-  float mean[W], istd[W], sc[W], bt[W], gi[W], m1[W], m2[W];
   if (inv_n_dev) inv_n = *inv_n_dev;   // SyncBN: 1 / global row count lives on the device (no host sync)
+  BnBwdConsts<W> k;
+  float s[W], ss[W];
 #pragma unroll
-  for (int k = 0; k < W; ++k) {
-    const int ch = cg * W + k;
-    mean[k] = stats[ch]; istd[k] = stats[c + ch];
-    sc[k] = istd[k] * (relu == 2 ? gamma[ch] : 0.f);
-    bt[k] = relu == 2 ? beta[ch] : 0.f;
-    gi[k] = gamma[ch] * istd[k];
-    m1[k] = sums[ch] * inv_n; m2[k] = sums[c + ch] * inv_n;
-  }
-  const int64_t stride = (int64_t)gridDim.x * RL;
-  for (int64_t r = (int64_t)blockIdx.x * RL + rl; r < n; r += stride) {
-    const int64_t o = r * c + cg * W;
-    float xv[W], gv[W];
-    ldv<W>(x + o, xv);
-    ldv<W>(dy + r * dy_ld + cg * W, gv);
-    if (relu == 1) {
-      float yv[W];
-      ldv<W>(y + r * y_ld + cg * W, yv);
-#pragma unroll
-      for (int k = 0; k < W; ++k) gv[k] = yv[k] > 0.f ? gv[k] : 0.f;
-    } else if (relu == 2) {
-#pragma unroll
-      for (int k = 0; k < W; ++k) gv[k] = ((xv[k] - mean[k]) * sc[k] + bt[k]) > 0.f ? gv[k] : 0.f;  // same expression as k_bn_apply
-    }
-    if (dres) stv_nt<W>(dres + o, gv);
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-      const float xh = (xv[k] - mean[k]) * istd[k];
-      xv[k] = gi[k] * (gv[k] - m1[k] - xh * m2[k]);
-    }
-    stv_nt<W>(dx + o, xv);
-  }
+  for (int i = 0; i < W; ++i) { s[i] = sums[cg * W + i]; ss[i] = sums[c + cg * W + i]; }
+  k.load(stats, gamma, beta, c, cg * W, relu, inv_n, s, ss);
+  bwd_apply_rows<T, true, kDxFma<T, kBwdThree>>(x, y, dy, n, c, k, relu, dx, dres, dy_ld, y_ld, cg, rl, RL);
 }
 
 // k_colreduce as the first of three launches: >= 128 rows per block, <= 512 blocks: coarse levels (a few thousand rows) still get
@@ -453,11 +465,6 @@ constexpr int kReduceMaxBlocks = 512;
 // (measured in the 8-scene step, layers <= 24 MB fused: 30.9 ms with 512 workgroups, 29.8 ms with 256, 30.0 ms unfused).
 constexpr int kFusedMaxBlocks = 256;
 
-// Values that cross workgroups inside a fused kernel (scratch rows, statistics) are written and read with agent-scope
-// accesses (sc1: coherent across the eight XCDs' L2s) instead of fencing: a release / acquire fence at agent scope writes back
-// and invalidates the whole L2 of the XCD, and 512 workgroups doing that twice cost 0.24 ms per launch.
-__device__ inline void st_coh(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline float ld_coh(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ inline void grid_arrive_wait(unsigned *ctr, unsigned target) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's coherent stores are acknowledged
   __syncthreads();
@@ -474,21 +481,6 @@ __device__ inline void grid_leave(unsigned *ctr, unsigned total) {
     if (old == total - 1) __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
-// fold_sums over rows other workgroups of this launch wrote
-__device__ inline void fold_sums_coh(const float *scratch, int nblocks, int c, int ch, int part, double &s, double &ss,
-                                     double (*red)[2][kFoldCh]) {
-  s = 0.0; ss = 0.0;
-  if (ch < c) {
-#pragma unroll 8
-    for (int b = part; b < nblocks; b += kFoldSl) { s += ld_coh(scratch + (int64_t)b * 2 * c + ch); ss += ld_coh(scratch + (int64_t)b * 2 * c + c + ch); }
-  }
-  red[part][0][threadIdx.x % kFoldCh] = s;
-  red[part][1][threadIdx.x % kFoldCh] = ss;
-  __syncthreads();
-  if (part == 0) {
-    for (int q = 1; q < kFoldSl; ++q) { s += red[q][0][threadIdx.x % kFoldCh]; ss += red[q][1][threadIdx.x % kFoldCh]; }
-  }
-}
 
 // column sums of one slab of rows [r0, r1) -> dst[2][C]; the body of k_colreduce (same summation order)
 template <typename T, int MODE>
@@ -501,33 +493,27 @@ __device__ inline void colreduce_slab(const T *x, const T *y, const T *dy, const
   float s0[W], s1[W];
 #pragma unroll
   for (int i = 0; i < W; ++i) s0[i] = s1[i] = 0.f;
-  float mean[W], istd[W], gm[W], bt[W];
-  if (MODE == 1) {
-#pragma unroll
-    for (int i = 0; i < W; ++i) {
-      mean[i] = stats[cg * W + i]; istd[i] = stats[c + cg * W + i];
-      gm[i] = relu == 2 ? gamma[cg * W + i] : 0.f; bt[i] = relu == 2 ? beta[cg * W + i] : 0.f;
-    }
-  } else {
-    if (n > 0) ldv<W>(x + cg * W, mean);   // pivot = row 0, as in k_colreduce<T, 0>
-  }
+  float pivot[W];
+  BnBwdConsts<W> k;
+  if (MODE == 1) k.load_norm(stats, gamma, beta, c, cg * W, relu);
+  else if (n > 0) ldv<W>(x + cg * W, pivot);   // row 0, as in k_colreduce<T, 0>
   if (active) {
     int64_t r = r0 + rl;
     constexpr int U = MODE == 0 ? 4 : 2;
     auto accumulate = [&](const float (&xv)[W], float (&gv)[W], const float (&yv)[W]) __attribute__((always_inline)) {
       if (MODE == 0) {
 #pragma unroll
-        for (int i = 0; i < W; ++i) { const float d = xv[i] - mean[i]; s0[i] += d; s1[i] += d * d; }
+        for (int i = 0; i < W; ++i) bn_acc_fwd(xv[i], pivot[i], s0[i], s1[i]);
       } else {
         if (relu == 1) {
 #pragma unroll
           for (int i = 0; i < W; ++i) gv[i] = yv[i] > 0.f ? gv[i] : 0.f;
         } else if (relu == 2) {
 #pragma unroll
-          for (int i = 0; i < W; ++i) gv[i] = ((xv[i] - mean[i]) * (istd[i] * gm[i]) + bt[i]) > 0.f ? gv[i] : 0.f;
+          for (int i = 0; i < W; ++i) gv[i] = k.out(i, xv[i]) > 0.f ? gv[i] : 0.f;
         }
 #pragma unroll
-        for (int i = 0; i < W; ++i) { s0[i] += gv[i]; s1[i] += gv[i] * (xv[i] - mean[i]) * istd[i]; }
+        for (int i = 0; i < W; ++i) bn_acc_bwd(gv[i], xv[i], k.mean[i], k.istd[i], s0[i], s1[i]);
       }
     };
     for (; r + (U - 1) * RL < r1; r += U * RL) {
@@ -579,64 +565,26 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(4))) void k
   const int64_t r1 = min(r0 + rows_per_block, n);
   // ---- step 1: per-workgroup column sums (or: fold the conv epilogue's partial rows into <= 128 rows)
   if (partials) {
-    const int c2 = 2 * c;
-    for (int pb = blockIdx.x; pb < nfoldrows; pb += nwg) {
-      const int p0 = pb * partial_rpb, p1 = min(p0 + partial_rpb, partial_rows);
-      for (int col = threadIdx.x; col < c2; col += kNT) {
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        int r = p0;
-        for (; r + 4 <= p1; r += 4) {
-          a0 += partials[(int64_t)(r + 0) * c2 + col]; a1 += partials[(int64_t)(r + 1) * c2 + col];
-          a2 += partials[(int64_t)(r + 2) * c2 + col]; a3 += partials[(int64_t)(r + 3) * c2 + col];
-        }
-        for (; r < p1; ++r) a0 += partials[(int64_t)r * c2 + col];
-        st_coh(scratch + (int64_t)pb * c2 + col, (a0 + a1) + (a2 + a3));
-      }
-    }
+    for (int pb = blockIdx.x; pb < nfoldrows; pb += nwg)
+      partial_reduce_rows<true>(partials, pb * partial_rpb, min(pb * partial_rpb + partial_rpb, partial_rows), 2 * c, scratch + (int64_t)pb * 2 * c);
   } else {
     colreduce_slab<T, 0>(x, nullptr, nullptr, nullptr, nullptr, nullptr, n, c, 0, r0, r1, scratch + (int64_t)blockIdx.x * 2 * c, c, c);
   }
   grid_arrive_wait(ctr, nwg);
   // ---- step 2: fold + finish the statistics, 16 channels per workgroup
-  {
-    __shared__ double red[kFoldSl][2][kFoldCh];
-    const int nfb = (c + kFoldCh - 1) / kFoldCh;
-    for (int fb = blockIdx.x; fb < nfb; fb += nwg) {
-      const int ch = fb * kFoldCh + (threadIdx.x % kFoldCh), part = threadIdx.x / kFoldCh;
-      double s, ss;
-      fold_sums_coh(scratch, nfoldrows, c, ch, part, s, ss, red);
-      if (part == 0 && ch < c) {
-        const double pivot = partials ? (pivot_ptr ? (double)pivot_ptr[ch] : 0.0) : (n > 0 ? (double)ld_elem(x + ch) : 0.0);
-        const double dm = n > 0 ? s / (double)n : 0.0;
-        double var = n > 0 ? ss / (double)n - dm * dm : 0.0;
-        if (var < 0.0) var = 0.0;
-        const double mean = pivot + dm;
-        st_coh(stats + ch, (float)mean);
-        st_coh(stats + c + ch, (float)(1.0 / sqrt(var + (double)eps)));
-        if (running_mean) {
-          const double unb = n > 1 ? var * (double)n / (double)(n - 1) : var;
-          running_mean[ch] = (float)((1.0 - momentum) * running_mean[ch] + momentum * mean);
-          running_var[ch] = (float)((1.0 - momentum) * running_var[ch] + momentum * unb);
-        }
-      }
-      __syncthreads();
-    }
-    if (nbt && blockIdx.x == 0 && threadIdx.x == 0) *nbt += 1;
+  for (int fb = blockIdx.x; fb < (c + kFoldCh - 1) / kFoldCh; fb += nwg) {
+    fold_fwd_body<T, true>(scratch, x, fb, nfoldrows, c, n, eps, momentum, running_mean, running_var, stats, partials != nullptr, pivot_ptr);
+    __syncthreads();
   }
+  count_batch(nbt);
   grid_arrive_wait(ctr, 2 * nwg);
   grid_leave(ctr, 3 * nwg);
   // ---- step 3: y = relu?((x - mean) * invstd * gamma + beta (+ residual)) over this workgroup's slab, last rows first
   const int G = c / W, RL = kNT / G;
   const int cg = threadIdx.x % G, rl = threadIdx.x / G;
   if (rl >= RL) return;
-  float sc[W], mean[W], bt[W];
-#pragma unroll
-  for (int k = 0; k < W; ++k) {
-    const int ch = cg * W + k;
-    sc[k] = ld_coh(stats + c + ch) * gamma[ch];
-    mean[k] = ld_coh(stats + ch);
-    bt[k] = beta[ch];
-  }
+  BnFwdConsts<W> k;
+  k.template load<Mem<true>>(stats, gamma, beta, c, cg * W);
   constexpr int U = W == 8 ? 2 : 4;   // rows in flight per thread (registers: <= 128 VGPRs, see above)
   for (int64_t r = r1 - 1 - rl; r >= r0; r -= (int64_t)U * RL) {
     float xv[U][W], rv[U][W];
@@ -653,10 +601,10 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(4))) void k
       const int64_t ru = r - (int64_t)u * RL;
       if (ru >= r0) {
 #pragma unroll
-        for (int k = 0; k < W; ++k) {
-          float o = (xv[u][k] - mean[k]) * sc[k] + bt[k];   // the exact expression of k_bn_apply (the backward recomputes the mask from it)
-          if (res) o += rv[u][k];
-          xv[u][k] = (relu && o < 0.f) ? 0.f : o;
+        for (int i = 0; i < W; ++i) {
+          float o = k.out(i, xv[u][i]);
+          if (res) o += rv[u][i];
+          xv[u][i] = (relu && o < 0.f) ? 0.f : o;
         }
         stv<W>(y + ru * y_ld + cg * W, xv[u]);
       }
@@ -675,35 +623,20 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(4))) void k
   const int64_t r1 = min(r0 + rows_per_block, n);
   colreduce_slab<T, 1>(x, y, dy, stats, gamma, beta, n, c, relu, r0, r1, scratch + (int64_t)blockIdx.x * 2 * c, dy_ld, y_ld);
   grid_arrive_wait(ctr, nwg);
-  {
-    __shared__ double red[kFoldSl][2][kFoldCh];
-    const int nfb = (c + kFoldCh - 1) / kFoldCh;
-    for (int fb = blockIdx.x; fb < nfb; fb += nwg) {
-      const int ch = fb * kFoldCh + (threadIdx.x % kFoldCh), part = threadIdx.x / kFoldCh;
-      double s, ss;
-      fold_sums_coh(scratch, (int)nwg, c, ch, part, s, ss, red);
-      if (part == 0 && ch < c) {
-        dbeta[ch] = (float)s; dgamma[ch] = (float)ss;
-        st_coh(sums + ch, (float)s); st_coh(sums + c + ch, (float)ss);
-      }
-      __syncthreads();
-    }
+  for (int fb = blockIdx.x; fb < (c + kFoldCh - 1) / kFoldCh; fb += nwg) {
+    fold_bwd_body<true>(scratch, fb, (int)nwg, c, dgamma, dbeta, sums);
+    __syncthreads();
   }
   grid_arrive_wait(ctr, 2 * nwg);
   grid_leave(ctr, 3 * nwg);
   const int G = c / W, RL = kNT / G;
   const int cg = threadIdx.x % G, rl = threadIdx.x / G;
   if (rl >= RL) return;
-  float mean[W], istd[W], sc[W], bt[W], gi[W], m1[W], m2[W];
+  BnBwdConsts<W> k;
+  float s[W], ss[W];
 #pragma unroll
-  for (int k = 0; k < W; ++k) {
-    const int ch = cg * W + k;
-    mean[k] = stats[ch]; istd[k] = stats[c + ch];
-    sc[k] = istd[k] * (relu == 2 ? gamma[ch] : 0.f);
-    bt[k] = relu == 2 ? beta[ch] : 0.f;
-    gi[k] = gamma[ch] * istd[k];
-    m1[k] = ld_coh(sums + ch) * inv_n; m2[k] = ld_coh(sums + c + ch) * inv_n;
-  }
+  for (int i = 0; i < W; ++i) { s[i] = ld_coh(sums + cg * W + i); ss[i] = ld_coh(sums + c + cg * W + i); }
+  k.load(stats, gamma, beta, c, cg * W, relu, inv_n, s, ss);
   constexpr int U = W == 8 ? 1 : 2;
   for (int64_t r = r1 - 1 - rl; r >= r0; r -= (int64_t)U * RL) {
     float xv[U][W], gv[U][W], yv[U][W];
@@ -722,17 +655,14 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(4))) void k
       if (ru >= r0) {
         if (relu == 1) {
 #pragma unroll
-          for (int k = 0; k < W; ++k) gv[u][k] = yv[u][k] > 0.f ? gv[u][k] : 0.f;
+          for (int i = 0; i < W; ++i) gv[u][i] = yv[u][i] > 0.f ? gv[u][i] : 0.f;
         } else if (relu == 2) {
 #pragma unroll
-          for (int k = 0; k < W; ++k) gv[u][k] = ((xv[u][k] - mean[k]) * sc[k] + bt[k]) > 0.f ? gv[u][k] : 0.f;
+          for (int i = 0; i < W; ++i) gv[u][i] = k.out(i, xv[u][i]) > 0.f ? gv[u][i] : 0.f;
         }
         if (dres) stv<W>(dres + ru * c + cg * W, gv[u]);
 #pragma unroll
-        for (int k = 0; k < W; ++k) {
-          const float xh = (xv[u][k] - mean[k]) * istd[k];
-          xv[u][k] = gi[k] * (gv[u][k] - m1[k] - xh * m2[k]);
-        }
+        for (int i = 0; i < W; ++i) xv[u][i] = k.template dx<kDxFma<T, kBwdFused>>(i, xv[u][i], gv[u][i]);
         stv<W>(dx + ru * c + cg * W, xv[u]);
       }
     }
@@ -780,6 +710,34 @@ __device__ inline void fold_in_block(const float *__restrict__ scratch, int npar
   }
 }
 
+// One norm's forward constants for this thread.  FOLD: from the workgroup's own fold of p.scratch (workgroup 0 also writes what
+// k_fold_fwd writes); otherwise from the saved statistics.  Every thread of the workgroup calls it (fold_in_block synchronises).
+template <typename T, bool FOLD>
+__device__ __forceinline__ void fwd_consts(const PairFwdNorm<T> &p, int64_t n, int c, int nparts, int G, int RL, int cg, int rl, BnFwdConsts<Width<T>::V> &k) {
+  constexpr int W = Width<T>::V;
+  if constexpr (FOLD) {
+    double t0[W], t1[W];
+    fold_in_block<W>(p.scratch, nparts, c, G, RL, cg, rl, t0, t1);
+    if (rl < RL) {
+      float piv[W];
+      if (n > 0) ldv<W>(p.x + cg * W, piv);          // the pivot of k_colreduce<T, 0>: row 0
+#pragma unroll
+      for (int i = 0; i < W; ++i) {
+        const int ch = cg * W + i;
+        const BnMoments m = bn_finish(t0[i], t1[i], n, n > 0 ? (double)piv[i] : 0.0, p.eps);
+        k.set(i, (float)m.mean, m.istd, p.gamma[ch], p.beta[ch]);
+        if (blockIdx.x == 0 && rl == 0) {
+          p.stats[ch] = (float)m.mean; p.stats[c + ch] = m.istd;
+          if (p.running_mean) bn_update_running(p.running_mean[ch], p.running_var[ch], p.momentum, m, n);
+        }
+      }
+    }
+    count_batch(p.nbt);
+  } else {
+    if (rl < RL) k.template load<Mem<false>>(p.stats, p.gamma, p.beta, c, cg * W);
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(kNT) void k_bn_apply_fold(const T *__restrict__ x, const T *__restrict__ res, int64_t n, int c,
                                                        const float *__restrict__ gamma, const float *__restrict__ beta, float eps,
@@ -790,55 +748,42 @@ __global__ __launch_bounds__(kNT) void k_bn_apply_fold(const T *__restrict__ x, 
   constexpr int W = Width<T>::V;
   const int G = c / W, RL = kNT / G;
   const int cg = threadIdx.x % G, rl = threadIdx.x / G;
-  double t0[W], t1[W];
-  fold_in_block<W>(scratch, nparts, c, G, RL, cg, rl, t0, t1);
+  BnFwdConsts<W> k;
+  fwd_consts<T, true>({x, gamma, beta, running_mean, running_var, nbt, stats, scratch, eps, momentum}, n, c, nparts, G, RL, cg, rl, k);
   if (rl >= RL) return;
-  float piv[W], sc[W], mean[W], bt[W];
-  if (n > 0) ldv<W>(x + cg * W, piv);          // the pivot of k_colreduce<T, 0>: row 0
+  apply_rows<T, false>(x, res, n, c, k, relu, y, y_ld, cg, rl, RL);
+}
+
+// one norm of a backward pair as the kernels see it
+template <typename T> struct PairBwdNorm {
+  const T *x;
+  const float *gamma, *beta, *stats;
+  const float *scratch;     // partial rows (FOLD)
+  const float *sums;        // folded sums (three launches)
+  float *dgamma, *dbeta;    // FOLD: workgroup 0 writes them
+  T *dx;
+};
+// One norm's backward constants for this thread.  FOLD: the sums from the workgroup's own fold of p.scratch, rounded as k_fold_bwd
+// stores them (workgroup 0 also writes dgamma / dbeta); otherwise from p.sums.  Every thread of the workgroup calls it.
+template <typename T, bool FOLD>
+__device__ __forceinline__ void bwd_consts(const PairBwdNorm<T> &p, int c, int nparts, float inv_n, int relu, int G, int RL, int cg, int rl,
+                                  BnBwdConsts<Width<T>::V> &k) {
+  constexpr int W = Width<T>::V;
+  double t0[W], t1[W];
+  if constexpr (FOLD) fold_in_block<W>(p.scratch, nparts, c, G, RL, cg, rl, t0, t1);
+  if (rl >= RL) return;
+  float s[W], ss[W];
 #pragma unroll
-  for (int k = 0; k < W; ++k) {
-    const int ch = cg * W + k;
-    const double dm = n > 0 ? t0[k] / (double)n : 0.0;
-    double var = n > 0 ? t1[k] / (double)n - dm * dm : 0.0;
-    if (var < 0.0) var = 0.0;
-    const double m = (n > 0 ? (double)piv[k] : 0.0) + dm;
-    const float mf = (float)m, isf = (float)(1.0 / sqrt(var + (double)eps));
-    mean[k] = mf; sc[k] = isf * gamma[ch]; bt[k] = beta[ch];
-    if (blockIdx.x == 0 && rl == 0) {
-      stats[ch] = mf; stats[c + ch] = isf;
-      if (running_mean) {
-        const double unb = n > 1 ? var * (double)n / (double)(n - 1) : var;
-        running_mean[ch] = (float)((1.0 - momentum) * running_mean[ch] + momentum * m);
-        running_var[ch] = (float)((1.0 - momentum) * running_var[ch] + momentum * unb);
-      }
+  for (int i = 0; i < W; ++i) {
+    const int ch = cg * W + i;
+    if constexpr (FOLD) {
+      s[i] = (float)t0[i]; ss[i] = (float)t1[i];
+      if (blockIdx.x == 0 && rl == 0) { p.dbeta[ch] = s[i]; p.dgamma[ch] = ss[i]; }
+    } else {
+      s[i] = p.sums[ch]; ss[i] = p.sums[c + ch];
     }
   }
-  if (nbt && blockIdx.x == 0 && threadIdx.x == 0) *nbt += 1;
-  const int64_t stride = (int64_t)gridDim.x * RL;
-  for (int64_t r = (int64_t)blockIdx.x * RL + rl; r < n; r += 2 * stride) {
-    const int64_t r2 = r + stride;
-    const bool two = r2 < n;
-    float xa[W], xb[W], ra[W], rb[W];
-    ldv<W>(x + r * c + cg * W, xa);
-    if (two) ldv<W>(x + r2 * c + cg * W, xb);
-    if (res) { ldv<W>(res + r * c + cg * W, ra); if (two) ldv<W>(res + r2 * c + cg * W, rb); }
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-      float o = (xa[k] - mean[k]) * sc[k] + bt[k];   // the exact expression of k_bn_apply (the backward recomputes the mask from it)
-      if (res) o += ra[k];
-      xa[k] = (relu && o < 0.f) ? 0.f : o;
-    }
-    stv<W>(y + r * y_ld + cg * W, xa);
-    if (two) {
-#pragma unroll
-      for (int k = 0; k < W; ++k) {
-        float o = (xb[k] - mean[k]) * sc[k] + bt[k];
-        if (res) o += rb[k];
-        xb[k] = (relu && o < 0.f) ? 0.f : o;
-      }
-      stv<W>(y + r2 * y_ld + cg * W, xb);
-    }
-  }
+  k.load(p.stats, p.gamma, p.beta, c, cg * W, relu, inv_n, s, ss);
 }
 
 template <typename T>
@@ -851,44 +796,10 @@ __global__ __launch_bounds__(kNT) void k_bn_bwd_apply_fold(const T *__restrict__
   constexpr int W = Width<T>::V;
   const int G = c / W, RL = kNT / G;
   const int cg = threadIdx.x % G, rl = threadIdx.x / G;
-  double t0[W], t1[W];
-  fold_in_block<W>(scratch, nparts, c, G, RL, cg, rl, t0, t1);
+  BnBwdConsts<W> k;
+  bwd_consts<T, true>({x, gamma, beta, stats, scratch, nullptr, dgamma, dbeta, dx}, c, nparts, inv_n, relu, G, RL, cg, rl, k);
   if (rl >= RL) return;
-  float mean[W], istd[W], sc[W], bt[W], gi[W], m1[W], m2[W];
-#pragma unroll
-  for (int k = 0; k < W; ++k) {
-    const int ch = cg * W + k;
-    const float s = (float)t0[k], ss = (float)t1[k];      // what k_fold_bwd stores (and k_bn_bwd_apply then reads)
-    if (blockIdx.x == 0 && rl == 0) { dbeta[ch] = s; dgamma[ch] = ss; }
-    mean[k] = stats[ch]; istd[k] = stats[c + ch];
-    sc[k] = istd[k] * (relu == 2 ? gamma[ch] : 0.f);
-    bt[k] = relu == 2 ? beta[ch] : 0.f;
-    gi[k] = gamma[ch] * istd[k];
-    m1[k] = s * inv_n; m2[k] = ss * inv_n;
-  }
-  const int64_t stride = (int64_t)gridDim.x * RL;
-  for (int64_t r = (int64_t)blockIdx.x * RL + rl; r < n; r += stride) {
-    const int64_t o = r * c + cg * W;
-    float xv[W], gv[W];
-    ldv<W>(x + o, xv);
-    ldv<W>(dy + r * dy_ld + cg * W, gv);
-    if (relu == 1) {
-      float yv[W];
-      ldv<W>(y + r * y_ld + cg * W, yv);
-#pragma unroll
-      for (int k = 0; k < W; ++k) gv[k] = yv[k] > 0.f ? gv[k] : 0.f;
-    } else if (relu == 2) {
-#pragma unroll
-      for (int k = 0; k < W; ++k) gv[k] = ((xv[k] - mean[k]) * sc[k] + bt[k]) > 0.f ? gv[k] : 0.f;  // same expression as k_bn_apply
-    }
-    if (dres) stv<W>(dres + o, gv);
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-      const float xh = (xv[k] - mean[k]) * istd[k];
-      xv[k] = gi[k] * (gv[k] - m1[k] - xh * m2[k]);
-    }
-    stv<W>(dx + o, xv);
-  }
+  bwd_apply_rows<T, false, kDxFma<T, kBwdFold>>(x, y, dy, n, c, k, relu, dx, dres, dy_ld, y_ld, cg, rl, RL);
 }
 
 // ------------------------------------------------------------------------------------------------ two norms, shared passes
@@ -898,64 +809,27 @@ __global__ __launch_bounds__(kNT) void k_bn_bwd_apply_fold(const T *__restrict__
 // once per step -- statistics of both norms in one launch, one fold launch (blockIdx.y = the norm), one apply -- 5 passes forward
 // and 10 backward.  Every per-element expression and every summation order is the single kernels': results are bit-identical.
 // FOLD: the `fold` path -- every workgroup folds both norms' partial rows itself, as k_bn_apply_fold / k_bn_bwd_apply_fold do.
-template <typename T, bool FOLD>
-__device__ inline void pair_fwd_consts(const PairFwdNorm<T> &p, int64_t n, int c, int nparts, int G, int RL, int cg, int rl,
-                                       float (&mean)[Width<T>::V], float (&sc)[Width<T>::V], float (&bt)[Width<T>::V]) {
-  constexpr int W = Width<T>::V;
-  if constexpr (FOLD) {
-    double t0[W], t1[W];
-    fold_in_block<W>(p.scratch, nparts, c, G, RL, cg, rl, t0, t1);
-    if (rl < RL) {
-      float piv[W];
-      if (n > 0) ldv<W>(p.x + cg * W, piv);          // the pivot of k_colreduce<T, 0>: row 0
-#pragma unroll
-      for (int k = 0; k < W; ++k) {
-        const int ch = cg * W + k;
-        const double dm = n > 0 ? t0[k] / (double)n : 0.0;
-        double var = n > 0 ? t1[k] / (double)n - dm * dm : 0.0;
-        if (var < 0.0) var = 0.0;
-        const double m = (n > 0 ? (double)piv[k] : 0.0) + dm;
-        const float mf = (float)m, isf = (float)(1.0 / sqrt(var + (double)p.eps));
-        mean[k] = mf; sc[k] = isf * p.gamma[ch]; bt[k] = p.beta[ch];
-        if (blockIdx.x == 0 && rl == 0) {
-          p.stats[ch] = mf; p.stats[c + ch] = isf;
-          if (p.running_mean) {
-            const double unb = n > 1 ? var * (double)n / (double)(n - 1) : var;
-            p.running_mean[ch] = (float)((1.0 - p.momentum) * p.running_mean[ch] + p.momentum * m);
-            p.running_var[ch] = (float)((1.0 - p.momentum) * p.running_var[ch] + p.momentum * unb);
-          }
-        }
-      }
-    }
-    if (p.nbt && blockIdx.x == 0 && threadIdx.x == 0) *p.nbt += 1;
-  } else {
-    if (rl < RL) {
-#pragma unroll
-      for (int k = 0; k < W; ++k) {
-        const int ch = cg * W + k;
-        sc[k] = p.stats[c + ch] * p.gamma[ch];
-        mean[k] = p.stats[ch];
-        bt[k] = p.beta[ch];
-      }
-    }
-  }
-}
 
 // y = relu?(bn_a(xa) + stored(bn_b(xb))); res (may be NULL) = bn_b(xb), the branch output the single calls materialise
 template <typename T, bool FOLD>
 __global__ __launch_bounds__(kNT) void k_bn_apply_pair(PairFwdNorm<T> a, PairFwdNorm<T> b, int64_t n, int c, int nparts, int relu,
                                                        T *__restrict__ y, int64_t y_ld, T *__restrict__ res) {
-  // the single kernels' arithmetic, spelled out: the compiler contracts (x - mean) * sc + bt to one fma in every instance of
-  // k_bn_apply / k_bn_apply_fold, and what it contracts in a kernel with two norms in flight is its own choice otherwise
-#pragma clang fp contract(off)
   constexpr int W = Width<T>::V;
   const int G = c / W, RL = kNT / G;
   const int cg = threadIdx.x % G, rl = threadIdx.x / G;
-  float sca[W], ma[W], bta[W], scb[W], mb[W], btb[W];
-  pair_fwd_consts<T, FOLD>(a, n, c, nparts, G, RL, cg, rl, ma, sca, bta);
+  BnFwdConsts<W> ka, kb;
+  fwd_consts<T, FOLD>(a, n, c, nparts, G, RL, cg, rl, ka);
   if constexpr (FOLD) __syncthreads();             // fold_in_block's LDS is read by the first fold until here
-  pair_fwd_consts<T, FOLD>(b, n, c, nparts, G, RL, cg, rl, mb, scb, btb);
+  fwd_consts<T, FOLD>(b, n, c, nparts, G, RL, cg, rl, kb);
   if (rl >= RL) return;
+  auto finish = [&](float (&xa)[W], float (&xb)[W]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+      xb[i] = kb.out(i, xb[i]);
+      const float o = ka.out(i, xa[i]) + stored_value<T>(xb[i]);      // the branch rounded as its store would
+      xa[i] = (relu && o < 0.f) ? 0.f : o;
+    }
+  };
   const int64_t stride = (int64_t)gridDim.x * RL;
   for (int64_t r = (int64_t)blockIdx.x * RL + rl; r < n; r += 2 * stride) {
     const int64_t r2 = r + stride;
@@ -964,62 +838,14 @@ __global__ __launch_bounds__(kNT) void k_bn_apply_pair(PairFwdNorm<T> a, PairFwd
     ldv<W>(a.x + r * c + cg * W, xa);
     ldv<W>(b.x + r * c + cg * W, xb);
     if (two) { ldv<W>(a.x + r2 * c + cg * W, xa2); ldv<W>(b.x + r2 * c + cg * W, xb2); }
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-      xb[k] = __builtin_fmaf(xb[k] - mb[k], scb[k], btb[k]);     // the expressions of k_bn_apply, the branch rounded as its store would
-      float o = __builtin_fmaf(xa[k] - ma[k], sca[k], bta[k]);
-      o += stored_value<T>(xb[k]);
-      xa[k] = (relu && o < 0.f) ? 0.f : o;
-    }
+    finish(xa, xb);
     if (res) stv_nt<W>(res + r * c + cg * W, xb);
     stv_nt<W>(y + r * y_ld + cg * W, xa);
     if (two) {
-#pragma unroll
-      for (int k = 0; k < W; ++k) {
-        xb2[k] = __builtin_fmaf(xb2[k] - mb[k], scb[k], btb[k]);
-        float o = __builtin_fmaf(xa2[k] - ma[k], sca[k], bta[k]);
-        o += stored_value<T>(xb2[k]);
-        xa2[k] = (relu && o < 0.f) ? 0.f : o;
-      }
+      finish(xa2, xb2);
       if (res) stv_nt<W>(res + r2 * c + cg * W, xb2);
       stv_nt<W>(y + r2 * y_ld + cg * W, xa2);
     }
-  }
-}
-
-// one norm of a backward pair as the kernels see it
-template <typename T> struct PairBwdNorm {
-  const T *x;
-  const float *gamma, *beta, *stats;
-  const float *scratch;     // partial rows (FOLD)
-  const float *sums;        // folded sums (three launches)
-  float *dgamma, *dbeta;    // FOLD: workgroup 0 writes them
-  T *dx;
-};
-template <typename T, bool FOLD>
-__device__ inline void pair_bwd_consts(const PairBwdNorm<T> &p, int c, int nparts, float inv_n, int relu, int G, int RL, int cg, int rl,
-                                       float (&mean)[Width<T>::V], float (&istd)[Width<T>::V], float (&sc)[Width<T>::V],
-                                       float (&bt)[Width<T>::V], float (&gi)[Width<T>::V], float (&m1)[Width<T>::V],
-                                       float (&m2)[Width<T>::V]) {
-  constexpr int W = Width<T>::V;
-  double t0[W], t1[W];
-  if constexpr (FOLD) fold_in_block<W>(p.scratch, nparts, c, G, RL, cg, rl, t0, t1);
-  if (rl >= RL) return;
-#pragma unroll
-  for (int k = 0; k < W; ++k) {
-    const int ch = cg * W + k;
-    float s, ss;
-    if constexpr (FOLD) {
-      s = (float)t0[k]; ss = (float)t1[k];            // what k_fold_bwd stores
-      if (blockIdx.x == 0 && rl == 0) { p.dbeta[ch] = s; p.dgamma[ch] = ss; }
-    } else {
-      s = p.sums[ch]; ss = p.sums[c + ch];
-    }
-    mean[k] = p.stats[ch]; istd[k] = p.stats[c + ch];
-    sc[k] = istd[k] * (relu == 2 ? p.gamma[ch] : 0.f);
-    bt[k] = relu == 2 ? p.beta[ch] : 0.f;
-    gi[k] = p.gamma[ch] * istd[k];
-    m1[k] = s * inv_n; m2[k] = ss * inv_n;
   }
 }
 
@@ -1029,19 +855,14 @@ template <typename T, bool FOLD>
 __global__ __launch_bounds__(kNT) void k_bn_bwd_apply_pair(PairBwdNorm<T> a, PairBwdNorm<T> b, const T *__restrict__ y,
                                                            const T *__restrict__ dy, int64_t n, int c, int nparts, float inv_n, int relu,
                                                            T *__restrict__ dres, int64_t dy_ld, int64_t y_ld) {
-  // the single kernels' arithmetic, spelled out.  In dy' - m1 - xhat * m2 the compiler contracts the last two operations to one
-  // fma in k_bn_bwd_apply<bf16> and in both k_bn_bwd_apply_fold, and not in k_bn_bwd_apply<float>; what it would choose with two
-  // norms in flight is something else again.  tests/test_gpu_norm_pair.py holds each instance to its single kernel bit for bit.
-#pragma clang fp contract(off)
-  constexpr bool kFma = FOLD || sizeof(T) == 2;
+  constexpr BwdKernel kAs = FOLD ? kBwdFold : kBwdThree;      // the single kernel this instance stands for
   constexpr int W = Width<T>::V;
   const int G = c / W, RL = kNT / G;
   const int cg = threadIdx.x % G, rl = threadIdx.x / G;
-  float mean[W], istd[W], sc[W], bt[W], gi[W], m1[W], m2[W];
-  float mean_b[W], istd_b[W], sc_b[W], bt_b[W], gi_b[W], m1_b[W], m2_b[W];
-  pair_bwd_consts<T, FOLD>(a, c, nparts, inv_n, relu, G, RL, cg, rl, mean, istd, sc, bt, gi, m1, m2);
+  BnBwdConsts<W> ka, kb;
+  bwd_consts<T, FOLD>(a, c, nparts, inv_n, relu, G, RL, cg, rl, ka);
   if constexpr (FOLD) __syncthreads();             // fold_in_block's LDS is read by the first fold until here
-  pair_bwd_consts<T, FOLD>(b, c, nparts, inv_n, 0, G, RL, cg, rl, mean_b, istd_b, sc_b, bt_b, gi_b, m1_b, m2_b);
+  bwd_consts<T, FOLD>(b, c, nparts, inv_n, 0, G, RL, cg, rl, kb);
   if (rl >= RL) return;
   const int64_t stride = (int64_t)gridDim.x * RL;
   for (int64_t r = (int64_t)blockIdx.x * RL + rl; r < n; r += stride) {
@@ -1054,15 +875,13 @@ __global__ __launch_bounds__(kNT) void k_bn_bwd_apply_pair(PairBwdNorm<T> a, Pai
       float yv[W];
       ldv<W>(y + r * y_ld + cg * W, yv);
 #pragma unroll
-      for (int k = 0; k < W; ++k) gv[k] = yv[k] > 0.f ? gv[k] : 0.f;
+      for (int i = 0; i < W; ++i) gv[i] = yv[i] > 0.f ? gv[i] : 0.f;
     }
     if (dres) stv_nt<W>(dres + o, gv);
 #pragma unroll
-    for (int k = 0; k < W; ++k) {
-      const float xh = (xv[k] - mean[k]) * istd[k], u = gv[k] - m1[k];
-      xv[k] = gi[k] * (kFma ? __builtin_fmaf(-xh, m2[k], u) : u - xh * m2[k]);
-      const float xhb = (xbv[k] - mean_b[k]) * istd_b[k], ub = gv[k] - m1_b[k];
-      xbv[k] = gi_b[k] * (kFma ? __builtin_fmaf(-xhb, m2_b[k], ub) : ub - xhb * m2_b[k]);
+    for (int i = 0; i < W; ++i) {
+      xv[i] = ka.template dx<kDxFma<T, kAs>>(i, xv[i], gv[i]);
+      xbv[i] = kb.template dx<kDxFma<T, kAs>>(i, xbv[i], gv[i]);
     }
     stv_nt<W>(a.dx + o, xv);
     stv_nt<W>(b.dx + o, xbv);
@@ -1278,23 +1097,29 @@ int bn_forward_t(const T *x, int64_t n, int c, const float *gamma, const float *
 // relu mode 1 with a dresidual output, paths `three` and `fold`: the reduce launch writes the masked gradient to dres while it sums,
 // and the apply launch reads it back as an unmasked dy -- y is read once and dy masked once (7 tensor passes instead of 8; the
 // value is dy or 0, exact in T, so dx and dres are what the two-mask launches give).  Knob BN_PAIR = 0: mask in both launches.
+template <typename T> struct MaskOnce {
+  T *gout;                  // where the reduce launch writes dy' (NULL: nowhere)
+  const T *y, *dy;          // what the apply launch reads, masks by (relu) ...
+  T *dres;                  // ... and writes dy' to
+  int relu;
+  int64_t dy_ld;
+};
+template <typename T> MaskOnce<T> mask_once(bool once, const T *y, const T *dy, T *dres, int relu, int64_t dy_ld, int c) {
+  if (once) return {dres, nullptr, dres, nullptr, 0, c};
+  return {nullptr, y, dy, dres, relu, dy_ld};
+}
 template <typename T>
 int bn_backward_t(const T *x, const T *y, const T *dy, int64_t n, int c, const float *gamma, const float *beta, const float *stats, int relu,
                   T *dx, T *dres, float *dgamma, float *dbeta, void *workspace, hipStream_t s, int64_t dy_ld, int64_t y_ld) {
   const NormPlan p = norm_plan(kNormBwd, n, c, dtype_of<T>(), 0, [] { return fused_resident(reinterpret_cast<const void *>(&k_bn_bwd_fused<T>)); });
   float *rows = region(workspace, p.partials), *sums = region(workspace, p.sums);
   const float inv_n = n > 0 ? 1.f / (float)n : 0.f;
-  const bool once = relu == 1 && dres && n > 0 && p.path != kNormFused && tune(T_BN_PAIR) != 0;
-  T *gout = once ? dres : nullptr;
-  const T *ay = once ? nullptr : y, *ady = once ? dres : dy;      // what the apply launch reads
-  T *adres = once ? nullptr : dres;
-  const int arelu = once ? 0 : relu;
-  const int64_t ady_ld = once ? c : dy_ld;
+  const MaskOnce<T> m = mask_once(relu == 1 && dres && n > 0 && p.path != kNormFused && tune(T_BN_PAIR) != 0, y, dy, dres, relu, dy_ld, c);
   switch (p.path) {
     case kNormFold:
-      LGS_KLAUNCH((k_colreduce<T, 1>), p.reduce_grid, kNT, 0, s, x, y, dy, stats, gamma, beta, n, c, relu, p.rows_per_block, rows, dy_ld, y_ld, gout);
-      LGS_KLAUNCH((k_bn_bwd_apply_fold<T>), p.apply_grid, kNT, 0, s, x, ay, ady, n, c, gamma, beta, stats, rows, p.fold_rows, inv_n, arelu, dx, adres, dgamma,
-                  dbeta, ady_ld, y_ld);
+      LGS_KLAUNCH((k_colreduce<T, 1>), p.reduce_grid, kNT, 0, s, x, y, dy, stats, gamma, beta, n, c, relu, p.rows_per_block, rows, dy_ld, y_ld, m.gout);
+      LGS_KLAUNCH((k_bn_bwd_apply_fold<T>), p.apply_grid, kNT, 0, s, x, m.y, m.dy, n, c, gamma, beta, stats, rows, p.fold_rows, inv_n, m.relu, dx, m.dres, dgamma,
+                  dbeta, m.dy_ld, y_ld);
       break;
     case kNormFused: {
       unsigned *ctr = fused_counter(s);
@@ -1304,9 +1129,9 @@ int bn_backward_t(const T *x, const T *y, const T *dy, int64_t n, int c, const f
       break;
     }
     default:
-      LGS_KLAUNCH((k_colreduce<T, 1>), p.reduce_grid, kNT, 0, s, x, y, dy, stats, gamma, beta, n, c, relu, p.rows_per_block, rows, dy_ld, y_ld, gout);
+      LGS_KLAUNCH((k_colreduce<T, 1>), p.reduce_grid, kNT, 0, s, x, y, dy, stats, gamma, beta, n, c, relu, p.rows_per_block, rows, dy_ld, y_ld, m.gout);
       LGS_KLAUNCH(k_fold_bwd, p.fold_grid, 256, 0, s, rows, p.fold_rows, c, dgamma, dbeta, sums);
-      if (p.apply_grid) LGS_KLAUNCH((k_bn_bwd_apply<T>), p.apply_grid, kNT, 0, s, x, ay, ady, n, c, gamma, beta, stats, sums, inv_n, arelu, dx, adres, ady_ld,
+      if (p.apply_grid) LGS_KLAUNCH((k_bn_bwd_apply<T>), p.apply_grid, kNT, 0, s, x, m.y, m.dy, n, c, gamma, beta, stats, sums, inv_n, m.relu, dx, m.dres, m.dy_ld,
                                     (const float *)nullptr, y_ld);
   }
   LGS_HIP(hipGetLastError());
@@ -1412,20 +1237,16 @@ int bn_backward_pair_t(const PairBwdNorm<T> &a0, const PairBwdNorm<T> &b0, const
   a.scratch = rows_a; b.scratch = rows_b;
   const float inv_n = 1.f / (float)n;
   // the masked gradient, where the caller wants it, is written by the reduce launch and read back by the apply (see bn_backward_t)
-  const bool once = relu == 1 && dres;
+  const MaskOnce<T> m = mask_once(relu == 1 && dres, y, dy, dres, relu, dy_ld, c);
   LGS_KLAUNCH((k_colreduce_pair<T, 1>), q.reduce_grid, kNT, 0, s, a.x, y, dy, a.stats, a.gamma, a.beta, n, c, relu, q.rows_per_block, rows_a, dy_ld,
-              y_ld, once ? dres : (T *)nullptr, b.x, b.stats, rows_b);
-  const T *ay = once ? nullptr : y, *ady = once ? dres : dy;
-  T *adres = once ? nullptr : dres;
-  const int arelu = once ? 0 : relu;
-  const int64_t ady_ld = once ? c : dy_ld;
+              y_ld, m.gout, b.x, b.stats, rows_b);
   if (q.path == kNormFold) {
-    LGS_KLAUNCH((k_bn_bwd_apply_pair<T, true>), q.apply_grid, kNT, 0, s, a, b, ay, ady, n, c, q.fold_rows, inv_n, arelu, adres, ady_ld, y_ld);
+    LGS_KLAUNCH((k_bn_bwd_apply_pair<T, true>), q.apply_grid, kNT, 0, s, a, b, m.y, m.dy, n, c, q.fold_rows, inv_n, m.relu, m.dres, m.dy_ld, y_ld);
   } else {
     float *sums_a = region(workspace, q.sums_a), *sums_b = region(workspace, q.sums_b);
     a.sums = sums_a; b.sums = sums_b;
     LGS_KLAUNCH(k_fold_bwd_pair, dim3(q.fold_grid, 2), 256, 0, s, rows_a, rows_b, q.fold_rows, c, a.dgamma, a.dbeta, sums_a, b.dgamma, b.dbeta, sums_b);
-    LGS_KLAUNCH((k_bn_bwd_apply_pair<T, false>), q.apply_grid, kNT, 0, s, a, b, ay, ady, n, c, q.fold_rows, inv_n, arelu, adres, ady_ld, y_ld);
+    LGS_KLAUNCH((k_bn_bwd_apply_pair<T, false>), q.apply_grid, kNT, 0, s, a, b, m.y, m.dy, n, c, q.fold_rows, inv_n, m.relu, m.dres, m.dy_ld, y_ld);
   }
   LGS_HIP(hipGetLastError());
   return 0;
