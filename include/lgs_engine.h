@@ -331,6 +331,11 @@ typedef struct lgs_conv_plan_info {
   lgs_pack_desc pack_desc;
 } lgs_conv_plan_info;
 int lgs_debug_conv_plan(const lgs_conv_plan_query *q, lgs_conv_plan_info *out);
+/* lgs_debug_conv_gather_residency: how many workgroups of a bf16 k_conv_gather instance the GPU holds per CU
+ * (hipOccupancyMaxActiveBlocksPerMultiprocessor; needs a GPU).  tile_id 7 with scl = 1 / 2 / 3 chunks per walked slab, or tile_id 2
+ * with 3 / 4; bn_stats = 1: the instance with the BatchNorm statistics epilogue (what a launch with statistics, and every launch
+ * under CONV_LEAN_EPI=0, runs), 0: the one without.  A NEW SYMBOL ONLY: LGS_ABI_VERSION stays 18. */
+int lgs_debug_conv_gather_residency(int tile_id, int scl, int bn_stats, int *workgroups_per_cu);
 
 /* lgs_debug_wgrad_plan (ABI 16): the same for lgs_conv_wgrad -- which kernel serves the call, its launch parameters and workspace
  * regions, and what lgs_conv_workspace_bytes(op 2) / lgs_conv_wgrad_supports_stride answer on that map

@@ -41,7 +41,7 @@ enum Tune {
   T_BN_FOLD, T_BN_FOLD_MAX_MB, T_BN_FOLD_PARTS, T_BN_FOLD_GRID, T_FP32_SPLIT, T_BLOCK_WGRAD_LATE, T_WGRAD_F32_LDS, T_WIDE_SCHED, T_HEAD_TILE, T_POINTWISE,
   T_INSTANCE_NORM, T_METRICS_BLOCKS, T_SUPCON_FUSED, T_BN_PAIR, T_MAP_WINDOW_SORT, T_MAP_BLOCK_DIR,
   T_MAP_PERMUTE_LDS, T_MAP_PERMUTE_GROUP, T_MAP_OWN_SORTS, T_MAP_CHILD_ROUNDS, T_CONV_SLAB_TRIM, T_CONV_ROW_TRIM,
-  T_NEAREST_MAX_RING, T_INST_EVAL_FUSED,
+  T_NEAREST_MAX_RING, T_INST_EVAL_FUSED, T_CONV_LEAN_EPI,
   T_COUNT
 };
 int64_t tune(Tune t);                                                   // current value (environment LGS_<NAME> at start, lgs_tuning_set later)
@@ -53,6 +53,21 @@ void dispatch_hit(int site);
     static const int _lgs_site = lgs::dispatch_site(#kernel, __PRETTY_FUNCTION__);               \
     lgs::dispatch_hit(_lgs_site);                                                                \
     hipLaunchKernelGGL(kernel, __VA_ARGS__);                                                     \
+  } while (0)
+
+// a launch of `kernel` counted at the site of `site_kernel`: an instance of the same tile and walk that the site names do not tell
+// apart (they are what tests and profiles key on); the caller counts which one ran with LGS_COUNT
+#define LGS_KLAUNCH_AS(site_kernel, kernel, ...)                                                 \
+  do {                                                                                           \
+    static const int _lgs_site = lgs::dispatch_site(#site_kernel, __PRETTY_FUNCTION__);          \
+    lgs::dispatch_hit(_lgs_site);                                                                \
+    hipLaunchKernelGGL(kernel, __VA_ARGS__);                                                     \
+  } while (0)
+// a counter of its own among the launch sites (no kernel): `text` as it stands
+#define LGS_COUNT(text)                                                                          \
+  do {                                                                                           \
+    static const int _lgs_site = lgs::dispatch_site(text, nullptr);                              \
+    lgs::dispatch_hit(_lgs_site);                                                                \
   } while (0)
 
 constexpr int kPadRows = 256;  // every position array is padded to a multiple of this

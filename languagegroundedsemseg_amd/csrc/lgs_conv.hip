@@ -241,8 +241,23 @@ template <> __device__ inline float sq16<bf16_t>(const u32x4 &f, float s) {
 // Tile: WM x WN waves; each wave owns RB*32 positions x NCB*32 output channels.
 // SCL = chunks FETCHED AND STAGED per slab (see below); ROW1 = the gathered rows are one 16-byte piece wide (conv0's padded
 // colour rows): only the t = 0 gather is issued, the fragments of the pieces beyond the row are zero registers.
-template <typename T, int RB, int NCB, int WM, int WN, int SC, int D, int EPI = 0, int SCL = SC, bool ROW1 = false>
-__global__ __launch_bounds__(WM *WN * 64) void k_conv_gather(View v, const T *__restrict__ in, int cin_real, int nc,
+// BN = the instance carries the BatchNorm statistics epilogue (BnEpi::partial).  The epilogue's vst[32 * NCB] butterfly is the
+// register peak of every instance that has it, although it sits behind a kernel-uniform branch no default launch takes: tile 7
+// is allocated 204 registers with it and 164 without (137 where it is built for three waves per SIMD).  launch_gather runs the BN instance exactly when a launch has `partial`
+// (and for every launch under CONV_LEAN_EPI=0, which is the kernel as it was before the split); all else runs BN = false.
+// ONEBUF = ONE weight slab in LDS instead of two: the next slab still waits in registers while this one is multiplied, but it
+// is staged between two barriers at the slab's end instead of beside the MFMAs.  For the walk whose two slabs cost the CU a
+// workgroup (tile 7, one slab of three chunks: 62 KB -> 38 KB).
+template <typename T, int RB, int NCB, int WM, int WN, int SC, int D, int EPI, int SCL, bool BN, bool ONEBUF>
+constexpr int gather_waves_per_simd() {
+  // The bf16 128 x 128 tile without the statistics epilogue is BUILT for three workgroups per CU (one wave of each per SIMD):
+  // 168 registers at most; 30 / 46 KB of LDS on its 1- and 2-chunk walks, 38 KB on the 3-chunk walk with one slab buffer (with
+  // two it holds 62 KB: two workgroups, nothing stated).  0 = nothing stated.
+  return (sizeof(T) == 2 && EPI == 0 && !BN && RB == 1 && NCB == 4 && WM == 4 && WN == 1 && SC == 2 && D == 4 && (SCL <= 2 || ONEBUF)) ? 3 : 0;
+}
+template <typename T, int RB, int NCB, int WM, int WN, int SC, int D, int EPI = 0, int SCL = SC, bool ROW1 = false, bool BN = (EPI == 0),
+          bool ONEBUF = false>
+__global__ __launch_bounds__(WM *WN * 64, (gather_waves_per_simd<T, RB, NCB, WM, WN, SC, D, EPI, SCL, BN, ONEBUF>())) void k_conv_gather(View v, const T *__restrict__ in, int cin_real, int nc,
                                                              const u32x4 *__restrict__ wp, int nb_total,
                                                              int ncp, int nbp,
                                                              T *__restrict__ out, int cout_real,
@@ -262,6 +277,8 @@ __global__ __launch_bounds__(WM *WN * 64) void k_conv_gather(View v, const T *__
   // (launch_gather picks it; SCL = SC is the walk of the image's own slabs, padding included).
   static_assert(SCL >= 1 && (EPI == 0 || SCL == SC), "the CLIP epilogue parks its similarity tile in the weight LDS of the image's own slabs");
   static_assert(!ROW1 || EPI == 0, "the one-piece row is a convolution input");
+  static_assert(!BN || EPI == 0, "BatchNorm statistics are a convolution epilogue");
+  static_assert(!ONEBUF || (EPI == 0 && !BN), "both epilogues that use the weight LDS count on two slabs of it");
   constexpr int EPL = Tr<T>::EPL, LD = Tr<T>::LD, WLD = Tr<T>::WLD;
   constexpr int NT = WM * WN * 64;
   constexpr int TM = WM * RB * 32;
@@ -269,8 +286,8 @@ __global__ __launch_bounds__(WM *WN * 64) void k_conv_gather(View v, const T *__
   constexpr int WCH = WB * WLD * 64;           // uint4 per chunk
   constexpr int SLAB = SCL * WCH;              // uint4 per slab
   constexpr int WR = (SLAB + NT - 1) / NT;     // staging registers per thread
-  __shared__ u32x4 lds[2][SLAB];
-  static_assert(EPI != 0 || WM * 2 * WB * 32 * 4 <= 2 * SLAB * 16, "the statistics epilogue folds the waves through the weight LDS");
+  __shared__ u32x4 lds[ONEBUF ? 1 : 2][SLAB];
+  static_assert(!BN || WM * 2 * WB * 32 * 4 <= 2 * SLAB * 16, "the statistics epilogue folds the waves through the weight LDS");
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
@@ -303,7 +320,7 @@ __global__ __launch_bounds__(WM *WN * 64) void k_conv_gather(View v, const T *__
   } else if (v.tile_k) {
     kw_single = v.tile_k[pos_wg / 64];
     if (kw_single < 0) {        // padding group: nothing to write (its statistics row is all zeros)
-      if constexpr (EPI == 0) {
+      if constexpr (BN) {
         if (be.partial != nullptr)
           for (int e = tid; e < 2 * WB * 32; e += NT) {
             const int st = e / (WB * 32), ch = nb_wg * 32 + e % (WB * 32);
@@ -560,9 +577,17 @@ __global__ __launch_bounds__(WM *WN * 64) void k_conv_gather(View v, const T *__
   act[D - 1] = 0;
   // at the end of a slab publish the prefetched next slab and cross one barrier
   auto slab_end = [&]() __attribute__((always_inline)) {
-    if (wnext) wstage(buf ^ 1, wreg);
-    __syncthreads();
-    buf ^= 1;
+    if constexpr (ONEBUF) {
+      if (wnext) {           // workgroup-uniform.  (After the last slab nobody touches the weight LDS again: no barrier.)
+        __syncthreads();     // every wave has multiplied the slab that is overwritten now
+        wstage(0, wreg);
+        __syncthreads();
+      }
+    } else {
+      if (wnext) wstage(buf ^ 1, wreg);
+      __syncthreads();
+      buf ^= 1;
+    }
     cc = 0;
     if (wnext) {
       ncs = min(SCL, nc - pslab * SCL);
@@ -758,7 +783,7 @@ __global__ __launch_bounds__(WM *WN * 64) void k_conv_gather(View v, const T *__
     }
   }
 stats:
-  if constexpr (EPI == 0) {
+  if constexpr (BN) {
     if (be.partial != nullptr) {   // kernel-uniform
       // ---- BatchNorm statistics of this workgroup's rows.  Lane (vx, h) holds, per row block, the 16 NCB channels
       // nb*32 + 8q + 4h + i of voxel vx: sum the row blocks in registers, then a HALVING butterfly over the 32 lanes of a
@@ -845,7 +870,7 @@ constexpr GatherCfg tile_of(int id, bool f32) {
     case 4: return {4, f32 ? 2 : 4, 1, 64};
     case 5: return {5, f32 ? 2 : 4, 2, 64};
     case 6: return {6, f32 ? 1 : 2, 7, 128};
-    case 7: return {7, 2, 4, 128};               // ids 7 .. 13, 16, 17: bf16 only.  128 positions x 128 channels (32 x 128 per wave), 2 workgroups / CU
+    case 7: return {7, 2, 4, 128};               // ids 7 .. 13, 16, 17: bf16 only.  128 positions x 128 channels (32 x 128 per wave), 3 workgroups / CU (2 with the statistics epilogue)
     case 8: return {8, 4, 2, 128};
     case 9: return {9, 4, 4, 64};
     case 10: return {10, 4, 2, 64};
@@ -874,7 +899,10 @@ int gather_id(const View &v, int nb_total) {
     if (!kF32 && tune(T_CONV_WIDE) != 0 && (nb_total % 8 == 0 || nb_total >= 16) && !(v.KS == 1 && v.nbr == nullptr && nb_total < 16))
       return 17;
     if (!kF32 && nb_total % 8 == 0) return 16;
-    return kF32 ? 3 : 7;                // bf16: 128-position tiles, 4 column blocks per wave at 2 waves/SIMD (204 registers)
+    // bf16: 128-position tiles, 4 column blocks per wave.  The main loop needs 137 - 147 registers: three waves per SIMD, i.e. three
+    // workgroups per CU; the 204 registers and two workgroups recorded here before were the BatchNorm statistics epilogue's, which
+    // only the instance of a launch that writes statistics carries now (k_conv_gather's BN flag, CONV_LEAN_EPI)
+    return kF32 ? 3 : 7;
   }
   if (nb_total == 1) return 4;
   if (kF32) return 5;
@@ -997,8 +1025,10 @@ inline int trimmed_slab(int tile_id, int sc, int nc, int gc) {
   const int64_t knob = tune(T_CONV_SLAB_TRIM);
   if (knob == 0 || gc != nc || nc > 8 || !(tile_id <= 2 || tile_id == 7)) return 0;
   if (nc < sc) return nc;
-  // tile 7 walks three chunks on 2-chunk slabs: ONE slab of three (62 KB of LDS at the tile's occupancy of 2: half the slab
-  // barriers), or with the knob at 2 three slabs of one
+  // tile 7 walks three chunks on 2-chunk slabs: ONE slab of three, or with the knob at 2 three slabs of one.  Two slabs of three in
+  // LDS are 62 KB, which fits twice per CU: the instance with the statistics epilogue (two per CU by its registers anyway) keeps
+  // them, the one without holds ONE slab (ONEBUF, 38 KB) and runs three per CU.  Level-0 96 -> 128 dgrad, stand-alone: 692 us with
+  // the epilogue, 638 us one slab of three at three per CU, 647 us three slabs of one at four (profiles/conv_lean_epilogue.txt)
   if (tile_id == 7 && nc == 3) return knob == 2 ? 1 : 3;
   if (nc % sc == 0) return 0;              // whole slabs: nothing to trim
   for (int d = sc - 1; d > 1; --d)         // the largest divisor of nc below sc; none (5, 7): the tile's own instance
@@ -1006,13 +1036,19 @@ inline int trimmed_slab(int tile_id, int sc, int nc, int gc) {
   return 0;
 }
 // launch-site text of a trimmed instance: "SlabWalk<SCL,ROW1>::k_conv_gather<T,...>", the tile's own text with the walk in front
-template <int SCL, bool ROW1>
+template <int SCL, bool ROW1, bool BN = true, bool ONEBUF = false>
 struct SlabWalk {
   template <typename T, int RB, int NCB, int WM, int WN, int SC, int D>
-  static constexpr auto k_conv_gather = &lgs::k_conv_gather<T, RB, NCB, WM, WN, SC, D, 0, SCL, ROW1>;
+  static constexpr auto k_conv_gather = &lgs::k_conv_gather<T, RB, NCB, WM, WN, SC, D, 0, SCL, ROW1, BN, ONEBUF>;
 };
 constexpr int kLdsPerCu = 160 * 1024;
-constexpr int gather_lds_bytes(int tm, int wb, int wld, int scl) { return 2 * scl * wb * wld * 64 * 16 + 27 * tm * 4; }
+constexpr int gather_lds_bytes(int tm, int wb, int wld, int scl, int slabs = 2) { return slabs * scl * wb * wld * 64 * 16 + 27 * tm * 4; }
+// an instance BUILT for a number of workgroups per CU (gather_waves_per_simd) must also fit that often in the CU's LDS
+template <typename T, int RB, int NCB, int WM, int WN, int SC, int D, int SCL, bool ONEBUF = false>
+constexpr bool lean_residency_fits() {
+  constexpr int w = gather_waves_per_simd<T, RB, NCB, WM, WN, SC, D, 0, SCL, false, ONEBUF>();
+  return w == 0 || (WM * WN == 4 && gather_lds_bytes(WM * RB * 32, WN * NCB, Tr<bf16_t>::WLD, SCL, ONEBUF ? 1 : 2) * w <= kLdsPerCu);
+}
 
 template <typename T>
 int launch_gather(const View &v, const ConvPlan &pl, const T *in, int cin_real, const uint4 *wp, int K, T *out, int cout_real,
@@ -1038,26 +1074,59 @@ int launch_gather(const View &v, const ConvPlan &pl, const T *in, int cin_real, 
   const BnEpi be = (bn && !split) ? *bn : BnEpi();
   const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)pl.grid_z);
   constexpr bool kF32 = (sizeof(T) == 4);
+  // THE choice of the epilogue variant: on the bf16 big-map tiles (0, 1, 2, 6, 7, 16 and their walks) a launch that writes no
+  // statistics runs the instance built without them (every dgrad, every forward without `partial`); CONV_LEAN_EPI=0, the fp32
+  // instances and the small-map tiles (whose registers the epilogue does not set: within 4 either way) run the one with them.
+  // Both are counted at the same launch site -- tile and walk are what the site names -- and the lean ones by a counter of their own.
+  // Tile 7 decides per launch: its lean instances hold three workgroups per CU instead of two, which a grid of at most two per CU
+  // cannot use -- level 3 of the 8-scene batch (256 -> 256, 308 workgroups) measured 1 % SLOWER on them and keeps the instance it
+  // had; 128 -> 128 at level 2 (633) gains 14 %, the 96 -> 128 dgrad 6 - 13 % (profiles/conv_lean_epilogue.txt section 2).
+  constexpr int64_t kTwoPerCu = 2 * 256;
+  const bool lean = !kF32 && be.partial == nullptr && tune(T_CONV_LEAN_EPI) != 0 &&
+                    (pl.tile_id != 7 || pl.grid_x * pl.grid_y * pl.grid_z > kTwoPerCu || tune(T_CONV_LEAN_EPI) == 2);
+#define LGS_COUNT_LEAN() LGS_COUNT("k_conv_gather:no_statistics_epilogue")
+#define LGS_GATHER_ARGS(WM, WN)                                                                                           \
+  grid, dim3(WM *WN * 64), 0, s, v, in, cin_real, nc, reinterpret_cast<const u32x4 *>(wp), nb_total, ncp, nbp, out, cout_real, \
+      split ? nullptr : bias, split ? zpartial : out_f32, row_scale, in_bytes, w_bytes, zstride, ClipEpi(), be, gc,       \
+      in_ld > 0 ? in_ld : cin_real
 #define LGS_LAUNCH(ID, RB, NCB, WM, WN, SC, D)                                                                            \
   do {                                                                                                                    \
     constexpr GatherCfg t = tile_of(ID, kF32);                                                                            \
     static_assert(t.sc == SC && t.wb == WN * NCB && t.tm == WM * RB * 32, "tile_of() and the launched instance disagree"); \
-    LGS_KLAUNCH((k_conv_gather<T, RB, NCB, WM, WN, SC, D>), grid, dim3(WM *WN * 64), 0, s, v, in, cin_real, nc,            \
-                       reinterpret_cast<const u32x4 *>(wp), nb_total, ncp, nbp, out, cout_real, split ? nullptr : bias,   \
-                       split ? zpartial : out_f32, row_scale, in_bytes, w_bytes, zstride, ClipEpi(), be, gc,              \
-                       in_ld > 0 ? in_ld : cin_real);                                                                     \
+    LGS_KLAUNCH((k_conv_gather<T, RB, NCB, WM, WN, SC, D>), LGS_GATHER_ARGS(WM, WN));                                      \
   } while (0)
-  // the same tile walked with SCL-chunk slabs; OCC = workgroups per CU of the tile's own instance (registers, from the ISA):
-  // the walk may not take more LDS than leaves that many
-#define LGS_LAUNCH_WALK(ID, RB, NCB, WM, WN, SC, D, SCL, ROW1, OCC)                                                       \
+  // a tile that has both epilogue variants
+#define LGS_LAUNCH_EPI(ID, RB, NCB, WM, WN, SC, D)                                                                        \
+  do {                                                                                                                    \
+    constexpr GatherCfg t = tile_of(ID, kF32);                                                                            \
+    static_assert(t.sc == SC && t.wb == WN * NCB && t.tm == WM * RB * 32, "tile_of() and the launched instance disagree"); \
+    bool ran = false;                                                                                                     \
+    if constexpr (!kF32) {                                                                                                \
+      static_assert(lean_residency_fits<T, RB, NCB, WM, WN, SC, D, SC>(), "the lean instance is built for more workgroups than its LDS admits"); \
+      if (lean) {                                                                                                         \
+        LGS_COUNT_LEAN();                                                                                                 \
+        LGS_KLAUNCH_AS((k_conv_gather<T, RB, NCB, WM, WN, SC, D>), (k_conv_gather<T, RB, NCB, WM, WN, SC, D, 0, SC, false, false>), \
+                       LGS_GATHER_ARGS(WM, WN));                                                                          \
+        ran = true;                                                                                                       \
+      }                                                                                                                   \
+    }                                                                                                                     \
+    if (!ran) LGS_KLAUNCH((k_conv_gather<T, RB, NCB, WM, WN, SC, D>), LGS_GATHER_ARGS(WM, WN));                            \
+  } while (0)
+  // the same tile walked with SCL-chunk slabs; OCC = workgroups per CU of the tile's own instance with the statistics epilogue
+  // (registers, from the ISA): the walk may not take more LDS than leaves that many.  A trailing `true`: the instance without the
+  // epilogue keeps ONE slab in LDS (ONEBUF)
+#define LGS_LAUNCH_WALK(ID, RB, NCB, WM, WN, SC, D, SCL, ROW1, OCC, ...)                                                     \
   do {                                                                                                                    \
     constexpr GatherCfg t = tile_of(ID, false);                                                                           \
     static_assert(t.sc == SC && t.wb == WN * NCB && t.tm == WM * RB * 32, "tile_of() and the launched instance disagree"); \
     static_assert(gather_lds_bytes(t.tm, t.wb, Tr<bf16_t>::WLD, SCL) * OCC <= kLdsPerCu, "the slab walk costs the tile occupancy"); \
-    LGS_KLAUNCH((SlabWalk<SCL, ROW1>::k_conv_gather<T, RB, NCB, WM, WN, SC, D>), grid, dim3(WM *WN * 64), 0, s, v, in, cin_real, nc, \
-                       reinterpret_cast<const u32x4 *>(wp), nb_total, ncp, nbp, out, cout_real, split ? nullptr : bias,   \
-                       split ? zpartial : out_f32, row_scale, in_bytes, w_bytes, zstride, ClipEpi(), be, gc,              \
-                       in_ld > 0 ? in_ld : cin_real);                                                                     \
+    static_assert(lean_residency_fits<T, RB, NCB, WM, WN, SC, D, SCL, ##__VA_ARGS__>(), "the lean instance is built for more workgroups than its LDS admits"); \
+    if (lean) {                                                                                                           \
+      LGS_COUNT_LEAN();                                                                                                   \
+      LGS_KLAUNCH_AS((SlabWalk<SCL, ROW1>::k_conv_gather<T, RB, NCB, WM, WN, SC, D>),                                      \
+                     (SlabWalk<SCL, ROW1, false, ##__VA_ARGS__>::k_conv_gather<T, RB, NCB, WM, WN, SC, D>), LGS_GATHER_ARGS(WM, WN)); \
+    } else                                                                                                                \
+      LGS_KLAUNCH((SlabWalk<SCL, ROW1>::k_conv_gather<T, RB, NCB, WM, WN, SC, D>), LGS_GATHER_ARGS(WM, WN));               \
   } while (0)
   if constexpr (!kF32) {
     const int scl = trimmed_slab(pl.tile_id, pl.sc, nc, gc);
@@ -1076,20 +1145,20 @@ int launch_gather(const View &v, const ConvPlan &pl, const T *in, int cin_real, 
       case 204: LGS_LAUNCH_WALK(2, 2, 3, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 2, false, 2); break;
       case 304: LGS_LAUNCH_WALK(2, 2, 3, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 3, false, 2); break;
       case 114: LGS_LAUNCH_WALK(7, 1, 4, 4, 1, 2, 4, 1, false, 2); break;
-      case 314: LGS_LAUNCH_WALK(7, 1, 4, 4, 1, 2, 4, 3, false, 2); break;
+      case 314: LGS_LAUNCH_WALK(7, 1, 4, 4, 1, 2, 4, 3, false, 2, true); break;
       default: done = false; break;
     }
     if (done) goto launched;
   }
   switch (pl.tile_id) {
-    case 0: LGS_LAUNCH(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
-    case 1: LGS_LAUNCH(1, 2, 2, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
-    case 2: LGS_LAUNCH(2, 2, 3, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
+    case 0: LGS_LAUNCH_EPI(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
+    case 1: LGS_LAUNCH_EPI(1, 2, 2, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
+    case 2: LGS_LAUNCH_EPI(2, 2, 3, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
     case 3: LGS_LAUNCH(3, 2, 4, 4, 1, (kF32 ? 1 : 2), (kF32 ? 2 : 3)); break;
     case 4: LGS_LAUNCH(4, 1, 1, 2, 1, (kF32 ? 2 : 4), (kF32 ? 4 : 8)); break;
-    case 6: LGS_LAUNCH(6, 1, 7, 4, 1, (kF32 ? 1 : 2), (kF32 ? 3 : 4)); break;
-    case 7: if constexpr (!kF32) LGS_LAUNCH(7, 1, 4, 4, 1, 2, 4); break;      // ids 7 .. 13, 16: bf16 only (gather_id)
-    case 16: if constexpr (!kF32) LGS_LAUNCH(16, 1, 8, 8, 1, 2, 4); break;
+    case 6: LGS_LAUNCH_EPI(6, 1, 7, 4, 1, (kF32 ? 1 : 2), (kF32 ? 3 : 4)); break;
+    case 7: if constexpr (!kF32) LGS_LAUNCH_EPI(7, 1, 4, 4, 1, 2, 4); break;      // ids 7 .. 13, 16: bf16 only (gather_id)
+    case 16: if constexpr (!kF32) LGS_LAUNCH_EPI(16, 1, 8, 8, 1, 2, 4); break;
     case 8: if constexpr (!kF32) LGS_LAUNCH(8, 1, 2, 4, 1, 4, 6); break;
     case 9: if constexpr (!kF32) LGS_LAUNCH(9, 1, 2, 2, 2, 4, 6); break;
     case 10: if constexpr (!kF32) LGS_LAUNCH(10, 1, 2, 2, 1, 4, 6); break;
@@ -1099,7 +1168,10 @@ int launch_gather(const View &v, const ConvPlan &pl, const T *in, int cin_real, 
     default: LGS_LAUNCH(5, 1, 1, 2, 2, (kF32 ? 2 : 4), (kF32 ? 4 : 8)); break;
   }
 #undef LGS_LAUNCH
+#undef LGS_LAUNCH_EPI
 #undef LGS_LAUNCH_WALK
+#undef LGS_COUNT_LEAN
+#undef LGS_GATHER_ARGS
 launched:
   if (split) {
     const int64_t n4 = zstride / 4;
@@ -1409,6 +1481,25 @@ int lgs_debug_conv_plan(const lgs_conv_plan_query *q, lgs_conv_plan_info *out) {
   out->q_bn_partial_rows = q->op == 0 ? lgs_conv_bn_partial_rows(&km, q->transposed, q->cout, q->dtype) : 0;
   out->q_can_accumulate = q->op == 1 ? lgs_conv_dgrad_can_accumulate(&km, q->transposed, q->cin, q->cout, q->dtype) : 0;
   return lgs_conv_pack_desc(&km, q->op, q->transposed, q->cin, q->cout, q->dtype, &out->pack_desc);
+}
+
+// the GPU's own count of resident workgroups per CU of a bf16 instance of tile 7 (scl 1 / 2 / 3) or tile 2 (scl 3 / 4)
+int lgs_debug_conv_gather_residency(int tile_id, int scl, int bn_stats, int *workgroups_per_cu) {
+  LGS_REQUIRE(workgroups_per_cu, "lgs_debug_conv_gather_residency: null argument");
+  const void *k = nullptr;
+#define LGS_RES(ID, SCL, ...)                                                                                               \
+  if (tile_id == ID && scl == SCL)                                                                                        \
+    k = bn_stats ? reinterpret_cast<const void *>(&k_conv_gather<bf16_t, __VA_ARGS__, 0, SCL, false, true>)               \
+                 : reinterpret_cast<const void *>(&k_conv_gather<bf16_t, __VA_ARGS__, 0, SCL, false, false, (ID == 7 && SCL == 3)>)
+  LGS_RES(7, 1, 1, 4, 4, 1, 2, 4);
+  LGS_RES(7, 2, 1, 4, 4, 1, 2, 4);
+  LGS_RES(7, 3, 1, 4, 4, 1, 2, 4);
+  LGS_RES(2, 3, 2, 3, 4, 1, 4, 4);
+  LGS_RES(2, 4, 2, 3, 4, 1, 4, 4);
+#undef LGS_RES
+  LGS_REQUIRE(k, "lgs_debug_conv_gather_residency: tile 7 with 1 / 2 / 3-chunk slabs or tile 2 with 3 / 4");
+  LGS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(workgroups_per_cu, k, 256, 0));
+  return 0;
 }
 
 int64_t lgs_clip_workspace_bytes(int c, int n_anchor, int dtype) {

@@ -128,6 +128,14 @@ const Knob kKnobs[T_COUNT] = {
                                               "and one table probe per proposal member, an LDS histogram per piece of a proposal); 0 = the torch lines CPU tensors "
                                               "take (torch.unique over the ids, one bincount over (proposal, id) pairs, torch.max / mean per proposal) -- read at call "
                                               "time.  The integer tables and the max confidences are equal (tests/test_gpu_insteval.py)"},
+    {T_CONV_LEAN_EPI, "CONV_LEAN_EPI", 1, "k_conv_gather, bf16 (A/B): 1 = a launch that writes no BatchNorm statistics (every dgrad, every forward without "
+                                          "`partial`) runs the instance built without the statistics epilogue, whose registers every instance used to be sized "
+                                          "for (tile 7: 204 -> 137 / 147 on its 2- and 3-chunk walks, three workgroups per CU instead of two, the 3-chunk walk with one weight slab in LDS); a launch with "
+                                          "`partial` runs the instance with it.  Tile 7 takes its lean instances only on a grid of more than 512 workgroups "
+                                          "(two per CU hold the rest; 256 -> 256 at level 3 measured 1 % slower on them); 2 = as 1 on every grid (tests reach "
+                                          "the instances on small maps with it).  0 = every launch runs the instance with the epilogue, the kernel as it was "
+                                          "before the split.  Same chunks, same order, same MFMAs, same stores: bit-identical "
+                                          "(profiles/conv_lean_epilogue.txt, tests/test_gpu_conv_lean_epilogue.py)"},
 };
 std::atomic<int64_t> g_val[T_COUNT];
 std::once_flag g_once;

@@ -201,7 +201,8 @@ _lib = None
 # every symbol include/lgs_engine.h declares; tests check the built library exports all of them
 EXPORTS = [
     "lgs_abi_version", "lgs_last_error",
-    "lgs_tuning_set", "lgs_tuning_get", "lgs_tuning_describe", "lgs_debug_dispatch_counts", "lgs_debug_conv_plan", "lgs_debug_wgrad_plan",
+    "lgs_tuning_set", "lgs_tuning_get", "lgs_tuning_describe", "lgs_debug_dispatch_counts", "lgs_debug_conv_plan", "lgs_debug_conv_gather_residency",
+    "lgs_debug_wgrad_plan",
     "lgs_debug_norm_plan", "lgs_debug_instnorm_plan", "lgs_debug_seg_plan", "lgs_debug_kmap_relation",
     "lgs_manager_create", "lgs_manager_destroy", "lgs_manager_insert", "lgs_manager_stride2", "lgs_manager_check",
     "lgs_manager_parent_of", "lgs_manager_map_size", "lgs_manager_get_coords", "lgs_manager_nearest", "lgs_manager_kernel_map",
@@ -287,6 +288,7 @@ def lib():
         "lgs_conv_pack_desc": [vp, ci, ci, ci, ci, ci, ctypes.POINTER(PackDesc)],
         "lgs_pack_weights_batch": [vp, ci, i64, vp],
         "lgs_debug_conv_plan": [ctypes.POINTER(ConvPlanQuery), ctypes.POINTER(ConvPlanInfo)],
+        "lgs_debug_conv_gather_residency": [ci, ci, ci, pi],
         "lgs_debug_wgrad_plan": [ctypes.POINTER(WgradPlanQuery), ctypes.POINTER(WgradPlanInfo)],
         "lgs_debug_norm_plan": [ctypes.POINTER(NormPlanQuery), ctypes.POINTER(NormPlanInfo)],
         "lgs_debug_instnorm_plan": [ctypes.POINTER(InstNormPlanQuery), ctypes.POINTER(InstNormPlanInfo)],

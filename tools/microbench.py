@@ -1,5 +1,5 @@
 """Per-op timings on the GPU (HIP events on torch's current stream) for the hot layer shapes.
-usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal | supcon | augment | paste | nearest | ap]"""
+usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal | supcon | augment | paste | nearest | ap | lean]"""
 import os
 import re
 import sys
@@ -1082,7 +1082,57 @@ def insteval():
     print("new route / get_instances: x %.1f" % (t_old / t_new))
 
 
+def lean():
+    """CONV_LEAN_EPI: k_conv_gather with and without the BatchNorm statistics epilogue (profiles/conv_lean_epilogue.txt section 2).
+    The tile-7 shapes of a Res16UNet34C step on the maps of the 8-scene batch and the 96 -> 96 control on tile 2; knob 0 / 1
+    alternating inside this process, three rounds, 20 calls after 3 warm-up calls, us per call (each call includes the op's
+    k_pack_weights launch).  Third column of the 96 -> 128 rows = knob 1 with CONV_SLAB_TRIM=2: the three-chunk reduction as three
+    1-chunk slabs; of the 256 -> 256 rows = knob 2: the lean instance on a grid of at most two workgroups per CU, which knob 1
+    leaves on the instance it had.  First the GPU's own count of resident workgroups per CU."""
+    import ctypes
+    from languagegroundedsemseg_amd import engine
+    for tile, scl in ((7, 1), (7, 2), (7, 3), (2, 3), (2, 4)):
+        got = []
+        for bn in (1, 0):
+            r = ctypes.c_int(0)
+            engine.check(engine.lib().lgs_debug_conv_gather_residency(tile, scl, bn, ctypes.byref(r)))
+            got.append(r.value)
+        print("resident workgroups / CU  tile %d, %d-chunk slabs: with the statistics epilogue %d, without %d" % (tile, scl, got[0], got[1]))
+    coords, feats, labels = make_batch(list(range(8)), n_target=150000, shift_seed=0)
+    x = ME.SparseTensor(torch.zeros(coords.shape[0], 3, device=DEV), torch.from_numpy(coords).to(DEV))
+    m, k = x.coordinate_manager, x.coordinate_map_key
+    keys = [k]
+    for _ in range(3):
+        keys.append(m.stride(keys[-1], 2))
+    # (level, K, cin, cout of the FORWARD layer, op): a dgrad reduces cout -> cin
+    cases = [(0, 27, 128, 96, "dgrad"), (0, 1, 128, 96, "dgrad"), (1, 27, 128, 96, "dgrad"), (1, 1, 128, 96, "dgrad"),
+             (2, 27, 128, 128, "fwd"), (2, 27, 128, 128, "dgrad"), (3, 27, 256, 256, "fwd"), (3, 27, 256, 256, "dgrad"),
+             (0, 27, 96, 96, "fwd"), (0, 27, 96, 96, "dgrad")]
+    print("%-34s %s" % ("shape", "   ".join("round %d: knob 0 / 1%s" % (r, "" if r else " (/ 1+trim2 | 2)") for r in range(3))))
+    for lvl, K, cin, cout, op in cases:
+        km = m.kernel_map_handle(keys[lvl], keys[lvl], 3 if K == 27 else 1)
+        n = m.size(keys[lvl])
+        f = torch.randn(n, cin, device=DEV).bfloat16()
+        g = torch.randn(n, cout, device=DEV).bfloat16()
+        w = torch.randn(K, cin, cout, device=DEV) * 0.05
+        fn = (lambda: km.conv_forward(f, w, None, False)) if op == "fwd" else (lambda: km.conv_dgrad(g, w, False))
+        settings = [dict(CONV_LEAN_EPI=0), dict(CONV_LEAN_EPI=1)] + ([dict(CONV_LEAN_EPI=1, CONV_SLAB_TRIM=2)] if (cin, cout, op) == (128, 96, "dgrad") else []) + \
+                   ([dict(CONV_LEAN_EPI=2)] if cin == 256 else [])
+        cols = []
+        for _ in range(3):
+            ts = []
+            for kn in settings:
+                with engine.tuning(**kn):
+                    ts.append(timeit(fn, 20, 3) * 1e3)
+            cols.append(" / ".join("%7.1f" % t for t in ts))
+        a, b_ = (cout, cin) if op == "dgrad" else (cin, cout)
+        print("L%d rows %7d K=%-2d %3d->%3d %-5s  %s" % (lvl, n, K, a, b_, op, "    ".join(cols)))
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "lean":
+        lean()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "insteval":
         insteval()
         sys.exit(0)
