@@ -332,10 +332,22 @@ typedef struct lgs_conv_plan_info {
 } lgs_conv_plan_info;
 int lgs_debug_conv_plan(const lgs_conv_plan_query *q, lgs_conv_plan_info *out);
 /* lgs_debug_conv_gather_residency: how many workgroups of a bf16 k_conv_gather instance the GPU holds per CU
- * (hipOccupancyMaxActiveBlocksPerMultiprocessor; needs a GPU).  tile_id 7 with scl = 1 / 2 / 3 chunks per walked slab, or tile_id 2
- * with 3 / 4; bn_stats = 1: the instance with the BatchNorm statistics epilogue (what a launch with statistics, and every launch
+ * (hipOccupancyMaxActiveBlocksPerMultiprocessor; needs a GPU).  Any instance a launch can run: a tile id with scl = chunks per
+ * walked slab (the tile's own slab length or 0: its own instance; e.g. tile_id 7 with 1 / 2 / 3, tile_id 2 with 3 / 4);
+ * bn_stats = 1: the instance with the BatchNorm statistics epilogue (what a launch with statistics, and every launch
  * under CONV_LEAN_EPI=0, runs), 0: the one without.  A NEW SYMBOL ONLY: LGS_ABI_VERSION stays 18. */
 int lgs_debug_conv_gather_residency(int tile_id, int scl, int bn_stats, int *workgroups_per_cu);
+/* lgs_debug_conv_gather_instance: which instance of k_conv_gather the launch of that plan runs (the query must plan path 4), with
+ * BatchNorm statistics (forward launches whose plan has statistic rows) or without.  No HIP call, like lgs_debug_conv_plan
+ * (tests/test_conv_instance_cpu.py holds it to a recorded table).  A NEW SYMBOL ONLY: LGS_ABI_VERSION stays 18. */
+typedef struct lgs_conv_gather_instance {
+  int tile_id;                              /* the plan's */
+  int scl, row1;                            /* chunks per walked slab, 0 = the tile's own instance; the one-piece-row walk */
+  int bn, onebuf;                           /* with the statistics epilogue; one weight slab in LDS */
+  int rb, ncb, wm, wn, sc, d;               /* the instance's <RB, NCB, WM, WN, SC, D> for the dtype */
+  char site[160];                           /* the launch site the launch is counted at (lgs_debug_dispatch_counts) */
+} lgs_conv_gather_instance;
+int lgs_debug_conv_gather_instance(const lgs_conv_plan_query *q, int with_statistics, lgs_conv_gather_instance *out);
 
 /* lgs_debug_wgrad_plan (ABI 16): the same for lgs_conv_wgrad -- which kernel serves the call, its launch parameters and workspace
  * regions, and what lgs_conv_workspace_bytes(op 2) / lgs_conv_wgrad_supports_stride answer on that map

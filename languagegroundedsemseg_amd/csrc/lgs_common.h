@@ -45,6 +45,7 @@ enum Tune {
   T_COUNT
 };
 int64_t tune(Tune t);                                                   // current value (environment LGS_<NAME> at start, lgs_tuning_set later)
+std::string dispatch_site_name(const char *kernel_text, const char *pretty_function);   // the name dispatch_site registers the site by
 int dispatch_site(const char *kernel_text, const char *pretty_function);   // registers a launch site once -> its index
 void dispatch_hit(int site);
 // every kernel launch of the engine: counted per launch site (kernel expression + template bindings of the enclosing function)
@@ -55,14 +56,6 @@ void dispatch_hit(int site);
     hipLaunchKernelGGL(kernel, __VA_ARGS__);                                                     \
   } while (0)
 
-// a launch of `kernel` counted at the site of `site_kernel`: an instance of the same tile and walk that the site names do not tell
-// apart (they are what tests and profiles key on); the caller counts which one ran with LGS_COUNT
-#define LGS_KLAUNCH_AS(site_kernel, kernel, ...)                                                 \
-  do {                                                                                           \
-    static const int _lgs_site = lgs::dispatch_site(#site_kernel, __PRETTY_FUNCTION__);          \
-    lgs::dispatch_hit(_lgs_site);                                                                \
-    hipLaunchKernelGGL(kernel, __VA_ARGS__);                                                     \
-  } while (0)
 // a counter of its own among the launch sites (no kernel): `text` as it stands
 #define LGS_COUNT(text)                                                                          \
   do {                                                                                           \
@@ -262,6 +255,22 @@ inline const char *synthetic_kmap_relation(lgs_kmap &km) {
   const char *refusal = classify_kmap(KmapRequest{true, same, !same, true, false, km.ks, 1, 1}, km.relation);
   if (!refusal) km.bwd.mirror = traits_of(km.relation).bwd_mirror ? 1 : 0;
   return refusal;
+}
+// the synthetic map itself, from the two views a debug plan query describes by plain integers: a table the view carries points at
+// one word that no planner reads.  -> synthetic_kmap_relation's refusal, nullptr = a map of the family
+inline const char *synthetic_kmap(const lgs_conv_plan_view &fwd, const lgs_conv_plan_view &bwd, int ks, lgs_kmap &km) {
+  static const int32_t present = 0;
+  auto view = [](const lgs_conv_plan_view &s) {
+    View v;
+    v.n_pad = s.n_pad; v.n_in = s.n_in; v.n_out = s.n_out; v.KS = s.KS; v.K = s.K;
+    if (s.has_nbr) v.nbr = &present;
+    if (s.has_nbr && s.KS > 1) v.mask64 = reinterpret_cast<const uint32_t *>(&present);
+    if (s.has_tile_k) v.tile_k = &present;
+    if (s.has_out_row) v.out_row = &present;
+    return v;
+  };
+  km.ks = ks; km.K = fwd.K; km.fwd = view(fwd); km.bwd = view(bwd);
+  return synthetic_kmap_relation(km);
 }
 }  // namespace lgs
 

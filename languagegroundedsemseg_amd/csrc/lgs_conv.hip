@@ -243,17 +243,70 @@ template <> __device__ inline float sq16<bf16_t>(const u32x4 &f, float s) {
 // colour rows): only the t = 0 gather is issued, the fragments of the pieces beyond the row are zero registers.
 // BN = the instance carries the BatchNorm statistics epilogue (BnEpi::partial).  The epilogue's vst[32 * NCB] butterfly is the
 // register peak of every instance that has it, although it sits behind a kernel-uniform branch no default launch takes: tile 7
-// is allocated 204 registers with it and 164 without (137 where it is built for three waves per SIMD).  launch_gather runs the BN instance exactly when a launch has `partial`
-// (and for every launch under CONV_LEAN_EPI=0, which is the kernel as it was before the split); all else runs BN = false.
+// is allocated 204 registers with it and 164 without (137 where it is built for three waves per SIMD).  gather_instance() picks the variant per launch.
 // ONEBUF = ONE weight slab in LDS instead of two: the next slab still waits in registers while this one is multiplied, but it
 // is staged between two barriers at the slab's end instead of beside the MFMAs.  For the walk whose two slabs cost the CU a
 // workgroup (tile 7, one slab of three chunks: 62 KB -> 38 KB).
+//
+// THE instance table of k_conv_gather: every instance that exists, one row each.  Which tile a launch gets is gather_id()'s
+// choice, which row of the tile gather_instance()'s; tile_of(), the dispatch (with_gather_kernel), the launch-site names, the
+// residency static_asserts and the debug queries are all generated from these rows (kF32 = the instance multiplies fp32).
+//   TILE(ID, RB, NCB, WM, WN, SC, D, BF16, LEAN, BUILT): the tile's own instance, walking the image's SC-chunk slabs.  SC = chunks
+//        per weight slab (sized to ~6-8 staging registers per thread), D = depth of the gather ring.  BF16: no fp32 instance.
+//        LEAN: the bf16 instance has a twin without the statistics epilogue (BN = false); BUILT = workgroups per CU the twins of
+//        the tile and of its walks are built for (__launch_bounds__; 0 = nothing stated).
+//   WALK(ID, RB, NCB, WM, WN, SC, D, SCL, ROW1, ONEBUF, OCC): the same tile (bf16) walked with SCL-chunk slabs, on one-piece rows
+//        (ROW1); both epilogue variants exist, ONEBUF: the lean one keeps ONE slab in LDS.  OCC = workgroups per CU of the tile's
+//        own instance with the statistics epilogue (registers, from the ISA): the walk may not take more LDS than leaves that many.
+//   CLIP(ID, RB, NCB, WM, WN, SC, D): the EPI = 1 instances of the fused CLIP loss, one column tile of NCB blocks; ID = -NCB.
+// The six tile parameters are spelled as the launch sites are named (tests and profiles key on that text), so walks repeat them.
+#define LGS_GATHER_TABLE(TILE, WALK, CLIP)                                                                                 \
+  TILE(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), false, true, 0)                                                      \
+  WALK(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 1, false, false, 3)                                                  \
+  WALK(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 1, true, false, 3)                                                   \
+  WALK(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 2, false, false, 3)                                                  \
+  WALK(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 3, false, false, 3)                                                  \
+  TILE(1, 2, 2, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), false, true, 0)                                                      \
+  WALK(1, 2, 2, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 1, false, false, 2)                                                  \
+  WALK(1, 2, 2, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 2, false, false, 2)                                                  \
+  WALK(1, 2, 2, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 3, false, false, 2)                                                  \
+  TILE(2, 2, 3, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), false, true, 0)                                                      \
+  WALK(2, 2, 3, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 1, false, false, 2)                                                  \
+  WALK(2, 2, 3, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 2, false, false, 2)                                                  \
+  WALK(2, 2, 3, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 3, false, false, 2)                                                  \
+  TILE(3, 2, 4, 4, 1, (kF32 ? 1 : 2), (kF32 ? 2 : 3), false, false, 0) /* 256 positions x 128 channels (64 x 128 per wave) */ \
+  TILE(4, 1, 1, 2, 1, (kF32 ? 2 : 4), (kF32 ? 4 : 8), false, false, 0)                                                     \
+  TILE(5, 1, 1, 2, 2, (kF32 ? 2 : 4), (kF32 ? 4 : 8), false, false, 0)                                                     \
+  TILE(6, 1, 7, 4, 1, (kF32 ? 1 : 2), (kF32 ? 3 : 4), false, true, 0)                                                      \
+  /* 128 positions x 128 channels (32 x 128 per wave).  Without the statistics epilogue it is BUILT for three workgroups per CU  \
+     (one wave of each per SIMD): 168 registers at most; 30 / 46 KB of LDS on its 1- and 2-chunk walks, 38 KB on the 3-chunk walk \
+     with one slab buffer (with two it would hold 62 KB: two workgroups).  With the epilogue: 204 registers, two per CU */   \
+  TILE(7, 1, 4, 4, 1, 2, 4, true, true, 3)                                                                                 \
+  WALK(7, 1, 4, 4, 1, 2, 4, 1, false, false, 2)                                                                            \
+  WALK(7, 1, 4, 4, 1, 2, 4, 3, false, true, 2)                                                                             \
+  TILE(8, 1, 2, 4, 1, 4, 6, true, false, 0)                                                                                \
+  TILE(9, 1, 2, 2, 2, 4, 6, true, false, 0)                                                                                \
+  TILE(10, 1, 2, 2, 1, 4, 6, true, false, 0)                                                                               \
+  TILE(11, 1, 4, 2, 1, 4, 6, true, false, 0)                                                                               \
+  TILE(12, 1, 2, 4, 1, 8, 6, true, false, 0) /* as 8 with 8-chunk (256-channel) weight slabs: half the slab barriers */     \
+  TILE(13, 1, 4, 4, 1, 8, 4, true, false, 0) /* 128 positions x 128 channels, 8-chunk slabs */                             \
+  TILE(16, 1, 8, 8, 1, 2, 4, true, true, 0)  /* eight waves of 32 positions x 256 channels */                              \
+  CLIP(-1, 1, 1, 4, 1, (kF32 ? 4 : 8), (kF32 ? 4 : 8))                                                                     \
+  CLIP(-2, 1, 2, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4))                                                                     \
+  CLIP(-4, 1, 4, 4, 1, (kF32 ? 1 : 2), (kF32 ? 3 : 4))                                                                     \
+  CLIP(-7, 1, 7, 4, 1, (kF32 ? 1 : 2), (kF32 ? 3 : 4))
+#define LGS_NO_ROW(...)
+
+// workgroups per CU the instance is built for (four waves: one of each per SIMD), 0 = nothing stated: BUILT of its tile's row
 template <typename T, int RB, int NCB, int WM, int WN, int SC, int D, int EPI, int SCL, bool BN, bool ONEBUF>
 constexpr int gather_waves_per_simd() {
-  // The bf16 128 x 128 tile without the statistics epilogue is BUILT for three workgroups per CU (one wave of each per SIMD):
-  // 168 registers at most; 30 / 46 KB of LDS on its 1- and 2-chunk walks, 38 KB on the 3-chunk walk with one slab buffer (with
-  // two it holds 62 KB: two workgroups, nothing stated).  0 = nothing stated.
-  return (sizeof(T) == 2 && EPI == 0 && !BN && RB == 1 && NCB == 4 && WM == 4 && WN == 1 && SC == 2 && D == 4 && (SCL <= 2 || ONEBUF)) ? 3 : 0;
+  constexpr bool kF32 = (sizeof(T) == 4);
+  if (kF32 || EPI != 0 || BN) return 0;
+#define LGS_BUILT(ID, RB_, NCB_, WM_, WN_, SC_, D_, BF16, LEAN, BUILT) \
+  if (RB == RB_ && NCB == NCB_ && WM == WM_ && WN == WN_ && SC == SC_ && D == D_) return BUILT;
+  LGS_GATHER_TABLE(LGS_BUILT, LGS_NO_ROW, LGS_NO_ROW)
+#undef LGS_BUILT
+  return 0;
 }
 template <typename T, int RB, int NCB, int WM, int WN, int SC, int D, int EPI = 0, int SCL = SC, bool ROW1 = false, bool BN = (EPI == 0),
           bool ONEBUF = false>
@@ -857,28 +910,16 @@ stats:
 
 // ------------------------------------------------------------------------------------ host side
 
-// THE tile table of k_conv_gather: id -> chunks per weight slab, column blocks and positions per workgroup of the
-// <RB, NCB, WM, WN, SC, D> instance launch_gather runs for it (every LGS_LAUNCH row static_asserts against its entry).
-// SC = chunks per weight slab (sized to ~6-8 staging registers per thread), D = depth of the gather ring.
-struct GatherCfg { int id, sc, wb, tm; };   // tm = positions per workgroup tile
-constexpr GatherCfg tile_of(int id, bool f32) {
-  switch (id) {
-    case 0: return {0, f32 ? 2 : 4, 1, 256};
-    case 1: return {1, f32 ? 2 : 4, 2, 256};
-    case 2: return {2, f32 ? 2 : 4, 3, 256};
-    case 3: return {3, f32 ? 1 : 2, 4, 256};     // 256 positions x 128 channels (64 x 128 per wave)
-    case 4: return {4, f32 ? 2 : 4, 1, 64};
-    case 5: return {5, f32 ? 2 : 4, 2, 64};
-    case 6: return {6, f32 ? 1 : 2, 7, 128};
-    case 7: return {7, 2, 4, 128};               // ids 7 .. 13, 16, 17: bf16 only.  128 positions x 128 channels (32 x 128 per wave), 3 workgroups / CU (2 with the statistics epilogue)
-    case 8: return {8, 4, 2, 128};
-    case 9: return {9, 4, 4, 64};
-    case 10: return {10, 4, 2, 64};
-    case 11: return {11, 4, 4, 64};
-    case 12: return {12, 8, 2, 128};             // as 8 with 8-chunk (256-channel) weight slabs: half the slab barriers
-    case 13: return {13, 8, 4, 128};             // 128 positions x 128 channels, 8-chunk slabs
-    default: return {id, 2, 8, 256};             // 16: eight waves of 32 positions x 256 channels; 17: k_conv_wide on the same image
-  }
+// What the packed image and the grid need of a row of LGS_GATHER_TABLE (TILE and CLIP rows): chunks per weight slab, column
+// blocks and positions per workgroup; lean = the tile has instances without the statistics epilogue.
+struct GatherCfg { int id, sc, wb, tm; bool lean; };   // tm = positions per workgroup tile
+constexpr GatherCfg tile_of(int id, bool kF32) {
+#define LGS_TILE(ID, RB, NCB, WM, WN, SC, D, BF16, LEAN, BUILT) if (id == ID) return {ID, SC, WN * NCB, WM * RB * 32, LEAN && !kF32};
+#define LGS_CLIP(ID, RB, NCB, WM, WN, SC, D) if (id == ID) return {ID, SC, WN * NCB, WM * RB * 32, false};
+  LGS_GATHER_TABLE(LGS_TILE, LGS_NO_ROW, LGS_CLIP)
+#undef LGS_TILE
+#undef LGS_CLIP
+  return {id, 2, 8, 256, false};   // 17: k_conv_wide, on the image of tile 16
 }
 
 // Tile choice: 256 positions x up to 128 channels when the map fills the chip, otherwise 128-position x 64-channel
@@ -1035,12 +1076,40 @@ inline int trimmed_slab(int tile_id, int sc, int nc, int gc) {
     if (nc % d == 0) return d;
   return 0;
 }
-// launch-site text of a trimmed instance: "SlabWalk<SCL,ROW1>::k_conv_gather<T,...>", the tile's own text with the walk in front
-template <int SCL, bool ROW1, bool BN = true, bool ONEBUF = false>
-struct SlabWalk {
-  template <typename T, int RB, int NCB, int WM, int WN, int SC, int D>
-  static constexpr auto k_conv_gather = &lgs::k_conv_gather<T, RB, NCB, WM, WN, SC, D, 0, SCL, ROW1, BN, ONEBUF>;
-};
+// ---- which row of the instance table a launch runs
+// scl = chunks per slab of the walk, 0 = the tile's own instance on the image's slabs; row1 = the one-piece-row walk;
+// bn = the instance with the statistics epilogue; onebuf = one weight slab in LDS
+struct GatherInstance { int tile_id, scl; bool row1, bn, onebuf; };
+constexpr bool walk_onebuf(int id, int scl, bool row1) {
+#define LGS_WALK(ID, RB, NCB, WM, WN, SC, D, SCL, ROW1, ONEBUF, OCC) if (id == ID && scl == SCL && row1 == ROW1) return ONEBUF;
+  LGS_GATHER_TABLE(LGS_NO_ROW, LGS_WALK, LGS_NO_ROW)
+#undef LGS_WALK
+  return false;
+}
+// THE choice, from the plan, the row width the launch gathers, whether it writes statistics and the tuning table.  Pure, like
+// conv_plan(); it picks an instance and never a plan.
+// Epilogue: on the bf16 tiles that have both variants (the big-map tiles 0, 1, 2, 6, 7, 16 and their walks) a launch that writes no
+// statistics runs the instance built without them (every dgrad, every forward without `partial`); CONV_LEAN_EPI=0, the fp32
+// instances and the small-map tiles (whose registers the epilogue does not set: within 4 either way) run the one with them.
+// Tile 7 decides per launch: its lean instances hold three workgroups per CU instead of two, which a grid of at most two per CU
+// cannot use -- level 3 of the 8-scene batch (256 -> 256, 308 workgroups) measured 1 % SLOWER on them and keeps the instance it
+// had; 128 -> 128 at level 2 (633) gains 14 %, the 96 -> 128 dgrad 6 - 13 % (profiles/conv_lean_epilogue.txt section 2).
+// Walk: trimmed_slab(); rows of one 16-byte piece (conv0: 3 colour channels padded to 8) take the walk whose second gather of a
+// chunk, out of range in every lane, is not issued.  The 3-chunk walk of tile 7 keeps one slab in LDS where it has no epilogue.
+template <typename T>
+GatherInstance gather_instance(const ConvPlan &pl, int cin_real, bool statistics) {
+  GatherInstance g = {pl.tile_id, 0, false, true, false};
+  if (sizeof(T) == 4) return g;
+  constexpr int64_t kTwoPerCu = 2 * 256;
+  const int64_t lean = tune(T_CONV_LEAN_EPI);
+  g.bn = !(tile_of(pl.tile_id, false).lean && !statistics && lean != 0 &&
+           (pl.tile_id != 7 || pl.grid_x * pl.grid_y * pl.grid_z > kTwoPerCu || lean == 2));
+  g.scl = trimmed_slab(pl.tile_id, pl.sc, pl.nc, pl.gc);
+  g.row1 = g.scl == 1 && pl.tile_id == 0 && cin_real <= Tr<T>::EPL && tune(T_CONV_ROW_TRIM) != 0;
+  g.onebuf = !g.bn && walk_onebuf(g.tile_id, g.scl, g.row1);
+  return g;
+}
+
 constexpr int kLdsPerCu = 160 * 1024;
 constexpr int gather_lds_bytes(int tm, int wb, int wld, int scl, int slabs = 2) { return slabs * scl * wb * wld * 64 * 16 + 27 * tm * 4; }
 // an instance BUILT for a number of workgroups per CU (gather_waves_per_simd) must also fit that often in the CU's LDS
@@ -1049,6 +1118,56 @@ constexpr bool lean_residency_fits() {
   constexpr int w = gather_waves_per_simd<T, RB, NCB, WM, WN, SC, D, 0, SCL, false, ONEBUF>();
   return w == 0 || (WM * WN == 4 && gather_lds_bytes(WM * RB * 32, WN * NCB, Tr<bf16_t>::WLD, SCL, ONEBUF ? 1 : 2) * w <= kLdsPerCu);
 }
+
+// ---- the dispatch: the kernel of the row `g` names -> f(GatherKernel<...>(), launch-site text).  The site names tile and walk,
+// not the epilogue variant ("k_conv_gather<T,...>", a walk with "SlabWalk<SCL,ROW1>::" in front, as tests and profiles know
+// them).  EPI = 0: the convolution rows, fp32 instances of the tiles that have one; EPI = 1: the CLIP rows.
+template <typename T, int RB, int NCB, int WM, int WN, int SC, int D, int EPI, int SCL, bool ROW1, bool BN, bool ONEBUF>
+struct GatherKernel {
+  static constexpr auto fn = &k_conv_gather<T, RB, NCB, WM, WN, SC, D, EPI, SCL, ROW1, BN, ONEBUF>;
+  static constexpr int rb = RB, ncb = NCB, wm = WM, wn = WN, sc = SC, d = D, threads = WM * WN * 64;
+};
+#define LGS_SITE(...) #__VA_ARGS__
+template <typename T, int EPI = 0, typename F>
+int with_gather_kernel(const GatherInstance &g, F &&f) {
+  constexpr bool kF32 = (sizeof(T) == 4);
+#define LGS_TILE(ID, RB, NCB, WM, WN, SC, D, BF16, LEAN, BUILT)                                                              \
+  if constexpr (EPI == 0 && !(BF16 && kF32))                                                                               \
+    if (g.tile_id == ID && g.scl == 0) {                                                                                   \
+      constexpr const char *site = LGS_SITE(k_conv_gather<T, RB, NCB, WM, WN, SC, D>);                                      \
+      if constexpr (LEAN && !kF32) {                                                                                       \
+        static_assert(lean_residency_fits<T, RB, NCB, WM, WN, SC, D, SC>(), "the lean instance is built for more workgroups than its LDS admits"); \
+        if (!g.bn) return f(GatherKernel<T, RB, NCB, WM, WN, SC, D, 0, SC, false, false, false>(), site);                   \
+      }                                                                                                                    \
+      LGS_REQUIRE(g.bn, "k_conv_gather: this tile has no instance without the statistics epilogue (internal error)");       \
+      return f(GatherKernel<T, RB, NCB, WM, WN, SC, D, 0, SC, false, true, false>(), site);                                 \
+    }
+#define LGS_WALK(ID, RB, NCB, WM, WN, SC, D, SCL, ROW1, ONEBUF, OCC)                                                         \
+  if constexpr (EPI == 0 && !kF32)                                                                                         \
+    if (g.tile_id == ID && g.scl == SCL && g.row1 == ROW1) {                                                               \
+      static_assert(gather_lds_bytes(WM * RB * 32, WN * NCB, Tr<bf16_t>::WLD, SCL) * OCC <= kLdsPerCu, "the slab walk costs the tile occupancy"); \
+      static_assert(lean_residency_fits<T, RB, NCB, WM, WN, SC, D, SCL, ONEBUF>(), "the lean instance is built for more workgroups than its LDS admits"); \
+      constexpr const char *site = LGS_SITE(SlabWalk<SCL, ROW1>::k_conv_gather<T, RB, NCB, WM, WN, SC, D>);                 \
+      return g.bn ? f(GatherKernel<T, RB, NCB, WM, WN, SC, D, 0, SCL, ROW1, true, false>(), site)                           \
+                  : f(GatherKernel<T, RB, NCB, WM, WN, SC, D, 0, SCL, ROW1, false, ONEBUF>(), site);                        \
+    }
+#define LGS_CLIP(ID, RB, NCB, WM, WN, SC, D)                                                                                \
+  if constexpr (EPI == 1)                                                                                                  \
+    if (g.tile_id == ID)                                                                                                   \
+      return f(GatherKernel<T, RB, NCB, WM, WN, SC, D, 1, SC, false, false, false>(), LGS_SITE(k_conv_gather<T, RB, NCB, WM, WN, SC, D, 1>));
+  LGS_GATHER_TABLE(LGS_TILE, LGS_WALK, LGS_CLIP)
+#undef LGS_TILE
+#undef LGS_WALK
+#undef LGS_CLIP
+  LGS_REQUIRE(false, "k_conv_gather: no such instance (tile " + std::to_string(g.tile_id) + ", " + std::to_string(g.scl) + "-chunk walk)");
+}
+// the launch of kernel `k` of the table, counted at `site_text` under the template bindings of the calling function (`pretty`)
+#define LGS_GATHER_LAUNCH(k, site_text, pretty, ...)                                                                       \
+  do {                                                                                                                     \
+    static const int _lgs_site = lgs::dispatch_site(site_text, pretty);                                                    \
+    lgs::dispatch_hit(_lgs_site);                                                                                          \
+    hipLaunchKernelGGL(decltype(k)::fn, __VA_ARGS__);                                                                      \
+  } while (0)
 
 template <typename T>
 int launch_gather(const View &v, const ConvPlan &pl, const T *in, int cin_real, const uint4 *wp, int K, T *out, int cout_real,
@@ -1073,106 +1192,17 @@ int launch_gather(const View &v, const ConvPlan &pl, const T *in, int cin_real, 
   const int64_t zstride = v.n_out * (int64_t)cout_real;
   const BnEpi be = (bn && !split) ? *bn : BnEpi();
   const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)pl.grid_z);
-  constexpr bool kF32 = (sizeof(T) == 4);
-  // THE choice of the epilogue variant: on the bf16 big-map tiles (0, 1, 2, 6, 7, 16 and their walks) a launch that writes no
-  // statistics runs the instance built without them (every dgrad, every forward without `partial`); CONV_LEAN_EPI=0, the fp32
-  // instances and the small-map tiles (whose registers the epilogue does not set: within 4 either way) run the one with them.
-  // Both are counted at the same launch site -- tile and walk are what the site names -- and the lean ones by a counter of their own.
-  // Tile 7 decides per launch: its lean instances hold three workgroups per CU instead of two, which a grid of at most two per CU
-  // cannot use -- level 3 of the 8-scene batch (256 -> 256, 308 workgroups) measured 1 % SLOWER on them and keeps the instance it
-  // had; 128 -> 128 at level 2 (633) gains 14 %, the 96 -> 128 dgrad 6 - 13 % (profiles/conv_lean_epilogue.txt section 2).
-  constexpr int64_t kTwoPerCu = 2 * 256;
-  const bool lean = !kF32 && be.partial == nullptr && tune(T_CONV_LEAN_EPI) != 0 &&
-                    (pl.tile_id != 7 || pl.grid_x * pl.grid_y * pl.grid_z > kTwoPerCu || tune(T_CONV_LEAN_EPI) == 2);
-#define LGS_COUNT_LEAN() LGS_COUNT("k_conv_gather:no_statistics_epilogue")
-#define LGS_GATHER_ARGS(WM, WN)                                                                                           \
-  grid, dim3(WM *WN * 64), 0, s, v, in, cin_real, nc, reinterpret_cast<const u32x4 *>(wp), nb_total, ncp, nbp, out, cout_real, \
-      split ? nullptr : bias, split ? zpartial : out_f32, row_scale, in_bytes, w_bytes, zstride, ClipEpi(), be, gc,       \
-      in_ld > 0 ? in_ld : cin_real
-#define LGS_LAUNCH(ID, RB, NCB, WM, WN, SC, D)                                                                            \
-  do {                                                                                                                    \
-    constexpr GatherCfg t = tile_of(ID, kF32);                                                                            \
-    static_assert(t.sc == SC && t.wb == WN * NCB && t.tm == WM * RB * 32, "tile_of() and the launched instance disagree"); \
-    LGS_KLAUNCH((k_conv_gather<T, RB, NCB, WM, WN, SC, D>), LGS_GATHER_ARGS(WM, WN));                                      \
-  } while (0)
-  // a tile that has both epilogue variants
-#define LGS_LAUNCH_EPI(ID, RB, NCB, WM, WN, SC, D)                                                                        \
-  do {                                                                                                                    \
-    constexpr GatherCfg t = tile_of(ID, kF32);                                                                            \
-    static_assert(t.sc == SC && t.wb == WN * NCB && t.tm == WM * RB * 32, "tile_of() and the launched instance disagree"); \
-    bool ran = false;                                                                                                     \
-    if constexpr (!kF32) {                                                                                                \
-      static_assert(lean_residency_fits<T, RB, NCB, WM, WN, SC, D, SC>(), "the lean instance is built for more workgroups than its LDS admits"); \
-      if (lean) {                                                                                                         \
-        LGS_COUNT_LEAN();                                                                                                 \
-        LGS_KLAUNCH_AS((k_conv_gather<T, RB, NCB, WM, WN, SC, D>), (k_conv_gather<T, RB, NCB, WM, WN, SC, D, 0, SC, false, false>), \
-                       LGS_GATHER_ARGS(WM, WN));                                                                          \
-        ran = true;                                                                                                       \
-      }                                                                                                                   \
-    }                                                                                                                     \
-    if (!ran) LGS_KLAUNCH((k_conv_gather<T, RB, NCB, WM, WN, SC, D>), LGS_GATHER_ARGS(WM, WN));                            \
-  } while (0)
-  // the same tile walked with SCL-chunk slabs; OCC = workgroups per CU of the tile's own instance with the statistics epilogue
-  // (registers, from the ISA): the walk may not take more LDS than leaves that many.  A trailing `true`: the instance without the
-  // epilogue keeps ONE slab in LDS (ONEBUF)
-#define LGS_LAUNCH_WALK(ID, RB, NCB, WM, WN, SC, D, SCL, ROW1, OCC, ...)                                                     \
-  do {                                                                                                                    \
-    constexpr GatherCfg t = tile_of(ID, false);                                                                           \
-    static_assert(t.sc == SC && t.wb == WN * NCB && t.tm == WM * RB * 32, "tile_of() and the launched instance disagree"); \
-    static_assert(gather_lds_bytes(t.tm, t.wb, Tr<bf16_t>::WLD, SCL) * OCC <= kLdsPerCu, "the slab walk costs the tile occupancy"); \
-    static_assert(lean_residency_fits<T, RB, NCB, WM, WN, SC, D, SCL, ##__VA_ARGS__>(), "the lean instance is built for more workgroups than its LDS admits"); \
-    if (lean) {                                                                                                           \
-      LGS_COUNT_LEAN();                                                                                                   \
-      LGS_KLAUNCH_AS((SlabWalk<SCL, ROW1>::k_conv_gather<T, RB, NCB, WM, WN, SC, D>),                                      \
-                     (SlabWalk<SCL, ROW1, false, ##__VA_ARGS__>::k_conv_gather<T, RB, NCB, WM, WN, SC, D>), LGS_GATHER_ARGS(WM, WN)); \
-    } else                                                                                                                \
-      LGS_KLAUNCH((SlabWalk<SCL, ROW1>::k_conv_gather<T, RB, NCB, WM, WN, SC, D>), LGS_GATHER_ARGS(WM, WN));               \
-  } while (0)
-  if constexpr (!kF32) {
-    const int scl = trimmed_slab(pl.tile_id, pl.sc, nc, gc);
-    // rows of one 16-byte piece (conv0: 3 colour channels padded to 8): the second gather of a chunk is out of range in every lane
-    const bool row1 = scl == 1 && pl.tile_id == 0 && cin_real <= Tr<T>::EPL && tune(T_CONV_ROW_TRIM) != 0;
-    bool done = true;
-    switch (scl * 100 + pl.tile_id * 2 + (row1 ? 1 : 0)) {
-      case 100: LGS_LAUNCH_WALK(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 1, false, 3); break;
-      case 101: LGS_LAUNCH_WALK(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 1, true, 3); break;
-      case 200: LGS_LAUNCH_WALK(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 2, false, 3); break;
-      case 300: LGS_LAUNCH_WALK(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 3, false, 3); break;
-      case 102: LGS_LAUNCH_WALK(1, 2, 2, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 1, false, 2); break;
-      case 202: LGS_LAUNCH_WALK(1, 2, 2, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 2, false, 2); break;
-      case 302: LGS_LAUNCH_WALK(1, 2, 2, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 3, false, 2); break;
-      case 104: LGS_LAUNCH_WALK(2, 2, 3, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 1, false, 2); break;
-      case 204: LGS_LAUNCH_WALK(2, 2, 3, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 2, false, 2); break;
-      case 304: LGS_LAUNCH_WALK(2, 2, 3, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4), 3, false, 2); break;
-      case 114: LGS_LAUNCH_WALK(7, 1, 4, 4, 1, 2, 4, 1, false, 2); break;
-      case 314: LGS_LAUNCH_WALK(7, 1, 4, 4, 1, 2, 4, 3, false, 2, true); break;
-      default: done = false; break;
-    }
-    if (done) goto launched;
-  }
-  switch (pl.tile_id) {
-    case 0: LGS_LAUNCH_EPI(0, 2, 1, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
-    case 1: LGS_LAUNCH_EPI(1, 2, 2, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
-    case 2: LGS_LAUNCH_EPI(2, 2, 3, 4, 1, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
-    case 3: LGS_LAUNCH(3, 2, 4, 4, 1, (kF32 ? 1 : 2), (kF32 ? 2 : 3)); break;
-    case 4: LGS_LAUNCH(4, 1, 1, 2, 1, (kF32 ? 2 : 4), (kF32 ? 4 : 8)); break;
-    case 6: LGS_LAUNCH_EPI(6, 1, 7, 4, 1, (kF32 ? 1 : 2), (kF32 ? 3 : 4)); break;
-    case 7: if constexpr (!kF32) LGS_LAUNCH_EPI(7, 1, 4, 4, 1, 2, 4); break;      // ids 7 .. 13, 16: bf16 only (gather_id)
-    case 16: if constexpr (!kF32) LGS_LAUNCH_EPI(16, 1, 8, 8, 1, 2, 4); break;
-    case 8: if constexpr (!kF32) LGS_LAUNCH(8, 1, 2, 4, 1, 4, 6); break;
-    case 9: if constexpr (!kF32) LGS_LAUNCH(9, 1, 2, 2, 2, 4, 6); break;
-    case 10: if constexpr (!kF32) LGS_LAUNCH(10, 1, 2, 2, 1, 4, 6); break;
-    case 11: if constexpr (!kF32) LGS_LAUNCH(11, 1, 4, 2, 1, 4, 6); break;
-    case 12: if constexpr (!kF32) LGS_LAUNCH(12, 1, 2, 4, 1, 8, 6); break;
-    case 13: if constexpr (!kF32) LGS_LAUNCH(13, 1, 4, 4, 1, 8, 4); break;
-    default: LGS_LAUNCH(5, 1, 1, 2, 2, (kF32 ? 2 : 4), (kF32 ? 4 : 8)); break;
-  }
-#undef LGS_LAUNCH
-#undef LGS_LAUNCH_EPI
-#undef LGS_LAUNCH_WALK
-#undef LGS_COUNT_LEAN
-#undef LGS_GATHER_ARGS
-launched:
+  // both epilogue variants are counted at the same launch site, the lean ones by a counter of their own
+  const GatherInstance g = gather_instance<T>(pl, cin_real, be.partial != nullptr);
+  if (!g.bn) LGS_COUNT("k_conv_gather:no_statistics_epilogue");
+  const char *const here = __PRETTY_FUNCTION__;
+  const int rc = with_gather_kernel<T>(g, [&](auto k, const char *site) {
+    LGS_GATHER_LAUNCH(k, site, here, grid, dim3(k.threads), 0, s, v, in, cin_real, nc, reinterpret_cast<const u32x4 *>(wp), nb_total, ncp, nbp,
+                      out, cout_real, split ? nullptr : bias, split ? zpartial : out_f32, row_scale, in_bytes, w_bytes, zstride, ClipEpi(), be,
+                      gc, in_ld > 0 ? in_ld : cin_real);
+    return 0;
+  });
+  if (rc) return rc;
   if (split) {
     const int64_t n4 = zstride / 4;
     if (n4 > 0) LGS_KLAUNCH((k_sum_partials<T>), (unsigned)((n4 + 255) / 256), 256, 0, s, zpartial, n4, zstride, bias, cout_real, out,
@@ -1180,6 +1210,19 @@ launched:
   }
   LGS_HIP(hipGetLastError());
   return 0;
+}
+
+// what launch_gather<T> would run and count for this plan (lgs_debug_conv_gather_instance): the choice, the numbers of its row,
+// the launch site by its registered name -- the function's only template binding is T, as launch_gather's
+template <typename T>
+int describe_gather(const ConvPlan &pl, int cin_real, bool statistics, lgs_conv_gather_instance *out) {
+  const GatherInstance g = gather_instance<T>(pl, cin_real, statistics);
+  const char *const here = __PRETTY_FUNCTION__;
+  return with_gather_kernel<T>(g, [&](auto k, const char *site) {
+    *out = {g.tile_id, g.scl, g.row1, g.bn, g.onebuf, k.rb, k.ncb, k.wm, k.wn, k.sc, k.d, {0}};
+    snprintf(out->site, sizeof(out->site), "%s", dispatch_site_name(site, here).c_str());
+    return 0;
+  });
 }
 
 template <typename T, typename TK = T>
@@ -1312,7 +1355,7 @@ int clip_loss_forward_t(const void *feat, int64_t n, int c, const float *anchors
   const int nb_total = pad32(na) / 32;
   const int ncb = nb_total <= 1 ? 1 : nb_total <= 2 ? 2 : nb_total <= 4 ? 4 : 7;
   ConvPlan pl = {};  // the image of the EPI = 1 instances: one column tile of ncb blocks
-  plan_image(pl, GatherCfg{-1, ncb == 1 ? (kF32 ? 4 : 8) : ncb == 2 ? (kF32 ? 2 : 4) : (kF32 ? 1 : 2), ncb, 128}, 1, c, na, Tr<T>::WLD);
+  plan_image(pl, tile_of(-ncb, kF32), 1, c, na, Tr<T>::WLD);
   const int nc = pl.nc, ncp = pl.ncp, nbp = pl.nbp;
   uint4 *wp = reinterpret_cast<uint4 *>(workspace);
   LGS_KLAUNCH(k_normalize_anchors, na, 64, 0, s, anchors, na, c, anchors_n);
@@ -1327,20 +1370,16 @@ int clip_loss_forward_t(const void *feat, int64_t n, int c, const float *anchors
   ClipEpi ce = ce_in;
   ce.n_anchor = na;
   const T *f = reinterpret_cast<const T *>(feat);
-  dim3 grid((unsigned)(v.n_pad / 128), 1);
-#define LGS_CLIP(NCB, SC, D)                                                                                              \
-  LGS_KLAUNCH((k_conv_gather<T, 1, NCB, 4, 1, SC, D, 1>), grid, dim3(256), 0, s, v, f, c, nc,                      \
-                     reinterpret_cast<const u32x4 *>(wp), nb_total, ncp, nbp, (T *)nullptr, na, (const float *)nullptr, sim, \
-                     (const float *)nullptr, (unsigned)in_bytes64, (unsigned)w_bytes64, (int64_t)0, ce, BnEpi(), nc, c)
-  switch (ncb) {
-    case 1: LGS_CLIP(1, (kF32 ? 4 : 8), (kF32 ? 4 : 8)); break;
-    case 2: LGS_CLIP(2, (kF32 ? 2 : 4), (kF32 ? 3 : 4)); break;
-    case 4: LGS_CLIP(4, (kF32 ? 1 : 2), (kF32 ? 3 : 4)); break;
-    default: LGS_CLIP(7, (kF32 ? 1 : 2), (kF32 ? 3 : 4)); break;
-  }
-#undef LGS_CLIP
+  const dim3 grid((unsigned)(v.n_pad / pl.tm), 1);
+  const char *const here = __PRETTY_FUNCTION__;
+  const int rc = with_gather_kernel<T, 1>(GatherInstance{-ncb, 0, false, false, false}, [&](auto k, const char *site) {
+    LGS_GATHER_LAUNCH(k, site, here, grid, dim3(k.threads), 0, s, v, f, c, nc, reinterpret_cast<const u32x4 *>(wp), nb_total, ncp, nbp,
+                      (T *)nullptr, na, (const float *)nullptr, sim, (const float *)nullptr, (unsigned)in_bytes64, (unsigned)w_bytes64,
+                      (int64_t)0, ce, BnEpi(), nc, c);
+    return 0;
+  });
   LGS_HIP(hipGetLastError());
-  return 0;
+  return rc;
 }
 
 // ---- one kernel instance per tensor dtype: f(Inst<storage type, multiplying instance>)
@@ -1460,22 +1499,11 @@ int lgs_conv_dgrad_accumulate(lgs_kmap *km, int transposed, const void *grad_out
   return conv_call(km, 1, transposed, grad_out, cin, weight, cout, nullptr, grad_in, dtype, workspace, &acc, packed, pack_mode, 0, stream);
 }
 
-// the plan of op 0 / 1 on a synthetic map + what the public queries say for it: no HIP call, `present` tables are never read
+// the plan of op 0 / 1 on a synthetic map + what the public queries say for it: no HIP call, the map's tables are never read
 int lgs_debug_conv_plan(const lgs_conv_plan_query *q, lgs_conv_plan_info *out) {
   LGS_REQUIRE(q && out && (q->op == 0 || q->op == 1) && known_dtype(q->dtype) && q->epilogue >= 0 && q->epilogue <= 2, "lgs_debug_conv_plan: bad argument");
-  static const int32_t present = 0;
-  auto view = [&](const lgs_conv_plan_view &s) {
-    View v;
-    v.n_pad = s.n_pad; v.n_in = s.n_in; v.n_out = s.n_out; v.KS = s.KS; v.K = s.K;
-    if (s.has_nbr) v.nbr = &present;
-    if (s.has_nbr && s.KS > 1) v.mask64 = reinterpret_cast<const uint32_t *>(&present);
-    if (s.has_tile_k) v.tile_k = &present;
-    if (s.has_out_row) v.out_row = &present;
-    return v;
-  };
   lgs_kmap km;
-  km.ks = q->ks; km.K = q->fwd.K; km.fwd = view(q->fwd); km.bwd = view(q->bwd);
-  LGS_REQUIRE(synthetic_kmap_relation(km) == nullptr, "lgs_debug_conv_plan: bad argument");
+  LGS_REQUIRE(synthetic_kmap(q->fwd, q->bwd, q->ks, km) == nullptr, "lgs_debug_conv_plan: bad argument");
   *out = plan_of(op_view(&km, q->op, q->transposed), km.K, q->op == 0 ? q->cin : q->cout, q->op == 0 ? q->cout : q->cin, q->dtype, (ConvEpi)q->epilogue);
   out->workspace_bytes = lgs_conv_workspace_bytes(&km, q->cin, q->cout, q->dtype, q->op);
   out->q_bn_partial_rows = q->op == 0 ? lgs_conv_bn_partial_rows(&km, q->transposed, q->cout, q->dtype) : 0;
@@ -1483,23 +1511,29 @@ int lgs_debug_conv_plan(const lgs_conv_plan_query *q, lgs_conv_plan_info *out) {
   return lgs_conv_pack_desc(&km, q->op, q->transposed, q->cin, q->cout, q->dtype, &out->pack_desc);
 }
 
-// the GPU's own count of resident workgroups per CU of a bf16 instance of tile 7 (scl 1 / 2 / 3) or tile 2 (scl 3 / 4)
+// the instance the k_conv_gather launch of that plan runs, as conv_gather_op hands the launch its rows: no HIP call either
+int lgs_debug_conv_gather_instance(const lgs_conv_plan_query *q, int with_statistics, lgs_conv_gather_instance *out) {
+  lgs_conv_plan_info info;
+  if (int rc = lgs_debug_conv_plan(q, &info)) return rc;
+  LGS_REQUIRE(out && info.path == kPathGather, "lgs_debug_conv_gather_instance: not a k_conv_gather launch");
+  LGS_REQUIRE(!with_statistics || info.q_bn_partial_rows > 0, "lgs_debug_conv_gather_instance: this launch shape produces no BatchNorm statistics");
+  const int g_real = q->op == 0 ? q->cin : q->cout;
+  return with_instance(q->dtype, [&](auto i) {
+    constexpr int EPL = Tr<typename decltype(i)::S>::EPL;     // (a padded input is gathered in rows of whole 16-byte pieces)
+    return describe_gather<typename decltype(i)::M>(info, info.pad_input ? (g_real + EPL - 1) / EPL * EPL : g_real, with_statistics != 0, out);
+  });
+}
+
+// the GPU's own count of resident workgroups per CU of a bf16 instance: scl chunks per walked slab (the tile's own slab length or
+// 0: its own instance), with the statistics epilogue or without (a tile that has one instance answers for that one)
 int lgs_debug_conv_gather_residency(int tile_id, int scl, int bn_stats, int *workgroups_per_cu) {
   LGS_REQUIRE(workgroups_per_cu, "lgs_debug_conv_gather_residency: null argument");
-  const void *k = nullptr;
-#define LGS_RES(ID, SCL, ...)                                                                                               \
-  if (tile_id == ID && scl == SCL)                                                                                        \
-    k = bn_stats ? reinterpret_cast<const void *>(&k_conv_gather<bf16_t, __VA_ARGS__, 0, SCL, false, true>)               \
-                 : reinterpret_cast<const void *>(&k_conv_gather<bf16_t, __VA_ARGS__, 0, SCL, false, false, (ID == 7 && SCL == 3)>)
-  LGS_RES(7, 1, 1, 4, 4, 1, 2, 4);
-  LGS_RES(7, 2, 1, 4, 4, 1, 2, 4);
-  LGS_RES(7, 3, 1, 4, 4, 1, 2, 4);
-  LGS_RES(2, 3, 2, 3, 4, 1, 4, 4);
-  LGS_RES(2, 4, 2, 3, 4, 1, 4, 4);
-#undef LGS_RES
-  LGS_REQUIRE(k, "lgs_debug_conv_gather_residency: tile 7 with 1 / 2 / 3-chunk slabs or tile 2 with 3 / 4");
-  LGS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(workgroups_per_cu, k, 256, 0));
-  return 0;
+  const GatherCfg t = tile_of(tile_id, false);
+  const GatherInstance g = {tile_id, scl == t.sc ? 0 : scl, false, bn_stats != 0 || !t.lean, false};
+  return with_gather_kernel<bf16_t>(g, [&](auto k, const char *) {
+    LGS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(workgroups_per_cu, reinterpret_cast<const void *>(k.fn), k.threads, 0));
+    return 0;
+  });
 }
 
 int64_t lgs_clip_workspace_bytes(int c, int n_anchor, int dtype) {

@@ -180,13 +180,18 @@ int64_t tune(Tune t) {
   return g_val[t].load(std::memory_order_relaxed);
 }
 
-int dispatch_site(const char *kernel_text, const char *pretty_function) {
+std::string dispatch_site_name(const char *kernel_text, const char *pretty_function) {
   std::string name = squeeze(kernel_text);
   // template bindings of the enclosing function, e.g. "[T = unsigned short, KIND = 0]" (clang's __PRETTY_FUNCTION__)
   if (pretty_function) {
     const char *b = strrchr(pretty_function, '[');
     if (b && strchr(b, '=')) name += " " + squeeze(b);
   }
+  return name;
+}
+
+int dispatch_site(const char *kernel_text, const char *pretty_function) {
+  const std::string name = dispatch_site_name(kernel_text, pretty_function);
   std::lock_guard<std::mutex> lk(g_site_mu);
   for (int i = 0; i < g_nsites; ++i)
     if (g_sites[i].name == name) return i;

@@ -1523,19 +1523,8 @@ int lgs_conv_wgrad(lgs_kmap *km, int transposed, const void *in, int cin, const 
 // the plan of lgs_conv_wgrad on a synthetic map + what the public queries say for it: no HIP call, `present` tables are never read
 int lgs_debug_wgrad_plan(const lgs_wgrad_plan_query *q, lgs_wgrad_plan_info *out) {
   LGS_REQUIRE(q && out && (q->dtype == LGS_F32 || q->dtype == LGS_BF16), "lgs_debug_wgrad_plan: bad argument");
-  static const int32_t present = 0;
-  auto view = [&](const lgs_conv_plan_view &s) {
-    View v;
-    v.n_pad = s.n_pad; v.n_in = s.n_in; v.n_out = s.n_out; v.KS = s.KS; v.K = s.K;
-    if (s.has_nbr) v.nbr = &present;
-    if (s.has_nbr && s.KS > 1) v.mask64 = reinterpret_cast<const uint32_t *>(&present);
-    if (s.has_tile_k) v.tile_k = &present;
-    if (s.has_out_row) v.out_row = &present;
-    return v;
-  };
   lgs_kmap km;
-  km.ks = q->ks; km.K = q->fwd.K; km.fwd = view(q->fwd); km.bwd = view(q->bwd);
-  LGS_REQUIRE(synthetic_kmap_relation(km) == nullptr && (!q->transposed || traits_of(&km).transposed_ok), "lgs_debug_wgrad_plan: bad argument");
+  LGS_REQUIRE(synthetic_kmap(q->fwd, q->bwd, q->ks, km) == nullptr && (!q->transposed || traits_of(&km).transposed_ok), "lgs_debug_wgrad_plan: bad argument");
   *out = wgrad_plan(km, q->transposed, q->cin, q->cout, q->dtype, q->in_row_stride);
   out->workspace_bytes = lgs_conv_workspace_bytes(&km, q->cin, q->cout, q->dtype, 2);
   out->supports_stride = lgs_conv_wgrad_supports_stride(&km, q->transposed, q->cin, q->cout, q->dtype, q->in_row_stride);

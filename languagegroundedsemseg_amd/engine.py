@@ -53,6 +53,12 @@ class ConvPlanInfo(ctypes.Structure):
                 ("q_bn_partial_rows", ctypes.c_int), ("q_can_accumulate", ctypes.c_int), ("pack_desc", PackDesc)]
 
 
+class ConvGatherInstance(ctypes.Structure):
+    """lgs_conv_gather_instance: what lgs_debug_conv_gather_instance answers (no GPU needed)"""
+    _fields_ = [(n, ctypes.c_int) for n in ("tile_id", "scl", "row1", "bn", "onebuf", "rb", "ncb", "wm", "wn", "sc", "d")] + \
+               [("site", ctypes.c_char * 160)]
+
+
 class WgradPlanQuery(ctypes.Structure):
     """lgs_wgrad_plan_query"""
     _fields_ = [("fwd", ConvPlanView), ("bwd", ConvPlanView)] + \
@@ -201,8 +207,8 @@ _lib = None
 # every symbol include/lgs_engine.h declares; tests check the built library exports all of them
 EXPORTS = [
     "lgs_abi_version", "lgs_last_error",
-    "lgs_tuning_set", "lgs_tuning_get", "lgs_tuning_describe", "lgs_debug_dispatch_counts", "lgs_debug_conv_plan", "lgs_debug_conv_gather_residency",
-    "lgs_debug_wgrad_plan",
+    "lgs_tuning_set", "lgs_tuning_get", "lgs_tuning_describe", "lgs_debug_dispatch_counts", "lgs_debug_conv_plan", "lgs_debug_conv_gather_instance",
+    "lgs_debug_conv_gather_residency", "lgs_debug_wgrad_plan",
     "lgs_debug_norm_plan", "lgs_debug_instnorm_plan", "lgs_debug_seg_plan", "lgs_debug_kmap_relation",
     "lgs_manager_create", "lgs_manager_destroy", "lgs_manager_insert", "lgs_manager_stride2", "lgs_manager_check",
     "lgs_manager_parent_of", "lgs_manager_map_size", "lgs_manager_get_coords", "lgs_manager_nearest", "lgs_manager_kernel_map",
@@ -288,6 +294,7 @@ def lib():
         "lgs_conv_pack_desc": [vp, ci, ci, ci, ci, ci, ctypes.POINTER(PackDesc)],
         "lgs_pack_weights_batch": [vp, ci, i64, vp],
         "lgs_debug_conv_plan": [ctypes.POINTER(ConvPlanQuery), ctypes.POINTER(ConvPlanInfo)],
+        "lgs_debug_conv_gather_instance": [ctypes.POINTER(ConvPlanQuery), ci, ctypes.POINTER(ConvGatherInstance)],
         "lgs_debug_conv_gather_residency": [ci, ci, ci, pi],
         "lgs_debug_wgrad_plan": [ctypes.POINTER(WgradPlanQuery), ctypes.POINTER(WgradPlanInfo)],
         "lgs_debug_norm_plan": [ctypes.POINTER(NormPlanQuery), ctypes.POINTER(NormPlanInfo)],

@@ -30,6 +30,16 @@ def deterministic_init(model, seed=42):
     return model
 
 
+# launch sites of k_conv_gather per tile id: the <T, RB, NCB, WM, WN, SC, D> text of the instance table in csrc/lgs_conv.hip as the
+# dispatch counters spell it ("k_conv_gather<T,%s> [T=...]"; a slab walk has "SlabWalk<chunks per slab,one-piece row>::" in front).
+# tests/test_conv_instance_cpu.py holds this table to the engine's own answer.
+GATHER_TILES = {0: "2,1,4,1,(kF32?2:4),(kF32?3:4)", 1: "2,2,4,1,(kF32?2:4),(kF32?3:4)", 2: "2,3,4,1,(kF32?2:4),(kF32?3:4)",
+                3: "2,4,4,1,(kF32?1:2),(kF32?2:3)", 4: "1,1,2,1,(kF32?2:4),(kF32?4:8)", 5: "1,1,2,2,(kF32?2:4),(kF32?4:8)",
+                6: "1,7,4,1,(kF32?1:2),(kF32?3:4)", 7: "1,4,4,1,2,4", 8: "1,2,4,1,4,6", 9: "1,2,2,2,4,6", 10: "1,2,2,1,4,6",
+                11: "1,4,2,1,4,6", 12: "1,2,4,1,8,6", 13: "1,4,4,1,8,4", 16: "1,8,8,1,2,4"}
+GATHER_LEAN_COUNTER = "k_conv_gather:no_statistics_epilogue"      # counted beside the launch site when the lean instance runs
+
+
 class Cfg:
     """the subset of config/config.py defaults the models read"""
     bn_momentum = 0.02

@@ -19,12 +19,12 @@ import torch
 
 import MinkowskiEngine as ME
 from languagegroundedsemseg_amd import engine
+from helpers import GATHER_LEAN_COUNTER as LEAN, GATHER_TILES
 from test_gpu_map_build import _slab
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-LEAN = "k_conv_gather:no_statistics_epilogue"
-T2, T7 = "2,3,4,1,(kF32?2:4),(kF32?3:4)", "1,4,4,1,2,4"
+T2, T7 = GATHER_TILES[2], GATHER_TILES[7]
 
 
 class Map:
@@ -112,6 +112,18 @@ def test_small_maps_bitwise(small, K, cin, cout, ops, split):
     if "d" in ops:
         _ab(lambda: km.conv_dgrad(g, w, False), T7, **knobs)
         _ab(lambda: km.conv_dgrad(g, w, False, accumulate_into=x.clone()), T7, **knobs)
+
+
+def test_the_instance_query_predicts_the_launch_site(small):
+    """lgs_debug_conv_gather_instance on the small map's sizes: the site it names is the site the 96 -> 128 dgrad is counted at"""
+    v = engine.ConvPlanView(2816, small.n, small.n, 27, 27, 1, 0, 1)
+    q, g = engine.ConvPlanQuery(v, v, 3, 1, 0, 128, 96, engine.LGS_BF16, 0), engine.ConvGatherInstance()
+    _, w, grad = _data(small.n, 27, 128, 96)
+    with engine.tuning(SMALL_CFG=7, CONV_LEAN_EPI=2):
+        engine.check(engine.lib().lgs_debug_conv_gather_instance(ctypes.byref(q), 0, ctypes.byref(g)))
+    _, sites = _run(lambda: small.km[3].conv_dgrad(grad, w, False), SMALL_CFG=7, CONV_LEAN_EPI=2)
+    assert (g.tile_id, g.scl, g.bn, g.onebuf) == (7, 3, 0, 1) and g.site.decode() == "SlabWalk<3,false>::k_conv_gather<T,%s> [T=unsignedshort]" % T7
+    assert g.site.decode() in sites and LEAN in sites, sorted(sites)
 
 
 def test_tile7_as_the_plan_picks_it(big):

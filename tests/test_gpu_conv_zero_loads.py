@@ -14,13 +14,14 @@ import torch
 import MinkowskiEngine as ME
 import precision as P
 from languagegroundedsemseg_amd import engine
+from helpers import GATHER_TILES
 from test_gpu_map_build import _slab
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 ON = dict(CONV_SLAB_TRIM=1, CONV_ROW_TRIM=1)
 OFF = dict(CONV_SLAB_TRIM=0, CONV_ROW_TRIM=0)
-T0, T1, T2, T7 = "2,1,4,1,(kF32?2:4),(kF32?3:4)", "2,2,4,1,(kF32?2:4),(kF32?3:4)", "2,3,4,1,(kF32?2:4),(kF32?3:4)", "1,4,4,1,2,4"
+T0, T1, T2, T7 = (GATHER_TILES[t] for t in (0, 1, 2, 7))
 
 
 def walk(scl, tile, row1=False):

@@ -12,17 +12,13 @@ import torch
 
 import MinkowskiEngine as ME
 import precision as P
-from helpers import small_scene
+from helpers import GATHER_TILES as _TILES, small_scene
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
-# launch sites of k_conv_gather per tile id: the <T, RB, NCB, WM, WN, SC, D> text of lgs_conv.hip's launch_gather switch, the
-# instance told apart by the T binding.  A site pattern "a&b" needs both substrings in ONE launch site.
-_TILES = {0: "2,1,4,1,(kF32?2:4),(kF32?3:4)", 1: "2,2,4,1,(kF32?2:4),(kF32?3:4)", 2: "2,3,4,1,(kF32?2:4),(kF32?3:4)",
-          3: "2,4,4,1,(kF32?1:2),(kF32?2:3)", 4: "1,1,2,1,(kF32?2:4),(kF32?4:8)", 5: "1,1,2,2,(kF32?2:4),(kF32?4:8)",
-          6: "1,7,4,1,(kF32?1:2),(kF32?3:4)", 7: "1,4,4,1,2,4", 8: "1,2,4,1,4,6", 9: "1,2,2,2,4,6", 10: "1,2,2,1,4,6",
-          11: "1,4,2,1,4,6", 12: "1,2,4,1,8,6", 13: "1,4,4,1,8,4", 16: "1,8,8,1,2,4"}
+# launch sites of k_conv_gather: _TILES[tile id] is the <T, RB, NCB, WM, WN, SC, D> text, the instance told apart by the T binding.
+# A site pattern "a&b" needs both substrings in ONE launch site.
 
 
 def gather(tile, dt="bf16"):

@@ -8,8 +8,10 @@ count (architectural + accumulation registers; .amdhsa_accum_offset says where t
 .amdhsa_group_segment_fixed_size the LDS bytes, .amdhsa_private_segment_fixed_size the scratch bytes.  Residency is arithmetic on
 those: a SIMD lane has 512 unified registers in granules of 8, a CU 160 KB of LDS and four SIMDs, and a four-wave workgroup puts
 one wave on each SIMD (eight waves: two).  The GPU's own answer is lgs_debug_conv_gather_residency (tools/microbench.py lean).
+The tile id of an instance is the engine's (its instance table, asked through lgs_debug_conv_gather_instance: the library must be built).
 Layout of profiles/conv_zero_loads.txt section 1; instances are <RB,NCB,WM,WN,SC,D,EPI,SCL,ROW1,BN,ONEBUF>, BN = 1: with the
 BatchNorm statistics epilogue, ONEBUF = 1: one weight slab in LDS."""
+import ctypes
 import os
 import re
 import subprocess
@@ -18,9 +20,22 @@ import tempfile
 
 LDS_PER_CU = 160 * 1024
 REGS_PER_LANE = 512
-TILES = {(2, 1, 4, 1, 4, 4): 0, (2, 2, 4, 1, 4, 4): 1, (2, 3, 4, 1, 4, 4): 2, (2, 4, 4, 1, 2, 3): 3, (1, 1, 2, 1, 4, 8): 4, (1, 1, 2, 2, 4, 8): 5,
-         (1, 7, 4, 1, 2, 4): 6, (1, 4, 4, 1, 2, 4): 7, (1, 2, 4, 1, 4, 6): 8, (1, 2, 2, 2, 4, 6): 9, (1, 2, 2, 1, 4, 6): 10, (1, 4, 2, 1, 4, 6): 11,
-         (1, 2, 4, 1, 8, 6): 12, (1, 4, 4, 1, 8, 4): 13, (1, 8, 8, 1, 2, 4): 16}
+
+
+def tiles():
+    """-> {(RB, NCB, WM, WN, SC, D): tile id} of the bf16 instances, as the engine's instance table has them: the answers of
+    lgs_debug_conv_gather_instance over launches that reach every tile (big and small maps, 1 .. 8 column blocks, SMALL_CFG)"""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    from languagegroundedsemseg_amd import engine
+    out = {}
+    for knobs in [{}, {"CONV_WIDE": 0}] + [{"SMALL_CFG": v} for v in (3, 5, 7, 9, 10, 11, 12, 13)]:
+        for n_pad, ks, cout in ((n, ks, c) for n in (4096, 65536) for ks in (3, 1) for c in (32, 64, 96, 128, 200, 256)):
+            v = engine.ConvPlanView(n_pad, n_pad, n_pad, ks ** 3, ks ** 3, int(ks == 3), 0, int(ks == 3))
+            q, g = engine.ConvPlanQuery(v, v, ks, 0, 0, 128, cout, engine.LGS_BF16, 1), engine.ConvGatherInstance()
+            with engine.tuning(**knobs):
+                if engine.lib().lgs_debug_conv_gather_instance(ctypes.byref(q), 0, ctypes.byref(g)) == 0:      # (else: not a k_conv_gather launch)
+                    out[(g.rb, g.ncb, g.wm, g.wn, g.sc, g.d)] = g.tile_id
+    return out
 
 
 def assembly(path):
@@ -49,6 +64,7 @@ def demangle(names):
 
 def rows(text, bf16_only=True):
     ks = [k for k in kernels(text) if "k_conv_gather" in k[0]]
+    TILES = tiles()
     res = []
     for (_, f), name in zip(ks, demangle([k[0] for k in ks])):
         m = re.search(r"k_conv_gather<([^>]*)>", name)
