@@ -974,6 +974,7 @@ int lgs_supcon_backward(const void *feat, int64_t n, int c, const int64_t *label
 #define LGS_AUG_I32X4 1
 #define LGS_AUG_STAGE_COLOR 16
 #define LGS_AUG_STAGE_PASTE 17          /* the tail-instance paste's trial draws (below) */
+#define LGS_AUG_STAGE_DROPOUT 18        /* RandomDropout's row keys (below) */
 #define LGS_PASTE_MAX_SLOTS 1024
 #define LGS_PASTE_SLOT_COLS 6
 #define LGS_PASTE_SCENE_COLS 4
@@ -1045,6 +1046,34 @@ int lgs_paste_instances(const int32_t *coords, const float *feats, const int64_t
                         const double *scene_xforms, const double *boxes, int64_t n_boxes, const int32_t *trial_draws, int trials,
                         int64_t seed, int64_t max_map_cells, void *workspace, int32_t *coords_out, float *feats_out,
                         int64_t *labels_out, int32_t *placement, int32_t *status, void *stream);
+
+/* ---- RandomDropout: an exact-count uniform row subset per scene (csrc/lgs_dropout.hip) -----------
+ * replaces: RandomDropout (lib/transforms.py:172-195, downstream/insseg/datasets/transforms.py:145-159): on the voxel rows of one
+ *   scene, np.random.choice(N, int(N * (1 - ratio)), replace=False) and the gathers by it.
+ * NEW SYMBOLS ONLY: LGS_ABI_VERSION stays 18; a library that lacks them lacks the capability.
+ * A batch is 1 <= b <= LGS_AUG_MAX_SCENES scenes of n rows in all, scene_offsets DEVICE int64 [b + 1] as above (entries are clamped
+ * into a non-decreasing table on [0, n]).  Scene s has n_s rows; bit s of apply_mask says whether it drops rows.
+ *   count      k_s = floor(n_s * keep) in IEEE double, keep in (0, 1] = the host's 1 - ratio; a scene whose bit is clear keeps n_s.
+ *   key        row i (0-based within its scene) has the uint32 key = word 0 of the Philox-4x32-10 block with counter
+ *              (i & 2^32-1, i >> 32, 0, LGS_AUG_STAGE_DROPOUT ^ seed >> 32) and key (seed & 2^32-1, scene_seeds[s]); scene_seeds: HOST
+ *              int32 [b] or NULL (zeros).  keys (DEVICE int32 [n], read as uint32, indexed by the batch row) replaces the generator
+ *              when not NULL (teacher-forced; the only way to meet equal keys on purpose).
+ *   selection  the k_s rows that are smallest under the lexicographic order (key, i): equal keys resolve towards the lower row.
+ *   output     rows_out (DEVICE int64, capacity n): scene after scene the kept rows in ascending order, as g (the row's index in the
+ *              batch), or through[g] when through (DEVICE int64 [n]) is not NULL; offsets_out DEVICE int64 [b + 1]: where each
+ *              scene's kept rows begin, offsets_out[b] = the number of rows written.  k_s and n_s may be 0.
+ * Two deviations from the reference: it returns the rows in np.random.choice's permutation order, this returns the same kind of set in
+ * ascending order; and equal 32-bit keys resolve towards the lower row, which touches the threshold key only (a probability of order
+ * n_s / 2^32 per scene that the threshold key is shared at all).
+ * How: a three-digit radix select (11 + 11 + 10 bits) over keys that are regenerated in every pass -- the selection reads no row data
+ * -- with per-scene histograms summed by integer atomics, then a count per tile, one scan per scene and a stable compaction by
+ * ballot and popcount.  Dependent steps are separate launches; the result does not depend on any launch grid, and two calls give the
+ * same bits.  Nothing is read back.  workspace: lgs_dropout_workspace_bytes(n, b) bytes (0 = bad shape: n < 0, n > 2^40, b out of
+ * range); the call initialises what it reads of it. */
+int64_t lgs_dropout_workspace_bytes(int64_t n, int b);
+int lgs_dropout_select(const int64_t *scene_offsets, int64_t n, int b, unsigned int apply_mask, double keep, int64_t seed,
+                       const int32_t *scene_seeds, const int32_t *keys, const int64_t *through, void *workspace, int64_t *rows_out,
+                       int64_t *offsets_out, void *stream);
 
 #ifdef __cplusplus
 }

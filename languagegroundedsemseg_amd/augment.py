@@ -16,8 +16,13 @@ With `tail_instances=TailInstancePaste(bank, ...)` the chain also runs the refer
 (--sample_tail_instances, lib/datasets/scannet.py:143-241; csrc/lgs_paste.hip): the voxeliser applies M_v only, `paste_instances`
 places the drawn bank instances on the scene's height map and rotates every row by M_r, and the chain's one dedup follows.
 
-Out of scope, refused by name: RandomDropout, HueSaturationTranslation, the clip bound, instance augmentation
-(the raw / latent colour and scale shifts of augment_instances), the paired voxeliser."""
+With `dropout=ratio` the chain also runs RandomDropout (csrc/lgs_dropout.hip): with probability `ratio` a scene keeps a uniformly
+random int(n * (1 - ratio)) of its voxel rows, as the last transform (lib/dataset.py:385-386) or the first (`dropout_position="first"`,
+downstream/insseg/datasets/dataset.py:505; `DeviceAugmentation.from_insseg_dataset` builds that recipe's chain).
+
+Out of scope, refused by name: HueSaturationTranslation, the clip bound, instance augmentation (the raw / latent
+colour and scale shifts of augment_instances), the paired voxeliser."""
+import collections
 import ctypes
 import dataclasses
 
@@ -259,6 +264,73 @@ def philox_words(counters, key):
     return out
 
 
+DropoutOffsets = collections.namedtuple("DropoutOffsets", "device host")      # int64 [B + 1] on the device / B + 1 host integers
+
+
+def _dropout_select(off_dev, n, apply, ratio, seed, scene_seeds, keys, through):
+    """lgs_dropout_select on checked arguments -> (rows_out with capacity n, offsets_out), both on the device; nothing synchronises"""
+    dev = off_dev.device
+    b = off_dev.shape[0] - 1
+    mask = sum(1 << s for s in range(b) if apply[s])
+    seeds = (ctypes.c_int32 * b)(*[i32(v) for v in scene_seeds])
+    L = engine.lib()
+    nbytes = int(L.lgs_dropout_workspace_bytes(int(n), b))
+    if nbytes <= 0:
+        raise ValueError("random_dropout_rows: bad shape (n = %d rows, %d scenes)" % (n, b))
+    ws = scratch(nbytes, dev)              # (lgs_dropout_select initialises what it reads of it)
+    rows = torch.empty(int(n), dtype=torch.int64, device=dev)
+    offsets = torch.empty(b + 1, dtype=torch.int64, device=dev)
+    engine.check(L.lgs_dropout_select(ptr(off_dev), int(n), b, i32(mask), 1 - ratio, i64(seed), seeds, ptr(keys), ptr(through), ptr(ws),
+                                      ptr(rows), ptr(offsets), raw_stream()))
+    return rows, offsets
+
+
+def random_dropout_rows(scene_offsets, n, apply, ratio=0.2, seed=0, scene_seeds=None, keys=None, through=None):
+    """RandomDropout's row choice for every scene of a batch (csrc/lgs_dropout.hip) -> (rows int64 [m], offsets).
+    scene_offsets: device int64 [B + 1], B <= 32, over n rows.  apply: one boolean per scene; a scene that applies keeps the
+    int(n_s * (1 - ratio)) rows with the smallest (Philox key, row), the others keep every row.  rows: the kept rows in ascending
+    order, scene after scene (through[row] instead when `through`, a device int64 [n] index, is given); offsets: a DropoutOffsets of
+    where each scene's kept rows begin, as the device tensor and as host integers.  Reading those B + 1 integers to size `rows` is the
+    call's only synchronisation.  keys: device int32 [n], read as uint32, in place of the generator (teacher-forced)."""
+    ratio = float(ratio)
+    if not 0.0 <= ratio < 1.0:
+        raise ValueError("random_dropout_rows: ratio must lie in [0, 1), got %r" % ratio)
+    require_hip(scene_offsets, "scene_offsets (device form)")
+    if scene_offsets.dtype != torch.int64 or scene_offsets.dim() != 1 or not 2 <= scene_offsets.shape[0] <= MAX_SCENES + 1:
+        raise ValueError("random_dropout_rows: scene_offsets must be int64 [B + 1] with 1 <= B <= %d" % MAX_SCENES)
+    off_dev = scene_offsets.contiguous()
+    b, n = off_dev.shape[0] - 1, int(n)
+    apply = [bool(v) for v in apply]
+    scene_seeds = [0] * b if scene_seeds is None else list(scene_seeds)
+    if len(apply) != b or len(scene_seeds) != b:
+        raise ValueError("random_dropout_rows: apply and scene_seeds take one value per scene (%d)" % b)
+    for t, what, dtype in ((keys, "keys", torch.int32), (through, "through", torch.int64)):
+        if t is not None:
+            require_hip(t, what)
+            if t.dtype != dtype or t.shape != (n,):
+                raise ValueError("random_dropout_rows: %s must be %s [n]" % (what, dtype))
+    keys = None if keys is None else keys.contiguous()
+    through = None if through is None else through.contiguous()
+    with on_device(off_dev.device):
+        rows, offsets = _dropout_select(off_dev, n, apply, ratio, seed, scene_seeds, keys, through)
+        host = [int(v) for v in offsets.tolist()]          # the one read
+    return rows[:host[-1]], DropoutOffsets(offsets, host)
+
+
+def random_dropout(coords, feats, labels, instances=None, scene_offsets=None, n=None, apply=None, **kw):
+    """RandomDropout on a batch's voxel rows: random_dropout_rows (same arguments; n defaults to the number of rows) and the gathers
+    -> (coords, feats, labels[, instances], rows, offsets)"""
+    for t, what in ((coords, "coords"), (feats, "feats"), (labels, "labels")):
+        require_hip(t, what)
+    if instances is not None:
+        require_hip(instances, "instances")
+    rows, offsets = random_dropout_rows(scene_offsets, coords.shape[0] if n is None else n, apply, **kw)
+    out = (coords.index_select(0, rows), feats.index_select(0, rows), labels.index_select(0, rows))
+    if instances is not None:
+        out += (instances.index_select(0, rows),)
+    return out + (rows, offsets)
+
+
 # ---- the chain
 @dataclasses.dataclass
 class AugmentPlan:
@@ -279,6 +351,7 @@ class AugmentPlan:
     shift: np.ndarray                 # [3] int        the trainer's per-batch coordinate shift (zeros unless coordinate_shift)
     rotations: np.ndarray = None      # [B, 4, 4]      M_r alone (the paste rotates after it has placed the instances)
     paste: "PastePlan" = None         # the tail-instance decisions, when the chain has tail_instances
+    dropout: np.ndarray = None        # [B] bool       RandomDropout applies (p = its ratio), when the chain has dropout
 
 
 def axis_rotation(axis, theta):
@@ -482,17 +555,21 @@ class DeviceAugmentation:
     """The reference's default train-time chain for one batch: elastic stages -> per-scene rigid matrix + floor -> dedup (first
     occurrence wins) -> flip on the voxel rows -> colour on the voxel rows.  `draw` makes the host decisions, `__call__` runs the
     kernels.  At most 32 scenes per batch.  With tail_instances (a TailInstancePaste) the second step becomes: M_v + floor -> paste
-    the drawn instances -> M_r + floor of every row (paste_instances); the dedup after it is still the chain's only one."""
+    the drawn instances -> M_r + floor of every row (paste_instances); the dedup after it is still the chain's only one.
+    With dropout (a ratio) a scene drops rows with probability `ratio` (the reference's application probability IS the ratio):
+    dropout_position "last" selects after the colour stage (lib/dataset.py:385-386: colour statistics over all rows), "first" right
+    after the dedup (insseg dataset.py:505: flip and autocontrast see the surviving rows only)."""
 
     def __init__(self, voxel_size, elastic_params=((0.2, 0.4), (0.8, 1.6)), rotation_bound=None, scale_bound=None, rotation_axis="z",
                  color_trans_ratio=0.1, color_jitter_std=0.05, color_scale=1.0, normalize_color=False, coordinate_shift=False,
                  max_cells=DEFAULT_MAX_CELLS, seed=0, random_dropout=None, hue_saturation=None, clip_bound=None,
-                 instance_augmentation=None, num_pairs=1, tail_instances=None):
+                 instance_augmentation=None, num_pairs=1, tail_instances=None, dropout=None, dropout_position="last"):
         given = dict(random_dropout=random_dropout, hue_saturation=hue_saturation, clip_bound=clip_bound,
                      instance_augmentation=instance_augmentation)
         for name in _REFUSED:
             if given[name] is not None:
-                raise NotImplementedError("DeviceAugmentation: %s is not part of the device chain (DESIGN.md section 8)" % name)
+                hint = "; RandomDropout on the device is dropout=ratio" if name == "random_dropout" else ""
+                raise NotImplementedError("DeviceAugmentation: %s is not part of the device chain (DESIGN.md section 8)%s" % (name, hint))
         if num_pairs != 1:
             raise NotImplementedError("DeviceAugmentation: the paired voxeliser (num_pairs == 2) is not part of the device chain")
         self.voxel_size = float(voxel_size)
@@ -508,6 +585,12 @@ class DeviceAugmentation:
         self.max_cells = int(max_cells)
         self.rng = np.random.default_rng(seed)
         self.tail = tail_instances
+        self.dropout = None if dropout is None else float(dropout)
+        if self.dropout is not None and not 0.0 <= self.dropout < 1.0:
+            raise ValueError("DeviceAugmentation: dropout must be a ratio in [0, 1), got %r" % dropout)
+        if dropout_position not in ("first", "last"):
+            raise ValueError("DeviceAugmentation: dropout_position must be 'first' or 'last', got %r" % (dropout_position,))
+        self.dropout_position = dropout_position
         if self.tail is not None and self.tail.rigid is None:          # an instance is voxelised by the scene's voxeliser, augmentation on
             self.tail.rigid = lambda r, n: draw_rigid(r, n, self.voxel_size, self.rotation_bound, self.scale_bound)[4]
 
@@ -516,8 +599,8 @@ class DeviceAugmentation:
         """The chain a reference dataset class and config describe (lib/dataset.py:337-389, lib/datasets/scannet.py)."""
         if getattr(DatasetClass, "CLIP_BOUND", None) is not None:
             kw.setdefault("clip_bound", DatasetClass.CLIP_BOUND)
-        if float(getattr(config, "data_aug_patch_dropout_ratio", 0.35)) == 0.0:
-            kw.setdefault("random_dropout", 0.2)          # lib/dataset.py:385 adds RandomDropout in that case only
+        if float(getattr(config, "data_aug_patch_dropout_ratio", 0.35)) == 0.0 and kw.get("dropout") is None:
+            kw.setdefault("random_dropout", 0.2)          # lib/dataset.py:385 adds RandomDropout in that case only: say dropout=0.2
         elastic = DatasetClass.ELASTIC_DISTORT_PARAMS if getattr(config, "elastic_distortion", True) else None
         bank, weights = kw.pop("instance_bank", None), kw.pop("instance_sampling_weights", None)
         if getattr(config, "sample_tail_instances", False) and kw.get("tail_instances") is None:
@@ -533,6 +616,24 @@ class DeviceAugmentation:
                    rotation_axis=DatasetClass.ROTATION_AXIS, color_trans_ratio=config.data_aug_color_trans_ratio,
                    color_jitter_std=config.data_aug_color_jitter_std, color_scale=config.data_aug_color_scaling_factor,
                    normalize_color=config.normalize_color, **kw)
+
+    @classmethod
+    def from_insseg_dataset(cls, DatasetClass, config, **kw):
+        """The chain the instance-segmentation recipe describes (downstream/insseg/datasets/dataset.py:471-541 with augment_data):
+        ElasticDistortion whenever the class has parameters (there is no elastic_distortion flag there), the voxeliser of
+        dataset.py:244-252, then RandomDropout(0.2) FIRST, flip, autocontrast, translation, jitter; no ChromaticScale; the per-sample
+        coordinate shift of dataset.py:330-332.  config: the recipe's nested config (config.augmentation.*)."""
+        if getattr(DatasetClass, "CLIP_BOUND", None) is not None:
+            kw.setdefault("clip_bound", DatasetClass.CLIP_BOUND)
+        a = config.augmentation
+        kw.setdefault("dropout", 0.2)
+        kw.setdefault("dropout_position", "first")
+        kw.setdefault("coordinate_shift", True)
+        return cls(voxel_size=DatasetClass.VOXEL_SIZE, elastic_params=DatasetClass.ELASTIC_DISTORT_PARAMS,
+                   rotation_bound=DatasetClass.ROTATION_AUGMENTATION_BOUND, scale_bound=DatasetClass.SCALE_AUGMENTATION_BOUND,
+                   rotation_axis=DatasetClass.ROTATION_AXIS, color_trans_ratio=a.data_aug_color_trans_ratio,
+                   color_jitter_std=a.data_aug_color_jitter_std, color_scale=1.0,
+                   normalize_color=bool(getattr(a, "normalize_color", False)), **kw)
 
     def draw(self, batch_size):
         """Every decision the reference draws with random.random() / np.random.uniform, for each scene of a batch."""
@@ -552,8 +653,9 @@ class DeviceAugmentation:
         seed = int(r.integers(0, 1 << 63))
         shift = np.floor(r.random(3) * 100).astype(np.int64) if self.coordinate_shift else np.zeros(3, np.int64)
         paste = self.tail.draw(B) if self.tail is not None else None          # from the paste's own generator
+        dropout = r.random(B) < self.dropout if self.dropout is not None else None      # last: the stream before it is unchanged
         return AugmentPlan(elastic, flip_axes, autocontrast, blend, translate, translation, jitter, angles, order, scale, matrices,
-                           scene_seeds, seed, shift, rotations=rotations, paste=paste)
+                           scene_seeds, seed, shift, rotations=rotations, paste=paste, dropout=dropout)
 
     def color_params(self, plan):
         return [ColorParams(blend=float(plan.blend[s]) if plan.autocontrast[s] else None,
@@ -570,7 +672,10 @@ class DeviceAugmentation:
         pasted rows have no scene instance id.
         elastic_noise: per stage a list of per-scene noise arrays; jitter_noise: callable(n) or device [n, 3] normals (teacher-forced).
         With tail_instances: scene_boxes (per scene a host [m_s, 2, 3] array of the scene's instance boxes, world units) and
-        optionally trial_draws, as paste_instances takes them; the voxeliser then applies M_v only and the paste rotates."""
+        optionally trial_draws, as paste_instances takes them; the voxeliser then applies M_v only and the paste rotates.
+        With dropout: a batch in which plan.dropout names a scene makes one more host read (the selection's B + 1 output offsets).
+        return_state then also has "dropout_rows" (the selection: input rows in first position, where they are state["keep"] too;
+        voxel rows in last position; None if no scene dropped) and "dedup_keep" (the dedup's rows before any dropout)."""
         if instances is not None and self.tail is not None:
             raise NotImplementedError("DeviceAugmentation: instances= together with tail_instances is not part of the device chain "
                                       "(pasted rows have no scene instance id; DESIGN.md section 8)")
@@ -588,6 +693,8 @@ class DeviceAugmentation:
         plan = self.draw(B) if plan is None else plan
         if self.tail is not None and (plan.paste is None or plan.rotations is None):
             raise ValueError("DeviceAugmentation: the plan has no paste decisions (draw it from this chain)")
+        if self.dropout is not None and plan.dropout is None:
+            raise ValueError("DeviceAugmentation: the plan has no dropout decisions (draw it from this chain)")
         state = {"status": [], "stages": []}
         feats_in, labels_in = None, labels
         previous = torch.cuda.get_sync_debug_mode()
@@ -623,6 +730,18 @@ class DeviceAugmentation:
             torch.cuda.set_sync_debug_mode(previous)
         from .me.utils import sparse_quantize
         keep = sparse_quantize(coords, return_maps_only=True)          # first occurrence wins, indices ascending (one host sync)
+        dropping = self.dropout is not None and bool(np.asarray(plan.dropout).any())
+        rows = None                   # dropout's selection: rows of the input ("first") or of the voxel rows ("last")
+        if dropping:
+            drop = dict(apply=plan.dropout, ratio=self.dropout, seed=plan.seed, scene_seeds=plan.scene_seeds)
+        if dropping and self.dropout_position == "first":
+            # the dedup keeps ascending input rows and the input's scenes are contiguous: voxel row offsets = positions of the input's
+            # scene offsets in `keep`.  The selection composes with `keep`, so every later gather is the one the chain makes anyway
+            off_in = off_dev if self.tail is None else _upload(np.asarray(off_p, np.int64), dev)
+            off_rows = torch.searchsorted(keep, off_in)
+            state["dedup_keep"] = keep
+            rows, _ = random_dropout_rows(off_rows, keep.shape[0], through=keep, **drop)      # (the chain's second host sync)
+            keep = rows
         coords, off_vox = horizontal_flip(coords.index_select(0, keep), plan.flip_axes, shift=plan.shift, batch_size=B, return_offsets=True)
         feats = (colors.detach().to(torch.float32) if feats_in is None else feats_in).index_select(0, keep)
         if callable(jitter_noise):
@@ -632,7 +751,12 @@ class DeviceAugmentation:
         out = (coords, feats, labels_in.index_select(0, keep).to(labels.dtype))
         if instances is not None:
             out += (instances.index_select(0, keep),)
+        if dropping and self.dropout_position == "last":
+            rows, _ = random_dropout_rows(off_vox, coords.shape[0], **drop)                    # (the chain's second host sync)
+            out = tuple(t.index_select(0, rows) for t in out)
         if return_state:
             state["points"], state["keep"] = pts, keep
+            state.setdefault("dedup_keep", keep)
+            state["dropout_rows"] = rows
             return out + (state,)
         return out

@@ -126,6 +126,24 @@ inline PasteWs paste_layout(int b, int slots, int64_t inst_rows, int64_t max_map
   return w;
 }
 
+// lgs_dropout.hip: one record per scene, one table of 2048 64-bit bins per (digit, scene), and two words per tile.  A tile is
+// kDropTile rows of one scene, so n rows in b scenes make at most n / kDropTile + b of them
+constexpr int kDropTile = 2048;
+constexpr int kDropSceneBytes = 24;    // sizeof(DropScene)
+constexpr int64_t kDropMaxRows = 1ll << 40;
+struct DropoutWs { int64_t scenes, hist, tile_lt, tile_eq, total, tiles; };
+inline DropoutWs dropout_layout(int64_t n, int b) {
+  Layout l;
+  DropoutWs w;
+  w.tiles = n / kDropTile + b;
+  w.scenes = l.take((int64_t)kDropSceneBytes * b);
+  w.hist = l.take((int64_t)sizeof(uint64_t) * 3 * b * 2048);
+  w.tile_lt = l.take((int64_t)sizeof(int64_t) * w.tiles);
+  w.tile_eq = l.take((int64_t)sizeof(int64_t) * w.tiles);
+  w.total = l.total();
+  return w;
+}
+
 // ---- 2. pure functions ----------------------------------------------------------------------------------------------------------
 // Binary searches over p[lo, hi), non-decreasing.  I is the index type of the caller (int or int64_t).
 // the first index whose element is not below k (hi if there is none)

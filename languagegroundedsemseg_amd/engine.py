@@ -239,6 +239,7 @@ EXPORTS = [
     "lgs_aug_bounds", "lgs_elastic_workspace_bytes", "lgs_elastic_distort", "lgs_voxelize_batched", "lgs_coords_flip_shift",
     "lgs_color_augment", "lgs_aug_status", "lgs_debug_philox",
     "lgs_paste_workspace_bytes", "lgs_paste_instances",
+    "lgs_dropout_workspace_bytes", "lgs_dropout_select",
 ]
 
 
@@ -347,6 +348,7 @@ def lib():
         "lgs_debug_philox": [vp, i64, i64, vp, vp],
         "lgs_paste_instances": [vp, vp, vp, i64, ci, vp, vp, vp, i64, vp, vp, ci, i64, vp, vp, vp, i64, vp, ci, i64, i64, vp, vp, vp, vp,
                                 vp, vp, vp],
+        "lgs_dropout_select": [vp, i64, ci, ci, ctypes.c_double, i64, ctypes.POINTER(ctypes.c_int32), vp, vp, vp, vp, vp, vp],
         "lgs_comm_unique_id": [vp],
         "lgs_comm_create": [vp, ci, ci, ci, ctypes.POINTER(vp)],
         "lgs_comm_create_ipc": [ci, ci, ci, ctypes.POINTER(vp), vp],
@@ -377,6 +379,8 @@ def lib():
     L.lgs_elastic_workspace_bytes.argtypes = [ci, i64]
     L.lgs_paste_workspace_bytes.restype = i64
     L.lgs_paste_workspace_bytes.argtypes = [ci, ci, i64, i64]
+    L.lgs_dropout_workspace_bytes.restype = i64
+    L.lgs_dropout_workspace_bytes.argtypes = [i64, ci]
     L.lgs_cluster_workspace_bytes.restype = i64
     L.lgs_cluster_workspace_bytes.argtypes = [i64]
     L.lgs_conv_workspace_bytes.restype = i64

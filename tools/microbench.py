@@ -1,5 +1,5 @@
 """Per-op timings on the GPU (HIP events on torch's current stream) for the hot layer shapes.
-usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal | supcon | augment | paste | nearest | ap | lean]"""
+usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal | supcon | augment | paste | dropout | nearest | ap | lean]"""
 import os
 import re
 import sys
@@ -889,6 +889,83 @@ def paste():
           % (len(v0), t_cpu * 1e3, 8 * t_cpu * 1e3, t_call))
 
 
+def dropout():
+    """RandomDropout on the device (csrc/lgs_dropout.hip) on the benchmark's 8-scene, 1.2 M-voxel batch: the selection alone, the chain
+    with dropout first against the same chain without it, torch's randperm formulation per scene on the same device, and
+    np.random.choice on one host core for one scene.  Device events around 200 back-to-back calls."""
+    from languagegroundedsemseg_amd import augment as A
+    coords, feats, labels = make_batch(list(range(8)), n_target=150000, shift_seed=0)
+    rng = np.random.default_rng(0)
+    order = np.argsort(coords[:, 0], kind="stable")
+    coords, labels = coords[order], labels[order]
+    sizes = np.bincount(coords[:, 0], minlength=8)
+    off_h = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    nv = int(off_h[-1])
+    off_v = torch.from_numpy(off_h).to(DEV)
+    seeds = list(range(1, 9))
+    every = [True] * 8
+    print("%d voxel rows in 8 scenes (%d .. %d per scene), ratio 0.2, every scene drops" % (nv, sizes.min(), sizes.max()))
+
+    def show(name, ms):
+        print("%-64s %8.3f ms per batch" % (name, ms))
+    rows, o = A.random_dropout_rows(off_v, nv, every, ratio=0.2, seed=7, scene_seeds=seeds)
+    assert np.diff(o.host).tolist() == [int(n * (1 - 0.2)) for n in sizes] and bool((rows[1:] > rows[:-1]).all())
+    show("lgs_dropout_select alone (11 launches, nothing read back)",
+         timeit(lambda: A._dropout_select(off_v, nv, every, 0.2, 7, seeds, None, None), iters=200, warm=5))
+    show("random_dropout_rows (the call and its read of 9 offsets)",
+         timeit(lambda: A.random_dropout_rows(off_v, nv, every, ratio=0.2, seed=7, scene_seeds=seeds), iters=200, warm=5))
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            for _ in range(10):
+                A._dropout_select(off_v, nv, every, 0.2, 7, seeds, None, None)
+            torch.cuda.synchronize()
+        for ev in sorted(prof.key_averages(), key=lambda e: e.key):
+            if "k_drop" in ev.key:
+                us = getattr(ev, "device_time_total", None) or getattr(ev, "cuda_time_total", 0.0)
+                print("  %-62s %8.1f us per call (%d launches)" % (re.search(r"k_[a-z_]+(<[^>]*>)?", ev.key).group(0), us / 10.0, ev.count // 10))
+    except Exception as e:      # the profiler is a convenience: the call's own time above stands without it
+        print("  (no per-kernel times: %s)" % e)
+    ks = [int(n * (1 - 0.2)) for n in sizes]
+
+    def torch_formulation():
+        return [torch.randperm(int(n), device=DEV)[:k].sort()[0] for n, k in zip(sizes, ks)]
+    show("torch.randperm(n_s, device)[:k].sort() per scene, 8 scenes", timeit(torch_formulation, iters=200, warm=5))
+    # the chain, raw points before the dedup (~2 per voxel), as `augment` builds them
+    rep = np.repeat(coords, 2, 0)
+    pts = ((rep[:, 1:].astype(np.float64) + rng.uniform(0.05, 0.95, (rep.shape[0], 3))) * 0.02).astype(np.float32)
+    off = np.concatenate([[0], np.cumsum(np.bincount(rep[:, 0], minlength=8))]).tolist()
+    for s in range(8):
+        pts[off[s]:off[s + 1]] -= pts[off[s]:off[s + 1]].min(0)
+    cols = np.floor(rng.random(pts.shape) * 256).astype(np.float32)
+    p, c, lab = torch.from_numpy(pts).to(DEV), torch.from_numpy(cols).to(DEV), torch.from_numpy(np.repeat(labels, 2)).to(DEV)
+    kw = dict(voxel_size=0.02, rotation_bound=((-np.pi / 64, np.pi / 64), (-np.pi / 64, np.pi / 64), (-np.pi, np.pi)), scale_bound=(0.9, 1.1),
+              normalize_color=True, seed=1)
+    plain, first, last = A.DeviceAugmentation(**kw), A.DeviceAugmentation(dropout=0.2, dropout_position="first", **kw), \
+        A.DeviceAugmentation(dropout=0.2, dropout_position="last", **kw)
+    plan = first.draw(8)
+    plan.elastic[:], plan.autocontrast[:], plan.translate[:], plan.jitter[:], plan.dropout[:] = True, True, True, True, True
+    plan.flip_axes[:] = 3
+    t_plain = timeit(lambda: plain(p, c, lab, off, plan=plan), iters=200, warm=5)
+    t_first = timeit(lambda: first(p, c, lab, off, plan=plan), iters=200, warm=5)
+    t_last = timeit(lambda: last(p, c, lab, off, plan=plan), iters=200, warm=5)
+    show("chain without dropout (%d points)" % p.shape[0], t_plain)
+    show("chain with dropout first, every scene drops", t_first)
+    print("%-64s %+8.3f ms" % ("  difference (selection, second read; fewer rows afterwards)", t_first - t_plain))
+    show("chain with dropout last, every scene drops", t_last)
+    print("%-64s %+8.3f ms" % ("  difference (selection, second read, three gathers)", t_last - t_plain))
+    # the reference's own call on one host core, one scene
+    torch.set_num_threads(1)
+    n0 = int(sizes.max())
+    np.random.seed(0)
+    t0 = time.perf_counter()
+    for _ in range(20):
+        np.random.choice(n0, int(n0 * (1 - 0.2)), replace=False)
+    t_cpu = (time.perf_counter() - t0) / 20
+    print("np.random.choice(%d, %d, replace=False), 1 host thread: %.2f ms per scene (x 8 scenes = %.1f ms per batch), without the gathers"
+          % (n0, int(n0 * 0.8), t_cpu * 1e3, 8 * t_cpu * 1e3))
+
+
 def nearest():
     """lgs_manager_nearest at the evaluation shape -- 8 scenes x ~150 k voxels, three points inside every occupied cell -- at
     NEAREST_MAX_RING 1, 2 and 4, anchors 0.0 and 0.5, with both lookup tables, and the share of queries that the ring search leaves to
@@ -1147,6 +1224,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "augment":
         augment()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "dropout":
+        dropout()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "paste":
         paste()
