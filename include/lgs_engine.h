@@ -975,6 +975,7 @@ int lgs_supcon_backward(const void *feat, int64_t n, int c, const int64_t *label
 #define LGS_AUG_STAGE_COLOR 16
 #define LGS_AUG_STAGE_PASTE 17          /* the tail-instance paste's trial draws (below) */
 #define LGS_AUG_STAGE_DROPOUT 18        /* RandomDropout's row keys (below) */
+#define LGS_AUG_STAGE_INSTSHIFT 19      /* the per-instance colour / scale decisions (below) */
 #define LGS_PASTE_MAX_SLOTS 1024
 #define LGS_PASTE_SLOT_COLS 6
 #define LGS_PASTE_SCENE_COLS 4
@@ -1074,6 +1075,52 @@ int64_t lgs_dropout_workspace_bytes(int64_t n, int b);
 int lgs_dropout_select(const int64_t *scene_offsets, int64_t n, int b, unsigned int apply_mask, double keep, int64_t seed,
                        const int32_t *scene_seeds, const int32_t *keys, const int64_t *through, void *workspace, int64_t *rows_out,
                        int64_t *offsets_out, void *stream);
+
+/* ---- per-instance colour and scale shifts (csrc/lgs_instshift.hip) -------------------------------
+ * replaces: ScannetVoxelizationDataset.augment_instances (lib/datasets/scannet.py:243-319, instance_augmentation == 'raw') with
+ *   InstanceAugmentation (lib/transforms.py:288-382): per tail instance of a scene one boolean mask over the cloud, a colour or a
+ *   scale shift with the attribute it is named by, and the np.delete / np.vstack that moves every tail instance to the end.
+ * NEW SYMBOLS ONLY: LGS_ABI_VERSION stays 18; a library that lacks them lacks the capability.
+ * A batch is 1 <= b <= LGS_AUG_MAX_SCENES scenes of n rows in all (n < 2^31 - 1), scene_offsets DEVICE int64 [b + 1] as above (entries
+ * are clamped into a non-decreasing table on [0, n]); points / colors DEVICE float32 [n, 3] (colours in 0 .. 255), labels /
+ * instance_ids DEVICE int64 [n]; scene_bounds DEVICE float32 [b, 6], lgs_aug_bounds over `points`.  tail_labels: HOST int64
+ * [n_tail], n_tail <= 256, any order.
+ *   segment    the rows of one scene that share (label in tail_labels, instance id), 0 <= id < 2^31.  A row with id -1 or an id
+ *              outside that range is in no segment (the reference would group such rows: a deviation); the latter sets bit `scene`
+ *              of status[1].  Segments are ordered by (scene, label, id).
+ *   decision   one per segment: attribute 0 (nothing), 1 .. 6 (colour: Red, Green, Blue, Yellow, Dark, Bright), 7 / 8 (scale up /
+ *              down) and a factor f.  forced_keys (DEVICE int64 [n_forced, 3] = (scene, label, id)) with forced_attr (DEVICE int32)
+ *              and forced_factor (DEVICE double) replaces the draws when not NULL; a segment it does not list gets 0.  Otherwise the
+ *              Philox-4x32-10 block with counter (id, label & 2^32-1, label >> 32, LGS_AUG_STAGE_INSTSHIFT ^ seed >> 32) and key
+ *              (seed & 2^32-1, scene_seeds[s]) (scene_seeds: HOST int32 [b] or NULL), u_k = word_k / 2^32 in double:
+ *              u_0 < color_prob -> colour 1 + floor(6 u_2); else u_1 < scale_prob -> up iff 2 u_2 > 1, f = 1 + (h - 1) u_3 with
+ *              h = min(1.5, min over the axes of fl32(scene extent / segment extent), inf and NaN quotients skipped), or down,
+ *              f = 0.5 + 0.5 u_3 (double, every operation rounded).
+ *   colour     Dark trunc(c 0.5); Bright trunc(255 - (255 - c) / 2), fp32.  The four hues, hue_as_written != 0 (the reference's
+ *              hsv_to_rgb casts values in [0, 1] to uint8): a channel is 255 iff the row's maximum is 255 and (the channel is in the
+ *              hue's set {r}, {g}, {b}, {r, g} or r == g == b), else 0.  hue_as_written == 0: the set's channels get max(r, g, b),
+ *              the others min(r, g, b).
+ *   scale      p' = fl32(fl32(p fl32(f)) + fl32(c fl32(1 - f))), c = ((lo_x + hi_x) / 2, (lo_y + hi_y) / 2, lo_z) over the segment's
+ *              rows before scaling, 1 - f in double.
+ *   output     per scene: the rows of no segment, ascending, then the segments in order, each with its rows ascending (the
+ *              reference's row order; the dedup that follows lets the first occurrence win).  order (DEVICE int64 [n]) = the
+ *              source row of every output row; points_out / colors_out [n, 3], labels_out int64 [n, 2] = (label, attribute),
+ *              instances_out int64 [n].  Outputs may not alias inputs.
+ * status: DEVICE int32 [2] of scene bits, OR-ed, never cleared here (read with lgs_aug_status, word by word).  status[0]: scenes
+ *   left exactly as they were (identity order, attribute 0) because they hold a segment whose rank among the batch's segments is
+ *   >= seg_cap (1 .. 65536); every scene, if the batch has more distinct segments than the table's 2^k >= 2 seg_cap entries.
+ * How: per-workgroup LDS tables folded into one open-addressing table by integer atomics (count, order-preserving min / max keys),
+ *   ranks by counting keys, one stable radix sort of (scene, rank) keys over the bits they use, one streaming gather.  The result
+ *   does not depend on any launch grid, two calls give the same bits, nothing is read back.
+ * workspace: lgs_instance_shift_workspace_bytes(n, b, seg_cap) bytes (0 = bad shape, or no device to size rocPRIM's temporary
+ *   for: the query launches nothing but asks the current device); the call initialises what it reads of it. */
+int64_t lgs_instance_shift_workspace_bytes(int64_t n, int b, int seg_cap);
+int lgs_instance_shift(const float *points, const float *colors, const int64_t *labels, const int64_t *instance_ids, int64_t n,
+                       const int64_t *scene_offsets, int b, const float *scene_bounds, const int64_t *tail_labels, int n_tail,
+                       double color_prob, double scale_prob, int64_t seed, const int32_t *scene_seeds, const int64_t *forced_keys,
+                       const int32_t *forced_attr, const double *forced_factor, int n_forced, int hue_as_written, int seg_cap,
+                       void *workspace, float *points_out, float *colors_out, int64_t *labels_out, int64_t *instances_out,
+                       int64_t *order, int32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

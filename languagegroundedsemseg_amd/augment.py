@@ -20,8 +20,13 @@ With `dropout=ratio` the chain also runs RandomDropout (csrc/lgs_dropout.hip): w
 random int(n * (1 - ratio)) of its voxel rows, as the last transform (lib/dataset.py:385-386) or the first (`dropout_position="first"`,
 downstream/insseg/datasets/dataset.py:505; `DeviceAugmentation.from_insseg_dataset` builds that recipe's chain).
 
-Out of scope, refused by name: HueSaturationTranslation, the clip bound, instance augmentation (the raw / latent
-colour and scale shifts of augment_instances), the paired voxeliser."""
+With `instance_shifts=InstanceShifts(tail_labels, ...)` the chain also runs the reference's per-instance colour and scale shifts
+(instance_augmentation == 'raw', lib/datasets/scannet.py:243-319 with lib/transforms.py:288-382; csrc/lgs_instshift.hip) between the
+elastic stages and the voxeliser: every tail instance of a scene gets nothing, a colour shift or a scale shift, its rows move behind
+the scene's other rows, and the labels come back as [n, 2] = (category, attribute).
+
+Out of scope, refused by name: HueSaturationTranslation, the clip bound, the `instance_augmentation` keyword
+(the raw shifts are instance_shifts=; the latent mode lives in the loss), instance shifts of pasted instances, the paired voxeliser."""
 import collections
 import ctypes
 import dataclasses
@@ -69,8 +74,9 @@ def aug_bounds(table, scene_offsets=None, batch_size=None):
 
 
 def aug_status(status):
-    """Reads the device status words of an elastic or paste call (this SYNCHRONISES) -> scenes whose noise grid exceeded max_cells
-    (elastic) / that were left unpasted (paste)"""
+    """Reads the device status words of an elastic, paste or instance-shift call (this SYNCHRONISES) -> scenes whose noise grid
+    exceeded max_cells (elastic) / that were left unpasted (paste) / that were left unshifted because the batch has more than seg_cap
+    segments (instance_shifts: word 0 of its status; instance_shift_status reads both words)"""
     out = []
     if isinstance(status, torch.Tensor):          # one word: what paste_instances returns
         status = [status]
@@ -331,6 +337,116 @@ def random_dropout(coords, feats, labels, instances=None, scene_offsets=None, n=
     return out + (rows, offsets)
 
 
+DEFAULT_SEG_CAP = 4096                # segments (scene, tail label, instance id) per batch of instance_shifts
+
+
+def _tail_labels(tail_labels, who):
+    tail = sorted({int(v) for v in np.asarray(list(tail_labels)).reshape(-1).tolist()})
+    if len(tail) > engine.LGS_INSTSHIFT_MAX_TAIL:
+        raise ValueError("%s: tail_labels holds %d labels, more than %d" % (who, len(tail), engine.LGS_INSTSHIFT_MAX_TAIL))
+    return tail
+
+
+def _check_shift_args(color_prob, scale_prob, seg_cap, who):
+    if not (0.0 <= float(color_prob) <= 1.0 and 0.0 <= float(scale_prob) <= 1.0):
+        raise ValueError("%s: color_prob and scale_prob must lie in [0, 1], got %r and %r" % (who, color_prob, scale_prob))
+    if not 1 <= int(seg_cap) <= engine.LGS_INSTSHIFT_MAX_CAP:
+        raise ValueError("%s: seg_cap must be in 1 .. %d, got %r" % (who, engine.LGS_INSTSHIFT_MAX_CAP, seg_cap))
+
+
+def instance_shifts(points, colors, labels, instances, scene_offsets, tail_labels, color_prob, scale_prob, seed=0, scene_seeds=None,
+                    scene_bounds=None, forced=None, hue_as_written=True, seg_cap=DEFAULT_SEG_CAP):
+    """augment_instances (instance_augmentation == 'raw') on every scene of a batch (csrc/lgs_instshift.hip), without a host
+    synchronisation.  points [n, 3], colors [n, 3] (0 .. 255), labels [n] (raw category ids), instances [n] (HIP tensors);
+    scene_offsets: B + 1 host integers or a device int64 tensor, B <= 32; tail_labels: at most 256 category ids.
+    A segment is the rows of one scene that share (label in tail_labels, instance id in [0, 2^31)).  Each gets one decision, a function
+    of (seed, scene_seeds[s], label, id) alone: with probability color_prob a colour shift (attribute 1 .. 6: Red, Green, Blue, Yellow,
+    Dark, Bright, uniform), else with probability scale_prob a scale shift about the box's (centre x, centre y, lowest z) (7 up, by at
+    most min(1.5, what the scene's extent allows); 8 down, to at least 0.5), else nothing (0).  forced = (keys [m, 3] = (scene, label,
+    id), attribute [m], factor [m] float64), host arrays, replaces the draws (teacher-forced); a segment it does not list gets 0.
+    hue_as_written: the four hue shifts as the reference computes them (channels become 0 or 255); False: the evident intent.
+    scene_bounds: device float32 [B, 6] as aug_bounds / the elastic stage return it; computed with aug_bounds when absent.
+    -> (points [n, 3], colors [n, 3], labels2 [n, 2] int64 = (category, attribute), instances [n] int64, order [n] int64, status):
+    per scene its rows of no segment, ascending, then the segments ascending by (label, id), rows ascending -- the reference's
+    np.delete / np.vstack order; order[j] is the input row of output row j.  status: device int32 [2] of scene bits
+    (instance_shift_status reads them): word 0, scenes left exactly as they were because the batch has more than seg_cap segments;
+    word 1, scenes with a tail row whose id is neither -1 nor in [0, 2^31) (such rows, and rows with id -1, are in no segment)."""
+    for t, what in ((points, "points"), (colors, "colors"), (labels, "labels"), (instances, "instances")):
+        require_hip(t, what)
+    tail = _tail_labels(tail_labels, "instance_shifts")
+    _check_shift_args(color_prob, scale_prob, seg_cap, "instance_shifts")
+    dev = points.device
+    pts = points.detach().to(torch.float32).contiguous()
+    col = colors.detach().to(torch.float32).contiguous()
+    lab = labels.detach().to(torch.int64).contiguous()
+    ids = instances.detach().to(torch.int64).contiguous()
+    n = pts.shape[0]
+    if pts.shape != (n, 3) or col.shape != (n, 3) or lab.shape != (n,) or ids.shape != (n,):
+        raise ValueError("instance_shifts: points and colors must be [n, 3], labels and instances [n]")
+    L = engine.lib()
+    with on_device(dev):
+        if isinstance(scene_offsets, torch.Tensor) and scene_offsets.is_cuda:
+            off_dev = scene_offsets.to(torch.int64).contiguous()
+        else:
+            off_dev = _upload(np.asarray(host_offsets(scene_offsets, n), np.int64), dev)
+        b = off_dev.shape[0] - 1
+        if off_dev.dim() != 1 or not 1 <= b <= MAX_SCENES:
+            raise ValueError("instance_shifts takes 1 .. %d scenes per call" % MAX_SCENES)
+        scene_seeds = [0] * b if scene_seeds is None else list(scene_seeds)
+        if len(scene_seeds) != b:
+            raise ValueError("instance_shifts: scene_seeds takes one value per scene (%d)" % b)
+        if scene_bounds is None:
+            scene_bounds, _ = aug_bounds(pts, off_dev)
+        require_hip(scene_bounds, "scene_bounds")
+        if scene_bounds.dtype != torch.float32 or tuple(scene_bounds.shape) != (b, 6):
+            raise ValueError("instance_shifts: scene_bounds must be float32 [B, 6]")
+        scene_bounds = scene_bounds.contiguous()
+        f_keys = f_attr = f_fac = None
+        m = 0
+        if forced is not None:
+            keys = np.asarray(forced[0], np.int64).reshape(-1, 3)
+            attr, fac = np.asarray(forced[1], np.int32).reshape(-1), np.asarray(forced[2], np.float64).reshape(-1)
+            m = keys.shape[0]
+            if attr.shape[0] != m or fac.shape[0] != m or (attr < 0).any() or (attr > 8).any():
+                raise ValueError("instance_shifts: forced = (keys [m, 3], attribute [m] in 0 .. 8, factor [m])")
+            if m == 0:                # an empty table still forces: every segment gets attribute 0
+                keys, attr, fac = np.zeros((1, 3), np.int64), np.zeros(1, np.int32), np.ones(1, np.float64)
+            f_keys, f_attr, f_fac = _upload(keys, dev), _upload(attr, dev), _upload(fac, dev)
+        nbytes = int(L.lgs_instance_shift_workspace_bytes(n, b, int(seg_cap)))
+        if nbytes <= 0:
+            raise ValueError("instance_shifts: bad shape (n = %d rows, %d scenes, seg_cap = %d)" % (n, b, seg_cap))
+        ws = scratch(nbytes, dev)          # (lgs_instance_shift initialises what it reads of it)
+        pts_out, col_out = torch.empty_like(pts), torch.empty_like(col)
+        lab_out = torch.empty((n, 2), dtype=torch.int64, device=dev)
+        ids_out, order = torch.empty_like(ids), torch.empty(n, dtype=torch.int64, device=dev)
+        status = torch.zeros(2, dtype=torch.int32, device=dev)
+        tail_c = (ctypes.c_int64 * max(len(tail), 1))(*tail)
+        seeds = (ctypes.c_int32 * b)(*[i32(v) for v in scene_seeds])
+        engine.check(L.lgs_instance_shift(ptr(pts), ptr(col), ptr(lab), ptr(ids), n, ptr(off_dev), b, ptr(scene_bounds), tail_c, len(tail),
+                                          float(color_prob), float(scale_prob), i64(seed), seeds, ptr(f_keys), ptr(f_attr), ptr(f_fac), m,
+                                          int(bool(hue_as_written)), int(seg_cap), ptr(ws), ptr(pts_out), ptr(col_out), ptr(lab_out),
+                                          ptr(ids_out), ptr(order), ptr(status), raw_stream()))
+    return pts_out, col_out, lab_out, ids_out, order, status
+
+
+def instance_shift_status(status):
+    """Reads both status words of an instance_shifts call (this SYNCHRONISES)
+    -> {"unshifted": scenes left as they were (more than seg_cap segments), "id_range": scenes with a tail row whose id is out of range}"""
+    return {"unshifted": aug_status(status[0:1]), "id_range": aug_status(status[1:2])}
+
+
+class InstanceShifts:
+    """The per-instance colour and scale shifts of the reference's long-tail recipe (instance_augmentation == 'raw') as a stage of
+    DeviceAugmentation: the raw category ids that count as tail, and the reference's two probabilities
+    (config.instance_augmentation_color_aug_prob / _scale_aug_prob; the defaults are the config's).  See instance_shifts."""
+
+    def __init__(self, tail_labels, color_prob=0.5, scale_prob=0.2, hue_as_written=True, seg_cap=DEFAULT_SEG_CAP):
+        self.tail_labels = _tail_labels(tail_labels, "InstanceShifts")
+        _check_shift_args(color_prob, scale_prob, seg_cap, "InstanceShifts")
+        self.color_prob, self.scale_prob = float(color_prob), float(scale_prob)
+        self.hue_as_written, self.seg_cap = bool(hue_as_written), int(seg_cap)
+
+
 # ---- the chain
 @dataclasses.dataclass
 class AugmentPlan:
@@ -558,17 +674,23 @@ class DeviceAugmentation:
     the drawn instances -> M_r + floor of every row (paste_instances); the dedup after it is still the chain's only one.
     With dropout (a ratio) a scene drops rows with probability `ratio` (the reference's application probability IS the ratio):
     dropout_position "last" selects after the colour stage (lib/dataset.py:385-386: colour statistics over all rows), "first" right
-    after the dedup (insseg dataset.py:505: flip and autocontrast see the surviving rows only)."""
+    after the dedup (insseg dataset.py:505: flip and autocontrast see the surviving rows only).
+    With instance_shifts (an InstanceShifts) the per-instance colour and scale shifts run between the elastic stages and the
+    voxeliser, on the plan's seed and scene seeds (no new host draw): the voxeliser, the dedup and every later stage see the shifted,
+    reordered rows, __call__ needs instances= and the labels come back as [n, 2] = (category, attribute)."""
 
     def __init__(self, voxel_size, elastic_params=((0.2, 0.4), (0.8, 1.6)), rotation_bound=None, scale_bound=None, rotation_axis="z",
                  color_trans_ratio=0.1, color_jitter_std=0.05, color_scale=1.0, normalize_color=False, coordinate_shift=False,
                  max_cells=DEFAULT_MAX_CELLS, seed=0, random_dropout=None, hue_saturation=None, clip_bound=None,
-                 instance_augmentation=None, num_pairs=1, tail_instances=None, dropout=None, dropout_position="last"):
+                 instance_augmentation=None, num_pairs=1, tail_instances=None, dropout=None, dropout_position="last",
+                 instance_shifts=None):
         given = dict(random_dropout=random_dropout, hue_saturation=hue_saturation, clip_bound=clip_bound,
                      instance_augmentation=instance_augmentation)
         for name in _REFUSED:
             if given[name] is not None:
-                hint = "; RandomDropout on the device is dropout=ratio" if name == "random_dropout" else ""
+                hint = {"random_dropout": "; RandomDropout on the device is dropout=ratio",
+                        "instance_augmentation": "; the raw colour / scale shifts on the device are instance_shifts=InstanceShifts(...)"
+                        }.get(name, "")
                 raise NotImplementedError("DeviceAugmentation: %s is not part of the device chain (DESIGN.md section 8)%s" % (name, hint))
         if num_pairs != 1:
             raise NotImplementedError("DeviceAugmentation: the paired voxeliser (num_pairs == 2) is not part of the device chain")
@@ -585,6 +707,12 @@ class DeviceAugmentation:
         self.max_cells = int(max_cells)
         self.rng = np.random.default_rng(seed)
         self.tail = tail_instances
+        self.shifts = instance_shifts
+        if self.shifts is not None and not isinstance(self.shifts, InstanceShifts):
+            raise ValueError("DeviceAugmentation: instance_shifts must be an InstanceShifts, got %r" % type(instance_shifts).__name__)
+        if self.shifts is not None and self.tail is not None:
+            raise NotImplementedError("DeviceAugmentation: instance_shifts together with tail_instances is not part of the device chain "
+                                      "(the pasted instances would need their own shifts and the two-column label; DESIGN.md section 8)")
         self.dropout = None if dropout is None else float(dropout)
         if self.dropout is not None and not 0.0 <= self.dropout < 1.0:
             raise ValueError("DeviceAugmentation: dropout must be a ratio in [0, 1), got %r" % dropout)
@@ -603,6 +731,13 @@ class DeviceAugmentation:
             kw.setdefault("random_dropout", 0.2)          # lib/dataset.py:385 adds RandomDropout in that case only: say dropout=0.2
         elastic = DatasetClass.ELASTIC_DISTORT_PARAMS if getattr(config, "elastic_distortion", True) else None
         bank, weights = kw.pop("instance_bank", None), kw.pop("instance_sampling_weights", None)
+        tail_labels = kw.pop("tail_labels", None)
+        if getattr(config, "instance_augmentation", None) == "raw" and kw.get("instance_shifts") is None:
+            if tail_labels is None:
+                raise NotImplementedError("DeviceAugmentation: config.instance_augmentation == 'raw' needs tail_labels= (the raw category "
+                                          "ids that count as tail); without them the recipe would train without its instance shifts")
+            kw["instance_shifts"] = InstanceShifts(tail_labels, config.instance_augmentation_color_aug_prob,
+                                                   config.instance_augmentation_scale_aug_prob)
         if getattr(config, "sample_tail_instances", False) and kw.get("tail_instances") is None:
             if bank is None:
                 raise NotImplementedError("DeviceAugmentation: config.sample_tail_instances needs instance_bank= (the cropped training "
@@ -669,7 +804,8 @@ class DeviceAugmentation:
         -> (coords [n, 4] int32, feats [n, 3] float32, labels [n]) of the surviving voxel rows.
         instances: [N] per-point instance ids (a HIP tensor); they ride through the chain like the labels (the dedup's first
         occurrence wins) and come back as a fourth value, ready for instances.instance_info.  Refused together with tail_instances:
-        pasted rows have no scene instance id.
+        pasted rows have no scene instance id.  Required with instance_shifts; the labels then come back as [n, 2] = (category,
+        attribute) and return_state has "instance_shift_order" (the stage's row order) and "instance_shift_status".
         elastic_noise: per stage a list of per-scene noise arrays; jitter_noise: callable(n) or device [n, 3] normals (teacher-forced).
         With tail_instances: scene_boxes (per scene a host [m_s, 2, 3] array of the scene's instance boxes, world units) and
         optionally trial_draws, as paste_instances takes them; the voxeliser then applies M_v only and the paste rotates.
@@ -679,6 +815,8 @@ class DeviceAugmentation:
         if instances is not None and self.tail is not None:
             raise NotImplementedError("DeviceAugmentation: instances= together with tail_instances is not part of the device chain "
                                       "(pasted rows have no scene instance id; DESIGN.md section 8)")
+        if self.shifts is not None and instances is None:
+            raise ValueError("DeviceAugmentation: instance_shifts needs instances= (one instance id per point)")
         for t, what in ((points, "points"), (colors, "colors"), (labels, "labels")):
             require_hip(t, what)
         if instances is not None:
@@ -703,6 +841,7 @@ class DeviceAugmentation:
             with on_device(dev):
                 pts = points.detach().to(torch.float32).contiguous().clone()
                 off_dev = _upload(np.asarray(off, np.int64), dev)
+                bounds = None
                 if self.elastic_params and plan.elastic.any():
                     bounds, _ = aug_bounds(pts, off_dev)
                     ws = _elastic_workspace(B, self.max_cells, dev)
@@ -714,6 +853,12 @@ class DeviceAugmentation:
                         if return_state:
                             state["stages"].append(pts.clone())
                     state["status"].append(status)
+                if self.shifts is not None:
+                    sh = self.shifts
+                    pts, colors, labels_in, instances, order, sstatus = instance_shifts(
+                        pts, colors, labels, instances, off_dev, sh.tail_labels, sh.color_prob, sh.scale_prob, seed=plan.seed,
+                        scene_seeds=plan.scene_seeds, scene_bounds=bounds, hue_as_written=sh.hue_as_written, seg_cap=sh.seg_cap)
+                    state.update(instance_shift_order=order, instance_shift_status=sstatus)
                 if self.tail is None:
                     coords = voxelize_batched(pts, off, plan.matrices, offsets_dev=off_dev)
                 else:                 # lib/datasets/scannet.py:344-347: voxelise without augmentation, paste, then rotate

@@ -144,6 +144,21 @@ inline DropoutWs dropout_layout(int64_t n, int b) {
   return w;
 }
 
+// lgs_instshift.hip: rocPRIM's temporary of the row sort, the segment table of 2^k >= 2 seg_cap entries (key, row count, three minima
+// and three maxima as order-preserving keys, the entry's rank), one record per segment in rank order, two flag words, and per row the
+// segment (entry, then rank), the sort key, the sorted key and the sorted row
+constexpr int kInstShiftMaxCap = 65536;
+constexpr int kInstShiftMaxTail = 256;
+constexpr int kInstShiftSegBytes = 24;   // sizeof(ShiftSeg)
+inline uint32_t inst_shift_table_size(int seg_cap) { return (uint32_t)table_pow2(64, 2 * (int64_t)seg_cap); }
+struct InstShiftWs { int64_t tmp, t_key, t_cnt, t_lo, t_hi, t_row, segs, flags, slot, keys, skeys, srows, total; };
+inline InstShiftWs inst_shift_layout(int64_t n, int seg_cap, int64_t tmp_bytes) {
+  Layout l;
+  const int64_t t = inst_shift_table_size(seg_cap), v = 4 * (n + 1);
+  return {l.take(tmp_bytes), l.take(8 * t), l.take(4 * t), l.take(12 * t), l.take(12 * t), l.take(4 * t),
+          l.take((int64_t)kInstShiftSegBytes * seg_cap), l.take(256), l.take(v), l.take(v), l.take(v), l.take(v), l.total()};
+}
+
 // ---- 2. pure functions ----------------------------------------------------------------------------------------------------------
 // Binary searches over p[lo, hi), non-decreasing.  I is the index type of the caller (int or int64_t).
 // the first index whose element is not below k (hi if there is none)

@@ -1,7 +1,7 @@
 // lgs_philox.h -- the engine's one counter-based generator: Philox-4x32-10 (Salmon et al., SC'11), plain C++.
 // A block is a function of (counter, key) alone, so what a kernel draws does not depend on its grid.
 // Users: lgs_supcon.hip (sample indices), lgs_augment.hip (elastic noise, colour jitter), lgs_paste.hip (trial draws),
-// lgs_dropout.hip (row keys).
+// lgs_dropout.hip (row keys), lgs_instshift.hip (per-segment decisions).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -13,6 +13,7 @@ LGS_F32, LGS_BF16 = 0, 1
 LGS_SUPCON_COS, LGS_SUPCON_L2 = 0, 1     # `distance` of lgs_supcon_forward / lgs_supcon_backward
 LGS_AUG_MAX_SCENES = 32                  # scenes per call of the lgs_aug_* / lgs_elastic_* / lgs_color_* entry points
 LGS_AUG_F32X3, LGS_AUG_I32X4 = 0, 1      # `form` of lgs_aug_bounds
+LGS_INSTSHIFT_MAX_TAIL, LGS_INSTSHIFT_MAX_CAP = 256, 65536     # tail labels / seg_cap of lgs_instance_shift
 LGS_PASTE_MAX_SLOTS = 1024               # (scene, instance) slots per call of lgs_paste_instances
 LGS_PASTE_SLOT_COLS, LGS_PASTE_SCENE_COLS = 6, 4
 LGS_COLOR_AUTOCONTRAST, LGS_COLOR_TRANSLATION, LGS_COLOR_JITTER = 1, 2, 4     # lgs_color_scene.flags
@@ -240,6 +241,7 @@ EXPORTS = [
     "lgs_color_augment", "lgs_aug_status", "lgs_debug_philox",
     "lgs_paste_workspace_bytes", "lgs_paste_instances",
     "lgs_dropout_workspace_bytes", "lgs_dropout_select",
+    "lgs_instance_shift_workspace_bytes", "lgs_instance_shift",
 ]
 
 
@@ -349,6 +351,8 @@ def lib():
         "lgs_paste_instances": [vp, vp, vp, i64, ci, vp, vp, vp, i64, vp, vp, ci, i64, vp, vp, vp, i64, vp, ci, i64, i64, vp, vp, vp, vp,
                                 vp, vp, vp],
         "lgs_dropout_select": [vp, i64, ci, ci, ctypes.c_double, i64, ctypes.POINTER(ctypes.c_int32), vp, vp, vp, vp, vp, vp],
+        "lgs_instance_shift": [vp, vp, vp, vp, i64, vp, ci, vp, pi64, ci, ctypes.c_double, ctypes.c_double, i64, ctypes.POINTER(ctypes.c_int32),
+                               vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp],
         "lgs_comm_unique_id": [vp],
         "lgs_comm_create": [vp, ci, ci, ci, ctypes.POINTER(vp)],
         "lgs_comm_create_ipc": [ci, ci, ci, ctypes.POINTER(vp), vp],
@@ -381,6 +385,8 @@ def lib():
     L.lgs_paste_workspace_bytes.argtypes = [ci, ci, i64, i64]
     L.lgs_dropout_workspace_bytes.restype = i64
     L.lgs_dropout_workspace_bytes.argtypes = [i64, ci]
+    L.lgs_instance_shift_workspace_bytes.restype = i64
+    L.lgs_instance_shift_workspace_bytes.argtypes = [i64, ci, ci]
     L.lgs_cluster_workspace_bytes.restype = i64
     L.lgs_cluster_workspace_bytes.argtypes = [i64]
     L.lgs_conv_workspace_bytes.restype = i64

@@ -1,5 +1,5 @@
 """Per-op timings on the GPU (HIP events on torch's current stream) for the hot layer shapes.
-usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal | supcon | augment | paste | dropout | nearest | ap | lean]"""
+usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal | supcon | augment | paste | dropout | instshift | nearest | ap | lean]"""
 import os
 import re
 import sys
@@ -966,6 +966,92 @@ def dropout():
           % (n0, int(n0 * 0.8), t_cpu * 1e3, 8 * t_cpu * 1e3))
 
 
+def instshift():
+    """The per-instance colour and scale shifts on the device (csrc/lgs_instshift.hip) on the benchmark's 8-scene, 2.4 M-point batch
+    (the points `dropout` feeds its chain): the stage alone, the chain with and without it, and the host method's shape of work (one
+    boolean mask over the cloud per instance, np.delete / np.vstack) on one host core for one scene.  SYNTHETIC CHOICE: 5 % of the
+    rows lie in tail segments, 40 segments per scene (4 tail labels x 10 ids), their rows spread at random over the scene.
+    Device events around 200 back-to-back calls."""
+    from languagegroundedsemseg_amd import augment as A
+    coords, feats, labels = make_batch(list(range(8)), n_target=150000, shift_seed=0)
+    rng = np.random.default_rng(0)
+    order = np.argsort(coords[:, 0], kind="stable")
+    coords, labels = coords[order], labels[order]
+    rep = np.repeat(coords, 2, 0)
+    pts = ((rep[:, 1:].astype(np.float64) + rng.uniform(0.05, 0.95, (rep.shape[0], 3))) * 0.02).astype(np.float32)
+    off = np.concatenate([[0], np.cumsum(np.bincount(rep[:, 0], minlength=8))]).tolist()
+    for s in range(8):
+        pts[off[s]:off[s + 1]] -= pts[off[s]:off[s + 1]].min(0)
+    cols = np.floor(rng.random(pts.shape) * 256).astype(np.float32)
+    n = pts.shape[0]
+    tail = [1001, 1002, 1003, 1004]                                   # ids no synthetic label uses
+    lab = np.repeat(labels, 2).astype(np.int64)
+    in_tail = rng.random(n) < 0.05
+    lab[in_tail] = rng.choice(tail, int(in_tail.sum()))
+    ids = rng.integers(0, 10, n).astype(np.int64)
+    print("%d points in 8 scenes; synthetic: %.1f %% of the rows in tail segments, 40 segments per scene, rows at random"
+          % (n, 100.0 * in_tail.mean()))
+    p, c, l, i = (torch.from_numpy(a).to(DEV) for a in (pts, cols, lab, ids))
+    off_dev = torch.from_numpy(np.asarray(off, np.int64)).to(DEV)
+    seeds = list(range(1, 9))
+
+    def show(name, ms):
+        print("%-64s %8.3f ms per batch" % (name, ms))
+    bounds, _ = A.aug_bounds(p, off_dev)
+    out = A.instance_shifts(p, c, l, i, off_dev, tail, 0.5, 0.2, seed=7, scene_seeds=seeds, scene_bounds=bounds)
+    assert A.instance_shift_status(out[5]) == {"unshifted": [], "id_range": []} and int((out[2][:, 1] > 0).sum()) > 0
+    show("instance_shifts alone, bounds given (5 launches + the sort)",
+         timeit(lambda: A.instance_shifts(p, c, l, i, off_dev, tail, 0.5, 0.2, seed=7, scene_seeds=seeds, scene_bounds=bounds), iters=200, warm=5))
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            for _ in range(10):
+                A.instance_shifts(p, c, l, i, off_dev, tail, 0.5, 0.2, seed=7, scene_seeds=seeds, scene_bounds=bounds)
+            torch.cuda.synchronize()
+        for ev in sorted(prof.key_averages(), key=lambda e: e.key):
+            us = getattr(ev, "device_time_total", None) or getattr(ev, "cuda_time_total", 0.0)
+            m = re.search(r"k_is_[a-z_]+", ev.key)
+            if not m and "rocprim" not in ev.key:
+                continue
+            name = m.group(0) if m else "rocPRIM " + (re.search(r"(onesweep|block_sort|merge|histogram|scan)\w*", ev.key) or re.search("sort", "sort")).group(0)
+            print("  %-62s %8.1f us per call (%d launches)" % (name, us / 10.0, ev.count // 10))
+    except Exception as e:      # the profiler is a convenience: the call's own time above stands without it
+        print("  (no per-kernel times: %s)" % e)
+    kw = dict(voxel_size=0.02, rotation_bound=((-np.pi / 64, np.pi / 64), (-np.pi / 64, np.pi / 64), (-np.pi, np.pi)), scale_bound=(0.9, 1.1),
+              normalize_color=True, seed=1)
+    plain, shifted = A.DeviceAugmentation(**kw), A.DeviceAugmentation(instance_shifts=A.InstanceShifts(tail), **kw)
+    plan = plain.draw(8)
+    plan.elastic[:], plan.autocontrast[:], plan.translate[:], plan.jitter[:] = True, True, True, True
+    plan.flip_axes[:] = 3
+    t_plain = timeit(lambda: plain(p, c, l, off, plan=plan), iters=200, warm=5)
+    t_shift = timeit(lambda: shifted(p, c, l, off, plan=plan, instances=i), iters=200, warm=5)
+    show("chain without the stage (%d points)" % n, t_plain)
+    show("chain with instance_shifts (and instances=)", t_shift)
+    print("%-64s %+8.3f ms" % ("  difference (the stage, the instances' gather)", t_shift - t_plain))
+    # the host method's shape of work on one core, one scene: a mask over the cloud per instance, then np.delete / np.vstack
+    torch.set_num_threads(1)
+    a, b = off[0], off[1]
+    hp, hc, hl, hi = pts[a:b], cols[a:b], lab[a:b], ids[a:b]
+    t0 = time.perf_counter()
+    for _ in range(3):
+        moved_p, moved_c, gone = [], [], []
+        idx = np.arange(b - a)
+        for cat in np.unique(hl):
+            if cat not in tail:
+                continue
+            cat_rows = hl == cat
+            for inst in np.unique(hi[cat_rows]):
+                rows = cat_rows * (hi == inst)
+                moved_p.append(hp[rows] * np.float32(0.9))
+                moved_c.append((hc[rows] * 0.5).astype(int))
+                gone.append(idx[rows])
+        gone = np.concatenate(gone)
+        np.vstack([np.delete(hp, gone, axis=0)] + moved_p), np.vstack([np.delete(hc, gone, axis=0)] + moved_c)
+    t_cpu = (time.perf_counter() - t0) / 3
+    print("host method (numpy: one mask per instance, np.delete / np.vstack), %d points, 1 host thread: %.1f ms per scene (x 8 scenes = %.0f ms per batch)"
+          % (b - a, t_cpu * 1e3, 8 * t_cpu * 1e3))
+
+
 def nearest():
     """lgs_manager_nearest at the evaluation shape -- 8 scenes x ~150 k voxels, three points inside every occupied cell -- at
     NEAREST_MAX_RING 1, 2 and 4, anchors 0.0 and 0.5, with both lookup tables, and the share of queries that the ring search leaves to
@@ -1227,6 +1313,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "dropout":
         dropout()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "instshift":
+        instshift()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "paste":
         paste()
