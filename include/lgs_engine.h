@@ -1122,6 +1122,41 @@ int lgs_instance_shift(const float *points, const float *colors, const int64_t *
                        void *workspace, float *points_out, float *colors_out, int64_t *labels_out, int64_t *instances_out,
                        int64_t *order, int32_t *status, void *stream);
 
+/* ---- furthest point sampling over segments: the limited-annotation subsets (csrc/lgs_fps.hip) ----
+ * replaces: furthest_point_sample (lib/ext/pointnet2/_ext_src/src/sampling_gpu.cu:75-178) as lib/datasets/preprocessing/
+ *   scannet_long.py:98-109 calls it, once per annotated instance of a scene with max(5, round(ratio * n)) samples.
+ * NEW SYMBOLS ONLY: LGS_ABI_VERSION stays 18; a library that lacks them lacks the capability.
+ * points DEVICE float32 [n, 3], 0 <= n < 2^31 - 1.  Segment q of 0 <= s <= 2^20 owns the positions [seg_offsets[q], seg_offsets[q + 1])
+ * of a sequence of length n (seg_offsets DEVICE int64 [s + 1]; entries are clamped into a non-decreasing table on [0, n]); position u
+ * is row through[u] of points (through DEVICE int64 [n]; a value outside [0, n) is clamped into it), row u when through is NULL.
+ *   segment    n_q points p[0 .. n_q) in position order, m_q samples.  Point k is eligible iff (x x + y y) + z z > 1e-3f (the reference's
+ *              skip of near-origin points, as written), every point if skip_origin == 0.  t[k] = 1e10f, out[0] = 0.  Round
+ *              j = 1 .. m_q - 1 with o = out[j - 1]: for every eligible k, d = ((xk - xo)^2 + (yk - yo)^2) + (zk - zo)^2 with every
+ *              operation rounded to fp32 in this order and no contraction, t[k] = min(d, t[k]); out[j] = the eligible k with the
+ *              largest t[k], the smallest such k on a tie, 0 if no point is eligible.  m_q > n_q is legal and repeats points.
+ *              Non-finite coordinates: the selection is unspecified, nothing is read or written out of bounds, the call ends.
+ *   count      m_q = counts[q] (DEVICE int32 [s], negative = 0) when counts is not NULL; else fixed_count when >= 0; else the recipe's
+ *              rule on the device, max(min_points, (int)rint(ratio * n_q)) in IEEE double with round-half-even (Python's
+ *              round(ratio * n)), 0 <= ratio <= 1.  n_q == 0 forces m_q = 0; m_q is capped at LGS_FPS_MAX_SAMPLES.
+ *   output     either or both.  idx_out DEVICE int32: out[0 .. m_q) of segment q, LOCAL to the segment, at out_offsets[q] (DEVICE
+ *              int64 [s]), or at q * fixed_count when out_offsets is NULL (a fixed count only).  rank_out DEVICE int32 [n], per ROW:
+ *              the first round that chose the row, -1 for every other row of the table; all n entries are written (a row that
+ *              several segments share takes the smallest round).
+ * Deviation: the reference resolves an exact tie in a round's maximum by its block-strided reduction tree, so its choice depends on
+ * its block size; here a tie goes to the smallest index.  The two agree on every input without an exact tie and after exhaustion.
+ * How: one wave (n_q <= LGS_FPS_WAVE_MAX) or one workgroup per segment; the state in registers up to LGS_FPS_GROUP16_MAX points, in
+ * the workspace beyond; per round one wave maximum of a 64-bit key (t's bits, ~k) and at most one barrier.  The result does not
+ * depend on tier, grid or workgroup size, two calls give the same bits, nothing is read back.  workspace:
+ * lgs_fps_workspace_bytes(n, s) bytes (0 = bad shape); the call initialises what it reads of it. */
+#define LGS_FPS_WAVE_MAX 256
+#define LGS_FPS_GROUP4_MAX 2048
+#define LGS_FPS_GROUP16_MAX 8192
+#define LGS_FPS_MAX_SAMPLES (1 << 24)
+int64_t lgs_fps_workspace_bytes(int64_t n, int64_t s);
+int lgs_fps_segments(const float *points, int64_t n, const int64_t *through, const int64_t *seg_offsets, int64_t s,
+                     const int32_t *counts, int fixed_count, double ratio, int min_points, int skip_origin,
+                     const int64_t *out_offsets, int32_t *idx_out, int32_t *rank_out, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

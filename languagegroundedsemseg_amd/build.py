@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "_lib")
 LIB_PATH = os.path.join(LIB_DIR, "liblgs_engine.so")
-SOURCES = ["lgs_manager.hip", "lgs_conv.hip", "lgs_conv_wide.hip", "lgs_pointwise.hip", "lgs_wgrad.hip", "lgs_wgrad_wide.hip", "lgs_norm.hip", "lgs_loss.hip", "lgs_voxel.hip", "lgs_cluster.hip", "lgs_tuning.hip", "lgs_block.hip", "lgs_comm.hip", "lgs_pool.hip", "lgs_instnorm.hip", "lgs_metrics.hip", "lgs_ap.hip", "lgs_insteval.hip", "lgs_insttarget.hip", "lgs_supcon.hip", "lgs_augment.hip", "lgs_paste.hip", "lgs_dropout.hip", "lgs_instshift.hip"]
+SOURCES = ["lgs_manager.hip", "lgs_conv.hip", "lgs_conv_wide.hip", "lgs_pointwise.hip", "lgs_wgrad.hip", "lgs_wgrad_wide.hip", "lgs_norm.hip", "lgs_loss.hip", "lgs_voxel.hip", "lgs_cluster.hip", "lgs_tuning.hip", "lgs_block.hip", "lgs_comm.hip", "lgs_pool.hip", "lgs_instnorm.hip", "lgs_metrics.hip", "lgs_ap.hip", "lgs_insteval.hip", "lgs_insttarget.hip", "lgs_supcon.hip", "lgs_augment.hip", "lgs_paste.hip", "lgs_dropout.hip", "lgs_instshift.hip", "lgs_fps.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "lgs_engine.h")]   # every header there is
 
 

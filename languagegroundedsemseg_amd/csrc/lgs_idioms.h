@@ -159,6 +159,16 @@ inline InstShiftWs inst_shift_layout(int64_t n, int seg_cap, int64_t tmp_bytes) 
           l.take((int64_t)kInstShiftSegBytes * seg_cap), l.take(256), l.take(v), l.take(v), l.take(v), l.take(v), l.total()};
 }
 
+// lgs_fps.hip: one record per segment, and one (x, y, z, t) record per position for the segments that keep their state in memory
+constexpr int kFpsSegBytes = 24;         // sizeof(FpsSeg)
+constexpr int64_t kFpsMaxRows = (1ll << 31) - 2;
+constexpr int64_t kFpsMaxSegments = 1ll << 20;
+struct FpsWs { int64_t segs, state, total; };
+inline FpsWs fps_layout(int64_t n, int64_t s) {
+  Layout l;
+  return {l.take((int64_t)kFpsSegBytes * (s + 1)), l.take(16 * (n + 1)), l.total()};
+}
+
 // ---- 2. pure functions ----------------------------------------------------------------------------------------------------------
 // Binary searches over p[lo, hi), non-decreasing.  I is the index type of the caller (int or int64_t).
 // the first index whose element is not below k (hi if there is none)

@@ -242,6 +242,7 @@ EXPORTS = [
     "lgs_paste_workspace_bytes", "lgs_paste_instances",
     "lgs_dropout_workspace_bytes", "lgs_dropout_select",
     "lgs_instance_shift_workspace_bytes", "lgs_instance_shift",
+    "lgs_fps_workspace_bytes", "lgs_fps_segments",
 ]
 
 
@@ -353,6 +354,7 @@ def lib():
         "lgs_dropout_select": [vp, i64, ci, ci, ctypes.c_double, i64, ctypes.POINTER(ctypes.c_int32), vp, vp, vp, vp, vp, vp],
         "lgs_instance_shift": [vp, vp, vp, vp, i64, vp, ci, vp, pi64, ci, ctypes.c_double, ctypes.c_double, i64, ctypes.POINTER(ctypes.c_int32),
                                vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp],
+        "lgs_fps_segments": [vp, i64, vp, vp, i64, vp, ci, ctypes.c_double, ci, ci, vp, vp, vp, vp, vp],
         "lgs_comm_unique_id": [vp],
         "lgs_comm_create": [vp, ci, ci, ci, ctypes.POINTER(vp)],
         "lgs_comm_create_ipc": [ci, ci, ci, ctypes.POINTER(vp), vp],
@@ -387,6 +389,8 @@ def lib():
     L.lgs_dropout_workspace_bytes.argtypes = [i64, ci]
     L.lgs_instance_shift_workspace_bytes.restype = i64
     L.lgs_instance_shift_workspace_bytes.argtypes = [i64, ci, ci]
+    L.lgs_fps_workspace_bytes.restype = i64
+    L.lgs_fps_workspace_bytes.argtypes = [i64, i64]
     L.lgs_cluster_workspace_bytes.restype = i64
     L.lgs_cluster_workspace_bytes.argtypes = [i64]
     L.lgs_conv_workspace_bytes.restype = i64

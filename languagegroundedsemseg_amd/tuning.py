@@ -47,6 +47,9 @@ HOST_KNOBS = {
     "INST_TARGETS_FUSED": (1, int, "0 = losses.fused_instance_offset_losses takes the torch lines of instance_offset_losses on the per-point "
                                    "centres (what CPU tensors always take) instead of lgs_offset_loss_forward / lgs_offset_loss_backward; read at "
                                    "every call (same losses within fp32 rounding: tests/test_gpu_insttarget.py)"),
+    "FPS_FUSED": (1, int, "0 = annotation.furthest_point_sample, furthest_point_sample_segments and limited_annotation take the torch lines "
+                          "of the same contract (what CPU tensors always take; one read-back per round) instead of lgs_fps_segments; "
+                          "read at every call (same picks: tests/test_gpu_fps.py)"),
     "SET_HW_QUEUES": (0, int, "1 = importing the package sets GPU_MAX_HW_QUEUES=8 before the HIP runtime starts (see configure_hw_queues)"),
 }
 

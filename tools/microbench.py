@@ -1,5 +1,5 @@
 """Per-op timings on the GPU (HIP events on torch's current stream) for the hot layer shapes.
-usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal | supcon | augment | paste | dropout | instshift | nearest | ap | lean]"""
+usage: python tools/microbench.py [scenes | wide | wgrad | coarse | cluster | insseg | quantize | clip | pool | instnorm | strided | metrics | focal | supcon | augment | paste | dropout | instshift | fps | nearest | ap | lean]"""
 import os
 import re
 import sys
@@ -966,6 +966,110 @@ def dropout():
           % (n0, int(n0 * 0.8), t_cpu * 1e3, 8 * t_cpu * 1e3))
 
 
+def fps():
+    """Furthest point sampling on the device (csrc/lgs_fps.hip) on the benchmark's 8-scene, 1.2 M-point batch, ratio 0.05: the whole
+    limited_annotation call, lgs_fps_segments alone, the largest segment alone (its rounds are the critical path), the time of a round
+    in every tier and on both sides of every tier bound, the torch lines of the same rounds on the same device, and the numpy
+    restatement on one host core, both for one scene.  SYNTHETIC CHOICE: per scene the lowest 10 cm are the floor, the outer 10 cm in
+    x and y are two walls, the rest belongs to the nearest of 40 random centres in the plan (one instance each); 10 % of the rows have
+    no instance.  Device events around back-to-back calls."""
+    from languagegroundedsemseg_amd import annotation as AN, instances as IN
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import fps_reference as fr
+    coords, feats, labels = make_batch(list(range(8)), n_target=150000, shift_seed=0)
+    rng = np.random.default_rng(0)
+    order = np.argsort(coords[:, 0], kind="stable")
+    coords, labels = coords[order], labels[order].astype(np.int64)
+    sizes = np.bincount(coords[:, 0], minlength=8)
+    off_h = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    n = int(off_h[-1])
+    pts = ((coords[:, 1:].astype(np.float64) + rng.uniform(0.05, 0.95, (n, 3))) * 0.02).astype(np.float32)
+    ids = np.empty(n, dtype=np.int64)
+    for s in range(8):
+        q = pts[off_h[s]:off_h[s + 1]]
+        lo, hi = q.min(0), q.max(0)
+        centres = rng.uniform(lo[:2], hi[:2], (40, 2))
+        i = 3 + np.argmin(((q[:, None, :2] - centres[None]) ** 2).sum(-1), axis=1)
+        i[(q[:, 0] < lo[0] + 0.1) | (q[:, 0] > hi[0] - 0.1)] = 1
+        i[(q[:, 1] < lo[1] + 0.1) | (q[:, 1] > hi[1] - 0.1)] = 2
+        i[q[:, 2] < lo[2] + 0.1] = 0
+        i[rng.random(len(q)) < 0.1] = -1
+        ids[off_h[s]:off_h[s + 1]] = i
+    seg_sizes = np.sort(np.concatenate([np.bincount(ids[off_h[s]:off_h[s + 1]][ids[off_h[s]:off_h[s + 1]] >= 0]) for s in range(8)]))
+    seg_sizes = seg_sizes[seg_sizes > 0]
+    b1, b2, b3 = AN.TIER_BOUNDS
+    print("%d points in 8 scenes, %d instances of %d .. %d points (median %d); per tier: %d wave, %d group<4>, %d group<16>, %d stream; "
+          "ratio 0.05: %d samples in all, %d in the largest" % (
+              n, len(seg_sizes), seg_sizes[0], seg_sizes[-1], int(np.median(seg_sizes)), (seg_sizes <= b1).sum(),
+              ((seg_sizes > b1) & (seg_sizes <= b2)).sum(), ((seg_sizes > b2) & (seg_sizes <= b3)).sum(), (seg_sizes > b3).sum(),
+              sum(fr.count_rule(int(v), 0.05) for v in seg_sizes), fr.count_rule(int(seg_sizes[-1]), 0.05)))
+    p, i_dev, l_dev, off_dev = (torch.from_numpy(a).to(DEV) for a in (pts, ids, labels, off_h))
+
+    def show(name, ms):
+        print("%-72s %9.3f ms" % (name, ms))
+    out = AN.limited_annotation(p, i_dev, l_dev, off_dev, 0.05)
+    assert 0 < int(out[1].sum()) <= sum(min(int(v), fr.count_rule(int(v), 0.05)) for v in seg_sizes)
+    show("limited_annotation, the batch (instance table, sort, scan, lgs_fps_segments)",
+         timeit(lambda: AN.limited_annotation(p, i_dev, l_dev, off_dev, 0.05), iters=5, warm=1))
+    # the engine call alone on the same segments
+    c4 = torch.zeros((n, 4), dtype=torch.int32, device=DEV)
+    c4[:, 0] = torch.from_numpy(coords[:, 0].astype(np.int32)).to(DEV)
+    info = IN.instance_info(c4, i_dev, return_centers=False)
+    cap = info.count.shape[0]
+    through = torch.sort(torch.where(info.slot >= 0, info.slot, torch.full_like(info.slot, cap)), stable=True)[1]
+    seg_off = torch.zeros(cap + 1, dtype=torch.int64, device=DEV)
+    seg_off[1:] = torch.cumsum(info.count, 0, dtype=torch.int64)
+    rank = torch.empty(n, dtype=torch.int32, device=DEV)
+    show("lgs_fps_segments alone, %d segment slots (6 launches, nothing read back)" % cap,
+         timeit(lambda: AN._fps_call(p, through, seg_off, ratio=0.05, rank_out=rank), iters=5, warm=1))
+    # the largest segment alone
+    big = int(np.argmax(info.count.cpu().numpy()))
+    lo, hi = int(seg_off[big]), int(seg_off[big + 1])
+    pb = p[through[lo:hi]].contiguous()[None]
+    mb = fr.count_rule(hi - lo, 0.05)
+    tb = timeit(lambda: AN.furthest_point_sample(pb, mb), iters=5, warm=1)
+    show("the largest segment alone (%d points, %d samples)" % (hi - lo, mb), tb)
+    print("%-72s %9.3f us" % ("  per round", tb * 1e3 / (mb - 1)))
+    # a round in every tier: one segment, 1001 samples; 64 equal segments in one call for the throughput side
+    print("one round, us (one segment alone | 64 segments in one call, per segment):")
+    cloud = torch.from_numpy(rng.uniform(-3, 3, (64 * 100000, 3)).astype(np.float32)).to(DEV)
+    for size in (64, b1, b1 + 1, 1024, b2, b2 + 1, 4096, b3, b3 + 1, 20000, 100000):
+        tier = "k_fps_wave" if size <= b1 else "k_fps_group<4>" if size <= b2 else "k_fps_group<16>" if size <= b3 else "k_fps_stream"
+        one = cloud[:size][None]
+        many = cloud[:64 * size].view(64, size, 3)
+        t1 = timeit(lambda: AN.furthest_point_sample(one, 1001), iters=3, warm=1)
+        t64 = timeit(lambda: AN.furthest_point_sample(many, 1001), iters=3, warm=1)
+        print("  n = %6d  %-16s %9.3f | %9.3f" % (size, tier, t1, t64 / 64))
+    # one scene: the torch lines of the same rounds on the device, the numpy restatement on one host core
+    ids0, p0 = ids[:off_h[1]], pts[:off_h[1]]
+    groups = [np.nonzero(ids0 == v)[0] for v in np.unique(ids0[ids0 >= 0])]
+    rounds = sum(fr.count_rule(len(g), 0.05) - 1 for g in groups)
+    dev_groups = [p[torch.from_numpy(g).to(DEV)].contiguous() for g in groups]
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for g in dev_groups:
+        AN.fps_torch(g, fr.count_rule(g.shape[0], 0.05))
+    torch.cuda.synchronize()
+    t_torch = time.perf_counter() - t0
+    off0 = torch.from_numpy(np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int64)).to(DEV)
+    p0g = torch.cat(dev_groups)
+    rank0 = torch.empty(p0g.shape[0], dtype=torch.int32, device=DEV)
+    t_dev = timeit(lambda: AN._fps_call(p0g, None, off0, ratio=0.05, rank_out=rank0), iters=5, warm=1)
+    print("scene 0 (%d instances, %d rounds in all): lgs_fps_segments %.3f ms; torch lines per segment on the device %.1f ms (%.1f us per "
+          "round)" % (len(groups), rounds, t_dev, t_torch * 1e3, t_torch * 1e6 / rounds))
+    torch.set_num_threads(1)
+    t0 = time.perf_counter()
+    want = [fr.fps_contract(p0[g], fr.count_rule(len(g), 0.05)) for g in groups]
+    t_cpu = time.perf_counter() - t0
+    got = rank0.cpu().numpy()
+    start = 0
+    for g, w in zip(groups, want):
+        assert np.array_equal(np.argsort(np.where(got[start:start + len(g)] < 0, 1 << 30, got[start:start + len(g)]),
+                                         kind="stable")[:len(np.unique(w))], w[:len(np.unique(w))])
+        start += len(g)
+    print("numpy restatement, scene 0, 1 host thread: %.0f ms (x 8 scenes = %.1f s per batch)" % (t_cpu * 1e3, 8 * t_cpu))
+
+
 def instshift():
     """The per-instance colour and scale shifts on the device (csrc/lgs_instshift.hip) on the benchmark's 8-scene, 2.4 M-point batch
     (the points `dropout` feeds its chain): the stage alone, the chain with and without it, and the host method's shape of work (one
@@ -1316,6 +1420,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "instshift":
         instshift()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "fps":
+        fps()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "paste":
         paste()
